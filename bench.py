@@ -12,7 +12,10 @@ the barrier and the max-over-ranks time.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for how every field is derived).
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for how every field is derived).  A plain run only sets up, warms
+up, times the steps and reports them; `--full` adds what takes runs of its own: the finite check, the roofline leg (eager
+per-launch profile), the f32 device engine and the CPU oracle on slice 0 (`cpu_baseline`, `fidelity`).
+`--dump-outputs DIR` writes the final latents of the last timed step (rank 0's batch) to DIR/latents.npy (float32).
 """
 import argparse
 import ctypes as C
@@ -121,6 +124,60 @@ def cpu_baseline(state_dict_cpu, cfg_oracle, threads, x_T, ctx, n_steps):
             "sample_steps_per_s": B * n_steps / dt}, traj[-1]
 
 
+def roofline_leg(unet, sched, lat, x_T, ctx, args):
+    """--full: the same workload, eager launches, a HIP event pair around EVERY kernel launch on the launch stream
+    (libmrisr's own profiler), aggregated per kernel class; two denoising steps.  Overwrites `lat`."""
+    import mrisr
+    from mrisr import _lib as L
+    lib = L.lib()
+    lib.mrisr_prof_reset()
+    lib.mrisr_prof_enable(1)
+    sampler2 = mrisr.Sampler(unet, sched, kind="ddim")
+    sampler2.set_range(0, 2)
+    lat.copy_(x_T)
+    sampler2.run(lat, ctx, use_graph=False)
+    torch.cuda.synchronize()
+    lib.mrisr_prof_enable(0)
+    classes = prof_report(lib)
+    lib.mrisr_prof_reset()
+    log("roofline leg done")
+    total_ms = sum(v["ms"] for v in classes.values()) or 1.0
+    gemm = {k: v for k, v in classes.items() if k.startswith("gemm_")}
+    dom_name = max(gemm, key=lambda k: gemm[k]["ms"]) if gemm else None
+    roof = None
+    if dom_name:
+        d = gemm[dom_name]
+        per_launch_ms = d["ms"] / d["launches"]
+        achieved = d["flops"] / d["launches"] / (per_launch_ms * 1e-3) / 1e12
+        all_fl = sum(v["flops"] for v in gemm.values())
+        all_ms = sum(v["ms"] for v in gemm.values())
+        roof = {"bound": "mfma", "kernel": dom_name, "achieved": achieved, "peak": PEAK_BF16_TFLOPS if args.dtype == "bf16" else 157.3,
+                "unit": "TFLOP/s", "frac": achieved / (PEAK_BF16_TFLOPS if args.dtype == "bf16" else 157.3), "traffic": None,
+                "launches": d["launches"], "avg_launch_us": per_launch_ms * 1e3,
+                "alg_gflop_per_launch": d["flops"] / d["launches"] / 1e9,
+                "share_of_step_time": d["ms"] / total_ms,
+                "all_gemm": {"achieved": all_fl / (all_ms * 1e-3) / 1e12, "share_of_step_time": all_ms / total_ms,
+                             "alg_gflop_per_unet_step": all_fl / 2 / 1e9},
+                "classes_ms_per_step": {k: round(v["ms"] / 2, 4) for k, v in sorted(classes.items(), key=lambda kv: -kv[1]["ms"])}}
+        try:  # HBM bytes per launch of the dominant kernel, from the committed PMC collection of this same command
+            tj = json.load(open(args.traffic_json))
+            if dom_name in tj:
+                roof["traffic"] = tj[dom_name]["hbm_bytes_per_launch"]
+                roof["traffic_source"] = (f"{os.path.relpath(args.traffic_json, ROOT)}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                          "command (tools/collect_traffic.sh), NOT collected in this run")
+                roof["alg_bytes_per_launch"] = d["bytes"] / d["launches"]
+        except (OSError, ValueError):
+            pass
+    return roof
+
+
+def dump_outputs(d, lat):
+    """--dump-outputs: what a caller of the timed path receives - the final latents of the last timed step - as float32."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "latents.npy"), lat.detach().float().cpu().numpy())
+
+
 def self_launch(n, argv):
     """`python bench.py --gpus N` without a launcher (WORLD_SIZE unset): this process has made NO GPU call (importing torch
     does not initialise HIP), so it may start N fresh children - one per GPU, the same environment torchrun would give them
@@ -174,7 +231,11 @@ def main():
     ap.add_argument("--batch", type=int, default=B_PER_GPU, help="slices per GPU (BASELINE config: 32)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the f32 engine / CPU oracle legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the finite check, the roofline leg and the f32 / CPU oracle legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final latents of the last timed step to DIR/latents.npy (float32)")
     ap.add_argument("--lora-merged", action="store_true", help="merge LoRA into W instead of the fused rank tail")
     ap.add_argument("--ddim-steps", type=int, default=N_DDIM, help="(profiling only) fewer denoising steps; the metric needs 50")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "r03_traffic.json"),
@@ -200,7 +261,6 @@ def main():
         dist.init_process_group("nccl", rank=rank, world_size=world)  # RCCL; barrier + max-reduce of the time only
 
     import mrisr
-    from mrisr import _lib as L
     from mrisr import params as P
 
     log("init weights on device")
@@ -248,56 +308,14 @@ def main():
     log(f"timed region done: {elapsed:.3f} s for {args.steps} batches")
     from mrisr import dist as mdist
     elapsed = mdist.max_over_ranks(elapsed, dev)  # slowest rank's wall time
-    finite = bool(torch.isfinite(lat).all())
-    final_slice0 = lat[:1].detach().float().cpu()  # the timed runs' result for slice 0 (the roofline leg below reuses `lat`)
 
     if rank != 0:
         if dist is not None:
             dist.barrier()
             dist.destroy_process_group()
         return
-
-    # ---- roofline leg: the same workload, eager launches, a HIP event pair around EVERY kernel launch on the launch
-    # stream (libmrisr's own profiler), aggregated per kernel class; two denoising steps.
-    lib = L.lib()
-    lib.mrisr_prof_reset()
-    lib.mrisr_prof_enable(1)
-    sampler2 = mrisr.Sampler(unet, sched, kind="ddim")
-    sampler2.set_range(0, 2)
-    lat.copy_(x_T)
-    sampler2.run(lat, ctx, use_graph=False)
-    torch.cuda.synchronize()
-    lib.mrisr_prof_enable(0)
-    classes = prof_report(lib)
-    lib.mrisr_prof_reset()
-    log("roofline leg done")
-    total_ms = sum(v["ms"] for v in classes.values()) or 1.0
-    gemm = {k: v for k, v in classes.items() if k.startswith("gemm_")}
-    dom_name = max(gemm, key=lambda k: gemm[k]["ms"]) if gemm else None
-    roof = None
-    if dom_name:
-        d = gemm[dom_name]
-        per_launch_ms = d["ms"] / d["launches"]
-        achieved = d["flops"] / d["launches"] / (per_launch_ms * 1e-3) / 1e12
-        all_fl = sum(v["flops"] for v in gemm.values())
-        all_ms = sum(v["ms"] for v in gemm.values())
-        roof = {"bound": "mfma", "kernel": dom_name, "achieved": achieved, "peak": PEAK_BF16_TFLOPS if args.dtype == "bf16" else 157.3,
-                "unit": "TFLOP/s", "frac": achieved / (PEAK_BF16_TFLOPS if args.dtype == "bf16" else 157.3), "traffic": None,
-                "launches": d["launches"], "avg_launch_us": per_launch_ms * 1e3,
-                "alg_gflop_per_launch": d["flops"] / d["launches"] / 1e9,
-                "share_of_step_time": d["ms"] / total_ms,
-                "all_gemm": {"achieved": all_fl / (all_ms * 1e-3) / 1e12, "share_of_step_time": all_ms / total_ms,
-                             "alg_gflop_per_unet_step": all_fl / 2 / 1e9},
-                "classes_ms_per_step": {k: round(v["ms"] / 2, 4) for k, v in sorted(classes.items(), key=lambda kv: -kv[1]["ms"])}}
-        try:  # HBM bytes per launch of the dominant kernel, from the committed PMC collection of this same command
-            tj = json.load(open(args.traffic_json))
-            if dom_name in tj:
-                roof["traffic"] = tj[dom_name]["hbm_bytes_per_launch"]
-                roof["traffic_source"] = (f"{os.path.relpath(args.traffic_json, ROOT)}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                          "command (tools/collect_traffic.sh), NOT collected in this run")
-                roof["alg_bytes_per_launch"] = d["bytes"] / d["launches"]
-        except (OSError, ValueError):
-            pass
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lat)
 
     total_slices = world * B * args.steps
     value = total_slices / elapsed
@@ -318,10 +336,12 @@ def main():
         "denoise_step_ms": step_ms,
         "unet_tflops_end_to_end": UNET_GFLOP_PER_SAMPLE * B / step_ms,
         "frac_of_bf16_peak_end_to_end": UNET_GFLOP_PER_SAMPLE * B / step_ms / PEAK_BF16_TFLOPS,
-        "finite": finite,
-        "roofline": roof,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        out["finite"] = bool(torch.isfinite(lat).all())
+        final_slice0 = lat[:1].detach().float().cpu()  # the timed runs' result for slice 0 (the roofline leg reuses `lat`)
+        out["roofline"] = roofline_leg(unet, sched, lat, x_T, ctx, args)
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import unet as ou
         threads = host_threads()
         # ---- the metric's second half ("PSNR vs ref"): slice 0 of this batch through the CPU oracle for all the DDIM steps,

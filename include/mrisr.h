@@ -270,6 +270,55 @@ int mrisr_optim_adamw(float* p_dev, const float* g_dev, float* m_dev, float* v_d
                       float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
                       int step, void* stream);
 
+/* ---- fine-tuning loop on the device (mrisr.fit; notebook ResDif c11:14-41) -------------------------------------------------
+ * One optimiser step = `accum` launches of mrisr_fit_micro (graph M) + one mrisr_fit_apply (graph O); with world > 1 the caller
+ * all-reduces the bound grad vector between them.  Both graphs read the optimiser step s and micro-batch k from a device counter.
+ *   micro      - batch builder -> mrisr_train_step (adds into grad) -> loss accumulated, k + 1.  Re-captured whenever the UNet's
+ *                workspace was re-planned (a validation forward, another geometry) - planning itself never runs inside a capture.
+ *   apply      - sumsq -> AdamW with lr / bias correction from the step's table row, grad_scale = 1 / (world * accum) -> adapter
+ *                re-pack -> EMA with the step's decay (use_ema) -> rings[s] = {mean loss of the micro-batches, grad norm, lr} ->
+ *                s + 1, k = 0 -> grad = 0
+ *   make_batch - the batch builder alone for a given (s, k), eagerly, into caller buffers: sample / target [batch][C][h][w] f32,
+ *                timesteps [batch] int64, ehs [batch][ctx_len][ctx_dim] f32; optional: eps_hr / eps_lr (the posterior-sampling noise,
+ *                latent-shaped) and caption_row [batch] int32
+ *   set_step   - counter <- {step, 0} (resume)
+ * Batch builder, for sample b of micro-batch k of step s: item = index_table[(s * accum + k) * batch + b];
+ *   z_hr = (mean_hr + std_hr * e_hr) * scaling_factor, z_lr likewise; t uniform on [0, num_train_timesteps); eps ~ N(0, 1);
+ *   sample = sqrt(abar_t) z_hr + (1 - sqrt(abar_t)) z_lr + sqrt(1 - abar_t) eps, target = eps;
+ *   ehs[b] = captions[caption_of_item[item]], or captions[empty_row] with probability proportion_empty.
+ * Every random number is Philox4x32-10 keyed by (seed, s, k, sample_base + b, element, stream): the same (seed, s, k) gives the same
+ * batch bit for bit, eager or captured, before or after a resume.
+ * moments_dev: f32 [n_items][4][latent_channels * h * w] = {HR mean, HR std, LR mean, LR std}; captions_dev: f32
+ * [n_captions][ctx_len][ctx_dim] (both caller-owned, alive as long as the handle).  Host tables, copied: caption_of_item [n_items],
+ * index_table [max_steps * accum * batch], alphas_cumprod [num_train_timesteps], lr_table / ema_decay_table [max_steps] (value of
+ * optimiser step s, s from 0).  The UNet must carry bound adapters (mrisr_train_bind); exp_avg / exp_avg_sq / ema are flat vectors of
+ * its trainable length, the rings f32 [max_steps]. */
+typedef struct mrisr_fit mrisr_fit;
+typedef struct {
+    int32_t batch, accum, max_steps, world;
+    int32_t sample_base;            /* global index of this rank's first sample (rank * batch): keys the RNG */
+    int32_t n_items, latent_channels, latent_h, latent_w;
+    int32_t n_captions, ctx_len, ctx_dim;
+    int32_t empty_row;              /* caption row of the empty prompt, -1: none */
+    int32_t num_train_timesteps;
+    int32_t use_ema;
+    float proportion_empty, scaling_factor;
+    float beta1, beta2, eps, weight_decay, max_grad_norm;
+    uint64_t seed;
+} mrisr_fit_config;
+int mrisr_fit_create(mrisr_model* unet, const mrisr_fit_config* cfg, const float* moments_dev, const float* captions_dev,
+                     const int32_t* caption_of_item, const int32_t* index_table, const float* alphas_cumprod, const float* lr_table,
+                     const float* ema_decay_table, float* exp_avg_dev, float* exp_avg_sq_dev, float* ema_dev, float* loss_ring_dev,
+                     float* grad_norm_ring_dev, float* lr_ring_dev, mrisr_fit** out);
+void mrisr_fit_destroy(mrisr_fit* f);
+int mrisr_fit_set_step(mrisr_fit* f, int step, void* stream);
+int mrisr_fit_get_step(const mrisr_fit* f);
+int mrisr_fit_num_captures(const mrisr_fit* f);  /* graphs captured so far (M and O together) */
+int mrisr_fit_micro(mrisr_fit* f, void* stream);
+int mrisr_fit_apply(mrisr_fit* f, void* stream);
+int mrisr_fit_make_batch(mrisr_fit* f, int step, int micro, float* sample_dev, int64_t* timesteps_dev, float* ehs_dev, float* target_dev,
+                         float* eps_hr_dev, float* eps_lr_dev, int32_t* caption_row_dev, void* stream);
+
 /* ---- image metrics of the reference's evaluator (src/eval/eval.py:15-51) --------------------------------------
  * pred / gt: f32 [batch][height][width] in [0, 1] (the reference divides its 8-bit PNGs by 255).  out: f32 [batch][4] =
  * {PSNR (torchmetrics, data_range 1), SSIM (torchmetrics defaults: 11x11 Gaussian sigma 1.5, k1 .01, k2 .03, mean over

@@ -997,10 +997,18 @@ int launch_sumsq(const float* g, long long n, float* out, hipStream_t st) {
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
-// sumsq: device scalar holding the (already all-reduced) sum of squared grads; clip scale = min(1, max_norm/(norm+1e-6))
+// sumsq: device scalar holding the (already all-reduced) sum of squared grads; clip scale = min(1, max_norm/(norm+1e-6)).
+// sched (optional): rows {lr, bc1, bc2} per optimiser step, row *step_ctr (clamped to n_rows - 1) replaces the scalar lr / bc1 / bc2
+// - the captured fine-tuning loop, whose one graph replays for every step (fit.hip)
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                              long long n, const float* sumsq, float grad_scale, float max_norm, float lr, float b1, float b2,
-                             float eps, float wd, float bc1, float bc2) {
+                             float eps, float wd, float bc1, float bc2, const float* sched, const int* step_ctr, int n_rows) {
+    if (sched) {
+        const int r = min(max(*step_ctr, 0), n_rows - 1);
+        lr = sched[3 * r];
+        bc1 = sched[3 * r + 1];
+        bc2 = sched[3 * r + 2];
+    }
     float clip = 1.0f;
     if (max_norm > 0.f) {
         const float norm = sqrtf(sumsq[0]) * grad_scale;
@@ -1022,7 +1030,14 @@ int launch_adamw(float* p, const float* g, float* m, float* v, long long n, cons
                  float lr, float b1, float b2, float eps, float wd, int step, hipStream_t st) {
     const float bc1 = 1.0f - powf(b1, (float)step), bc2 = 1.0f - powf(b2, (float)step);
     hipLaunchKernelGGL(adamw_kernel, dim3(bw_blocks(n)), dim3(256), 0, st, p, g, m, v, n, sumsq, grad_scale, max_norm, lr, b1, b2, eps,
-                       wd, bc1, bc2);
+                       wd, bc1, bc2, (const float*)nullptr, (const int*)nullptr, 0);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_adamw_sched(float* p, const float* g, float* m, float* v, long long n, const float* sumsq, float grad_scale, float max_norm,
+                       float b1, float b2, float eps, float wd, const float* sched, const int* step_ctr, int n_rows, hipStream_t st) {
+    hipLaunchKernelGGL(adamw_kernel, dim3(bw_blocks(n)), dim3(256), 0, st, p, g, m, v, n, sumsq, grad_scale, max_norm, 0.f, b1, b2, eps,
+                       wd, 1.f, 1.f, sched, step_ctr, n_rows);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1465,11 +1480,19 @@ int launch_pack_conv_dgrad(const float* w, void* wd, int Cout, int Cin, hipStrea
 }
 
 // exponential moving average of the trainable vector (diffusers EMAModel.step): ema = decay * ema + (1 - decay) * theta
-__global__ void ema_kernel(float* __restrict__ ema, const float* __restrict__ theta, long long n, float decay) {
+// decay_tab (optional): the decay of each optimiser step, entry *step_ctr (clamped to n_rows - 1) replaces `decay`
+__global__ void ema_kernel(float* __restrict__ ema, const float* __restrict__ theta, long long n, float decay, const float* decay_tab,
+                           const int* step_ctr, int n_rows) {
+    if (decay_tab) decay = decay_tab[min(max(*step_ctr, 0), n_rows - 1)];
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) ema[i] = decay * ema[i] + (1.f - decay) * theta[i];
 }
 int launch_ema(float* ema, const float* theta, long long n, float decay, hipStream_t st) {
-    hipLaunchKernelGGL(ema_kernel, dim3(bw_blocks(n)), dim3(256), 0, st, ema, theta, n, decay);
+    hipLaunchKernelGGL(ema_kernel, dim3(bw_blocks(n)), dim3(256), 0, st, ema, theta, n, decay, (const float*)nullptr, (const int*)nullptr, 0);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_ema_sched(float* ema, const float* theta, long long n, const float* decay_tab, const int* step_ctr, int n_rows, hipStream_t st) {
+    hipLaunchKernelGGL(ema_kernel, dim3(bw_blocks(n)), dim3(256), 0, st, ema, theta, n, 0.f, decay_tab, step_ctr, n_rows);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }

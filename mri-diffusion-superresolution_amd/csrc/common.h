@@ -326,6 +326,9 @@ int launch_im2col_all_T(const void* x, void* out, int B, int H, int W, int C, in
 template <typename T> int launch_pack_conv_dgrad(const float* w, void* wd, int Cout, int Cin, hipStream_t st);
 int launch_sumsq(const float* g, long long n, float* out, hipStream_t st);
 int launch_ema(float* ema, const float* theta, long long n, float decay, hipStream_t st);
+int launch_ema_sched(float* ema, const float* theta, long long n, const float* decay_tab, const int* step_ctr, int n_rows, hipStream_t st);
+int launch_adamw_sched(float* p, const float* g, float* m, float* v, long long n, const float* sumsq, float grad_scale, float max_norm,
+                       float b1, float b2, float eps, float wd, const float* sched, const int* step_ctr, int n_rows, hipStream_t st);
 int launch_adamw(float* p, const float* g, float* m, float* v, long long n, const float* sumsq, float grad_scale, float max_norm,
                  float lr, float b1, float b2, float eps, float wd, int step, hipStream_t st);
 

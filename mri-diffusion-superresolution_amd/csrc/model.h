@@ -141,6 +141,8 @@ struct Model {
     int train_prepare(hipStream_t st);   // dgrad weight copies + trainable layout (after finalize)
     int train_bind(float* theta_dev, float* grad_dev, hipStream_t st);
     int lora_refresh(hipStream_t st);    // re-pack the adapters from theta
+    int train_plan(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs, const mrisr_tensor* target,
+                   float* loss_dev, hipStream_t st);  // train_step's workspace planning alone (synchronises; never inside a capture)
     int train_step(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,
                    const mrisr_tensor* intrablock, int n_intra, const mrisr_tensor* target, float* loss_dev,
                    mrisr_tensor* pred_out, hipStream_t st);

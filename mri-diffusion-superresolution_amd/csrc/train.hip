@@ -1334,7 +1334,7 @@ int Model::controlnet_train_backward(const mrisr_tensor* d_down, int n_down, con
 }
 
 template <typename T>
-static int train_step_t(Model& m, const mrisr_tensor& sample, const long long* t, int t_scalar, const mrisr_tensor& ehs,
+static int train_plan_t(Model& m, const mrisr_tensor& sample, const long long* t, int t_scalar, const mrisr_tensor& ehs,
                         const mrisr_tensor* intrablock, int n_intra, const mrisr_tensor& target, float* loss_dev,
                         const mrisr_tensor* pred_out, hipStream_t st) {
     if (m.train_ws_key != m.ws_key) {
@@ -1355,8 +1355,34 @@ static int train_step_t(Model& m, const mrisr_tensor& sample, const long long* t
         m.arena.reset();
         m.train_ws_key = m.ws_key;
     }
+    return 0;
+}
+
+template <typename T>
+static int train_step_t(Model& m, const mrisr_tensor& sample, const long long* t, int t_scalar, const mrisr_tensor& ehs,
+                        const mrisr_tensor* intrablock, int n_intra, const mrisr_tensor& target, float* loss_dev,
+                        const mrisr_tensor* pred_out, hipStream_t st) {
+    TRY(train_plan_t<T>(m, sample, t, t_scalar, ehs, intrablock, n_intra, target, loss_dev, pred_out, st));
     Trainer<T> tr(m, st, false);
     return tr.step(sample, t, t_scalar, ehs, intrablock, n_intra, target, loss_dev, pred_out);
+}
+
+// the planning half of train_step alone (workspace + dry pass; both synchronise): what a stream capture of train_step needs done first
+int Model::train_plan(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs, const mrisr_tensor* target,
+                      float* loss_dev, hipStream_t st) {
+    MRISR_REQUIRE(train_ready && (n_trainable == 0 || (theta && grad)), "bind the trainable vector first (mrisr_train_bind)");
+    MRISR_REQUIRE(sample && sample->ndim == 4 && timestep && ehs && ehs->ndim == 3 && target && loss_dev, "train_plan arguments");
+    const int B = (int)sample->shape[0], h = (int)sample->shape[2], w = (int)sample->shape[3];
+    const int t_scalar = timestep->ndim == 0 || timestep->shape[0] == 1;
+    keep = true;
+    int rc = ensure_workspace(B, h, w, (int)ehs->shape[1], st);
+    if (!rc) {
+        const long long* t = static_cast<const long long*>(timestep->data);
+        rc = cfg.compute_dtype == MRISR_F32 ? train_plan_t<float>(*this, *sample, t, t_scalar, *ehs, nullptr, 0, *target, loss_dev, nullptr, st)
+                                            : train_plan_t<bf16>(*this, *sample, t, t_scalar, *ehs, nullptr, 0, *target, loss_dev, nullptr, st);
+    }
+    keep = false;
+    return rc;
 }
 
 int Model::train_step(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs, const mrisr_tensor* intrablock,

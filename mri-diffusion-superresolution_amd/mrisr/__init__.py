@@ -16,3 +16,4 @@ from .datasets import (FastMRILazyDataset, SliceDataset, gaussian_blur, get_data
                        pad_or_center_crop, resize_slices, simulate_low_field)
 from .prompts import compute_embeddings_sd1x5, encode_prompt_sd1x5, get_fixed_prompt_embeds  # noqa: F401
 from .config import TrainConfig, log_configs  # noqa: F401
+from .fit import FitLoop, FitResult, fit  # noqa: F401,E402  (the name `mrisr.fit` is the function; the module stays importable)

@@ -318,6 +318,34 @@ int mrisr_fit_micro(mrisr_fit* f, void* stream);
 int mrisr_fit_apply(mrisr_fit* f, void* stream);
 int mrisr_fit_make_batch(mrisr_fit* f, int step, int micro, float* sample_dev, int64_t* timesteps_dev, float* ehs_dev, float* target_dev,
                          float* eps_hr_dev, float* eps_lr_dev, int32_t* caption_row_dev, void* stream);
+/* T2I-Adapter in the loop (the notebook's lora_rank: null run, or LoRA + adapter as joint_step trains them).  The UNet may be frozen
+ * (n_trainable == 0).  Per micro-batch graph M then also builds the condition, runs the adapter forward, feeds its features to the UNet
+ * step as intrablock residuals and their gradients to the adapter backward (adds into the adapter's bound grad); graph O clips BOTH
+ * buckets by their joint norm (one sumsq, the grad-norm ring holds it), AdamW on each from the same lr table, adapter re-pack, EMA of
+ * each (use_ema), zeroes both gradients.
+ *   adapter          - train-prepared and bound (mrisr_adapter_train_bind), compute dtype of the UNet, cin 192, one feature per UNet
+ *                      level with that level's channels
+ *   cond_dev         - f32 [n_items][res][res]: each item's LR image (1 channel, in [-1, 1], at the training resolution), caller-owned
+ *   res              - multiple of 8, res / 8 == latent_h == latent_w
+ *   exp_avg / exp_avg_sq / ema - flat f32 vectors of the adapter's trainable length (ema: with use_ema)
+ * make_condition - the condition of sample b of (step, micro) for the item make_batch draws, eagerly:
+ *   form 0: f32 [batch][3][res][res] (the image expanded to 3 channels: the input of mrisr_adapter_forward);
+ *   form 1: the adapter's input activation graph M uses, [batch][res/8][res/8][192] in the compute dtype, channel
+ *           c * 64 + dy * 8 + dx = image[8 i + dy][8 j + dx] (PixelUnshuffle(8) of form 0, NHWC). */
+typedef struct {
+    mrisr_adapter* adapter;
+    const float* cond_dev;
+    int32_t res;
+    float* exp_avg_dev;
+    float* exp_avg_sq_dev;
+    float* ema_dev;
+} mrisr_fit_adapter_args;
+int mrisr_fit_create_adapter(mrisr_model* unet, const mrisr_fit_config* cfg, const float* moments_dev, const float* captions_dev,
+                             const int32_t* caption_of_item, const int32_t* index_table, const float* alphas_cumprod,
+                             const float* lr_table, const float* ema_decay_table, float* exp_avg_dev, float* exp_avg_sq_dev,
+                             float* ema_dev, float* loss_ring_dev, float* grad_norm_ring_dev, float* lr_ring_dev,
+                             const mrisr_fit_adapter_args* adapter, mrisr_fit** out);
+int mrisr_fit_make_condition(mrisr_fit* f, int step, int micro, void* out_dev, int form, void* stream);
 
 /* ---- image metrics of the reference's evaluator (src/eval/eval.py:15-51) --------------------------------------
  * pred / gt: f32 [batch][height][width] in [0, 1] (the reference divides its 8-bit PNGs by 255).  out: f32 [batch][4] =

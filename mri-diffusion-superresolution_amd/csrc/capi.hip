@@ -473,6 +473,10 @@ struct mrisr_adapter {
     std::vector<AdRec> recs;
     Act bwd_dcur;             // running gradient between the level-wise backward calls
     int bwd_next_level = -1;  // next level mrisr_adapter_backward_level expects (descending)
+    // the training loop's plan (adapter_fit_plan): geometry it was made for, bumped on every re-plan (captured graphs key on it);
+    // an eager forward clears the key, since it resets (and may reallocate) the arena
+    std::string fit_plan_key;
+    unsigned long long fit_plan_gen = 0;
     std::vector<ConvW*> all_convs() {
         std::vector<ConvW*> v{&conv_in};
         for (auto& b : blocks) {
@@ -657,6 +661,10 @@ struct AdRunner {
         Act u = new_act(B, H / 8, W / 8, C * 64);
         if (!u.p) return 7;
         if (!dry) TRY(launch_pixel_unshuffle_nchw<T>(x.data, x.dtype, u.p, B, C, H, W, 8, st));
+        return forward_from(u, feats, n_feats);
+    }
+    // the forward from the already-unshuffled input u [B, H/8, W/8, cin] (compute dtype, NHWC); u must stay alive for the backward
+    int forward_from(const Act& u, mrisr_tensor* feats, int n_feats) {
         Act cur;
         TRY(conv(u, a.conv_in, 1, ACT_NONE, nullptr, &cur));
         a.rec_u = u;
@@ -801,6 +809,7 @@ int mrisr_adapter_forward(mrisr_adapter* a, const mrisr_tensor* x, mrisr_tensor*
     hipStream_t st = (hipStream_t)stream;
     // size the arena with a dry pass (exact), then run
     int rc;
+    a->fit_plan_key.clear();
     a->arena.dry = true; a->arena.reset(); a->arena.peak = 0;
     a->recorded = false;
     // training: the backward continues in the same arena (the activations must stay put), so size it for both now
@@ -912,6 +921,94 @@ int mrisr_adapter_train_level_range(const mrisr_adapter* ac, int level, int64_t*
 }
 
 }  // extern "C"
+
+// ---- the adapter inside mrisr.fit's captured graphs (fit.hip): planning split from the launches ----
+namespace mrisr {
+
+int adapter_fit_info(const mrisr_adapter* a, AdapterFitInfo* out) {
+    MRISR_REQUIRE(a && out && a->finalized, "adapter not finalized");
+    out->compute_dtype = a->cfg.compute_dtype;
+    out->cin = a->cfg.cin;
+    out->nums_rb = a->cfg.nums_rb;
+    out->n_levels = a->cfg.nums_rb > 0 ? (int)a->blocks.size() / a->cfg.nums_rb : 0;
+    for (int i = 0; i < 4; ++i) out->channels[i] = a->cfg.channels[i];
+    out->n_trainable = a->train_ready ? a->n_trainable : 0;
+    out->theta = a->theta;
+    out->grad = a->grad;
+    return 0;
+}
+
+static Act u_act(const mrisr_tensor& u) {
+    Act x;
+    x.p = u.data; x.B = (int)u.shape[0]; x.C = (int)u.shape[1]; x.H = (int)u.shape[2]; x.W = (int)u.shape[3];
+    return x;
+}
+
+int adapter_fit_plan(mrisr_adapter* a, const mrisr_tensor* u, mrisr_tensor* feats, const mrisr_tensor* d_feats, int n_feats, hipStream_t st) {
+    MRISR_REQUIRE(a && u && feats && d_feats && a->finalized && a->train_ready && a->theta && a->grad, "bind the adapter's trainable vector first");
+    MRISR_REQUIRE(u->ndim == 4 && u->layout == MRISR_NHWC && u->dtype == a->cfg.compute_dtype && u->shape[1] == a->cfg.cin,
+                  "adapter input activation: [B, cin, h, w] stored NHWC in the compute dtype");
+    char kb[96];
+    snprintf(kb, sizeof(kb), "B%lld,%lld,%lld,n%d", (long long)u->shape[0], (long long)u->shape[1], (long long)u->shape[2], n_feats);
+    if (a->fit_plan_key == kb) return 0;
+    const Act ua = u_act(*u);
+    a->arena.dry = true; a->arena.reset(); a->arena.peak = 0;
+    a->recorded = false;
+    int rc;
+    if (a->cfg.compute_dtype == MRISR_F32) {
+        AdRunner<float> r{*a, st, true};
+        rc = r.forward_from(ua, feats, n_feats);
+        if (!rc) rc = r.backward(d_feats, n_feats);
+    } else {
+        AdRunner<bf16> r{*a, st, true};
+        rc = r.forward_from(ua, feats, n_feats);
+        if (!rc) rc = r.backward(d_feats, n_feats);
+    }
+    a->arena.dry = false;
+    a->arena.reset();
+    if (rc) return rc;
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));  // the old buffer may still be in use
+    TRY(a->arena.buf.reserve(a->arena.peak + 4096, false));
+    a->fit_plan_key = kb;
+    ++a->fit_plan_gen;
+    return 0;
+}
+
+int adapter_fit_forward(mrisr_adapter* a, const mrisr_tensor* u, mrisr_tensor* feats, int n_feats, hipStream_t st) {
+    MRISR_REQUIRE(a && u && !a->fit_plan_key.empty(), "plan the adapter first (adapter_fit_plan)");
+    a->arena.reset();
+    int rc;
+    if (a->cfg.compute_dtype == MRISR_F32) { AdRunner<float> r{*a, st, false}; rc = r.forward_from(u_act(*u), feats, n_feats); }
+    else { AdRunner<bf16> r{*a, st, false}; rc = r.forward_from(u_act(*u), feats, n_feats); }
+    a->recorded = rc == 0;
+    return rc;
+}
+
+int adapter_fit_backward(mrisr_adapter* a, const mrisr_tensor* d_feats, int n_feats, hipStream_t st) {
+    MRISR_REQUIRE(a && d_feats && a->train_ready && a->grad, "bind the adapter's trainable vector first");
+    if (a->cfg.compute_dtype == MRISR_F32) { AdRunner<float> r{*a, st, false}; return r.backward(d_feats, n_feats); }
+    AdRunner<bf16> r{*a, st, false};
+    return r.backward(d_feats, n_feats);
+}
+
+int adapter_fit_repack(mrisr_adapter* a, hipStream_t st) {
+    MRISR_REQUIRE(a && a->train_ready && a->theta, "bind the adapter's trainable vector first");
+    return a->cfg.compute_dtype == MRISR_F32 ? adapter_repack_t<float>(*a, st) : adapter_repack_t<bf16>(*a, st);
+}
+
+std::string adapter_fit_key(const mrisr_adapter* ac) {
+    mrisr_adapter* a = const_cast<mrisr_adapter*>(ac);
+    char kb[128];
+    snprintf(kb, sizeof(kb), ",ag%llu,aa%p,ath%p,agr%p", a->fit_plan_gen, a->arena.buf.p, (void*)a->theta, (void*)a->grad);
+    std::string k = kb;
+    for (ConvW* c : a->all_convs()) {
+        snprintf(kb, sizeof(kb), ",%p/%p/%p", c->w, c->wd, (const void*)c->b);
+        k += kb;
+    }
+    return k;
+}
+
+}  // namespace mrisr
 
 // =================================================================================================
 // single-op entry points (parity tests drive the very kernels the models launch)

@@ -5,6 +5,9 @@
 //                                      -> EMA from the decay table -> ring writes, step counter + 1 -> grad memset
 // Both read the optimiser step s and the micro-batch k from a device counter {s, k}, so one capture of each replays for every step;
 // the host only enqueues graph launches (and, with world > 1, the all-reduce of grad between them).
+// With a T2I-Adapter (mrisr_fit_create_adapter) graph M also builds the condition (fit_cond_kernel: the item's LR image, 1 -> 3
+// channels, PixelUnshuffle(8), straight into the adapter's input activation), runs the adapter forward, hands its features to the
+// UNet step and the feature gradients to the adapter backward; graph O clips both buckets by their joint norm and steps both.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -151,6 +154,82 @@ __global__ __launch_bounds__(256) void fit_context_kernel(BatchArgs a) {
     }
 }
 
+// ---- condition builder: LR image table [n_items][res][res] f32 -> the adapter's input ----
+struct CondArgs {
+    const float* img;        // [n_items][res][res]
+    const int* index;
+    const int* ctr;
+    int s_fixed, k_fixed, max_steps, accum, B, res;
+    void* out;
+};
+__device__ inline void load_sk(const CondArgs& a, int& s, int& k) {
+    s = a.ctr ? a.ctr[0] : a.s_fixed;
+    k = a.ctr ? a.ctr[1] : a.k_fixed;
+    s = min(max(s, 0), a.max_steps - 1);
+    k = min(max(k, 0), a.accum - 1);
+}
+// form 1: u [B][res/8][res/8][192] in the compute dtype, channel c * 64 + dy * 8 + dx = image[8 i + dy][8 j + dx] for c = 0, 1, 2
+// (F.pixel_unshuffle(x.expand(3), 8) in NHWC).  One thread per 16 output bytes: V = 16 / sizeof(T) channels of one (c, dy) row,
+// read as V contiguous floats of the image row (res % 8 == 0 keeps every read 16-byte aligned).
+template <typename T>
+__global__ __launch_bounds__(256) void fit_cond_kernel(CondArgs a) {
+    constexpr int V = 16 / sizeof(T);
+    constexpr int PER_PIX = 192 / V;  // 16-byte chunks per output pixel
+    const int h = a.res / 8;
+    const long long gid = blockIdx.x * 256ll + threadIdx.x;
+    if (gid >= (long long)a.B * h * h * PER_PIX) return;
+    const int q = (int)(gid % PER_PIX);
+    const long long pix = gid / PER_PIX;
+    const int j = (int)(pix % h), i = (int)((pix / h) % h), b = (int)(pix / ((long long)h * h));
+    int s, k;
+    load_sk(a, s, k);
+    const int item = a.index[((long long)s * a.accum + k) * a.B + b];
+    const int r = (q * V) % 64, dy = r / 8, dx = r % 8;
+    const float* src = a.img + ((long long)item * a.res + (8 * i + dy)) * a.res + 8 * j + dx;
+    T* dst = static_cast<T*>(a.out) + pix * 192 + q * V;
+    if constexpr (V == 4) {
+        *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
+    } else {
+        const float4 lo = *reinterpret_cast<const float4*>(src), hi = *reinterpret_cast<const float4*>(src + 4);
+        const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        union { T t[8]; uint4 u; } o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o.t[e] = from_f32<T>(v[e]);
+        *reinterpret_cast<uint4*>(dst) = o.u;
+    }
+}
+// form 0: x [B][3][res][res] f32 (the input of Adapter_XL.forward): one thread per 4 pixels, the same float4 to each channel
+__global__ __launch_bounds__(256) void fit_cond_image_kernel(CondArgs a) {
+    const long long plane = (long long)a.res * a.res, groups = plane / 4;
+    const long long gid = blockIdx.x * 256ll + threadIdx.x;
+    if (gid >= groups * a.B) return;
+    const int b = (int)(gid / groups);
+    const long long g = gid - (long long)b * groups;
+    int s, k;
+    load_sk(a, s, k);
+    const int item = a.index[((long long)s * a.accum + k) * a.B + b];
+    const float4 v = reinterpret_cast<const float4*>(a.img + (long long)item * plane)[g];
+    float4* dst = reinterpret_cast<float4*>(static_cast<float*>(a.out) + (long long)b * 3 * plane);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dst[c * groups + g] = v;
+}
+
+int launch_cond(const CondArgs& a, int form, int dtype, hipStream_t st) {
+    const long long h = a.res / 8;
+    if (form == 0) {
+        const long long n = (long long)a.res * a.res / 4 * a.B;
+        hipLaunchKernelGGL(fit_cond_image_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    } else if (dtype == MRISR_F32) {
+        const long long n = (long long)a.B * h * h * (192 / 4);
+        hipLaunchKernelGGL(fit_cond_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    } else {
+        const long long n = (long long)a.B * h * h * (192 / 8);
+        hipLaunchKernelGGL(fit_cond_kernel<bf16>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    }
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 int launch_batch(const BatchArgs& a, hipStream_t st) {
     const long long n1 = (a.n + 3) / 4 * a.B, n2 = a.row * a.B;
     hipLaunchKernelGGL(fit_latents_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, a);
@@ -190,6 +269,14 @@ struct mrisr_fit {
     float *loss_ring = nullptr, *gnorm_ring = nullptr, *lr_ring = nullptr;
     DevBuf d_index, d_capid, d_ac, d_sched, d_decay, d_ctr, d_x, d_tgt, d_t, d_ehs, d_scalars;
     int host_ctr[4] = {0, 0, 0, 0};  // host mirror of {s, k}; also the source of set_step's copy
+    // T2I-Adapter (mrisr_fit_create_adapter; null: the LoRA-only loop)
+    mrisr_adapter* ad = nullptr;
+    AdapterFitInfo ai{};
+    int res = 0;
+    const float* cond = nullptr;
+    float *ad_exp_avg = nullptr, *ad_exp_avg_sq = nullptr, *ad_ema = nullptr;
+    DevBuf d_u, d_feat[4], d_dfeat[4];
+    mrisr_tensor u_t{}, feats[4]{}, dfeats[4]{};
     hipGraphExec_t exec_m = nullptr, exec_o = nullptr;
     std::string key_m, key_o;
     int captures = 0;
@@ -244,6 +331,12 @@ struct mrisr_fit {
         e = mrisr_tensor{}; e.data = d_ehs.p; e.ndim = 3; e.dtype = MRISR_F32; e.layout = MRISR_NCHW;
         e.shape[0] = cfg.batch; e.shape[1] = cfg.ctx_len; e.shape[2] = cfg.ctx_dim;
     }
+    CondArgs cond_args() const {
+        CondArgs a{};
+        a.img = cond; a.index = static_cast<const int*>(d_index.p); a.ctr = static_cast<const int*>(d_ctr.p);
+        a.max_steps = cfg.max_steps; a.accum = cfg.accum; a.B = cfg.batch; a.res = res; a.out = u_t.data;
+        return a;
+    }
     // every address a capture bakes in besides this handle's own buffers (fixed for its lifetime): the model's workspace generation
     // (persist / arena base addresses change when a validation forward or another geometry re-plans them), the bound vectors, the
     // adapter scale the re-pack kernels take by value
@@ -270,16 +363,18 @@ static int capture(hipStream_t st, hipGraphExec_t* exec, const std::function<int
 
 extern "C" {
 
-int mrisr_fit_create(mrisr_model* unet, const mrisr_fit_config* cfg, const float* moments_dev, const float* captions_dev,
-                     const int32_t* caption_of_item, const int32_t* index_table, const float* alphas_cumprod, const float* lr_table,
-                     const float* ema_decay_table, float* exp_avg_dev, float* exp_avg_sq_dev, float* ema_dev, float* loss_ring_dev,
-                     float* grad_norm_ring_dev, float* lr_ring_dev, mrisr_fit** out) {
-    API_BEGIN
+static int fit_create(mrisr_model* unet, const mrisr_fit_config* cfg, const float* moments_dev, const float* captions_dev,
+                      const int32_t* caption_of_item, const int32_t* index_table, const float* alphas_cumprod, const float* lr_table,
+                      const float* ema_decay_table, float* exp_avg_dev, float* exp_avg_sq_dev, float* ema_dev, float* loss_ring_dev,
+                      float* grad_norm_ring_dev, float* lr_ring_dev, const mrisr_fit_adapter_args* ad, mrisr_fit** out) {
     MRISR_REQUIRE(unet && cfg && moments_dev && captions_dev && caption_of_item && index_table && alphas_cumprod && lr_table && out,
                   "null argument");
-    MRISR_REQUIRE(exp_avg_dev && exp_avg_sq_dev && loss_ring_dev && grad_norm_ring_dev && lr_ring_dev, "optimiser state / rings");
+    MRISR_REQUIRE(loss_ring_dev && grad_norm_ring_dev && lr_ring_dev, "optimiser state / rings");
     Model& U = *unet;
-    MRISR_REQUIRE(U.train_ready && U.theta && U.grad && U.n_trainable > 0, "bind the adapters first (mrisr_train_bind; lora_fused = 1)");
+    if (!ad) MRISR_REQUIRE(U.train_ready && U.theta && U.grad && U.n_trainable > 0, "bind the adapters first (mrisr_train_bind; lora_fused = 1)");
+    else MRISR_REQUIRE(U.train_ready && (U.n_trainable == 0 || (U.theta && U.grad)), "prepare the UNet for training first (mrisr_train_bind)");
+    const bool lora = U.n_trainable > 0;
+    MRISR_REQUIRE(!lora || (exp_avg_dev && exp_avg_sq_dev), "optimiser state / rings");
     const mrisr_fit_config& c = *cfg;
     MRISR_REQUIRE(c.batch > 0 && c.accum > 0 && c.max_steps > 0 && c.world > 0 && c.sample_base >= 0, "batch / accum / steps / world");
     MRISR_REQUIRE(c.n_items > 0 && c.n_captions > 0 && c.ctx_len > 0 && c.ctx_dim == U.cfg.cross_attention_dim, "items / captions");
@@ -287,7 +382,22 @@ int mrisr_fit_create(mrisr_model* unet, const mrisr_fit_config* cfg, const float
     MRISR_REQUIRE(c.num_train_timesteps > 0 && c.empty_row >= -1 && c.empty_row < c.n_captions, "timesteps / empty row");
     MRISR_REQUIRE(c.proportion_empty >= 0.f && c.proportion_empty <= 1.f && (c.proportion_empty == 0.f || c.empty_row >= 0),
                   "proportion_empty_prompts needs the empty-prompt row");
-    MRISR_REQUIRE(!c.use_ema || (ema_dev && ema_decay_table), "EMA needs its vector and decay table");
+    MRISR_REQUIRE(!c.use_ema || ((ema_dev || !lora) && ema_decay_table), "EMA needs its vector and decay table");
+    AdapterFitInfo ai{};
+    if (ad) {
+        MRISR_REQUIRE(ad->adapter && ad->cond_dev && ad->exp_avg_dev && ad->exp_avg_sq_dev && (!c.use_ema || ad->ema_dev),
+                      "adapter: handle, condition table, optimiser state");
+        TRY(adapter_fit_info(ad->adapter, &ai));
+        MRISR_REQUIRE(ai.n_trainable > 0 && ai.theta && ai.grad, "bind the adapter's trainable vector first (mrisr_adapter_train_bind)");
+        MRISR_REQUIRE(ai.compute_dtype == U.cfg.compute_dtype, "the adapter's compute dtype differs from the UNet's");
+        MRISR_REQUIRE(ai.cin == 192, "the condition builder feeds cin = 192 (3 channels, PixelUnshuffle(8))");
+        MRISR_REQUIRE(ad->res > 0 && ad->res % 8 == 0, "condition resolution must be a multiple of 8");
+        MRISR_REQUIRE(ad->res / 8 == c.latent_h && ad->res / 8 == c.latent_w, "condition resolution / 8 must equal the latent size");
+        // one feature per UNet level, of that level's channels and size (stride-2 convs on both sides: (n - 1) / 2 + 1)
+        MRISR_REQUIRE(ai.n_levels == U.cfg.num_levels && ai.n_levels <= 4, "adapter levels must equal the UNet's down levels");
+        for (int i = 0; i < ai.n_levels; ++i)
+            MRISR_REQUIRE(ai.channels[i] == U.cfg.block_out_channels[i], "adapter feature channels do not match the UNet's intrablock positions");
+    }
     // every index the kernels follow unchecked is checked here once
     const long long n_idx = (long long)c.max_steps * c.accum * c.batch;
     for (long long i = 0; i < n_idx; ++i) MRISR_REQUIRE(index_table[i] >= 0 && index_table[i] < c.n_items, "index table entry out of range");
@@ -332,8 +442,60 @@ int mrisr_fit_create(mrisr_model* unet, const mrisr_fit_config* cfg, const float
         TRY(f->d_decay.reserve(sizeof(float) * c.max_steps, false));
         MRISR_CHECK_HIP(hipMemcpy(f->d_decay.p, ema_decay_table, sizeof(float) * c.max_steps, hipMemcpyHostToDevice));
     }
+    if (ad) {
+        f->ad = ad->adapter;
+        f->ai = ai;
+        f->res = ad->res;
+        f->cond = ad->cond_dev;
+        f->ad_exp_avg = ad->exp_avg_dev;
+        f->ad_exp_avg_sq = ad->exp_avg_sq_dev;
+        f->ad_ema = c.use_ema ? ad->ema_dev : nullptr;
+        const int cdt = U.cfg.compute_dtype;
+        const size_t es = dtype_size(cdt);
+        const int h = ad->res / 8;
+        mrisr_tensor& u = f->u_t;
+        u.ndim = 4; u.dtype = cdt; u.layout = MRISR_NHWC;
+        u.shape[0] = c.batch; u.shape[1] = 192; u.shape[2] = h; u.shape[3] = h;  // logical [B, C, H, W], stored NHWC
+        TRY(f->d_u.reserve((size_t)c.batch * h * h * 192 * es, false));
+        u.data = f->d_u.p;
+        int hh = h;
+        for (int i = 0; i < ai.n_levels; ++i) {
+            if (i) hh = (hh - 1) / 2 + 1;
+            mrisr_tensor t{};
+            t.ndim = 4; t.dtype = cdt; t.layout = MRISR_NHWC;
+            t.shape[0] = c.batch; t.shape[1] = ai.channels[i]; t.shape[2] = hh; t.shape[3] = hh;  // logical [B, C, H, W], stored NHWC
+            const size_t bytes = (size_t)c.batch * ai.channels[i] * hh * hh * es;
+            TRY(f->d_feat[i].reserve(bytes, false));
+            TRY(f->d_dfeat[i].reserve(bytes, false));
+            f->feats[i] = t;
+            f->feats[i].data = f->d_feat[i].p;
+            f->dfeats[i] = t;
+            f->dfeats[i].data = f->d_dfeat[i].p;
+        }
+    }
     *out = f.release();
     return 0;
+}
+
+int mrisr_fit_create(mrisr_model* unet, const mrisr_fit_config* cfg, const float* moments_dev, const float* captions_dev,
+                     const int32_t* caption_of_item, const int32_t* index_table, const float* alphas_cumprod, const float* lr_table,
+                     const float* ema_decay_table, float* exp_avg_dev, float* exp_avg_sq_dev, float* ema_dev, float* loss_ring_dev,
+                     float* grad_norm_ring_dev, float* lr_ring_dev, mrisr_fit** out) {
+    API_BEGIN
+    return fit_create(unet, cfg, moments_dev, captions_dev, caption_of_item, index_table, alphas_cumprod, lr_table, ema_decay_table,
+                      exp_avg_dev, exp_avg_sq_dev, ema_dev, loss_ring_dev, grad_norm_ring_dev, lr_ring_dev, nullptr, out);
+    API_END
+}
+
+int mrisr_fit_create_adapter(mrisr_model* unet, const mrisr_fit_config* cfg, const float* moments_dev, const float* captions_dev,
+                             const int32_t* caption_of_item, const int32_t* index_table, const float* alphas_cumprod,
+                             const float* lr_table, const float* ema_decay_table, float* exp_avg_dev, float* exp_avg_sq_dev,
+                             float* ema_dev, float* loss_ring_dev, float* grad_norm_ring_dev, float* lr_ring_dev,
+                             const mrisr_fit_adapter_args* adapter, mrisr_fit** out) {
+    API_BEGIN
+    MRISR_REQUIRE(adapter, "null adapter arguments");
+    return fit_create(unet, cfg, moments_dev, captions_dev, caption_of_item, index_table, alphas_cumprod, lr_table, ema_decay_table,
+                      exp_avg_dev, exp_avg_sq_dev, ema_dev, loss_ring_dev, grad_norm_ring_dev, lr_ring_dev, adapter, out);
     API_END
 }
 
@@ -370,6 +532,21 @@ int mrisr_fit_make_batch(mrisr_fit* f, int step, int micro, float* sample_dev, i
     API_END
 }
 
+int mrisr_fit_make_condition(mrisr_fit* f, int step, int micro, void* out_dev, int form, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(f && out_dev, "null argument");
+    MRISR_REQUIRE(f->ad, "the loop trains no T2I-Adapter (mrisr_fit_create_adapter)");
+    MRISR_REQUIRE(form == 0 || form == 1, "form 0 (NCHW f32 image) or 1 (unshuffled NHWC activation)");
+    MRISR_REQUIRE(step >= 0 && step < f->cfg.max_steps && micro >= 0 && micro < f->cfg.accum, "(step, micro) outside the run");
+    CondArgs a = f->cond_args();
+    a.ctr = nullptr;
+    a.s_fixed = step;
+    a.k_fixed = micro;
+    a.out = out_dev;
+    return launch_cond(a, form, f->ai.compute_dtype, (hipStream_t)stream);
+    API_END
+}
+
 int mrisr_fit_micro(mrisr_fit* f, void* stream) {
     API_BEGIN
     MRISR_REQUIRE(f, "null handle");
@@ -377,8 +554,11 @@ int mrisr_fit_micro(mrisr_fit* f, void* stream) {
     hipStream_t user = (hipStream_t)stream, st;
     TRY(f->enter(user, &st));
     Model& U = *f->m;
-    // a plain training step of this model may have left T2I-Adapter / ControlNet hooks set: the loop trains the LoRA UNet alone
-    U.d_intra.clear();
+    // a plain training step of this model may have left T2I-Adapter / ControlNet hooks set: the loop trains the LoRA UNet alone,
+    // or with this handle's adapter, whose feature gradients go to the handle's own buffers
+    const int n_feats = f->ad ? f->ai.n_levels : 0;
+    if (f->ad) U.d_intra.assign(f->dfeats, f->dfeats + n_feats);
+    else U.d_intra.clear();
     if (!U.tr_down.empty() || U.has_tr_mid) {
         U.tr_down.clear(); U.d_tr_down.clear(); U.has_tr_mid = false; U.tr_mid = mrisr_tensor{}; U.d_tr_mid = mrisr_tensor{};
         U.train_ws_key.clear();
@@ -387,14 +567,21 @@ int mrisr_fit_micro(mrisr_fit* f, void* stream) {
     f->describe(x, t, e, g);
     // plan OUTSIDE the capture (workspace + dry pass synchronise); a no-op while the geometry is planned
     TRY(gemm_prepare());
-    TRY(U.train_plan(&x, &t, &e, &g, f->loss(), st));
+    if (f->ad) TRY(adapter_fit_plan(f->ad, &f->u_t, f->feats, f->dfeats, n_feats, st));
+    TRY(U.train_plan(&x, &t, &e, f->ad ? f->feats : nullptr, n_feats, &g, f->loss(), st));
     char kb[128];
     snprintf(kb, sizeof(kb), ",B%d,%d,%d,L%d", f->cfg.batch, f->cfg.latent_h, f->cfg.latent_w, f->cfg.ctx_len);
-    const std::string key = f->model_key() + kb;
+    std::string key = f->model_key() + kb;
+    if (f->ad) key += adapter_fit_key(f->ad);
     if (!f->exec_m || f->key_m != key) {
         TRY(capture(st, &f->exec_m, [&]() -> int {
             TRY(launch_batch(f->args(), st));
-            TRY(U.train_step(&x, &t, &e, nullptr, 0, &g, f->loss(), nullptr, st));
+            if (f->ad) {
+                TRY(launch_cond(f->cond_args(), 1, f->ai.compute_dtype, st));
+                TRY(adapter_fit_forward(f->ad, &f->u_t, f->feats, n_feats, st));
+            }
+            TRY(U.train_step(&x, &t, &e, f->ad ? f->feats : nullptr, n_feats, &g, f->loss(), nullptr, st));
+            if (f->ad) TRY(adapter_fit_backward(f->ad, f->dfeats, n_feats, st));
             hipLaunchKernelGGL(fit_micro_end_kernel, dim3(1), dim3(1), 0, st, f->ctr(), (const float*)f->loss(), f->loss_acc());
             MRISR_CHECK_HIP(hipGetLastError());
             return 0;
@@ -418,8 +605,43 @@ int mrisr_fit_apply(mrisr_fit* f, void* stream) {
     Model& U = *f->m;
     const mrisr_fit_config& c = f->cfg;
     const float grad_scale = 1.0f / ((float)c.world * (float)c.accum);
-    const std::string key = f->model_key();
-    if (!f->exec_o || f->key_o != key) {
+    std::string key = f->model_key();
+    if (f->ad) {
+        char kb[160];
+        snprintf(kb, sizeof(kb), ",m%p,v%p,e%p", (void*)f->ad_exp_avg, (void*)f->ad_exp_avg_sq, (void*)f->ad_ema);
+        key += adapter_fit_key(f->ad) + kb;
+    }
+    if (f->ad && (!f->exec_o || f->key_o != key)) {
+        // both buckets as one optimiser over all trainable parameters: one clip by the joint norm, one lr table, one grad_scale
+        const bool lora = f->n_theta > 0;
+        const AdapterFitInfo& ai = f->ai;
+        const float* sched = static_cast<const float*>(f->d_sched.p);
+        const float* decay = static_cast<const float*>(f->d_decay.p);
+        TRY(capture(st, &f->exec_o, [&]() -> int {
+            MRISR_CHECK_HIP(hipMemsetAsync(f->sumsq(), 0, sizeof(float), st));
+            if (lora) TRY(launch_sumsq(U.grad, f->n_theta, f->sumsq(), st));
+            TRY(launch_sumsq(ai.grad, ai.n_trainable, f->sumsq(), st));
+            if (lora) {
+                TRY(launch_adamw_sched(U.theta, U.grad, f->exp_avg, f->exp_avg_sq, f->n_theta, f->sumsq(), grad_scale, c.max_grad_norm,
+                                       c.beta1, c.beta2, c.eps, c.weight_decay, sched, f->ctr(), c.max_steps, st));
+                TRY(U.lora_refresh(st));
+            }
+            TRY(launch_adamw_sched(ai.theta, ai.grad, f->ad_exp_avg, f->ad_exp_avg_sq, ai.n_trainable, f->sumsq(), grad_scale,
+                                   c.max_grad_norm, c.beta1, c.beta2, c.eps, c.weight_decay, sched, f->ctr(), c.max_steps, st));
+            TRY(adapter_fit_repack(f->ad, st));
+            if (lora && f->ema) TRY(launch_ema_sched(f->ema, U.theta, f->n_theta, decay, f->ctr(), c.max_steps, st));
+            if (f->ad_ema) TRY(launch_ema_sched(f->ad_ema, ai.theta, ai.n_trainable, decay, f->ctr(), c.max_steps, st));
+            hipLaunchKernelGGL(fit_step_end_kernel, dim3(1), dim3(1), 0, st, f->ctr(), f->loss_acc(), (const float*)f->sumsq(), sched,
+                               1.0f / (float)c.accum, grad_scale, c.max_steps, f->loss_ring, f->gnorm_ring, f->lr_ring);
+            MRISR_CHECK_HIP(hipGetLastError());
+            if (lora) MRISR_CHECK_HIP(hipMemsetAsync(U.grad, 0, sizeof(float) * f->n_theta, st));
+            MRISR_CHECK_HIP(hipMemsetAsync(ai.grad, 0, sizeof(float) * ai.n_trainable, st));
+            return 0;
+        }));
+        f->key_o = key;
+        ++f->captures;
+    }
+    if (!f->ad && (!f->exec_o || f->key_o != key)) {
         TRY(capture(st, &f->exec_o, [&]() -> int {
             MRISR_CHECK_HIP(hipMemsetAsync(f->sumsq(), 0, sizeof(float), st));
             TRY(launch_sumsq(U.grad, f->n_theta, f->sumsq(), st));

@@ -141,11 +141,29 @@ struct Model {
     int train_prepare(hipStream_t st);   // dgrad weight copies + trainable layout (after finalize)
     int train_bind(float* theta_dev, float* grad_dev, hipStream_t st);
     int lora_refresh(hipStream_t st);    // re-pack the adapters from theta
-    int train_plan(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs, const mrisr_tensor* target,
-                   float* loss_dev, hipStream_t st);  // train_step's workspace planning alone (synchronises; never inside a capture)
+    int train_plan(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs, const mrisr_tensor* intrablock,
+                   int n_intra, const mrisr_tensor* target, float* loss_dev,
+                   hipStream_t st);  // train_step's workspace planning alone (synchronises; never inside a capture)
     int train_step(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,
                    const mrisr_tensor* intrablock, int n_intra, const mrisr_tensor* target, float* loss_dev,
                    mrisr_tensor* pred_out, hipStream_t st);
 };
+
+// ---- the T2I-Adapter inside the device training loop (capi.hip; used by fit.hip) ----
+struct AdapterFitInfo {
+    int compute_dtype, cin, nums_rb, n_levels;
+    int channels[4];
+    long long n_trainable;
+    float* theta;  // bound flat parameter / gradient vectors (null: not bound)
+    float* grad;
+};
+int adapter_fit_info(const mrisr_adapter* a, AdapterFitInfo* out);
+// dry forward + backward from u [B, cin, h, w] (stored NHWC, compute dtype), arena reserve, GEMM tuning: synchronises; a no-op while the
+// geometry is planned.  Never inside a capture.
+int adapter_fit_plan(mrisr_adapter* a, const mrisr_tensor* u, mrisr_tensor* feats, const mrisr_tensor* d_feats, int n_feats, hipStream_t st);
+int adapter_fit_forward(mrisr_adapter* a, const mrisr_tensor* u, mrisr_tensor* feats, int n_feats, hipStream_t st);  // launches only
+int adapter_fit_backward(mrisr_adapter* a, const mrisr_tensor* d_feats, int n_feats, hipStream_t st);               // adds into grad
+int adapter_fit_repack(mrisr_adapter* a, hipStream_t st);  // forward and dgrad banks from theta (mrisr_adapter_train_refresh)
+std::string adapter_fit_key(const mrisr_adapter* a);      // every address a capture of the calls above bakes in, plus the plan generation
 
 }  // namespace mrisr

@@ -785,7 +785,8 @@ struct Trainer : Runner<T> {
     // also d(feature); hand it to the caller's tensor (mrisr_train_set_intrablock_grads) for the adapter's own backward
     int export_feature_grad(const Act& x, int ib) {
         if (ib >= (int)m.d_intra.size() || !m.d_intra[ib].data) return 0;
-        MRISR_REQUIRE(is_live(x), "adapter feature enters before any trainable block");
+        // a frozen UNet (no LoRA upstream): the feature itself is the trainable input, so x carries a gradient from here on
+        if (!is_live(x)) live.insert(x.p);
         const mrisr_tensor out = m.d_intra[ib];
         tape.push_back([=]() -> int {
             auto it = slots.find(x.p);
@@ -1333,11 +1334,24 @@ int Model::controlnet_train_backward(const mrisr_tensor* d_down, int n_down, con
     return rc;
 }
 
+// what a training step's workspace plan depends on besides the geometry (ws_key): the adapter features (their layout decides whether
+// they pass through the arena) and which of them export a gradient (a frozen UNet differentiates its encoder only then).  Without
+// features the key is ws_key itself, so a plan made with features is never reused without them, nor the reverse.
+static std::string train_plan_key(const Model& m, const mrisr_tensor* intrablock, int n_intra) {
+    if (n_intra <= 0 && m.d_intra.empty()) return m.ws_key;
+    std::string k = m.ws_key + ",intra:";
+    for (int i = 0; i < n_intra; ++i) k += intrablock[i].layout == MRISR_NHWC && intrablock[i].dtype == m.cfg.compute_dtype ? 'h' : 'c';
+    k += ",d:";
+    for (const mrisr_tensor& d : m.d_intra) k += d.data ? '1' : '0';
+    return k;
+}
+
 template <typename T>
 static int train_plan_t(Model& m, const mrisr_tensor& sample, const long long* t, int t_scalar, const mrisr_tensor& ehs,
                         const mrisr_tensor* intrablock, int n_intra, const mrisr_tensor& target, float* loss_dev,
                         const mrisr_tensor* pred_out, hipStream_t st) {
-    if (m.train_ws_key != m.ws_key) {
+    const std::string key = train_plan_key(m, intrablock, n_intra);
+    if (m.train_ws_key != key) {
         // dry pass of forward + backward sizes the arena exactly
         ++m.ws_gen;  // the arena may be reallocated below
         m.arena.dry = true;
@@ -1353,7 +1367,7 @@ static int train_plan_t(Model& m, const mrisr_tensor& sample, const long long* t
         MRISR_CHECK_HIP(hipStreamSynchronize(st));
         TRY(m.arena.buf.reserve(m.arena.peak + 4096, false));
         m.arena.reset();
-        m.train_ws_key = m.ws_key;
+        m.train_ws_key = key;
     }
     return 0;
 }
@@ -1368,8 +1382,8 @@ static int train_step_t(Model& m, const mrisr_tensor& sample, const long long* t
 }
 
 // the planning half of train_step alone (workspace + dry pass; both synchronise): what a stream capture of train_step needs done first
-int Model::train_plan(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs, const mrisr_tensor* target,
-                      float* loss_dev, hipStream_t st) {
+int Model::train_plan(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs, const mrisr_tensor* intrablock,
+                      int n_intra, const mrisr_tensor* target, float* loss_dev, hipStream_t st) {
     MRISR_REQUIRE(train_ready && (n_trainable == 0 || (theta && grad)), "bind the trainable vector first (mrisr_train_bind)");
     MRISR_REQUIRE(sample && sample->ndim == 4 && timestep && ehs && ehs->ndim == 3 && target && loss_dev, "train_plan arguments");
     const int B = (int)sample->shape[0], h = (int)sample->shape[2], w = (int)sample->shape[3];
@@ -1378,8 +1392,8 @@ int Model::train_plan(const mrisr_tensor* sample, const mrisr_tensor* timestep, 
     int rc = ensure_workspace(B, h, w, (int)ehs->shape[1], st);
     if (!rc) {
         const long long* t = static_cast<const long long*>(timestep->data);
-        rc = cfg.compute_dtype == MRISR_F32 ? train_plan_t<float>(*this, *sample, t, t_scalar, *ehs, nullptr, 0, *target, loss_dev, nullptr, st)
-                                            : train_plan_t<bf16>(*this, *sample, t, t_scalar, *ehs, nullptr, 0, *target, loss_dev, nullptr, st);
+        rc = cfg.compute_dtype == MRISR_F32 ? train_plan_t<float>(*this, *sample, t, t_scalar, *ehs, intrablock, n_intra, *target, loss_dev, nullptr, st)
+                                            : train_plan_t<bf16>(*this, *sample, t, t_scalar, *ehs, intrablock, n_intra, *target, loss_dev, nullptr, st);
     }
     keep = false;
     return rc;

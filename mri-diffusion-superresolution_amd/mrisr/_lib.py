@@ -72,7 +72,7 @@ EXPORTS = [
     "mrisr_op_conv3x3", "mrisr_op_linear", "mrisr_op_ln_linear", "mrisr_op_linear_fp8", "mrisr_op_mlp", "mrisr_op_groupnorm", "mrisr_op_layernorm", "mrisr_op_attention",
     "mrisr_op_attention_bwd",
     "mrisr_fit_create", "mrisr_fit_destroy", "mrisr_fit_set_step", "mrisr_fit_get_step", "mrisr_fit_num_captures", "mrisr_fit_micro",
-    "mrisr_fit_apply", "mrisr_fit_make_batch",
+    "mrisr_fit_apply", "mrisr_fit_make_batch", "mrisr_fit_create_adapter", "mrisr_fit_make_condition",
 ]
 
 

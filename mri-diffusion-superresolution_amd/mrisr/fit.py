@@ -15,6 +15,11 @@ draws exactly the batches the uninterrupted run would have drawn.
             ehs = caption embedding, or the "" embedding with probability proportion_empty_prompts
             loss_k = mse(unet(noisy, t, ehs), eps); grad += d loss_k
         clip_grad_norm_(max_grad_norm) of grad / (world * accum); AdamW(lr = schedule(s)); EMA(decay(s + 1)); grad = 0
+
+With ``adapter=`` (the notebook's T2I-Adapter run, ``lora_rank: null``) each micro-batch also builds the condition (the item's LR
+image, 3 channels, PixelUnshuffle(8)), runs the adapter, adds its features inside the UNet and differentiates the adapter with the
+feature gradients; the clip then takes the joint norm of the LoRA bucket (if the UNet trains) and the adapter bucket, as
+``joint_step`` does.
 """
 from __future__ import annotations
 
@@ -31,10 +36,11 @@ import torch
 from . import _lib as L
 from .config import TrainConfig, log_configs
 from .dist import all_reduce_sum_, shard_range
-from .train import LoRATrainer, _FlatAdamW, cosine_lr
+from .train import AdapterTrainer, LoRATrainer, _FlatAdamW, cosine_lr
 
 LR_SCHEDULERS = ("cosine", "constant")
 WEIGHTS_NAME = "pytorch_lora_weights.safetensors"
+ADAPTER_NAME = "t2i_adapter.safetensors"
 STATE_NAME = "fit_state.json"
 
 
@@ -44,6 +50,11 @@ class _FitConfig(C.Structure):
                                          "num_train_timesteps", "use_ema")] + \
                [(n, C.c_float) for n in ("proportion_empty", "scaling_factor", "beta1", "beta2", "eps", "weight_decay",
                                          "max_grad_norm")] + [("seed", C.c_uint64)]
+
+
+class _FitAdapterArgs(C.Structure):
+    _fields_ = [("adapter", C.c_void_p), ("cond", C.c_void_p), ("res", C.c_int32), ("exp_avg", C.c_void_p),
+                ("exp_avg_sq", C.c_void_p), ("ema", C.c_void_p)]
 
 
 # ---------------------------------------------------------------------------------------------- host-side tables (no GPU)
@@ -63,6 +74,36 @@ def check_config(config: TrainConfig, caption_embeds: Optional[Dict[str, torch.T
             raise ValueError(f"{k} must be >= 1")
     if config.lr_warmup_steps < 0:
         raise ValueError("lr_warmup_steps must be >= 0")
+
+
+def trained_buckets(lora: bool, adapter: bool) -> List[str]:
+    """The parameter sets a run trains, as ``fit_state.json`` records them."""
+    return [b for b, on in (("lora", lora), ("adapter", adapter)) if on]
+
+
+def check_resume_buckets(state: dict, buckets: List[str], path: str = "") -> None:
+    """A checkpoint resumes only into a run that trains the same parameter sets; a state file without the field was written by a
+    LoRA-only run."""
+    have = list(state.get("buckets", ["lora"]))
+    if sorted(have) != sorted(buckets):
+        raise ValueError(f"checkpoint {path} trained {'+'.join(have)}; this run trains {'+'.join(buckets) or 'nothing'}")
+
+
+def check_adapter(config: TrainConfig, unet, adapter) -> None:
+    """What ``fit(adapter=...)`` refuses before the loop handle exists: the condition builder feeds ``cin = 192`` at ``resolution``,
+    and the adapter's four features must land on the UNet's intrablock positions in the UNet's compute dtype."""
+    res = int(config.resolution)
+    if res % 8:
+        raise ValueError(f"resolution {res} is not a multiple of 8: the adapter's PixelUnshuffle(8) needs one")
+    if int(adapter.cin) != 192:
+        raise ValueError(f"the condition builder feeds cin = 192 (3 channels, PixelUnshuffle(8)); the adapter has cin = {adapter.cin}")
+    want = L.torch_dtype(L.dtype_id(config.compute_dtype()))
+    if adapter.compute_dtype != want or adapter.compute_dtype != unet.compute_dtype:
+        raise ValueError(f"mixed_precision={config.mixed_precision!r} means compute dtype {want}; the adapter computes in "
+                         f"{adapter.compute_dtype}, the UNet in {unet.compute_dtype}")
+    levels = tuple(unet.config.block_out_channels)
+    if tuple(adapter.channels) != levels or adapter.nums_rb < 1:
+        raise ValueError(f"the adapter's features {tuple(adapter.channels)} do not fit the UNet's intrablock positions {levels}")
 
 
 def base_learning_rate(config: TrainConfig, world: int = 1) -> float:
@@ -129,10 +170,17 @@ class FitLoop:
     """The C-ABI loop handle plus what it reads: the encoded training set, the caption table, the rings."""
 
     def __init__(self, config: TrainConfig, trainer: LoRATrainer, vae, train_dataset, caption_embeds: Dict[str, torch.Tensor],
-                 world: int = 1, rank: int = 0, use_ema: bool = False, encode_batch: int = 16):
+                 world: int = 1, rank: int = 0, use_ema: bool = False, encode_batch: int = 16,
+                 adapter_trainer: Optional[AdapterTrainer] = None):
         unet = trainer.unet
         dev = unet.device
         self.config, self.trainer, self.world, self.rank = config, trainer, int(world), int(rank)
+        self.adapter_trainer = adapter_trainer
+        if adapter_trainer is not None:
+            check_adapter(config, unet, adapter_trainer.adapter)
+            for k in ("betas", "eps", "weight_decay", "max_grad_norm"):
+                if getattr(adapter_trainer, k) != getattr(trainer, k):
+                    raise ValueError(f"one optimiser over both buckets: the adapter trainer's {k} differs from the UNet trainer's")
         B, accum, S = int(config.train_batch_size), int(config.gradient_accumulation_steps), int(config.max_train_steps)
         self.batch, self.accum, self.max_steps = B, accum, S
         # ---- encode every item once: posterior moments {HR mean, HR std, LR mean, LR std}, f32 on the device ----
@@ -151,6 +199,12 @@ class FitLoop:
                     mom += [d.mean.float(), d.std.float()]
                 chunks.append(torch.stack(mom, 1).reshape(len(part), 4, -1))
         self.moments = torch.cat(chunks).contiguous()
+        if adapter_trainer is not None:
+            # the condition of every item: its LR image at `resolution`, one channel (the kernel expands it to three)
+            lrs = [_image(it["lr"], res, 1, dev) for it in items]
+            if any(x.shape[0] != 1 for x in lrs):
+                raise ValueError("the adapter's condition is built from 1-channel LR images")
+            self.cond = torch.cat(lrs).contiguous()
         lat_c = int(vae.config.latent_channels)
         f = 2 ** (len(vae.config.block_out_channels) - 1)
         self.latent_shape = (lat_c, res // f, res // f)
@@ -177,6 +231,8 @@ class FitLoop:
         self.lr_ring = torch.zeros(S, dtype=torch.float32, device=dev)
         if use_ema and getattr(trainer, "ema", None) is None:
             trainer.ema_init()  # EMAModel(unet parameters) before the first step
+        if use_ema and adapter_trainer is not None and getattr(adapter_trainer, "ema", None) is None:
+            adapter_trainer.ema_init()
         self.use_ema = bool(use_ema)
         c = _FitConfig(batch=B, accum=accum, max_steps=S, world=self.world, sample_base=self.rank * B, n_items=len(items),
                        latent_channels=lat_c, latent_h=self.latent_shape[1], latent_w=self.latent_shape[2], n_captions=len(names),
@@ -193,11 +249,17 @@ class FitLoop:
         lib.mrisr_fit_num_captures.argtypes = [C.c_void_p]
         self._h = C.c_void_p()
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        L.check(lib.mrisr_fit_create(unet._h, C.byref(c), p(self.moments), p(self.captions), cap_of_item.ctypes.data_as(C.c_void_p),
-                                     self.index.ctypes.data_as(C.c_void_p), ac.ctypes.data_as(C.c_void_p),
-                                     self.lrs.ctypes.data_as(C.c_void_p), self.decays.ctypes.data_as(C.c_void_p),
-                                     p(trainer.exp_avg), p(trainer.exp_avg_sq), p(trainer.ema) if use_ema else None,
-                                     p(self.loss_ring), p(self.grad_norm_ring), p(self.lr_ring), C.byref(self._h)))
+        args = (unet._h, C.byref(c), p(self.moments), p(self.captions), cap_of_item.ctypes.data_as(C.c_void_p),
+                self.index.ctypes.data_as(C.c_void_p), ac.ctypes.data_as(C.c_void_p), self.lrs.ctypes.data_as(C.c_void_p),
+                self.decays.ctypes.data_as(C.c_void_p), p(trainer.exp_avg), p(trainer.exp_avg_sq), p(trainer.ema) if use_ema else None,
+                p(self.loss_ring), p(self.grad_norm_ring), p(self.lr_ring))
+        if adapter_trainer is None:
+            L.check(lib.mrisr_fit_create(*args, C.byref(self._h)))
+        else:
+            at = adapter_trainer
+            self._ad = _FitAdapterArgs(adapter=at.adapter._h.value, cond=self.cond.data_ptr(), res=res, exp_avg=at.exp_avg.data_ptr(),
+                                       exp_avg_sq=at.exp_avg_sq.data_ptr(), ema=at.ema.data_ptr() if use_ema else None)
+            L.check(lib.mrisr_fit_create_adapter(*args, C.byref(self._ad), C.byref(self._h)))
 
     def __del__(self):
         try:
@@ -256,6 +318,22 @@ class FitLoop:
                                              p["target"], p["eps_hr"], p["eps_lr"], p["caption_row"], L.stream_ptr()))
         return out
 
+    def make_condition(self, step: int, micro: int = 0, form: int = 0) -> torch.Tensor:
+        """The adapter condition graph M builds for (step, micro), eagerly: form 0 is the [B, 3, res, res] f32 image (the input of
+        ``Adapter_XL.forward``), form 1 the PixelUnshuffle(8) activation the graph feeds the adapter, [B, res/8, res/8, 192] NHWC
+        in the compute dtype."""
+        if self.adapter_trainer is None:
+            raise ValueError("this loop trains no T2I-Adapter")
+        dev, B, res = self.moments.device, self.batch, int(self.config.resolution)
+        if form == 0:
+            out = torch.empty((B, 3, res, res), dtype=torch.float32, device=dev)
+        elif form == 1:
+            out = torch.empty((B, res // 8, res // 8, 192), dtype=self.adapter_trainer.adapter.compute_dtype, device=dev)
+        else:
+            raise ValueError("form must be 0 (image) or 1 (unshuffled activation)")
+        L.check(L.lib().mrisr_fit_make_condition(self._h, int(step), int(micro), C.c_void_p(out.data_ptr()), int(form), L.stream_ptr()))
+        return out
+
     def item_indices(self, step: int, micro: int = 0) -> np.ndarray:
         return self.index[step * self.accum + micro]
 
@@ -271,6 +349,7 @@ class FitResult:
     validation_paths: List[str] = field(default_factory=list)
     checkpoint_paths: List[str] = field(default_factory=list)
     loop: Optional[FitLoop] = None
+    adapter_trainer: Optional[AdapterTrainer] = None  # the trained T2I-Adapter (fit(adapter=...)); None otherwise
 
 
 class _Accel:
@@ -288,28 +367,41 @@ def _world(process_group) -> Tuple[int, int]:
 
 
 def fit(config: TrainConfig, unet, vae, train_dataset, caption_embeds: Dict[str, torch.Tensor], val_dataset=None, fixed_embeds=None,
-        resume_from: Optional[str] = None, use_ema: bool = False, process_group=None) -> FitResult:
+        resume_from: Optional[str] = None, use_ema: bool = False, process_group=None, adapter=None) -> FitResult:
     """LoRA fine-tuning of ``unet`` (created with ``lora_rank > 0, lora_fused=True`` and loaded) on ``train_dataset`` (items
     ``{'hr', 'lr', 'txt'}``, images in [-1, 1]); ``caption_embeds[txt]`` is the [L, D] text embedding of each prompt ("" for the
     dropped caption).  Writes ``output_dir/metrics.jsonl``, ``validation/step-N.png`` (with ``val_dataset``) and
-    ``checkpoint-N/``; ``resume_from`` is such a checkpoint directory."""
+    ``checkpoint-N/``; ``resume_from`` is such a checkpoint directory.  ``adapter``: a loaded ``Adapter_XL`` trained as well,
+    conditioned on each item's LR image; with a ``lora_rank=0`` UNet it is the only thing trained (the UNet is frozen)."""
     check_config(config, caption_embeds)
     # the whole run on one side stream: graph launches, the all-reduce between them, ring reads, checkpoints and validation are then
     # ordered by the stream itself (the library fences the legacy default stream through an internal one otherwise)
     side = torch.cuda.Stream(device=unet.device)
     side.wait_stream(torch.cuda.current_stream(unet.device))
     with torch.cuda.stream(side):
-        res = _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_embeds, resume_from, use_ema, process_group)
+        res = _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_embeds, resume_from, use_ema, process_group,
+                   adapter)
     torch.cuda.current_stream(unet.device).wait_stream(side)
     return res
 
 
-def _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_embeds, resume_from, use_ema, process_group) -> FitResult:
+def _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_embeds, resume_from, use_ema, process_group,
+         adapter=None) -> FitResult:
     want = L.torch_dtype(L.dtype_id(config.compute_dtype()))
     if unet.compute_dtype != want:
         raise ValueError(f"mixed_precision={config.mixed_precision!r} means compute dtype {want}; the UNet computes in {unet.compute_dtype}")
+    lora = bool(getattr(unet, "lora_rank", 0))
+    if not lora and adapter is None:
+        raise ValueError("the UNet has no LoRA (lora_rank=0) and no adapter was given: nothing to train")
+    if adapter is not None:
+        if not getattr(adapter, "_finalized", False):
+            raise ValueError("load the adapter's weights first (Adapter_XL.load_state_dict)")
+        check_adapter(config, unet, adapter)
+    buckets = trained_buckets(lora, adapter is not None)
     world, rank = _world(process_group)
-    trainer = LoRATrainer(unet, **{**config.optimizer_kwargs(), "lr": base_learning_rate(config, world)}, process_group=process_group)
+    opt = {**config.optimizer_kwargs(), "lr": base_learning_rate(config, world)}
+    trainer = LoRATrainer(unet, **opt, process_group=process_group)
+    atr = AdapterTrainer(adapter, **opt, process_group=process_group) if adapter is not None else None
     S = int(config.max_train_steps)
     start, state = 0, None
     if resume_from is not None:
@@ -317,9 +409,14 @@ def _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_em
             state = json.load(fh)
         if int(state["seed"]) != int(config.seed):
             raise ValueError(f"checkpoint {resume_from} was written by a run with seed {state['seed']}, not {config.seed}")
-        trainer.load_checkpoint(os.path.join(resume_from, WEIGHTS_NAME))  # before the loop handle: it binds the EMA vector's address
+        check_resume_buckets(state, buckets, resume_from)
+        # before the loop handle: it binds the EMA vectors' addresses
+        if lora:
+            trainer.load_checkpoint(os.path.join(resume_from, WEIGHTS_NAME))
+        if atr is not None:
+            atr.load_checkpoint(os.path.join(resume_from, ADAPTER_NAME))
         start = int(state["step"])
-    loop = FitLoop(config, trainer, vae, train_dataset, caption_embeds, world, rank, use_ema)
+    loop = FitLoop(config, trainer, vae, train_dataset, caption_embeds, world, rank, use_ema, adapter_trainer=atr)
     if state is not None:
         for ring, key in ((loop.loss_ring, "losses"), (loop.grad_norm_ring, "grad_norms"), (loop.lr_ring, "lrs")):
             ring[:start].copy_(torch.tensor(state[key][:start], dtype=torch.float32))
@@ -333,7 +430,7 @@ def _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_em
         with open(metrics_path, "a") as fh:
             fh.write(json.dumps(log_configs(config), default=str) + "\n")
     res = FitResult(trainer, np.zeros(S, np.float32), np.zeros(S, np.float32), np.zeros(S, np.float32), start,
-                    metrics_path if writer else None, loop=loop)
+                    metrics_path if writer else None, loop=loop, adapter_trainer=atr)
     val_batch = None
     if val_dataset is not None:
         it = val_dataset[0]
@@ -350,12 +447,17 @@ def _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_em
         for _ in range(config.gradient_accumulation_steps):
             loop.micro()
         if world > 1:
-            all_reduce_sum_(trainer.grad, process_group)
+            if lora:
+                all_reduce_sum_(trainer.grad, process_group)
+            if atr is not None:
+                all_reduce_sum_(atr.grad, process_group)
         loop.apply()
         step = s + 1
-        trainer.step_count = step
-        if use_ema:
-            trainer.ema_steps = step
+        for t in (trainer, atr):
+            if t is not None:
+                t.step_count = step
+                if use_ema:
+                    t.ema_steps = step
         if step % config.logging_steps == 0 or step == S:
             window = slice(last_log, step)
             loss, gn, lr = (r[window].cpu() for r in (loop.loss_ring, loop.grad_norm_ring, loop.lr_ring))  # the one sync of the window
@@ -371,28 +473,37 @@ def _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_em
             from .pipeline import log_validation
             from .schedulers import DDPMScheduler
             panel = log_validation(unet, None, vae, [val_batch], DDPMScheduler(**config.scheduler_kwargs()), torch.float32,
-                                   _Accel(unet.device), fixed_embeds)
+                                   _Accel(unet.device), fixed_embeds, adapter=adapter)
             os.makedirs(os.path.join(out, "validation"), exist_ok=True)
             path = os.path.join(out, "validation", f"step-{step}.png")
             panel.save(path)
             res.validation_paths.append(path)
         if step % config.checkpointing_steps == 0 and writer:
-            res.checkpoint_paths.append(_save(out, step, config, trainer, loop, use_ema))
+            res.checkpoint_paths.append(_save(out, step, config, trainer, loop, use_ema, atr, buckets))
     torch.cuda.current_stream().synchronize()
     res.losses, res.grad_norms, res.lrs = (r.cpu().numpy() for r in (loop.loss_ring, loop.grad_norm_ring, loop.lr_ring))
     res.step = loop.step
     return res
 
 
-def _save(out: str, step: int, config: TrainConfig, trainer: LoRATrainer, loop: FitLoop, use_ema: bool) -> str:
+def _save(out: str, step: int, config: TrainConfig, trainer: LoRATrainer, loop: FitLoop, use_ema: bool,
+          adapter_trainer: Optional[AdapterTrainer] = None, buckets: Optional[List[str]] = None) -> str:
     d = os.path.join(out, f"checkpoint-{step}")
     os.makedirs(d, exist_ok=True)
-    trainer.save_checkpoint(os.path.join(d, WEIGHTS_NAME))  # peft keys; moments and EMA in the .optim.pt next to it
-    if use_ema:
-        trainer.save_checkpoint(os.path.join(d, "ema_" + WEIGHTS_NAME), use_ema=True)
+    buckets = buckets or ["lora"]
+    if "lora" in buckets:
+        trainer.save_checkpoint(os.path.join(d, WEIGHTS_NAME))  # peft keys; moments and EMA in the .optim.pt next to it
+        if use_ema:
+            trainer.save_checkpoint(os.path.join(d, "ema_" + WEIGHTS_NAME), use_ema=True)
+    if adapter_trainer is not None:
+        adapter_trainer.save_checkpoint(os.path.join(d, ADAPTER_NAME))  # the reference module's own keys (Adapter_XL state dict)
+        if use_ema:
+            adapter_trainer.save_checkpoint(os.path.join(d, "ema_" + ADAPTER_NAME), use_ema=True)
     state = {"step": step, "seed": int(config.seed),
              "losses": loop.loss_ring[:step].cpu().tolist(), "grad_norms": loop.grad_norm_ring[:step].cpu().tolist(),
              "lrs": loop.lr_ring[:step].cpu().tolist()}
+    if adapter_trainer is not None:
+        state["buckets"] = buckets  # LoRA-only runs write the file as before: no field means LoRA-only
     with open(os.path.join(d, STATE_NAME), "w") as fh:
         json.dump(state, fh)
     return d

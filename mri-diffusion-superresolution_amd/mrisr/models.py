@@ -281,6 +281,7 @@ class Adapter_XL:
             raise L.MrisrError("mrisr needs an AMD GPU (gfx950); there is no CPU fallback")
         self.channels, self.nums_rb, self.cin, self.ksize, self.use_conv = tuple(channels), nums_rb, cin, ksize, use_conv
         self.device = torch.device(device)
+        self.compute_dtype = L.torch_dtype(L.dtype_id(compute_dtype))
         c = L.AdapterCfg()
         for i, ch in enumerate(channels):
             c.channels[i] = ch

@@ -127,10 +127,11 @@ class Sampler:
 
 @torch.no_grad()
 def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weight_dtype, accelerator, fixed_embeds,
-                   num_inference_steps=20):
+                   num_inference_steps=20, adapter=None):
     """Drop-in for the reference's validation sampler (res_srdiff.py:35-105): same inputs, same PIL panel out.
     The timestep loop is one fused sampler call; the per-step noise is drawn up front from the same global RNG
-    stream, in the same order, as the reference's per-step ``torch.randn_like`` calls."""
+    stream, in the same order, as the reference's per-step ``torch.randn_like`` calls.  ``adapter`` (a T2I-Adapter):
+    its features of the condition image, at the LR image's own size so that they land on the latents, enter every step."""
     from PIL import Image
 
     unet.eval()
@@ -149,8 +150,13 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     n_noise = sum(1 for i in range(len(timesteps)) if (int(timesteps[i + 1]) if i + 1 < len(timesteps) else 0) > 0)
     step_noise = torch.stack([torch.randn_like(latents) for _ in range(n_noise)]) if n_noise else None
     sampler = Sampler(unet, noise_scheduler, controlnet, kind="resshift")
+    feats = None
+    if adapter is not None:
+        cond = control_image if tuple(control_image.shape[-2:]) == tuple(lr_raw.shape[-2:]) else \
+            prepare_condition_image(lr_raw, tuple(lr_raw.shape[-2:]))
+        feats = adapter(cond.to(torch.float32))
     sampler.run(latents, fixed_embeds[0:1], lr_latents=lr_anchor, step_noise=step_noise,
-                controlnet_cond=control_image if controlnet is not None else None)
+                controlnet_cond=control_image if controlnet is not None else None, adapter_features=feats)
     gen_vis = decode_to_vis(latents.to(weight_dtype), vae)
     hr_vis = decode_to_vis(hr_raw, vae, is_latent=False)
     lr_vis = decode_to_vis(lr_raw, vae, is_latent=False)

@@ -163,6 +163,25 @@ int mrisr_sampler_set_range(mrisr_sampler* s, int first_step, int last_step);
  * (the default, as in the SD-1.5 scheduler config). */
 int mrisr_sampler_set_clip(mrisr_sampler* s, float clip_sample_range);
 
+/* ---- classifier-free guidance (off unless mrisr_sampler_run_guided is called) ----------------------
+ * A guided step of B slices is ONE forward of 2B rows inside the same captured graph plus one fused step kernel.  Row order is
+ * diffusers': rows 0..B-1 of ehs2 / cond2 / intrablock2 (and of the network's output) are the UNCONDITIONAL half, rows B..2B-1 the
+ * CONDITIONAL half.  Per element, with g = guidance_scale and phi = guidance_rescale (Lin et al., "Common Diffusion Noise
+ * Schedules and Sample Steps are Flawed", sec. 3.4):
+ *     e = eps_u + g (eps_c - eps_u)
+ *     phi > 0:  e = e (phi std_b(eps_c) / std_b(e) + (1 - phi))     std_b: over the C*h*w elements of sample b, unbiased (n-1)
+ *                                                                    like torch.std; a sample with std_b(e) == 0 is left as it is
+ *     x = the sampler's own DDIM / Res-SRDiff / DDPM update of x with e
+ * latents, lr_latents and the step_noise slabs stay [B]: both halves share them.  g = 1 gives the conditional prediction, so
+ * the defaults (g = 1, phi = 0) make a guided run a dearer form of the plain one.  The values are read by the next
+ * mrisr_sampler_run_guided; plain mrisr_sampler_run ignores them.  phi must lie in [0, 1]. */
+int mrisr_sampler_set_guidance(mrisr_sampler* s, float guidance_scale, float guidance_rescale);
+/* As mrisr_sampler_run, with ehs2 [2B, L, D], cond2 [2B, 3, 8h, 8w] or NULL and every intrablock2 feature [2B, ...]; C*h*w of the
+ * latents must be a multiple of 4.  ControlNet runs on both halves.  mrisr_sampler_set_range keeps its meaning. */
+int mrisr_sampler_run_guided(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents,
+                             const mrisr_tensor* step_noise, const mrisr_tensor* ehs2, const mrisr_tensor* cond2,
+                             const mrisr_tensor* intrablock2, int n_intrablock, int use_graph, void* stream);
+
 /* ---- T2I-Adapter training (in BASELINE config 3 the adapter runs, and is differentiated, every step)
  * Same ownership model as the LoRA step: the caller owns ONE flat f32 vector of all adapter parameters (PyTorch layouts,
  * state-dict keys via tensor_info) and its gradient.  After train_prepare / train_bind, mrisr_adapter_forward keeps what the
@@ -406,6 +425,15 @@ int mrisr_op_attention(const mrisr_tensor* q, const mrisr_tensor* k, const mrisr
 /* gradients of mrisr_op_attention (bf16, flash path): dq [B,N,H*d], dk, dv [B,Nk,H*d] for an upstream dout [B,N,H*d] */
 int mrisr_op_attention_bwd(const mrisr_tensor* q, const mrisr_tensor* k, const mrisr_tensor* v, const mrisr_tensor* dout,
                            int heads, mrisr_tensor* dq, mrisr_tensor* dk, mrisr_tensor* dv, void* stream);
+
+
+/* the fused guided step of mrisr_sampler_run_guided alone: x [B,C,h,w] f32 (in place), x2 [2B,C,h,w] f32 (receives the new x in
+ * both halves), eps2 [2B,C,h,w] f32 (unconditional rows, then conditional), lr / noise [B,C,h,w] f32 or NULL (one noise slab),
+ * coef_row_host: the step kind's coefficient row on the host - DDIM {cx, ce}; RESSHIFT {sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sigma};
+ * DDPM {1/sqrt(abar_t), sqrt(1-abar_t)/sqrt(abar_t), x0 coefficient, x_t coefficient, sigma} */
+int mrisr_op_guided_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const mrisr_tensor* eps2, const mrisr_tensor* lr,
+                         const mrisr_tensor* noise, const float* coef_row_host, float clip, float guidance_scale,
+                         float guidance_rescale, void* stream);
 
 #ifdef __cplusplus
 }

@@ -164,8 +164,10 @@ struct mrisr_sampler {
     mrisr_model* cnet = nullptr;
     int kind = 0, n_steps = 0, first = 0, last = 0;
     float clip = 0.f;
+    float guidance_scale = 1.f, guidance_rescale = 0.f;  // classifier-free guidance of mrisr_sampler_run_guided
     std::vector<float> sigma;  // host copy of each step's noise coefficient (which steps read a step_noise slab)
     DevBuf d_ts, d_coef, d_step, d_curt, d_eps;
+    DevBuf d_x2;  // guided runs: the [2B] f32 latents the forwards read (both halves = the state; the guided step keeps them current)
     DevBuf tp_unet, tp_cnet;  // per-run time-embedding tables [scratch | n_steps x tproj_total] (f32)
     std::vector<std::unique_ptr<DevBuf>> res_bufs;   // ControlNet -> UNet residuals (NHWC, compute dtype)
     std::vector<std::unique_ptr<DevBuf>> intra_bufs;  // adapter features converted once
@@ -260,9 +262,20 @@ int mrisr_sampler_set_clip(mrisr_sampler* s, float clip_sample_range) {
     return 0;
 }
 
-int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents,
-                      const mrisr_tensor* step_noise, const mrisr_tensor* ehs, const mrisr_tensor* cond,
-                      const mrisr_tensor* intrablock, int n_intrablock, int use_graph, void* stream) {
+int mrisr_sampler_set_guidance(mrisr_sampler* s, float guidance_scale, float guidance_rescale) {
+    MRISR_REQUIRE(s, "null sampler");
+    MRISR_REQUIRE(std::isfinite(guidance_scale), "guidance_scale must be finite");
+    MRISR_REQUIRE(guidance_rescale >= 0.f && guidance_rescale <= 1.f, "guidance_rescale must lie in [0, 1]");
+    s->guidance_scale = guidance_scale;  // passed to the step kernel by value: part of the graph key
+    s->guidance_rescale = guidance_rescale;
+    return 0;
+}
+
+// the body of mrisr_sampler_run (guided = false: B rows everywhere) and mrisr_sampler_run_guided (the forwards see NB = 2B rows:
+// ehs / cond / intrablock carry 2B, the latents are read from the staging buffer; the state, the LR anchor and the noise stay [B])
+static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents,
+                            const mrisr_tensor* step_noise, const mrisr_tensor* ehs, const mrisr_tensor* cond,
+                            const mrisr_tensor* intrablock, int n_intrablock, int use_graph, void* stream, bool guided) {
     API_BEGIN
     MRISR_REQUIRE(s && latents && ehs, "null argument");
     MRISR_REQUIRE(latents->ndim == 4 && latents->dtype == MRISR_F32 && latents->layout == MRISR_NCHW, "latents: f32 NCHW");
@@ -273,18 +286,26 @@ int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tenso
     Model& U = *s->unet;
     const int B = (int)latents->shape[0], h = (int)latents->shape[2], w = (int)latents->shape[3];
     const int L = (int)ehs->shape[1];
-    const long long n = (long long)B * latents->shape[1] * h * w;
+    const int NB = guided ? 2 * B : B;  // rows of every forward
+    const long long per = (long long)latents->shape[1] * h * w;
+    const long long n = (long long)B * per;
     const int cdt = U.cfg.compute_dtype;
     const int esz = dtype_size(cdt);
     // every operand the step kernels index is checked against the latents here: the kernels themselves read
     // lr[i], noise[step * n + i] for i < n without bounds
     auto numel = [](const mrisr_tensor* t) { long long k = 1; for (int i = 0; i < t->ndim; ++i) k *= t->shape[i]; return k; };
     MRISR_REQUIRE(latents->shape[1] == U.cfg.in_channels, "latents channels vs the UNet's in_channels");
-    MRISR_REQUIRE(ehs->ndim == 3 && ehs->shape[0] == B && ehs->shape[2] == U.cfg.cross_attention_dim,
-                  "encoder_hidden_states must be [B, L, cross_attention_dim] with the latents' batch");
+    if (!guided)
+        MRISR_REQUIRE(ehs->ndim == 3 && ehs->shape[0] == B && ehs->shape[2] == U.cfg.cross_attention_dim,
+                      "encoder_hidden_states must be [B, L, cross_attention_dim] with the latents' batch");
+    else
+        MRISR_REQUIRE(ehs->ndim == 3 && ehs->shape[0] == NB && ehs->shape[2] == U.cfg.cross_attention_dim,
+                      "guided run: encoder_hidden_states must be [2B, L, cross_attention_dim]: B unconditional rows, then B conditional rows");
+    if (guided) MRISR_REQUIRE(B > 0 && per % 4 == 0, "guided run: C*h*w of the latents must be a multiple of 4");
     if (lr_latents) MRISR_REQUIRE(lr_latents->dtype == MRISR_F32 && numel(lr_latents) == n, "lr_latents: f32, same shape as latents");
-    if (cond) MRISR_REQUIRE(cond->ndim == 4 && cond->shape[0] == B && cond->shape[2] == 8 * h && cond->shape[3] == 8 * w,
-                            "controlnet_cond must be [B, C, 8h, 8w] with the latents' batch");
+    if (cond) MRISR_REQUIRE(cond->ndim == 4 && cond->shape[0] == NB && cond->shape[2] == 8 * h && cond->shape[3] == 8 * w,
+                            guided ? "guided run: controlnet_cond must be [2B, C, 8h, 8w] (the [B] images twice)"
+                                   : "controlnet_cond must be [B, C, 8h, 8w] with the latents' batch");
     {
         int need = 0;  // slabs read: one per step, indexed by the step's position in the schedule, when its sigma != 0
         for (int i = s->first; i < s->last; ++i)
@@ -296,7 +317,9 @@ int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tenso
         }
     }
     for (int i = 0; i < n_intrablock; ++i)
-        MRISR_REQUIRE(intrablock[i].ndim == 4 && intrablock[i].shape[0] == B, "adapter features must carry the latents' batch");
+        MRISR_REQUIRE(intrablock[i].ndim == 4 && intrablock[i].shape[0] == NB,
+                      guided ? "guided run: adapter features must be [2B, ...] (the [B] features twice)"
+                             : "adapter features must carry the latents' batch");
 
     if (use_graph && user == nullptr) {
         // the legacy default stream cannot be captured: run on an internal stream fenced by events
@@ -312,13 +335,13 @@ int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tenso
 
     // ---- one-time (per run) timestep-invariant work: context projections, condition embedding, features ----
     TRY(gemm_prepare());
-    TRY(U.set_context(ehs, B, h, w, st));
+    TRY(U.set_context(ehs, NB, h, w, st));
     std::vector<mrisr_tensor> down_t;
     mrisr_tensor mid_t{};
     int ns = 0;
     if (s->cnet) {
         Model& C = *s->cnet;
-        TRY(C.set_context(ehs, B, h, w, st));
+        TRY(C.set_context(ehs, NB, h, w, st));
         TRY(C.set_cond(cond, L, st));
         ns = C.num_skips();
         s->res_bufs.resize(ns + 1);
@@ -326,7 +349,7 @@ int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tenso
         for (int k = 0; k <= ns; ++k) {
             mrisr_tensor t{};
             t.ndim = 4; t.dtype = cdt; t.layout = MRISR_NHWC;
-            C.skip_shape(k, B, h, w, t.shape);
+            C.skip_shape(k, NB, h, w, t.shape);
             if (!s->res_bufs[k]) s->res_bufs[k].reset(new DevBuf());
             TRY(s->res_bufs[k]->reserve((size_t)t.shape[0] * t.shape[1] * t.shape[2] * t.shape[3] * esz, false));
             t.data = s->res_bufs[k]->p;
@@ -348,7 +371,13 @@ int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tenso
         intra[i].layout = MRISR_NHWC;
         intra[i].dtype = cdt;
     }
-    TRY(s->d_eps.reserve((size_t)n * sizeof(float), false));
+    TRY(s->d_eps.reserve((size_t)NB * per * sizeof(float), false));
+    if (guided) {
+        // [x; x] once per run; from then on the guided step itself writes every new state to both halves
+        TRY(s->d_x2.reserve((size_t)2 * n * sizeof(float), false));
+        MRISR_CHECK_HIP(hipMemcpyAsync(s->d_x2.p, latents->data, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        MRISR_CHECK_HIP(hipMemcpyAsync(static_cast<float*>(s->d_x2.p) + n, latents->data, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
     // the time embedding of every step of this run, once (it depends on the timestep only): sinusoid -> MLP -> the 22 per-resnet projections for
     // all rows at once instead of three GEMVs over 50 MB of weights in every step.  MRISR_TEMB_TABLE=0 / mrisr_debug_temb_table(0): per step.
     struct TableGuard {  // the models must not keep pointing at this sampler's table after the run (plain forward calls compute their own)
@@ -375,7 +404,9 @@ int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tenso
 
     mrisr_tensor tt{};
     tt.data = s->d_curt.p; tt.dtype = MRISR_I64; tt.ndim = 0;
-    mrisr_tensor eps_t = *latents;
+    mrisr_tensor xin = *latents;  // what the forwards read
+    if (guided) { xin.shape[0] = NB; xin.data = s->d_x2.p; }
+    mrisr_tensor eps_t = xin;
     eps_t.data = s->d_eps.p;
     const int* step = static_cast<const int*>(s->d_step.p);
 
@@ -383,10 +414,14 @@ int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tenso
         hipLaunchKernelGGL(load_t_kernel, dim3(1), dim3(1), 0, st, static_cast<long long*>(s->d_curt.p),
                            static_cast<const long long*>(s->d_ts.p), step);
         if (s->cnet)
-            TRY(s->cnet->forward_controlnet(latents, &tt, nullptr, nullptr, 1.0f, down_t.data(), ns, &mid_t, st));
-        TRY(U.forward_unet(latents, &tt, nullptr, s->cnet ? down_t.data() : nullptr, ns, s->cnet ? &mid_t : nullptr,
+            TRY(s->cnet->forward_controlnet(&xin, &tt, nullptr, nullptr, 1.0f, down_t.data(), ns, &mid_t, st));
+        TRY(U.forward_unet(&xin, &tt, nullptr, s->cnet ? down_t.data() : nullptr, ns, s->cnet ? &mid_t : nullptr,
                            intra.data(), n_intrablock, &eps_t, st));
-        if (s->kind == MRISR_STEP_DDIM)
+        if (guided)
+            TRY(launch_guided_step(s->kind, (float*)latents->data, (float*)s->d_x2.p, (const float*)s->d_eps.p,
+                                   lr_latents ? (const float*)lr_latents->data : nullptr, step_noise ? (const float*)step_noise->data : nullptr,
+                                   (const float*)s->d_coef.p, step, s->clip, s->guidance_scale, s->guidance_rescale, B, per, st));
+        else if (s->kind == MRISR_STEP_DDIM)
             TRY(launch_ddim_step((float*)latents->data, (const float*)s->d_eps.p, (const float*)s->d_coef.p, step, n, st));
         else if (s->kind == MRISR_STEP_DDPM)
             TRY(launch_ddpm_step((float*)latents->data, (const float*)s->d_eps.p, step_noise ? (const float*)step_noise->data : nullptr,
@@ -413,6 +448,10 @@ int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tenso
             key += kb;
             for (auto& rb : s->res_bufs) { snprintf(kb, sizeof(kb), ",r%p", rb ? rb->p : nullptr); key += kb; }
             for (auto& f : intra) { snprintf(kb, sizeof(kb), ",f%p", f.data); key += kb; }
+            if (guided) {  // the 2B geometry, the staging buffer and the two scalars the guided step takes by value
+                snprintf(kb, sizeof(kb), ",G%p,%a,%a", s->d_x2.p, (double)s->guidance_scale, (double)s->guidance_rescale);
+                key += kb;
+            }
         }
         if (!s->exec || s->graph_key != key) {
             if (s->exec) { (void)hipGraphExecDestroy(s->exec); s->exec = nullptr; }
@@ -433,6 +472,49 @@ int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tenso
         MRISR_CHECK_HIP(hipEventRecord(s->ev_out, st));
         MRISR_CHECK_HIP(hipStreamWaitEvent(user, s->ev_out, 0));
     }
+    return 0;
+    API_END
+}
+
+int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents,
+                      const mrisr_tensor* step_noise, const mrisr_tensor* ehs, const mrisr_tensor* cond,
+                      const mrisr_tensor* intrablock, int n_intrablock, int use_graph, void* stream) {
+    return sampler_run_impl(s, latents, lr_latents, step_noise, ehs, cond, intrablock, n_intrablock, use_graph, stream, false);
+}
+int mrisr_sampler_run_guided(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents,
+                             const mrisr_tensor* step_noise, const mrisr_tensor* ehs2, const mrisr_tensor* cond2,
+                             const mrisr_tensor* intrablock2, int n_intrablock, int use_graph, void* stream) {
+    return sampler_run_impl(s, latents, lr_latents, step_noise, ehs2, cond2, intrablock2, n_intrablock, use_graph, stream, true);
+}
+
+// the guided step alone, on caller buffers (parity test): coef_row_host is this step kind's coefficient row (2 / 4 / 5 floats)
+int mrisr_op_guided_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const mrisr_tensor* eps2, const mrisr_tensor* lr,
+                         const mrisr_tensor* noise, const float* coef_row_host, float clip, float guidance_scale,
+                         float guidance_rescale, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(x && x2 && eps2 && coef_row_host, "guided step: null argument");
+    MRISR_REQUIRE(step_kind >= MRISR_STEP_DDIM && step_kind <= MRISR_STEP_DDPM, "guided step: unknown step kind");
+    auto numel = [](const mrisr_tensor* t) { long long k = 1; for (int i = 0; i < t->ndim; ++i) k *= t->shape[i]; return k; };
+    MRISR_REQUIRE(x->ndim == 4 && x->dtype == MRISR_F32 && x->shape[0] > 0, "guided step: x must be f32 [B, C, h, w]");
+    const int B = (int)x->shape[0];
+    const long long n = numel(x), per = n / B;
+    MRISR_REQUIRE(x2->dtype == MRISR_F32 && numel(x2) == 2 * n, "guided step: the staging buffer must be f32 [2B, C, h, w]");
+    MRISR_REQUIRE(eps2->dtype == MRISR_F32 && numel(eps2) == 2 * n, "guided step: eps2 must be f32 [2B, C, h, w]");
+    if (lr) MRISR_REQUIRE(lr->dtype == MRISR_F32 && numel(lr) == n, "guided step: lr must be f32 [B, C, h, w]");
+    if (noise) MRISR_REQUIRE(noise->dtype == MRISR_F32 && numel(noise) == n, "guided step: noise must be one f32 [B, C, h, w] slab");
+    hipStream_t st = (hipStream_t)stream;
+    const int width = step_kind == MRISR_STEP_DDIM ? 2 : (step_kind == MRISR_STEP_RESSHIFT ? 4 : 5);
+    float row[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    std::copy(coef_row_host, coef_row_host + width, row);
+    DevBuf d_row, d_step;
+    TRY(d_row.reserve(sizeof(row), false));
+    TRY(d_step.reserve(16, true));  // zeroed: step 0 = the one row, the one noise slab
+    MRISR_CHECK_HIP(hipMemcpyAsync(d_row.p, row, sizeof(row), hipMemcpyHostToDevice, st));
+    MRISR_CHECK_HIP(hipMemsetAsync(d_step.p, 0, 16, st));
+    TRY(launch_guided_step(step_kind, (float*)x->data, (float*)x2->data, (const float*)eps2->data, lr ? (const float*)lr->data : nullptr,
+                           noise ? (const float*)noise->data : nullptr, (const float*)d_row.p, (const int*)d_step.p, clip,
+                           guidance_scale, guidance_rescale, B, per, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
     API_END
 }

@@ -444,6 +444,10 @@ int launch_ddpm_step(float* x, const float* eps, const float* noise, const float
 int launch_resshift_step(float* x, const float* eps, const float* lr, const float* noise, const float* coef_table,
                          const int* step_idx, long long n, hipStream_t st);
 int launch_advance_step(int* step_idx, hipStream_t st);
+//   classifier-free guidance: eps2 = [uncond rows; cond rows] of a [2B] forward -> guided (and rescaled) eps -> the step above of kind
+//   `kind`; the new x goes to x [B] and to both halves of the staging buffer x2 [2B].  `per` = elements per sample (multiple of 4)
+int launch_guided_step(int kind, float* x, float* x2, const float* eps2, const float* lr, const float* noise, const float* coef_table,
+                       const int* step_idx, float clip, float g, float phi, int B, long long per, hipStream_t st);
 //   forward shift (reference res_srdiff.py:7-25): per-sample alpha from table[t[b]]
 int launch_resshift_forward(const float* hr, const float* lr, const float* noise, const float* alphas_cumprod,
                             const long long* t, int t_is_scalar, float* out, int B, long long per_sample,

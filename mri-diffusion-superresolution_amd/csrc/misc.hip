@@ -1,5 +1,6 @@
 // Small / bandwidth-bound kernels: time-embedding GEMV, direct convolutions for tiny channel counts,
 // NCHW<->NHWC boundary conversion, weight packers, and the fused sampler steps.
+#include "../../include/mrisr.h"  // mrisr_step_kind (the guided step serves all three)
 #include "common.h"
 #include "prof.h"
 
@@ -869,6 +870,204 @@ int launch_ddpm_step(float* x, const float* eps, const float* noise, const float
                      long long n, hipStream_t st) {
     ProfScope ps("sampler_step", 0.0, 16.0 * n, st);
     hipLaunchKernelGGL(ddpm_step_kernel, dim3(nblocks(n)), dim3(256), 0, st, x, eps, noise, coef_table, step_idx, clip, n);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+// ------------------------------------------------------------------------------------------------
+// guided step (classifier-free guidance): ONE launch that combines the two halves of a [2B] UNet output,
+//   e = eps_u + g (eps_c - eps_u);   phi > 0:  e *= phi std_b(eps_c) / std_b(e) + (1 - phi)   (per sample b, n-1 as torch.std),
+// applies the DDIM / Res-SRDiff / DDPM update above to x with e, and writes the new x to the caller's latents and to both halves
+// of the [2B] staging buffer the next forward reads.  eps2 rows 0..B-1 are unconditional, B..2B-1 conditional (diffusers' order).
+//   phi == 0: grid-stride over float4 pieces.
+//   phi  > 0: one workgroup of 1024 threads per sample; up to 16 Ki elements per sample both eps rows stay in registers (ITEMS
+//             float4 pieces per thread): means, then centred sums of squares (wave shuffle -> LDS over the 16 waves), then the
+//             update - eps2 is read once.  Larger samples take the re-reading kernel (three passes over eps2; correct, not fast).
+// A sample whose guided prediction has no spread (centred sum of squares below f32 resolution of its mean, or per == 1) is left
+// unrescaled, so an all-equal prediction cannot produce inf / NaN.
+// ------------------------------------------------------------------------------------------------
+struct StepRow { float a, b, c, d, sig; };
+__device__ __forceinline__ StepRow load_step_row(int kind, const float* coef, int s) {
+    StepRow r{0.f, 0.f, 0.f, 0.f, 0.f};
+    if (kind == MRISR_STEP_DDIM) { r.a = coef[2 * s]; r.b = coef[2 * s + 1]; }
+    else if (kind == MRISR_STEP_RESSHIFT) { r.a = coef[4 * s]; r.b = coef[4 * s + 1]; r.c = coef[4 * s + 2]; r.sig = coef[4 * s + 3]; }
+    else { r.a = coef[8 * s]; r.b = coef[8 * s + 1]; r.c = coef[8 * s + 2]; r.d = coef[8 * s + 3]; r.sig = coef[8 * s + 4]; }
+    return r;
+}
+// the arithmetic of ddim_step_kernel / resshift_step_kernel / ddpm_step_kernel, one element
+__device__ __forceinline__ float step_value(int kind, const StepRow& r, float clip, float xv, float e, float l, float nz, bool noisy) {
+    if (kind == MRISR_STEP_DDIM) return r.a * xv + r.b * e;
+    float v;
+    if (kind == MRISR_STEP_RESSHIFT) {
+        const float x0 = (xv - (1.f - r.a) * l - r.b * e) / r.a;
+        v = r.c * x0 + (1.f - r.c) * l;
+    } else {
+        float x0 = r.a * xv - r.b * e;
+        if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
+        v = r.c * x0 + r.d * xv;
+    }
+    if (noisy) v += r.sig * nz;
+    return v;
+}
+__device__ __forceinline__ float4 step_value4(int kind, const StepRow& r, float clip, float4 xv, float4 e, float4 l, float4 nz, bool noisy) {
+    return make_float4(step_value(kind, r, clip, xv.x, e.x, l.x, nz.x, noisy), step_value(kind, r, clip, xv.y, e.y, l.y, nz.y, noisy),
+                       step_value(kind, r, clip, xv.z, e.z, l.z, nz.z, noisy), step_value(kind, r, clip, xv.w, e.w, l.w, nz.w, noisy));
+}
+__device__ __forceinline__ float4 guide4(float4 eu, float4 ec, float g) {
+    return make_float4(eu.x + g * (ec.x - eu.x), eu.y + g * (ec.y - eu.y), eu.z + g * (ec.z - eu.z), eu.w + g * (ec.w - eu.w));
+}
+__device__ __forceinline__ float sum4(float4 v) { return (v.x + v.y) + (v.z + v.w); }
+__device__ __forceinline__ float ssq4(float4 v, float m) {
+    const float a = v.x - m, b = v.y - m, c = v.z - m, d = v.w - m;
+    return (a * a + b * b) + (c * c + d * d);
+}
+__device__ __forceinline__ float4 scale4(float4 v, float f) { return make_float4(v.x * f, v.y * f, v.z * f, v.w * f); }
+// x, staging half 0, staging half 1 of one float4 piece
+__device__ __forceinline__ void store_x3(float* x, float* x2, long long n, long long i4, float4 v) {
+    reinterpret_cast<float4*>(x)[i4] = v;
+    reinterpret_cast<float4*>(x2)[i4] = v;
+    reinterpret_cast<float4*>(x2 + n)[i4] = v;
+}
+
+__global__ __launch_bounds__(256) void guided_step_kernel(int kind, float* x, float* x2, const float* eps2, const float* lr,
+                                                          const float* noise_base, const float* coef, const int* step, float clip,
+                                                          float g, long long n) {
+    const int s = *step;
+    const StepRow r = load_step_row(kind, coef, s);
+    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256) {
+        const float4 eu = reinterpret_cast<const float4*>(eps2)[i], ec = reinterpret_cast<const float4*>(eps2 + n)[i];
+        const float4 xv = reinterpret_cast<const float4*>(x)[i];
+        const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
+        const float4 nz = noise ? reinterpret_cast<const float4*>(noise)[i] : z4;
+        store_x3(x, x2, n, i, step_value4(kind, r, clip, xv, guide4(eu, ec, g), l, nz, noise != nullptr));
+    }
+}
+
+constexpr int GS_THREADS = 1024;
+// sums of (a, b) over the workgroup, the same value in every thread; `red` holds one pair per wave
+__device__ __forceinline__ void block_sum2(float& a, float& b, float* red) {
+    a = wsum(a);
+    b = wsum(b);
+    __syncthreads();  // the previous round's readers are done with `red`
+    if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = a; red[2 * (threadIdx.x >> 6) + 1] = b; }
+    __syncthreads();
+    float sa = 0.f, sb = 0.f;
+#pragma unroll
+    for (int w = 0; w < GS_THREADS / 64; ++w) { sa += red[2 * w]; sb += red[2 * w + 1]; }
+    a = sa;
+    b = sb;
+}
+// phi std(eps_c) / std(e) + (1 - phi) from the centred sums of squares (the n-1 of both estimates cancels)
+__device__ __forceinline__ float rescale_factor(float qc, float qe, float me, int per, float phi) {
+    if (per < 2 || !(qe > 1e-12f * (float)per * me * me) || !(qe > 0.f)) return 1.f;
+    const float f = phi * sqrtf(qc / qe) + (1.f - phi);
+    return f <= 3.0e38f ? f : 1.f;
+}
+
+template <int ITEMS>
+__global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(int kind, float* x, float* x2, const float* eps2, const float* lr,
+                                                                         const float* noise_base, const float* coef, const int* step,
+                                                                         float clip, float g, float phi, int B, int per) {
+    __shared__ float red[2 * GS_THREADS / 64];
+    const int s = *step;
+    const StepRow r = load_step_row(kind, coef, s);
+    const long long n = (long long)B * per;
+    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
+    const long long base4 = (long long)blockIdx.x * (per >> 2);
+    const int per4 = per >> 2;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 e[ITEMS], c[ITEMS];
+    float sc = 0.f, se = 0.f;
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int j = threadIdx.x + k * GS_THREADS;
+        e[k] = z4; c[k] = z4;
+        if (j < per4) {
+            const float4 eu = reinterpret_cast<const float4*>(eps2)[base4 + j];
+            c[k] = reinterpret_cast<const float4*>(eps2 + n)[base4 + j];
+            e[k] = guide4(eu, c[k], g);
+            sc += sum4(c[k]); se += sum4(e[k]);
+        }
+    }
+    block_sum2(sc, se, red);
+    const float mc = sc / (float)per, me = se / (float)per;
+    float qc = 0.f, qe = 0.f;
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k)
+        if (threadIdx.x + k * GS_THREADS < per4) { qc += ssq4(c[k], mc); qe += ssq4(e[k], me); }
+    block_sum2(qc, qe, red);
+    const float f = rescale_factor(qc, qe, me, per, phi);
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int j = threadIdx.x + k * GS_THREADS;
+        if (j < per4) {
+            const long long i = base4 + j;
+            const float4 xv = reinterpret_cast<const float4*>(x)[i];
+            const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
+            const float4 nz = noise ? reinterpret_cast<const float4*>(noise)[i] : z4;
+            store_x3(x, x2, n, i, step_value4(kind, r, clip, xv, scale4(e[k], f), l, nz, noise != nullptr));
+        }
+    }
+}
+// samples too large for the register file: the same three passes, each re-reading eps2
+__global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_reread_kernel(int kind, float* x, float* x2, const float* eps2, const float* lr,
+                                                                                const float* noise_base, const float* coef, const int* step,
+                                                                                float clip, float g, float phi, int B, int per) {
+    __shared__ float red[2 * GS_THREADS / 64];
+    const int s = *step;
+    const StepRow r = load_step_row(kind, coef, s);
+    const long long n = (long long)B * per;
+    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
+    const long long base4 = (long long)blockIdx.x * (per >> 2);
+    const int per4 = per >> 2;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4* pu = reinterpret_cast<const float4*>(eps2) + base4;
+    const float4* pc = reinterpret_cast<const float4*>(eps2 + n) + base4;
+    float sc = 0.f, se = 0.f;
+    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 c = pc[j]; sc += sum4(c); se += sum4(guide4(pu[j], c, g)); }
+    block_sum2(sc, se, red);
+    const float mc = sc / (float)per, me = se / (float)per;
+    float qc = 0.f, qe = 0.f;
+    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 c = pc[j]; qc += ssq4(c, mc); qe += ssq4(guide4(pu[j], c, g), me); }
+    block_sum2(qc, qe, red);
+    const float f = rescale_factor(qc, qe, me, per, phi);
+    for (int j = threadIdx.x; j < per4; j += GS_THREADS) {
+        const long long i = base4 + j;
+        const float4 xv = reinterpret_cast<const float4*>(x)[i];
+        const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
+        const float4 nz = noise ? reinterpret_cast<const float4*>(noise)[i] : z4;
+        store_x3(x, x2, n, i, step_value4(kind, r, clip, xv, scale4(guide4(pu[j], pc[j], g), f), l, nz, noise != nullptr));
+    }
+}
+int launch_guided_step(int kind, float* x, float* x2, const float* eps2, const float* lr, const float* noise, const float* coef_table,
+                       const int* step_idx, float clip, float g, float phi, int B, long long per, hipStream_t st) {
+    MRISR_REQUIRE(kind >= MRISR_STEP_DDIM && kind <= MRISR_STEP_DDPM, "guided step: unknown step kind");
+    MRISR_REQUIRE(x && x2 && eps2 && coef_table && step_idx && B > 0 && per > 0, "guided step: null operand");
+    MRISR_REQUIRE(per % 4 == 0 && per < (1ll << 31), "guided step: the per-sample size must be a multiple of 4");
+    MRISR_REQUIRE(phi >= 0.f && phi <= 1.f, "guided step: guidance_rescale must lie in [0, 1]");
+    MRISR_REQUIRE(kind != MRISR_STEP_RESSHIFT || lr, "guided step: Res-SRDiff needs the LR anchor latents");
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    MRISR_REQUIRE(al16(x) && al16(x2) && al16(eps2) && al16(lr) && al16(noise), "guided step: operands must be 16-byte aligned");
+    const long long n = (long long)B * per;
+    if (kind != MRISR_STEP_RESSHIFT) lr = nullptr;
+    if (kind == MRISR_STEP_DDIM) noise = nullptr;
+    ProfScope ps("sampler_step", 0.0, 28.0 * n + (lr ? 4.0 * n : 0.0), st);
+    if (phi == 0.f) {
+        hipLaunchKernelGGL(guided_step_kernel, dim3(nblocks(n >> 2)), dim3(256), 0, st, kind, x, x2, eps2, lr, noise, coef_table, step_idx,
+                           clip, g, n);
+    } else {
+#define MRISR_GS(ITEMS)                                                                                                              \
+    hipLaunchKernelGGL(guided_step_rescale_kernel<ITEMS>, dim3(B), dim3(GS_THREADS), 0, st, kind, x, x2, eps2, lr, noise, coef_table, \
+                       step_idx, clip, g, phi, B, (int)per)
+        if (per <= 4 * GS_THREADS) MRISR_GS(1);
+        else if (per <= 8 * GS_THREADS) MRISR_GS(2);
+        else if (per <= 16 * GS_THREADS) MRISR_GS(4);
+        else
+            hipLaunchKernelGGL(guided_step_rescale_reread_kernel, dim3(B), dim3(GS_THREADS), 0, st, kind, x, x2, eps2, lr, noise,
+                               coef_table, step_idx, clip, g, phi, B, (int)per);
+#undef MRISR_GS
+    }
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }

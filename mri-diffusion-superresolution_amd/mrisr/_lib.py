@@ -59,6 +59,7 @@ EXPORTS = [
     "mrisr_model_skip_shape", "mrisr_controlnet_forward", "mrisr_controlnet_set_cond", "mrisr_adapter_create",
     "mrisr_adapter_destroy", "mrisr_adapter_set_param", "mrisr_adapter_finalize", "mrisr_adapter_forward",
     "mrisr_resshift_forward", "mrisr_sampler_create", "mrisr_sampler_destroy", "mrisr_sampler_run", "mrisr_sampler_set_range", "mrisr_sampler_set_clip",
+    "mrisr_sampler_set_guidance", "mrisr_sampler_run_guided", "mrisr_op_guided_step",
     "mrisr_adapter_train_prepare", "mrisr_adapter_train_num_trainable", "mrisr_adapter_train_num_tensors",
     "mrisr_adapter_train_tensor_info", "mrisr_adapter_train_bind", "mrisr_adapter_train_refresh", "mrisr_adapter_backward", "mrisr_adapter_backward_level", "mrisr_adapter_train_level_range",
     "mrisr_vae_create", "mrisr_vae_destroy", "mrisr_vae_set_param", "mrisr_vae_num_params", "mrisr_vae_finalize",
@@ -91,6 +92,9 @@ def lib() -> C.CDLL:
         L.mrisr_adapter_destroy.restype = None
         L.mrisr_sampler_destroy.restype = None
         L.mrisr_sampler_set_clip.argtypes = [C.c_void_p, C.c_float]
+        L.mrisr_sampler_set_guidance.argtypes = [C.c_void_p, C.c_float, C.c_float]
+        L.mrisr_op_guided_step.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                           C.c_float, C.c_float, C.c_void_p]
         L.mrisr_resize_scratch_bytes.restype = C.c_size_t
         L.mrisr_resize_scratch_bytes.argtypes = [C.c_int] * 6
         L.mrisr_resize_slices.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

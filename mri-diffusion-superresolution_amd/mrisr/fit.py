@@ -76,6 +76,20 @@ def check_config(config: TrainConfig, caption_embeds: Optional[Dict[str, torch.T
         raise ValueError("lr_warmup_steps must be >= 0")
 
 
+def check_validation_guidance(guidance_scale: float, guidance_rescale: float,
+                              caption_embeds: Optional[Dict[str, torch.Tensor]]) -> bool:
+    """What ``fit(validation_guidance_scale=..., validation_guidance_rescale=...)`` refuses, before any GPU work: the rules of
+    ``Sampler.run``'s guidance, with ``caption_embeds[""]`` (what caption dropout trains on) as the unconditional embedding.
+    Returns whether validation will sample with guidance."""
+    from .pipeline import check_guidance
+    shape = None
+    if caption_embeds is not None and "" in caption_embeds:
+        shape = (1,) + tuple(torch.as_tensor(caption_embeds[""]).shape[-2:])
+    if float(guidance_scale) != 1.0 and shape is None:
+        raise ValueError("validation_guidance_scale != 1 needs the empty prompt's embedding under the key \"\" in caption_embeds")
+    return check_guidance(guidance_scale, guidance_rescale, shape if shape is not None else (1, 1, 1), shape, 1)
+
+
 def trained_buckets(lora: bool, adapter: bool) -> List[str]:
     """The parameter sets a run trains, as ``fit_state.json`` records them."""
     return [b for b, on in (("lora", lora), ("adapter", adapter)) if on]
@@ -367,26 +381,31 @@ def _world(process_group) -> Tuple[int, int]:
 
 
 def fit(config: TrainConfig, unet, vae, train_dataset, caption_embeds: Dict[str, torch.Tensor], val_dataset=None, fixed_embeds=None,
-        resume_from: Optional[str] = None, use_ema: bool = False, process_group=None, adapter=None) -> FitResult:
+        resume_from: Optional[str] = None, use_ema: bool = False, process_group=None, adapter=None,
+        validation_guidance_scale: float = 1.0, validation_guidance_rescale: float = 0.0) -> FitResult:
     """LoRA fine-tuning of ``unet`` (created with ``lora_rank > 0, lora_fused=True`` and loaded) on ``train_dataset`` (items
     ``{'hr', 'lr', 'txt'}``, images in [-1, 1]); ``caption_embeds[txt]`` is the [L, D] text embedding of each prompt ("" for the
     dropped caption).  Writes ``output_dir/metrics.jsonl``, ``validation/step-N.png`` (with ``val_dataset``) and
     ``checkpoint-N/``; ``resume_from`` is such a checkpoint directory.  ``adapter``: a loaded ``Adapter_XL`` trained as well,
-    conditioned on each item's LR image; with a ``lora_rank=0`` UNet it is the only thing trained (the UNet is frozen)."""
+    conditioned on each item's LR image; with a ``lora_rank=0`` UNet it is the only thing trained (the UNet is frozen).
+    ``validation_guidance_scale`` / ``validation_guidance_rescale``: the validation panels are sampled with classifier-free guidance
+    against ``caption_embeds[""]`` (``log_validation``); the defaults sample as before."""
     check_config(config, caption_embeds)
+    guided = check_validation_guidance(validation_guidance_scale, validation_guidance_rescale, caption_embeds)
+    guidance = (float(validation_guidance_scale), float(validation_guidance_rescale)) if guided else None
     # the whole run on one side stream: graph launches, the all-reduce between them, ring reads, checkpoints and validation are then
     # ordered by the stream itself (the library fences the legacy default stream through an internal one otherwise)
     side = torch.cuda.Stream(device=unet.device)
     side.wait_stream(torch.cuda.current_stream(unet.device))
     with torch.cuda.stream(side):
         res = _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_embeds, resume_from, use_ema, process_group,
-                   adapter)
+                   adapter, guidance)
     torch.cuda.current_stream(unet.device).wait_stream(side)
     return res
 
 
 def _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_embeds, resume_from, use_ema, process_group,
-         adapter=None) -> FitResult:
+         adapter=None, guidance=None) -> FitResult:
     want = L.torch_dtype(L.dtype_id(config.compute_dtype()))
     if unet.compute_dtype != want:
         raise ValueError(f"mixed_precision={config.mixed_precision!r} means compute dtype {want}; the UNet computes in {unet.compute_dtype}")
@@ -440,6 +459,11 @@ def _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_em
             txt = it.get("txt", "") if isinstance(it, dict) else ""
             fixed_embeds = torch.as_tensor(caption_embeds[txt] if txt in caption_embeds else next(iter(caption_embeds.values())))
         fixed_embeds = fixed_embeds.reshape(-1, *fixed_embeds.shape[-2:]).to(unet.device, torch.float32)
+    val_kw = {}
+    if guidance is not None:  # classifier-free guidance against the embedding the caption dropout trained on
+        empty = torch.as_tensor(caption_embeds[""])
+        val_kw = dict(guidance_scale=guidance[0], guidance_rescale=guidance[1],
+                      uncond_embeds=empty.reshape(-1, *empty.shape[-2:]).to(unet.device, torch.float32))
 
     samples = config.train_batch_size * config.gradient_accumulation_steps * world
     t_log, last_log = time.perf_counter(), start
@@ -473,7 +497,7 @@ def _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_em
             from .pipeline import log_validation
             from .schedulers import DDPMScheduler
             panel = log_validation(unet, None, vae, [val_batch], DDPMScheduler(**config.scheduler_kwargs()), torch.float32,
-                                   _Accel(unet.device), fixed_embeds, adapter=adapter)
+                                   _Accel(unet.device), fixed_embeds, adapter=adapter, **val_kw)
             os.makedirs(os.path.join(out, "validation"), exist_ok=True)
             path = os.path.join(out, "validation", f"step-{step}.png")
             panel.save(path)

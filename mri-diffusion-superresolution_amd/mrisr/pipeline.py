@@ -63,6 +63,34 @@ def decode_to_vis(data, vae, is_latent=True):
     return img_np
 
 
+def check_guidance(guidance_scale, guidance_rescale, ehs_shape, uncond_shape, batch) -> bool:
+    """The argument rules of ``Sampler.run``'s classifier-free guidance, on shapes alone (no device is touched).  Returns whether
+    guidance is ACTIVE: an unconditional context is given and ``guidance_scale != 1`` (at 1 the guided prediction is the
+    conditional one, so the plain call is taken).  Raises ``ValueError`` for anything a guided run could not honour."""
+    g, phi = float(guidance_scale), float(guidance_rescale)
+    if not np.isfinite(g):
+        raise ValueError(f"guidance_scale must be finite, got {guidance_scale!r}")
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale!r}")
+    if uncond_shape is None:
+        if g != 1.0:
+            raise ValueError("guidance_scale != 1 needs uncond_hidden_states (the embedding of the empty caption)")
+        if phi > 0.0:
+            raise ValueError("guidance_rescale > 0 needs active guidance: uncond_hidden_states and guidance_scale != 1")
+        return False
+    ehs_shape, uncond_shape = tuple(ehs_shape), tuple(uncond_shape)
+    if len(ehs_shape) != 3 or ehs_shape[0] not in (1, batch):
+        raise ValueError(f"encoder_hidden_states must be [1, L, D] or [{batch}, L, D], got {ehs_shape}")
+    if len(uncond_shape) != 3 or uncond_shape[0] not in (1, batch) or uncond_shape[1:] != ehs_shape[1:]:
+        raise ValueError(f"uncond_hidden_states must be [1, L, D] or [{batch}, L, D] with the L and D of encoder_hidden_states "
+                         f"{ehs_shape}, got {uncond_shape}")
+    if g == 1.0:
+        if phi > 0.0:
+            raise ValueError("guidance_rescale > 0 needs active guidance: guidance_scale != 1")
+        return False
+    return True
+
+
 class Sampler:
     """Owns a C-ABI sampler (device tables + the captured step graph) for one (unet, controlnet, schedule)."""
 
@@ -99,10 +127,21 @@ class Sampler:
 
     def run(self, latents: torch.Tensor, encoder_hidden_states: torch.Tensor, lr_latents: Optional[torch.Tensor] = None,
             step_noise: Optional[torch.Tensor] = None, controlnet_cond: Optional[torch.Tensor] = None,
-            adapter_features: Optional[Sequence[torch.Tensor]] = None, use_graph: bool = True) -> torch.Tensor:
-        """Advance ``latents`` [B,C,h,w] (f32, updated IN PLACE) through every timestep."""
+            adapter_features: Optional[Sequence[torch.Tensor]] = None, use_graph: bool = True,
+            guidance_scale: float = 1.0, guidance_rescale: float = 0.0,
+            uncond_hidden_states: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Advance ``latents`` [B,C,h,w] (f32, updated IN PLACE) through every timestep.
+
+        Classifier-free guidance: with ``uncond_hidden_states`` ([1,L,D] or [B,L,D]) and ``guidance_scale`` g != 1 every step runs
+        ONE forward of 2B rows (unconditional rows first) and the fused guided step: eps = eps_u + g (eps_c - eps_u), then, for
+        ``guidance_rescale`` phi > 0, eps *= phi std(eps_c) / std(eps) + (1 - phi) per sample (Lin et al. 2023, sec. 3.4).  Everything
+        else is given at [B] as without guidance.  Without these arguments, or at g == 1, the call is the unguided one."""
         if latents.dtype != torch.float32 or not latents.is_contiguous():
             raise ValueError("latents must be contiguous float32 (updated in place)")
+        if check_guidance(guidance_scale, guidance_rescale, encoder_hidden_states.shape,
+                          None if uncond_hidden_states is None else uncond_hidden_states.shape, latents.shape[0]):
+            return self._run_guided(latents, encoder_hidden_states, uncond_hidden_states, lr_latents, step_noise, controlnet_cond,
+                                    adapter_features, use_graph, float(guidance_scale), float(guidance_rescale))
         dev = latents.device
         ehs = encoder_hidden_states.to(dev).contiguous()
         if ehs.shape[0] != latents.shape[0]:
@@ -124,14 +163,44 @@ class Sampler:
         self._keep = keep
         return latents
 
+    def _run_guided(self, latents, ehs_c, ehs_u, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, g, phi):
+        B, dev = latents.shape[0], latents.device
+        if int(np.prod(latents.shape[1:])) % 4:
+            raise ValueError("guided sampling needs C*h*w of the latents to be a multiple of 4")
+        if controlnet_cond is not None and controlnet_cond.shape[0] != B:
+            raise ValueError(f"controlnet_cond must carry the latents' batch {B}, got {tuple(controlnet_cond.shape)}")
+        for f in (adapter_features or []):
+            if f.shape[0] != B:
+                raise ValueError(f"adapter features must carry the latents' batch {B}, got {tuple(f.shape)}")
+        # timestep-invariant plumbing, once per run: [unconditional rows; conditional rows] (diffusers' order), images and features twice
+        ehs2 = torch.cat([e.to(dev).expand(B, -1, -1) for e in (ehs_u, ehs_c)]).contiguous()
+        lr = lr_latents.to(dev, torch.float32).contiguous() if lr_latents is not None else None
+        nz = step_noise.to(dev, torch.float32).contiguous() if step_noise is not None else None
+        cond2 = torch.cat([controlnet_cond.to(dev)] * 2).contiguous() if controlnet_cond is not None else None
+        feats2 = [torch.cat([f.to(dev)] * 2).contiguous() for f in (adapter_features or [])]
+        keep = (ehs2, lr, nz, cond2, feats2)
+        t_lat, t_e = L.as_tensor(latents), L.as_tensor(ehs2)
+        t_lr = L.as_tensor(lr) if lr is not None else None
+        t_nz = L.as_tensor(nz, shape=(nz.shape[0] * nz.shape[1],) + tuple(nz.shape[2:])) if nz is not None else None
+        t_c = L.as_tensor(cond2) if cond2 is not None else None
+        f_arr = L.tensor_array([L.as_tensor(f) for f in feats2])
+        L.check(L.lib().mrisr_sampler_set_guidance(self._h, g, phi))
+        L.check(L.lib().mrisr_sampler_run_guided(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None,
+                                                 C.byref(t_nz) if t_nz else None, C.byref(t_e), C.byref(t_c) if t_c else None,
+                                                 f_arr if feats2 else None, len(feats2), 1 if use_graph else 0, L.stream_ptr()))
+        self._keep = keep
+        return latents
+
 
 @torch.no_grad()
 def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weight_dtype, accelerator, fixed_embeds,
-                   num_inference_steps=20, adapter=None):
+                   num_inference_steps=20, adapter=None, guidance_scale=1.0, guidance_rescale=0.0, uncond_embeds=None):
     """Drop-in for the reference's validation sampler (res_srdiff.py:35-105): same inputs, same PIL panel out.
     The timestep loop is one fused sampler call; the per-step noise is drawn up front from the same global RNG
     stream, in the same order, as the reference's per-step ``torch.randn_like`` calls.  ``adapter`` (a T2I-Adapter):
-    its features of the condition image, at the LR image's own size so that they land on the latents, enter every step."""
+    its features of the condition image, at the LR image's own size so that they land on the latents, enter every step.
+    ``guidance_scale`` / ``guidance_rescale`` / ``uncond_embeds`` (the empty caption's embedding, [1,L,D]): classifier-free
+    guidance as in ``Sampler.run``; the defaults leave the result unchanged."""
     from PIL import Image
 
     unet.eval()
@@ -156,7 +225,9 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
             prepare_condition_image(lr_raw, tuple(lr_raw.shape[-2:]))
         feats = adapter(cond.to(torch.float32))
     sampler.run(latents, fixed_embeds[0:1], lr_latents=lr_anchor, step_noise=step_noise,
-                controlnet_cond=control_image if controlnet is not None else None, adapter_features=feats)
+                controlnet_cond=control_image if controlnet is not None else None, adapter_features=feats,
+                guidance_scale=guidance_scale, guidance_rescale=guidance_rescale,
+                uncond_hidden_states=uncond_embeds[0:1] if uncond_embeds is not None else None)
     gen_vis = decode_to_vis(latents.to(weight_dtype), vae)
     hr_vis = decode_to_vis(hr_raw, vae, is_latent=False)
     lr_vis = decode_to_vis(lr_raw, vae, is_latent=False)

@@ -426,6 +426,55 @@ int mrisr_op_attention(const mrisr_tensor* q, const mrisr_tensor* k, const mrisr
 int mrisr_op_attention_bwd(const mrisr_tensor* q, const mrisr_tensor* k, const mrisr_tensor* v, const mrisr_tensor* dout,
                            int heads, mrisr_tensor* dq, mrisr_tensor* dk, mrisr_tensor* dv, void* stream);
 
+/* ---- single-op entry points of the backward (csrc/bwd.hip, csrc/train_ops.h): each runs the launcher the training step runs, on
+ * device pointers of the caller; `dtype` is MRISR_F32 or MRISR_BF16 (the type of every operand called T below), gradients of
+ * parameters are f32 and are ADDED to what the output holds.  Every call checks the shapes and alignments its kernels assume before
+ * the first launch and synchronises the stream before it returns. ---- */
+/* GroupNorm(+SiLU) backward over x = [x0 | x1] (NHWC, T, [B][HW][c0] and [B][HW][c1]; x1 NULL with c1 = 0): the forward statistics
+ * as the recorded forward computes them, then dx0 / dx1 (T; acc0 / acc1: add into them); g_gamma / g_beta [c0] (both or neither,
+ * only without x1): the affine gradients.  Honours mrisr_debug_gn_fused (one-pass kernel or the two-kernel path). */
+int mrisr_op_groupnorm_bwd(int dtype, const void* x0, int c0, const void* x1, int c1, int B, int HW, const float* gamma_dev,
+                           const float* beta_dev, int groups, float eps, int silu, const void* dy, void* dx0, int acc0, void* dx1,
+                           int acc1, float* g_gamma, float* g_beta, void* stream);
+/* LayerNorm backward on rows [M][C] (T); g_gamma / g_beta [C] optional (both or neither); dx NULL: the affine gradients alone */
+int mrisr_op_layernorm_bwd(int dtype, const void* x, const void* dy, void* dx, const float* gamma_dev, int M, int C, float eps,
+                           int accumulate, float* g_gamma, float* g_beta, void* stream);
+/* GEGLU on a stored pre-activation [M][2*half] in the projection's 16-wide (value, gate) interleave.  backward = 0: out [M][half] =
+ * u * gelu(g) (dout unused); backward = 1: out [M][2*half] = d pre for an upstream dout [M][half] */
+int mrisr_op_geglu(int dtype, int backward, const void* pre, const void* dout, void* out, int64_t M, int half, void* stream);
+/* the element-wise / reduction group.  kind:
+ *   0 silu_bwd     out[i] = a[i] * silu'(b[i])                      (a = dy, b = pre-activation; n elements)
+ *   1 relu_bwd     out[i] = b[i] > 0 ? a[i] : 0                     (a = dy, b = the ReLU's output; n elements)
+ *   2 sumpool2     out[B][H][W][C] (+)= 2x2 sums of a[B][2H][2W][C] (flag: accumulate)
+ *   3 mse_grad     a = prediction NHWC T [B][H][W][C], b = target NCHW f32; out = d pred (T), out_f32[0] = the loss
+ *   4 rowvec_grad  out_f32[(flag ? 0 : b) * ld_out + off + c] += sum_hw a[b][hw][c]   (a: [B][H*W][C]; flag: scalar timestep)
+ *   5 colsum       out_f32[c] += sum_m a[m][c]                      (a: [B*H*W][C]) */
+int mrisr_op_pointwise_bwd(int kind, int dtype, const void* a, const void* b, void* out, float* out_f32, int64_t n, int B, int H, int W,
+                           int C, int flag, int ld_out, int off, void* stream);
+/* LoRA weight gradients.  mode 0 (dB): out_j[secN][r] += scale * P_j^T Q_j, P = dY [M][C = nmod*secN] (T, pitch ldp), Q = z [M][nmod*r]
+ * (f32, pitch ldq); mode 1 (dA): out_j[r][C] += scale * Q_j^T P, P = x [M][C].  r in {4, 8, 12, 16}, nmod <= 3; a NULL out_j is skipped */
+int mrisr_op_lora_wgrad(int dtype, const void* P, int ldp, const float* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN,
+                        float* out0, float* out1, float* out2, float scale, void* stream);
+/* dst[z][c][r] = src[z][r][c] for r < r_valid, 0 for r_valid <= r < R (T; pitches ld_src >= C, ld_dst >= R; batch strides in elements) */
+int mrisr_op_transpose(int dtype, const void* src, void* dst, int R, int C, int ld_src, int ld_dst, int64_t bs_src, int64_t bs_dst,
+                       int batch, int r_valid, void* stream);
+/* dS = scale * P o (dP - rowsum(dP o P)) on rows of pitch ld: P (T), dP (f32) -> dS (T); columns nk .. ld-1 of dS are zeroed */
+int mrisr_op_softmax_bwd(int dtype, const void* p, const float* dp, void* ds, int ld, int64_t rows, int nk, float scale, void* stream);
+/* the tiny dense layers of the time-embedding MLP (rows <= 64, f32 activations).  which = 0: out[N][K] += dY^T act(X), gB[N] += colsum(dY)
+ * (xw = X f32 [rows][ldx]; act = SiLU when silu_in; gB optional); which = 1: out[rows][ld_out] = (dY W) * (pre ? silu'(pre) : 1)
+ * (xw = W [N][K] of type `dtype`; pre f32 [rows][ldpre] optional) */
+int mrisr_op_small_dense_bwd(int dtype, int which, const float* dY, int ldy, const void* xw, int ldx, int rows, int N, int K, int silu_in,
+                             const float* pre, int ldpre, float* out, float* gB, int ld_out, void* stream);
+/* weight / bias gradient of a conv (ks = 3, pad 1) or linear (ks = 1; xB = 1, xH = M, xW = 1): x NHWC [xB][xH][xW][cin_src] (T), dY rows
+ * [M][ldy] (T), columns col0 .. col0 + cout_src; gW f32 [cout][cin][ks][ks] and gB f32 [cout] (optional) are added to; cout <= cout_src,
+ * cin <= cin_src (zero-padded layers); geglu_half > 0: the rows of dY are in the GEGLU interleave of a projection with cout = 2 * geglu_half */
+int mrisr_op_conv_wgrad(int dtype, const void* x, int xB, int xH, int xW, int cin_src, const void* dY, int ldy, int col0, int cout_src,
+                        int ks, int stride, float* gW, float* gB, int cout, int cin, int geglu_half, void* stream);
+/* input gradient of a 3x3 conv (pad 1): dy NHWC [B][H][W][cout] (T), w f32 [cout][cin][3][3]; mode 0: stride 1, dx [B][H][W][cin];
+ * mode 1: stride 2, dx [B][2H][2W][cin]; accumulate: dx += */
+int mrisr_op_conv_dgrad(int dtype, const void* dy, int B, int H, int W, int cout, const float* w_oihw_dev, int cin, int mode, void* dx,
+                        int accumulate, void* stream);
+
 
 /* the fused guided step of mrisr_sampler_run_guided alone: x [B,C,h,w] f32 (in place), x2 [2B,C,h,w] f32 (receives the new x in
  * both halves), eps2 [2B,C,h,w] f32 (unconditional rows, then conditional), lr / noise [B,C,h,w] f32 or NULL (one noise slab),

@@ -3,8 +3,11 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
+#include <vector>
 
 #include "model.h"
+#include "train_ops.h"
 
 using namespace mrisr;
 
@@ -1487,6 +1490,285 @@ extern "C" int mrisr_op_attention_bwd(const mrisr_tensor* q, const mrisr_tensor*
     return op_attention_bwd_bf16(q, k, v, dout, heads, dq, dk, dv, (hipStream_t)stream);
     API_END
 }
+
+// =================================================================================================
+// single-op entry points of the backward (tests/test_gpu_bwd_ops.py): the launchers of bwd.hip and the two composites of train_ops.h on
+// the caller's device pointers.  Every argument the kernels index or vector-load by is checked before the first launch.
+// =================================================================================================
+namespace {
+struct OpScratch {  // scratch of one call: freed when the entry returns (after its stream synchronisation)
+    std::vector<std::unique_ptr<DevBuf>> bufs;
+    void* alloc(size_t bytes, bool zero = false) {
+        bufs.emplace_back(new DevBuf());
+        if (bufs.back()->reserve(bytes ? bytes : 1, zero)) return nullptr;
+        return bufs.back()->p;
+    }
+};
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline int bwd_dtype_ok(int dtype) {
+    MRISR_REQUIRE(dtype == MRISR_F32 || dtype == MRISR_BF16, "backward ops: f32 or bf16 operands");
+    return 0;
+}
+template <typename T>
+int op_gemm_run(OpScratch& sc, hipStream_t st, GemmArgs& g) {  // Runner::run_gemm on scratch buffers
+    TRY(gemm_choose(g, sizeof(T) == 2));
+    if (g.splitk > 1) {
+        g.partial = static_cast<float*>(sc.alloc((size_t)g.splitk * g.batch * g.M * g.N * sizeof(float)));
+        if (!g.partial) return 7;
+    }
+    return launch_gemm<T>(g, st);
+}
+
+template <typename T>
+int op_groupnorm_bwd_t(const void* x0, int c0, const void* x1, int c1, int B, int HW, const float* gamma, const float* beta, int groups,
+                       float eps, int silu, const void* dy, void* dx0, int acc0, void* dx1, int acc1, float* g_gamma, float* g_beta,
+                       hipStream_t st) {
+    constexpr int VE = 16 / (int)sizeof(T);
+    const int C = c0 + c1;
+    MRISR_REQUIRE(c0 % VE == 0 && c1 % VE == 0, "GroupNorm backward: channel counts in whole 16-byte vectors");
+    MRISR_REQUIRE(al16(x0) && al16(x1) && al16(dy) && al16(dx0) && al16(dx1), "GroupNorm backward: 16-byte aligned operands");
+    {
+        const int nvec = C / VE;
+        int vpt = 1;
+        while (nvec / vpt > 256 || (nvec % vpt) != 0) ++vpt;
+        MRISR_REQUIRE(vpt <= 4, "GroupNorm backward: too many channels");
+    }
+    OpScratch sc;
+    GroupNormArgs f;
+    f.x0 = x0; f.c0 = c0; f.x1 = x1; f.c1 = c1; f.B = B; f.HW = HW; f.groups = groups; f.eps = eps;
+    f.gamma = gamma; f.beta = beta; f.silu = silu;
+    f.nsplit = groupnorm_nsplit(B, HW);
+    const size_t pbytes = (size_t)B * f.nsplit * groups * 2 * sizeof(float);
+    f.y = sc.alloc((size_t)B * HW * C * sizeof(T));
+    f.partial = static_cast<float*>(sc.alloc(pbytes));
+    GroupNormBwdArgs a;
+    a.x0 = x0; a.c0 = c0; a.x1 = x1; a.c1 = c1; a.B = B; a.HW = HW; a.groups = groups; a.eps = eps;
+    a.gamma = gamma; a.beta = beta; a.silu = silu;
+    a.dy = dy; a.dx0 = dx0; a.dx1 = dx1; a.acc0 = acc0 ? 1 : 0; a.acc1 = acc1 ? 1 : 0;
+    a.fwd_partial = f.partial; a.nsplit = f.nsplit;
+    a.bwd_partial = static_cast<float*>(sc.alloc(pbytes));
+    if (!f.y || !f.partial || !a.bwd_partial) return 7;
+    TRY(launch_groupnorm<T>(f, st));  // the forward statistics, exactly as the recorded forward leaves them
+    TRY(launch_groupnorm_bwd<T>(a, st));
+    if (g_gamma) TRY(launch_gn_affine_grad<T>(x0, dy, gamma, beta, f.partial, f.nsplit, groups, B, HW, C, eps, silu ? 1 : 0, g_gamma, g_beta, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+template <typename T>
+int op_lora_wgrad_t(const void* P, int ldp, const float* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN, float* const out[3],
+                    float scale, hipStream_t st) {
+    constexpr int VE = 16 / (int)sizeof(T);
+    MRISR_REQUIRE(C % VE == 0 && ldp % VE == 0 && ldp >= C && al16(P), "LoRA wgrad: P rows in whole, aligned 16-byte vectors");
+    MRISR_REQUIRE(mode == 1 || (secN % VE == 0 && C == nmod * secN), "LoRA wgrad (dB): C = nmod sections of whole vectors");
+    const int R = nmod * r, nq = (mode == 0 || R > 16) ? r : R;
+    {   // the LDS tile of the kernel's geometry (lora_wgrad_geom)
+        const int cx = C / VE, gx = (cx + 255) / 256, cxb = (cx + gx - 1) / gx, RL = 256 / cxb;
+        MRISR_REQUIRE(RL <= 1 || (size_t)cxb * VE * nq * sizeof(float) <= 65536, "LoRA wgrad: LDS tile");
+    }
+    OpScratch sc;
+    float* scratch = static_cast<float*>(sc.alloc(lora_wgrad_scratch_bytes(M, C, R, sizeof(T))));
+    if (!scratch) return 7;
+    TRY(launch_lora_wgrad<T>(P, ldp, Q, ldq, M, C, mode, r, nmod, secN, out, scale, scratch, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+template <typename T>
+int op_conv_wgrad_t(const void* x, int xB, int xH, int xW, int cin_src, const void* dY, int ldy, int col0, int cout_src, int ks, int stride,
+                    float* gW, float* gB, int cout, int cin, int geglu_half, hipStream_t st) {
+    OpScratch sc;
+    const int Ho = (xH - 1) / stride + 1, Wo = (xW - 1) / stride + 1;
+    TRY(conv_wgrad_run<T>(st, false, [&](size_t n) { return sc.alloc(n); }, [&](GemmArgs& g) { return op_gemm_run<T>(sc, st, g); }, x, xB, xH,
+                          xW, cin_src, dY, ldy, col0, Ho, Wo, cout_src, ks, stride, gW, gB, cout, cin, geglu_half));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+template <typename T>
+int op_conv_dgrad_t(const void* dy, int B, int H, int W, int cout, const float* w, int cin, int mode, void* dx, int accumulate,
+                    hipStream_t st) {
+    OpScratch sc;
+    void* wd = sc.alloc((size_t)cout * cin * 9 * sizeof(T));
+    if (!wd) return 7;
+    TRY(launch_pack_conv_dgrad<T>(w, wd, cout, cin, st));  // the packer of train_prepare
+    TRY(conv_dgrad_run<T>(st, false, [&](GemmArgs& g) { return op_gemm_run<T>(sc, st, g); }, dy, B, H, W, cout, cin, wd, mode, dx,
+                          accumulate != 0));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+}  // namespace
+
+#define BWD_DISPATCH(dtype, fn, ...) ((dtype) == MRISR_F32 ? fn<float>(__VA_ARGS__) : fn<bf16>(__VA_ARGS__))
+
+extern "C" {
+
+int mrisr_op_groupnorm_bwd(int dtype, const void* x0, int c0, const void* x1, int c1, int B, int HW, const float* gamma_dev,
+                           const float* beta_dev, int groups, float eps, int silu, const void* dy, void* dx0, int acc0, void* dx1,
+                           int acc1, float* g_gamma, float* g_beta, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    MRISR_REQUIRE(x0 && gamma_dev && beta_dev && dy && dx0 && B >= 1 && HW >= 1 && c0 >= 1 && c1 >= 0, "GroupNorm backward: null / empty operand");
+    MRISR_REQUIRE((c1 > 0) == (x1 != nullptr) && (c1 > 0) == (dx1 != nullptr), "GroupNorm backward: x1 / dx1 exactly when c1 > 0");
+    MRISR_REQUIRE(groups >= 1 && groups <= 64 && (c0 + c1) % groups == 0, "GroupNorm backward: at most 64 groups dividing the channels");
+    MRISR_REQUIRE((g_gamma != nullptr) == (g_beta != nullptr) && (!g_gamma || c1 == 0), "GroupNorm affine gradients: both, on a single source");
+    return BWD_DISPATCH(dtype, op_groupnorm_bwd_t, x0, c0, x1, c1, B, HW, gamma_dev, beta_dev, groups, eps, silu, dy, dx0, acc0, dx1, acc1,
+                        g_gamma, g_beta, (hipStream_t)stream);
+    API_END
+}
+
+int mrisr_op_layernorm_bwd(int dtype, const void* x, const void* dy, void* dx, const float* gamma_dev, int M, int C, float eps,
+                           int accumulate, float* g_gamma, float* g_beta, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    hipStream_t st = (hipStream_t)stream;
+    const int VE = dtype == MRISR_F32 ? 4 : 8;
+    MRISR_REQUIRE(x && dy && (dx || g_gamma) && M >= 1 && C >= 1, "LayerNorm backward: null / empty operand");
+    MRISR_REQUIRE(!dx || (gamma_dev && C % VE == 0 && C / VE <= 5 * 64 && al16(x) && al16(dy) && al16(dx)),
+                  "LayerNorm backward: rows of at most 320 aligned 16-byte vectors");
+    MRISR_REQUIRE((g_gamma != nullptr) == (g_beta != nullptr) && (!g_gamma || C <= 64 * 24), "LayerNorm affine gradients: both, C <= 1536");
+    if (dx) TRY(BWD_DISPATCH(dtype, launch_layernorm_bwd, x, dy, dx, gamma_dev, M, C, eps, accumulate ? 1 : 0, st));
+    if (g_gamma) TRY(BWD_DISPATCH(dtype, launch_ln_affine_grad, x, dy, M, C, eps, g_gamma, g_beta, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
+int mrisr_op_geglu(int dtype, int backward, const void* pre, const void* dout, void* out, int64_t M, int half, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    hipStream_t st = (hipStream_t)stream;
+    MRISR_REQUIRE(pre && out && (!backward || dout) && M >= 1 && half >= 16, "GEGLU: null / empty operand");
+    MRISR_REQUIRE(half % 16 == 0, "GEGLU: the (value, gate) interleave is 16 columns wide");
+    if (backward) TRY(BWD_DISPATCH(dtype, launch_geglu_bwd, pre, dout, out, (long long)M, half, st));
+    else TRY(BWD_DISPATCH(dtype, launch_geglu_fwd, pre, out, (long long)M, half, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
+int mrisr_op_pointwise_bwd(int kind, int dtype, const void* a, const void* b, void* out, float* out_f32, int64_t n, int B, int H, int W,
+                           int C, int flag, int ld_out, int off, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    hipStream_t st = (hipStream_t)stream;
+    MRISR_REQUIRE(kind >= 0 && kind <= 5 && a, "pointwise backward: kind 0..5, operand a");
+    if (kind <= 1) {
+        MRISR_REQUIRE(b && out && n >= 1, "silu_bwd / relu_bwd: b, out, n elements");
+        if (kind == 0) TRY(BWD_DISPATCH(dtype, launch_silu_bwd, a, b, out, (long long)n, st));
+        else TRY(BWD_DISPATCH(dtype, launch_relu_bwd, a, b, out, (long long)n, st));
+    } else {
+        MRISR_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 1 && (long long)B * H * W * C < (1ll << 31), "pointwise backward: [B][H][W][C] extents");
+        if (kind == 2) {
+            MRISR_REQUIRE(out, "sumpool2: out");
+            TRY(BWD_DISPATCH(dtype, launch_sumpool2, a, out, B, H, W, C, flag ? 1 : 0, st));
+        } else if (kind == 3) {
+            MRISR_REQUIRE(b && out && out_f32, "mse_grad: target, d pred, loss");
+            MRISR_CHECK_HIP(hipMemsetAsync(out_f32, 0, sizeof(float), st));
+            TRY(BWD_DISPATCH(dtype, launch_mse_grad, a, static_cast<const float*>(b), out, out_f32, B, C, H, W, st));
+        } else if (kind == 4) {
+            MRISR_REQUIRE(out_f32 && off >= 0 && off + C <= ld_out, "rowvec_grad: columns off .. off + C inside the row pitch");
+            TRY(BWD_DISPATCH(dtype, launch_rowvec_grad, a, out_f32, ld_out, off, B, H * W, C, flag ? 1 : 0, st));
+        } else {
+            MRISR_REQUIRE(out_f32, "colsum: out");
+            TRY(BWD_DISPATCH(dtype, launch_colsum, a, out_f32, B * H * W, C, st));
+        }
+    }
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
+int mrisr_op_lora_wgrad(int dtype, const void* P, int ldp, const float* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN,
+                        float* out0, float* out1, float* out2, float scale, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    MRISR_REQUIRE(P && Q && M >= 1 && C >= 1 && (mode == 0 || mode == 1), "LoRA wgrad: null / empty operand, mode 0 / 1");
+    MRISR_REQUIRE(r % 4 == 0 && r >= 4 && r <= 16 && nmod >= 1 && nmod <= 3, "LoRA wgrad: rank 4/8/12/16, <= 3 fused modules");
+    MRISR_REQUIRE(ldq % 4 == 0 && ldq >= nmod * r && al16(Q), "LoRA wgrad: Q rows in whole, aligned 16-byte vectors");
+    float* const out[3] = {out0, nmod > 1 ? out1 : nullptr, nmod > 2 ? out2 : nullptr};
+    return BWD_DISPATCH(dtype, op_lora_wgrad_t, P, ldp, Q, ldq, M, C, mode, r, nmod, secN, out, scale, (hipStream_t)stream);
+    API_END
+}
+
+int mrisr_op_transpose(int dtype, const void* src, void* dst, int R, int C, int ld_src, int ld_dst, int64_t bs_src, int64_t bs_dst,
+                       int batch, int r_valid, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    hipStream_t st = (hipStream_t)stream;
+    MRISR_REQUIRE(src && dst && R >= 1 && C >= 1 && batch >= 1 && batch <= 65535, "transpose: null / empty operand");
+    MRISR_REQUIRE(ld_src >= C && ld_dst >= R && r_valid >= 0 && r_valid <= R, "transpose: pitches cover the rows, r_valid <= R");
+    MRISR_REQUIRE(batch == 1 || (bs_src >= (long long)(R - 1) * ld_src + C && bs_dst >= (long long)(C - 1) * ld_dst + R),
+                  "transpose: batch strides cover one matrix");
+    TRY(BWD_DISPATCH(dtype, launch_transpose, src, dst, R, C, ld_src, ld_dst, (long long)bs_src, (long long)bs_dst, batch, r_valid, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
+int mrisr_op_softmax_bwd(int dtype, const void* p, const float* dp, void* ds, int ld, int64_t rows, int nk, float scale, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    hipStream_t st = (hipStream_t)stream;
+    MRISR_REQUIRE(p && dp && ds && rows >= 1 && nk >= 1 && nk <= ld, "softmax backward: null / empty operand, nk <= ld");
+    MRISR_REQUIRE(ld % 4 != 0 || ld > 4096 || (al16(p) && al16(dp) && al16(ds)), "softmax backward: aligned rows for the vector kernel");
+    TRY(BWD_DISPATCH(dtype, launch_softmax_bwd, p, dp, ds, ld, (long long)rows, nk, scale, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
+int mrisr_op_small_dense_bwd(int dtype, int which, const float* dY, int ldy, const void* xw, int ldx, int rows, int N, int K, int silu_in,
+                             const float* pre, int ldpre, float* out, float* gB, int ld_out, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    hipStream_t st = (hipStream_t)stream;
+    MRISR_REQUIRE(dY && xw && out && (which == 0 || which == 1), "small dense backward: null operand, which 0 / 1");
+    MRISR_REQUIRE(rows >= 1 && rows <= 64 && N >= 1 && K >= 1 && ldy >= N, "small dense backward: 1..64 rows, dY pitch covers N");
+    if (which == 0) {
+        MRISR_REQUIRE(ldx >= K, "small wgrad: X pitch covers K");
+        TRY(launch_small_wgrad(dY, ldy, static_cast<const float*>(xw), ldx, rows, N, K, silu_in ? 1 : 0, out, gB, st));
+    } else {
+        MRISR_REQUIRE(ld_out >= K && (!pre || ldpre >= K), "small dgrad: dX / pre pitches cover K");
+        TRY(BWD_DISPATCH(dtype, launch_small_dgrad, dY, ldy, xw, rows, N, K, pre, ldpre, out, ld_out, st));
+    }
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
+int mrisr_op_conv_wgrad(int dtype, const void* x, int xB, int xH, int xW, int cin_src, const void* dY, int ldy, int col0, int cout_src,
+                        int ks, int stride, float* gW, float* gB, int cout, int cin, int geglu_half, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    TRY(gemm_prepare());
+    MRISR_REQUIRE(x && dY && gW && xB >= 1 && xH >= 1 && xW >= 1, "conv wgrad: null / empty operand");
+    MRISR_REQUIRE((ks == 1 || ks == 3) && (stride == 1 || stride == 2), "conv wgrad: 1x1 or 3x3, stride 1 or 2");
+    MRISR_REQUIRE(cout >= 1 && cout <= cout_src && cin >= 1 && cin <= cin_src, "conv wgrad: raw tensor inside the (padded) layer");
+    MRISR_REQUIRE(col0 >= 0 && col0 + cout_src <= ldy, "conv wgrad: dY columns inside the row pitch");
+    MRISR_REQUIRE(geglu_half == 0 || (geglu_half % 16 == 0 && cout == 2 * geglu_half), "conv wgrad: GEGLU interleave of a [2 * half] projection");
+    MRISR_REQUIRE((long long)xB * xH * xW < (1ll << 24) && (long long)ks * ks * cin_src * cout_src < (1ll << 28), "conv wgrad: extents");
+    return BWD_DISPATCH(dtype, op_conv_wgrad_t, x, xB, xH, xW, cin_src, dY, ldy, col0, cout_src, ks, stride, gW, gB, cout, cin, geglu_half,
+                        (hipStream_t)stream);
+    API_END
+}
+
+int mrisr_op_conv_dgrad(int dtype, const void* dy, int B, int H, int W, int cout, const float* w_oihw_dev, int cin, int mode, void* dx,
+                        int accumulate, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    TRY(gemm_prepare());
+    MRISR_REQUIRE(dy && w_oihw_dev && dx && B >= 1 && H >= 1 && W >= 1 && cout >= 1 && cin >= 1, "conv dgrad: null / empty operand");
+    MRISR_REQUIRE(mode == 0 || mode == 1, "conv dgrad: mode 0 (stride 1) or 1 (stride 2)");
+    const int bk = dtype == MRISR_F32 ? 32 : 64;
+    MRISR_REQUIRE(mode == 0 || (cout % bk == 0 && cin % 4 == 0), "strided dgrad of a tiny conv");
+    MRISR_REQUIRE(al16(dy) && al16(dx), "conv dgrad: 16-byte aligned activations");
+    return BWD_DISPATCH(dtype, op_conv_dgrad_t, dy, B, H, W, cout, w_oihw_dev, cin, mode, dx, accumulate, (hipStream_t)stream);
+    API_END
+}
+
+}  // extern "C"
+#undef BWD_DISPATCH
 
 // =================================================================================================
 // GEMM micro-benchmark (tools/gemm_sweep.py): times one implicit-GEMM shape with a forced tile / split-K on

@@ -478,13 +478,17 @@ __global__ __launch_bounds__(256) void conv_in_mfma_kernel(const DirectConvArgs 
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf1, af1, acc, 0, 0, 0);
             const int n = i * 16 + fg * 4;
             const f32x4 b4 = *reinterpret_cast<const f32x4*>(bl + n);
+            // `add` joins in f32, before the one rounding (as the GEMM epilogue's residual does): rounding the conv first and the sum
+            // again costs up to a bf16 ulp of the larger term
+            bf16x4 ad = bf16x4{0, 0, 0, 0};
+            if (a.add && m < M) ad = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16*>(a.add) + (size_t)m * a.Cout + n);
             bf16x4 o;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float v = acc[r] + b4[r];
                 if (a.act == ACT_SILU) v = silu_f(v);
                 else if (a.act == ACT_RELU) v = fmaxf(v, 0.f);
-                o[r] = (bf16)v;
+                o[r] = (bf16)(v + (float)ad[r]);
             }
             *reinterpret_cast<bf16x4*>(ot + fr * OP + n) = o;
         }
@@ -494,13 +498,7 @@ __global__ __launch_bounds__(256) void conv_in_mfma_kernel(const DirectConvArgs 
             const int row = c / CPR, col = (c - row * CPR) * 8;
             const int mo = pg * 16 + row;
             if (mo >= M) continue;
-            bf16x8 v = *reinterpret_cast<const bf16x8*>(ot + row * OP + col);
-            if (a.add) {
-                const bf16x8 ad = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16*>(a.add) + (size_t)mo * a.Cout + col);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = (bf16)((float)v[e] + (float)ad[e]);
-            }
-            *reinterpret_cast<bf16x8*>(y + (size_t)mo * a.Cout + col) = v;
+            *reinterpret_cast<bf16x8*>(y + (size_t)mo * a.Cout + col) = *reinterpret_cast<const bf16x8*>(ot + row * OP + col);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // tile reads done before the next group overwrites it
         __builtin_amdgcn_wave_barrier();

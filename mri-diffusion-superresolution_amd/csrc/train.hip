@@ -12,25 +12,13 @@
 
 #include "model.h"
 #include "runner.h"
+#include "train_ops.h"
 
 namespace mrisr {
 
 // ================================================================================================
 // load-time packing for the backward
 // ================================================================================================
-// wd[ci][ky][kx][co] = w[co][ci][2-ky][2-kx]: the dgrad of a 3x3 conv is a 3x3 conv of dY with this bank
-template <typename T>
-__global__ void pack_conv_dgrad_kernel(const float* __restrict__ w, T* __restrict__ wd, int Cout, int Cin) {
-    const long long total = (long long)Cout * Cin * 9;
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int co = (int)(i % Cout);
-        const int t = (int)((i / Cout) % 9);
-        const int ci = (int)(i / (9ll * Cout));
-        const int ky = t / 3, kx = t - ky * 3;
-        wd[i] = from_f32<T>(w[(((size_t)co * Cin + ci) * 3 + (2 - ky)) * 3 + (2 - kx)]);
-    }
-}
-
 // adapter of fused-module slot `slot` (theta: A [r][k], B [n][r]) -> the four device views the kernels read:
 //   loraA [R][k] T (forward down-projection), loraAT [k][R] f32 (dgrad epilogue),
 //   loraB [ntot][r] f32 = s*B (forward epilogue), loraBT [R][ntot] T = s*B^T (backward down-projection)
@@ -86,10 +74,8 @@ static int train_prepare_t(Model& m, hipStream_t st) {
         if (!w) { err = 3; set_error("missing parameter: " + c.name + ".weight"); return; }
         c.wd = m.new_packed((size_t)w->numel() * sizeof(T), false);
         if (!c.wd) { err = 4; return; }
-        long long blocks = (w->numel() + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(pack_conv_dgrad_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const float*>(w->data->p),
-                           static_cast<T*>(c.wd), c.cout, c.cin);
+        // wd[ci][ky][kx][co] = w[co][ci][2-ky][2-kx]: the dgrad of a 3x3 conv is a 3x3 conv of dY with this bank
+        if (launch_pack_conv_dgrad<T>(static_cast<const float*>(w->data->p), c.wd, c.cout, c.cin, st)) err = 5;
     };
     auto lin_t = [&](LinW& l) {
         if (!l.w || l.wT) return;
@@ -240,28 +226,9 @@ struct Trainer : Runner<T> {
     // col0 .. col0 + cout_src; the raw tensor is [cout][cin][ks][ks] with cout <= cout_src, cin <= cin_src (zero-padded layers).
     int wgrad(const void* x, int xB, int xH, int xW, int cin_src, const void* dY, int ldy, int col0, int Ho, int Wo, int cout_src, int ks,
               int stride, float* gW, float* gB, int cout, int cin, int geglu_half = 0) {
-        const int M = xB * Ho * Wo, Mpad = (M + 63) / 64 * 64, taps = ks * ks;
-        const int ncol = (taps * cin_src + 3) & ~3;  // the GEMM's N in multiples of 4 (3-channel images: 27 -> 28, one zero column)
         const size_t mk = m.arena.mark();
-        T* dyT = static_cast<T*>(alloc((size_t)cout_src * Mpad * sizeof(T)));
-        T* xT = static_cast<T*>(alloc((size_t)ncol * Mpad * sizeof(T)));
-        float* tmp = static_cast<float*>(alloc((size_t)cout_src * ncol * sizeof(float)));
-        if (!dyT || !xT || !tmp) return 7;
-        if (!dry) {
-            if (Mpad != M || ncol != taps * cin_src) {
-                MRISR_CHECK_HIP(hipMemsetAsync(dyT, 0, (size_t)cout_src * Mpad * sizeof(T), st));
-                MRISR_CHECK_HIP(hipMemsetAsync(xT, 0, (size_t)ncol * Mpad * sizeof(T), st));
-            }
-            TRY(launch_transpose<T>(static_cast<const T*>(dY) + col0, dyT, M, cout_src, ldy, Mpad, 0, 0, 1, M, st));
-            if (gB) TRY(launch_colsum_gen<T>(dY, ldy, col0, gB, M, cout, geglu_half, st));
-            TRY(launch_im2col_all_T<T>(x, xT, xB, xH, xW, cin_src, Ho, Wo, stride, ks / 2, ks, Mpad, st));
-        }
-        GemmArgs g;
-        g.a0 = dyT; g.c0 = Mpad; g.lda0 = Mpad;
-        g.w = xT; g.M = cout_src; g.N = ncol; g.K = Mpad;
-        g.out_mode = OUT_F32; g.out = tmp; g.ldo = ncol;
-        TRY(R::run_gemm(g));
-        if (!dry && gW) TRY(launch_wgrad_accum_gen(tmp, ncol, cin_src, gW, cout, cin, taps, geglu_half, st));
+        TRY(conv_wgrad_run<T>(st, dry, [this](size_t n) { return alloc(n); }, [this](GemmArgs& g) { return R::run_gemm(g); }, x, xB, xH, xW,
+                              cin_src, dY, ldy, col0, Ho, Wo, cout_src, ks, stride, gW, gB, cout, cin, geglu_half));
         m.arena.release(mk);
         return 0;
     }
@@ -331,23 +298,8 @@ struct Trainer : Runner<T> {
     // dX (+)= conv3x3(dY, wd).  mode 1: the forward conv had stride 2 -> dY is zero-stuffed to twice its size
     int conv_dgrad(const Act& dy, const ConvW& cw, int mode, void* out, bool acc) {
         MRISR_REQUIRE(cw.wd && dy.C == cw.cout, "conv dgrad weights");
-        const int Ho = dy.H << mode, Wo = dy.W << mode;
-        if (cw.cout % BK != 0 || cw.cin % 4 != 0) {  // conv_out (4 channels): far below one K tile
-            MRISR_REQUIRE(mode == 0, "strided dgrad of a tiny conv");
-            DirectConvArgs a;
-            a.x = dy.p; a.w = cw.wd; a.y = out; a.B = dy.B; a.Hin = dy.H; a.Win = dy.W; a.Cin = cw.cout;
-            a.Hout = Ho; a.Wout = Wo; a.Cout = cw.cin; a.ks = 3; a.stride = 1; a.pad = 1; a.act = ACT_NONE;
-            a.add = acc ? out : nullptr;
-            if (dry) return 0;
-            return launch_direct_conv<T>(a, st);
-        }
-        GemmArgs g;
-        g.a0 = dy.p; g.c0 = cw.cout; g.lda0 = cw.cout;
-        g.conv = 1; g.B = dy.B; g.Hin = dy.H; g.Win = dy.W; g.Hout = Ho; g.Wout = Wo; g.stride = 1; g.ups = mode; g.zstuff = mode;
-        g.w = cw.wd; g.M = dy.B * Ho * Wo; g.N = cw.cin; g.K = 9 * cw.cout;
-        if (acc) { g.resid = out; g.ldr = cw.cin; }
-        g.out = out; g.ldo = cw.cin;
-        return R::run_gemm(g);
+        return conv_dgrad_run<T>(st, dry, [this](GemmArgs& g) { return R::run_gemm(g); }, dy.p, dy.B, dy.H, dy.W, cw.cout, cw.cin, cw.wd,
+                                 mode, out, acc);
     }
 
     int gn_bwd(const Act& x0, const Act* x1, const NormW& nw, bool silu, float eps, const float* fwd_partial, int nsplit,
@@ -1187,10 +1139,8 @@ static int full_train_prepare_t(Model& m, hipStream_t st) {
         if (!w) { err = 3; set_error("missing parameter: " + c.name + ".weight"); return; }
         c.wd = m.new_packed((size_t)w->numel() * sizeof(T), false);
         if (!c.wd) { err = 4; return; }
-        long long blocks = (w->numel() + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(pack_conv_dgrad_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const float*>(w->data->p),
-                           static_cast<T*>(c.wd), c.cout, c.cin);
+        // wd[ci][ky][kx][co] = w[co][ci][2-ky][2-kx]: the dgrad of a 3x3 conv is a 3x3 conv of dY with this bank
+        if (launch_pack_conv_dgrad<T>(static_cast<const float*>(w->data->p), c.wd, c.cout, c.cin, st)) err = 5;
     };
     auto lin_t = [&](LinW& l) {
         if (!l.w) return;

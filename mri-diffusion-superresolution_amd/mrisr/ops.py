@@ -150,3 +150,112 @@ def attention_backward(q, k, v, dout, heads):
     L.check(L.lib().mrisr_op_attention_bwd(C.byref(ts[0]), C.byref(ts[1]), C.byref(ts[2]), C.byref(ts[3]), heads,
                                            C.byref(ts[4]), C.byref(ts[5]), C.byref(ts[6]), L.stream_ptr()))
     return dq, dk, dv
+
+
+# ---- the backward (mrisr_op_*_bwd and friends): thin wrappers over raw device pointers.  Tensors are used as they are (contiguous, on
+# the GPU, already in the kernels' layouts: NHWC activations, token rows); outputs that a kernel adds into are passed in by the caller.
+def _p(t: Optional[torch.Tensor]):
+    if t is None:
+        return None
+    if not t.is_cuda or not t.is_contiguous():
+        raise L.MrisrError("backward ops take contiguous GPU tensors")
+    return t.data_ptr()
+
+
+def _dt(t: torch.Tensor) -> int:
+    return L.dtype_id(t.dtype)
+
+
+def groupnorm_backward(x, dy, gamma, beta, groups=32, eps=1e-5, silu=False, x2=None, dx=None, dx2=None, acc=False, acc2=False,
+                       g_gamma=None, g_beta=None):
+    """x [B,HW,c0] (and x2 [B,HW,c1]) NHWC rows, dy [B,HW,c0+c1]; returns (dx, dx2).  ``dx`` / ``dx2`` given with ``acc`` / ``acc2``: the
+    gradient is added into them.  ``g_gamma`` / ``g_beta`` (f32 [c0], x2 None): the affine gradients are added into them."""
+    B, HW, c0 = x.shape
+    c1 = 0 if x2 is None else x2.shape[2]
+    dx = torch.empty_like(x) if dx is None else dx
+    if x2 is not None and dx2 is None:
+        dx2 = torch.empty_like(x2)
+    L.check(L.lib().mrisr_op_groupnorm_bwd(_dt(x), _p(x), c0, _p(x2), c1, B, HW, _p(gamma), _p(beta), groups, eps, 1 if silu else 0, _p(dy),
+                                           _p(dx), 1 if acc else 0, _p(dx2), 1 if acc2 else 0, _p(g_gamma), _p(g_beta), L.stream_ptr()))
+    return dx, dx2
+
+
+def layernorm_backward(x, dy, gamma, eps=1e-5, dx=None, acc=False, g_gamma=None, g_beta=None, need_dx=True):
+    """rows x, dy [M,C] -> dx (added into a given ``dx`` with ``acc``); g_gamma / g_beta f32 [C] are added into.  ``need_dx`` False: the
+    affine gradients alone (rows wider than the dx kernel takes, up to 1536 channels)."""
+    M, Cc = x.shape
+    dx = (torch.empty_like(x) if dx is None else dx) if need_dx else None
+    L.check(L.lib().mrisr_op_layernorm_bwd(_dt(x), _p(x), _p(dy), _p(dx), _p(gamma), M, Cc, eps, 1 if acc else 0, _p(g_gamma), _p(g_beta),
+                                           L.stream_ptr()))
+    return dx
+
+
+def geglu(pre, dout=None):
+    """pre [M, 2*half] in the projection's 16-wide interleave.  Without ``dout``: u * gelu(g) [M, half]; with it: d pre [M, 2*half]."""
+    M, two = pre.shape
+    half = two // 2
+    out = torch.empty((M, half) if dout is None else (M, two), dtype=pre.dtype, device=pre.device)
+    L.check(L.lib().mrisr_op_geglu(_dt(pre), 0 if dout is None else 1, _p(pre), _p(dout), _p(out), M, half, L.stream_ptr()))
+    return out
+
+
+PW_SILU_BWD, PW_RELU_BWD, PW_SUMPOOL2, PW_MSE_GRAD, PW_ROWVEC_GRAD, PW_COLSUM = range(6)
+
+
+def pointwise_backward(kind, a, b=None, out=None, out_f32=None, n=0, B=0, H=0, W=0, Cc=0, flag=0, ld_out=0, off=0):
+    """mrisr_op_pointwise_bwd as declared in include/mrisr.h (kind = one of the PW_* constants)."""
+    L.check(L.lib().mrisr_op_pointwise_bwd(kind, _dt(a), _p(a), _p(b), _p(out), _p(out_f32), n, B, H, W, Cc, flag, ld_out, off, L.stream_ptr()))
+
+
+def lora_wgrad(P, Q, M, Cc, mode, r, nmod, secN, outs, scale=1.0, ldp=None, ldq=None):
+    """P [M, ldp] (T), Q [M, ldq] f32; ``outs``: up to three f32 tensors (None: no adapter on that module), added into."""
+    outs = list(outs) + [None] * (3 - len(outs))
+    L.check(L.lib().mrisr_op_lora_wgrad(_dt(P), _p(P), P.shape[1] if ldp is None else ldp, _p(Q), Q.shape[1] if ldq is None else ldq, M, Cc,
+                                        mode, r, nmod, secN, _p(outs[0]), _p(outs[1]), _p(outs[2]), scale, L.stream_ptr()))
+
+
+def transpose(src, dst, R, Cc, ld_src, ld_dst, bs_src=0, bs_dst=0, batch=1, r_valid=None):
+    L.check(L.lib().mrisr_op_transpose(_dt(src), _p(src), _p(dst), R, Cc, ld_src, ld_dst, bs_src, bs_dst, batch, R if r_valid is None else r_valid,
+                                       L.stream_ptr()))
+
+
+def softmax_backward(p, dp, nk, scale):
+    """p [rows, ld] (T), dp [rows, ld] f32 -> dS [rows, ld] (T)."""
+    rows, ld = p.shape
+    ds = torch.empty_like(p)
+    L.check(L.lib().mrisr_op_softmax_bwd(_dt(p), _p(p), _p(dp), _p(ds), ld, rows, nk, scale, L.stream_ptr()))
+    return ds
+
+
+def small_wgrad(dY, X, N, K, gW, gB=None, silu_in=False, rows=None):
+    """gW [N,K] += dY^T act(X), gB [N] += colsum(dY): f32 rows dY [rows, ldy], X [rows, ldx]."""
+    L.check(L.lib().mrisr_op_small_dense_bwd(L.MRISR_F32, 0, _p(dY), dY.shape[1], _p(X), X.shape[1], dY.shape[0] if rows is None else rows, N, K,
+                                             1 if silu_in else 0, None, 0, _p(gW), _p(gB), 0, L.stream_ptr()))
+
+
+def small_dgrad(dY, Wt, N, K, pre=None, rows=None):
+    """dX [rows,K] = (dY W) * silu'(pre): dY f32 [rows, ldy], W [N,K] f32 or bf16, pre f32 [rows, ldpre] or None."""
+    rows = dY.shape[0] if rows is None else rows
+    dX = torch.empty((max(rows, 1), K), dtype=torch.float32, device=dY.device)
+    L.check(L.lib().mrisr_op_small_dense_bwd(_dt(Wt), 1, _p(dY), dY.shape[1], _p(Wt), 0, rows, N, K, 0, _p(pre), 0 if pre is None else pre.shape[1],
+                                             _p(dX), None, K, L.stream_ptr()))
+    return dX
+
+
+def conv_wgrad(x, dY, gW, gB=None, ks=3, stride=1, col0=0, cout_src=None, cout=None, cin=None, geglu_half=0):
+    """x NHWC [B,H,W,cin_src] (a linear: [1,M,1,K]), dY rows [M, ldy]; gW f32 [cout,cin,ks,ks] and gB f32 [cout] are added into."""
+    B, H, W, cin_src = x.shape
+    cout_src = dY.shape[1] - col0 if cout_src is None else cout_src
+    L.check(L.lib().mrisr_op_conv_wgrad(_dt(x), _p(x), B, H, W, cin_src, _p(dY), dY.shape[1], col0, cout_src, ks, stride, _p(gW), _p(gB),
+                                        gW.shape[0] if cout is None else cout, gW.shape[1] if cin is None else cin, geglu_half, L.stream_ptr()))
+
+
+def conv_dgrad(dy, weight, stride=1, dx=None, acc=False):
+    """dy NHWC [B,H,W,cout], weight f32 [cout,cin,3,3] -> dx NHWC [B,H*stride,W*stride,cin] (added into a given ``dx`` with ``acc``)."""
+    B, H, W, cout = dy.shape
+    cin = weight.shape[1]
+    mode = stride - 1
+    if dx is None:
+        dx = torch.empty((B, H << max(mode, 0), W << max(mode, 0), cin), dtype=dy.dtype, device=dy.device)
+    L.check(L.lib().mrisr_op_conv_dgrad(_dt(dy), _p(dy), B, H, W, cout, _p(weight), cin, mode, _p(dx), 1 if acc else 0, L.stream_ptr()))
+    return dx

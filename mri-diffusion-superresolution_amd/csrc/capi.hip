@@ -1,32 +1,18 @@
-// C ABI (include/mrisr.h): thin extern "C" layer over Model, plus the sampler (per-step hipGraph), the
-// T2I-Adapter runtime and the single-op entry points the parity tests call.
+// C ABI (include/mrisr.h), the product part: thin extern "C" layer over Model (handles, forward, training step, optimiser) plus the
+// sampler (per-step hipGraph).  The T2I-Adapter lives in adapter.hip, the fine-tuning loop in fit.hip, the VAE in vae.hip, the
+// single-op and bench entry points in capi_ops.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <memory>
 #include <vector>
 
+#include "api.h"
 #include "model.h"
-#include "train_ops.h"
 
 using namespace mrisr;
 
 struct mrisr_model : public Model {};
-
-#define TRY(expr)            \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
-#define API_BEGIN try {
-#define API_END                                              \
-    }                                                        \
-    catch (const std::exception& e) {                        \
-        set_error(std::string("exception: ") + e.what());    \
-        return 99;                                           \
-    }
-
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 extern "C" {
 
@@ -523,1354 +509,6 @@ int mrisr_op_guided_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const
 }
 
 }  // extern "C"
-
-// =================================================================================================
-// T2I-Adapter (reference src/adapters/modules.py:114-157, sk=True)
-// =================================================================================================
-struct AdBlock {
-    bool down = false, has_in = false;
-    ConvW down_w, in_w, b1, b2;
-    int in_c = 0, out_c = 0;
-};
-struct AdRec {  // what one block's backward needs (activations stay in the arena until the next forward)
-    Act x_in, x_down, x_pre, hmid, y;
-};
-struct AdTrainable {
-    std::string key;
-    long long offset = 0, numel = 0;
-    std::vector<int64_t> shape;
-};
-struct mrisr_adapter {
-    mrisr_adapter_cfg cfg{};
-    std::map<std::string, RawParam> raw;
-    std::vector<std::unique_ptr<DevBuf>> packed;
-    ConvW conv_in;
-    std::vector<AdBlock> blocks;
-    Arena arena;
-    bool finalized = false;
-    // ---- training (the adapter runs and is differentiated every step) ----
-    bool train_ready = false, recorded = false;
-    std::vector<AdTrainable> trainables;
-    long long n_trainable = 0;
-    float* theta = nullptr;
-    float* grad = nullptr;
-    Act rec_u;
-    std::vector<AdRec> recs;
-    Act bwd_dcur;             // running gradient between the level-wise backward calls
-    int bwd_next_level = -1;  // next level mrisr_adapter_backward_level expects (descending)
-    // the training loop's plan (adapter_fit_plan): geometry it was made for, bumped on every re-plan (captured graphs key on it);
-    // an eager forward clears the key, since it resets (and may reallocate) the arena
-    std::string fit_plan_key;
-    unsigned long long fit_plan_gen = 0;
-    std::vector<ConvW*> all_convs() {
-        std::vector<ConvW*> v{&conv_in};
-        for (auto& b : blocks) {
-            if (b.down) v.push_back(&b.down_w);
-            if (b.has_in) v.push_back(&b.in_w);
-            v.push_back(&b.b1);
-            v.push_back(&b.b2);
-        }
-        return v;
-    }
-};
-
-template <typename T>
-struct AdRunner {
-    mrisr_adapter& a;
-    hipStream_t st;
-    bool dry;
-    Act new_act(int B, int H, int W, int C) {
-        Act x; x.B = B; x.H = H; x.W = W; x.C = C;
-        x.p = a.arena.alloc(x.numel() * sizeof(T));
-        if (!x.p) set_error("adapter workspace exhausted");
-        return x;
-    }
-    int conv(const Act& x, const ConvW& cw, int stride, int act, const Act* resid, Act* out) {
-        MRISR_REQUIRE(cw.cin == x.C, "adapter conv channel mismatch");
-        const int Ho = (x.H - 1) / stride + 1, Wo = (x.W - 1) / stride + 1;
-        *out = new_act(x.B, cw.ks == 3 ? Ho : x.H, cw.ks == 3 ? Wo : x.W, cw.cout);
-        if (!out->p) return 7;
-        GemmArgs g;
-        g.a0 = x.p; g.c0 = x.C; g.lda0 = x.C;
-        g.w = cw.w; g.N = cw.cout; g.bias = cw.b; g.act = act;
-        if (cw.ks == 3) {
-            g.conv = 1; g.B = x.B; g.Hin = x.H; g.Win = x.W; g.Hout = Ho; g.Wout = Wo; g.stride = stride;
-            g.M = x.B * Ho * Wo; g.K = 9 * x.C;
-        } else {
-            MRISR_REQUIRE(stride == 1, "1x1 conv stride");
-            g.M = (int)x.rows(); g.K = x.C;
-        }
-        if (resid) { g.resid = resid->p; g.ldr = resid->C; }
-        g.out = out->p; g.ldo = cw.cout;
-        TRY(gemm_choose(g, sizeof(T) == 2));
-        if (g.splitk > 1) {
-            g.partial = static_cast<float*>(a.arena.alloc((size_t)g.splitk * g.M * g.N * sizeof(float)));
-            if (!g.partial) return 7;
-        }
-        if (dry) return 0;
-        return launch_gemm<T>(g, st);
-    }
-    // ---- backward building blocks ----
-    void* alloc(size_t bytes) {
-        void* p = a.arena.alloc(bytes);
-        if (!p) set_error("adapter workspace exhausted");
-        return p;
-    }
-    int gemm(GemmArgs& g) {
-        TRY(gemm_choose(g, sizeof(T) == 2));
-        if (g.splitk > 1) {
-            g.partial = static_cast<float*>(alloc((size_t)g.splitk * g.M * g.N * sizeof(float)));
-            if (!g.partial) return 7;
-        }
-        if (dry) return 0;
-        return launch_gemm<T>(g, st);
-    }
-    // dX = dgrad(dY) (+ resid);  3x3: conv with the flipped / transposed bank, stride 2 through zero-stuffing;  1x1: dY W
-    int conv_dgrad(const Act& dy, const ConvW& cw, int stride, const Act* resid, Act* dx) {
-        MRISR_REQUIRE(cw.wd && dy.C == cw.cout, "adapter dgrad weights");
-        const int up = stride == 2 ? 1 : 0;
-        *dx = new_act(dy.B, dy.H << up, dy.W << up, cw.cin);
-        if (!dx->p) return 7;
-        GemmArgs g;
-        g.a0 = dy.p; g.c0 = cw.cout; g.lda0 = cw.cout;
-        g.w = cw.wd; g.N = cw.cin; g.out = dx->p; g.ldo = cw.cin;
-        if (cw.ks == 3) {
-            g.conv = 1; g.B = dy.B; g.Hin = dy.H; g.Win = dy.W; g.Hout = dy.H << up; g.Wout = dy.W << up; g.stride = 1; g.ups = up; g.zstuff = up;
-            g.M = dy.B * g.Hout * g.Wout; g.K = 9 * cw.cout;
-        } else {
-            g.M = (int)dy.rows(); g.K = cw.cout;
-        }
-        if (resid) { g.resid = resid->p; g.ldr = resid->C; }
-        return gemm(g);
-    }
-    // dW, db of y = conv(x): one GEMM per tap over the pixel index (operands transposed into pixel-major scratch)
-    int conv_wgrad(const Act& x, const Act& dy, const ConvW& cw, int stride) {
-        MRISR_REQUIRE(cw.offW >= 0 && a.grad, "adapter gradient vector not bound");
-        const int M = (int)dy.rows(), Mpad = (M + 63) / 64 * 64, taps = cw.ks * cw.ks, pad = cw.ks / 2;
-        const size_t mk = a.arena.mark();
-        // ONE pixel-contraction GEMM per conv: dW[co][tap * Cin + ci] = sum_m dY^T[co][m] * im2col^T[tap * Cin + ci][m]
-        // (one transposed im2col launch for all taps, one GEMM, one scatter-add into the PyTorch layout; per-tap GEMMs
-        // meant 27 launches per conv)
-        T* dyT = static_cast<T*>(alloc((size_t)cw.cout * Mpad * sizeof(T)));
-        T* xT = static_cast<T*>(alloc((size_t)taps * cw.cin * Mpad * sizeof(T)));
-        float* tmp = static_cast<float*>(alloc((size_t)cw.cout * taps * cw.cin * sizeof(float)));
-        if (!dyT || !xT || !tmp) return 7;
-        if (!dry) {
-            if (Mpad != M) MRISR_CHECK_HIP(hipMemsetAsync(dyT, 0, (size_t)cw.cout * Mpad * sizeof(T), st));
-            TRY(launch_transpose<T>(dy.p, dyT, M, cw.cout, cw.cout, Mpad, 0, 0, 1, M, st));
-            if (cw.offB >= 0) TRY(launch_colsum<T>(dy.p, a.grad + cw.offB, M, cw.cout, st));
-            TRY(launch_im2col_all_T<T>(x.p, xT, x.B, x.H, x.W, x.C, dy.H, dy.W, stride, pad, cw.ks, Mpad, st));
-        }
-        GemmArgs g;
-        g.a0 = dyT; g.c0 = Mpad; g.lda0 = Mpad;
-        g.w = xT; g.M = cw.cout; g.N = taps * cw.cin; g.K = Mpad;
-        g.out_mode = OUT_F32; g.out = tmp; g.ldo = taps * cw.cin;
-        TRY(gemm(g));
-        if (!dry) TRY(launch_wgrad_accum_all(tmp, a.grad + cw.offW, cw.cout, cw.cin, taps, st));
-        a.arena.release(mk);
-        return 0;
-    }
-    // d_feats: gradients w.r.t. the four feature maps (what mrisr_train_step wrote through mrisr_train_set_intrablock_grads)
-    // Blocks k_hi .. k_lo (descending) of the backward; the running gradient lives in a.bwd_dcur between calls, so that the host
-    // can cut the pass at level boundaries and start the exchange of a level's finished weight gradients while the lower
-    // levels are still being differentiated (mrisr_adapter_backward_level).
-    int backward_blocks(const mrisr_tensor* d_feats, int n_feats, int k_hi, int k_lo, bool with_conv_in) {
-        MRISR_REQUIRE(a.recorded || dry, "run the adapter forward first");
-        MRISR_REQUIRE(n_feats * a.cfg.nums_rb == (int)a.blocks.size(), "one feature gradient per level");
-        Act dcur = a.bwd_dcur;
-        for (int k = k_hi; k >= k_lo; --k) {
-            AdBlock& b = a.blocks[k];
-            AdRec& r = a.recs[k];
-            if ((k + 1) % a.cfg.nums_rb == 0) {
-                const mrisr_tensor& f = d_feats[(k + 1) / a.cfg.nums_rb - 1];
-                MRISR_REQUIRE(f.ndim == 4 && f.shape[0] == r.y.B && f.shape[1] == r.y.C && f.shape[2] == r.y.H && f.shape[3] == r.y.W,
-                              "adapter feature gradient shape");
-                Act gf = new_act(r.y.B, r.y.H, r.y.W, r.y.C);
-                if (!gf.p) return 7;
-                if (!dry) {
-                    if (f.layout == MRISR_NHWC) {
-                        MRISR_REQUIRE(f.dtype == a.cfg.compute_dtype, "NHWC feature gradients use the compute dtype");
-                        MRISR_CHECK_HIP(hipMemcpyAsync(gf.p, f.data, gf.numel() * sizeof(T), hipMemcpyDeviceToDevice, st));
-                    } else {
-                        TRY(launch_nchw_to_nhwc<T>(f.data, f.dtype, gf.p, gf.B, gf.C, gf.H, gf.W, st));
-                    }
-                    if (dcur.p) TRY(launch_add_inplace<T>(gf.p, dcur.p, (long long)gf.numel(), st));
-                }
-                dcur = gf;
-            }
-            MRISR_REQUIRE(dcur.p, "no gradient reaches the last adapter block");
-            // y = block2(relu(block1(x_pre))) + x_pre
-            TRY(conv_wgrad(r.hmid, dcur, b.b2, 1));
-            Act dh, dx;
-            TRY(conv_dgrad(dcur, b.b2, 1, nullptr, &dh));
-            if (!dry) TRY(launch_relu_bwd<T>(dh.p, r.hmid.p, dh.p, (long long)dh.numel(), st));
-            TRY(conv_wgrad(r.x_pre, dh, b.b1, 1));
-            TRY(conv_dgrad(dh, b.b1, 1, &dcur, &dx));
-            if (b.has_in) {
-                TRY(conv_wgrad(r.x_down, dx, b.in_w, 1));
-                Act d2;
-                TRY(conv_dgrad(dx, b.in_w, 1, nullptr, &d2));
-                dx = d2;
-            }
-            if (b.down) {
-                TRY(conv_wgrad(r.x_in, dx, b.down_w, 2));
-                Act d2;
-                TRY(conv_dgrad(dx, b.down_w, 2, nullptr, &d2));
-                dx = d2;
-            }
-            dcur = dx;
-        }
-        a.bwd_dcur = dcur;
-        if (with_conv_in) return conv_wgrad(a.rec_u, dcur, a.conv_in, 1);
-        return 0;
-    }
-    int backward(const mrisr_tensor* d_feats, int n_feats) {
-        a.bwd_dcur = Act();
-        a.bwd_next_level = -1;
-        return backward_blocks(d_feats, n_feats, (int)a.blocks.size() - 1, 0, true);
-    }
-    // one level (nums_rb blocks) of the backward, levels in descending order; level 0 also differentiates conv_in
-    int backward_level(const mrisr_tensor* d_feats, int n_feats, int level) {
-        const int nlev = (int)a.blocks.size() / a.cfg.nums_rb;
-        MRISR_REQUIRE(level >= 0 && level < nlev, "adapter level");
-        if (level == nlev - 1) { a.bwd_dcur = Act(); a.bwd_next_level = level; }
-        MRISR_REQUIRE(a.bwd_next_level == level, "adapter backward levels must run in descending order, starting at the top level");
-        a.bwd_next_level = level - 1;
-        return backward_blocks(d_feats, n_feats, (level + 1) * a.cfg.nums_rb - 1, level * a.cfg.nums_rb, level == 0);
-    }
-
-    int forward(const mrisr_tensor& x, mrisr_tensor* feats, int n_feats) {
-        a.arena.reset();
-        const int B = (int)x.shape[0], C = (int)x.shape[1], H = (int)x.shape[2], W = (int)x.shape[3];
-        MRISR_REQUIRE(H % 8 == 0 && W % 8 == 0 && C * 64 == a.cfg.cin, "adapter input must be [B, cin/64, 8h, 8w]");
-        Act u = new_act(B, H / 8, W / 8, C * 64);
-        if (!u.p) return 7;
-        if (!dry) TRY(launch_pixel_unshuffle_nchw<T>(x.data, x.dtype, u.p, B, C, H, W, 8, st));
-        return forward_from(u, feats, n_feats);
-    }
-    // the forward from the already-unshuffled input u [B, H/8, W/8, cin] (compute dtype, NHWC); u must stay alive for the backward
-    int forward_from(const Act& u, mrisr_tensor* feats, int n_feats) {
-        Act cur;
-        TRY(conv(u, a.conv_in, 1, ACT_NONE, nullptr, &cur));
-        a.rec_u = u;
-        a.recs.assign(a.blocks.size(), AdRec());
-        int fi = 0;
-        for (size_t k = 0; k < a.blocks.size(); ++k) {
-            AdBlock& b = a.blocks[k];
-            AdRec& rec = a.recs[k];
-            Act y;
-            rec.x_in = cur;
-            if (b.down) { TRY(conv(cur, b.down_w, 2, ACT_NONE, nullptr, &y)); cur = y; }
-            rec.x_down = cur;
-            if (b.has_in) { TRY(conv(cur, b.in_w, 1, ACT_NONE, nullptr, &y)); cur = y; }
-            rec.x_pre = cur;
-            Act hmid;
-            TRY(conv(cur, b.b1, 1, ACT_RELU, nullptr, &hmid));
-            TRY(conv(hmid, b.b2, 1, ACT_NONE, &cur, &y));
-            rec.hmid = hmid;
-            rec.y = y;
-            cur = y;
-            if ((k + 1) % a.cfg.nums_rb == 0) {
-                MRISR_REQUIRE(fi < n_feats, "too few feature outputs");
-                const mrisr_tensor& f = feats[fi++];
-                MRISR_REQUIRE(f.ndim == 4 && f.shape[0] == cur.B && f.shape[1] == cur.C && f.shape[2] == cur.H && f.shape[3] == cur.W,
-                              "adapter feature output shape");
-                if (!dry) {
-                    if (f.layout == MRISR_NHWC) {
-                        MRISR_REQUIRE(f.dtype == a.cfg.compute_dtype, "NHWC feature outputs use the compute dtype");
-                        MRISR_CHECK_HIP(hipMemcpyAsync(f.data, cur.p, cur.numel() * sizeof(T), hipMemcpyDeviceToDevice, st));
-                    } else {
-                        TRY(launch_nhwc_to_nchw<T>(cur.p, f.data, f.dtype, cur.B, cur.C, cur.H, cur.W, 1.0f, st));
-                    }
-                }
-            }
-        }
-        return 0;
-    }
-};
-
-template <typename T>
-static int adapter_finalize_t(mrisr_adapter& a, hipStream_t st) {
-    a.packed.clear();
-    a.blocks.clear();
-    int err = 0;
-    auto conv = [&](const std::string& name) {
-        ConvW c;
-        auto it = a.raw.find(name + ".weight");
-        if (it == a.raw.end()) { set_error("missing parameter: " + name + ".weight"); err = 3; return c; }
-        const RawParam& w = it->second;
-        c.cout = (int)w.shape[0]; c.cin = (int)w.shape[1]; c.ks = (int)w.shape[2];
-        c.name = name;
-        a.packed.emplace_back(new DevBuf());
-        if (a.packed.back()->reserve((size_t)w.numel() * sizeof(T), false)) { err = 4; return c; }
-        c.w = a.packed.back()->p;
-        if (launch_pack_conv3x3<T>(static_cast<const float*>(w.data->p), c.w, c.cout, c.cin, c.ks, st)) err = 5;
-        auto ib = a.raw.find(name + ".bias");
-        c.b = ib == a.raw.end() ? nullptr : static_cast<const float*>(ib->second.data->p);
-        return c;
-    };
-    a.conv_in = conv("conv_in");
-    int k = 0;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < a.cfg.nums_rb; ++j, ++k) {
-            AdBlock b;
-            const std::string n = "body." + std::to_string(k);
-            b.out_c = a.cfg.channels[i];
-            b.in_c = (i > 0 && j == 0) ? a.cfg.channels[i - 1] : b.out_c;
-            b.down = (i > 0 && j == 0);
-            if (b.down) {
-                if (!a.cfg.use_conv) { set_error("avg-pool downsample (use_conv=False) is not built"); return 8; }
-                b.down_w = conv(n + ".down_opt.op");
-            }
-            if (a.raw.count(n + ".in_conv.weight")) { b.has_in = true; b.in_w = conv(n + ".in_conv"); }
-            else if (b.in_c != b.out_c) { set_error("missing parameter: " + n + ".in_conv.weight"); return 3; }
-            if (a.raw.count(n + ".skep.weight")) {
-                // reference quirk: sk=False cannot run in the reference either
-                set_error("Adapter_XL with sk=False is not runnable in the reference (channel mismatch in skep); use sk=True");
-                return 8;
-            }
-            b.b1 = conv(n + ".block1");
-            b.b2 = conv(n + ".block2");
-            a.blocks.push_back(b);
-        }
-    if (err) return err;
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    a.finalized = true;
-    return 0;
-}
-
-// re-pack every conv of the adapter (forward bank, dgrad bank, bias pointer) from the bound trainable vector
-template <typename T>
-static int adapter_repack_t(mrisr_adapter& a, hipStream_t st) {
-    for (ConvW* c : a.all_convs()) {
-        const float* w = a.theta + c->offW;
-        TRY(launch_pack_conv3x3<T>(w, c->w, c->cout, c->cin, c->ks, st));
-        if (c->ks == 3) TRY(launch_pack_conv_dgrad<T>(w, c->wd, c->cout, c->cin, st));
-        else TRY(launch_transpose<T>(c->w, c->wd, c->cout, c->cin, c->cin, c->cout, 0, 0, 1, c->cout, st));
-        if (c->offB >= 0) c->b = a.theta + c->offB;
-    }
-    return 0;
-}
-extern "C" {
-
-int mrisr_adapter_create(const mrisr_adapter_cfg* cfg, mrisr_adapter** out) {
-    API_BEGIN
-    MRISR_REQUIRE(cfg && out, "null argument");
-    MRISR_REQUIRE(cfg->compute_dtype == MRISR_F32 || cfg->compute_dtype == MRISR_BF16, "compute dtype");
-    MRISR_REQUIRE(cfg->ksize == 1 || cfg->ksize == 3, "ksize 1 or 3");
-    auto* a = new mrisr_adapter();
-    a->cfg = *cfg;
-    *out = a;
-    return 0;
-    API_END
-}
-void mrisr_adapter_destroy(mrisr_adapter* a) { delete a; }
-int mrisr_adapter_set_param(mrisr_adapter* a, const char* key, const float* data, const int64_t* shape, int ndim,
-                            int is_device) {
-    API_BEGIN
-    MRISR_REQUIRE(a && key && data, "null argument");
-    RawParam rp;
-    rp.shape.assign(shape, shape + ndim);
-    rp.data = std::make_shared<DevBuf>();
-    TRY(rp.data->reserve((size_t)rp.numel() * sizeof(float), false));
-    MRISR_CHECK_HIP(hipMemcpy(rp.data->p, data, (size_t)rp.numel() * sizeof(float), is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    a->raw[key] = rp;
-    a->finalized = false;
-    return 0;
-    API_END
-}
-int mrisr_adapter_finalize(mrisr_adapter* a, void* stream) {
-    API_BEGIN
-    MRISR_REQUIRE(a, "null handle");
-    TRY(gemm_prepare());
-    if (a->cfg.compute_dtype == MRISR_F32) return adapter_finalize_t<float>(*a, (hipStream_t)stream);
-    return adapter_finalize_t<bf16>(*a, (hipStream_t)stream);
-    API_END
-}
-int mrisr_adapter_forward(mrisr_adapter* a, const mrisr_tensor* x, mrisr_tensor* feats, int n_feats, void* stream) {
-    API_BEGIN
-    MRISR_REQUIRE(a && x && feats && a->finalized, "adapter not finalized / null argument");
-    MRISR_REQUIRE(x->ndim == 4 && x->layout == MRISR_NCHW, "adapter input: NCHW image");
-    hipStream_t st = (hipStream_t)stream;
-    // size the arena with a dry pass (exact), then run
-    int rc;
-    a->fit_plan_key.clear();
-    a->arena.dry = true; a->arena.reset(); a->arena.peak = 0;
-    a->recorded = false;
-    // training: the backward continues in the same arena (the activations must stay put), so size it for both now
-    if (a->cfg.compute_dtype == MRISR_F32) { AdRunner<float> r{*a, st, true}; rc = r.forward(*x, feats, n_feats); if (!rc && a->train_ready) rc = r.backward(feats, n_feats); }
-    else { AdRunner<bf16> r{*a, st, true}; rc = r.forward(*x, feats, n_feats); if (!rc && a->train_ready) rc = r.backward(feats, n_feats); }
-    a->arena.dry = false;
-    if (rc) return rc;
-    if (a->arena.peak + 4096 > a->arena.buf.bytes) MRISR_CHECK_HIP(hipStreamSynchronize(st));  // the old buffer may still be in use
-    TRY(a->arena.buf.reserve(a->arena.peak + 4096, false));
-    if (a->cfg.compute_dtype == MRISR_F32) { AdRunner<float> r{*a, st, false}; rc = r.forward(*x, feats, n_feats); }
-    else { AdRunner<bf16> r{*a, st, false}; rc = r.forward(*x, feats, n_feats); }
-    a->recorded = rc == 0;
-    return rc;
-    API_END
-}
-
-// ---- T2I-Adapter training: flat f32 trainable / gradient vectors owned by the caller (as for the LoRA adapters) ----
-int mrisr_adapter_train_prepare(mrisr_adapter* a, void* stream) {
-    API_BEGIN
-    MRISR_REQUIRE(a && a->finalized, "adapter not finalized");
-    if (a->train_ready) return 0;
-    a->trainables.clear();
-    long long off = 0;
-    const size_t es = a->cfg.compute_dtype == MRISR_F32 ? 4 : 2;
-    for (ConvW* c : a->all_convs()) {
-        MRISR_REQUIRE(c->ks == 1 || c->ks == 3, "adapter conv kernel size");
-        c->offW = off;
-        a->trainables.push_back({c->name + ".weight", off, (long long)c->cout * c->cin * c->ks * c->ks, {c->cout, c->cin, c->ks, c->ks}});
-        off += (long long)c->cout * c->cin * c->ks * c->ks;
-        if (c->b) {
-            c->offB = off;
-            a->trainables.push_back({c->name + ".bias", off, c->cout, {c->cout}});
-            off += c->cout;
-        }
-        a->packed.emplace_back(new DevBuf());
-        TRY(a->packed.back()->reserve((size_t)c->cout * c->cin * c->ks * c->ks * es, false));
-        c->wd = a->packed.back()->p;
-    }
-    a->n_trainable = off;
-    a->train_ready = true;
-    (void)stream;
-    return 0;
-    API_END
-}
-int64_t mrisr_adapter_train_num_trainable(const mrisr_adapter* a) { return a && a->train_ready ? (int64_t)a->n_trainable : -1; }
-int mrisr_adapter_train_num_tensors(const mrisr_adapter* a) { return a && a->train_ready ? (int)a->trainables.size() : -1; }
-int mrisr_adapter_train_tensor_info(const mrisr_adapter* a, int i, const char** key, int64_t* offset, int64_t shape[4], int* ndim) {
-    MRISR_REQUIRE(a && a->train_ready && i >= 0 && i < (int)a->trainables.size() && key && offset && shape && ndim, "adapter trainable index");
-    const AdTrainable& t = a->trainables[i];
-    *key = t.key.c_str();
-    *offset = t.offset;
-    *ndim = (int)t.shape.size();
-    for (size_t k = 0; k < t.shape.size(); ++k) shape[k] = t.shape[k];
-    return 0;
-}
-int mrisr_adapter_train_refresh(mrisr_adapter* a, void* stream) {
-    API_BEGIN
-    MRISR_REQUIRE(a && a->train_ready && a->theta, "bind the adapter's trainable vector first");
-    return a->cfg.compute_dtype == MRISR_F32 ? adapter_repack_t<float>(*a, (hipStream_t)stream) : adapter_repack_t<bf16>(*a, (hipStream_t)stream);
-    API_END
-}
-int mrisr_adapter_train_bind(mrisr_adapter* a, float* theta_dev, float* grad_dev, int init_from_model, void* stream) {
-    API_BEGIN
-    TRY(mrisr_adapter_train_prepare(a, stream));
-    MRISR_REQUIRE(theta_dev && grad_dev, "theta / grad device buffers");
-    a->theta = theta_dev;
-    a->grad = grad_dev;
-    if (init_from_model)
-        for (auto& t : a->trainables) {
-            auto it = a->raw.find(t.key);
-            MRISR_REQUIRE(it != a->raw.end() && it->second.numel() == t.numel, "adapter tensor missing from the loaded parameters");
-            MRISR_CHECK_HIP(hipMemcpyAsync(theta_dev + t.offset, it->second.data->p, (size_t)t.numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-        }
-    return mrisr_adapter_train_refresh(a, stream);
-    API_END
-}
-int mrisr_adapter_backward(mrisr_adapter* a, const mrisr_tensor* d_feats, int n_feats, void* stream) {
-    API_BEGIN
-    MRISR_REQUIRE(a && d_feats && a->train_ready && a->grad, "bind the adapter's trainable vector first");
-    hipStream_t st = (hipStream_t)stream;
-    if (a->cfg.compute_dtype == MRISR_F32) { AdRunner<float> r{*a, st, false}; return r.backward(d_feats, n_feats); }
-    AdRunner<bf16> r{*a, st, false};
-    return r.backward(d_feats, n_feats);
-    API_END
-}
-int mrisr_adapter_backward_level(mrisr_adapter* a, const mrisr_tensor* d_feats, int n_feats, int level, void* stream) {
-    API_BEGIN
-    MRISR_REQUIRE(a && d_feats && a->train_ready && a->grad, "bind the adapter's trainable vector first");
-    hipStream_t st = (hipStream_t)stream;
-    if (a->cfg.compute_dtype == MRISR_F32) { AdRunner<float> r{*a, st, false}; return r.backward_level(d_feats, n_feats, level); }
-    AdRunner<bf16> r{*a, st, false};
-    return r.backward_level(d_feats, n_feats, level);
-    API_END
-}
-int mrisr_adapter_train_level_range(const mrisr_adapter* ac, int level, int64_t* offset, int64_t* numel) {
-    API_BEGIN
-    mrisr_adapter* a = const_cast<mrisr_adapter*>(ac);
-    MRISR_REQUIRE(a && a->train_ready && offset && numel, "adapter not prepared for training");
-    const int rb = a->cfg.nums_rb, nlev = (int)a->blocks.size() / rb;
-    MRISR_REQUIRE(level >= 0 && level < nlev, "adapter level");
-    // all_convs() order = flat-vector order: conv_in, then per block (down, in_conv, block1, block2): a level is one contiguous range
-    auto first_off = [&](AdBlock& b) { return b.down ? b.down_w.offW : (b.has_in ? b.in_w.offW : b.b1.offW); };
-    const long long lo = level == 0 ? 0 : first_off(a->blocks[level * rb]);
-    const long long hi = level + 1 < nlev ? first_off(a->blocks[(level + 1) * rb]) : a->n_trainable;
-    *offset = lo;
-    *numel = hi - lo;
-    return 0;
-    API_END
-}
-
-}  // extern "C"
-
-// ---- the adapter inside mrisr.fit's captured graphs (fit.hip): planning split from the launches ----
-namespace mrisr {
-
-int adapter_fit_info(const mrisr_adapter* a, AdapterFitInfo* out) {
-    MRISR_REQUIRE(a && out && a->finalized, "adapter not finalized");
-    out->compute_dtype = a->cfg.compute_dtype;
-    out->cin = a->cfg.cin;
-    out->nums_rb = a->cfg.nums_rb;
-    out->n_levels = a->cfg.nums_rb > 0 ? (int)a->blocks.size() / a->cfg.nums_rb : 0;
-    for (int i = 0; i < 4; ++i) out->channels[i] = a->cfg.channels[i];
-    out->n_trainable = a->train_ready ? a->n_trainable : 0;
-    out->theta = a->theta;
-    out->grad = a->grad;
-    return 0;
-}
-
-static Act u_act(const mrisr_tensor& u) {
-    Act x;
-    x.p = u.data; x.B = (int)u.shape[0]; x.C = (int)u.shape[1]; x.H = (int)u.shape[2]; x.W = (int)u.shape[3];
-    return x;
-}
-
-int adapter_fit_plan(mrisr_adapter* a, const mrisr_tensor* u, mrisr_tensor* feats, const mrisr_tensor* d_feats, int n_feats, hipStream_t st) {
-    MRISR_REQUIRE(a && u && feats && d_feats && a->finalized && a->train_ready && a->theta && a->grad, "bind the adapter's trainable vector first");
-    MRISR_REQUIRE(u->ndim == 4 && u->layout == MRISR_NHWC && u->dtype == a->cfg.compute_dtype && u->shape[1] == a->cfg.cin,
-                  "adapter input activation: [B, cin, h, w] stored NHWC in the compute dtype");
-    char kb[96];
-    snprintf(kb, sizeof(kb), "B%lld,%lld,%lld,n%d", (long long)u->shape[0], (long long)u->shape[1], (long long)u->shape[2], n_feats);
-    if (a->fit_plan_key == kb) return 0;
-    const Act ua = u_act(*u);
-    a->arena.dry = true; a->arena.reset(); a->arena.peak = 0;
-    a->recorded = false;
-    int rc;
-    if (a->cfg.compute_dtype == MRISR_F32) {
-        AdRunner<float> r{*a, st, true};
-        rc = r.forward_from(ua, feats, n_feats);
-        if (!rc) rc = r.backward(d_feats, n_feats);
-    } else {
-        AdRunner<bf16> r{*a, st, true};
-        rc = r.forward_from(ua, feats, n_feats);
-        if (!rc) rc = r.backward(d_feats, n_feats);
-    }
-    a->arena.dry = false;
-    a->arena.reset();
-    if (rc) return rc;
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));  // the old buffer may still be in use
-    TRY(a->arena.buf.reserve(a->arena.peak + 4096, false));
-    a->fit_plan_key = kb;
-    ++a->fit_plan_gen;
-    return 0;
-}
-
-int adapter_fit_forward(mrisr_adapter* a, const mrisr_tensor* u, mrisr_tensor* feats, int n_feats, hipStream_t st) {
-    MRISR_REQUIRE(a && u && !a->fit_plan_key.empty(), "plan the adapter first (adapter_fit_plan)");
-    a->arena.reset();
-    int rc;
-    if (a->cfg.compute_dtype == MRISR_F32) { AdRunner<float> r{*a, st, false}; rc = r.forward_from(u_act(*u), feats, n_feats); }
-    else { AdRunner<bf16> r{*a, st, false}; rc = r.forward_from(u_act(*u), feats, n_feats); }
-    a->recorded = rc == 0;
-    return rc;
-}
-
-int adapter_fit_backward(mrisr_adapter* a, const mrisr_tensor* d_feats, int n_feats, hipStream_t st) {
-    MRISR_REQUIRE(a && d_feats && a->train_ready && a->grad, "bind the adapter's trainable vector first");
-    if (a->cfg.compute_dtype == MRISR_F32) { AdRunner<float> r{*a, st, false}; return r.backward(d_feats, n_feats); }
-    AdRunner<bf16> r{*a, st, false};
-    return r.backward(d_feats, n_feats);
-}
-
-int adapter_fit_repack(mrisr_adapter* a, hipStream_t st) {
-    MRISR_REQUIRE(a && a->train_ready && a->theta, "bind the adapter's trainable vector first");
-    return a->cfg.compute_dtype == MRISR_F32 ? adapter_repack_t<float>(*a, st) : adapter_repack_t<bf16>(*a, st);
-}
-
-std::string adapter_fit_key(const mrisr_adapter* ac) {
-    mrisr_adapter* a = const_cast<mrisr_adapter*>(ac);
-    char kb[128];
-    snprintf(kb, sizeof(kb), ",ag%llu,aa%p,ath%p,agr%p", a->fit_plan_gen, a->arena.buf.p, (void*)a->theta, (void*)a->grad);
-    std::string k = kb;
-    for (ConvW* c : a->all_convs()) {
-        snprintf(kb, sizeof(kb), ",%p/%p/%p", c->w, c->wd, (const void*)c->b);
-        k += kb;
-    }
-    return k;
-}
-
-}  // namespace mrisr
-
-// =================================================================================================
-// single-op entry points (parity tests drive the very kernels the models launch)
-// =================================================================================================
-template <typename T>
-__global__ void rows_to_heads_kernel(const T* x, T* dst, int B, int N, int H, int hd, int npad, int dpad, int tr) {
-    const long long total = (long long)B * N * H * hd;
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int dd = (int)(i % hd);
-        const int h = (int)((i / hd) % H);
-        const int tok = (int)((i / ((long long)hd * H)) % N);
-        const int b = (int)(i / ((long long)hd * H * N));
-        const size_t bh = (size_t)b * H + h;
-        if (!tr) dst[(bh * npad + tok) * dpad + dd] = x[i];
-        else dst[(bh * dpad + dd) * npad + tok] = x[i];
-    }
-}
-
-template <typename T>
-static int op_conv3x3_t(const mrisr_tensor* x, const mrisr_tensor* x2, const float* w, const float* bias, int cout,
-                        int stride, int ups, int act, int splitk, mrisr_tensor* y, hipStream_t st) {
-    const int B = (int)x->shape[0], C0 = (int)x->shape[1], H = (int)x->shape[2], W = (int)x->shape[3];
-    const int C1 = x2 ? (int)x2->shape[1] : 0;
-    const int Cin = C0 + C1;
-    DevBuf wp, part;
-    TRY(wp.reserve((size_t)cout * Cin * 9 * sizeof(T), false));
-    TRY(launch_pack_conv3x3<T>(w, wp.p, cout, Cin, 3, st));
-    if (!x2 && !ups && Cin % (128 / (int)sizeof(T)) != 0) {
-        // fan-in below one K tile (conv_in: 4 channels): the direct kernels (matrix-core conv_in form for bf16, 4 channels)
-        DirectConvArgs a;
-        a.x = x->data; a.w = wp.p; a.bias = bias; a.y = y->data; a.B = B; a.Hin = H; a.Win = W; a.Cin = Cin;
-        a.Hout = (H - 1) / stride + 1; a.Wout = (W - 1) / stride + 1; a.Cout = cout; a.ks = 3; a.stride = stride; a.pad = 1; a.act = act;
-        MRISR_REQUIRE(y->shape[1] == cout && y->shape[2] == a.Hout && y->shape[3] == a.Wout, "conv output shape");
-        TRY(launch_direct_conv<T>(a, st));
-        MRISR_CHECK_HIP(hipStreamSynchronize(st));
-        return 0;
-    }
-    if (ups == 2) {  // the sub-pixel form of `nearest x2 -> conv3x3` (runner.h::upsample_conv): four 2 x 2 parity convs + interleave
-        MRISR_REQUIRE(sizeof(T) == 2 && !x2 && stride == 1 && act == ACT_NONE && (4 * Cin) % 64 == 0 && cout % 8 == 0, "sub-pixel upsample conv: bf16, single source");
-        MRISR_REQUIRE(y->shape[1] == cout && y->shape[2] == 2 * H && y->shape[3] == 2 * W, "conv output shape");
-        DevBuf sp, planes;
-        TRY(sp.reserve((size_t)16 * cout * Cin * sizeof(T), false));
-        TRY(planes.reserve((size_t)4 * B * H * W * cout * sizeof(T), false));
-        TRY(launch_pack_conv_subpix<T>(w, sp.p, cout, Cin, st));
-        GemmArgs g;
-        g.a0 = x->data; g.c0 = C0; g.lda0 = C0;
-        g.conv = 1; g.B = B; g.Hin = H; g.Win = W; g.Hout = H; g.Wout = W; g.stride = 1;
-        g.kw = 2; g.subpix = 1; g.batch = 4; g.w_bs = (long long)cout * 4 * Cin; g.o_bs = (long long)B * H * W * cout;
-        g.w = sp.p; g.M = B * H * W; g.N = cout; g.K = 4 * Cin; g.bias = bias; g.out = planes.p; g.ldo = cout;
-        TRY(gemm_choose(g, true));
-        TRY(launch_gemm<T>(g, st));
-        TRY(launch_subpix_shuffle<T>(planes.p, y->data, B, H, W, cout, st));
-        MRISR_CHECK_HIP(hipStreamSynchronize(st));
-        return 0;
-    }
-    GemmArgs g;
-    g.a0 = x->data; g.c0 = C0; g.lda0 = C0;
-    if (x2) { g.a1 = x2->data; g.c1 = C1; g.lda1 = C1; }
-    const int Hc = H << ups, Wc = W << ups;
-    g.conv = 1; g.B = B; g.Hin = H; g.Win = W; g.Hout = (Hc - 1) / stride + 1; g.Wout = (Wc - 1) / stride + 1;
-    g.stride = stride; g.ups = ups;
-    MRISR_REQUIRE(y->shape[1] == cout && y->shape[2] == g.Hout && y->shape[3] == g.Wout, "conv output shape");
-    g.w = wp.p; g.M = B * g.Hout * g.Wout; g.N = cout; g.K = 9 * Cin; g.bias = bias; g.act = act;
-    g.out = y->data; g.ldo = cout;
-    g.splitk = splitk;
-    if (splitk <= 0) { g.splitk = 1; TRY(gemm_choose(g, sizeof(T) == 2)); }
-    if (g.splitk > 1) {
-        TRY(part.reserve((size_t)g.splitk * g.M * g.N * sizeof(float), false));
-        g.partial = static_cast<float*>(part.p);
-    }
-    TRY(launch_gemm<T>(g, st));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-}
-
-extern "C" void mrisr_debug_force_tile(int t);
-
-template <typename T>
-static int op_attention_t(const mrisr_tensor* q, const mrisr_tensor* k, const mrisr_tensor* v, int H, int flash,
-                          mrisr_tensor* out, hipStream_t st) {
-    const int B = (int)q->shape[0], N = (int)q->shape[1], C = (int)q->shape[2], Nk = (int)k->shape[1];
-    const int hd = C / H;
-    constexpr int BK = 128 / (int)sizeof(T);
-    const bool use_flash = flash && sizeof(T) == 2;
-    const int dpad = round_up(hd, use_flash ? 32 : BK), npad = round_up(N, 64), nkpad = round_up(Nk, 64);
-    DevBuf qb, kb, vb, sb, pb;
-    TRY(qb.reserve((size_t)B * H * npad * dpad * sizeof(T), true));
-    TRY(kb.reserve((size_t)B * H * nkpad * dpad * sizeof(T), true));
-    TRY(vb.reserve((size_t)B * H * dpad * nkpad * sizeof(T), true));
-    auto conv = [&](const mrisr_tensor* x, void* dst, int n, int np, int tr) {
-        hipLaunchKernelGGL(rows_to_heads_kernel<T>, dim3(1024), dim3(256), 0, st, static_cast<const T*>(x->data),
-                           static_cast<T*>(dst), B, n, H, hd, np, dpad, tr);
-    };
-    conv(q, qb.p, N, npad, 0);
-    conv(k, kb.p, Nk, nkpad, 0);
-    conv(v, vb.p, Nk, nkpad, 1);
-    MRISR_CHECK_HIP(hipGetLastError());
-    const float scale = 1.0f / sqrtf((float)hd);
-    if (use_flash) {
-        AttnArgs a;
-        a.q = qb.p; a.k = kb.p; a.vt = vb.p; a.out = out->data;
-        a.B = B; a.H = H; a.nq = N; a.nk = Nk; a.nkpad = nkpad; a.hd = hd; a.dpad = dpad; a.scale = scale;
-        if (flash == 2) {  // fp8 (OCP e4m3) Q K^T and P V
-            DevBuf k8, v8, sc;
-            TRY(k8.reserve((size_t)B * H * nkpad * dpad, false));
-            TRY(v8.reserve((size_t)B * H * nkpad * dpad, false));
-            TRY(sc.reserve((size_t)B * H * 4 * sizeof(float), false));
-            a.k8 = k8.p; a.vt8 = v8.p; a.f8_scales = static_cast<float*>(sc.p);
-            TRY(launch_attention_fp8(a, st));
-            MRISR_CHECK_HIP(hipStreamSynchronize(st));
-        } else {
-            TRY(launch_attention_bf16(a, st));
-        }
-    } else {
-        const int BH = B * H;
-        TRY(sb.reserve((size_t)BH * N * nkpad * sizeof(float), false));
-        void* P = sb.p;
-        if (sizeof(T) == 2) { TRY(pb.reserve((size_t)BH * N * nkpad * sizeof(T), false)); P = pb.p; }
-        GemmArgs g;
-        g.a0 = qb.p; g.c0 = dpad; g.lda0 = dpad; g.a_bs = (long long)npad * dpad;
-        g.w = kb.p; g.w_bs = (long long)nkpad * dpad; g.M = N; g.N = nkpad; g.K = dpad; g.batch = BH; g.alpha = scale;
-        g.out_mode = OUT_F32; g.out = sb.p; g.ldo = nkpad; g.o_bs = (long long)N * nkpad;
-        TRY(launch_gemm<T>(g, st));
-        TRY(launch_softmax_rows<T>(static_cast<const float*>(sb.p), nkpad, P, nkpad, (long long)BH * N, Nk, st));
-        GemmArgs o;
-        o.a0 = P; o.c0 = nkpad; o.lda0 = nkpad; o.a_bs = (long long)N * nkpad;
-        o.w = vb.p; o.w_bs = (long long)dpad * nkpad; o.M = N; o.N = hd; o.K = nkpad; o.batch = BH;
-        o.heads = H; o.o_bs = (long long)N * C; o.o_hs = hd; o.out = out->data; o.ldo = C;
-        TRY(launch_gemm<T>(o, st));
-    }
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-}
-
-
-extern "C" {
-
-static int op_dtype_ok(const mrisr_tensor* x) {
-    MRISR_REQUIRE(x && (x->dtype == MRISR_F32 || x->dtype == MRISR_BF16), "op tensors: f32 or bf16");
-    return 0;
-}
-
-int mrisr_op_conv3x3(const mrisr_tensor* x, const mrisr_tensor* x2, const float* w_oihw_dev, const float* bias_dev,
-                     int cout, int stride, int upsample, int act, int splitk, int tile, mrisr_tensor* y,
-                     void* stream) {
-    API_BEGIN
-    TRY(op_dtype_ok(x));
-    TRY(gemm_prepare());
-    MRISR_REQUIRE(x->layout == MRISR_NHWC && y && y->layout == MRISR_NHWC && y->dtype == x->dtype, "NHWC in/out, same dtype");
-    mrisr_debug_force_tile(tile);
-    int rc = x->dtype == MRISR_F32
-                 ? op_conv3x3_t<float>(x, x2, w_oihw_dev, bias_dev, cout, stride, upsample, act, splitk, y, (hipStream_t)stream)
-                 : op_conv3x3_t<bf16>(x, x2, w_oihw_dev, bias_dev, cout, stride, upsample, act, splitk, y, (hipStream_t)stream);
-    mrisr_debug_force_tile(0);
-    return rc;
-    API_END
-}
-
-int mrisr_op_linear(const mrisr_tensor* x, const float* w_dev, const float* bias_dev, int n, int act, int splitk,
-                    int tile, mrisr_tensor* y, void* stream) {
-    API_BEGIN
-    TRY(op_dtype_ok(x));
-    TRY(gemm_prepare());
-    MRISR_REQUIRE(x->ndim == 2 && y && y->ndim == 2 && y->dtype == x->dtype, "rows in/out");
-    hipStream_t st = (hipStream_t)stream;
-    const int M = (int)x->shape[0], K = (int)x->shape[1];
-    const bool f32 = x->dtype == MRISR_F32;
-    const int esz = f32 ? 4 : 2;
-    DevBuf wp, part, bp;
-    TRY(wp.reserve((size_t)n * K * esz, false));
-    const bool geglu = act == ACT_GEGLU;
-    if (f32) TRY(launch_pack_rows<float>(w_dev, n, K, wp.p, K, 0, 0, geglu ? 1 : 0, n / 2, 1.0f, st));
-    else TRY(launch_pack_rows<bf16>(w_dev, n, K, wp.p, K, 0, 0, geglu ? 1 : 0, n / 2, 1.0f, st));
-    const float* bias = bias_dev;
-    if (geglu && bias_dev) {
-        TRY(bp.reserve((size_t)n * sizeof(float), false));
-        TRY(launch_pack_bias_geglu(bias_dev, static_cast<float*>(bp.p), n / 2, st));
-        bias = static_cast<const float*>(bp.p);
-    }
-    GemmArgs g;
-    g.a0 = x->data; g.c0 = K; g.lda0 = K; g.w = wp.p; g.M = M; g.N = n; g.K = K; g.bias = bias; g.act = act;
-    g.out = y->data; g.ldo = (int)y->shape[1];
-    g.splitk = splitk;
-    if (splitk <= 0) { g.splitk = 1; mrisr_debug_force_tile(tile); TRY(gemm_choose(g, !f32)); }
-    if (g.splitk > 1) {
-        TRY(part.reserve((size_t)g.splitk * M * n * sizeof(float), false));
-        g.partial = static_cast<float*>(part.p);
-    }
-    mrisr_debug_force_tile(tile);
-    int rc = f32 ? launch_gemm<float>(g, st) : launch_gemm<bf16>(g, st);
-    mrisr_debug_force_tile(0);
-    if (rc) return rc;
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-    API_END
-}
-
-int mrisr_op_ln_linear(const mrisr_tensor* x, const float* gamma_dev, const float* beta_dev, const float* w_dev, const float* bias_dev,
-                       int n, int act, mrisr_tensor* y, void* stream) {
-    API_BEGIN
-    TRY(op_dtype_ok(x));
-    TRY(gemm_prepare());
-    MRISR_REQUIRE(x->ndim == 2 && y && y->ndim == 2 && y->dtype == x->dtype && x->dtype == MRISR_BF16, "bf16 rows in/out");
-    MRISR_REQUIRE(gamma_dev && beta_dev && w_dev, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    const int M = (int)x->shape[0], K = (int)x->shape[1];
-    DevBuf wp, bp;
-    TRY(wp.reserve((size_t)n * K * 2, false));
-    const bool geglu = act == ACT_GEGLU;
-    TRY(launch_pack_rows<bf16>(w_dev, n, K, wp.p, K, 0, 0, geglu ? 1 : 0, n / 2, 1.0f, st));
-    const float* bias = bias_dev;
-    if (geglu && bias_dev) {
-        TRY(bp.reserve((size_t)n * sizeof(float), false));
-        TRY(launch_pack_bias_geglu(bias_dev, static_cast<float*>(bp.p), n / 2, st));
-        bias = static_cast<const float*>(bp.p);
-    }
-    GemmArgs g;
-    g.a0 = x->data; g.c0 = K; g.lda0 = K; g.w = wp.p; g.M = M; g.N = n; g.K = K; g.bias = bias; g.act = act;
-    g.out = y->data; g.ldo = (int)y->shape[1];
-    MRISR_REQUIRE(gemm_rp_tile(g) != 0, "LayerNorm prologue: the row-panel kernel does not take this shape (K = 320 / 640, N % 16 == 0)");
-    g.ln_gamma = gamma_dev; g.ln_beta = beta_dev; g.ln_eps = 1e-5f;
-    TRY(gemm_choose(g, true));
-    TRY(launch_gemm<bf16>(g, st));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-    API_END
-}
-
-int mrisr_op_mlp(const mrisr_tensor* x, const float* gamma_dev, const float* beta_dev, const float* w1_dev, const float* b1_dev,
-                 const float* w2_dev, const float* b2_dev, int hidden, int residual, mrisr_tensor* y, void* stream) {
-    API_BEGIN
-    TRY(op_dtype_ok(x));
-    TRY(gemm_prepare());
-    MRISR_REQUIRE(x->ndim == 2 && y && y->ndim == 2 && y->dtype == x->dtype && x->dtype == MRISR_BF16, "bf16 rows in/out");
-    MRISR_REQUIRE(gamma_dev && beta_dev && w1_dev && w2_dev, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    const int M = (int)x->shape[0], C = (int)x->shape[1], N2 = (int)y->shape[1];
-    MRISR_REQUIRE(y->shape[0] == M && mlp_fused_ok(C, hidden, N2), "fused feed-forward: C = 320 rows in and out, hidden % 32 == 0");
-    DevBuf w1p, b1p, w2b, w2p;
-    TRY(w1p.reserve((size_t)2 * hidden * C * 2, false));
-    TRY(w2b.reserve((size_t)N2 * hidden * 2, false));
-    TRY(w2p.reserve((size_t)N2 * hidden * 2, false));
-    TRY(launch_pack_rows<bf16>(w1_dev, 2 * hidden, C, w1p.p, C, 0, 0, 1, hidden, 1.0f, st));
-    TRY(launch_pack_rows<bf16>(w2_dev, N2, hidden, w2b.p, hidden, 0, 0, 0, 0, 1.0f, st));
-    TRY(launch_pack_mlp_w2(w2b.p, w2p.p, N2, hidden, st));
-    const float* b1 = nullptr;
-    if (b1_dev) {
-        TRY(b1p.reserve((size_t)2 * hidden * sizeof(float), false));
-        TRY(launch_pack_bias_geglu(b1_dev, static_cast<float*>(b1p.p), hidden, st));
-        b1 = static_cast<const float*>(b1p.p);
-    }
-    MlpArgs a;
-    a.x = x->data; a.ldx = C; a.M = M; a.ln_gamma = gamma_dev; a.ln_beta = beta_dev; a.ln_eps = 1e-5f;
-    a.w1 = w1p.p; a.b1 = b1; a.w2p = w2p.p; a.b2 = b2_dev;
-    a.resid = residual ? x->data : nullptr; a.ldr = C; a.out = y->data; a.ldo = N2; a.C = C; a.H = hidden; a.N2 = N2;
-    TRY(launch_mlp_fused(a, st));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-    API_END
-}
-
-int mrisr_op_linear_fp8(const mrisr_tensor* x, const float* gamma_dev, const float* beta_dev, const float* w_dev, const float* bias_dev,
-                        int n, int act, mrisr_tensor* y, void* stream) {
-    API_BEGIN
-    TRY(op_dtype_ok(x));
-    TRY(gemm_prepare());
-    MRISR_REQUIRE(x->ndim == 2 && y && y->ndim == 2 && y->dtype == x->dtype && x->dtype == MRISR_BF16 && w_dev, "bf16 rows in/out");
-    hipStream_t st = (hipStream_t)stream;
-    const int M = (int)x->shape[0], K = (int)x->shape[1];
-    DevBuf wp, w8, ws, bp;
-    TRY(wp.reserve((size_t)n * K * 2, false));
-    TRY(w8.reserve((size_t)n * K, false));
-    TRY(ws.reserve((size_t)n * sizeof(float), false));
-    const bool geglu = act == ACT_GEGLU;
-    TRY(launch_pack_rows<bf16>(w_dev, n, K, wp.p, K, 0, 0, geglu ? 1 : 0, n / 2, 1.0f, st));
-    TRY(launch_quant_rows_fp8(wp.p, n, K, w8.p, static_cast<float*>(ws.p), st));
-    const float* bias = bias_dev;
-    if (geglu && bias_dev) {
-        TRY(bp.reserve((size_t)n * sizeof(float), false));
-        TRY(launch_pack_bias_geglu(bias_dev, static_cast<float*>(bp.p), n / 2, st));
-        bias = static_cast<const float*>(bp.p);
-    }
-    GemmArgs g;
-    g.a0 = x->data; g.c0 = K; g.lda0 = K; g.w = wp.p; g.M = M; g.N = n; g.K = K; g.bias = bias; g.act = act;
-    g.out = y->data; g.ldo = (int)y->shape[1];
-    g.w8 = w8.p; g.w_scale = static_cast<const float*>(ws.p);
-    MRISR_REQUIRE(gemm_rp_tile(g) != 0, "fp8 operands: the row-panel kernel does not take this shape (K = 320 / 640, N % 16 == 0)");
-    if (gamma_dev) { g.ln_gamma = gamma_dev; g.ln_beta = beta_dev; g.ln_eps = 1e-5f; }
-    TRY(gemm_choose(g, true));
-    TRY(launch_gemm<bf16>(g, st));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-    API_END
-}
-
-int mrisr_op_groupnorm(const mrisr_tensor* x, const mrisr_tensor* x2, const float* gamma_dev, const float* beta_dev,
-                       int groups, float eps, int silu, mrisr_tensor* y, void* stream) {
-    API_BEGIN
-    TRY(op_dtype_ok(x));
-    MRISR_REQUIRE(x->layout == MRISR_NHWC && y && y->dtype == x->dtype, "NHWC in/out, same dtype");
-    hipStream_t st = (hipStream_t)stream;
-    GroupNormArgs a;
-    a.x0 = x->data; a.c0 = (int)x->shape[1];
-    if (x2) { a.x1 = x2->data; a.c1 = (int)x2->shape[1]; }
-    a.B = (int)x->shape[0]; a.HW = (int)(x->shape[2] * x->shape[3]); a.groups = groups; a.eps = eps;
-    a.gamma = gamma_dev; a.beta = beta_dev; a.silu = silu; a.y = y->data;
-    a.nsplit = groupnorm_nsplit(a.B, a.HW);
-    DevBuf part;
-    TRY(part.reserve((size_t)a.B * a.nsplit * groups * 2 * sizeof(float), false));
-    a.partial = static_cast<float*>(part.p);
-    int rc = x->dtype == MRISR_F32 ? launch_groupnorm<float>(a, st) : launch_groupnorm<bf16>(a, st);
-    if (rc) return rc;
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-    API_END
-}
-
-int mrisr_op_layernorm(const mrisr_tensor* x, const float* gamma_dev, const float* beta_dev, float eps,
-                       mrisr_tensor* y, void* stream) {
-    API_BEGIN
-    TRY(op_dtype_ok(x));
-    MRISR_REQUIRE(x->ndim == 2 && y && y->dtype == x->dtype, "rows in/out");
-    hipStream_t st = (hipStream_t)stream;
-    const int M = (int)x->shape[0], C = (int)x->shape[1];
-    return x->dtype == MRISR_F32 ? launch_layernorm<float>(x->data, y->data, gamma_dev, beta_dev, M, C, eps, st)
-                                 : launch_layernorm<bf16>(x->data, y->data, gamma_dev, beta_dev, M, C, eps, st);
-    API_END
-}
-
-int mrisr_op_attention(const mrisr_tensor* q, const mrisr_tensor* k, const mrisr_tensor* v, int heads, int flash,
-                       mrisr_tensor* out, void* stream) {
-    API_BEGIN
-    TRY(op_dtype_ok(q));
-    TRY(gemm_prepare());
-    MRISR_REQUIRE(q->ndim == 3 && k && v && out && k->dtype == q->dtype && v->dtype == q->dtype && out->dtype == q->dtype,
-                  "q,k,v,out: [B,N,C] same dtype");
-    return q->dtype == MRISR_F32 ? op_attention_t<float>(q, k, v, heads, flash, out, (hipStream_t)stream)
-                                 : op_attention_t<bf16>(q, k, v, heads, flash, out, (hipStream_t)stream);
-    API_END
-}
-
-}  // extern "C"
-
-// flash attention forward (with log-sum-exp) + backward on bf16 token rows: the kernels the fine-tuning step runs
-static int op_attention_bwd_bf16(const mrisr_tensor* q, const mrisr_tensor* k, const mrisr_tensor* v, const mrisr_tensor* dout, int H,
-                                 mrisr_tensor* dq, mrisr_tensor* dk, mrisr_tensor* dv, hipStream_t st) {
-    typedef bf16 T;
-    const int B = (int)q->shape[0], N = (int)q->shape[1], C = (int)q->shape[2], Nk = (int)k->shape[1];
-    const int hd = C / H, BH = B * H;
-    const int dpad = round_up(hd, 32), npad = round_up(N, 64), nkpad = round_up(Nk, 64);
-    const size_t qsz = (size_t)BH * npad * dpad * sizeof(T), ksz = (size_t)BH * nkpad * dpad * sizeof(T);
-    DevBuf qb, kb, vtb, vb, ktb, qtb, doh, doht, ob, lse, dsum;
-    TRY(qb.reserve(qsz, true)); TRY(kb.reserve(ksz, true)); TRY(vtb.reserve(ksz, true)); TRY(vb.reserve(ksz, true));
-    TRY(ktb.reserve(ksz, true)); TRY(qtb.reserve(qsz, true)); TRY(doh.reserve(qsz, true)); TRY(doht.reserve(qsz, true));
-    TRY(ob.reserve((size_t)B * N * C * sizeof(T), false));
-    TRY(lse.reserve((size_t)BH * npad * sizeof(float), true)); TRY(dsum.reserve((size_t)BH * npad * sizeof(float), true));
-    auto conv = [&](const mrisr_tensor* x, void* dst, int n, int np, int tr) {
-        hipLaunchKernelGGL(rows_to_heads_kernel<T>, dim3(1024), dim3(256), 0, st, static_cast<const T*>(x->data), static_cast<T*>(dst), B,
-                           n, H, hd, np, dpad, tr);
-    };
-    conv(q, qb.p, N, npad, 0);
-    conv(k, kb.p, Nk, nkpad, 0);
-    conv(v, vtb.p, Nk, nkpad, 1);
-    MRISR_CHECK_HIP(hipGetLastError());
-    const float scale = 1.0f / sqrtf((float)hd);
-    AttnArgs a;
-    a.q = qb.p; a.k = kb.p; a.vt = vtb.p; a.out = ob.p;
-    a.B = B; a.H = H; a.nq = N; a.nk = Nk; a.nkpad = nkpad; a.hd = hd; a.dpad = dpad; a.scale = scale;
-    a.lse = static_cast<float*>(lse.p);
-    TRY(launch_attention_bf16(a, st));
-    TRY(launch_attention_bwd_prep(dout->data, ob.p, doh.p, static_cast<float*>(dsum.p), B, N, H, hd, npad, dpad, st));
-    TRY(launch_transpose<T>(vtb.p, vb.p, dpad, nkpad, nkpad, dpad, (long long)dpad * nkpad, (long long)nkpad * dpad, BH, dpad, st));
-    TRY(launch_transpose<T>(kb.p, ktb.p, nkpad, dpad, dpad, nkpad, (long long)nkpad * dpad, (long long)dpad * nkpad, BH, nkpad, st));
-    TRY(launch_transpose<T>(qb.p, qtb.p, npad, dpad, dpad, npad, (long long)npad * dpad, (long long)dpad * npad, BH, npad, st));
-    TRY(launch_transpose<T>(doh.p, doht.p, npad, dpad, dpad, npad, (long long)npad * dpad, (long long)dpad * npad, BH, npad, st));
-    AttnBwdArgs g;
-    g.q = qb.p; g.k = kb.p; g.v = vb.p; g.doh = doh.p; g.qt = qtb.p; g.kt = ktb.p; g.doht = doht.p;
-    g.lse = static_cast<const float*>(lse.p); g.dsum = static_cast<const float*>(dsum.p);
-    g.dq = dq->data; g.ldq = C; g.dk = dk->data; g.dv = dv->data; g.ldkv = C;
-    g.B = B; g.H = H; g.nq = N; g.nk = Nk; g.npad = npad; g.nkpad = nkpad; g.hd = hd; g.dpad = dpad; g.scale = scale;
-    TRY(launch_attention_bwd_bf16(g, st));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-}
-
-extern "C" int mrisr_op_attention_bwd(const mrisr_tensor* q, const mrisr_tensor* k, const mrisr_tensor* v, const mrisr_tensor* dout,
-                                      int heads, mrisr_tensor* dq, mrisr_tensor* dk, mrisr_tensor* dv, void* stream) {
-    API_BEGIN
-    MRISR_REQUIRE(q && k && v && dout && dq && dk && dv && q->ndim == 3 && q->dtype == MRISR_BF16 && k->dtype == MRISR_BF16 &&
-                      v->dtype == MRISR_BF16 && dout->dtype == MRISR_BF16 && dq->dtype == MRISR_BF16 && dk->dtype == MRISR_BF16 &&
-                      dv->dtype == MRISR_BF16,
-                  "attention backward: bf16 [B,N,C] tensors");
-    MRISR_REQUIRE(heads >= 1 && q->shape[2] % heads == 0 && (q->shape[2] / heads) % 4 == 0, "head dim must be a multiple of 4");
-    return op_attention_bwd_bf16(q, k, v, dout, heads, dq, dk, dv, (hipStream_t)stream);
-    API_END
-}
-
-// =================================================================================================
-// single-op entry points of the backward (tests/test_gpu_bwd_ops.py): the launchers of bwd.hip and the two composites of train_ops.h on
-// the caller's device pointers.  Every argument the kernels index or vector-load by is checked before the first launch.
-// =================================================================================================
-namespace {
-struct OpScratch {  // scratch of one call: freed when the entry returns (after its stream synchronisation)
-    std::vector<std::unique_ptr<DevBuf>> bufs;
-    void* alloc(size_t bytes, bool zero = false) {
-        bufs.emplace_back(new DevBuf());
-        if (bufs.back()->reserve(bytes ? bytes : 1, zero)) return nullptr;
-        return bufs.back()->p;
-    }
-};
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline int bwd_dtype_ok(int dtype) {
-    MRISR_REQUIRE(dtype == MRISR_F32 || dtype == MRISR_BF16, "backward ops: f32 or bf16 operands");
-    return 0;
-}
-template <typename T>
-int op_gemm_run(OpScratch& sc, hipStream_t st, GemmArgs& g) {  // Runner::run_gemm on scratch buffers
-    TRY(gemm_choose(g, sizeof(T) == 2));
-    if (g.splitk > 1) {
-        g.partial = static_cast<float*>(sc.alloc((size_t)g.splitk * g.batch * g.M * g.N * sizeof(float)));
-        if (!g.partial) return 7;
-    }
-    return launch_gemm<T>(g, st);
-}
-
-template <typename T>
-int op_groupnorm_bwd_t(const void* x0, int c0, const void* x1, int c1, int B, int HW, const float* gamma, const float* beta, int groups,
-                       float eps, int silu, const void* dy, void* dx0, int acc0, void* dx1, int acc1, float* g_gamma, float* g_beta,
-                       hipStream_t st) {
-    constexpr int VE = 16 / (int)sizeof(T);
-    const int C = c0 + c1;
-    MRISR_REQUIRE(c0 % VE == 0 && c1 % VE == 0, "GroupNorm backward: channel counts in whole 16-byte vectors");
-    MRISR_REQUIRE(al16(x0) && al16(x1) && al16(dy) && al16(dx0) && al16(dx1), "GroupNorm backward: 16-byte aligned operands");
-    {
-        const int nvec = C / VE;
-        int vpt = 1;
-        while (nvec / vpt > 256 || (nvec % vpt) != 0) ++vpt;
-        MRISR_REQUIRE(vpt <= 4, "GroupNorm backward: too many channels");
-    }
-    OpScratch sc;
-    GroupNormArgs f;
-    f.x0 = x0; f.c0 = c0; f.x1 = x1; f.c1 = c1; f.B = B; f.HW = HW; f.groups = groups; f.eps = eps;
-    f.gamma = gamma; f.beta = beta; f.silu = silu;
-    f.nsplit = groupnorm_nsplit(B, HW);
-    const size_t pbytes = (size_t)B * f.nsplit * groups * 2 * sizeof(float);
-    f.y = sc.alloc((size_t)B * HW * C * sizeof(T));
-    f.partial = static_cast<float*>(sc.alloc(pbytes));
-    GroupNormBwdArgs a;
-    a.x0 = x0; a.c0 = c0; a.x1 = x1; a.c1 = c1; a.B = B; a.HW = HW; a.groups = groups; a.eps = eps;
-    a.gamma = gamma; a.beta = beta; a.silu = silu;
-    a.dy = dy; a.dx0 = dx0; a.dx1 = dx1; a.acc0 = acc0 ? 1 : 0; a.acc1 = acc1 ? 1 : 0;
-    a.fwd_partial = f.partial; a.nsplit = f.nsplit;
-    a.bwd_partial = static_cast<float*>(sc.alloc(pbytes));
-    if (!f.y || !f.partial || !a.bwd_partial) return 7;
-    TRY(launch_groupnorm<T>(f, st));  // the forward statistics, exactly as the recorded forward leaves them
-    TRY(launch_groupnorm_bwd<T>(a, st));
-    if (g_gamma) TRY(launch_gn_affine_grad<T>(x0, dy, gamma, beta, f.partial, f.nsplit, groups, B, HW, C, eps, silu ? 1 : 0, g_gamma, g_beta, st));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-}
-
-template <typename T>
-int op_lora_wgrad_t(const void* P, int ldp, const float* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN, float* const out[3],
-                    float scale, hipStream_t st) {
-    constexpr int VE = 16 / (int)sizeof(T);
-    MRISR_REQUIRE(C % VE == 0 && ldp % VE == 0 && ldp >= C && al16(P), "LoRA wgrad: P rows in whole, aligned 16-byte vectors");
-    MRISR_REQUIRE(mode == 1 || (secN % VE == 0 && C == nmod * secN), "LoRA wgrad (dB): C = nmod sections of whole vectors");
-    const int R = nmod * r, nq = (mode == 0 || R > 16) ? r : R;
-    {   // the LDS tile of the kernel's geometry (lora_wgrad_geom)
-        const int cx = C / VE, gx = (cx + 255) / 256, cxb = (cx + gx - 1) / gx, RL = 256 / cxb;
-        MRISR_REQUIRE(RL <= 1 || (size_t)cxb * VE * nq * sizeof(float) <= 65536, "LoRA wgrad: LDS tile");
-    }
-    OpScratch sc;
-    float* scratch = static_cast<float*>(sc.alloc(lora_wgrad_scratch_bytes(M, C, R, sizeof(T))));
-    if (!scratch) return 7;
-    TRY(launch_lora_wgrad<T>(P, ldp, Q, ldq, M, C, mode, r, nmod, secN, out, scale, scratch, st));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-}
-
-template <typename T>
-int op_conv_wgrad_t(const void* x, int xB, int xH, int xW, int cin_src, const void* dY, int ldy, int col0, int cout_src, int ks, int stride,
-                    float* gW, float* gB, int cout, int cin, int geglu_half, hipStream_t st) {
-    OpScratch sc;
-    const int Ho = (xH - 1) / stride + 1, Wo = (xW - 1) / stride + 1;
-    TRY(conv_wgrad_run<T>(st, false, [&](size_t n) { return sc.alloc(n); }, [&](GemmArgs& g) { return op_gemm_run<T>(sc, st, g); }, x, xB, xH,
-                          xW, cin_src, dY, ldy, col0, Ho, Wo, cout_src, ks, stride, gW, gB, cout, cin, geglu_half));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-}
-
-template <typename T>
-int op_conv_dgrad_t(const void* dy, int B, int H, int W, int cout, const float* w, int cin, int mode, void* dx, int accumulate,
-                    hipStream_t st) {
-    OpScratch sc;
-    void* wd = sc.alloc((size_t)cout * cin * 9 * sizeof(T));
-    if (!wd) return 7;
-    TRY(launch_pack_conv_dgrad<T>(w, wd, cout, cin, st));  // the packer of train_prepare
-    TRY(conv_dgrad_run<T>(st, false, [&](GemmArgs& g) { return op_gemm_run<T>(sc, st, g); }, dy, B, H, W, cout, cin, wd, mode, dx,
-                          accumulate != 0));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-}
-}  // namespace
-
-#define BWD_DISPATCH(dtype, fn, ...) ((dtype) == MRISR_F32 ? fn<float>(__VA_ARGS__) : fn<bf16>(__VA_ARGS__))
-
-extern "C" {
-
-int mrisr_op_groupnorm_bwd(int dtype, const void* x0, int c0, const void* x1, int c1, int B, int HW, const float* gamma_dev,
-                           const float* beta_dev, int groups, float eps, int silu, const void* dy, void* dx0, int acc0, void* dx1,
-                           int acc1, float* g_gamma, float* g_beta, void* stream) {
-    API_BEGIN
-    TRY(bwd_dtype_ok(dtype));
-    MRISR_REQUIRE(x0 && gamma_dev && beta_dev && dy && dx0 && B >= 1 && HW >= 1 && c0 >= 1 && c1 >= 0, "GroupNorm backward: null / empty operand");
-    MRISR_REQUIRE((c1 > 0) == (x1 != nullptr) && (c1 > 0) == (dx1 != nullptr), "GroupNorm backward: x1 / dx1 exactly when c1 > 0");
-    MRISR_REQUIRE(groups >= 1 && groups <= 64 && (c0 + c1) % groups == 0, "GroupNorm backward: at most 64 groups dividing the channels");
-    MRISR_REQUIRE((g_gamma != nullptr) == (g_beta != nullptr) && (!g_gamma || c1 == 0), "GroupNorm affine gradients: both, on a single source");
-    return BWD_DISPATCH(dtype, op_groupnorm_bwd_t, x0, c0, x1, c1, B, HW, gamma_dev, beta_dev, groups, eps, silu, dy, dx0, acc0, dx1, acc1,
-                        g_gamma, g_beta, (hipStream_t)stream);
-    API_END
-}
-
-int mrisr_op_layernorm_bwd(int dtype, const void* x, const void* dy, void* dx, const float* gamma_dev, int M, int C, float eps,
-                           int accumulate, float* g_gamma, float* g_beta, void* stream) {
-    API_BEGIN
-    TRY(bwd_dtype_ok(dtype));
-    hipStream_t st = (hipStream_t)stream;
-    const int VE = dtype == MRISR_F32 ? 4 : 8;
-    MRISR_REQUIRE(x && dy && (dx || g_gamma) && M >= 1 && C >= 1, "LayerNorm backward: null / empty operand");
-    MRISR_REQUIRE(!dx || (gamma_dev && C % VE == 0 && C / VE <= 5 * 64 && al16(x) && al16(dy) && al16(dx)),
-                  "LayerNorm backward: rows of at most 320 aligned 16-byte vectors");
-    MRISR_REQUIRE((g_gamma != nullptr) == (g_beta != nullptr) && (!g_gamma || C <= 64 * 24), "LayerNorm affine gradients: both, C <= 1536");
-    if (dx) TRY(BWD_DISPATCH(dtype, launch_layernorm_bwd, x, dy, dx, gamma_dev, M, C, eps, accumulate ? 1 : 0, st));
-    if (g_gamma) TRY(BWD_DISPATCH(dtype, launch_ln_affine_grad, x, dy, M, C, eps, g_gamma, g_beta, st));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-    API_END
-}
-
-int mrisr_op_geglu(int dtype, int backward, const void* pre, const void* dout, void* out, int64_t M, int half, void* stream) {
-    API_BEGIN
-    TRY(bwd_dtype_ok(dtype));
-    hipStream_t st = (hipStream_t)stream;
-    MRISR_REQUIRE(pre && out && (!backward || dout) && M >= 1 && half >= 16, "GEGLU: null / empty operand");
-    MRISR_REQUIRE(half % 16 == 0, "GEGLU: the (value, gate) interleave is 16 columns wide");
-    if (backward) TRY(BWD_DISPATCH(dtype, launch_geglu_bwd, pre, dout, out, (long long)M, half, st));
-    else TRY(BWD_DISPATCH(dtype, launch_geglu_fwd, pre, out, (long long)M, half, st));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-    API_END
-}
-
-int mrisr_op_pointwise_bwd(int kind, int dtype, const void* a, const void* b, void* out, float* out_f32, int64_t n, int B, int H, int W,
-                           int C, int flag, int ld_out, int off, void* stream) {
-    API_BEGIN
-    TRY(bwd_dtype_ok(dtype));
-    hipStream_t st = (hipStream_t)stream;
-    MRISR_REQUIRE(kind >= 0 && kind <= 5 && a, "pointwise backward: kind 0..5, operand a");
-    if (kind <= 1) {
-        MRISR_REQUIRE(b && out && n >= 1, "silu_bwd / relu_bwd: b, out, n elements");
-        if (kind == 0) TRY(BWD_DISPATCH(dtype, launch_silu_bwd, a, b, out, (long long)n, st));
-        else TRY(BWD_DISPATCH(dtype, launch_relu_bwd, a, b, out, (long long)n, st));
-    } else {
-        MRISR_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 1 && (long long)B * H * W * C < (1ll << 31), "pointwise backward: [B][H][W][C] extents");
-        if (kind == 2) {
-            MRISR_REQUIRE(out, "sumpool2: out");
-            TRY(BWD_DISPATCH(dtype, launch_sumpool2, a, out, B, H, W, C, flag ? 1 : 0, st));
-        } else if (kind == 3) {
-            MRISR_REQUIRE(b && out && out_f32, "mse_grad: target, d pred, loss");
-            MRISR_CHECK_HIP(hipMemsetAsync(out_f32, 0, sizeof(float), st));
-            TRY(BWD_DISPATCH(dtype, launch_mse_grad, a, static_cast<const float*>(b), out, out_f32, B, C, H, W, st));
-        } else if (kind == 4) {
-            MRISR_REQUIRE(out_f32 && off >= 0 && off + C <= ld_out, "rowvec_grad: columns off .. off + C inside the row pitch");
-            TRY(BWD_DISPATCH(dtype, launch_rowvec_grad, a, out_f32, ld_out, off, B, H * W, C, flag ? 1 : 0, st));
-        } else {
-            MRISR_REQUIRE(out_f32, "colsum: out");
-            TRY(BWD_DISPATCH(dtype, launch_colsum, a, out_f32, B * H * W, C, st));
-        }
-    }
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-    API_END
-}
-
-int mrisr_op_lora_wgrad(int dtype, const void* P, int ldp, const float* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN,
-                        float* out0, float* out1, float* out2, float scale, void* stream) {
-    API_BEGIN
-    TRY(bwd_dtype_ok(dtype));
-    MRISR_REQUIRE(P && Q && M >= 1 && C >= 1 && (mode == 0 || mode == 1), "LoRA wgrad: null / empty operand, mode 0 / 1");
-    MRISR_REQUIRE(r % 4 == 0 && r >= 4 && r <= 16 && nmod >= 1 && nmod <= 3, "LoRA wgrad: rank 4/8/12/16, <= 3 fused modules");
-    MRISR_REQUIRE(ldq % 4 == 0 && ldq >= nmod * r && al16(Q), "LoRA wgrad: Q rows in whole, aligned 16-byte vectors");
-    float* const out[3] = {out0, nmod > 1 ? out1 : nullptr, nmod > 2 ? out2 : nullptr};
-    return BWD_DISPATCH(dtype, op_lora_wgrad_t, P, ldp, Q, ldq, M, C, mode, r, nmod, secN, out, scale, (hipStream_t)stream);
-    API_END
-}
-
-int mrisr_op_transpose(int dtype, const void* src, void* dst, int R, int C, int ld_src, int ld_dst, int64_t bs_src, int64_t bs_dst,
-                       int batch, int r_valid, void* stream) {
-    API_BEGIN
-    TRY(bwd_dtype_ok(dtype));
-    hipStream_t st = (hipStream_t)stream;
-    MRISR_REQUIRE(src && dst && R >= 1 && C >= 1 && batch >= 1 && batch <= 65535, "transpose: null / empty operand");
-    MRISR_REQUIRE(ld_src >= C && ld_dst >= R && r_valid >= 0 && r_valid <= R, "transpose: pitches cover the rows, r_valid <= R");
-    MRISR_REQUIRE(batch == 1 || (bs_src >= (long long)(R - 1) * ld_src + C && bs_dst >= (long long)(C - 1) * ld_dst + R),
-                  "transpose: batch strides cover one matrix");
-    TRY(BWD_DISPATCH(dtype, launch_transpose, src, dst, R, C, ld_src, ld_dst, (long long)bs_src, (long long)bs_dst, batch, r_valid, st));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-    API_END
-}
-
-int mrisr_op_softmax_bwd(int dtype, const void* p, const float* dp, void* ds, int ld, int64_t rows, int nk, float scale, void* stream) {
-    API_BEGIN
-    TRY(bwd_dtype_ok(dtype));
-    hipStream_t st = (hipStream_t)stream;
-    MRISR_REQUIRE(p && dp && ds && rows >= 1 && nk >= 1 && nk <= ld, "softmax backward: null / empty operand, nk <= ld");
-    MRISR_REQUIRE(ld % 4 != 0 || ld > 4096 || (al16(p) && al16(dp) && al16(ds)), "softmax backward: aligned rows for the vector kernel");
-    TRY(BWD_DISPATCH(dtype, launch_softmax_bwd, p, dp, ds, ld, (long long)rows, nk, scale, st));
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-    API_END
-}
-
-int mrisr_op_small_dense_bwd(int dtype, int which, const float* dY, int ldy, const void* xw, int ldx, int rows, int N, int K, int silu_in,
-                             const float* pre, int ldpre, float* out, float* gB, int ld_out, void* stream) {
-    API_BEGIN
-    TRY(bwd_dtype_ok(dtype));
-    hipStream_t st = (hipStream_t)stream;
-    MRISR_REQUIRE(dY && xw && out && (which == 0 || which == 1), "small dense backward: null operand, which 0 / 1");
-    MRISR_REQUIRE(rows >= 1 && rows <= 64 && N >= 1 && K >= 1 && ldy >= N, "small dense backward: 1..64 rows, dY pitch covers N");
-    if (which == 0) {
-        MRISR_REQUIRE(ldx >= K, "small wgrad: X pitch covers K");
-        TRY(launch_small_wgrad(dY, ldy, static_cast<const float*>(xw), ldx, rows, N, K, silu_in ? 1 : 0, out, gB, st));
-    } else {
-        MRISR_REQUIRE(ld_out >= K && (!pre || ldpre >= K), "small dgrad: dX / pre pitches cover K");
-        TRY(BWD_DISPATCH(dtype, launch_small_dgrad, dY, ldy, xw, rows, N, K, pre, ldpre, out, ld_out, st));
-    }
-    MRISR_CHECK_HIP(hipStreamSynchronize(st));
-    return 0;
-    API_END
-}
-
-int mrisr_op_conv_wgrad(int dtype, const void* x, int xB, int xH, int xW, int cin_src, const void* dY, int ldy, int col0, int cout_src,
-                        int ks, int stride, float* gW, float* gB, int cout, int cin, int geglu_half, void* stream) {
-    API_BEGIN
-    TRY(bwd_dtype_ok(dtype));
-    TRY(gemm_prepare());
-    MRISR_REQUIRE(x && dY && gW && xB >= 1 && xH >= 1 && xW >= 1, "conv wgrad: null / empty operand");
-    MRISR_REQUIRE((ks == 1 || ks == 3) && (stride == 1 || stride == 2), "conv wgrad: 1x1 or 3x3, stride 1 or 2");
-    MRISR_REQUIRE(cout >= 1 && cout <= cout_src && cin >= 1 && cin <= cin_src, "conv wgrad: raw tensor inside the (padded) layer");
-    MRISR_REQUIRE(col0 >= 0 && col0 + cout_src <= ldy, "conv wgrad: dY columns inside the row pitch");
-    MRISR_REQUIRE(geglu_half == 0 || (geglu_half % 16 == 0 && cout == 2 * geglu_half), "conv wgrad: GEGLU interleave of a [2 * half] projection");
-    MRISR_REQUIRE((long long)xB * xH * xW < (1ll << 24) && (long long)ks * ks * cin_src * cout_src < (1ll << 28), "conv wgrad: extents");
-    return BWD_DISPATCH(dtype, op_conv_wgrad_t, x, xB, xH, xW, cin_src, dY, ldy, col0, cout_src, ks, stride, gW, gB, cout, cin, geglu_half,
-                        (hipStream_t)stream);
-    API_END
-}
-
-int mrisr_op_conv_dgrad(int dtype, const void* dy, int B, int H, int W, int cout, const float* w_oihw_dev, int cin, int mode, void* dx,
-                        int accumulate, void* stream) {
-    API_BEGIN
-    TRY(bwd_dtype_ok(dtype));
-    TRY(gemm_prepare());
-    MRISR_REQUIRE(dy && w_oihw_dev && dx && B >= 1 && H >= 1 && W >= 1 && cout >= 1 && cin >= 1, "conv dgrad: null / empty operand");
-    MRISR_REQUIRE(mode == 0 || mode == 1, "conv dgrad: mode 0 (stride 1) or 1 (stride 2)");
-    const int bk = dtype == MRISR_F32 ? 32 : 64;
-    MRISR_REQUIRE(mode == 0 || (cout % bk == 0 && cin % 4 == 0), "strided dgrad of a tiny conv");
-    MRISR_REQUIRE(al16(dy) && al16(dx), "conv dgrad: 16-byte aligned activations");
-    return BWD_DISPATCH(dtype, op_conv_dgrad_t, dy, B, H, W, cout, w_oihw_dev, cin, mode, dx, accumulate, (hipStream_t)stream);
-    API_END
-}
-
-}  // extern "C"
-#undef BWD_DISPATCH
-
-// =================================================================================================
-// GEMM micro-benchmark (tools/gemm_sweep.py): times one implicit-GEMM shape with a forced tile / split-K on
-// pseudo-random operands (zero-filled operands would flatter the clock; guide rule 25).
-// =================================================================================================
-__global__ void fill_random_bf16_kernel(bf16* p, long long n, unsigned seed) {
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        unsigned x = (unsigned)i * 2654435761u + seed;
-        x ^= x >> 15; x *= 2246822519u; x ^= x >> 13;
-        p[i] = (bf16)(((float)(x & 0xFFFF) / 32768.0f - 1.0f) * 0.5f);
-    }
-}
-extern "C" void mrisr_debug_force_tile(int t);
-extern "C" int mrisr_bench_mlp(int M, int hidden, int iters, float* ms_out) {
-    API_BEGIN
-    TRY(gemm_prepare());
-    hipStream_t st = nullptr;
-    const int C = 320;
-    DevBuf x, w1, w2, o, b1, b2, gb;
-    TRY(x.reserve((size_t)M * C * 2, false));
-    TRY(o.reserve((size_t)M * C * 2, false));
-    TRY(w1.reserve((size_t)2 * hidden * C * 2, false));
-    TRY(w2.reserve((size_t)C * hidden * 2, false));
-    TRY(b1.reserve((size_t)2 * hidden * 4, true));
-    TRY(b2.reserve((size_t)C * 4, true));
-    TRY(gb.reserve((size_t)C * 4, true));
-    hipLaunchKernelGGL(fill_random_bf16_kernel, dim3(2048), dim3(256), 0, st, (bf16*)x.p, (long long)M * C, 1u);
-    hipLaunchKernelGGL(fill_random_bf16_kernel, dim3(2048), dim3(256), 0, st, (bf16*)w1.p, (long long)2 * hidden * C, 2u);
-    hipLaunchKernelGGL(fill_random_bf16_kernel, dim3(2048), dim3(256), 0, st, (bf16*)w2.p, (long long)C * hidden, 3u);
-    MlpArgs a;
-    a.x = x.p; a.ldx = C; a.M = M; a.ln_gamma = (const float*)gb.p; a.ln_beta = (const float*)gb.p;
-    a.w1 = w1.p; a.b1 = (const float*)b1.p; a.w2p = w2.p; a.b2 = (const float*)b2.p;
-    a.resid = x.p; a.ldr = C; a.out = o.p; a.ldo = C; a.C = C; a.H = hidden; a.N2 = C;
-    for (int i = 0; i < 2; ++i) TRY(launch_mlp_fused(a, st));
-    hipEvent_t e0, e1;
-    MRISR_CHECK_HIP(hipEventCreate(&e0));
-    MRISR_CHECK_HIP(hipEventCreate(&e1));
-    MRISR_CHECK_HIP(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i) (void)launch_mlp_fused(a, st);
-    MRISR_CHECK_HIP(hipEventRecord(e1, st));
-    MRISR_CHECK_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    MRISR_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_out = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return 0;
-    API_END
-}
-
-extern "C" int mrisr_bench_gemm(int M, int N, int K, int conv, int B, int H, int W, int stride, int ups, int c1,
-                                int tile, int splitk, int iters, float* ms_out) {
-    API_BEGIN
-    TRY(gemm_prepare());
-    hipStream_t st = nullptr;
-    GemmArgs g;
-    const int Cin = conv ? K / 9 : K;
-    const int c0 = Cin - c1;
-    DevBuf a0, a1, wb, ob, part, bias;
-    const long long a_rows = conv ? (long long)B * H * W : M;
-    TRY(a0.reserve((size_t)a_rows * c0 * 2, false));
-    if (c1) TRY(a1.reserve((size_t)a_rows * c1 * 2, false));
-    TRY(wb.reserve((size_t)N * K * 2, false));
-    TRY(ob.reserve((size_t)M * N * 2, false));
-    TRY(bias.reserve((size_t)N * 4, true));
-    hipLaunchKernelGGL(fill_random_bf16_kernel, dim3(2048), dim3(256), 0, st, (bf16*)a0.p, a_rows * c0, 1u);
-    if (c1) hipLaunchKernelGGL(fill_random_bf16_kernel, dim3(2048), dim3(256), 0, st, (bf16*)a1.p, a_rows * c1, 2u);
-    hipLaunchKernelGGL(fill_random_bf16_kernel, dim3(2048), dim3(256), 0, st, (bf16*)wb.p, (long long)N * K, 3u);
-    g.a0 = a0.p; g.c0 = c0; g.lda0 = c0;
-    if (c1) { g.a1 = a1.p; g.c1 = c1; g.lda1 = c1; }
-    if (conv) {
-        const int Hc = H << ups, Wc = W << ups;
-        g.conv = 1; g.B = B; g.Hin = H; g.Win = W; g.Hout = (Hc - 1) / stride + 1; g.Wout = (Wc - 1) / stride + 1;
-        g.stride = stride; g.ups = ups;
-        MRISR_REQUIRE(M == B * g.Hout * g.Wout, "bench conv M");
-    }
-    g.w = wb.p; g.M = M; g.N = N; g.K = K; g.bias = (const float*)bias.p; g.out = ob.p; g.ldo = N;
-    if (const char* e = getenv("MRISR_BENCH_NOSTORE")) { if (e[0] == '1') g.out_mode = OUT_NONE; }  // experiment: epilogue without the store
-    g.splitk = splitk;
-    if (splitk <= 0) { g.splitk = 1; mrisr_debug_force_tile(tile); TRY(gemm_choose(g, true)); }
-    if (g.splitk > 1) {
-        TRY(part.reserve((size_t)g.splitk * M * N * 4, false));
-        g.partial = (float*)part.p;
-    }
-    mrisr_debug_force_tile(tile);
-    for (int i = 0; i < 2; ++i) { int rc = launch_gemm<bf16>(g, st); if (rc) { mrisr_debug_force_tile(0); return rc; } }
-    hipEvent_t e0, e1;
-    MRISR_CHECK_HIP(hipEventCreate(&e0));
-    MRISR_CHECK_HIP(hipEventCreate(&e1));
-    MRISR_CHECK_HIP(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i) (void)launch_gemm<bf16>(g, st);
-    MRISR_CHECK_HIP(hipEventRecord(e1, st));
-    MRISR_CHECK_HIP(hipEventSynchronize(e1));
-    mrisr_debug_force_tile(0);
-    float ms = 0.f;
-    MRISR_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_out = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return g.splitk * 1000 == 0 ? 0 : 0;
-    API_END
-}
 
 // ================================================================================================
 // LoRA fine-tuning step (train.hip)

@@ -299,14 +299,9 @@ size_t lora_wgrad_scratch_bytes(int M, int C, int nq, int elem_size);
 template <typename T> int launch_sumpool2(const void* src, void* dst, int B, int H, int W, int C, int accumulate, hipStream_t st);
 template <typename T>
 int launch_mse_grad(const void* pred, const float* tgt, void* dpred, float* loss, int B, int C, int H, int W, hipStream_t st);
-template <typename T>
-int launch_im2col_tap_T(const void* x, void* out, int B, int H, int W, int C, int Ho, int Wo, int stride, int pad, int ky, int kx,
-                        int Mpad, hipStream_t st);
 template <typename T> int launch_relu_bwd(const void* dy, const void* h, void* out, long long n, hipStream_t st);
-template <typename T> int launch_colsum(const void* dy, float* out, int M, int C, hipStream_t st);
-int launch_wgrad_accum(const float* tmp, float* gw, long long n, int taps, int tap, hipStream_t st);
-int launch_wgrad_accum_all(const float* tmp, float* gw, int Cout, int Cin, int taps, hipStream_t st);
-// full-parameter training: tmp rows with pitch ld_tmp, per-tap channel pitch cin_src (zero-padded layers), GEGLU row interleave (half > 0)
+// the two reductions behind a weight / bias gradient: tmp rows with pitch ld_tmp, per-tap channel pitch cin_src (zero-padded layers),
+// GEGLU row interleave (half > 0); dy rows of pitch ld, columns from col0
 int launch_wgrad_accum_gen(const float* tmp, int ld_tmp, int cin_src, float* gw, int Cout, int Cin, int taps, int geglu_half, hipStream_t st);
 template <typename T> int launch_colsum_gen(const void* dy, int ld, int col0, float* out, int M, int C, int geglu_half, hipStream_t st);
 template <typename T>

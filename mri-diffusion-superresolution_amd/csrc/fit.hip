@@ -16,24 +16,12 @@
 #include <string>
 #include <vector>
 
+#include "api.h"
 #include "model.h"
 
 using namespace mrisr;
 
 struct mrisr_model : public Model {};
-
-#define TRY(expr)            \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
-#define API_BEGIN try {
-#define API_END                                              \
-    }                                                        \
-    catch (const std::exception& e) {                        \
-        set_error(std::string("exception: ") + e.what());    \
-        return 99;                                           \
-    }
 
 namespace {
 

@@ -149,7 +149,7 @@ struct Model {
                    mrisr_tensor* pred_out, hipStream_t st);
 };
 
-// ---- the T2I-Adapter inside the device training loop (capi.hip; used by fit.hip) ----
+// ---- the T2I-Adapter inside the device training loop (adapter.hip; used by fit.hip) ----
 struct AdapterFitInfo {
     int compute_dtype, cin, nums_rb, n_levels;
     int channels[4];

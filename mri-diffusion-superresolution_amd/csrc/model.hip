@@ -15,8 +15,6 @@ thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 const char* last_error_cstr() { return g_err.c_str(); }
 
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
 // ================================================================================================
 // parameters
 // ================================================================================================

@@ -5,19 +5,12 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "api.h"
 #include "model.h"
 
 namespace mrisr {
 
 extern int g_subpix_override;  // test hook (mrisr_debug_subpix): -1 = MRISR_SUBPIX / default, 0 = off, n = minimum low-resolution rows
-
-#ifndef TRY
-#define TRY(expr)              \
-    do {                       \
-        int _rc = (expr);      \
-        if (_rc) return _rc;   \
-    } while (0)
-#endif
 
 // MRISR_LORA_INKERNEL=0 restores the separate down-projection pass (A/B measurements)
 // MRISR_FUSE_LN=0: LayerNorm always as its own launch (A/B measurements)

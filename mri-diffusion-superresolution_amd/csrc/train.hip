@@ -65,24 +65,32 @@ std::vector<LinW*> Model::lora_linears() {
     return v;
 }
 
+// the backward's copies of one layer's weights (both prepare functions below); err keeps the last failure
+// wd[ci][ky][kx][co] = w[co][ci][2-ky][2-kx]: the dgrad of a 3x3 conv is a 3x3 conv of dY with this bank
+template <typename T>
+static void pack_conv_dgrad(Model& m, ConvW& c, hipStream_t st, int& err) {
+    if (!c.w || c.ks != 3 || c.wd) return;
+    const RawParam* w = m.find(c.name + ".weight");
+    if (!w) { err = 3; set_error("missing parameter: " + c.name + ".weight"); return; }
+    c.wd = m.new_packed((size_t)w->numel() * sizeof(T), false);
+    if (!c.wd) { err = 4; return; }
+    if (launch_pack_conv_dgrad<T>(static_cast<const float*>(w->data->p), c.wd, c.cout, c.cin, st)) err = 5;
+}
+// wT = w^T.  repack: a linear that already has its wT is transposed again into the same buffer (full-parameter training: the weights
+// change every step); otherwise it is left alone (frozen base weights)
+template <typename T>
+static void pack_lin_t(Model& m, LinW& l, bool repack, hipStream_t st, int& err) {
+    if (!l.w || (l.wT && !repack)) return;
+    if (!l.wT) l.wT = m.new_packed((size_t)l.n * l.k * sizeof(T), false);
+    if (!l.wT) { err = 4; return; }
+    if (launch_transpose<T>(l.w, l.wT, l.n, l.k, l.k, l.n, 0, 0, 1, l.n, st)) err = 5;
+}
+
 template <typename T>
 static int train_prepare_t(Model& m, hipStream_t st) {
     int err = 0;
-    auto conv_dgrad = [&](ConvW& c) {
-        if (!c.w || c.ks != 3 || c.wd) return;
-        const RawParam* w = m.find(c.name + ".weight");
-        if (!w) { err = 3; set_error("missing parameter: " + c.name + ".weight"); return; }
-        c.wd = m.new_packed((size_t)w->numel() * sizeof(T), false);
-        if (!c.wd) { err = 4; return; }
-        // wd[ci][ky][kx][co] = w[co][ci][2-ky][2-kx]: the dgrad of a 3x3 conv is a 3x3 conv of dY with this bank
-        if (launch_pack_conv_dgrad<T>(static_cast<const float*>(w->data->p), c.wd, c.cout, c.cin, st)) err = 5;
-    };
-    auto lin_t = [&](LinW& l) {
-        if (!l.w || l.wT) return;
-        l.wT = m.new_packed((size_t)l.n * l.k * sizeof(T), false);
-        if (!l.wT) { err = 4; return; }
-        if (launch_transpose<T>(l.w, l.wT, l.n, l.k, l.k, l.n, 0, 0, 1, l.n, st)) err = 5;
-    };
+    auto conv_dgrad = [&](ConvW& c) { pack_conv_dgrad<T>(m, c, st, err); };
+    auto lin_t = [&](LinW& l) { pack_lin_t<T>(m, l, false, st, err); };
     for_each_res(m, [&](ResW& r) {
         conv_dgrad(r.c1);
         conv_dgrad(r.c2);
@@ -299,7 +307,7 @@ struct Trainer : Runner<T> {
     int conv_dgrad(const Act& dy, const ConvW& cw, int mode, void* out, bool acc) {
         MRISR_REQUIRE(cw.wd && dy.C == cw.cout, "conv dgrad weights");
         return conv_dgrad_run<T>(st, dry, [this](GemmArgs& g) { return R::run_gemm(g); }, dy.p, dy.B, dy.H, dy.W, cw.cout, cw.cin, cw.wd,
-                                 mode, out, acc);
+                                 mode, out, acc ? out : nullptr, cw.cin);
     }
 
     int gn_bwd(const Act& x0, const Act* x1, const NormW& nw, bool silu, float eps, const float* fwd_partial, int nsplit,
@@ -1133,21 +1141,8 @@ struct Trainer : Runner<T> {
 template <typename T>
 static int full_train_prepare_t(Model& m, hipStream_t st) {
     int err = 0;
-    auto conv_dgrad = [&](ConvW& c) {
-        if (!c.w || c.ks != 3 || c.wd) return;
-        const RawParam* w = m.find(c.name + ".weight");
-        if (!w) { err = 3; set_error("missing parameter: " + c.name + ".weight"); return; }
-        c.wd = m.new_packed((size_t)w->numel() * sizeof(T), false);
-        if (!c.wd) { err = 4; return; }
-        // wd[ci][ky][kx][co] = w[co][ci][2-ky][2-kx]: the dgrad of a 3x3 conv is a 3x3 conv of dY with this bank
-        if (launch_pack_conv_dgrad<T>(static_cast<const float*>(w->data->p), c.wd, c.cout, c.cin, st)) err = 5;
-    };
-    auto lin_t = [&](LinW& l) {
-        if (!l.w) return;
-        if (!l.wT) l.wT = m.new_packed((size_t)l.n * l.k * sizeof(T), false);
-        if (!l.wT) { err = 4; return; }
-        if (launch_transpose<T>(l.w, l.wT, l.n, l.k, l.k, l.n, 0, 0, 1, l.n, st)) err = 5;
-    };
+    auto conv_dgrad = [&](ConvW& c) { pack_conv_dgrad<T>(m, c, st, err); };
+    auto lin_t = [&](LinW& l) { pack_lin_t<T>(m, l, true, st, err); };
     for (auto& lv : m.down) {
         for (auto& r : lv.res) { conv_dgrad(r.c1); conv_dgrad(r.c2); if (r.has_sc) lin_t(r.sc); }
         if (lv.has_down) conv_dgrad(lv.down);

@@ -1,6 +1,7 @@
 // The two composite backward operations of the training step that are more than one launch - the weight gradient of a conv / linear and
-// the input gradient of a 3x3 conv - as free functions: the trainer (train.hip) calls them on its arena, the single-op entry points
-// (capi.hip: mrisr_op_conv_wgrad / mrisr_op_conv_dgrad) on scratch buffers of their own, so the parity tests run the trainer's code.
+// the input gradient of a 3x3 conv - as free functions: the UNet / ControlNet trainer (train.hip) and the T2I-Adapter (adapter.hip) call
+// them on their arenas, the single-op entry points (capi_ops.hip: mrisr_op_conv_wgrad / mrisr_op_conv_dgrad) on scratch buffers of
+// their own, so the parity tests run the trainers' code.
 #pragma once
 #include <functional>
 
@@ -27,10 +28,10 @@ int conv_wgrad_run(hipStream_t st, bool dry, const TrainAllocFn& alloc, const Tr
     float* tmp = static_cast<float*>(alloc((size_t)cout_src * ncol * sizeof(float)));
     if (!dyT || !xT || !tmp) return 7;
     if (!dry) {
-        if (Mpad != M || ncol != taps * cin_src) {
-            MRISR_CHECK_HIP(hipMemsetAsync(dyT, 0, (size_t)cout_src * Mpad * sizeof(T), st));
-            MRISR_CHECK_HIP(hipMemsetAsync(xT, 0, (size_t)ncol * Mpad * sizeof(T), st));
-        }
+        // what the two fills below leave unwritten: the transpose the pixels M .. Mpad of dyT (the im2col zeroes its own), the im2col
+        // the rows beyond taps * cin_src of xT
+        if (Mpad != M) MRISR_CHECK_HIP(hipMemsetAsync(dyT, 0, (size_t)cout_src * Mpad * sizeof(T), st));
+        if (ncol != taps * cin_src) MRISR_CHECK_HIP(hipMemsetAsync(xT, 0, (size_t)ncol * Mpad * sizeof(T), st));
         int rc = launch_transpose<T>(static_cast<const T*>(dY) + col0, dyT, M, cout_src, ldy, Mpad, 0, 0, 1, M, st);
         if (rc) return rc;
         if (gB && (rc = launch_colsum_gen<T>(dY, ldy, col0, gB, M, cout, geglu_half, st)) != 0) return rc;
@@ -45,19 +46,20 @@ int conv_wgrad_run(hipStream_t st, bool dry, const TrainAllocFn& alloc, const Tr
     return 0;
 }
 
-// dX (+)= conv3x3(dY, wd), wd = the tap-flipped filter bank [cin][ky][kx][cout] (launch_pack_conv_dgrad).  dy: NHWC [B][H][W][cout].
+// dX = conv3x3(dY, wd) (+ resid), wd = the tap-flipped filter bank [cin][ky][kx][cout] (launch_pack_conv_dgrad).  dy: NHWC [B][H][W][cout];
+// resid: rows of pitch ldr in out's shape, or null (resid == out accumulates in place).
 // mode 1: the forward conv had stride 2 -> dY is zero-stuffed to twice its size.  Channel counts below one K tile take the direct kernel.
 template <typename T>
 int conv_dgrad_run(hipStream_t st, bool dry, const TrainGemmFn& run_gemm, const void* dy, int B, int H, int W, int cout, int cin,
-                   const void* wd, int mode, void* out, bool acc) {
+                   const void* wd, int mode, void* out, const void* resid, int ldr) {
     constexpr int BK = 128 / (int)sizeof(T);
     const int Ho = H << mode, Wo = W << mode;
     if (cout % BK != 0 || cin % 4 != 0) {  // conv_out (4 channels): far below one K tile
-        MRISR_REQUIRE(mode == 0, "strided dgrad of a tiny conv");
+        MRISR_REQUIRE(mode == 0 && (!resid || ldr == cin), "strided / pitched-residual dgrad of a tiny conv");
         DirectConvArgs a;
         a.x = dy; a.w = wd; a.y = out; a.B = B; a.Hin = H; a.Win = W; a.Cin = cout;
         a.Hout = Ho; a.Wout = Wo; a.Cout = cin; a.ks = 3; a.stride = 1; a.pad = 1; a.act = ACT_NONE;
-        a.add = acc ? out : nullptr;
+        a.add = resid;
         if (dry) return 0;
         return launch_direct_conv<T>(a, st);
     }
@@ -65,7 +67,7 @@ int conv_dgrad_run(hipStream_t st, bool dry, const TrainGemmFn& run_gemm, const 
     g.a0 = dy; g.c0 = cout; g.lda0 = cout;
     g.conv = 1; g.B = B; g.Hin = H; g.Win = W; g.Hout = Ho; g.Wout = Wo; g.stride = 1; g.ups = mode; g.zstuff = mode;
     g.w = wd; g.M = B * Ho * Wo; g.N = cin; g.K = 9 * cout;
-    if (acc) { g.resid = out; g.ldr = cin; }
+    if (resid) { g.resid = resid; g.ldr = ldr; }
     g.out = out; g.ldo = cin;
     return run_gemm(g);
 }

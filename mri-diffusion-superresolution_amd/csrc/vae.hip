@@ -5,18 +5,11 @@
 // one single-head attention per mid block), driven through the Runner helpers over this handle's own arena.
 #include <cstring>
 
+#include "api.h"
 #include "model.h"
 #include "runner.h"
 
 using namespace mrisr;
-
-#define API_BEGIN try {
-#define API_END                                              \
-    }                                                        \
-    catch (const std::exception& e) {                        \
-        set_error(std::string("exception: ") + e.what());    \
-        return 99;                                           \
-    }
 
 namespace {
 

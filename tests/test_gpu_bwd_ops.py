@@ -1,5 +1,5 @@
-"""GPU: every backward kernel on its own (csrc/bwd.hip, csrc/train_ops.h) through the mrisr_op_* entry points, against float64 autograd or
-the closed formula on the CPU.
+"""GPU: every backward kernel on its own (csrc/bwd.hip, csrc/train_ops.h) through the mrisr_op_* entry points (csrc/capi_ops.hip), against
+float64 autograd or the closed formula on the CPU.
 
 Reference: inputs are drawn in f32 and rounded to the dtype under test; the reference is evaluated in float64 on those rounded inputs and
 rounds nowhere else; where a kernel adds into an existing tensor the reference is ``prior + g``.

@@ -143,7 +143,15 @@ int mrisr_resshift_forward(const mrisr_tensor* hr, const mrisr_tensor* lr, const
  * DDPM"): t_prev = t - T/n, alpha_t = abar_t / abar_prev, x0 = (x - sqrt(1-abar_t) eps) / sqrt(abar_t) [clipped to
  * +-clip_sample_range when set], x_prev = sqrt(abar_prev) (1-alpha_t)/(1-abar_t) x0 + sqrt(alpha_t) (1-abar_prev)/(1-abar_t) x
  * + sqrt((1-abar_prev)/(1-abar_t) (1-alpha_t)) z for t > 0;  z = step_noise slab i (NULL: the mean only). */
-typedef enum { MRISR_STEP_DDIM = 0, MRISR_STEP_RESSHIFT = 1, MRISR_STEP_DDPM = 2 } mrisr_step_kind;
+/* MRISR_STEP_UNIPC / MRISR_STEP_DPMSOLVERPP: deterministic linear multistep solvers in data prediction - UniPC with the bh2 variant
+ * (Zhao et al. 2023) and DPM-Solver++ 2M, midpoint (Lu et al. 2022) - on the grid t_0 > ... > t_{n-1} of `timesteps`, then a final
+ * point.  The papers' algorithms on this table; not pinned to diffusers (which is not available to this project).  The sampler owns
+ * a ring of solver_order x0 predictions and, for UniPC, the previous corrected state; both are zeroed at the start of every run.
+ * With lr_latents the solver integrates z = x - LR: the probability-flow ODE of the reference's shift process (res_srdiff.py:7-25),
+ * not the reference's stochastic step.  step_noise and x0 clipping are refused.  C*h*w must be a multiple of 4. */
+typedef enum {
+    MRISR_STEP_DDIM = 0, MRISR_STEP_RESSHIFT = 1, MRISR_STEP_DDPM = 2, MRISR_STEP_UNIPC = 3, MRISR_STEP_DPMSOLVERPP = 4
+} mrisr_step_kind;
 /* timesteps: host int64[n_steps]; alphas_cumprod: host f32[n_train]; unet required, controlnet may be NULL. */
 int mrisr_sampler_create(mrisr_model* unet, mrisr_model* controlnet, int step_kind, const int64_t* timesteps,
                          int n_steps, const float* alphas_cumprod, int n_train, mrisr_sampler** out);
@@ -162,6 +170,14 @@ int mrisr_sampler_set_range(mrisr_sampler* s, int first_step, int last_step);
 /* DDPM only: clip the predicted x0 to [-range, range] (diffusers clip_sample / clip_sample_range); range <= 0 disables
  * (the default, as in the SD-1.5 scheduler config). */
 int mrisr_sampler_set_clip(mrisr_sampler* s, float clip_sample_range);
+/* Multistep kinds only (defaults: order 2, final point "zero").  solver_order: 1..3 for UniPC, 1..2 for DPM-Solver++.
+ * final_sigmas_zero: 1 - the last step lands on alpha = 1, sigma = 0 (diffusers' final_sigmas_type "zero"; that step is first order);
+ * 0 - on alphas_cumprod[0] ("sigma_min", as the DDIM kind).  lower_order_final must be 1: UniPC's order is min(solver_order, steps
+ * left, steps taken + 1); DPM-Solver++ drops to first order on the last step when n_steps < 15.  disable_corrector: UniPC step
+ * indices without a corrector (NULL / 0: none).  A run restricted by mrisr_sampler_set_range starts COLD at first_step (order 1, no
+ * corrector there: the history of the steps before it is not available), so for these kinds a split run differs from the full one. */
+int mrisr_sampler_set_solver(mrisr_sampler* s, int solver_order, int final_sigmas_zero, int lower_order_final,
+                             const int* disable_corrector, int n_disable);
 
 /* ---- classifier-free guidance (off unless mrisr_sampler_run_guided is called) ----------------------
  * A guided step of B slices is ONE forward of 2B rows inside the same captured graph plus one fused step kernel.  Row order is
@@ -483,6 +499,15 @@ int mrisr_op_conv_dgrad(int dtype, const void* dy, int B, int H, int W, int cout
 int mrisr_op_guided_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const mrisr_tensor* eps2, const mrisr_tensor* lr,
                          const mrisr_tensor* noise, const float* coef_row_host, float clip, float guidance_scale,
                          float guidance_rescale, void* stream);
+
+/* the fused multistep step (MRISR_STEP_UNIPC / MRISR_STEP_DPMSOLVERPP) alone: x [B,C,h,w] f32 (in place), eps [B,C,h,w], lr or NULL,
+ * hist [solver_order][B,C,h,w] f32 (x0 predictions; slot `slot` % solver_order is written, the prediction k steps back is read from
+ * slot (slot - k) % solver_order), xc [B,C,h,w] (UniPC: previous corrected state in, this step's out; NULL for DPM-Solver++).
+ * row_host, 16 floats: {m: z, eps | corrected state: z, eps, xc, h1, h2, h3 | next state: z, eps, xc, h1, h2, h3 | 0, 0} with
+ * z = x - lr.  x2 != NULL: the guided form - eps is [2B] (unconditional rows first), x2 [2B] receives the new x in both halves. */
+int mrisr_op_multistep_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const mrisr_tensor* eps, const mrisr_tensor* lr,
+                            mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot, float guidance_scale,
+                            float guidance_rescale, void* stream);
 
 #ifdef __cplusplus
 }

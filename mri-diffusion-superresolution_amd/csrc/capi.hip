@@ -148,6 +148,104 @@ static bool temb_table_enabled() {
     static const int env = [] { const char* e = getenv("MRISR_TEMB_TABLE"); return e ? atoi(e) : 1; }();
     return g_temb_table < 0 ? env != 0 : g_temb_table != 0;
 }
+// ---- multistep solvers (UniPC bh2 / DPM-Solver++ 2M): one row of 16 folded coefficients per step (layout: misc.hip) ----
+// rho of the UniPC predictor / corrector: solves the leading k x k block of R rho = b, rows of R = [r_1 .. r_{p-1}, 1]^(j-1),
+// b_j = (phi_{j+1}-recurrence value) j! / B(h), B(h) = expm1(-h) (bh2); Gaussian elimination with partial pivoting, k <= 3
+static void unipc_rho(const double* rks, int p, double h, int k, double* rho) {
+    const double hh = -h, Bh = std::expm1(hh);
+    double A[3][4];
+    double phik = std::expm1(hh) / hh - 1.0, fact = 1.0;
+    for (int j = 1; j <= p; ++j) {
+        if (j <= k) {
+            for (int c = 0; c < k; ++c) A[j - 1][c] = std::pow(rks[c], j - 1);
+            A[j - 1][k] = phik * fact / Bh;
+        }
+        fact *= j + 1;
+        phik = phik / hh - 1.0 / fact;
+    }
+    for (int c = 0; c < k; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < k; ++r) if (std::fabs(A[r][c]) > std::fabs(A[piv][c])) piv = r;
+        for (int q = 0; q <= k; ++q) std::swap(A[c][q], A[piv][q]);
+        for (int r = c + 1; r < k; ++r) {
+            const double f = A[r][c] / A[c][c];
+            for (int q = c; q <= k; ++q) A[r][q] -= f * A[c][q];
+        }
+    }
+    for (int r = k - 1; r >= 0; --r) {
+        double v = A[r][k];
+        for (int q = r + 1; q < k; ++q) v -= A[r][q] * rho[q];
+        rho[r] = v / A[r][r];
+    }
+}
+struct MultistepOpts {
+    int order = 2;
+    int final_zero = 1;        // 1: the last step lands on alpha = 1, sigma = 0 (diffusers' "zero"); 0: on alphas_cumprod[0] ("sigma_min")
+    int lower_order_final = 1;
+    std::vector<int> disable_corrector;  // UniPC: step indices without a corrector
+};
+// abar: the clamped alphas_cumprod at the n grid timesteps followed by the final point's (ignored when final_zero).  The run starts
+// cold at `first`: order 1 and no corrector there.  All arithmetic in double.
+static std::vector<float> build_multistep_rows(int kind, const MultistepOpts& o, const std::vector<double>& abar, int n, int first) {
+    std::vector<double> al(n + 1), sg(n + 1), lam(n + 1);
+    for (int i = 0; i <= n; ++i) {
+        al[i] = std::sqrt(abar[i]); sg[i] = std::sqrt(1.0 - abar[i]); lam[i] = std::log(al[i] / sg[i]);
+    }
+    if (o.final_zero) { al[n] = 1.0; sg[n] = 0.0; lam[n] = INFINITY; }
+    auto order_at = [&](int i) {  // order of the predictor step from t_i
+        int p = std::min(o.order, i - first + 1);
+        if (kind == MRISR_STEP_UNIPC) { if (o.lower_order_final) p = std::min(p, n - i); }
+        else if (i == n - 1 && ((o.lower_order_final && n < 15) || o.final_zero)) p = 1;
+        return std::max(p, 1);
+    };
+    std::vector<float> rows((size_t)n * 16, 0.f);
+    for (int i = first; i < n; ++i) {
+        const double ma = 1.0 / al[i], mb = -sg[i] / al[i];
+        // corrected state zc = c[0] z + c[1] eps + c[2] xc + c[3..5] h_1..3      (m = ma z + mb eps folded in)
+        double c[6] = {1.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        const bool corr = kind == MRISR_STEP_UNIPC && i > first &&
+                          std::find(o.disable_corrector.begin(), o.disable_corrector.end(), i) == o.disable_corrector.end();
+        if (corr) {
+            const int p = order_at(i - 1);
+            const double h = lam[i] - lam[i - 1], phi1 = std::expm1(-h), Bh = phi1;
+            double rks[3], rho[3] = {0.5, 0.0, 0.0};
+            for (int k = 1; k < p; ++k) rks[k - 1] = (lam[i - 1 - k] - lam[i - 1]) / h;
+            rks[p - 1] = 1.0;
+            if (p > 1) unipc_rho(rks, p, h, p, rho);
+            const double cm = -al[i] * Bh * rho[p - 1];
+            double ch1 = -al[i] * phi1 + al[i] * Bh * rho[p - 1];
+            c[0] = cm * ma; c[1] = cm * mb; c[2] = sg[i] / sg[i - 1];
+            for (int k = 1; k < p; ++k) { c[3 + k] = -al[i] * Bh * rho[k - 1] / rks[k - 1]; ch1 += al[i] * Bh * rho[k - 1] / rks[k - 1]; }
+            c[3] = ch1;
+        }
+        // next state from (zc, m, h_1, h_2)
+        const int p = order_at(i);
+        double pz, pm, ph[3] = {0.0, 0.0, 0.0};
+        if (i == n - 1 && o.final_zero) { pz = 0.0; pm = 1.0; }  // h = inf: the state IS the x0 prediction
+        else {
+            const double h = lam[i + 1] - lam[i], e1 = std::expm1(-h);
+            pz = sg[i + 1] / sg[i];
+            pm = -al[i + 1] * e1;
+            if (kind == MRISR_STEP_UNIPC && p > 1) {
+                double rks[3], rho[3] = {0.5, 0.0, 0.0};
+                for (int k = 1; k < p; ++k) rks[k - 1] = (lam[i - k] - lam[i]) / h;
+                rks[p - 1] = 1.0;
+                if (p > 2) unipc_rho(rks, p, h, p - 1, rho);
+                for (int k = 1; k < p; ++k) { ph[k - 1] = -al[i + 1] * e1 * rho[k - 1] / rks[k - 1]; pm -= ph[k - 1]; }
+            } else if (kind == MRISR_STEP_DPMSOLVERPP && p > 1) {
+                const double r0 = (lam[i] - lam[i - 1]) / h;
+                ph[0] = 0.5 * al[i + 1] * e1 / r0;
+                pm -= ph[0];
+            }
+        }
+        const double nx[6] = {pz * c[0] + pm * ma, pz * c[1] + pm * mb, pz * c[2], pz * c[3] + ph[0], pz * c[4] + ph[1], pz * c[5] + ph[2]};
+        float* r = &rows[(size_t)i * 16];
+        r[0] = (float)ma; r[1] = (float)mb;
+        for (int k = 0; k < 6; ++k) { r[2 + k] = (float)c[k]; r[8 + k] = (float)nx[k]; }
+    }
+    return rows;
+}
+
 struct mrisr_sampler {
     mrisr_model* unet = nullptr;
     mrisr_model* cnet = nullptr;
@@ -156,6 +254,14 @@ struct mrisr_sampler {
     float guidance_scale = 1.f, guidance_rescale = 0.f;  // classifier-free guidance of mrisr_sampler_run_guided
     std::vector<float> sigma;  // host copy of each step's noise coefficient (which steps read a step_noise slab)
     DevBuf d_ts, d_coef, d_step, d_curt, d_eps;
+    // multistep kinds: solver options, the clamped alphas_cumprod on the grid (+ alphas_cumprod[0]), the host rows of the current range,
+    // the history ring of `order` x0 predictions and (UniPC) the previous corrected state
+    MultistepOpts ms;
+    std::vector<double> ms_abar;
+    std::vector<float> ms_rows;
+    DevBuf d_hist, d_xc;
+    bool multistep() const { return kind > MRISR_STEP_DDPM; }
+    void rebuild_rows() { if (multistep()) ms_rows = build_multistep_rows(kind, ms, ms_abar, n_steps, first); }
     DevBuf d_x2;  // guided runs: the [2B] f32 latents the forwards read (both halves = the state; the guided step keeps them current)
     DevBuf tp_unet, tp_cnet;  // per-run time-embedding tables [scratch | n_steps x tproj_total] (f32)
     std::vector<std::unique_ptr<DevBuf>> res_bufs;   // ControlNet -> UNet residuals (NHWC, compute dtype)
@@ -187,8 +293,8 @@ int mrisr_sampler_create(mrisr_model* unet, mrisr_model* controlnet, int step_ki
     s->first = 0;
     s->last = n_steps;
     std::vector<long long> ts(timesteps, timesteps + n_steps);
-    MRISR_REQUIRE(step_kind >= MRISR_STEP_DDIM && step_kind <= MRISR_STEP_DDPM, "unknown step kind");
-    std::vector<float> coef((size_t)n_steps * 8, 0.f);
+    MRISR_REQUIRE(step_kind >= MRISR_STEP_DDIM && step_kind <= MRISR_STEP_DPMSOLVERPP, "unknown step kind");
+    std::vector<float> coef((size_t)n_steps * (s->multistep() ? 16 : 8), 0.f);
     for (int i = 0; i < n_steps; ++i) {
         const long long t = ts[i];
         MRISR_REQUIRE(t >= 0 && t < n_train, "timestep out of range");
@@ -196,7 +302,10 @@ int mrisr_sampler_create(mrisr_model* unet, mrisr_model* controlnet, int step_ki
         // samples that entry first: every step divides by sqrt(abar_t) (res_srdiff.py:86), so it is clamped to 2^-24 here
         // (the reference itself would produce inf)
         const double a_t = std::max((double)alphas_cumprod[t], 5.9604644775390625e-8);
-        if (step_kind == MRISR_STEP_DDIM) {
+        if (s->multistep()) {
+            MRISR_REQUIRE(i == 0 || t < ts[i - 1], "multistep solvers need strictly decreasing timesteps");
+            s->ms_abar.push_back(a_t);
+        } else if (step_kind == MRISR_STEP_DDIM) {
             // t_prev = t - T/n; alpha_prev = alpha[t_prev] or alpha[0] (set_alpha_to_one=False)
             const long long tp = t - n_train / n_steps;
             const double a_p = tp >= 0 ? alphas_cumprod[tp] : alphas_cumprod[0];
@@ -222,8 +331,12 @@ int mrisr_sampler_create(mrisr_model* unet, mrisr_model* controlnet, int step_ki
             coef[4 * i + 3] = tp > 0 ? (float)std::sqrt((1.0 - a_p) / (1.0 - a_t) * (1.0 - a_t / a_p)) : 0.f;
         }
     }
+    if (s->multistep()) {  // defaults: order 2, diffusers' "zero" final point; mrisr_sampler_set_solver changes them
+        s->ms_abar.push_back(std::max((double)alphas_cumprod[0], 5.9604644775390625e-8));
+        s->rebuild_rows();
+    }
     s->sigma.assign(n_steps, 0.f);
-    for (int i = 0; i < n_steps; ++i)
+    for (int i = 0; i < n_steps && !s->multistep(); ++i)
         s->sigma[i] = step_kind == MRISR_STEP_DDPM ? coef[8 * i + 4] : (step_kind == MRISR_STEP_RESSHIFT ? coef[4 * i + 3] : 0.f);
     TRY(s->d_ts.reserve(sizeof(long long) * n_steps, false));
     TRY(s->d_coef.reserve(sizeof(float) * coef.size(), false));
@@ -237,10 +350,32 @@ int mrisr_sampler_create(mrisr_model* unet, mrisr_model* controlnet, int step_ki
 }
 void mrisr_sampler_destroy(mrisr_sampler* s) { delete s; }
 int mrisr_sampler_set_range(mrisr_sampler* s, int first_step, int last_step) {
+    API_BEGIN
     MRISR_REQUIRE(s && first_step >= 0 && first_step <= last_step && last_step <= s->n_steps, "step range");
     s->first = first_step;
     s->last = last_step;
+    s->rebuild_rows();  // multistep kinds start cold at first_step: order 1, no corrector (allocates: hence the guard)
     return 0;
+    API_END
+}
+
+int mrisr_sampler_set_solver(mrisr_sampler* s, int solver_order, int final_sigmas_zero, int lower_order_final,
+                             const int* disable_corrector, int n_disable) {
+    API_BEGIN
+    MRISR_REQUIRE(s, "null sampler");
+    MRISR_REQUIRE(s->multistep(), "solver options belong to the multistep kinds (UniPC, DPM-Solver++)");
+    MRISR_REQUIRE(solver_order >= 1 && solver_order <= (s->kind == MRISR_STEP_UNIPC ? 3 : 2),
+                  "solver_order: 1..3 for UniPC, 1..2 for DPM-Solver++");
+    MRISR_REQUIRE(lower_order_final == 1, "lower_order_final = false is not implemented");
+    MRISR_REQUIRE(n_disable >= 0 && (n_disable == 0 || disable_corrector), "disable_corrector: a list of step indices");
+    MRISR_REQUIRE(n_disable == 0 || s->kind == MRISR_STEP_UNIPC, "disable_corrector belongs to UniPC");
+    s->ms.order = solver_order;
+    s->ms.final_zero = final_sigmas_zero ? 1 : 0;
+    s->ms.lower_order_final = 1;
+    s->ms.disable_corrector.assign(disable_corrector, disable_corrector + n_disable);
+    s->rebuild_rows();
+    return 0;
+    API_END
 }
 
 int mrisr_sampler_set_clip(mrisr_sampler* s, float clip_sample_range) {
@@ -269,6 +404,7 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
     MRISR_REQUIRE(s && latents && ehs, "null argument");
     MRISR_REQUIRE(latents->ndim == 4 && latents->dtype == MRISR_F32 && latents->layout == MRISR_NCHW, "latents: f32 NCHW");
     MRISR_REQUIRE(s->kind != MRISR_STEP_RESSHIFT || lr_latents, "Res-SRDiff needs the LR anchor latents");
+    MRISR_REQUIRE(!s->multistep() || !step_noise, "the multistep solvers are deterministic: step_noise is refused");
     MRISR_REQUIRE(!s->cnet || cond, "ControlNet needs the condition image");
     hipStream_t user = (hipStream_t)stream;
     hipStream_t st = user;
@@ -291,6 +427,7 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
         MRISR_REQUIRE(ehs->ndim == 3 && ehs->shape[0] == NB && ehs->shape[2] == U.cfg.cross_attention_dim,
                       "guided run: encoder_hidden_states must be [2B, L, cross_attention_dim]: B unconditional rows, then B conditional rows");
     if (guided) MRISR_REQUIRE(B > 0 && per % 4 == 0, "guided run: C*h*w of the latents must be a multiple of 4");
+    if (s->multistep()) MRISR_REQUIRE(B > 0 && per % 4 == 0, "multistep solvers: C*h*w of the latents must be a multiple of 4");
     if (lr_latents) MRISR_REQUIRE(lr_latents->dtype == MRISR_F32 && numel(lr_latents) == n, "lr_latents: f32, same shape as latents");
     if (cond) MRISR_REQUIRE(cond->ndim == 4 && cond->shape[0] == NB && cond->shape[2] == 8 * h && cond->shape[3] == 8 * w,
                             guided ? "guided run: controlnet_cond must be [2B, C, 8h, 8w] (the [B] images twice)"
@@ -388,6 +525,23 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
         tguard.a = &U;
         if (s->cnet) { TRY(build(*s->cnet, s->tp_cnet)); tguard.b = s->cnet; }
     }
+    float* hist = nullptr;
+    float* xc = nullptr;
+    if (s->multistep()) {
+        // this range's rows, and a zeroed history: the rows of a cold start carry zero coefficients for the absent terms, and
+        // 0 x (whatever an earlier run or the allocator left) is not 0
+        TRY(s->d_hist.reserve((size_t)s->ms.order * n * sizeof(float), false));
+        MRISR_CHECK_HIP(hipMemsetAsync(s->d_hist.p, 0, (size_t)s->ms.order * n * sizeof(float), st));
+        hist = static_cast<float*>(s->d_hist.p);
+        if (s->kind == MRISR_STEP_UNIPC) {
+            TRY(s->d_xc.reserve((size_t)n * sizeof(float), false));
+            MRISR_CHECK_HIP(hipMemsetAsync(s->d_xc.p, 0, (size_t)n * sizeof(float), st));
+            xc = static_cast<float*>(s->d_xc.p);
+        }
+        // ms_rows is pageable and may be rebuilt (set_solver / set_range) right after this call returns: like the copy of s->first
+        // below, this relies on the runtime staging a pageable host-to-device copy before hipMemcpyAsync returns
+        MRISR_CHECK_HIP(hipMemcpyAsync(s->d_coef.p, s->ms_rows.data(), sizeof(float) * s->ms_rows.size(), hipMemcpyHostToDevice, st));
+    }
     MRISR_CHECK_HIP(hipMemsetAsync(s->d_step.p, 0, 16, st));
     MRISR_CHECK_HIP(hipMemcpyAsync(s->d_step.p, &s->first, sizeof(int), hipMemcpyHostToDevice, st));
 
@@ -409,7 +563,11 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
         if (guided)
             TRY(launch_guided_step(s->kind, (float*)latents->data, (float*)s->d_x2.p, (const float*)s->d_eps.p,
                                    lr_latents ? (const float*)lr_latents->data : nullptr, step_noise ? (const float*)step_noise->data : nullptr,
-                                   (const float*)s->d_coef.p, step, s->clip, s->guidance_scale, s->guidance_rescale, B, per, st));
+                                   (const float*)s->d_coef.p, step, s->clip, s->guidance_scale, s->guidance_rescale, B, per, st, hist, xc,
+                                   s->ms.order));
+        else if (s->multistep())
+            TRY(launch_multistep_step((float*)latents->data, (const float*)s->d_eps.p, lr_latents ? (const float*)lr_latents->data : nullptr,
+                                      (const float*)s->d_coef.p, step, hist, xc, s->ms.order, n, st));
         else if (s->kind == MRISR_STEP_DDIM)
             TRY(launch_ddim_step((float*)latents->data, (const float*)s->d_eps.p, (const float*)s->d_coef.p, step, n, st));
         else if (s->kind == MRISR_STEP_DDPM)
@@ -440,6 +598,11 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
             if (guided) {  // the 2B geometry, the staging buffer and the two scalars the guided step takes by value
                 snprintf(kb, sizeof(kb), ",G%p,%a,%a", s->d_x2.p, (double)s->guidance_scale, (double)s->guidance_rescale);
                 key += kb;
+            }
+            if (s->multistep()) {  // the ring, the corrected state and the solver order the step takes by value; the other options live in the rows
+                snprintf(kb, sizeof(kb), ",M%p,%p,%d,%d,%d", (void*)hist, (void*)xc, s->ms.order, s->ms.final_zero, s->ms.lower_order_final);
+                key += kb;
+                for (int d : s->ms.disable_corrector) { snprintf(kb, sizeof(kb), ",d%d", d); key += kb; }
             }
         }
         if (!s->exec || s->graph_key != key) {
@@ -503,6 +666,45 @@ int mrisr_op_guided_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const
     TRY(launch_guided_step(step_kind, (float*)x->data, (float*)x2->data, (const float*)eps2->data, lr ? (const float*)lr->data : nullptr,
                            noise ? (const float*)noise->data : nullptr, (const float*)d_row.p, (const int*)d_step.p, clip,
                            guidance_scale, guidance_rescale, B, per, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
+// the multistep step alone, on caller buffers (parity test): row_host = one 16-float row; slot = the step counter the kernel sees
+int mrisr_op_multistep_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const mrisr_tensor* eps, const mrisr_tensor* lr,
+                            mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot, float guidance_scale,
+                            float guidance_rescale, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(x && eps && hist && row_host, "multistep step: null argument");
+    MRISR_REQUIRE(step_kind == MRISR_STEP_UNIPC || step_kind == MRISR_STEP_DPMSOLVERPP, "multistep step: UniPC or DPM-Solver++");
+    MRISR_REQUIRE(solver_order >= 1 && solver_order <= 3 && slot >= 0 && slot < 1024, "multistep step: solver order 1..3, slot 0..1023");
+    MRISR_REQUIRE((step_kind == MRISR_STEP_UNIPC) == (xc != nullptr), "multistep step: the corrected-state buffer belongs to UniPC");
+    auto numel = [](const mrisr_tensor* t) { long long k = 1; for (int i = 0; i < t->ndim; ++i) k *= t->shape[i]; return k; };
+    MRISR_REQUIRE(x->ndim == 4 && x->dtype == MRISR_F32 && x->shape[0] > 0, "multistep step: x must be f32 [B, C, h, w]");
+    const int B = (int)x->shape[0];
+    const long long n = numel(x), per = n / B;
+    MRISR_REQUIRE(per % 4 == 0, "multistep step: C*h*w must be a multiple of 4");
+    MRISR_REQUIRE(eps->dtype == MRISR_F32 && numel(eps) == (x2 ? 2 : 1) * n, "multistep step: eps must be f32 [B] (plain) or [2B] (guided)");
+    if (x2) MRISR_REQUIRE(x2->dtype == MRISR_F32 && numel(x2) == 2 * n, "multistep step: the staging buffer must be f32 [2B, C, h, w]");
+    if (lr) MRISR_REQUIRE(lr->dtype == MRISR_F32 && numel(lr) == n, "multistep step: lr must be f32 [B, C, h, w]");
+    MRISR_REQUIRE(hist->dtype == MRISR_F32 && numel(hist) == (long long)solver_order * n, "multistep step: hist must be f32 [order, B, C, h, w]");
+    if (xc) MRISR_REQUIRE(xc->dtype == MRISR_F32 && numel(xc) == n, "multistep step: xc must be f32 [B, C, h, w]");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<float> rows((size_t)(slot + 1) * 16, 0.f);
+    std::copy(row_host, row_host + 16, rows.begin() + (size_t)slot * 16);
+    DevBuf d_rows, d_step;
+    TRY(d_rows.reserve(sizeof(float) * rows.size(), false));
+    TRY(d_step.reserve(16, true));
+    MRISR_CHECK_HIP(hipMemcpyAsync(d_rows.p, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice, st));
+    MRISR_CHECK_HIP(hipMemcpyAsync(d_step.p, &slot, sizeof(int), hipMemcpyHostToDevice, st));
+    if (x2)
+        TRY(launch_guided_step(step_kind, (float*)x->data, (float*)x2->data, (const float*)eps->data, lr ? (const float*)lr->data : nullptr,
+                               nullptr, (const float*)d_rows.p, (const int*)d_step.p, 0.f, guidance_scale, guidance_rescale, B, per, st,
+                               (float*)hist->data, xc ? (float*)xc->data : nullptr, solver_order));
+    else
+        TRY(launch_multistep_step((float*)x->data, (const float*)eps->data, lr ? (const float*)lr->data : nullptr, (const float*)d_rows.p,
+                                  (const int*)d_step.p, (float*)hist->data, xc ? (float*)xc->data : nullptr, solver_order, n, st));
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
     API_END

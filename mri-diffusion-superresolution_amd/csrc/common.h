@@ -442,7 +442,13 @@ int launch_advance_step(int* step_idx, hipStream_t st);
 //   classifier-free guidance: eps2 = [uncond rows; cond rows] of a [2B] forward -> guided (and rescaled) eps -> the step above of kind
 //   `kind`; the new x goes to x [B] and to both halves of the staging buffer x2 [2B].  `per` = elements per sample (multiple of 4)
 int launch_guided_step(int kind, float* x, float* x2, const float* eps2, const float* lr, const float* noise, const float* coef_table,
-                       const int* step_idx, float clip, float g, float phi, int B, long long per, hipStream_t st);
+                       const int* step_idx, float clip, float g, float phi, int B, long long per, hipStream_t st, float* hist = nullptr,
+                       float* xc = nullptr, int order = 0);
+//   multistep step (MRISR_STEP_UNIPC / MRISR_STEP_DPMSOLVERPP): rows of 16 floats (misc.hip), hist = `order` slabs of n floats (the x0
+//   predictions, slot step % order), xc = the previous corrected state (UniPC) or nullptr; lr (or nullptr) anchors the state: the solver
+//   runs on x - lr.  n must be a multiple of 4.  The guided form is launch_guided_step with the same three buffers.
+int launch_multistep_step(float* x, const float* eps, const float* lr, const float* coef_table, const int* step_idx, float* hist, float* xc,
+                          int order, long long n, hipStream_t st);
 //   forward shift (reference res_srdiff.py:7-25): per-sample alpha from table[t[b]]
 int launch_resshift_forward(const float* hr, const float* lr, const float* noise, const float* alphas_cumprod,
                             const long long* t, int t_is_scalar, float* out, int B, long long per_sample,

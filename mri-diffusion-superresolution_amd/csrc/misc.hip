@@ -886,6 +886,7 @@ int launch_ddpm_step(float* x, const float* eps, const float* noise, const float
 struct StepRow { float a, b, c, d, sig; };
 __device__ __forceinline__ StepRow load_step_row(int kind, const float* coef, int s) {
     StepRow r{0.f, 0.f, 0.f, 0.f, 0.f};
+    if (kind > MRISR_STEP_DDPM) return r;  // multistep kinds read their own 16-float row (multistep_value4)
     if (kind == MRISR_STEP_DDIM) { r.a = coef[2 * s]; r.b = coef[2 * s + 1]; }
     else if (kind == MRISR_STEP_RESSHIFT) { r.a = coef[4 * s]; r.b = coef[4 * s + 1]; r.c = coef[4 * s + 2]; r.sig = coef[4 * s + 3]; }
     else { r.a = coef[8 * s]; r.b = coef[8 * s + 1]; r.c = coef[8 * s + 2]; r.d = coef[8 * s + 3]; r.sig = coef[8 * s + 4]; }
@@ -926,19 +927,103 @@ __device__ __forceinline__ void store_x3(float* x, float* x2, long long n, long 
     reinterpret_cast<float4*>(x2 + n)[i4] = v;
 }
 
-__global__ __launch_bounds__(256) void guided_step_kernel(int kind, float* x, float* x2, const float* eps2, const float* lr,
-                                                          const float* noise_base, const float* coef, const int* step, float clip,
-                                                          float g, long long n) {
+// ------------------------------------------------------------------------------------------------
+// multistep step (UniPC bh2 / DPM-Solver++ 2M, data prediction): ONE launch per step.  Every quantity of a linear multistep
+// step is linear in (z, eps, previous corrected state, history), z = x - LR (LR-anchored run) or x, so the host folds the order
+// schedule, the cold first step, disabled correctors and the final point into one row of 16 floats per step (capi.hip:
+// build_multistep_rows); a zero coefficient switches an absent term off and nothing here branches on the step:
+//   row = { m: z, eps | corrected state: z, eps, xc, h1, h2, h3 | next state: z, eps, xc, h1, h2, h3 | 0, 0 }
+//   m   = the x0 prediction at this step            -> history slot s % R   (h_k = the prediction k steps back, slot (s - k) % R)
+//   zc  = the corrected state (UniPC; else unused)  -> xc
+//   x   = next state + LR
+// The three forms are folded separately down to the raw inputs, so the next state never goes through the ill-conditioned
+// m = (z - sigma eps) / alpha of a high-noise step, and order 1 is the DDIM expression itself.  R = solver_order slabs of n floats;
+// the slot an element overwrites is the one it read as h_R.  The ring and xc are zeroed by the host at the start of a run.
+// ------------------------------------------------------------------------------------------------
+struct MsBuf { float* hist; float* xc; int R; };  // xc == nullptr: no corrector (DPM-Solver++)
+constexpr int MS_ROW = 16;
+__device__ __forceinline__ float4 fma4(float c, float4 v, float4 acc) {
+    return make_float4(fmaf(c, v.x, acc.x), fmaf(c, v.y, acc.y), fmaf(c, v.z, acc.z), fmaf(c, v.w, acc.w));
+}
+// one float4 piece: reads the history and xc, writes history slot s % R and xc, returns the new x
+__device__ __forceinline__ float4 multistep_value4(const float* __restrict__ row, const MsBuf& ms, int s, long long n, long long i,
+                                                   float4 xv, float4 e, float4 l) {
+    const float4 z = make_float4(xv.x - l.x, xv.y - l.y, xv.z - l.z, xv.w - l.w);
+    const int cur = s % ms.R;
+    float4 m = fma4(row[1], e, scale4(z, row[0]));
+    float4 zc = fma4(row[3], e, scale4(z, row[2]));
+    float4 zn = fma4(row[9], e, scale4(z, row[8]));
+    if (ms.xc) {
+        const float4 xc = reinterpret_cast<const float4*>(ms.xc)[i];
+        zc = fma4(row[4], xc, zc);
+        zn = fma4(row[10], xc, zn);
+    }
+#pragma unroll
+    for (int k = 1; k <= 3; ++k) {
+        if (k <= ms.R) {
+            const int slot = (cur + ms.R - (k % ms.R)) % ms.R;
+            const float4 h = reinterpret_cast<const float4*>(ms.hist + (size_t)slot * n)[i];
+            zc = fma4(row[4 + k], h, zc);
+            zn = fma4(row[10 + k], h, zn);
+        }
+    }
+    reinterpret_cast<float4*>(ms.hist + (size_t)cur * n)[i] = m;
+    if (ms.xc) reinterpret_cast<float4*>(ms.xc)[i] = zc;
+    return make_float4(zn.x + l.x, zn.y + l.y, zn.z + l.z, zn.w + l.w);
+}
+__global__ __launch_bounds__(256) void multistep_step_kernel(float* x, const float* eps, const float* lr, const float* coef, const int* step,
+                                                             MsBuf ms, long long n) {
     const int s = *step;
-    const StepRow r = load_step_row(kind, coef, s);
-    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
+    const float* row = coef + (size_t)MS_ROW * s;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256) {
-        const float4 eu = reinterpret_cast<const float4*>(eps2)[i], ec = reinterpret_cast<const float4*>(eps2 + n)[i];
-        const float4 xv = reinterpret_cast<const float4*>(x)[i];
         const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
+        reinterpret_cast<float4*>(x)[i] =
+            multistep_value4(row, ms, s, n, i, reinterpret_cast<const float4*>(x)[i], reinterpret_cast<const float4*>(eps)[i], l);
+    }
+}
+static int check_multistep(const float* x, const float* eps, const float* lr, const MsBuf& ms, long long n) {
+    MRISR_REQUIRE(x && eps && ms.hist && ms.R >= 1 && ms.R <= 3, "multistep step: null operand or solver order outside 1..3");
+    MRISR_REQUIRE(n > 0 && n % 4 == 0, "multistep step: C*h*w of the latents must be a multiple of 4");
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    MRISR_REQUIRE(al16(x) && al16(eps) && al16(lr) && al16(ms.hist) && al16(ms.xc), "multistep step: operands must be 16-byte aligned");
+    return 0;
+}
+int launch_multistep_step(float* x, const float* eps, const float* lr, const float* coef_table, const int* step_idx, float* hist, float* xc,
+                          int order, long long n, hipStream_t st) {
+    const MsBuf ms{hist, xc, order};
+    MRISR_REQUIRE(coef_table && step_idx, "multistep step: null operand");
+    if (int rc = check_multistep(x, eps, lr, ms, n)) return rc;
+    // x in and out, eps, `order` history reads, one history write, xc in and out, lr
+    ProfScope ps("sampler_step", 0.0, (16.0 + 4.0 * order + (xc ? 8.0 : 0.0) + (lr ? 4.0 : 0.0)) * n, st);
+    hipLaunchKernelGGL(multistep_step_kernel, dim3(nblocks(n >> 2)), dim3(256), 0, st, x, eps, lr, coef_table, step_idx, ms, n);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+// the update of one float4 piece of a guided step with the guided prediction e: the step kinds above, or the multistep step
+__device__ __forceinline__ void guided_apply4(int kind, const StepRow& r, const float* msrow, const MsBuf& ms, int s, float clip, float* x,
+                                              float* x2, const float* lr, const float* noise, long long n, long long i, float4 e) {
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 xv = reinterpret_cast<const float4*>(x)[i];
+    const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
+    if (msrow) {
+        store_x3(x, x2, n, i, multistep_value4(msrow, ms, s, n, i, xv, e, l));
+    } else {
         const float4 nz = noise ? reinterpret_cast<const float4*>(noise)[i] : z4;
-        store_x3(x, x2, n, i, step_value4(kind, r, clip, xv, guide4(eu, ec, g), l, nz, noise != nullptr));
+        store_x3(x, x2, n, i, step_value4(kind, r, clip, xv, e, l, nz, noise != nullptr));
+    }
+}
+
+__global__ __launch_bounds__(256) void guided_step_kernel(int kind, float* x, float* x2, const float* eps2, const float* lr,
+                                                          const float* noise_base, const float* coef, const int* step, float clip,
+                                                          float g, long long n, MsBuf ms) {
+    const int s = *step;
+    const StepRow r = load_step_row(kind, coef, s);
+    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
+    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256) {
+        const float4 eu = reinterpret_cast<const float4*>(eps2)[i], ec = reinterpret_cast<const float4*>(eps2 + n)[i];
+        guided_apply4(kind, r, msrow, ms, s, clip, x, x2, lr, noise, n, i, guide4(eu, ec, g));
     }
 }
 
@@ -966,10 +1051,11 @@ __device__ __forceinline__ float rescale_factor(float qc, float qe, float me, in
 template <int ITEMS>
 __global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(int kind, float* x, float* x2, const float* eps2, const float* lr,
                                                                          const float* noise_base, const float* coef, const int* step,
-                                                                         float clip, float g, float phi, int B, int per) {
+                                                                         float clip, float g, float phi, int B, int per, MsBuf ms) {
     __shared__ float red[2 * GS_THREADS / 64];
     const int s = *step;
     const StepRow r = load_step_row(kind, coef, s);
+    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
     const long long n = (long long)B * per;
     const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
     const long long base4 = (long long)blockIdx.x * (per >> 2);
@@ -999,27 +1085,21 @@ __global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(int kin
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
         const int j = threadIdx.x + k * GS_THREADS;
-        if (j < per4) {
-            const long long i = base4 + j;
-            const float4 xv = reinterpret_cast<const float4*>(x)[i];
-            const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
-            const float4 nz = noise ? reinterpret_cast<const float4*>(noise)[i] : z4;
-            store_x3(x, x2, n, i, step_value4(kind, r, clip, xv, scale4(e[k], f), l, nz, noise != nullptr));
-        }
+        if (j < per4) guided_apply4(kind, r, msrow, ms, s, clip, x, x2, lr, noise, n, base4 + j, scale4(e[k], f));
     }
 }
 // samples too large for the register file: the same three passes, each re-reading eps2
 __global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_reread_kernel(int kind, float* x, float* x2, const float* eps2, const float* lr,
                                                                                 const float* noise_base, const float* coef, const int* step,
-                                                                                float clip, float g, float phi, int B, int per) {
+                                                                                float clip, float g, float phi, int B, int per, MsBuf ms) {
     __shared__ float red[2 * GS_THREADS / 64];
     const int s = *step;
     const StepRow r = load_step_row(kind, coef, s);
+    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
     const long long n = (long long)B * per;
     const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
     const long long base4 = (long long)blockIdx.x * (per >> 2);
     const int per4 = per >> 2;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     const float4* pu = reinterpret_cast<const float4*>(eps2) + base4;
     const float4* pc = reinterpret_cast<const float4*>(eps2 + n) + base4;
     float sc = 0.f, se = 0.f;
@@ -1030,17 +1110,19 @@ __global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_reread_kernel(
     for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 c = pc[j]; qc += ssq4(c, mc); qe += ssq4(guide4(pu[j], c, g), me); }
     block_sum2(qc, qe, red);
     const float f = rescale_factor(qc, qe, me, per, phi);
-    for (int j = threadIdx.x; j < per4; j += GS_THREADS) {
-        const long long i = base4 + j;
-        const float4 xv = reinterpret_cast<const float4*>(x)[i];
-        const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
-        const float4 nz = noise ? reinterpret_cast<const float4*>(noise)[i] : z4;
-        store_x3(x, x2, n, i, step_value4(kind, r, clip, xv, scale4(guide4(pu[j], pc[j], g), f), l, nz, noise != nullptr));
-    }
+    for (int j = threadIdx.x; j < per4; j += GS_THREADS)
+        guided_apply4(kind, r, msrow, ms, s, clip, x, x2, lr, noise, n, base4 + j, scale4(guide4(pu[j], pc[j], g), f));
 }
 int launch_guided_step(int kind, float* x, float* x2, const float* eps2, const float* lr, const float* noise, const float* coef_table,
-                       const int* step_idx, float clip, float g, float phi, int B, long long per, hipStream_t st) {
-    MRISR_REQUIRE(kind >= MRISR_STEP_DDIM && kind <= MRISR_STEP_DDPM, "guided step: unknown step kind");
+                       const int* step_idx, float clip, float g, float phi, int B, long long per, hipStream_t st, float* hist, float* xc,
+                       int order) {
+    MRISR_REQUIRE(kind >= MRISR_STEP_DDIM && kind <= MRISR_STEP_DPMSOLVERPP, "guided step: unknown step kind");
+    const bool multistep = kind > MRISR_STEP_DDPM;
+    const MsBuf ms{multistep ? hist : nullptr, multistep && kind == MRISR_STEP_UNIPC ? xc : nullptr, multistep ? order : 0};
+    if (multistep) {
+        if (int rc = check_multistep(x, eps2, lr, ms, (long long)B * per)) return rc;
+        MRISR_REQUIRE(kind != MRISR_STEP_UNIPC || xc, "guided step: UniPC needs the corrected-state buffer");
+    }
     MRISR_REQUIRE(x && x2 && eps2 && coef_table && step_idx && B > 0 && per > 0, "guided step: null operand");
     MRISR_REQUIRE(per % 4 == 0 && per < (1ll << 31), "guided step: the per-sample size must be a multiple of 4");
     MRISR_REQUIRE(phi >= 0.f && phi <= 1.f, "guided step: guidance_rescale must lie in [0, 1]");
@@ -1048,22 +1130,23 @@ int launch_guided_step(int kind, float* x, float* x2, const float* eps2, const f
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     MRISR_REQUIRE(al16(x) && al16(x2) && al16(eps2) && al16(lr) && al16(noise), "guided step: operands must be 16-byte aligned");
     const long long n = (long long)B * per;
-    if (kind != MRISR_STEP_RESSHIFT) lr = nullptr;
-    if (kind == MRISR_STEP_DDIM) noise = nullptr;
-    ProfScope ps("sampler_step", 0.0, 28.0 * n + (lr ? 4.0 * n : 0.0), st);
+    if (kind != MRISR_STEP_RESSHIFT && !multistep) lr = nullptr;
+    if (kind == MRISR_STEP_DDIM || multistep) noise = nullptr;
+    // eps2 twice, x in, three stores of x; multistep: + `order` history reads, one history write, xc in and out
+    ProfScope ps("sampler_step", 0.0, (28.0 + (lr ? 4.0 : 0.0) + (multistep ? 4.0 * order + 4.0 + (ms.xc ? 8.0 : 0.0) : 0.0)) * n, st);
     if (phi == 0.f) {
         hipLaunchKernelGGL(guided_step_kernel, dim3(nblocks(n >> 2)), dim3(256), 0, st, kind, x, x2, eps2, lr, noise, coef_table, step_idx,
-                           clip, g, n);
+                           clip, g, n, ms);
     } else {
 #define MRISR_GS(ITEMS)                                                                                                              \
     hipLaunchKernelGGL(guided_step_rescale_kernel<ITEMS>, dim3(B), dim3(GS_THREADS), 0, st, kind, x, x2, eps2, lr, noise, coef_table, \
-                       step_idx, clip, g, phi, B, (int)per)
+                       step_idx, clip, g, phi, B, (int)per, ms)
         if (per <= 4 * GS_THREADS) MRISR_GS(1);
         else if (per <= 8 * GS_THREADS) MRISR_GS(2);
         else if (per <= 16 * GS_THREADS) MRISR_GS(4);
         else
             hipLaunchKernelGGL(guided_step_rescale_reread_kernel, dim3(B), dim3(GS_THREADS), 0, st, kind, x, x2, eps2, lr, noise,
-                               coef_table, step_idx, clip, g, phi, B, (int)per);
+                               coef_table, step_idx, clip, g, phi, B, (int)per, ms);
 #undef MRISR_GS
     }
     MRISR_CHECK_HIP(hipGetLastError());

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "csrc", "libmrisr.so")
 
 MRISR_F32, MRISR_BF16, MRISR_F16, MRISR_I64 = 0, 1, 2, 3
 MRISR_NCHW, MRISR_NHWC = 0, 1
-STEP_DDIM, STEP_RESSHIFT, STEP_DDPM = 0, 1, 2
+STEP_DDIM, STEP_RESSHIFT, STEP_DDPM, STEP_UNIPC, STEP_DPMSOLVERPP = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_GEGLU = 0, 1, 2, 3
 
 _DT = {torch.float32: MRISR_F32, torch.bfloat16: MRISR_BF16, torch.float16: MRISR_F16, torch.int64: MRISR_I64}
@@ -59,7 +59,7 @@ EXPORTS = [
     "mrisr_model_skip_shape", "mrisr_controlnet_forward", "mrisr_controlnet_set_cond", "mrisr_adapter_create",
     "mrisr_adapter_destroy", "mrisr_adapter_set_param", "mrisr_adapter_finalize", "mrisr_adapter_forward",
     "mrisr_resshift_forward", "mrisr_sampler_create", "mrisr_sampler_destroy", "mrisr_sampler_run", "mrisr_sampler_set_range", "mrisr_sampler_set_clip",
-    "mrisr_sampler_set_guidance", "mrisr_sampler_run_guided", "mrisr_op_guided_step",
+    "mrisr_sampler_set_guidance", "mrisr_sampler_run_guided", "mrisr_op_guided_step", "mrisr_sampler_set_solver", "mrisr_op_multistep_step",
     "mrisr_adapter_train_prepare", "mrisr_adapter_train_num_trainable", "mrisr_adapter_train_num_tensors",
     "mrisr_adapter_train_tensor_info", "mrisr_adapter_train_bind", "mrisr_adapter_train_refresh", "mrisr_adapter_backward", "mrisr_adapter_backward_level", "mrisr_adapter_train_level_range",
     "mrisr_vae_create", "mrisr_vae_destroy", "mrisr_vae_set_param", "mrisr_vae_num_params", "mrisr_vae_finalize",
@@ -97,6 +97,9 @@ def lib() -> C.CDLL:
         L.mrisr_sampler_set_guidance.argtypes = [C.c_void_p, C.c_float, C.c_float]
         L.mrisr_op_guided_step.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                            C.c_float, C.c_float, C.c_void_p]
+        L.mrisr_sampler_set_solver.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.mrisr_op_multistep_step.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]
         # backward op entry points: raw device pointers, so every argument is typed (an untyped Python int is passed as a C int)
         P, I, F, Q = C.c_void_p, C.c_int, C.c_float, C.c_int64
         L.mrisr_op_groupnorm_bwd.argtypes = [I, P, I, P, I, I, I, P, P, I, F, I, P, P, I, P, I, P, P, P]

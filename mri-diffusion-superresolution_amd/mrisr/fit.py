@@ -76,6 +76,13 @@ def check_config(config: TrainConfig, caption_embeds: Optional[Dict[str, torch.T
         raise ValueError("lr_warmup_steps must be >= 0")
 
 
+def check_validation_solver(validation_solver) -> None:
+    """What ``fit(validation_solver=...)`` refuses, before any GPU work: anything but ``None`` or a multistep sampler kind."""
+    if validation_solver is not None:
+        from .pipeline import check_solver
+        check_solver(validation_solver)
+
+
 def check_validation_guidance(guidance_scale: float, guidance_rescale: float,
                               caption_embeds: Optional[Dict[str, torch.Tensor]]) -> bool:
     """What ``fit(validation_guidance_scale=..., validation_guidance_rescale=...)`` refuses, before any GPU work: the rules of
@@ -382,15 +389,19 @@ def _world(process_group) -> Tuple[int, int]:
 
 def fit(config: TrainConfig, unet, vae, train_dataset, caption_embeds: Dict[str, torch.Tensor], val_dataset=None, fixed_embeds=None,
         resume_from: Optional[str] = None, use_ema: bool = False, process_group=None, adapter=None,
-        validation_guidance_scale: float = 1.0, validation_guidance_rescale: float = 0.0) -> FitResult:
+        validation_guidance_scale: float = 1.0, validation_guidance_rescale: float = 0.0,
+        validation_solver: Optional[str] = None) -> FitResult:
     """LoRA fine-tuning of ``unet`` (created with ``lora_rank > 0, lora_fused=True`` and loaded) on ``train_dataset`` (items
     ``{'hr', 'lr', 'txt'}``, images in [-1, 1]); ``caption_embeds[txt]`` is the [L, D] text embedding of each prompt ("" for the
     dropped caption).  Writes ``output_dir/metrics.jsonl``, ``validation/step-N.png`` (with ``val_dataset``) and
     ``checkpoint-N/``; ``resume_from`` is such a checkpoint directory.  ``adapter``: a loaded ``Adapter_XL`` trained as well,
     conditioned on each item's LR image; with a ``lora_rank=0`` UNet it is the only thing trained (the UNet is frozen).
     ``validation_guidance_scale`` / ``validation_guidance_rescale``: the validation panels are sampled with classifier-free guidance
-    against ``caption_embeds[""]`` (``log_validation``); the defaults sample as before."""
+    against ``caption_embeds[""]`` (``log_validation``); the defaults sample as before.  ``validation_solver`` ("unipc" /
+    "dpmsolver++"): the panels are sampled with that LR-anchored deterministic multistep solver (order 2, "zero" final point) and no
+    step noise is drawn; ``None`` keeps the reference's stochastic sampler."""
     check_config(config, caption_embeds)
+    check_validation_solver(validation_solver)
     guided = check_validation_guidance(validation_guidance_scale, validation_guidance_rescale, caption_embeds)
     guidance = (float(validation_guidance_scale), float(validation_guidance_rescale)) if guided else None
     # the whole run on one side stream: graph launches, the all-reduce between them, ring reads, checkpoints and validation are then
@@ -399,13 +410,13 @@ def fit(config: TrainConfig, unet, vae, train_dataset, caption_embeds: Dict[str,
     side.wait_stream(torch.cuda.current_stream(unet.device))
     with torch.cuda.stream(side):
         res = _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_embeds, resume_from, use_ema, process_group,
-                   adapter, guidance)
+                   adapter, guidance, validation_solver)
     torch.cuda.current_stream(unet.device).wait_stream(side)
     return res
 
 
 def _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_embeds, resume_from, use_ema, process_group,
-         adapter=None, guidance=None) -> FitResult:
+         adapter=None, guidance=None, validation_solver=None) -> FitResult:
     want = L.torch_dtype(L.dtype_id(config.compute_dtype()))
     if unet.compute_dtype != want:
         raise ValueError(f"mixed_precision={config.mixed_precision!r} means compute dtype {want}; the UNet computes in {unet.compute_dtype}")
@@ -460,9 +471,11 @@ def _fit(config, unet, vae, train_dataset, caption_embeds, val_dataset, fixed_em
             fixed_embeds = torch.as_tensor(caption_embeds[txt] if txt in caption_embeds else next(iter(caption_embeds.values())))
         fixed_embeds = fixed_embeds.reshape(-1, *fixed_embeds.shape[-2:]).to(unet.device, torch.float32)
     val_kw = {}
+    if validation_solver is not None:
+        val_kw["solver"] = validation_solver
     if guidance is not None:  # classifier-free guidance against the embedding the caption dropout trained on
         empty = torch.as_tensor(caption_embeds[""])
-        val_kw = dict(guidance_scale=guidance[0], guidance_rescale=guidance[1],
+        val_kw.update(guidance_scale=guidance[0], guidance_rescale=guidance[1],
                       uncond_embeds=empty.reshape(-1, *empty.shape[-2:]).to(unet.device, torch.float32))
 
     samples = config.train_batch_size * config.gradient_accumulation_steps * world

@@ -91,16 +91,53 @@ def check_guidance(guidance_scale, guidance_rescale, ehs_shape, uncond_shape, ba
     return True
 
 
+MULTISTEP_KINDS = ("unipc", "dpmsolver++")
+
+
+def check_solver(kind, solver_order=2, final_sigmas_type="zero", lower_order_final=True, disable_corrector=()):
+    """The argument rules of the multistep sampler kinds (no device is touched); returns the normalised
+    (solver_order, final_sigmas_type, disable_corrector).  Raises ``ValueError`` for anything the solver could not honour."""
+    if kind not in MULTISTEP_KINDS:
+        raise ValueError(f"solver must be one of {MULTISTEP_KINDS}, got {kind!r}")
+    top = 3 if kind == "unipc" else 2
+    if isinstance(solver_order, bool) or not isinstance(solver_order, (int, np.integer)) or not 1 <= solver_order <= top:
+        raise ValueError(f"solver_order must be 1..{top} for {kind}, got {solver_order!r}")
+    if final_sigmas_type not in ("zero", "sigma_min"):
+        raise ValueError(f"final_sigmas_type must be 'zero' or 'sigma_min', got {final_sigmas_type!r}")
+    if lower_order_final is not True:
+        raise ValueError("lower_order_final=False is not implemented")
+    disable = [int(i) for i in (disable_corrector or ())]
+    if disable and kind != "unipc":
+        raise ValueError("disable_corrector belongs to UniPC")
+    if any(i < 0 for i in disable):
+        raise ValueError("disable_corrector: step indices must be >= 0")
+    return int(solver_order), final_sigmas_type, disable
+
+
 class Sampler:
     """Owns a C-ABI sampler (device tables + the captured step graph) for one (unet, controlnet, schedule)."""
 
     def __init__(self, unet: UNet2DConditionModel, scheduler, controlnet: Optional[ControlNetModel] = None,
                  kind: str = "ddim", clip_sample_range: float = 0.0):
-        """``kind``: "ddim" (eta 0), "resshift" (res_srdiff.py:84-96) or "ddpm" (ancestral, diffusers DDPMScheduler.step with
-        "fixed_small" variance; ``clip_sample_range`` > 0 clips the predicted x0 as diffusers' ``clip_sample`` does)."""
-        kinds = {"ddim": L.STEP_DDIM, "resshift": L.STEP_RESSHIFT, "ddpm": L.STEP_DDPM}
+        """``kind``: "ddim" (eta 0), "resshift" (res_srdiff.py:84-96), "ddpm" (ancestral, diffusers DDPMScheduler.step with
+        "fixed_small" variance; ``clip_sample_range`` > 0 clips the predicted x0 as diffusers' ``clip_sample`` does), or one of the
+        deterministic multistep solvers "unipc" (UniPC bh2) / "dpmsolver++" (DPM-Solver++ 2M), whose options come from the scheduler
+        (``UniPCMultistepScheduler`` / ``DPMSolverMultistepScheduler``) or from ``set_solver``.  Given ``lr_latents``, a multistep run
+        integrates x - LR: the probability-flow ODE of the reference's shift process, not its stochastic step."""
+        kinds = {"ddim": L.STEP_DDIM, "resshift": L.STEP_RESSHIFT, "ddpm": L.STEP_DDPM, "unipc": L.STEP_UNIPC,
+                 "dpmsolver++": L.STEP_DPMSOLVERPP}
         if kind not in kinds:
             raise ValueError(f"unknown sampler kind {kind!r}")
+        solver = None
+        if kind in MULTISTEP_KINDS:
+            if clip_sample_range > 0:
+                raise ValueError("clip_sample_range belongs to the DDPM step; the multistep solvers do not clip")
+            if getattr(scheduler, "kind", kind) != kind:
+                raise ValueError(f"a {type(scheduler).__name__} cannot drive Sampler(kind={kind!r})")
+            solver = check_solver(kind, getattr(scheduler, "solver_order", 2), getattr(scheduler, "final_sigmas_type", "zero"),
+                                  getattr(scheduler, "lower_order_final", True), getattr(scheduler, "disable_corrector", ()))
+            if len(scheduler.timesteps) > 1 and not bool((scheduler.timesteps[1:] < scheduler.timesteps[:-1]).all()):
+                raise ValueError("multistep solvers need strictly decreasing timesteps")
         self.unet, self.controlnet, self.kind = unet, controlnet, kind
         ts = scheduler.timesteps.detach().cpu().to(torch.int64).numpy().copy()
         ac = scheduler.alphas_cumprod.detach().cpu().to(torch.float32).numpy().copy()
@@ -112,6 +149,8 @@ class Sampler:
                                              ac.ctypes.data_as(C.c_void_p), int(len(ac)), C.byref(self._h)))
         if clip_sample_range > 0:
             L.check(L.lib().mrisr_sampler_set_clip(self._h, float(clip_sample_range)))
+        if solver is not None:
+            self.set_solver(*solver)
 
     def __del__(self):
         try:
@@ -121,8 +160,21 @@ class Sampler:
         except Exception:
             pass
 
+    def set_solver(self, solver_order: int = 2, final_sigmas_type: str = "zero", disable_corrector=()):
+        """Multistep kinds: change the solver options for the next ``run`` (the step graph is captured again when they change).
+        A sampler built on a ``UniPCMultistepScheduler`` / ``DPMSolverMultistepScheduler`` starts with that scheduler's options,
+        one built on a plain table with order 2 and the "zero" final point."""
+        if self.kind not in MULTISTEP_KINDS:
+            raise ValueError("solver options belong to the multistep kinds")
+        order, final, disable = check_solver(self.kind, solver_order, final_sigmas_type, True, disable_corrector)
+        arr = (C.c_int * max(1, len(disable)))(*disable)
+        L.check(L.lib().mrisr_sampler_set_solver(self._h, order, 1 if final == "zero" else 0, 1, arr if disable else None, len(disable)))
+        self.solver_order, self.final_sigmas_type, self.disable_corrector = order, final, disable
+
     def set_range(self, first_step: int, last_step: int):
-        """Run only steps [first_step, last_step) of the schedule on the next ``run`` (resume / inspection)."""
+        """Run only steps [first_step, last_step) of the schedule on the next ``run`` (resume / inspection).  The multistep kinds start
+        COLD at ``first_step`` (order 1, no corrector: the history of earlier steps is gone), so a split run of theirs is not the
+        full run; the first-order kinds reproduce it."""
         L.check(L.lib().mrisr_sampler_set_range(self._h, int(first_step), int(last_step)))
 
     def run(self, latents: torch.Tensor, encoder_hidden_states: torch.Tensor, lr_latents: Optional[torch.Tensor] = None,
@@ -138,6 +190,13 @@ class Sampler:
         else is given at [B] as without guidance.  Without these arguments, or at g == 1, the call is the unguided one."""
         if latents.dtype != torch.float32 or not latents.is_contiguous():
             raise ValueError("latents must be contiguous float32 (updated in place)")
+        if self.kind in MULTISTEP_KINDS:
+            if step_noise is not None:
+                raise ValueError(f"kind={self.kind!r} is deterministic: step_noise is refused")
+            if latents.ndim != 4 or int(np.prod(latents.shape[1:])) % 4:
+                raise ValueError("the multistep solvers need [B,C,h,w] latents with C*h*w a multiple of 4")
+            if lr_latents is not None and tuple(lr_latents.shape) != tuple(latents.shape):
+                raise ValueError(f"lr_latents must have the latents' shape {tuple(latents.shape)}, got {tuple(lr_latents.shape)}")
         if check_guidance(guidance_scale, guidance_rescale, encoder_hidden_states.shape,
                           None if uncond_hidden_states is None else uncond_hidden_states.shape, latents.shape[0]):
             return self._run_guided(latents, encoder_hidden_states, uncond_hidden_states, lr_latents, step_noise, controlnet_cond,
@@ -194,14 +253,20 @@ class Sampler:
 
 @torch.no_grad()
 def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weight_dtype, accelerator, fixed_embeds,
-                   num_inference_steps=20, adapter=None, guidance_scale=1.0, guidance_rescale=0.0, uncond_embeds=None):
+                   num_inference_steps=20, adapter=None, solver=None, guidance_scale=1.0, guidance_rescale=0.0, uncond_embeds=None):
     """Drop-in for the reference's validation sampler (res_srdiff.py:35-105): same inputs, same PIL panel out.
     The timestep loop is one fused sampler call; the per-step noise is drawn up front from the same global RNG
     stream, in the same order, as the reference's per-step ``torch.randn_like`` calls.  ``adapter`` (a T2I-Adapter):
     its features of the condition image, at the LR image's own size so that they land on the latents, enter every step.
     ``guidance_scale`` / ``guidance_rescale`` / ``uncond_embeds`` (the empty caption's embedding, [1,L,D]): classifier-free
-    guidance as in ``Sampler.run``; the defaults leave the result unchanged."""
+    guidance as in ``Sampler.run``; the defaults leave the result unchanged.  ``solver`` ("unipc" / "dpmsolver++"): sample the panel
+    with that LR-anchored deterministic multistep solver (the scheduler's solver options when it carries any) instead of the
+    reference's stochastic step; no step noise is drawn then.  ``None``: the reference's sampler."""
     from PIL import Image
+
+    if solver is not None:
+        check_solver(solver, getattr(noise_scheduler, "solver_order", 2), getattr(noise_scheduler, "final_sigmas_type", "zero"),
+                     getattr(noise_scheduler, "lower_order_final", True), getattr(noise_scheduler, "disable_corrector", ()))
 
     unet.eval()
     if controlnet is not None:
@@ -217,8 +282,10 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     timesteps = noise_scheduler.timesteps
     latents = get_res_shifting_latents(lr_anchor, lr_anchor, timesteps[0], noise_scheduler).contiguous()
     n_noise = sum(1 for i in range(len(timesteps)) if (int(timesteps[i + 1]) if i + 1 < len(timesteps) else 0) > 0)
+    if solver is not None:
+        n_noise = 0
     step_noise = torch.stack([torch.randn_like(latents) for _ in range(n_noise)]) if n_noise else None
-    sampler = Sampler(unet, noise_scheduler, controlnet, kind="resshift")
+    sampler = Sampler(unet, noise_scheduler, controlnet, kind=solver if solver is not None else "resshift")
     feats = None
     if adapter is not None:
         cond = control_image if tuple(control_image.shape[-2:]) == tuple(lr_raw.shape[-2:]) else \

@@ -471,6 +471,11 @@ int mrisr_op_pointwise_bwd(int kind, int dtype, const void* a, const void* b, vo
  * (f32, pitch ldq); mode 1 (dA): out_j[r][C] += scale * Q_j^T P, P = x [M][C].  r in {4, 8, 12, 16}, nmod <= 3; a NULL out_j is skipped */
 int mrisr_op_lora_wgrad(int dtype, const void* P, int ldp, const float* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN,
                         float* out0, float* out1, float* out2, float scale, void* stream);
+/* dB of an adapter on ff.net.0.proj: P = d pre [M][2*half] (T, pitch ldp) in the projection's 16-wide (value, gate) interleave, Q = z [M][r]
+ * (f32, pitch ldq); out [2*half][r] += scale * P^T Q with its rows in the raw order of lora_B (value rows [0, half), gate rows [half, 2*half)):
+ * the un-interleave happens in the scatter of the reduction */
+int mrisr_op_lora_wgrad_geglu(int dtype, const void* P, int ldp, const float* Q, int ldq, int M, int half, int r, float* out, float scale,
+                              void* stream);
 /* dst[z][c][r] = src[z][r][c] for r < r_valid, 0 for r_valid <= r < R (T; pitches ld_src >= C, ld_dst >= R; batch strides in elements) */
 int mrisr_op_transpose(int dtype, const void* src, void* dst, int R, int C, int ld_src, int ld_dst, int64_t bs_src, int64_t bs_dst,
                        int batch, int r_valid, void* stream);

@@ -751,6 +751,7 @@ struct LoraWgradArgs {
     const float* Q = nullptr;
     int ldq = 0;
     int M = 0, C = 0, mode = 0, r = 0, nmod = 1, secN = 0, qbase = 0;
+    int half = 0;  // mode 0 on ff.net.0.proj: P's columns are (value, gate) interleaved in blocks of 16, out[0] rows are raw
     float* out[3] = {nullptr, nullptr, nullptr};
     float scale = 1.0f;
     float* partial = nullptr;  // [gy][gx * cxb * VE * NQ]
@@ -846,7 +847,10 @@ __global__ __launch_bounds__(256) void lora_wgrad_kernel(const LoraWgradArgs a) 
     for (int i = threadIdx.x; i < tile; i += 256) dst[i] = red[i];
 }
 // sums the partial tiles and adds them into the gradient tensors: 16 outputs x 16 row-slab groups per block (the
-// partial rows are ~100 dependent-latency loads apart if one thread walks them alone)
+// partial rows are ~100 dependent-latency loads apart if one thread walks them alone).  GEGLU (dB of ff.net.0.proj): the partial
+// tiles are in the column order of dpre, packed; the scatter is where a column finds its raw row - value rows [0, half), gate rows
+// [half, 2 half) - so the interleave costs no pass over dpre and no second copy of the gradient
+template <bool GEGLU>
 __global__ __launch_bounds__(256) void lora_wgrad_reduce_kernel(const LoraWgradArgs a, int VE, int NQ) {
     __shared__ float red[16][17];
     const int tile = a.cxb * VE * NQ;
@@ -872,7 +876,9 @@ __global__ __launch_bounds__(256) void lora_wgrad_reduce_kernel(const LoraWgradA
     const int c = bx * a.cxb * VE + cl;
     if (c >= a.C) return;
     s *= a.scale;
-    if (a.mode == 0) {
+    if (GEGLU) {
+        a.out[0][(size_t)geglu_raw_row(c, a.half) * a.r + q] += s;
+    } else if (a.mode == 0) {
         const int j = c / a.secN;
         if (a.out[j]) a.out[j][(size_t)(c - j * a.secN) * a.r + q] += s;
     } else {
@@ -885,14 +891,17 @@ __global__ __launch_bounds__(256) void lora_wgrad_reduce_kernel(const LoraWgradA
 // scratch: lora_wgrad_scratch_bytes(M, C, nmod*r, sizeof(T)) bytes.
 template <typename T>
 int launch_lora_wgrad(const void* P, int ldp, const float* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN,
-                      float* const out[3], float scale, float* scratch, hipStream_t st) {
+                      float* const out[3], float scale, float* scratch, hipStream_t st, int geglu_half) {
     constexpr int VE = BVec<T>::N;
     MRISR_REQUIRE(r % 4 == 0 && r >= 4 && r <= 16 && nmod >= 1 && nmod <= 3, "LoRA wgrad: rank 4/8/12/16, <= 3 fused modules");
+    MRISR_REQUIRE(geglu_half == 0 || (mode == 0 && nmod == 1 && geglu_half % 16 == 0 && C == 2 * geglu_half && secN == C && out[0]),
+                  "LoRA wgrad: the GEGLU interleave is for dB of one [2 * half] projection, half a multiple of 16");
     MRISR_REQUIRE(C % VE == 0 && ldp % VE == 0 && ldq % 4 == 0 && (mode == 1 || secN % VE == 0) && scratch, "LoRA wgrad alignment");
     LoraWgradArgs a;
     a.P = P; a.ldp = ldp; a.Q = Q; a.ldq = ldq; a.M = M; a.C = C; a.mode = mode; a.r = r; a.nmod = nmod; a.secN = secN;
     for (int j = 0; j < 3; ++j) a.out[j] = j < nmod ? out[j] : nullptr;
     a.scale = scale;
+    a.half = geglu_half;
     a.partial = scratch;
     lora_wgrad_geom(a, VE);
     const dim3 grid(a.gx, a.gy);
@@ -909,7 +918,8 @@ int launch_lora_wgrad(const void* P, int ldp, const float* Q, int ldq, int M, in
             default: hipLaunchKernelGGL((lora_wgrad_kernel<T, 16>), grid, dim3(256), smem, st, a); break;
         }
         const int total = a.gx * a.cxb * VE * nq;
-        hipLaunchKernelGGL(lora_wgrad_reduce_kernel, dim3((total + 15) / 16), dim3(256), 0, st, a, VE, nq);
+        if (a.half) hipLaunchKernelGGL(lora_wgrad_reduce_kernel<true>, dim3((total + 15) / 16), dim3(256), 0, st, a, VE, nq);
+        else hipLaunchKernelGGL(lora_wgrad_reduce_kernel<false>, dim3((total + 15) / 16), dim3(256), 0, st, a, VE, nq);
         return 0;
     };
     if (mode == 0) TRY_(go(r, 0));
@@ -1426,7 +1436,7 @@ int launch_ema_sched(float* ema, const float* theta, long long n, const float* d
     template int launch_softmax_bwd<T>(const void*, const float*, void*, int, long long, int, float, hipStream_t);          \
     template int launch_transpose<T>(const void*, void*, int, int, int, int, long long, long long, int, int, hipStream_t);  \
     template int launch_lora_wgrad<T>(const void*, int, const float*, int, int, int, int, int, int, int, float* const[3],   \
-                                      float, float*, hipStream_t);                                                          \
+                                      float, float*, hipStream_t, int);                                                     \
     template int launch_sumpool2<T>(const void*, void*, int, int, int, int, int, hipStream_t);                              \
     template int launch_mse_grad<T>(const void*, const float*, void*, float*, int, int, int, int, hipStream_t);                  \
     template int launch_im2col_all_T<T>(const void*, void*, int, int, int, int, int, int, int, int, int, int, hipStream_t);                    \

@@ -474,7 +474,7 @@ int op_groupnorm_bwd_t(const void* x0, int c0, const void* x1, int c1, int B, in
 
 template <typename T>
 int op_lora_wgrad_t(const void* P, int ldp, const float* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN, float* const out[3],
-                    float scale, hipStream_t st) {
+                    float scale, int geglu_half, hipStream_t st) {
     constexpr int VE = 16 / (int)sizeof(T);
     MRISR_REQUIRE(C % VE == 0 && ldp % VE == 0 && ldp >= C && al16(P), "LoRA wgrad: P rows in whole, aligned 16-byte vectors");
     MRISR_REQUIRE(mode == 1 || (secN % VE == 0 && C == nmod * secN), "LoRA wgrad (dB): C = nmod sections of whole vectors");
@@ -486,7 +486,7 @@ int op_lora_wgrad_t(const void* P, int ldp, const float* Q, int ldq, int M, int 
     OpScratch sc;
     float* scratch = static_cast<float*>(sc.alloc(lora_wgrad_scratch_bytes(M, C, R, sizeof(T))));
     if (!scratch) return 7;
-    TRY(launch_lora_wgrad<T>(P, ldp, Q, ldq, M, C, mode, r, nmod, secN, out, scale, scratch, st));
+    TRY(launch_lora_wgrad<T>(P, ldp, Q, ldq, M, C, mode, r, nmod, secN, out, scale, scratch, st, geglu_half));
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -604,7 +604,20 @@ int mrisr_op_lora_wgrad(int dtype, const void* P, int ldp, const float* Q, int l
     MRISR_REQUIRE(r % 4 == 0 && r >= 4 && r <= 16 && nmod >= 1 && nmod <= 3, "LoRA wgrad: rank 4/8/12/16, <= 3 fused modules");
     MRISR_REQUIRE(ldq % 4 == 0 && ldq >= nmod * r && al16(Q), "LoRA wgrad: Q rows in whole, aligned 16-byte vectors");
     float* const out[3] = {out0, nmod > 1 ? out1 : nullptr, nmod > 2 ? out2 : nullptr};
-    return BWD_DISPATCH(dtype, op_lora_wgrad_t, P, ldp, Q, ldq, M, C, mode, r, nmod, secN, out, scale, (hipStream_t)stream);
+    return BWD_DISPATCH(dtype, op_lora_wgrad_t, P, ldp, Q, ldq, M, C, mode, r, nmod, secN, out, scale, 0, (hipStream_t)stream);
+    API_END
+}
+
+int mrisr_op_lora_wgrad_geglu(int dtype, const void* P, int ldp, const float* Q, int ldq, int M, int half, int r, float* out, float scale,
+                              void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    MRISR_REQUIRE(P && Q && out && M >= 1 && half >= 16 && half <= (1 << 20), "LoRA wgrad (GEGLU): null / empty operand");
+    MRISR_REQUIRE(half % 16 == 0, "LoRA wgrad (GEGLU): the (value, gate) interleave is 16 columns wide");
+    MRISR_REQUIRE(r % 4 == 0 && r >= 4 && r <= 16, "LoRA wgrad: rank 4/8/12/16");
+    MRISR_REQUIRE(ldq % 4 == 0 && ldq >= r && al16(Q), "LoRA wgrad: Q rows in whole, aligned 16-byte vectors");
+    float* const o[3] = {out, nullptr, nullptr};
+    return BWD_DISPATCH(dtype, op_lora_wgrad_t, P, ldp, Q, ldq, M, 2 * half, 0, r, 1, 2 * half, o, scale, half, (hipStream_t)stream);
     API_END
 }
 

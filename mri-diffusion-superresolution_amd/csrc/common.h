@@ -292,9 +292,18 @@ int launch_softmax_bwd(const void* p, const float* dp, void* ds, int ld, long lo
 template <typename T>
 int launch_transpose(const void* src, void* dst, int R, int C, int ld_src, int ld_dst, long long bs_src, long long bs_dst, int batch,
                      int r_valid, hipStream_t st);
+// geglu_half > 0 (mode 0, one module, C = 2 * geglu_half): P's columns are in the GEGLU interleave of ff.net.0.proj, out[0] rows in raw order
 template <typename T>
 int launch_lora_wgrad(const void* P, int ldp, const float* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN,
-                      float* const out[3], float scale, float* scratch, hipStream_t st);
+                      float* const out[3], float scale, float* scratch, hipStream_t st, int geglu_half = 0);
+// the row interleave of ff.net.0.proj: raw row g * half + j (g = 0 value, 1 gate) <-> packed row (j >> 4) * 32 + (j & 15) + 16 g
+__host__ __device__ __forceinline__ int geglu_packed_row(int raw, int half) {
+    const int g = raw >= half, j = g ? raw - half : raw;
+    return (j >> 4) * 32 + (j & 15) + (g ? 16 : 0);
+}
+__host__ __device__ __forceinline__ int geglu_raw_row(int packed, int half) {
+    return ((packed >> 4) & 1) * half + (packed >> 5) * 16 + (packed & 15);
+}
 size_t lora_wgrad_scratch_bytes(int M, int C, int nq, int elem_size);
 template <typename T> int launch_sumpool2(const void* src, void* dst, int B, int H, int W, int C, int accumulate, hipStream_t st);
 template <typename T>

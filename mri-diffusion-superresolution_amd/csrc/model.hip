@@ -141,6 +141,7 @@ struct Packer {
         }
         l.n = ntot;
         l.k = k;
+        l.geglu_half = geglu ? ntot / 2 : 0;
         l.mod_names = mods;
         for (auto& mod : mods) l.mod_lora.push_back(m.find(mod + ".lora_A.default.weight") ? 1 : 0);
         const int ktot = k;
@@ -186,9 +187,9 @@ struct Packer {
             if (la && lb && fused_lora) {
                 const int r = (int)la->shape[0];
                 if (r != l.r || n != l.secN) { set_error("fused LoRA needs the same rank / width for every fused module: " + mod); err = 6; }
-                // A rows -> loraA[rcol .. rcol+r);  (alpha/r) * B -> f32 [n][r] rows of this module
+                // A rows -> loraA[rcol .. rcol+r);  (alpha/r) * B -> f32 [n][r] rows of this module (GEGLU: interleaved like the weight rows)
                 if (launch_pack_rows<T>(static_cast<const float*>(la->data->p), r, k, l.loraA, k, rcol, 0, 0, 0, 1.0f, st)) err = 5;
-                if (launch_pack_rows<float>(static_cast<const float*>(lb->data->p), n, r, lbuf, r, row, 0, 0, 0, m.lora_scale, st)) err = 5;
+                if (launch_pack_rows<float>(static_cast<const float*>(lb->data->p), n, r, lbuf, r, row, 0, geglu ? 1 : 0, n / 2, m.lora_scale, st)) err = 5;
             }
             if (fused_lora && any_lora) rcol += l.r;
             if (const RawParam* b = m.find(mod + ".bias")) {

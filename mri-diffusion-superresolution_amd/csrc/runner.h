@@ -456,7 +456,16 @@ struct Runner {
         } else {
             T* ff = static_cast<T*>(alloc((size_t)M * 4 * C * sizeof(T)));
             if (!ff) return 7;
-            TRY(linear(t, M, C, xw.ff1, ACT_GEGLU, nullptr, 0, nullptr, ff, 4 * C, nullptr, &xw.ln3, nrm));
+            if (xw.ff1.R) {
+                // un-merged adapter on ff.net.0.proj: the GEGLU epilogue has no LoRA term, so the adapted pre-activation is written out
+                // (interleaved columns, loraB in the same order) and gated by its own kernel - the sequence of the training forward
+                T* pre = static_cast<T*>(alloc((size_t)M * 8 * C * sizeof(T)));
+                if (!pre) return 7;
+                TRY(linear(t, M, C, xw.ff1, ACT_NONE, nullptr, 0, nullptr, pre, 8 * C, nullptr, &xw.ln3, nrm));
+                if (!dry) TRY(launch_geglu_fwd<T>(pre, ff, M, 4 * C, st));
+            } else {
+                TRY(linear(t, M, C, xw.ff1, ACT_GEGLU, nullptr, 0, nullptr, ff, 4 * C, nullptr, &xw.ln3, nrm));
+            }
             TRY(linear(ff, M, 4 * C, xw.ff2, ACT_NONE, t, C, nullptr, t, C));
         }
         if (!proj_done) TRY(linear(t, M, C, xw.proj_out, ACT_NONE, x.p, C, nullptr, o.p, C));

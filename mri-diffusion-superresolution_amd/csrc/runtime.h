@@ -79,8 +79,10 @@ struct LinW {  // packed [n][k] in compute dtype, bias f32 (GEGLU: interleaved)
     void* w = nullptr;
     const float* b = nullptr;
     int n = 0, k = 0;
+    int geglu_half = 0;  // > 0 (= n / 2): rows stored in the GEGLU interleave; raw row g * half + j sits at (j >> 4) * 32 + (j & 15) + 16 g
     // fused LoRA (peft): per fused module one rank-r adapter.  loraA [R = nmod*r][k] compute dtype, loraB f32 [n][r]
-    // already scaled by lora_alpha/r; output column n uses z columns (n / secN) * r .. +r
+    // already scaled by lora_alpha/r; output column n uses z columns (n / secN) * r .. +r.  loraB / loraBT follow the row order of w
+    // (geglu_half: interleaved)
     int r = 0, R = 0, secN = 1;
     void* loraA = nullptr;
     const float* loraB = nullptr;

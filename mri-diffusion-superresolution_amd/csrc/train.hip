@@ -22,9 +22,11 @@ namespace mrisr {
 // adapter of fused-module slot `slot` (theta: A [r][k], B [n][r]) -> the four device views the kernels read:
 //   loraA [R][k] T (forward down-projection), loraAT [k][R] f32 (dgrad epilogue),
 //   loraB [ntot][r] f32 = s*B (forward epilogue), loraBT [R][ntot] T = s*B^T (backward down-projection)
+// half > 0 (ff.net.0.proj, n = 2 * half): theta keeps B in raw row order (value half, then gate half); the views are written in
+// the packed weight's row order, (value, gate) interleaved in blocks of 16
 template <typename T>
 __global__ void lora_refresh_kernel(const float* __restrict__ A, const float* __restrict__ B, T* loraA, float* loraAT, float* loraB,
-                                    T* loraBT, int r, int R, int k, int n, int ntot, int slot, int row0, float s) {
+                                    T* loraBT, int r, int R, int k, int n, int ntot, int slot, int row0, float s, int half) {
     const long long na = (long long)r * k, nb = (long long)n * r;
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < na + nb; i += (long long)gridDim.x * 256) {
         if (i < na) {
@@ -36,8 +38,9 @@ __global__ void lora_refresh_kernel(const float* __restrict__ A, const float* __
             const long long j = i - na;
             const int c = (int)(j / r), q = (int)(j - (long long)c * r);
             const float v = s * B[j];
-            loraB[(size_t)(row0 + c) * r + q] = v;
-            loraBT[(size_t)(slot * r + q) * ntot + row0 + c] = from_f32<T>(v);
+            const int row = row0 + (half ? geglu_packed_row(c, half) : c);
+            loraB[(size_t)row * r + q] = v;
+            loraBT[(size_t)(slot * r + q) * ntot + row] = from_f32<T>(v);
         }
     }
 }
@@ -59,7 +62,7 @@ static void for_each_res(Model& m, F f) {
 std::vector<LinW*> Model::lora_linears() {
     std::vector<LinW*> v;
     for_each_xf(*this, [&](XfW& x) {
-        for (LinW* l : {&x.proj_in, &x.qkv, &x.out1, &x.q2, &x.kv2, &x.out2, &x.ff2, &x.proj_out})
+        for (LinW* l : {&x.proj_in, &x.qkv, &x.out1, &x.q2, &x.kv2, &x.out2, &x.ff1, &x.ff2, &x.proj_out})
             if (l->R) v.push_back(l);
     });
     return v;
@@ -101,7 +104,9 @@ static int train_prepare_t(Model& m, hipStream_t st) {
     conv_dgrad(m.conv_out);
     for_each_xf(m, [&](XfW& x) {
         for (LinW* l : {&x.proj_in, &x.qkv, &x.out1, &x.q2, &x.out2, &x.ff1, &x.ff2, &x.proj_out}) lin_t(*l);
-        if (x.ff1.R) { err = 6; set_error("LoRA on the GEGLU projection is not supported by the fine-tuning step"); }
+        // the fp8 forward of the step has no adapted GEGLU projection: refuse before any step runs in another precision
+        if (x.ff1.R && m.cfg.fp8_train) { err = 6; set_error("fp8_train does not cover LoRA on ff.net.0.proj: train this handle without fp8_train"); }
+        if (x.ff1.R && x.ff1.geglu_half % 16 != 0) { err = 6; set_error("LoRA on ff.net.0.proj: the (value, gate) interleave is 16 rows wide"); }
     });
     if (err) return err;
     // flat trainable vector: [A_0 | B_0 | A_1 | B_1 ...] in lora_linears() x fused-module order
@@ -162,10 +167,10 @@ int Model::lora_refresh(hipStream_t st) {
             const unsigned blocks = (unsigned)((total + 255) / 256);
             if (cfg.compute_dtype == MRISR_F32)
                 hipLaunchKernelGGL(lora_refresh_kernel<float>, dim3(blocks), dim3(256), 0, st, A, B, static_cast<float*>(l->loraA), l->loraAT,
-                                   l->loraB_rw, static_cast<float*>(l->loraBT), l->r, l->R, l->k, l->secN, l->n, (int)j, row0, lora_scale);
+                                   l->loraB_rw, static_cast<float*>(l->loraBT), l->r, l->R, l->k, l->secN, l->n, (int)j, row0, lora_scale, l->geglu_half);
             else
                 hipLaunchKernelGGL(lora_refresh_kernel<bf16>, dim3(blocks), dim3(256), 0, st, A, B, static_cast<bf16*>(l->loraA), l->loraAT,
-                                   l->loraB_rw, static_cast<bf16*>(l->loraBT), l->r, l->R, l->k, l->secN, l->n, (int)j, row0, lora_scale);
+                                   l->loraB_rw, static_cast<bf16*>(l->loraBT), l->r, l->R, l->k, l->secN, l->n, (int)j, row0, lora_scale, l->geglu_half);
         }
         // the fp8 copy of the adapters' A rows (inference through the fp8 projections after training steps)
         if (l->loraA8 && cfg.compute_dtype != MRISR_F32) TRY(launch_quant_rows_fp8(l->loraA, l->R, l->k, l->loraA8, l->loraA_scale, st));
@@ -213,7 +218,7 @@ struct Trainer : Runner<T> {
         return 0;
     }
     static bool has_lora(const XfW& x) {
-        return x.proj_in.R || x.qkv.R || x.out1.R || x.q2.R || x.kv2.R || x.out2.R || x.ff2.R || x.proj_out.R;
+        return x.proj_in.R || x.qkv.R || x.out1.R || x.q2.R || x.kv2.R || x.out2.R || x.ff1.R || x.ff2.R || x.proj_out.R;
     }
 
     // ---------------------------------------------------------------------------------------------
@@ -363,7 +368,8 @@ struct Trainer : Runner<T> {
                     oA[j] = m.grad + lw.offA[j];
                     oB[j] = m.grad + lw.offB[j];
                 }
-                TRY(launch_lora_wgrad<T>(dY, ldy, z, lw.R, M, lw.n, 0, lw.r, nmod, lw.secN, oB, m.lora_scale, scratch, st));
+                // (ff.net.0.proj: dY columns in the GEGLU interleave, gradient rows in raw order - un-interleaved by the reduce's scatter)
+                TRY(launch_lora_wgrad<T>(dY, ldy, z, lw.R, M, lw.n, 0, lw.r, nmod, lw.secN, oB, m.lora_scale, scratch, st, lw.geglu_half));
                 TRY(launch_lora_wgrad<T>(x, ldx, dz, lw.R, M, lw.k, 1, lw.r, nmod, lw.secN, oA, 1.0f, scratch, st));
             }
         }
@@ -636,7 +642,7 @@ struct Trainer : Runner<T> {
         void *q1 = alloc(hsz), *k1 = alloc(hsz), *vt1 = alloc(hsz), *q2 = alloc(hsz);
         if (!t3 || !q2) return 7;
         TRY(zero(q1, hsz)); TRY(zero(k1, hsz)); TRY(zero(vt1, hsz)); TRY(zero(q2, hsz));
-        float *z_pi = nullptr, *z_qkv = nullptr, *z_o1 = nullptr, *z_q2 = nullptr, *z_o2 = nullptr, *z_f2 = nullptr, *z_po = nullptr;
+        float *z_pi = nullptr, *z_qkv = nullptr, *z_o1 = nullptr, *z_q2 = nullptr, *z_o2 = nullptr, *z_f1 = nullptr, *z_f2 = nullptr, *z_po = nullptr;
         TRY(R::linear(xn.p, M, C, xw.proj_in, ACT_NONE, nullptr, 0, nullptr, t0, C, &z_pi));
         TRY(R::layernorm(t0, xw.ln1, M, C, n1));
         {
@@ -659,7 +665,7 @@ struct Trainer : Runner<T> {
         TRY(attention_t(hb, &a2, ao2));
         TRY(R::linear(ao2, M, C, xw.out2, ACT_NONE, t1, C, nullptr, t2, C, &z_o2));
         TRY(R::layernorm(t2, xw.ln3, M, C, n3));
-        TRY(R::linear(n3, M, C, xw.ff1, ACT_NONE, nullptr, 0, nullptr, ffpre, 8 * C));
+        TRY(R::linear(n3, M, C, xw.ff1, ACT_NONE, nullptr, 0, nullptr, ffpre, 8 * C, &z_f1));
         if (!dry) TRY(launch_geglu_fwd<T>(ffpre, ff, M, 4 * C, st));
         TRY(R::linear(ff, M, 4 * C, xw.ff2, ACT_NONE, t2, C, nullptr, t3, C, &z_f2));
         TRY(R::linear(t3, M, C, xw.proj_out, ACT_NONE, x.p, C, nullptr, o.p, C, &z_po));
@@ -688,7 +694,7 @@ struct Trainer : Runner<T> {
             // t3 = t2 + ff2(geglu(ff1(LN3(t2))))
             TRY(linear_bwd(w.ff2, ff, 4 * C, z_f2, dt, C, M, dff, false, true));
             if (!dry) TRY(launch_geglu_bwd<T>(ffpre, dff, dpre, M, 4 * C, st));
-            TRY(linear_bwd(w.ff1, n3, C, nullptr, dpre, 8 * C, M, dn, false, true));
+            TRY(linear_bwd(w.ff1, n3, C, z_f1, dpre, 8 * C, M, dn, false, true));
             TRY(ln_affine(t2, dn, w.ln3, M, C));
             if (!dry) TRY(launch_layernorm_bwd<T>(t2, dn, dt, w.ln3.g, M, C, 1e-5f, 1, st));
             // t2 = t1 + out2(attn(q2(LN2(t1)), K_ctx, V_ctx))

@@ -214,6 +214,24 @@ def lora_wgrad(P, Q, M, Cc, mode, r, nmod, secN, outs, scale=1.0, ldp=None, ldq=
                                         mode, r, nmod, secN, _p(outs[0]), _p(outs[1]), _p(outs[2]), scale, L.stream_ptr()))
 
 
+def geglu_packed_rows(half: int) -> torch.Tensor:
+    """Packed row of every raw row of ``ff.net.0.proj`` ([2*half] rows: value half, then gate half): raw row ``g * half + j`` is stored at
+    ``(j >> 4) * 32 + (j & 15) + 16 g`` - (value, gate) interleaved in blocks of 16.  ``packed[perm] = raw`` packs, ``packed[perm]`` unpacks."""
+    if half <= 0 or half % 16:
+        raise ValueError("half must be a positive multiple of 16")
+    j = torch.arange(half, dtype=torch.int64)
+    p = (j >> 4) * 32 + (j & 15)
+    return torch.cat([p, p + 16])
+
+
+def lora_wgrad_geglu(dpre, z, out, scale=1.0, M=None, ldp=None, ldq=None, r=None):
+    """dB of an adapter on ``ff.net.0.proj``: dpre [M, 2*half] (T) in the 16-wide (value, gate) interleave, z [M, r] f32; ``out`` f32
+    [2*half, r] in lora_B's raw row order (value rows, then gate rows) is added into."""
+    L.check(L.lib().mrisr_op_lora_wgrad_geglu(_dt(dpre), _p(dpre), dpre.shape[1] if ldp is None else ldp, _p(z), z.shape[1] if ldq is None else ldq,
+                                              dpre.shape[0] if M is None else M, out.shape[0] // 2, out.shape[1] if r is None else r, _p(out),
+                                              scale, L.stream_ptr()))
+
+
 def transpose(src, dst, R, Cc, ld_src, ld_dst, bs_src=0, bs_dst=0, batch=1, r_valid=None):
     L.check(L.lib().mrisr_op_transpose(_dt(src), _p(src), _p(dst), R, Cc, ld_src, ld_dst, bs_src, bs_dst, batch, R if r_valid is None else r_valid,
                                        L.stream_ptr()))

@@ -148,6 +148,19 @@ def lora_param_shapes(cfg: UNetConfig, rank: int) -> Iterator[Tuple[str, Shape, 
                 yield mod + ".lora_B.default.weight", (shape[0], rank), -2
 
 
+LORA_FF_TARGETS = ("ff.net.0.proj", "ff.net.2")
+
+
+def lora_ff_param_shapes(cfg: UNetConfig, rank: int) -> Iterator[Tuple[str, Shape, int]]:
+    """peft keys for the feed-forward half of target_modules = to_q,to_k,to_v,to_out.0,ff.net.0.proj,ff.net.2 (``lora_B`` of
+    ``ff.net.0.proj`` is [8C, r]: value rows, then gate rows)."""
+    for key, shape, _ in unet_param_shapes(cfg):
+        if key.endswith(".weight") and key[: -len(".weight")].endswith(LORA_FF_TARGETS):
+            mod = key[: -len(".weight")]
+            yield mod + ".lora_A.default.weight", (rank, shape[1]), shape[1]
+            yield mod + ".lora_B.default.weight", (shape[0], rank), -2
+
+
 def random_state_dict(shapes, seed: int, device="cuda", lora_B_std: float = 0.02) -> Dict[str, torch.Tensor]:
     g = torch.Generator(device=device).manual_seed(seed)
     out = {}

@@ -3,7 +3,7 @@
 SD-1.5 UNet + r=4 LoRA, [B,4,32,32] latents, forward + MSE + backward + all-reduce(flat LoRA grads) + clip + AdamW.
 Not the headline metric (bench.py is) - a secondary line for DESIGN.md.
 
-  python tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--dtype bf16] [--profile]
+  python tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--dtype bf16] [--profile] [--lora-ff]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py --gpus N
 """
 import argparse
@@ -53,6 +53,8 @@ def main():
                                                                      "FROZEN UNet; condition images 8x the latent size; all-reduce of the 1.45 GB bucket")
     ap.add_argument("--fp8", action="store_true", help="BASELINE configs[4] training leg: forward through the fp8 projections + fp8 attention "
                                                        "(fp8_train), backward in bf16")
+    ap.add_argument("--lora-ff", action="store_true", help="rank-4 adapters on ff.net.0.proj and ff.net.2 as well (the attention + feed-forward "
+                                                           "target set)")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -71,6 +73,8 @@ def main():
     cfg = mrisr.UNetConfig()
     sd = P.random_state_dict(P.unet_param_shapes(cfg), 20260501, dev)  # same weights on every rank
     sd.update(P.random_state_dict(P.lora_param_shapes(cfg, 4), 20260504, dev))
+    if args.lora_ff:
+        sd.update(P.random_state_dict(P.lora_ff_param_shapes(cfg, 4), 20260505, dev))
     f8 = dict(fp8=True, fp8_attention=True, fp8_train=True) if args.fp8 else {}
     if args.train_controlnet:
         sd = P.random_state_dict(P.unet_param_shapes(cfg), 20260501, dev)
@@ -138,7 +142,7 @@ def main():
            "workspace_GiB": round(unet.workspace_bytes / 2**30, 2),
            "config": {"workload": f"SD-1.5 UNet + LoRA r=4 fine-tune step, [{B},4,{h},{h}] per GPU, all-reduce of "
                                   f"{tr.num_trainable} f32 grads" + (f" + trainable Adapter_XL ({atr.num_trainable} f32 grads)" if atr else "") + (f"; TRAINABLE ControlNet ({ctr.num_trainable} f32 grads), UNet frozen" if ctr else ""),
-                      "adapter_features": bool(intra), "adapter_trained": atr is not None}}
+                      "adapter_features": bool(intra), "adapter_trained": atr is not None, "lora_ff": bool(args.lora_ff)}}
     if args.profile and rank == 0:
         lib = L.lib()
         lib.mrisr_prof_reset()

@@ -416,6 +416,12 @@ int mrisr_prof_report(char* buf, int cap);
 int mrisr_op_conv3x3(const mrisr_tensor* x_nhwc, const mrisr_tensor* x2_nhwc, const float* w_oihw_dev,
                      const float* bias_dev, int cout, int stride, int upsample, int act, int splitk, int tile,
                      mrisr_tensor* y_nhwc, void* stream);
+/* a resnet's conv2 with its 1x1 conv_shortcut (bf16, stride 1, channel counts multiples of 64): y = conv3x3([x | x2]) + bias +
+ * W_sc [xs | xs2] + bias_sc, the shortcut sources read at the output pixel.  fused = 1: one launch, the shortcut as the last K steps of
+ * the conv on a concatenated filter bank; fused = 0: the shortcut GEMM, then the conv with its output as the residual */
+int mrisr_op_conv3x3_sc(const mrisr_tensor* x_nhwc, const mrisr_tensor* x2_nhwc, const float* w_oihw_dev, const float* bias_dev,
+                        const mrisr_tensor* xs_nhwc, const mrisr_tensor* xs2_nhwc, const float* w_sc_dev, const float* bias_sc_dev,
+                        int cout, int splitk, int tile, int fused, mrisr_tensor* y_nhwc, void* stream);
 int mrisr_op_linear(const mrisr_tensor* x_rows, const float* w_dev, const float* bias_dev, int n, int act,
                     int splitk, int tile, mrisr_tensor* y_rows, void* stream);
 /* y = LayerNorm(x; gamma, beta, eps 1e-5) W^T + bias with the normalisation as a prologue of the row-panel GEMM kernel (bf16;

@@ -56,6 +56,10 @@ void mrisr_debug_mlp_proj(int on);
  * (one launch instead of splitk_reduce + GroupNorm), 0 the two launches, 1 on */
 void mrisr_debug_gn_slabs(int on);
 
+/* a resnet's 1x1 conv_shortcut as the last K steps of its conv2 (bf16 inference; one launch on a concatenated filter bank instead of
+ * shortcut GEMM + conv2 with a residual): -1 default (MRISR_SC_FUSED, on), 0 the two launches, 1 on */
+void mrisr_debug_sc_fused(int on);
+
 /* the fused row-local middle of the C = 320 transformer blocks (csrc/xtail.hip: attn1.to_out + residual, LayerNorm2, attn2.to_q,
  * cross-attention, attn2.to_out + residual in one launch): -1 default (MRISR_XTAIL, on), 0 the four separate launches, 1 on */
 void mrisr_debug_xattn_tail(int on);

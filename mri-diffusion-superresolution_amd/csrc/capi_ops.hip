@@ -88,6 +88,70 @@ static int op_conv3x3_t(const mrisr_tensor* x, const mrisr_tensor* x2, const flo
 
 extern "C" void mrisr_debug_force_tile(int t);
 
+// conv3x3(x) + bias + (W_sc [xs | xs2] + b_sc): a resnet's conv2 with its 1x1 conv_shortcut.  fused: ONE launch over K = [9 Cin | Cs] on the
+// concatenated bank (the shortcut as the 1x1 tail of the K loop, summed bias); otherwise the two launches it replaces - the shortcut GEMM
+// into y, then the conv with y as its residual in place.  `tile` picks the conv's kernel (the shortcut GEMM of the two-launch form is planned).
+static int op_conv3x3_sc_t(const mrisr_tensor* x, const mrisr_tensor* x2, const float* w, const float* bias, const mrisr_tensor* xs,
+                           const mrisr_tensor* xs2, const float* w_sc, const float* bias_sc, int cout, int splitk, int tile, int fused,
+                           mrisr_tensor* y, hipStream_t st) {
+    typedef bf16 T;
+    const int B = (int)x->shape[0], C0 = (int)x->shape[1], H = (int)x->shape[2], W = (int)x->shape[3];
+    const int C1 = x2 ? (int)x2->shape[1] : 0, Cin = C0 + C1;
+    const int S0 = (int)xs->shape[1], S1 = xs2 ? (int)xs2->shape[1] : 0, Cs = S0 + S1;
+    MRISR_REQUIRE(xs->shape[0] == B && xs->shape[2] == H && xs->shape[3] == W && (!xs2 || (xs2->shape[0] == B && xs2->shape[2] == H && xs2->shape[3] == W)),
+                  "shortcut sources: the conv input's batch and image size");
+    MRISR_REQUIRE(y->shape[1] == cout && y->shape[2] == H && y->shape[3] == W, "conv output shape");
+    MRISR_REQUIRE(Cin % 64 == 0 && S0 % 64 == 0 && S1 % 64 == 0 && cout % 4 == 0, "channel counts: multiples of 64");
+    const size_t K9 = (size_t)9 * Cin, Kt = K9 + Cs;
+    DevBuf w9, wsc, bank, bsum, part;
+    TRY(w9.reserve((size_t)cout * K9 * sizeof(T), false));
+    TRY(wsc.reserve((size_t)cout * Cs * sizeof(T), false));
+    TRY(launch_pack_conv3x3<T>(w, w9.p, cout, Cin, 3, st));
+    TRY(launch_pack_rows<T>(w_sc, cout, Cs, wsc.p, Cs, 0, 0, 0, 0, 1.0f, st));
+    GemmArgs g;
+    g.a0 = x->data; g.c0 = C0; g.lda0 = C0;
+    if (x2) { g.a1 = x2->data; g.c1 = C1; g.lda1 = C1; }
+    g.conv = 1; g.B = B; g.Hin = H; g.Win = W; g.Hout = H; g.Wout = W;
+    g.M = B * H * W; g.N = cout; g.out = y->data; g.ldo = cout;
+    if (fused) {
+        TRY(bank.reserve((size_t)cout * Kt * sizeof(T), false));
+        TRY(bsum.reserve((size_t)cout * sizeof(float), false));
+        MRISR_CHECK_HIP(hipMemcpy2DAsync(bank.p, Kt * sizeof(T), w9.p, K9 * sizeof(T), K9 * sizeof(T), cout, hipMemcpyDeviceToDevice, st));
+        MRISR_CHECK_HIP(hipMemcpy2DAsync(static_cast<T*>(bank.p) + K9, Kt * sizeof(T), wsc.p, (size_t)Cs * sizeof(T), (size_t)Cs * sizeof(T), cout,
+                                         hipMemcpyDeviceToDevice, st));
+        MRISR_CHECK_HIP(hipMemcpyAsync(bsum.p, bias, (size_t)cout * sizeof(float), hipMemcpyDeviceToDevice, st));
+        TRY(launch_add_inplace<float>(bsum.p, bias_sc, cout, st));
+        g.s0 = xs->data; g.cs0 = S0; g.lds0 = S0;
+        if (xs2) { g.s1 = xs2->data; g.cs1 = S1; g.lds1 = S1; }
+        g.w = bank.p; g.K = (int)Kt; g.bias = static_cast<const float*>(bsum.p);
+    } else {
+        GemmArgs s;
+        s.a0 = xs->data; s.c0 = S0; s.lda0 = S0;
+        if (xs2) { s.a1 = xs2->data; s.c1 = S1; s.lda1 = S1; }
+        s.w = wsc.p; s.M = g.M; s.N = cout; s.K = Cs; s.bias = bias_sc; s.out = y->data; s.ldo = cout;
+        TRY(gemm_choose(s, true));
+        DevBuf spart;
+        if (s.splitk > 1) { TRY(spart.reserve((size_t)s.splitk * s.M * s.N * sizeof(float), false)); s.partial = static_cast<float*>(spart.p); }
+        TRY(launch_gemm<T>(s, st));
+        MRISR_CHECK_HIP(hipStreamSynchronize(st));
+        g.w = w9.p; g.K = (int)K9; g.bias = bias; g.resid = y->data; g.ldr = cout;
+    }
+    mrisr_debug_force_tile(tile);
+    g.splitk = splitk;
+    int rc = 0;
+    if (splitk <= 0) { g.splitk = 1; rc = gemm_choose(g, true); }
+    else if (tile <= 0) { const int sk = splitk; rc = gemm_choose(g, true); g.splitk = sk; }
+    if (!rc && g.splitk > 1) {
+        rc = part.reserve((size_t)g.splitk * g.M * g.N * sizeof(float), false);
+        g.partial = static_cast<float*>(part.p);
+    }
+    if (!rc) rc = launch_gemm<T>(g, st);
+    mrisr_debug_force_tile(0);
+    if (rc) return rc;
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 template <typename T>
 static int op_attention_t(const mrisr_tensor* q, const mrisr_tensor* k, const mrisr_tensor* v, int H, int flash,
                           mrisr_tensor* out, hipStream_t st) {
@@ -166,6 +230,22 @@ int mrisr_op_conv3x3(const mrisr_tensor* x, const mrisr_tensor* x2, const float*
                  : op_conv3x3_t<bf16>(x, x2, w_oihw_dev, bias_dev, cout, stride, upsample, act, splitk, y, (hipStream_t)stream);
     mrisr_debug_force_tile(0);
     return rc;
+    API_END
+}
+
+int mrisr_op_conv3x3_sc(const mrisr_tensor* x, const mrisr_tensor* x2, const float* w_oihw_dev, const float* bias_dev, const mrisr_tensor* xs,
+                        const mrisr_tensor* xs2, const float* w_sc_dev, const float* bias_sc_dev, int cout, int splitk, int tile, int fused,
+                        mrisr_tensor* y, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(x && xs && y && w_oihw_dev && bias_dev && w_sc_dev && bias_sc_dev, "null argument");
+    MRISR_REQUIRE(x->dtype == MRISR_BF16 && xs->dtype == MRISR_BF16 && y->dtype == MRISR_BF16 && (!x2 || x2->dtype == MRISR_BF16) &&
+                      (!xs2 || xs2->dtype == MRISR_BF16),
+                  "conv3x3 + 1x1 shortcut: bf16 tensors");
+    MRISR_REQUIRE(x->layout == MRISR_NHWC && xs->layout == MRISR_NHWC && y->layout == MRISR_NHWC && (!x2 || x2->layout == MRISR_NHWC) &&
+                      (!xs2 || xs2->layout == MRISR_NHWC),
+                  "NHWC in/out");
+    TRY(gemm_prepare());
+    return op_conv3x3_sc_t(x, x2, w_oihw_dev, bias_dev, xs, xs2, w_sc_dev, bias_sc_dev, cout, splitk, tile, fused, y, (hipStream_t)stream);
     API_END
 }
 

@@ -107,7 +107,13 @@ struct GemmArgs {
                                // (pad = 0 with Hout = Hin / 2: diffusers' Downsample2D(padding=0), asymmetric (0,1,0,1))
     int zstuff = 0;            // with ups = 1: the x2 image is ZERO-STUFFED (odd rows/cols are 0) instead of nearest -
                                // the input of a stride-2 conv's dgrad (transposed convolution)
-    // ---- W operand: [N][K] elements of T, K = taps*(c0+c1) ----
+    // ---- optional 1x1 tail of a 3x3 conv (bf16 tiled 2-stage and 4-wave halo kernels only; stride 1, no up-sampling): up to two more row
+    // sources read at the OUTPUT pixel itself - a resnet's conv_shortcut on its raw input, run as the last K steps of conv2 ----
+    const void* s0 = nullptr;  // [B*Hin*Win][lds0]
+    const void* s1 = nullptr;  // second source (channels cs0..cs0+cs1), may be null
+    int cs0 = 0, cs1 = 0;      // channels of each source (multiples of 64); cs0 == 0: no tail
+    int lds0 = 0, lds1 = 0;    // row pitch in elements
+    // ---- W operand: [N][K] elements of T, K = taps*(c0+c1) + (cs0+cs1), the tail's columns last ----
     const void* w = nullptr;
     int M = 0, N = 0, K = 0;
     // ---- batching (blockIdx.z): element offsets ----
@@ -213,6 +219,8 @@ size_t xattn_tail_kv_bytes(int B);
 int launch_pack_xattn_kv(const void* kc, const void* vtc, void* dst, int B, int ctx_pad, int dpad, int nk, hipStream_t st);
 int launch_xattn_tail(const XTailArgs& x, hipStream_t st);
 int gemm_rp_tile(const GemmArgs& g);  // row-panel kernel id for this (plain, short-K, bf16) GEMM, 0 if it is not eligible
+bool gemm_sc_tail_ok(const GemmArgs& g);  // the launch (with its 1x1 tail fields set) has the form the two tail-capable kernel families take
+bool sc_fused_enabled();                  // resnet shortcut as conv2's 1x1 tail (MRISR_SC_FUSED, default 1; mrisr_debug_sc_fused)
 int gemm_choose(GemmArgs& g, bool is_bf16);  // sets g.tile / g.splitk (autotuned per signature for bf16)  // set launch attributes of every GEMM instantiation (call before graph capture)
 
 // ---------------------------------------------------------------------------------------------

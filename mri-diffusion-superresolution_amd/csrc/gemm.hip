@@ -775,9 +775,10 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
     const int Hc = g.Hin << g.ups, Wc = g.Win << g.ups;
     // conv walk state (uniform): current tap and channel position; seg_key identifies (tap, source)
     int tap = 0, cc = 0, seg_key = -1;
+    const int ntaps = g.kw * g.kw;  // tap == ntaps: the 1x1 tail segment (only a launch with g.cs0 has K steps there)
     if (g.conv) {
         const int k0 = kt_beg * BK;
-        tap = k0 / Ct;
+        tap = min(k0 / Ct, ntaps);
         cc = k0 - tap * Ct;
     }
 
@@ -807,12 +808,15 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
                 for (int it = 0; it < A_IT; ++it) bl16(ra1, sb + (it * 256 + wave * 64) * 16, avo1[it], kb);
             }
         } else {
-            const bool second = cc >= g.c0;
+            const bool tail = tap >= ntaps;  // (uniform) past the last tap: the 1x1 tail, its pixel is the window's centre (oy, ox)
+            const int cfirst = tail ? +g.cs0 : +g.c0;
+            const bool second = cc >= cfirst;
             const int key = tap * 2 + (second ? 1 : 0);
             if (key != seg_key) {  // new (tap, source) segment: refresh the per-lane offsets (uniform branch)
                 seg_key = key;
-                const int ky = g.kw == 3 ? tap / 3 : tap / g.kw, kx = tap - ky * g.kw;
-                const int ld = second ? g.lda1 : g.lda0;
+                int ky = g.kw == 3 ? tap / 3 : tap / g.kw, kx = tap - ky * g.kw;
+                int ld = second ? g.lda1 : g.lda0;
+                if (tail) { ky = kx = g.pad; ld = second ? +g.lds1 : +g.lds0; }
 #pragma unroll
                 for (int it = 0; it < A_IT; ++it) {
                     const int row = it * 32 + lrow;
@@ -823,8 +827,15 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
                     avo[it] = ok ? (pix * (unsigned)ld + (unsigned)c * 8u) * 2u : BL_OOB;
                 }
             }
-            const unsigned chb = (unsigned)(second ? cc - g.c0 : cc) * 2;
-            if (!second) {
+            const unsigned chb = (unsigned)(second ? cc - cfirst : cc) * 2;
+            if (tail) {
+                // (the descriptor is built per K step - four scalar moves: one kept across the loop for each tail source made the compiler
+                // leave the whole walk state in scratch memory)
+                const long long ld_cur = second ? +g.lds1 : +g.lds0;
+                const __amdgpu_buffer_rsrc_t rs = make_rsrc(second ? g.s1 : g.s0, (unsigned)min(a_rows * ld_cur * 2, 0x7FFFFFFFll));
+#pragma unroll
+                for (int it = 0; it < A_IT; ++it) bl16(rs, sb + (it * 256 + wave * 64) * 16, avo[it], chb);
+            } else if (!second) {
 #pragma unroll
                 for (int it = 0; it < A_IT; ++it) bl16(ra0, sb + (it * 256 + wave * 64) * 16, avo[it], chb);
             } else {
@@ -832,7 +843,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
                 for (int it = 0; it < A_IT; ++it) bl16(ra1, sb + (it * 256 + wave * 64) * 16, avo[it], chb);
             }
             cc += BK;
-            if (cc >= Ct) { cc = 0; ++tap; }
+            if (cc >= Ct && !tail) { cc = 0; ++tap; }
         }
     };
     auto stage = [&](int kt, int buf) { stage_w(kt, buf); stage_a(kt, buf); };
@@ -1148,6 +1159,12 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
     const int nch = Ct / BK;                       // 64-channel chunks over both sources
     const int per = (nch + g.splitk - 1) / g.splitk;
     const int ch_beg = split * per, ch_end = min(nch, ch_beg + per);
+    // 1x1 tail (g.cs0 > 0): its 64-channel chunks are dealt to the splits the same way; a split runs them after its 3x3 chunks
+    const int nsc = (g.cs0 + g.cs1) / BK;
+    const int per_sc = (nsc + g.splitk - 1) / g.splitk;
+    const int sc_beg = min(nsc, split * per_sc), sc_end = min(nsc, sc_beg + per_sc);
+    const __amdgpu_buffer_rsrc_t rs0 = make_rsrc(g.s0 ? g.s0 : (const void*)a0p, g.s0 ? (unsigned)min(a_rows * g.lds0 * 2, 0x7FFFFFFFll) : 0u);
+    const __amdgpu_buffer_rsrc_t rs1 = make_rsrc(g.s1 ? g.s1 : (const void*)a0p, g.s1 ? (unsigned)min(a_rows * g.lds1 * 2, 0x7FFFFFFFll) : 0u);
 
     auto stage_patch = [&](int ch) {
         const int cc = ch * BK;
@@ -1166,6 +1183,42 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
         const unsigned kb = (unsigned)(tap * Ct + ch * BK) * 2;
 #pragma unroll
         for (int it = 0; it < W_IT; ++it) bl16(rw, sb + (it * 256 + wave * 64) * 16, wvo[it], kb);
+    };
+    // tail chunk sc: its weight columns follow the nine taps; its rows come into the patch with the patch's own geometry (the pixel
+    // of transfer t is the one stage_patch gives it), centre rows only - the one phase that reads them uses the centre tap's offset
+    auto stage_w_sc = [&](int sc, int buf) {
+        char* sb = wbase + buf * WSTAGE;
+        const unsigned kb = (unsigned)(9 * Ct + sc * BK) * 2;
+#pragma unroll
+        for (int it = 0; it < W_IT; ++it) bl16(rw, sb + (it * 256 + wave * 64) * 16, wvo[it], kb);
+    };
+    unsigned spix[PIT_MAX];  // source pixel of each transfer (centre rows of the patch), ~0u outside: set up after the 3x3 phases (sc_setup)
+    auto sc_setup = [&]() {
+#pragma unroll
+        for (int it = 0; it < PIT_MAX; ++it) {
+            int t = it * 256 + tid;
+            asm volatile("" : "+v"(t));  // (keeps this arithmetic out of the 3x3 phases: merged with the pvo0 / pvo1 set-up it would hold registers across them)
+            const int pp = t >> 3;
+            const int hy = pp / PW, hx = pp - hy * PW;
+            const bool ok = hy >= 1 && hy <= TH && hx >= 1 && hx <= Wd;  // (rows y0 .. y0 + TH - 1 lie inside the image: whole tiles per image)
+            spix[it] = ok ? (unsigned)((img * Hd + y0 - 1 + hy) * Wd + hx - 1) : ~0u;
+        }
+    };
+    auto stage_patch_sc = [&](int sc) {
+        const int cc = sc * BK;
+        const bool second = cc >= g.cs0;
+        const unsigned chb = (unsigned)(second ? cc - g.cs0 : cc) * 2;
+        const unsigned ld2 = (unsigned)(second ? g.lds1 : g.lds0) * 2u;
+#pragma unroll
+        for (int it = 0; it < PIT_MAX; ++it) {
+            if (it < pit) {
+                const int t = it * 256 + tid;
+                const unsigned c16 = (unsigned)((t & 7) ^ ((t >> 3) & 7)) * 16u;
+                const unsigned off = spix[it] != ~0u ? spix[it] * ld2 + c16 : BL_OOB;
+                if (!second) bl16(rs0, patch + (it * 256 + wave * 64) * 16, off, chb);
+                else bl16(rs1, patch + (it * 256 + wave * 64) * 16, off, chb);
+            }
+        }
     };
 
     f32x4 acc[NF][MF];
@@ -1206,10 +1259,11 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
         }
     };
 
-    if (ch_beg < ch_end) {
+    if (ch_beg < ch_end || sc_beg < sc_end) {
         int cur = 0;
         if (g.pretouch) pretouch_weights(rw, (long long)g.N * g.K * 2, wbase + WSTAGE, wave, lane, g.pretouch);
-        stage_w(ch_beg, 0, 0);
+        if (ch_beg < ch_end) stage_w(ch_beg, 0, 0);
+        else stage_w_sc(sc_beg, 0);
         for (int ch = ch_beg; ch < ch_end; ++ch) {
             stage_patch(ch);  // the previous chunk's last tap ended with a barrier: the patch buffer is free
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1231,11 +1285,24 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
             for (int tap = 0; tap < 9; ++tap) {
                 if (tap + 1 < 9) stage_w(ch, tap + 1, cur ^ 1);
                 else if (ch + 1 < ch_end) stage_w(ch + 1, 0, cur ^ 1);
+                else if (sc_beg < sc_end) stage_w_sc(sc_beg, cur ^ 1);
                 compute(cur, tap);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 cur ^= 1;
             }
+        }
+        // 1x1 tail: one phase per chunk, the stage / wait / barrier sequence of the phases above (chunk sc's weight tile is already on its way)
+        if (sc_beg < sc_end) sc_setup();
+        for (int sc = sc_beg; sc < sc_end; ++sc) {
+            stage_patch_sc(sc);  // the previous phase ended with a barrier: the patch buffer is free
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (sc + 1 < sc_end) stage_w_sc(sc + 1, cur ^ 1);
+            compute(cur, 4);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            cur ^= 1;
         }
     }
 
@@ -2795,7 +2862,7 @@ static int launch_bl(const GemmArgs& g, hipStream_t st) {
     std::string pname = base_name;
     if (prof_enabled() && prof_shapes()) {
         char buf[160];
-        snprintf(buf, sizeof(buf), "%s %s M=%d N=%d K=%d s=%d b=%d", base_name.c_str(), g.conv ? (g.ups ? "convup" : (g.stride == 2 ? "convs2" : "conv")) : "lin",
+        snprintf(buf, sizeof(buf), "%s %s M=%d N=%d K=%d s=%d b=%d", base_name.c_str(), g.conv ? (g.cs0 ? "convsc" : (g.ups ? "convup" : (g.stride == 2 ? "convs2" : "conv"))) : "lin",
                  g.M, g.N, g.K, g.splitk, g.batch);
         pname = buf;
     }
@@ -2803,7 +2870,7 @@ static int launch_bl(const GemmArgs& g, hipStream_t st) {
     if (prof_enabled()) {
         if (fl == 0.0) fl = 2.0 * g.M * (double)g.N * g.K * g.batch;
         if (by == 0.0) {
-            const double a_el = g.conv ? (double)g.B * g.Hin * g.Win * (g.c0 + g.c1) : (double)g.M * g.K;
+            const double a_el = g.conv ? (double)g.B * g.Hin * g.Win * (g.c0 + g.c1 + g.cs0 + g.cs1) : (double)g.M * g.K;
             by = 2.0 * g.batch * (a_el + (double)g.N * g.K + (double)g.M * g.N);
         }
     }
@@ -2887,13 +2954,13 @@ static int launch_halo(const GemmArgs& g, hipStream_t st) {
     std::string pname = base_name;
     if (prof_enabled() && prof_shapes()) {
         char buf[160];
-        snprintf(buf, sizeof(buf), "%s conv M=%d N=%d K=%d s=%d b=%d", base_name.c_str(), g.M, g.N, g.K, g.splitk, g.batch);
+        snprintf(buf, sizeof(buf), "%s %s M=%d N=%d K=%d s=%d b=%d", base_name.c_str(), g.cs0 ? "convsc" : "conv", g.M, g.N, g.K, g.splitk, g.batch);
         pname = buf;
     }
     double fl = g.alg_flops, by = g.alg_bytes;
     if (prof_enabled()) {
         if (fl == 0.0) fl = 2.0 * g.M * (double)g.N * g.K;
-        if (by == 0.0) by = 2.0 * ((double)g.B * g.Hin * g.Win * (g.c0 + g.c1) + (double)g.N * g.K + (double)g.M * g.N);
+        if (by == 0.0) by = 2.0 * ((double)g.B * g.Hin * g.Win * (g.c0 + g.c1 + g.cs0 + g.cs1) + (double)g.N * g.K + (double)g.M * g.N);
     }
     ProfScope ps(prof_intern(pname), fl, by, st);
     hipLaunchKernelGGL((gemm_halo_kernel<BM, BN, WGM, WGN>), grid, dim3(256), smem, st, g);
@@ -3145,6 +3212,35 @@ static bool bl_ok(const GemmArgs& g) {
     return a_rows * g.lda0 * 2 < lim && a_rows * (long long)g.lda1 * 2 < lim && (long long)g.N * g.K * 2 < lim;
 }
 
+// ---- 1x1 tail of a 3x3 conv (GemmArgs::s0 ...) ----
+// kernel families that carry it: gemm_bl_kernel in its 2-stage form and the 4-wave gemm_halo_kernel.  Not the counted rings (32-39), halo8
+// (46-48), the weight-stationary / row-panel kernels or the f32 gemm_kernel.
+static bool sc_tail_tile(int tile) {
+    switch (tile) {
+#define X(id, bm, bn, wm, wn, ns) case id: return ns == 2;
+        BL_CFGS(X)
+#undef X
+#define X(id, bm, bn, wm, wn) case id: return true;
+        HALO_CFGS(X)
+#undef X
+    }
+    return false;
+}
+bool gemm_sc_tail_ok(const GemmArgs& g) {
+    if (!g.conv || g.kw != 3 || g.subpix || g.stride != 1 || g.ups || g.zstuff || g.pad != 1 || g.batch != 1) return false;
+    if (g.Hout != g.Hin || g.Wout != g.Win || g.act == ACT_GEGLU || g.lora_a) return false;
+    if (!g.s0 || g.cs0 <= 0 || g.cs0 % 64 || g.cs1 % 64 || (g.cs1 > 0) != (g.s1 != nullptr) || g.c0 % 64 || g.c1 % 64) return false;
+    if (g.lds0 < g.cs0 || (g.s1 && g.lds1 < g.cs1) || (g.lds0 & 7) || (g.lds1 & 7)) return false;
+    const long long a_rows = (long long)g.B * g.Hin * g.Win, lim = 0x7FFFFFFFll;
+    return bl_ok(g) && a_rows * g.lds0 * 2 < lim && a_rows * (long long)g.lds1 * 2 < lim;
+}
+static int g_sc_fused = -1;  // test hook: -1 = MRISR_SC_FUSED (default 1), 0 off, 1 on
+extern "C" void mrisr_debug_sc_fused(int on) { g_sc_fused = on; ++g_plan_salt; }
+bool sc_fused_enabled() {
+    static const int env = [] { const char* e = getenv("MRISR_SC_FUSED"); return e ? atoi(e) : 1; }();
+    return g_sc_fused < 0 ? env != 0 : g_sc_fused != 0;
+}
+
 // ---- tile / split-K planner ------------------------------------------------------------------
 struct TileCfg { int id, bm, bn; double eff; bool bl; };
 // eff: relative main-loop efficiency measured with tools/gemm_sweep.py (profiles/r01_gemm_sweep.log)
@@ -3234,6 +3330,7 @@ static int tune(const GemmArgs& g0, int* tile_out, int* split_out) {
     snprintf(key, sizeof(key), "%d,%d,%d,c%d,s%d,u%d,%d,%d,a%d,o%d,b%d,r%d,v%d,h%d,w%d", g0.M, g0.N, g0.K, g0.conv, g0.stride + 8 * (1 - g0.pad), g0.ups, g0.c0,
              g0.c1, g0.act, g0.out_mode, g0.batch, g0.resid ? 1 : 0, g0.rowvec ? 1 : 0, g0.Hin, g0.Win);
     if (g0.kw != 3 || g0.subpix) snprintf(key + strlen(key), sizeof(key) - strlen(key), ",q%d", g0.kw * 2 + g0.subpix);  // (older tables have no such keys)
+    if (g0.cs0) snprintf(key + strlen(key), sizeof(key) - strlen(key), ",t%d,%d", g0.cs0, g0.cs1);  // 1x1 tail (launches without one keep their keys)
     static bool cache_loaded = false;
     const char* cache_path = getenv("MRISR_TUNE_CACHE");  // optional on-disk table: "key<TAB>tile<TAB>split" per line
     if (!cache_loaded) {
@@ -3253,13 +3350,14 @@ static int tune(const GemmArgs& g0, int* tile_out, int* split_out) {
     GemmArgs g = g0;
     const long long a_rows = g.conv ? (long long)g.B * g.Hin * g.Win : (long long)g.M;
     const size_t zb = (size_t)(g.batch > 1 ? g.batch : 1);
-    if (g_ts.reserve(0, (size_t)a_rows * g.lda0 * 2 * zb + 4096, true)) return 1;
-    if (g.c1 && g_ts.reserve(1, (size_t)a_rows * g.lda1 * 2 + 4096, true)) return 1;
+    if (g_ts.reserve(0, (size_t)a_rows * std::max(g.lda0, g.lds0) * 2 * zb + 4096, true)) return 1;
+    if ((g.c1 || g.cs1) && g_ts.reserve(1, (size_t)a_rows * std::max(g.lda1, g.lds1) * 2 + 4096, true)) return 1;
     if (g_ts.reserve(2, (size_t)g.N * g.K * 2 * zb + 4096, true)) return 1;
     if (g_ts.reserve(3, (size_t)g.M * g.N * 4 * zb + 4096, false)) return 1;
     if (g_ts.reserve(5, (size_t)(g.N + 64) * 4 + ((size_t)(g.rowvec ? g.M / (g.rowvec_div > 0 ? g.rowvec_div : 1) + 1 : 1)) * (g.N + 64) * 4, false)) return 1;
     g.a0 = g_ts.p[0]; g.a_bs = g.batch > 1 ? (long long)a_rows * g.lda0 : 0;
     g.a1 = g.c1 ? g_ts.p[1] : nullptr;
+    if (g.cs0) { g.s0 = g_ts.p[0]; g.s1 = g.cs1 ? g_ts.p[1] : nullptr; }  // (the tail's rows: the same random scratch)
     g.w = g_ts.p[2]; g.w_bs = g.batch > 1 ? (long long)g.N * g.K : 0;
     g.bias = g.bias ? (const float*)g_ts.p[5] : nullptr;
     if (g.rowvec) { g.rowvec = (const float*)g_ts.p[5] + g.N + 64; g.rowvec_ld = g.N + 64; }
@@ -3297,6 +3395,7 @@ static int tune(const GemmArgs& g0, int* tile_out, int* split_out) {
             if (!skip.empty() && ("," + skip + ",").find("," + std::to_string(tile) + ",") != std::string::npos) continue;
         }
         if (tile >= 32 && tile <= 39 && !ring_ok(g, tile)) continue;  // counted-ring variants: exact plain GEMMs only
+        if (g.cs0 && !sc_tail_tile(tile)) continue;  // a 1x1 tail: the 2-stage tiled and 4-wave halo kernels only
         if (is_halo8(tile)) { if (!halo8_ok(g)) continue; }
         else if (tile >= 40 && tile < 50 && !halo_ok(g, halo_bm(tile))) continue;  // LDS-halo conv kernels: stride-1 3x3, whole tiles per image
         if (tile >= 50 && tile < 60 && !ws_ok(g, tile)) continue;  // weight-stationary kernels: short-K plain GEMMs that tile exactly
@@ -3373,8 +3472,11 @@ int gemm_choose(GemmArgs& g, bool is_bf16) {
         MRISR_REQUIRE(g.tile != 0, "LayerNorm prologue / fp8 operands need the row-panel kernel");
         return 0;
     }
-    if (g_force_tile) { g.tile = g_force_tile; if (g.splitk < 1) g.splitk = 1; return 0; }
-    if (g_prefer_tile && is_bf16 && bl_ok(g) &&
+    const bool sc_tail = g.cs0 || g.s0;
+    if (sc_tail) MRISR_REQUIRE(is_bf16 && gemm_sc_tail_ok(g), "1x1 tail: bf16 stride-1 3x3 conv, channel counts multiples of 64");
+    // (a forced / preferred kernel that cannot carry a 1x1 tail is not taken for a launch that has one: the planner decides)
+    if (g_force_tile && !(sc_tail && !(sc_tail_tile(g_force_tile) && (g_force_tile < 40 || halo_ok(g, halo_bm(g_force_tile)))))) { g.tile = g_force_tile; if (g.splitk < 1) g.splitk = 1; return 0; }
+    if (g_prefer_tile && !(sc_tail && !sc_tail_tile(g_prefer_tile)) && is_bf16 && bl_ok(g) &&
         ((g_prefer_tile >= 60 && rp_ok(g, g_prefer_tile)) || (g_prefer_tile >= 50 && g_prefer_tile < 60 && ws_ok(g, g_prefer_tile)) || (g_prefer_tile >= 40 && g_prefer_tile < 50 && (is_halo8(g_prefer_tile) ? halo8_ok(g) : halo_ok(g, halo_bm(g_prefer_tile)))))) {
         g.tile = g_prefer_tile;
         g.splitk = 1;
@@ -3388,6 +3490,7 @@ int gemm_choose(GemmArgs& g, bool is_bf16) {
     }
     (void)cs;
     if ((t >= 60 && !rp_ok(g, t)) || (t >= 32 && t <= 39 && (!ring_ok(g, t) || s > 1)) || (is_halo8(t) && !halo8_ok(g))) plan(g, is_bf16, 0, &t, &s);  // (a table entry tuned without this launch's operand forms)
+    if (sc_tail && !(sc_tail_tile(t) && (t < 40 || halo_ok(g, halo_bm(t))))) plan(g, true, 0, &t, &s);  // (a table row naming a kernel without the tail: the cost model picks among 14-18)
     if (g_force_split > 1 && g.act != ACT_GEGLU && g.K / (is_bf16 ? 64 : 32) >= g_force_split && !g.lora_a) {
         s = g_force_split;
         if (t >= 50) t = is_bf16 ? 14 : 1;
@@ -3451,7 +3554,7 @@ int launch_gemm(const GemmArgs& g, hipStream_t st) {
     MRISR_REQUIRE(g.splitk == 1 || g.partial != nullptr, "split-K needs a partial buffer");
     MRISR_REQUIRE(g.splitk == 1 || g.act != ACT_GEGLU, "GEGLU epilogue cannot be split");
     MRISR_REQUIRE(zero_page() != nullptr, "zero page not initialised");
-    if (g.conv) { MRISR_REQUIRE(g.K == g.kw * g.kw * (g.c0 + g.c1) && (g.kw == 3 || g.kw == 2), "conv K"); }
+    if (g.conv) { MRISR_REQUIRE(g.K == g.kw * g.kw * (g.c0 + g.c1) + g.cs0 + g.cs1 && (g.kw == 3 || g.kw == 2), "conv K"); }
     else { MRISR_REQUIRE(g.K == g.c0 + g.c1, "plain K"); }
     if (g.kw != 3 || g.subpix) {
         MRISR_REQUIRE(sizeof(T) == 2 && g.conv && !g.c1 && g.stride == 1 && !g.ups && !g.zstuff && g.splitk == 1 && (!g.subpix || g.batch == 4),
@@ -3464,6 +3567,10 @@ int launch_gemm(const GemmArgs& g, hipStream_t st) {
     if (!tile) plan(g, sizeof(T) == 2, g.splitk, &tile, &s);
     if ((sizeof(T) != 2 || !bl_ok(g)) && tile > 4) tile = 1;
     if ((g.kw != 3 || g.subpix) && !(tile >= 14 && tile <= 31)) tile = 25;  // only gemm_bl_kernel's gather knows these forms
+    if (g.cs0 || g.cs1 || g.s0 || g.s1) {
+        MRISR_REQUIRE(sizeof(T) == 2 && gemm_sc_tail_ok(g), "1x1 tail: bf16 stride-1 3x3 conv, channel counts multiples of 64, operands below 2 GiB");
+        MRISR_REQUIRE(sc_tail_tile(tile) && (tile < 40 || halo_ok(g, halo_bm(tile))), "1x1 tail: only the 2-stage tiled kernels (14-31) and the 4-wave halo kernels (41-45) carry it");
+    }
     // split-K: the bf16 DMA kernels (tiled and halo) finish the reduction themselves
     {   // cold-weight pre-touch: matrices of at least MRISR_PRETOUCH_MIN_KB (default 512; 0 ... 1024 measure the same); MRISR_PRETOUCH=0 turns it off
         static const int on = [] { const char* e = getenv("MRISR_PRETOUCH"); return e ? atoi(e) : 1; }();
@@ -3472,7 +3579,7 @@ int launch_gemm(const GemmArgs& g, hipStream_t st) {
         const_cast<GemmArgs&>(g).pretouch = (on && sizeof(T) == 2 && g.batch == 1 && (long long)g.N * g.K * 2 >= min_b) ? cap : 0;
     }
     const_cast<GemmArgs&>(g).sk_counters = nullptr;
-    if (g.splitk > 1 && sizeof(T) == 2 && !g.defer_reduce && tile_reduces_in_kernel(tile)) {
+    if (g.splitk > 1 && sizeof(T) == 2 && !g.defer_reduce && tile_reduces_in_kernel(tile) && !g.cs0) {
         const long long ntiles = tile_count(tile, g) * (long long)g.batch;
         if (ntiles > 0 && ntiles <= kSkCounters) const_cast<GemmArgs&>(g).sk_counters = sk_counters_for(st);
     }

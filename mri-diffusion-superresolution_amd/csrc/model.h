@@ -10,6 +10,10 @@ struct ResW {
     bool has_sc = false;
     LinW sc;
     int temb_off = 0, cin = 0, cout = 0;
+    // bf16 engine, has_sc: conv2 and the shortcut as ONE filter bank [cout][9 * cout + cin] (the shortcut's columns last) and the summed bias
+    // b2 + b_sc - conv2 then runs the shortcut as a 1x1 tail of its K loop (runner.h::resnet); c2 / sc stay for the literal and training paths
+    void* c2sc = nullptr;
+    const float* b2sc = nullptr;
 };
 struct XfW {
     int C = 0;

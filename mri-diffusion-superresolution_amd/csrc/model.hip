@@ -233,6 +233,21 @@ struct Packer {
         if (m.find(name + ".conv_shortcut.weight")) {
             r.has_sc = true;
             r.sc = linear({name + ".conv_shortcut"});
+            // the fused bank (built from the packed bf16 weights: the same rounded values both forms multiply); channel counts that fill K tiles
+            if (sizeof(T) == 2 && !err && r.c2.w && r.sc.w && !r.sc.R && !r.sc.w8 && r.c2.b && r.sc.b && r.c2.ks == 3 && r.c2.cin == r.cout &&
+                r.sc.k == r.cin && r.sc.n == r.cout && r.cin % 64 == 0 && r.cout % 64 == 0) {
+                const size_t k2 = (size_t)9 * r.cout, kt = k2 + r.cin;
+                r.c2sc = m.new_packed((size_t)r.cout * kt * sizeof(T), false);
+                float* bs = static_cast<float*>(m.new_packed((size_t)r.cout * sizeof(float), false));
+                if (!r.c2sc || !bs) { err = 4; return r; }
+                if (hipMemcpy2DAsync(r.c2sc, kt * sizeof(T), r.c2.w, k2 * sizeof(T), k2 * sizeof(T), r.cout, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+                    hipMemcpy2DAsync(static_cast<T*>(r.c2sc) + k2, kt * sizeof(T), r.sc.w, (size_t)r.cin * sizeof(T), (size_t)r.cin * sizeof(T), r.cout,
+                                     hipMemcpyDeviceToDevice, st) != hipSuccess ||
+                    hipMemcpyAsync(bs, r.c2.b, (size_t)r.cout * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess ||
+                    launch_add_inplace<float>(bs, r.sc.b, r.cout, st))
+                    err = 5;
+                r.b2sc = bs;
+            }
         }
         m.temb_mods.push_back(name + ".time_emb_proj");
         r.temb_off = m.tproj_total;

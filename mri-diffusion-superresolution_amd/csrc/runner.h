@@ -258,12 +258,23 @@ struct Runner {
         GemmArgs g2;  // conv2, planned before anything else is allocated: whether the fused form applies decides what must outlive this block
         bool fuse2 = false;
         GroupNormArgs a2;
+        // the 1x1 shortcut as the tail of conv2's K loop (bf16 inference): conv2(h) + b2 + (W_sc x + b_sc) is one GEMM over K = [9 cout | cin]
+        // on the bank built at finalize, bias b2 + b_sc, no residual - the shortcut's output is never written or read back
+        GemmArgs gt;
+        gt.c0 = r.cout; gt.lda0 = r.cout; gt.a0 = reinterpret_cast<void*>(0x1000);
+        gt.conv = 1; gt.B = x.B; gt.Hin = x.H; gt.Win = x.W; gt.Hout = x.H; gt.Wout = x.W;
+        gt.s0 = x.p; gt.cs0 = x.C; gt.lds0 = x.C;
+        if (x1) { gt.s1 = x1->p; gt.cs1 = x1->C; gt.lds1 = x1->C; }
+        gt.w = r.c2sc; gt.M = (int)x.rows(); gt.N = r.cout; gt.K = 9 * r.cout + r.cin; gt.bias = r.b2sc;
+        gt.out = o.p; gt.ldo = r.cout;
+        const bool sc_tail = sizeof(T) == 2 && !m.keep && r.has_sc && r.c2sc && sc_fused_enabled() && x.C + (x1 ? x1->C : 0) == r.cin && gemm_sc_tail_ok(gt);
         if (next && next_out && sizeof(T) == 2 && !m.keep && next->c == r.cout && groupnorm_slabs_ok(r.cout, m.cfg.norm_num_groups, x.H * x.W)) {
             g2.c0 = r.cout; g2.lda0 = r.cout;
             g2.conv = 1; g2.B = x.B; g2.Hin = x.H; g2.Win = x.W; g2.Hout = x.H; g2.Wout = x.W;
             g2.w = r.c2.w; g2.M = (int)x.rows(); g2.N = r.cout; g2.K = 9 * r.cout; g2.bias = r.c2.b;
             g2.a0 = reinterpret_cast<void*>(0x1000); g2.resid = reinterpret_cast<void*>(0x1000); g2.ldr = r.cout;
             g2.out = reinterpret_cast<void*>(0x1000); g2.ldo = r.cout;
+            if (sc_tail) g2 = gt;  // (the planner sees the fused K and the launch without a residual)
             TRY(gemm_choose(g2, true));
             fuse2 = g2.splitk > 1;
             if (fuse2) {
@@ -279,7 +290,9 @@ struct Runner {
         const int div = m.t_scalar ? INT_MAX : x.H * x.W;
         TRY(conv3_gn(xn, nullptr, r.c1, m.tproj_out + r.temb_off, m.tproj_total, div, nullptr, r.n2, true, m.cfg.norm_eps, nullptr, &hn));
         Act res = x;
-        if (r.has_sc) {
+        if (sc_tail) {
+            res.p = nullptr;  // (no residual: the shortcut rides in conv2's K loop)
+        } else if (r.has_sc) {
             // 1x1 shortcut on the (concatenated) raw input, written straight into the output buffer
             GemmArgs g;
             if (x1) { g.a1 = x1->p; g.c1 = x1->C; g.lda1 = x1->C; }
@@ -302,9 +315,12 @@ struct Runner {
                 a2.x0 = nullptr; a2.c0 = r.cout; a2.B = x.B; a2.HW = x.H * x.W; a2.groups = m.cfg.norm_num_groups; a2.eps = next_eps;
                 a2.gamma = next->g; a2.beta = next->b; a2.silu = 0; a2.y = next_out->p;
                 GnSlabSrc ss;
-                ss.partial = g2.partial; ss.splitk = g2.splitk; ss.alpha = g2.alpha; ss.bias = g2.bias; ss.resid = res.p; ss.ldr = r.cout; ss.raw_out = o.p;
+                ss.partial = g2.partial; ss.splitk = g2.splitk; ss.alpha = g2.alpha; ss.bias = g2.bias; ss.resid = res.p; ss.ldr = r.cout; ss.raw_out = o.p;  // (1x1 tail: summed bias, null residual)
                 TRY(launch_groupnorm_slabs(a2, ss, st));
             }
+        } else if (sc_tail) {
+            gt.a0 = hn.p;
+            TRY(run_gemm(gt));
         } else {
             GemmArgs g;
             g.a0 = hn.p; g.c0 = hn.C; g.lda0 = hn.C;

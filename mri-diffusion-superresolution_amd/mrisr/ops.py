@@ -41,6 +41,24 @@ def conv3x3(x, weight, bias=None, x2=None, stride=1, upsample=False, act=L.ACT_N
     return yb.permute(0, 3, 1, 2)
 
 
+def conv3x3_sc(x, weight, bias, xs, weight_sc, bias_sc, x2=None, xs2=None, splitk=0, tile=0, fused=True):
+    """A resnet's conv2 with its 1x1 shortcut (bf16): conv3x3([x | x2]) + bias + weight_sc [xs | xs2] + bias_sc.  ``fused``: one launch with
+    the shortcut as the 1x1 tail of the conv's K loop; otherwise the shortcut GEMM followed by the conv with it as residual."""
+    bufs = [_nhwc(t) if t is not None else (None, None) for t in (x, x2, xs, xs2)]
+    w = weight.detach().to(torch.float32).contiguous()
+    ws = weight_sc.detach().to(torch.float32).reshape(weight_sc.shape[0], -1).contiguous()
+    b, bs = (t.detach().to(torch.float32).contiguous() for t in (bias, bias_sc))
+    B, _, H, W = x.shape
+    cout = w.shape[0]
+    yb = torch.empty((B, H, W, cout), dtype=x.dtype, device=x.device)
+    ty = L.as_tensor(yb, L.MRISR_NHWC, shape=(B, cout, H, W))
+    ref = lambda d: C.byref(d) if d is not None else None
+    L.check(L.lib().mrisr_op_conv3x3_sc(ref(bufs[0][1]), ref(bufs[1][1]), C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()),
+                                        ref(bufs[2][1]), ref(bufs[3][1]), C.c_void_p(ws.data_ptr()), C.c_void_p(bs.data_ptr()), cout,
+                                        splitk, tile, 1 if fused else 0, C.byref(ty), L.stream_ptr()))
+    return yb.permute(0, 3, 1, 2)
+
+
 def linear(x, weight, bias=None, act=L.ACT_NONE, splitk=0, tile=0):
     """x [M,K], weight [N,K] f32 -> [M,N] (GEGLU: [M,N/2])."""
     x = x.contiguous()

@@ -422,6 +422,11 @@ int mrisr_op_conv3x3(const mrisr_tensor* x_nhwc, const mrisr_tensor* x2_nhwc, co
 int mrisr_op_conv3x3_sc(const mrisr_tensor* x_nhwc, const mrisr_tensor* x2_nhwc, const float* w_oihw_dev, const float* bias_dev,
                         const mrisr_tensor* xs_nhwc, const mrisr_tensor* xs2_nhwc, const float* w_sc_dev, const float* bias_sc_dev,
                         int cout, int splitk, int tile, int fused, mrisr_tensor* y_nhwc, void* stream);
+/* a transformer block's ff.net.2 followed by the transformer's proj_out (bf16 rows; widths multiples of 64):
+ * y = (h W2^T + b2 + t) Wp^T + bp + x with h [M][K4], t / x / y [M][C], W2 [C][K4], Wp [C][C] (f32 on the device; biases may be NULL).
+ * fused = 1: one launch over K = [K4 | C] on the composed weight [Wp W2 | Wp]; fused = 0: the two launches */
+int mrisr_op_ff_proj(const mrisr_tensor* h_rows, const mrisr_tensor* t_rows, const mrisr_tensor* x_rows, const float* w2_dev,
+                     const float* b2_dev, const float* wp_dev, const float* bp_dev, int tile, int fused, mrisr_tensor* y_rows, void* stream);
 int mrisr_op_linear(const mrisr_tensor* x_rows, const float* w_dev, const float* bias_dev, int n, int act,
                     int splitk, int tile, mrisr_tensor* y_rows, void* stream);
 /* y = LayerNorm(x; gamma, beta, eps 1e-5) W^T + bias with the normalisation as a prologue of the row-panel GEMM kernel (bf16;

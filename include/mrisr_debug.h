@@ -60,6 +60,11 @@ void mrisr_debug_gn_slabs(int on);
  * shortcut GEMM + conv2 with a residual): -1 default (MRISR_SC_FUSED, on), 0 the two launches, 1 on */
 void mrisr_debug_sc_fused(int on);
 
+/* a transformer block's ff.net.2 and the transformer's proj_out as ONE GEMM over K = [4C | C] (bf16 inference, C >= 640: the composed
+ * weight [Wp W2 | Wp] built at finalize, sources the GEGLU output and the residual stream): -1 default (MRISR_FF_PROJ_FUSED, on),
+ * 0 the two launches, 1 on */
+void mrisr_debug_ff_proj_fused(int on);
+
 /* the fused row-local middle of the C = 320 transformer blocks (csrc/xtail.hip: attn1.to_out + residual, LayerNorm2, attn2.to_q,
  * cross-attention, attn2.to_out + residual in one launch): -1 default (MRISR_XTAIL, on), 0 the four separate launches, 1 on */
 void mrisr_debug_xattn_tail(int on);

@@ -152,6 +152,60 @@ static int op_conv3x3_sc_t(const mrisr_tensor* x, const mrisr_tensor* x2, const 
     return 0;
 }
 
+// (h W2^T + b2 + t) Wp^T + bp + x: a transformer block's ff.net.2 followed by the transformer's proj_out.  fused: ONE launch over K = [K4 | C]
+// on the composed bank [Wp W2 | Wp] (launch_compose_ff_proj), sources h and t, bias Wp b2 + bp, residual x; otherwise the two launches it
+// replaces (the intermediate rounded to bf16).  Every launch is planned by gemm_choose (`tile` and mrisr_debug_force_split apply).
+static int run_planned(GemmArgs& g, DevBuf& part, hipStream_t st) {
+    TRY(gemm_choose(g, true));
+    if (g.splitk > 1) {
+        TRY(part.reserve((size_t)g.splitk * g.M * g.N * sizeof(float), false));
+        g.partial = static_cast<float*>(part.p);
+    }
+    return launch_gemm<bf16>(g, st);
+}
+static int op_ff_proj_t(const mrisr_tensor* h, const mrisr_tensor* t, const mrisr_tensor* x, const float* w2, const float* b2, const float* wp,
+                        const float* bp, int tile, int fused, mrisr_tensor* y, hipStream_t st) {
+    typedef bf16 T;
+    const int M = (int)h->shape[0], K4 = (int)h->shape[1], C = (int)t->shape[1];
+    MRISR_REQUIRE(t->shape[0] == M && x->shape[0] == M && x->shape[1] == C && y->shape[0] == M && y->shape[1] == C, "ff.net.2 + proj_out: row shapes");
+    MRISR_REQUIRE(C % 64 == 0 && K4 % 64 == 0, "ff.net.2 + proj_out: widths that are multiples of 64");
+    DevBuf bank, bsum, w2p, wpp, mid, part;
+    int rc = 0;
+    if (fused) {
+        const int Kt = K4 + C;
+        TRY(bank.reserve((size_t)C * Kt * sizeof(T), false));
+        TRY(bsum.reserve((size_t)C * sizeof(float), false));
+        TRY(launch_compose_ff_proj(wp, w2, b2, bp, bank.p, Kt, static_cast<float*>(bsum.p), C, K4, st));
+        TRY(launch_pack_rows<T>(wp, C, C, bank.p, Kt, 0, K4, 0, 0, 1.0f, st));
+        GemmArgs g;
+        g.a0 = h->data; g.c0 = K4; g.lda0 = K4;
+        g.a1 = t->data; g.c1 = C; g.lda1 = C;
+        g.w = bank.p; g.M = M; g.N = C; g.K = Kt; g.bias = static_cast<const float*>(bsum.p);
+        g.resid = x->data; g.ldr = C; g.out = y->data; g.ldo = C; g.no_rp = 1;
+        mrisr_debug_force_tile(tile);
+        rc = run_planned(g, part, st);
+    } else {
+        TRY(w2p.reserve((size_t)C * K4 * sizeof(T), false));
+        TRY(wpp.reserve((size_t)C * C * sizeof(T), false));
+        TRY(mid.reserve((size_t)M * C * sizeof(T), false));
+        TRY(launch_pack_rows<T>(w2, C, K4, w2p.p, K4, 0, 0, 0, 0, 1.0f, st));
+        TRY(launch_pack_rows<T>(wp, C, C, wpp.p, C, 0, 0, 0, 0, 1.0f, st));
+        GemmArgs g1, g2;
+        g1.a0 = h->data; g1.c0 = K4; g1.lda0 = K4; g1.w = w2p.p; g1.M = M; g1.N = C; g1.K = K4; g1.bias = b2;
+        g1.resid = t->data; g1.ldr = C; g1.out = mid.p; g1.ldo = C;
+        g2.a0 = mid.p; g2.c0 = C; g2.lda0 = C; g2.w = wpp.p; g2.M = M; g2.N = C; g2.K = C; g2.bias = bp;
+        g2.resid = x->data; g2.ldr = C; g2.out = y->data; g2.ldo = C;
+        mrisr_debug_force_tile(tile);
+        rc = run_planned(g1, part, st);
+        if (!rc) rc = hipStreamSynchronize(st) != hipSuccess;  // (`part` is reused)
+        if (!rc) rc = run_planned(g2, part, st);
+    }
+    mrisr_debug_force_tile(0);
+    if (rc) return rc;
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 template <typename T>
 static int op_attention_t(const mrisr_tensor* q, const mrisr_tensor* k, const mrisr_tensor* v, int H, int flash,
                           mrisr_tensor* out, hipStream_t st) {
@@ -246,6 +300,17 @@ int mrisr_op_conv3x3_sc(const mrisr_tensor* x, const mrisr_tensor* x2, const flo
                   "NHWC in/out");
     TRY(gemm_prepare());
     return op_conv3x3_sc_t(x, x2, w_oihw_dev, bias_dev, xs, xs2, w_sc_dev, bias_sc_dev, cout, splitk, tile, fused, y, (hipStream_t)stream);
+    API_END
+}
+
+int mrisr_op_ff_proj(const mrisr_tensor* h, const mrisr_tensor* t, const mrisr_tensor* x, const float* w2_dev, const float* b2_dev,
+                     const float* wp_dev, const float* bp_dev, int tile, int fused, mrisr_tensor* y, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(h && t && x && y && w2_dev && wp_dev, "null argument");
+    MRISR_REQUIRE(h->dtype == MRISR_BF16 && t->dtype == MRISR_BF16 && x->dtype == MRISR_BF16 && y->dtype == MRISR_BF16, "ff.net.2 + proj_out: bf16 rows");
+    MRISR_REQUIRE(h->ndim == 2 && t->ndim == 2 && x->ndim == 2 && y->ndim == 2, "rows in/out");
+    TRY(gemm_prepare());
+    return op_ff_proj_t(h, t, x, w2_dev, b2_dev, wp_dev, bp_dev, tile, fused, y, (hipStream_t)stream);
     API_END
 }
 

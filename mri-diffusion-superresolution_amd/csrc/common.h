@@ -221,6 +221,7 @@ int launch_xattn_tail(const XTailArgs& x, hipStream_t st);
 int gemm_rp_tile(const GemmArgs& g);  // row-panel kernel id for this (plain, short-K, bf16) GEMM, 0 if it is not eligible
 bool gemm_sc_tail_ok(const GemmArgs& g);  // the launch (with its 1x1 tail fields set) has the form the two tail-capable kernel families take
 bool sc_fused_enabled();                  // resnet shortcut as conv2's 1x1 tail (MRISR_SC_FUSED, default 1; mrisr_debug_sc_fused)
+bool ff_proj_fused_enabled();             // ff.net.2 and proj_out as one GEMM over K = [4C | C] (MRISR_FF_PROJ_FUSED, default 1; mrisr_debug_ff_proj_fused)
 int gemm_choose(GemmArgs& g, bool is_bf16);  // sets g.tile / g.splitk (autotuned per signature for bf16)  // set launch attributes of every GEMM instantiation (call before graph capture)
 
 // ---------------------------------------------------------------------------------------------
@@ -443,6 +444,10 @@ int launch_subpix_shuffle(const void* planes, void* out, int B, int H, int W, in
 template <typename T>
 int launch_pack_conv3x3_padded(const float* src, void* dst, int Cout, int Cin, int ks, int Cout_pad, int Cin_pad, hipStream_t st);
 int launch_pack_bias_geglu(const float* src, float* dst, int half, hipStream_t st);
+// two linear maps with nothing between them as one: dst[n][0..K4) = bf16(sum_j wp[n][j] w2[j][k]) (wp [C][C], w2 [C][K4], f32 masters, f32
+// accumulation), bias_dst[n] = sum_j wp[n][j] b2[j] + bp[n] (b2 / bp may be null); C and K4 multiples of 64
+int launch_compose_ff_proj(const float* wp, const float* w2, const float* b2, const float* bp, void* dst_bf16, int ld_dst, float* bias_dst,
+                           int C, int K4, hipStream_t st);
 template <typename T> int launch_fill_zero(void* p, long long n, hipStream_t st);
 // packed bf16 rows -> OCP e4m3 rows + one f32 scale per row (amax / 448)
 int launch_quant_rows_fp8(const void* src_bf16, int rows, int cols, void* dst8, float* scales, hipStream_t st);

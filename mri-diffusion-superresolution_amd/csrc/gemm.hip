@@ -3240,6 +3240,12 @@ bool sc_fused_enabled() {
     static const int env = [] { const char* e = getenv("MRISR_SC_FUSED"); return e ? atoi(e) : 1; }();
     return g_sc_fused < 0 ? env != 0 : g_sc_fused != 0;
 }
+static int g_ff_proj_fused = -1;  // test hook: -1 = MRISR_FF_PROJ_FUSED (default 1), 0 off, 1 on
+extern "C" void mrisr_debug_ff_proj_fused(int on) { g_ff_proj_fused = on; ++g_plan_salt; }
+bool ff_proj_fused_enabled() {
+    static const int env = [] { const char* e = getenv("MRISR_FF_PROJ_FUSED"); return e ? atoi(e) : 1; }();
+    return g_ff_proj_fused < 0 ? env != 0 : g_ff_proj_fused != 0;
+}
 
 // ---- tile / split-K planner ------------------------------------------------------------------
 struct TileCfg { int id, bm, bn; double eff; bool bl; };

@@ -788,6 +788,56 @@ int launch_pack_bias_geglu(const float* src, float* dst, int half, hipStream_t s
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
+// ---- ff.net.2 composed with proj_out (runner.h::transformer): W'[n][k] = sum_j Wp[n][j] W2[j][k] and b'[n] = sum_j Wp[n][j] b2[j] + bp[n],
+// both in f32 from the f32 masters (j ascending), W' rounded once to bf16.  64 x 64 output tiles, 16 values of j per LDS stage.
+__global__ void __launch_bounds__(256) compose_ff_proj_kernel(const float* __restrict__ wp, const float* __restrict__ w2, bf16* __restrict__ dst,
+                                                              int C, int K4, int ld_dst) {
+    __shared__ float sa[16][64 + 1];  // Wp tile [j][n]
+    __shared__ float sb[16][64];      // W2 tile [j][k]
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int n0 = blockIdx.y * 64, k0 = blockIdx.x * 64;
+    float acc[4][4] = {};
+    for (int j0 = 0; j0 < C; j0 += 16) {
+        for (int i = threadIdx.x; i < 64 * 16; i += 256) {
+            sa[i & 15][i >> 4] = wp[(size_t)(n0 + (i >> 4)) * C + j0 + (i & 15)];
+            sb[i >> 6][i & 63] = w2[(size_t)(j0 + (i >> 6)) * K4 + k0 + (i & 63)];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            float a[4], b[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { a[r] = sa[j][ty * 4 + r]; b[r] = sb[j][tx * 4 + r]; }
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[r][c] += a[r] * b[c];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) dst[(size_t)(n0 + ty * 4 + r) * ld_dst + k0 + tx * 4 + c] = from_f32<bf16>(acc[r][c]);
+}
+__global__ void compose_ff_proj_bias_kernel(const float* __restrict__ wp, const float* __restrict__ b2, const float* __restrict__ bp,
+                                            float* __restrict__ dst, int C) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= C) return;
+    float acc = 0.f;
+    if (b2)
+        for (int j = 0; j < C; ++j) acc += wp[(size_t)n * C + j] * b2[j];
+    dst[n] = acc + (bp ? bp[n] : 0.f);
+}
+int launch_compose_ff_proj(const float* wp, const float* w2, const float* b2, const float* bp, void* dst_bf16, int ld_dst, float* bias_dst,
+                           int C, int K4, hipStream_t st) {
+    MRISR_REQUIRE(wp && w2 && dst_bf16 && bias_dst && C > 0 && C % 64 == 0 && K4 > 0 && K4 % 64 == 0 && ld_dst >= K4,
+                  "composed ff.net.2 / proj_out bank: widths that are multiples of 64");
+    hipLaunchKernelGGL(compose_ff_proj_kernel, dim3(K4 / 64, C / 64), dim3(256), 0, st, wp, w2, reinterpret_cast<bf16*>(dst_bf16), C, K4, ld_dst);
+    hipLaunchKernelGGL(compose_ff_proj_bias_kernel, dim3((C + 255) / 256), dim3(256), 0, st, wp, b2, bp, bias_dst, C);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 template <typename T>
 __global__ void scale_inplace_kernel(T* p, float s, long long n) {
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) p[i] = from_f32<T>(to_f32(p[i]) * s);

@@ -28,6 +28,12 @@ struct XfW {
     void* proj_outp = nullptr;  // proj_out.w K-permuted: the continuation of the fused feed-forward kernel
     void* out2p = nullptr;
     void* kvp = nullptr;
+    // bf16 engine, blocks outside the fused feed-forward kernel (C >= 640): ff.net.2 and proj_out - two linear maps with only a residual add
+    // between them - as ONE weight [C][4C + C] = [Wp W2 | Wp] (the product in f32 from the masters, rounded once; the last C columns the packed
+    // proj_out.w) and the bias Wp b2 + bp: o = [ff | t] ffpo^T + bffpo + x is one GEMM (runner.h::transformer); ff2 / proj_out stay for the
+    // literal and training paths
+    void* ffpo = nullptr;
+    const float* bffpo = nullptr;
 };
 struct Level {
     std::vector<ResW> res;

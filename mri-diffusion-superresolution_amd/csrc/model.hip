@@ -221,6 +221,20 @@ struct Packer {
     }
     // host-side helper for merged mode (load time only): W' = W + s*B*A via a tiny kernel
     int merge_lora(const float* w, const float* A, const float* B, float* out, int n, int k, int r);
+    // the f32 weight [n][k] a module multiplies by, as linear() packs it: the master copy, or - an adapter in merged mode (lora_fused = 0) -
+    // W + s B A in `hold`
+    const float* effective_f32(const std::string& mod, int n, int k, std::unique_ptr<DevBuf>& hold) {
+        const RawParam* w = need(mod + ".weight");
+        if (!w) return nullptr;
+        const RawParam* la = m.find(mod + ".lora_A.default.weight");
+        const RawParam* lb = m.find(mod + ".lora_B.default.weight");
+        if (!(la && lb) || (m.cfg.lora_rank > 0 && m.cfg.lora_fused)) return static_cast<const float*>(w->data->p);
+        hold.reset(new DevBuf());
+        if (hold->reserve((size_t)n * k * sizeof(float), false)) { err = 4; return nullptr; }
+        if (merge_lora(static_cast<const float*>(w->data->p), static_cast<const float*>(la->data->p), static_cast<const float*>(lb->data->p),
+                       static_cast<float*>(hold->p), n, k, (int)la->shape[0])) { err = 6; return nullptr; }
+        return static_cast<const float*>(hold->p);
+    }
 
     ResW resnet(const std::string& name) {
         ResW r;
@@ -281,6 +295,28 @@ struct Packer {
                 if (!x.proj_outp) { err = 4; return x; }
                 if (launch_pack_mlp_w2(x.proj_out.w, x.proj_outp, 320, 320, st)) err = 5;
             }
+        }
+        // ff.net.2 composed with proj_out (the blocks the fused feed-forward kernel does not take): [Wp W2 | Wp] and Wp b2 + bp, the product from
+        // the f32 masters (a merged adapter included), the tail columns the packed proj_out.w itself
+        if (sizeof(T) == 2 && !err && !mlp_fused_ok(x.C, x.ff2.k, x.ff2.n) && x.C % 64 == 0 && x.ff2.k == 4 * x.C && x.ff2.n == x.C &&
+            x.proj_out.n == x.C && x.proj_out.k == x.C && !x.ff2.R && !x.proj_out.R && !x.ff2.w8 && !x.proj_out.w8 && x.ff2.w && x.proj_out.w) {
+            const int C = x.C, K4 = 4 * C, Kt = 5 * C;
+            x.ffpo = m.new_packed((size_t)C * Kt * sizeof(T), false);
+            float* bs = static_cast<float*>(m.new_packed((size_t)C * sizeof(float), false));
+            if (!x.ffpo || !bs) { err = 4; return x; }
+            std::unique_ptr<DevBuf> hp, h2;
+            const float* wp = effective_f32(name + ".proj_out", C, C, hp);
+            const float* w2 = effective_f32(b + ".ff.net.2", C, K4, h2);
+            const RawParam* b2 = m.find(b + ".ff.net.2.bias");
+            const RawParam* bp = m.find(name + ".proj_out.bias");
+            if (!wp || !w2) return x;
+            if (launch_compose_ff_proj(wp, w2, b2 ? static_cast<const float*>(b2->data->p) : nullptr, bp ? static_cast<const float*>(bp->data->p) : nullptr,
+                                       x.ffpo, Kt, bs, C, K4, st) ||
+                hipMemcpy2DAsync(static_cast<T*>(x.ffpo) + K4, (size_t)Kt * sizeof(T), x.proj_out.w, (size_t)C * sizeof(T), (size_t)C * sizeof(T), C,
+                                 hipMemcpyDeviceToDevice, st) != hipSuccess)
+                err = 5;
+            x.bffpo = bs;
+            if (hp || h2) (void)hipStreamSynchronize(st);  // merged buffers die at scope end
         }
         // fused middle (xtail.hip xattn_tail_kernel): to_q / to_out of attn2 read their row operand in accumulator order
         if (sizeof(T) == 2 && !err && x.C == 320 && m.cfg.num_heads == 8 && x.q2.n == 320 && x.q2.k == 320 && x.out2.n == 320 && x.out2.k == 320 &&

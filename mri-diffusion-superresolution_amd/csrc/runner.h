@@ -482,7 +482,21 @@ struct Runner {
             } else {
                 TRY(linear(t, M, C, xw.ff1, ACT_GEGLU, nullptr, 0, nullptr, ff, 4 * C, nullptr, &xw.ln3, nrm));
             }
-            TRY(linear(ff, M, 4 * C, xw.ff2, ACT_NONE, t, C, nullptr, t, C));
+            if (sizeof(T) == 2 && !m.keep && xw.ffpo && !xw.ff2.R && !xw.proj_out.R && ff_proj_fused_enabled()) {
+                // ff.net.2 and proj_out as one GEMM over K = [4C | C] on the bank built at finalize:
+                // o = ff (Wp W2)^T + t Wp^T + (Wp b2 + bp) + x - the block's output t' = ff2(ff) + t is never written or read back
+                GemmArgs g;
+                g.a0 = ff; g.c0 = 4 * C; g.lda0 = 4 * C;
+                g.a1 = t; g.c1 = C; g.lda1 = C;
+                g.w = xw.ffpo; g.M = M; g.N = C; g.K = 5 * C; g.bias = xw.bffpo;
+                g.resid = x.p; g.ldr = C; g.out = o.p; g.ldo = C;
+                g.no_rp = 1;  // (two sources: not a row-panel launch)
+                g.alg_flops = 2.0 * M * (double)C * (5 * C);
+                TRY(run_gemm(g));
+                proj_done = true;
+            } else {
+                TRY(linear(ff, M, 4 * C, xw.ff2, ACT_NONE, t, C, nullptr, t, C));
+            }
         }
         if (!proj_done) TRY(linear(t, M, C, xw.proj_out, ACT_NONE, x.p, C, nullptr, o.p, C));
         if (!m.keep) m.arena.release(mk);

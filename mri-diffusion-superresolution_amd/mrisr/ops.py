@@ -59,6 +59,20 @@ def conv3x3_sc(x, weight, bias, xs, weight_sc, bias_sc, x2=None, xs2=None, split
     return yb.permute(0, 3, 1, 2)
 
 
+def ff_proj(h, t, x, w2, b2, wp, bp, tile=0, fused=True):
+    """A transformer block's ff.net.2 followed by the transformer's proj_out (bf16 rows): (h w2^T + b2 + t) wp^T + bp + x with h [M,K4],
+    t / x [M,C], w2 [C,K4], wp [C,C].  ``fused``: one launch over K = [K4 | C] on the composed weight [wp w2 | wp]; otherwise the two launches."""
+    h, t, x = h.contiguous(), t.contiguous(), x.contiguous()
+    f = lambda a: a.detach().to(torch.float32).contiguous() if a is not None else None
+    w2f, b2f, wpf, bpf = (f(a) for a in (w2, b2, wp.reshape(wp.shape[0], -1), bp))
+    y = torch.empty_like(x)
+    th, tt, tx, ty = (L.as_tensor(a) for a in (h, t, x, y))
+    p = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+    L.check(L.lib().mrisr_op_ff_proj(C.byref(th), C.byref(tt), C.byref(tx), p(w2f), p(b2f), p(wpf), p(bpf), tile, 1 if fused else 0,
+                                     C.byref(ty), L.stream_ptr()))
+    return y
+
+
 def linear(x, weight, bias=None, act=L.ACT_NONE, splitk=0, tile=0):
     """x [M,K], weight [N,K] f32 -> [M,N] (GEGLU: [M,N/2])."""
     x = x.contiguous()

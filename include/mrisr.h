@@ -264,6 +264,9 @@ int mrisr_train_prepare(mrisr_model* m, void* stream);
 int64_t mrisr_train_num_trainable(const mrisr_model* m);
 int mrisr_train_num_tensors(const mrisr_model* m);
 int mrisr_train_tensor_info(const mrisr_model* m, int i, const char** key, int64_t* offset, int64_t shape[2]);
+/* The PyTorch shape of trainable tensor i: 4-D ([r, cin, 3, 3] / [cout, r, 1, 1]) for the adapters of a resnet's 3x3 convs, 2-D for the
+ * rest.  (mrisr_train_tensor_info reports a conv tensor as rows = shape[0], cols = the product of the others.) */
+int mrisr_train_tensor_shape(const mrisr_model* m, int i, int64_t shape[4], int* ndim);
 int mrisr_train_bind(mrisr_model* m, float* theta_dev, float* grad_dev, int init_from_model, void* stream);
 int mrisr_train_refresh(mrisr_model* m, void* stream);
 int mrisr_train_step(mrisr_model* m, const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,
@@ -506,6 +509,18 @@ int mrisr_op_conv_wgrad(int dtype, const void* x, int xB, int xH, int xW, int ci
  * mode 1: stride 2, dx [B][2H][2W][cin]; accumulate: dx += */
 int mrisr_op_conv_dgrad(int dtype, const void* dy, int B, int H, int W, int cout, const float* w_oihw_dev, int cin, int mode, void* dx,
                         int accumulate, void* stream);
+/* LoRA on a 3x3 conv (peft lora.Conv2d; stride 1, pad 1).  a_dev: lora_A [r][cin][3][3] f32, b_dev: lora_B [cout][r] f32, both on the device.
+ * conv_lora_down: z [B*H*W][r] f32 = conv3x3(x, A) on NHWC x of `dtype`; route 0 = planned, else 100 * (waves per pixel group: 1 or 4) +
+ * K slabs (bf16).  conv_lora_dgrad: dx NHWC [B][H][W][cin] of `dtype` (+)= the transposed conv of dz [B*H*W][r] f32 (r in 4 / 8 / 12 / 16).
+ * conv3x3_lora: y = conv3x3(x, W) + bias + rowvec[image] + scale * B conv3x3(x, A) + resid as the down-projection followed by the conv with
+ * the rank-r term in its epilogue; rowvec_dev ([B][cout] f32) and resid may be null; splitk / tile force the conv's plan as in mrisr_op_conv3x3. */
+int mrisr_op_conv_lora_down(int dtype, const void* x_nhwc, int B, int H, int W, int cin, const float* a_dev, int r, float* z, int route,
+                            void* stream);
+int mrisr_op_conv_lora_dgrad(int dtype, const float* dz, int B, int H, int W, int r, const float* a_dev, int cin, void* dx_nhwc, int accumulate,
+                             void* stream);
+int mrisr_op_conv3x3_lora(const mrisr_tensor* x, const float* w_oihw_dev, const float* bias_dev, const float* a_dev, const float* b_dev, int r,
+                          float scale, const float* rowvec_dev, const mrisr_tensor* resid, int cout, int splitk, int tile, mrisr_tensor* y,
+                          void* stream);
 
 
 /* the fused guided step of mrisr_sampler_run_guided alone: x [B,C,h,w] f32 (in place), x2 [2B,C,h,w] f32 (receives the new x in

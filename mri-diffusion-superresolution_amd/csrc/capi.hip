@@ -736,6 +736,15 @@ int mrisr_train_tensor_info(const mrisr_model* m, int i, const char** key, int64
     shape[1] = t.cols;
     return 0;
 }
+int mrisr_train_tensor_shape(const mrisr_model* m, int i, int64_t shape[4], int* ndim) {
+    MRISR_REQUIRE(m && m->train_ready, "call mrisr_train_prepare first");
+    MRISR_REQUIRE(i >= 0 && i < (int)m->trainables.size() && shape && ndim, "trainable tensor index");
+    const Model::Trainable& t = m->trainables[i];
+    *ndim = t.ndim;
+    if (t.ndim == 2) { shape[0] = t.rows; shape[1] = t.cols; shape[2] = shape[3] = 1; }
+    else for (int k = 0; k < 4; ++k) shape[k] = t.shape[k];
+    return 0;
+}
 int mrisr_train_bind(mrisr_model* m, float* theta_dev, float* grad_dev, int init_from_model, void* stream) {
     API_BEGIN
     MRISR_REQUIRE(m, "null handle");

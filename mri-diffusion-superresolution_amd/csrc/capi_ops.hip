@@ -264,6 +264,70 @@ static int op_attention_t(const mrisr_tensor* q, const mrisr_tensor* k, const mr
 }
 
 
+// ---- LoRA on a 3x3 conv (lora_conv.hip): the adapter arrives as peft's f32 tensors and is packed here by the trainer's own packer ----
+template <typename T>
+static int op_conv_lora_down_t(const void* x, int B, int H, int W, int cin, const float* A, int r, float* z, int route, hipStream_t st) {
+    DevBuf av, bdummy, scr;
+    TRY(av.reserve((size_t)r * 9 * cin * sizeof(T), false));
+    TRY(bdummy.reserve((size_t)r * sizeof(float), true));  // (a [1][r] B: the packer takes both tensors)
+    TRY(launch_conv_lora_pack<T>(A, static_cast<const float*>(bdummy.p), 1.0f, av.p, nullptr, nullptr, nullptr, cin, 1, r, st));
+    const size_t sb = conv_lora_down_scratch_bytes(B * H * W, cin, r, sizeof(T), route);
+    if (sb) TRY(scr.reserve(sb, false));
+    TRY(launch_conv_lora_down<T>(x, av.p, z, B, H, W, cin, r, static_cast<float*>(scr.p), st, route));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+template <typename T>
+static int op_conv_lora_dgrad_t(const float* dz, int B, int H, int W, int r, const float* A, int cin, void* dx, int accumulate, hipStream_t st) {
+    DevBuf av, bank, bdummy;
+    TRY(av.reserve((size_t)r * 9 * cin * sizeof(T), false));
+    if (sizeof(T) == 2) TRY(bank.reserve((size_t)cin * conv_lora_kpad(r) * 2, true));
+    TRY(bdummy.reserve((size_t)r * sizeof(float), true));
+    TRY(launch_conv_lora_pack<T>(A, static_cast<const float*>(bdummy.p), 1.0f, av.p, bank.p, nullptr, nullptr, cin, 1, r, st));
+    TRY(launch_conv_lora_dgrad<T>(dz, av.p, bank.p, dx, B, H, W, cin, r, accumulate, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+// conv3x3(x) + bias + rowvec[image] + s B conv3x3(x, A) + resid: the down-projection kernel, then the conv GEMM with the rank-r term in its
+// epilogue - the two launches of an adapted resnet conv (runner.h::conv_lora_z / conv3)
+template <typename T>
+static int op_conv3x3_lora_t(const mrisr_tensor* x, const float* w, const float* bias, const float* A, const float* Bm, int r, float scale,
+                             const float* rowvec, const mrisr_tensor* resid, int cout, int splitk, int tile, mrisr_tensor* y, hipStream_t st) {
+    const int B = (int)x->shape[0], Cin = (int)x->shape[1], H = (int)x->shape[2], W = (int)x->shape[3], M = B * H * W;
+    DevBuf wp, av, sb, zb, scr, part;
+    TRY(wp.reserve((size_t)cout * Cin * 9 * sizeof(T), false));
+    TRY(launch_pack_conv3x3<T>(w, wp.p, cout, Cin, 3, st));
+    TRY(av.reserve((size_t)r * 9 * Cin * sizeof(T), false));
+    TRY(sb.reserve((size_t)cout * r * sizeof(float), false));
+    TRY(zb.reserve((size_t)M * r * sizeof(float), false));
+    TRY(launch_conv_lora_pack<T>(A, Bm, scale, av.p, nullptr, static_cast<float*>(sb.p), nullptr, Cin, cout, r, st));
+    const size_t sbytes = conv_lora_down_scratch_bytes(M, Cin, r, sizeof(T));
+    if (sbytes) TRY(scr.reserve(sbytes, false));
+    TRY(launch_conv_lora_down<T>(x->data, av.p, static_cast<float*>(zb.p), B, H, W, Cin, r, static_cast<float*>(scr.p), st));
+    GemmArgs g;
+    g.a0 = x->data; g.c0 = Cin; g.lda0 = Cin;
+    g.conv = 1; g.B = B; g.Hin = H; g.Win = W; g.Hout = H; g.Wout = W;
+    g.w = wp.p; g.M = M; g.N = cout; g.K = 9 * Cin; g.bias = bias;
+    if (rowvec) { g.rowvec = rowvec; g.rowvec_ld = cout; g.rowvec_div = H * W; }
+    if (resid) { g.resid = resid->data; g.ldr = cout; }
+    g.out = y->data; g.ldo = cout;
+    g.lora_z = static_cast<const float*>(zb.p); g.lora_zld = r; g.lora_b = static_cast<const float*>(sb.p); g.lora_r = r; g.lora_secN = cout;
+    mrisr_debug_force_tile(tile);
+    g.splitk = splitk;
+    int rc = 0;
+    if (splitk <= 0) { g.splitk = 1; rc = gemm_choose(g, sizeof(T) == 2); }
+    else if (tile <= 0) { const int sk = splitk; rc = gemm_choose(g, sizeof(T) == 2); g.splitk = sk; }
+    if (!rc && g.splitk > 1) {
+        rc = part.reserve((size_t)g.splitk * g.M * g.N * sizeof(float), false);
+        g.partial = static_cast<float*>(part.p);
+    }
+    if (!rc) rc = launch_gemm<T>(g, st);
+    mrisr_debug_force_tile(0);
+    if (rc) return rc;
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 extern "C" {
 
 static int op_dtype_ok(const mrisr_tensor* x) {
@@ -839,6 +903,47 @@ int mrisr_op_conv_dgrad(int dtype, const void* dy, int B, int H, int W, int cout
     MRISR_REQUIRE(mode == 0 || (cout % bk == 0 && cin % 4 == 0), "strided dgrad of a tiny conv");
     MRISR_REQUIRE(al16(dy) && al16(dx), "conv dgrad: 16-byte aligned activations");
     return BWD_DISPATCH(dtype, op_conv_dgrad_t, dy, B, H, W, cout, w_oihw_dev, cin, mode, dx, accumulate, (hipStream_t)stream);
+    API_END
+}
+
+int mrisr_op_conv_lora_down(int dtype, const void* x_nhwc, int B, int H, int W, int cin, const float* a_dev, int r, float* z, int route,
+                            void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    MRISR_REQUIRE(x_nhwc && a_dev && z && B >= 1 && H >= 1 && W >= 1, "conv_lora_down: null / empty operand");
+    MRISR_REQUIRE(r >= 1 && r <= 16 && cin >= 1 && cin % (dtype == MRISR_F32 ? 4 : 8) == 0, "conv_lora_down: rank <= 16, channels in 16-byte pieces");
+    MRISR_REQUIRE(al16(x_nhwc) && al16(z) && (long long)B * H * W * std::max(cin, 16) < (1ll << 31), "conv_lora_down: alignment / extents");
+    return BWD_DISPATCH(dtype, op_conv_lora_down_t, x_nhwc, B, H, W, cin, a_dev, r, z, route, (hipStream_t)stream);
+    API_END
+}
+
+int mrisr_op_conv_lora_dgrad(int dtype, const float* dz, int B, int H, int W, int r, const float* a_dev, int cin, void* dx_nhwc, int accumulate,
+                             void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    MRISR_REQUIRE(dz && a_dev && dx_nhwc && B >= 1 && H >= 1 && W >= 1, "conv_lora_dgrad: null / empty operand");
+    MRISR_REQUIRE((r == 4 || r == 8 || r == 12 || r == 16) && cin >= 4 && cin % 4 == 0, "conv_lora_dgrad: rank 4 / 8 / 12 / 16, channels in fours");
+    MRISR_REQUIRE(al16(dz) && al16(dx_nhwc) && (long long)B * H * W * cin < (1ll << 31), "conv_lora_dgrad: alignment / extents");
+    return BWD_DISPATCH(dtype, op_conv_lora_dgrad_t, dz, B, H, W, r, a_dev, cin, dx_nhwc, accumulate, (hipStream_t)stream);
+    API_END
+}
+
+int mrisr_op_conv3x3_lora(const mrisr_tensor* x, const float* w_oihw_dev, const float* bias_dev, const float* a_dev, const float* b_dev, int r,
+                          float scale, const float* rowvec_dev, const mrisr_tensor* resid, int cout, int splitk, int tile, mrisr_tensor* y,
+                          void* stream) {
+    API_BEGIN
+    TRY(op_dtype_ok(x));
+    TRY(gemm_prepare());
+    MRISR_REQUIRE(w_oihw_dev && a_dev && b_dev && y, "conv3x3 + LoRA: null argument");
+    MRISR_REQUIRE(x->layout == MRISR_NHWC && y->layout == MRISR_NHWC && y->dtype == x->dtype && (!resid || (resid->layout == MRISR_NHWC && resid->dtype == x->dtype)),
+                  "NHWC in/out, same dtype");
+    MRISR_REQUIRE(y->shape[0] == x->shape[0] && y->shape[1] == cout && y->shape[2] == x->shape[2] && y->shape[3] == x->shape[3], "conv output shape");
+    MRISR_REQUIRE(!resid || (resid->shape[0] == y->shape[0] && resid->shape[1] == cout && resid->shape[2] == y->shape[2] && resid->shape[3] == y->shape[3]),
+                  "residual of the output's shape");
+    MRISR_REQUIRE(r >= 1 && r <= 16 && x->shape[1] % (x->dtype == MRISR_F32 ? 32 : 64) == 0 && cout % 4 == 0, "conv3x3 + LoRA: rank <= 16, whole K tiles");
+    hipStream_t st = (hipStream_t)stream;
+    return x->dtype == MRISR_F32 ? op_conv3x3_lora_t<float>(x, w_oihw_dev, bias_dev, a_dev, b_dev, r, scale, rowvec_dev, resid, cout, splitk, tile, y, st)
+                                 : op_conv3x3_lora_t<bf16>(x, w_oihw_dev, bias_dev, a_dev, b_dev, r, scale, rowvec_dev, resid, cout, splitk, tile, y, st);
     API_END
 }
 

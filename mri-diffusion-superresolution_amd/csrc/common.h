@@ -401,6 +401,21 @@ int launch_gemv_rows(const float* x, int ldx, const void* w, const float* bias, 
 // LoRA down-projection z[M][R] = x[M][K] . A[R][K]^T  (x, A of type T; z f32): one wave per row, memory-bound
 template <typename T>
 int launch_lora_down(const void* x, int ldx, const void* A, float* z, int M, int K, int R, hipStream_t st);
+// LoRA on a 3x3 conv (lora_conv.hip; stride 1, pad 1, NHWC): the down-projection z[m][q] = sum_{tap, ci} x[pix(m) + tap][ci] A[q][tap][ci]
+// (A = the Av view [R][ky][kx][cin] of T; z f32 [M][R], R <= 16; scratch: conv_lora_down_scratch_bytes(...) bytes, may be null when that is 0;
+// route 0 = planned, else 100 * waves per pixel group (1 / 4) + K slabs), its transposed conv dx[m][ci] (+)= sum_{tap, q} dz[pix(m) - tap][q]
+// A[q][tap][ci] (bf16: `bank` [cin][conv_lora_kpad(R)], dz rounded to bf16; otherwise the Av view), and the packer of the four device views
+// (bank / sB / sBT may be null)
+int conv_lora_kpad(int R);
+size_t conv_lora_down_scratch_bytes(int M, int cin, int R, int elem_size, int route = 0);
+template <typename T>
+int launch_conv_lora_down(const void* x, const void* A, float* z, int B, int H, int W, int cin, int R, float* scratch, hipStream_t st, int route = 0);
+template <typename T>
+int launch_conv_lora_dgrad(const float* dz, const void* A, const void* bank, void* dx, int B, int H, int W, int cin, int R, int accumulate,
+                           hipStream_t st);
+template <typename T>
+int launch_conv_lora_pack(const float* A, const float* Bm, float s, void* Av, void* bank, float* sB, void* sBT, int cin, int cout, int r, hipStream_t st);
+template <typename T> int launch_cast_rows(const float* src, void* dst, long long n, hipStream_t st);  // f32 -> T
 // sinusoidal timestep embedding [rows][dim] = [cos | sin], t from device int64 (scalar broadcast or [rows])
 int launch_timestep_embedding(const long long* t, int t_is_scalar, float* out, int rows, int dim, hipStream_t st);
 // out[j] = table[(*step - first) * n + j], j < n (the fused sampler's per-run time-embedding table)

@@ -118,7 +118,7 @@ struct Model {
     int set_cond(const mrisr_tensor* cond, int L, hipStream_t st);
 
     // ---- LoRA fine-tuning (train.hip) ----
-    struct Trainable { std::string key; long long offset, numel; int rows, cols; };
+    struct Trainable { std::string key; long long offset, numel; int rows, cols; int ndim = 2; long long shape[4] = {0, 0, 0, 0}; };  // (shape: 4-D conv adapters)
     std::vector<Trainable> trainables;   // lora_A / lora_B tensors in flat-vector order
     long long n_trainable = 0;
     float* theta = nullptr;              // caller-owned flat f32 parameter vector (bound)
@@ -148,6 +148,7 @@ struct Model {
                                  float scale, mrisr_tensor* down_out, int n_down, mrisr_tensor* mid_out, hipStream_t st);
     int controlnet_train_backward(const mrisr_tensor* d_down, int n_down, const mrisr_tensor* d_mid, float scale, hipStream_t st);
     std::vector<LinW*> lora_linears();   // every LinW that carries adapters, fixed order
+    std::vector<ConvW*> lora_convs();    // every resnet conv that carries an adapter: resnets in walk order, conv1 then conv2
     int train_prepare(hipStream_t st);   // dgrad weight copies + trainable layout (after finalize)
     int train_bind(float* theta_dev, float* grad_dev, hipStream_t st);
     int lora_refresh(hipStream_t st);    // re-pack the adapters from theta

@@ -86,7 +86,9 @@ struct Packer {
         if (n.g) n.c = (int)m.find(name + ".weight")->shape[0];
         return n;
     }
-    ConvW conv(const std::string& name) {
+    // lora_target (conv1 / conv2 of a UNet's ResnetBlock2D): a peft Conv2d adapter on the module is consumed - kept apart as the four views
+    // of lora_conv.hip (lora_fused), or folded into the f32 weight before packing (merged mode), as linear() does
+    ConvW conv(const std::string& name, bool lora_target = false) {
         ConvW c;
         const RawParam* w = need(name + ".weight");
         if (!w) return c;
@@ -96,8 +98,42 @@ struct Packer {
         c.ks = (int)w->shape[2];
         c.w = m.new_packed((size_t)w->numel() * sizeof(T), false);
         if (!c.w) { err = 4; return c; }
-        if (launch_pack_conv3x3<T>(static_cast<const float*>(w->data->p), c.w, c.cout, c.cin, c.ks, st)) err = 5;
+        const float* wsrc = static_cast<const float*>(w->data->p);
+        const RawParam* la = lora_target && !m.is_controlnet ? m.find(name + ".lora_A.default.weight") : nullptr;
+        const RawParam* lb = la ? m.find(name + ".lora_B.default.weight") : nullptr;
+        const bool fused_lora = m.cfg.lora_rank > 0 && m.cfg.lora_fused;
+        const int r = la ? (int)la->shape[0] : 0;
+        if (la && lb) {
+            if (c.ks != 3 || la->numel() != (int64_t)r * c.cin * 9 || lb->numel() != (int64_t)c.cout * r || (int)lb->shape[0] != c.cout) {
+                set_error("conv LoRA: lora_A [r, cin, 3, 3] / lora_B [cout, r, 1, 1] expected on " + name);
+                err = 6;
+                return c;
+            }
+        }
+        std::unique_ptr<DevBuf> merged;
+        if (la && lb && !fused_lora) {  // W' = W + s B A on [cout][cin * 9] (A's rows in the same [cin][3][3] order)
+            merged.reset(new DevBuf());
+            if (merged->reserve((size_t)w->numel() * sizeof(float), false)) { err = 4; return c; }
+            if (merge_lora(wsrc, static_cast<const float*>(la->data->p), static_cast<const float*>(lb->data->p), static_cast<float*>(merged->p), c.cout,
+                           c.cin * 9, r))
+                err = 6;
+            wsrc = static_cast<const float*>(merged->p);
+        }
+        if (launch_pack_conv3x3<T>(wsrc, c.w, c.cout, c.cin, c.ks, st)) err = 5;
+        if (merged) (void)hipStreamSynchronize(st);  // merged buffer dies at scope end
         c.b = m.find(name + ".bias") ? f32(name + ".bias") : nullptr;
+        if (la && lb && fused_lora) {
+            if (r % 4 != 0 || r > 16) { set_error("conv LoRA: rank 4 / 8 / 12 / 16: " + name); err = 6; return c; }
+            c.r = r;
+            c.loraA = m.new_packed((size_t)r * 9 * c.cin * sizeof(T), false);
+            if (sizeof(T) == 2) c.loraAd = m.new_packed((size_t)c.cin * conv_lora_kpad(r) * 2, true);
+            c.loraB = static_cast<float*>(m.new_packed((size_t)c.cout * r * sizeof(float), false));
+            c.loraBT = m.new_packed((size_t)r * c.cout * sizeof(T), false);
+            if (!c.loraA || (sizeof(T) == 2 && !c.loraAd) || !c.loraB || !c.loraBT) { err = 4; return c; }
+            if (launch_conv_lora_pack<T>(static_cast<const float*>(la->data->p), static_cast<const float*>(lb->data->p), m.lora_scale, c.loraA, c.loraAd,
+                                         c.loraB, c.loraBT, c.cin, c.cout, r, st))
+                err = 5;
+        }
         return c;
     }
     // 3x3 conv with its channel counts padded up to multiples of `quantum` (zero filter rows / columns, zero bias): a narrow
@@ -239,16 +275,17 @@ struct Packer {
     ResW resnet(const std::string& name) {
         ResW r;
         r.n1 = norm(name + ".norm1");
-        r.c1 = conv(name + ".conv1");
+        r.c1 = conv(name + ".conv1", true);
         r.n2 = norm(name + ".norm2");
-        r.c2 = conv(name + ".conv2");
+        r.c2 = conv(name + ".conv2", true);
         r.cin = r.c1.cin;
         r.cout = r.c1.cout;
         if (m.find(name + ".conv_shortcut.weight")) {
             r.has_sc = true;
             r.sc = linear({name + ".conv_shortcut"});
             // the fused bank (built from the packed bf16 weights: the same rounded values both forms multiply); channel counts that fill K tiles
-            if (sizeof(T) == 2 && !err && r.c2.w && r.sc.w && !r.sc.R && !r.sc.w8 && r.c2.b && r.sc.b && r.c2.ks == 3 && r.c2.cin == r.cout &&
+            // (a resnet with an un-merged conv adapter runs the literal sequence: no fused bank)
+            if (sizeof(T) == 2 && !err && !r.c1.r && !r.c2.r && r.c2.w && r.sc.w && !r.sc.R && !r.sc.w8 && r.c2.b && r.sc.b && r.c2.ks == 3 && r.c2.cin == r.cout &&
                 r.sc.k == r.cin && r.sc.n == r.cout && r.cin % 64 == 0 && r.cout % 64 == 0) {
                 const size_t k2 = (size_t)9 * r.cout, kt = k2 + r.cin;
                 r.c2sc = m.new_packed((size_t)r.cout * kt * sizeof(T), false);

@@ -77,8 +77,9 @@ struct Runner {
     }
 
     // 3x3 conv (pad 1) over NHWC, optional second concat source, stride, nearest-x2 upsample of the input
+    // lz: the down-projection z of the conv's LoRA adapter (conv_lora_z): s B z joins in the epilogue
     int conv3(const Act& x, const Act* x1, const ConvW& cw, int stride, int ups, const float* rowvec, int rowvec_ld,
-              int rowvec_div, const Act* resid, int act, Act* out) {
+              int rowvec_div, const Act* resid, int act, Act* out, const float* lz = nullptr) {
         const int Cin = x.C + (x1 ? x1->C : 0);
         MRISR_REQUIRE(cw.cin == Cin && cw.ks == 3, "conv3x3 weight mismatch");
         const int Hc = x.H << ups, Wc = x.W << ups;
@@ -93,7 +94,22 @@ struct Runner {
         g.bias = cw.b; g.rowvec = rowvec; g.rowvec_ld = rowvec_ld; g.rowvec_div = rowvec_div; g.act = act;
         if (resid) { g.resid = resid->p; g.ldr = resid->C; }
         g.out = out->p; g.ldo = cw.cout;
+        if (lz) lora_epilogue(g, cw, lz);
         return run_gemm(g);
+    }
+    static void lora_epilogue(GemmArgs& g, const ConvW& cw, const float* z) {
+        g.lora_z = z; g.lora_zld = cw.r; g.lora_b = cw.loraB; g.lora_r = cw.r; g.lora_secN = cw.cout;
+    }
+    // z [M][r] f32 = conv3x3(x, lora_A) of an adapted conv (lora_conv.hip): stays allocated for the conv's epilogue (training: the backward)
+    int conv_lora_z(const Act& x, const ConvW& cw, float** z) {
+        MRISR_REQUIRE(cw.r && cw.loraA && cw.loraB && x.C == cw.cin, "conv LoRA: adapter views");
+        const int M = (int)x.rows();
+        *z = static_cast<float*>(alloc((size_t)M * cw.r * sizeof(float)));
+        const size_t sb = conv_lora_down_scratch_bytes(M, x.C, cw.r, (int)sizeof(T));
+        float* scr = sb ? static_cast<float*>(alloc(sb)) : nullptr;
+        if (!*z || (sb && !scr)) return 7;
+        if (dry) return 0;
+        return launch_conv_lora_down<T>(x.p, cw.loraA, *z, x.B, x.H, x.W, x.C, cw.r, scr, st);
     }
 
     // conv3x3 whose only consumer is a GroupNorm (+ SiLU): when the autotuner splits K for it, the f32 slabs are summed by the GroupNorm
@@ -248,6 +264,42 @@ struct Runner {
     }
 
     // ---- ResnetBlock2D (App. A.3) ----
+    // The literal sequence - GroupNorm, conv1 (+ time embedding), GroupNorm, shortcut GEMM, conv2 + residual - into `o`, every intermediate
+    // handed back: the training forward (train.hip::resnet_t keeps them for its tape) and the inference path of a resnet whose conv1 / conv2
+    // carry un-merged LoRA adapters (z1 / z2: their down-projections; the rank-r terms join in the convs' epilogues).
+    struct ResTape {
+        Act xn, h, hn;
+        float *p1 = nullptr, *p2 = nullptr;
+        int ns1 = 1, ns2 = 1;
+        float *z1 = nullptr, *z2 = nullptr;
+    };
+    int resnet_literal(const ResW& r, const Act& x, const Act* x1, const Act& o, ResTape* t) {
+        TRY(gn(x, x1, r.n1, true, m.cfg.norm_eps, &t->xn, &t->p1, &t->ns1));
+        const int div = m.t_scalar ? INT_MAX : x.H * x.W;
+        if (r.c1.r) TRY(conv_lora_z(t->xn, r.c1, &t->z1));
+        TRY(conv3(t->xn, nullptr, r.c1, 1, 0, m.tproj_out + r.temb_off, m.tproj_total, div, nullptr, ACT_NONE, &t->h, t->z1));
+        TRY(gn(t->h, nullptr, r.n2, true, m.cfg.norm_eps, &t->hn, &t->p2, &t->ns2));
+        Act res = x;
+        if (r.has_sc) {
+            GemmArgs g;
+            if (x1) { g.a1 = x1->p; g.c1 = x1->C; g.lda1 = x1->C; }
+            g.a0 = x.p; g.c0 = x.C; g.lda0 = x.C;
+            g.w = r.sc.w; g.M = (int)x.rows(); g.N = r.cout; g.K = r.cin; g.bias = r.sc.b; g.out = o.p; g.ldo = r.cout;
+            TRY(run_gemm(g));
+            res = o;
+        } else {
+            MRISR_REQUIRE(!x1, "concat input requires a shortcut conv");
+        }
+        if (r.c2.r) TRY(conv_lora_z(t->hn, r.c2, &t->z2));
+        GemmArgs g;
+        g.a0 = t->hn.p; g.c0 = t->hn.C; g.lda0 = t->hn.C;
+        g.conv = 1; g.B = x.B; g.Hin = x.H; g.Win = x.W; g.Hout = x.H; g.Wout = x.W;
+        g.w = r.c2.w; g.M = (int)x.rows(); g.N = r.cout; g.K = 9 * r.cout; g.bias = r.c2.b;
+        g.resid = res.p; g.ldr = r.cout; g.out = o.p; g.ldo = r.cout;
+        if (t->z2) lora_epilogue(g, r.c2, t->z2);
+        return run_gemm(g);
+    }
+
     // next / next_out: the GroupNorm of the block that consumes this resnet's output and nothing else in between (the transformer's norm).
     // When conv2 is K-split, its slabs are summed by that GroupNorm's kernel (launch_groupnorm_slabs: + bias + residual, the raw output
     // stored as well) and next_out receives the normalised tensor; otherwise next_out->p stays null and the consumer normalises itself.
@@ -255,6 +307,14 @@ struct Runner {
         Act o = new_act(x.B, x.H, x.W, r.cout);  // allocated first: survives the temporaries below
         if (!o.p) return 7;
         if (next_out) next_out->p = nullptr;
+        if (r.c1.r || r.c2.r) {  // un-merged conv adapters: no tenth-tap fold, no slab-summing GroupNorm (the slab reduce has no LoRA term)
+            const size_t mk0 = m.arena.mark();
+            ResTape t;
+            TRY(resnet_literal(r, x, x1, o, &t));
+            if (!m.keep) m.arena.release(mk0);
+            *out = o;
+            return 0;
+        }
         GemmArgs g2;  // conv2, planned before anything else is allocated: whether the fused form applies decides what must outlive this block
         bool fuse2 = false;
         GroupNormArgs a2;

@@ -74,6 +74,14 @@ struct ConvW {  // packed [cout][ks*ks*cin] in compute dtype, bias f32
     std::string name;    // state-dict module name (the dgrad packer re-reads the raw f32 weight)
     void* wd = nullptr;  // training: dgrad filter bank [cin][ky'][kx'][cout] (taps flipped; 1x1: W^T [cin][cout]), compute dtype
     long long offW = -1, offB = -1;  // training (T2I-Adapter): offsets of weight / bias in the flat trainable vector
+    // LoRA (peft lora.Conv2d on a resnet's conv1 / conv2; lora_conv.hip): the rank and the device views of lora_A [r][cin][3][3] and
+    // lora_B [cout][r][1][1], B already scaled by lora_alpha / r
+    int r = 0;
+    void* loraA = nullptr;    // [r][ky][kx][cin] compute dtype: the down-projection z = conv3x3(x, A)
+    void* loraAd = nullptr;   // bf16 engine: the tap-flipped dgrad bank [cin][conv_lora_kpad(r)]
+    float* loraB = nullptr;   // f32 [cout][r]: the conv's epilogue (GemmArgs::lora_b)
+    void* loraBT = nullptr;   // [r][cout] compute dtype: dz = dY (s B) through launch_lora_down
+    long long offLA = -1, offLB = -1;  // training: offsets of lora_A / lora_B in the flat trainable vector
 };
 struct LinW {  // packed [n][k] in compute dtype, bias f32 (GEGLU: interleaved)
     void* w = nullptr;

@@ -68,6 +68,15 @@ std::vector<LinW*> Model::lora_linears() {
     return v;
 }
 
+std::vector<ConvW*> Model::lora_convs() {
+    std::vector<ConvW*> v;
+    for_each_res(*this, [&](ResW& r) {
+        if (r.c1.r) v.push_back(&r.c1);
+        if (r.c2.r) v.push_back(&r.c2);
+    });
+    return v;
+}
+
 // the backward's copies of one layer's weights (both prepare functions below); err keeps the last failure
 // wd[ci][ky][kx][co] = w[co][ci][2-ky][2-kx]: the dgrad of a 3x3 conv is a 3x3 conv of dY with this bank
 template <typename T>
@@ -131,6 +140,20 @@ static int train_prepare_t(Model& m, hipStream_t st) {
             if (!l->loraBT || !l->loraAT) return 4;
         }
     }
+    // conv adapters follow ALL linear adapters (whose offsets are therefore the same with and without them): resnets in walk order,
+    // conv1 A, B, then conv2 A, B; tensors in PyTorch's 4-D shapes
+    for (ConvW* c : m.lora_convs()) {
+        Model::Trainable ta{c->name + ".lora_A.default.weight", off, (long long)c->r * c->cin * 9, c->r, c->cin * 9};
+        ta.ndim = 4; ta.shape[0] = c->r; ta.shape[1] = c->cin; ta.shape[2] = 3; ta.shape[3] = 3;
+        c->offLA = off;
+        m.trainables.push_back(ta);
+        off += ta.numel;
+        Model::Trainable tb{c->name + ".lora_B.default.weight", off, (long long)c->cout * c->r, c->cout, c->r};
+        tb.ndim = 4; tb.shape[0] = c->cout; tb.shape[1] = c->r; tb.shape[2] = 1; tb.shape[3] = 1;
+        c->offLB = off;
+        m.trainables.push_back(tb);
+        off += tb.numel;
+    }
     m.n_trainable = off;
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     m.train_ready = true;
@@ -174,6 +197,12 @@ int Model::lora_refresh(hipStream_t st) {
         }
         // the fp8 copy of the adapters' A rows (inference through the fp8 projections after training steps)
         if (l->loraA8 && cfg.compute_dtype != MRISR_F32) TRY(launch_quant_rows_fp8(l->loraA, l->R, l->k, l->loraA8, l->loraA_scale, st));
+    }
+    for (ConvW* c : lora_convs()) {
+        const float* A = theta + c->offLA;
+        const float* B = theta + c->offLB;
+        if (cfg.compute_dtype == MRISR_F32) TRY(launch_conv_lora_pack<float>(A, B, lora_scale, c->loraA, c->loraAd, c->loraB, c->loraBT, c->cin, c->cout, c->r, st));
+        else TRY(launch_conv_lora_pack<bf16>(A, B, lora_scale, c->loraA, c->loraAd, c->loraB, c->loraBT, c->cin, c->cout, c->r, st));
     }
     MRISR_CHECK_HIP(hipGetLastError());
     ctx_valid = false;  // cached cross-attention K / V depend on attn2.to_k / to_v adapters
@@ -535,38 +564,40 @@ struct Trainer : Runner<T> {
     // ---------------------------------------------------------------------------------------------
     // ResnetBlock2D
     // ---------------------------------------------------------------------------------------------
+    // backward of the adapter of one 3x3 conv, y = conv(x, W) + s B conv3x3(x, A):  dz = dY (s B);  dB = s dY^T z and dA = the weight gradient of
+    // the r-channel conv (dz as its dY) into m.grad;  dX += the transposed conv of dz (dX holds the base conv's dgrad already; null: not needed)
+    int conv_lora_bwd(const ConvW& cw, const Act& x, const float* z, const void* dY, void* dX) {
+        const int M = (int)x.rows(), R = cw.r;
+        MRISR_REQUIRE(z && cw.loraBT && cw.loraA && m.grad && cw.offLA >= 0 && cw.offLB >= 0 && x.C == cw.cin, "conv adapter backward state");
+        const size_t mk = m.arena.mark();
+        float* dz = static_cast<float*>(alloc((size_t)M * R * sizeof(float)));
+        float* scratch = static_cast<float*>(alloc(lora_wgrad_scratch_bytes(M, cw.cout, R, sizeof(T))));
+        void* dzT = sizeof(T) == 4 ? static_cast<void*>(dz) : alloc((size_t)M * R * sizeof(T));
+        if (!dz || !scratch || !dzT) return 7;
+        if (!dry) {
+            TRY(launch_lora_down<T>(dY, cw.cout, cw.loraBT, dz, M, cw.cout, R, st));
+            float* oB[3] = {m.grad + cw.offLB, nullptr, nullptr};
+            TRY(launch_lora_wgrad<T>(dY, cw.cout, z, R, M, cw.cout, 0, R, 1, cw.cout, oB, m.lora_scale, scratch, st));
+            if (sizeof(T) == 2) TRY(launch_cast_rows<T>(dz, dzT, (long long)M * R, st));
+        }
+        TRY(wgrad(x.p, x.B, x.H, x.W, x.C, dzT, R, 0, x.H, x.W, R, 3, 1, m.grad + cw.offLA, nullptr, R, x.C));
+        if (dX && !dry) TRY(launch_conv_lora_dgrad<T>(dz, cw.loraA, cw.loraAd, dX, x.B, x.H, x.W, x.C, R, 1, st));
+        m.arena.release(mk);
+        return 0;
+    }
+
     int resnet_t(const ResW& r, const Act& x, const Act* x1, Act* out) {
         Act o = new_act(x.B, x.H, x.W, r.cout);
         if (!o.p) return 7;
-        Act xn, h, hn;
-        float *p1 = nullptr, *p2 = nullptr;
-        int ns1 = 1, ns2 = 1;
-        TRY(R::gn(x, x1, r.n1, true, m.cfg.norm_eps, &xn, &p1, &ns1));
-        const int div = m.t_scalar ? INT_MAX : x.H * x.W;
-        TRY(R::conv3(xn, nullptr, r.c1, 1, 0, m.tproj_out + r.temb_off, m.tproj_total, div, nullptr, ACT_NONE, &h));
-        TRY(R::gn(h, nullptr, r.n2, true, m.cfg.norm_eps, &hn, &p2, &ns2));
-        Act res = x;
-        if (r.has_sc) {
-            GemmArgs g;
-            if (x1) { g.a1 = x1->p; g.c1 = x1->C; g.lda1 = x1->C; }
-            g.a0 = x.p; g.c0 = x.C; g.lda0 = x.C;
-            g.w = r.sc.w; g.M = (int)x.rows(); g.N = r.cout; g.K = r.cin; g.bias = r.sc.b; g.out = o.p; g.ldo = r.cout;
-            TRY(R::run_gemm(g));
-            res = o;
-        } else {
-            MRISR_REQUIRE(!x1, "concat input requires a shortcut conv");
-        }
-        {
-            GemmArgs g;
-            g.a0 = hn.p; g.c0 = hn.C; g.lda0 = hn.C;
-            g.conv = 1; g.B = x.B; g.Hin = x.H; g.Win = x.W; g.Hout = x.H; g.Wout = x.W;
-            g.w = r.c2.w; g.M = (int)x.rows(); g.N = r.cout; g.K = 9 * r.cout; g.bias = r.c2.b;
-            g.resid = res.p; g.ldr = r.cout; g.out = o.p; g.ldo = r.cout;
-            TRY(R::run_gemm(g));
-        }
+        typename R::ResTape ft;
+        TRY(R::resnet_literal(r, x, x1, o, &ft));
+        const Act xn = ft.xn, h = ft.h, hn = ft.hn;
+        float *p1 = ft.p1, *p2 = ft.p2, *z1 = ft.z1, *z2 = ft.z2;
+        const int ns1 = ft.ns1, ns2 = ft.ns2;
         *out = o;
-        const bool lv = is_live(x) || (x1 && is_live(*x1));
-        if (!lv) return 0;  // nothing trainable upstream: the block has no backward
+        // an adapter makes the block live even when its input is not (the first resnet after conv_in): weight gradients only, then
+        const bool x_live = is_live(x) || (x1 && is_live(*x1));
+        if (!x_live && !r.c1.r && !r.c2.r) return 0;  // nothing trainable upstream or inside: the block has no backward
         live.insert(o.p);
         const bool has_x1 = x1 != nullptr;
         const Act x1v = x1 ? *x1 : Act();
@@ -576,14 +607,20 @@ struct Trainer : Runner<T> {
             auto it = slots.find(o.p);
             MRISR_REQUIRE(it != slots.end() && it->second.written, "resnet output has no gradient");
             void* dO = it->second.g;
-            Slot& s0 = slot(x);
-            Slot* s1 = has_x1 ? &slot(x1v) : nullptr;
+            Slot* s0 = x_live ? &slot(x) : nullptr;
+            Slot* s1 = x_live && has_x1 ? &slot(x1v) : nullptr;
             const size_t mk = m.arena.mark();
             Act dOa = o; dOa.p = dO;
-            Act dhn = new_act(o.B, o.H, o.W, rr.cout), dh = new_act(o.B, o.H, o.W, rr.cout), dxn = new_act(o.B, o.H, o.W, rr.cin);
-            if (!dhn.p || !dh.p || !dxn.p) return 7;
+            if (!x_live && !rr.c1.r) {  // only conv2 is adapted and nothing upstream wants dX: its weight gradients alone
+                TRY(conv_lora_bwd(rr.c2, hn, z2, dO, nullptr));
+                m.arena.release(mk);
+                return 0;
+            }
+            Act dhn = new_act(o.B, o.H, o.W, rr.cout), dh = new_act(o.B, o.H, o.W, rr.cout);
+            if (!dhn.p || !dh.p) return 7;
             TRY(wgrad_conv(hn, dOa, rr.c2, 1));
             TRY(conv_dgrad(dOa, rr.c2, 0, dhn.p, false));
+            if (rr.c2.r) TRY(conv_lora_bwd(rr.c2, hn, z2, dO, dhn.p));
             TRY(gn_affine(h, dhn.p, rr.n2, true, m.cfg.norm_eps, p2, ns2));
             TRY(gn_bwd(h, nullptr, rr.n2, true, m.cfg.norm_eps, p2, ns2, dhn.p, dh.p, false, nullptr, false));
             if (full() && m.d_tproj && !dry)  // h = conv1(.) + time_emb_proj(silu(emb))[:, :, None, None]: its gradient is the per-image sum of dh
@@ -593,11 +630,19 @@ struct Trainer : Runner<T> {
                 MRISR_REQUIRE(!has_x1, "full-parameter training: single-source shortcut");
                 TRY(wgrad_linear(rr.sc, x.p, x.C, dO, rr.cout, (int)x.rows()));
             }
+            if (!x_live) {  // conv1's adapter gradients and nothing beyond the block
+                TRY(conv_lora_bwd(rr.c1, xn, z1, dh.p, nullptr));
+                m.arena.release(mk);
+                return 0;
+            }
+            Act dxn = new_act(o.B, o.H, o.W, rr.cin);
+            if (!dxn.p) return 7;
             TRY(conv_dgrad(dh, rr.c1, 0, dxn.p, false));
+            if (rr.c1.r) TRY(conv_lora_bwd(rr.c1, xn, z1, dh.p, dxn.p));
             if (!has_x1) TRY(gn_affine(x, dxn.p, rr.n1, true, m.cfg.norm_eps, p1, ns1));
-            TRY(gn_bwd(x, has_x1 ? &x1v : nullptr, rr.n1, true, m.cfg.norm_eps, p1, ns1, dxn.p, s0.g, s0.written,
+            TRY(gn_bwd(x, has_x1 ? &x1v : nullptr, rr.n1, true, m.cfg.norm_eps, p1, ns1, dxn.p, s0->g, s0->written,
                        s1 ? s1->g : nullptr, s1 ? s1->written : false));
-            s0.written = true;
+            s0->written = true;
             if (s1) s1->written = true;
             if (rr.has_sc) {
                 // 1x1 shortcut over the concatenated input: one dgrad GEMM per source, accumulated in place
@@ -605,7 +650,7 @@ struct Trainer : Runner<T> {
                 MRISR_REQUIRE(wT, "shortcut dgrad weights");
                 GemmArgs g;
                 g.a0 = dO; g.c0 = rr.cout; g.lda0 = rr.cout; g.w = wT; g.M = (int)x.rows(); g.N = x.C; g.K = rr.cout;
-                g.resid = s0.g; g.ldr = x.C; g.out = s0.g; g.ldo = x.C;
+                g.resid = s0->g; g.ldr = x.C; g.out = s0->g; g.ldo = x.C;
                 TRY(R::run_gemm(g));
                 if (s1) {
                     GemmArgs g1;
@@ -614,7 +659,7 @@ struct Trainer : Runner<T> {
                     TRY(R::run_gemm(g1));
                 }
             } else if (!dry) {
-                TRY(launch_add_inplace<T>(s0.g, dO, (long long)x.numel(), st));
+                TRY(launch_add_inplace<T>(s0->g, dO, (long long)x.numel(), st));
             }
             m.arena.release(mk);
             return 0;

@@ -309,3 +309,41 @@ def conv_dgrad(dy, weight, stride=1, dx=None, acc=False):
         dx = torch.empty((B, H << max(mode, 0), W << max(mode, 0), cin), dtype=dy.dtype, device=dy.device)
     L.check(L.lib().mrisr_op_conv_dgrad(_dt(dy), _p(dy), B, H, W, cout, _p(weight), cin, mode, _p(dx), 1 if acc else 0, L.stream_ptr()))
     return dx
+
+
+def conv_lora_down(x, A, route=0):
+    """x NHWC [B,H,W,cin] (f32 / bf16), A = lora_A [r,cin,3,3] -> z [B*H*W, r] f32 = conv3x3(x, A) (stride 1, pad 1).  ``route``: 0 planned,
+    else 100 * (waves per pixel group: 1 or 4) + K slabs."""
+    B, H, W, cin = x.shape
+    a = A.detach().to(torch.float32).contiguous()
+    z = torch.empty((B * H * W, a.shape[0]), dtype=torch.float32, device=x.device)
+    L.check(L.lib().mrisr_op_conv_lora_down(_dt(x), _p(x), B, H, W, cin, _p(a), a.shape[0], _p(z), route, L.stream_ptr()))
+    return z
+
+
+def conv_lora_dgrad(dz, A, B, H, W, dtype=torch.float32, dx=None, acc=False):
+    """dz [B*H*W, r] f32, A = lora_A [r,cin,3,3] -> dx NHWC [B,H,W,cin]: the transposed conv of dz (added into a given ``dx`` with ``acc``)."""
+    a = A.detach().to(torch.float32).contiguous()
+    r, cin = a.shape[0], a.shape[1]
+    if dx is None:
+        dx = torch.empty((B, H, W, cin), dtype=dtype, device=dz.device)
+    L.check(L.lib().mrisr_op_conv_lora_dgrad(_dt(dx), _p(dz), B, H, W, r, _p(a), cin, _p(dx), 1 if acc else 0, L.stream_ptr()))
+    return dx
+
+
+def conv3x3_lora(x, weight, bias, A, Bm, scale, rowvec=None, resid=None, splitk=0, tile=0):
+    """conv3x3(x, weight) + bias + rowvec[b, :, None, None] + scale * lora_B(lora_A(x)) + resid on NCHW x (f32 / bf16): the conv with the
+    adapter's rank-r term in its epilogue.  A [r,cin,3,3], Bm [cout,r,1,1], rowvec [B,cout] f32."""
+    xb, tx = _nhwc(x)
+    tr = None
+    if resid is not None:
+        rb, tr = _nhwc(resid)
+    f = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
+    w, b, a, bm, rv = f(weight), f(bias), f(A), f(Bm), f(rowvec)
+    Bn, _, H, W = x.shape
+    cout = w.shape[0]
+    yb = torch.empty((Bn, H, W, cout), dtype=x.dtype, device=x.device)
+    ty = L.as_tensor(yb, L.MRISR_NHWC, shape=(Bn, cout, H, W))
+    L.check(L.lib().mrisr_op_conv3x3_lora(C.byref(tx), _p(w), _p(b), _p(a), _p(bm), a.shape[0], float(scale), _p(rv),
+                                          C.byref(tr) if tr is not None else None, cout, splitk, tile, C.byref(ty), L.stream_ptr()))
+    return yb.permute(0, 3, 1, 2)

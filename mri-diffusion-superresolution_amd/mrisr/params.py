@@ -161,6 +161,19 @@ def lora_ff_param_shapes(cfg: UNetConfig, rank: int) -> Iterator[Tuple[str, Shap
             yield mod + ".lora_B.default.weight", (shape[0], rank), -2
 
 
+LORA_CONV_TARGETS = ("conv1", "conv2")
+
+
+def lora_conv_param_shapes(cfg: UNetConfig, rank: int) -> Iterator[Tuple[str, Shape, int]]:
+    """peft Conv2d-LoRA keys for conv1 / conv2 of every ResnetBlock2D: ``lora_A`` [r, cin, 3, 3] (a 3x3 conv, stride 1, pad 1, no bias),
+    ``lora_B`` [cout, r, 1, 1] (a 1x1 conv, no bias)."""
+    for key, shape, _ in unet_param_shapes(cfg):
+        if ".resnets." in key and key.endswith(".weight") and key[: -len(".weight")].endswith(LORA_CONV_TARGETS):
+            mod = key[: -len(".weight")]
+            yield mod + ".lora_A.default.weight", (rank, shape[1], 3, 3), shape[1] * 9
+            yield mod + ".lora_B.default.weight", (shape[0], rank, 1, 1), -2
+
+
 def random_state_dict(shapes, seed: int, device="cuda", lora_B_std: float = 0.02) -> Dict[str, torch.Tensor]:
     g = torch.Generator(device=device).manual_seed(seed)
     out = {}

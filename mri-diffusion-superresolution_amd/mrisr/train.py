@@ -198,11 +198,15 @@ class LoRATrainer(_FlatAdamW):
         dev = unet.device
         self._init_flat(n, dev, lr, betas, weight_decay, eps, max_grad_norm, process_group)
         self._loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.layout: List[Tuple[str, int, Tuple[int, int]]] = []
+        # (key, offset, PyTorch shape): 2-D for the linears' adapters, 4-D ([r, cin, 3, 3] / [cout, r, 1, 1]) for the resnet convs', which
+        # follow all the linear ones
+        self.layout: List[Tuple[str, int, Tuple[int, ...]]] = []
         for i in range(int(lib.mrisr_train_num_tensors(unet._h))):
             key, off, shp = C.c_char_p(), C.c_int64(), (C.c_int64 * 2)()
             L.check(lib.mrisr_train_tensor_info(unet._h, i, C.byref(key), C.byref(off), shp))
-            self.layout.append((key.value.decode(), int(off.value), (int(shp[0]), int(shp[1]))))
+            shp4, nd = (C.c_int64 * 4)(), C.c_int()
+            L.check(lib.mrisr_train_tensor_shape(unet._h, i, shp4, C.byref(nd)))
+            self.layout.append((key.value.decode(), int(off.value), tuple(int(shp4[k]) for k in range(nd.value))))
         L.check(lib.mrisr_train_bind(unet._h, C.c_void_p(self.theta.data_ptr()), C.c_void_p(self.grad.data_ptr()), 1,
                                      L.stream_ptr()))
         import weakref
@@ -210,7 +214,7 @@ class LoRATrainer(_FlatAdamW):
 
     # ---- views ----
     def _views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        return {k: flat[o:o + r * c].view(r, c) for k, o, (r, c) in self.layout}
+        return {k: flat[o:o + math.prod(shp)].view(*shp) for k, o, shp in self.layout}
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The adapters under their peft keys (what ``unet.save_attn_procs`` / ``get_peft_model_state_dict`` would hold)."""
@@ -223,8 +227,20 @@ class LoRATrainer(_FlatAdamW):
         views = self._views(self.theta)
         for k, v in lora_keys_from_disk(sd).items():
             if k in views:
+                if tuple(v.shape) != tuple(views[k].shape):
+                    raise ValueError(f"{k}: shape {tuple(v.shape)}, the trainable tensor is {tuple(views[k].shape)}")
                 views[k].copy_(v.to(self.theta.device, torch.float32))
         L.check(L.lib().mrisr_train_refresh(self.unet._h, L.stream_ptr()))
+
+    def load_checkpoint(self, path: str):
+        """As ``_FlatAdamW.load_checkpoint``; a checkpoint whose adapter set is not this trainer's (tensors this handle does not train,
+        e.g. conv adapters saved by a run that had them) is refused, like a changed bucket."""
+        from safetensors.torch import load_file
+        views = self._views(self.theta)
+        extra = [k for k in lora_keys_from_disk(load_file(path)) if ".lora_" in k and k not in views]
+        if extra:
+            raise ValueError(f"checkpoint {path} holds {len(extra)} adapter tensors this run does not train, e.g. {extra[0]}")
+        super().load_checkpoint(path)
 
     # ---- the step, in the reference's order ----
     def forward_backward(self, noisy_latents: torch.Tensor, timesteps, encoder_hidden_states: torch.Tensor,

@@ -3,7 +3,7 @@
 SD-1.5 UNet + r=4 LoRA, [B,4,32,32] latents, forward + MSE + backward + all-reduce(flat LoRA grads) + clip + AdamW.
 Not the headline metric (bench.py is) - a secondary line for DESIGN.md.
 
-  python tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--dtype bf16] [--profile] [--lora-ff]
+  python tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--dtype bf16] [--profile] [--lora-ff] [--lora-conv]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py --gpus N
 """
 import argparse
@@ -55,6 +55,8 @@ def main():
                                                        "(fp8_train), backward in bf16")
     ap.add_argument("--lora-ff", action="store_true", help="rank-4 adapters on ff.net.0.proj and ff.net.2 as well (the attention + feed-forward "
                                                            "target set)")
+    ap.add_argument("--lora-conv", action="store_true", help="rank-4 adapters on conv1 / conv2 of all 22 resnets as well (the attention + resnet-conv "
+                                                             "target set; with --lora-ff: attention + feed-forward + resnet convs)")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -75,6 +77,8 @@ def main():
     sd.update(P.random_state_dict(P.lora_param_shapes(cfg, 4), 20260504, dev))
     if args.lora_ff:
         sd.update(P.random_state_dict(P.lora_ff_param_shapes(cfg, 4), 20260505, dev))
+    if args.lora_conv:
+        sd.update(P.random_state_dict(P.lora_conv_param_shapes(cfg, 4), 20260508, dev))
     f8 = dict(fp8=True, fp8_attention=True, fp8_train=True) if args.fp8 else {}
     if args.train_controlnet:
         sd = P.random_state_dict(P.unet_param_shapes(cfg), 20260501, dev)
@@ -142,7 +146,7 @@ def main():
            "workspace_GiB": round(unet.workspace_bytes / 2**30, 2),
            "config": {"workload": f"SD-1.5 UNet + LoRA r=4 fine-tune step, [{B},4,{h},{h}] per GPU, all-reduce of "
                                   f"{tr.num_trainable} f32 grads" + (f" + trainable Adapter_XL ({atr.num_trainable} f32 grads)" if atr else "") + (f"; TRAINABLE ControlNet ({ctr.num_trainable} f32 grads), UNet frozen" if ctr else ""),
-                      "adapter_features": bool(intra), "adapter_trained": atr is not None, "lora_ff": bool(args.lora_ff)}}
+                      "adapter_features": bool(intra), "adapter_trained": atr is not None, "lora_ff": bool(args.lora_ff), "lora_conv": bool(args.lora_conv)}}
     if args.profile and rank == 0:
         lib = L.lib()
         lib.mrisr_prof_reset()

@@ -108,6 +108,20 @@ int mrisr_model_num_skips(const mrisr_model* m);
 /* shape {B,C,H,W} of skip k for a latent of h x w (k == num_skips -> the mid block tensor) */
 int mrisr_model_skip_shape(const mrisr_model* m, int k, int B, int h, int w, int64_t shape[4]);
 
+/* ---- feature cache (DeepCache, Ma et al. 2023): one forward ------------------------------------- */
+/* The encoder hands the decoder the skips s_0 .. s_{n-1} (n = mrisr_model_num_skips); decoder stage q = 0 .. n-1 (one up-block
+ * resnet + its transformer) consumes s_{n-1-q}.  For 1 <= depth <= n-1 the cache is the input x of stage n-1-depth: the tensor
+ * concatenated with s_depth, after any upsampler conv before that stage.  shape {B,C,H,W} of it for a latent of h x w: */
+int mrisr_unet_cache_shape(const mrisr_model* m, int depth, int B, int h, int w, int64_t shape[4]);
+/* mrisr_unet_forward without ControlNet residuals, with `cache`: a caller tensor of exactly mrisr_unet_cache_shape, layout NHWC, the
+ * compute dtype.  shallow == 0: the ordinary forward, which also WRITES cache.  shallow == 1: READS it - time embedding, conv_in and
+ * the encoder up to the producer of s_depth (adapter features that land in s_0 .. s_depth are added, deeper ones ignored), no mid
+ * block, decoder stages n-1-depth .. n-1 starting from cache, conv_norm_out, conv_out.  A shallow forward fed the cache of a full
+ * forward of the same (sample, timestep, ehs) reproduces its output. */
+int mrisr_unet_forward_cached(mrisr_model* m, const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,
+                              const mrisr_tensor* intrablock, int n_intrablock, int depth, int shallow, mrisr_tensor* cache,
+                              mrisr_tensor* out, void* stream);
+
 /* ---- ControlNetModel.forward ------------------------------------------------------------------- */
 /* cond [B,3,8h,8w] or NULL to reuse the cached condition embedding; down_out: n_skips tensors, mid_out: 1. */
 int mrisr_controlnet_forward(mrisr_model* m, const mrisr_tensor* sample, const mrisr_tensor* timestep,
@@ -170,6 +184,13 @@ int mrisr_sampler_set_range(mrisr_sampler* s, int first_step, int last_step);
 /* DDPM only: clip the predicted x0 to [-range, range] (diffusers clip_sample / clip_sample_range); range <= 0 disables
  * (the default, as in the SD-1.5 scheduler config). */
 int mrisr_sampler_set_clip(mrisr_sampler* s, float clip_sample_range);
+/* Feature cache for the next runs (default: interval 1 = none; the step graph is then the one without it).  With interval N > 1,
+ * step i of a run over [first_step, last_step) is a full forward that stores the cache when (i - first_step) % N == 0 and a shallow
+ * forward that reads it otherwise (mrisr_unet_forward_cached), so the first step of every run is full and no run reads an earlier
+ * run's cache.  The sampler owns the buffer (2B rows in a guided run) and keeps two step graphs.  depth: 1 .. num_skips-1.  Works
+ * with every step kind, guidance, the LR anchor, step noise and adapter features; a sampler with a ControlNet refuses interval > 1.
+ * The result deviates from the uncached run: the deep features of the last full step stand in for the current ones. */
+int mrisr_sampler_set_cache(mrisr_sampler* s, int interval, int depth);
 /* Multistep kinds only (defaults: order 2, final point "zero").  solver_order: 1..3 for UniPC, 1..2 for DPM-Solver++.
  * final_sigmas_zero: 1 - the last step lands on alpha = 1, sigma = 0 (diffusers' final_sigmas_type "zero"; that step is first order);
  * 0 - on alphas_cumprod[0] ("sigma_min", as the DDIM kind).  lower_order_final must be 1: UniPC's order is min(solver_order, steps

@@ -86,6 +86,32 @@ int mrisr_unet_forward(mrisr_model* m, const mrisr_tensor* sample, const mrisr_t
                            (hipStream_t)stream);
     API_END
 }
+int mrisr_unet_cache_shape(const mrisr_model* m, int depth, int B, int h, int w, int64_t shape[4]) {
+    MRISR_REQUIRE(m && shape, "null argument");
+    MRISR_REQUIRE(!m->is_controlnet, "not a UNet handle");
+    return m->cache_shape(depth, B, h, w, shape);
+}
+int mrisr_unet_forward_cached(mrisr_model* m, const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,
+                              const mrisr_tensor* intrablock, int n_intrablock, int depth, int shallow, mrisr_tensor* cache,
+                              mrisr_tensor* out, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(m && sample && cache, "null argument");
+    MRISR_REQUIRE(!m->is_controlnet, "not a UNet handle");
+    MRISR_REQUIRE(sample->ndim == 4, "sample must be [B, in_channels, h, w]");
+    int64_t cs[4];
+    TRY(m->cache_shape(depth, (int)sample->shape[0], (int)sample->shape[2], (int)sample->shape[3], cs));
+    // the forward copies cs[0] * ... * cs[3] elements of the compute dtype to / reads them from cache->data without further checks
+    MRISR_REQUIRE(cache->data && cache->ndim == 4 && cache->layout == MRISR_NHWC && cache->dtype == m->cfg.compute_dtype,
+                  "feature cache: an NHWC tensor in the compute dtype");
+    MRISR_REQUIRE(cache->shape[0] == cs[0] && cache->shape[1] == cs[1] && cache->shape[2] == cs[2] && cache->shape[3] == cs[3],
+                  "feature cache: shape differs from mrisr_unet_cache_shape");
+    UNetCache fc;
+    fc.mode = shallow ? CACHE_USE : CACHE_STORE;
+    fc.depth = depth;
+    fc.p = cache->data;
+    return m->forward_unet(sample, timestep, ehs, nullptr, 0, nullptr, intrablock, n_intrablock, out, (hipStream_t)stream, &fc);
+    API_END
+}
 int mrisr_model_set_context(mrisr_model* m, const mrisr_tensor* ehs, int latent_h, int latent_w, void* stream) {
     API_BEGIN
     MRISR_REQUIRE(m && ehs, "null argument");
@@ -266,12 +292,22 @@ struct mrisr_sampler {
     DevBuf tp_unet, tp_cnet;  // per-run time-embedding tables [scratch | n_steps x tproj_total] (f32)
     std::vector<std::unique_ptr<DevBuf>> res_bufs;   // ControlNet -> UNet residuals (NHWC, compute dtype)
     std::vector<std::unique_ptr<DevBuf>> intra_bufs;  // adapter features converted once
+    // feature cache: step i of a run over [first, last) is full (and stores the cache) when (i - first) % interval == 0,
+    // shallow (reads it) otherwise; interval 1 = no cache: the body, the key and the graph without it
+    int cache_interval = 1, cache_depth = 1;
+    DevBuf d_cache;
     hipGraphExec_t exec = nullptr;
+    hipGraphExec_t exec_shallow = nullptr;  // cache_interval > 1: exec is the full + store step, this the shallow one
     std::string graph_key;
+    void drop_graphs() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (exec_shallow) (void)hipGraphExecDestroy(exec_shallow);
+        exec = exec_shallow = nullptr;
+    }
     hipStream_t own_stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     ~mrisr_sampler() {
-        if (exec) (void)hipGraphExecDestroy(exec);
+        drop_graphs();
         if (own_stream) (void)hipStreamDestroy(own_stream);
         if (ev_in) (void)hipEventDestroy(ev_in);
         if (ev_out) (void)hipEventDestroy(ev_out);
@@ -381,8 +417,19 @@ int mrisr_sampler_set_solver(mrisr_sampler* s, int solver_order, int final_sigma
 int mrisr_sampler_set_clip(mrisr_sampler* s, float clip_sample_range) {
     MRISR_REQUIRE(s, "null sampler");
     MRISR_REQUIRE(s->kind == MRISR_STEP_DDPM, "x0 clipping belongs to the DDPM step");
-    if (s->clip != clip_sample_range && s->exec) { (void)hipGraphExecDestroy(s->exec); s->exec = nullptr; }  // baked into the graph
+    if (s->clip != clip_sample_range) s->drop_graphs();  // baked into the graph
     s->clip = clip_sample_range;
+    return 0;
+}
+
+int mrisr_sampler_set_cache(mrisr_sampler* s, int interval, int depth) {
+    MRISR_REQUIRE(s, "null sampler");
+    MRISR_REQUIRE(interval >= 1, "cache interval must be >= 1 (1: no cache)");
+    MRISR_REQUIRE(depth >= 1 && depth <= s->unet->num_skips() - 1, "cache depth must lie in 1 .. num_skips - 1");
+    MRISR_REQUIRE(interval == 1 || !s->cnet, "a feature cache together with a ControlNet is not supported");
+    if (interval != s->cache_interval || depth != s->cache_depth) s->drop_graphs();  // the next run captures again
+    s->cache_interval = interval;
+    s->cache_depth = depth;
     return 0;
 }
 
@@ -406,6 +453,8 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
     MRISR_REQUIRE(s->kind != MRISR_STEP_RESSHIFT || lr_latents, "Res-SRDiff needs the LR anchor latents");
     MRISR_REQUIRE(!s->multistep() || !step_noise, "the multistep solvers are deterministic: step_noise is refused");
     MRISR_REQUIRE(!s->cnet || cond, "ControlNet needs the condition image");
+    const bool cached = s->cache_interval > 1;
+    MRISR_REQUIRE(!cached || !s->cnet, "a feature cache together with a ControlNet is not supported");
     hipStream_t user = (hipStream_t)stream;
     hipStream_t st = user;
     Model& U = *s->unet;
@@ -498,6 +547,14 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
         intra[i].dtype = cdt;
     }
     TRY(s->d_eps.reserve((size_t)NB * per * sizeof(float), false));
+    UNetCache fc;
+    if (cached) {  // reserved here, before any capture; written by the first step of every run before anything reads it
+        int64_t cs[4];
+        TRY(U.cache_shape(s->cache_depth, NB, h, w, cs));
+        TRY(s->d_cache.reserve((size_t)cs[0] * cs[1] * cs[2] * cs[3] * esz, false));
+        fc.depth = s->cache_depth;
+        fc.p = s->d_cache.p;
+    }
     if (guided) {
         // [x; x] once per run; from then on the guided step itself writes every new state to both halves
         TRY(s->d_x2.reserve((size_t)2 * n * sizeof(float), false));
@@ -553,13 +610,14 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
     eps_t.data = s->d_eps.p;
     const int* step = static_cast<const int*>(s->d_step.p);
 
-    auto body = [&]() -> int {
+    auto body = [&](int cache_mode) -> int {
+        fc.mode = cache_mode;
         hipLaunchKernelGGL(load_t_kernel, dim3(1), dim3(1), 0, st, static_cast<long long*>(s->d_curt.p),
                            static_cast<const long long*>(s->d_ts.p), step);
         if (s->cnet)
             TRY(s->cnet->forward_controlnet(&xin, &tt, nullptr, nullptr, 1.0f, down_t.data(), ns, &mid_t, st));
         TRY(U.forward_unet(&xin, &tt, nullptr, s->cnet ? down_t.data() : nullptr, ns, s->cnet ? &mid_t : nullptr,
-                           intra.data(), n_intrablock, &eps_t, st));
+                           intra.data(), n_intrablock, &eps_t, st, cached ? &fc : nullptr));
         if (guided)
             TRY(launch_guided_step(s->kind, (float*)latents->data, (float*)s->d_x2.p, (const float*)s->d_eps.p,
                                    lr_latents ? (const float*)lr_latents->data : nullptr, step_noise ? (const float*)step_noise->data : nullptr,
@@ -579,8 +637,9 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
         return launch_advance_step(static_cast<int*>(s->d_step.p), st);
     };
 
+    auto mode_of = [&](int i) { return !cached ? CACHE_NONE : ((i - s->first) % s->cache_interval == 0 ? CACHE_STORE : CACHE_USE); };
     if (!use_graph) {
-        for (int i = s->first; i < s->last; ++i) TRY(body());
+        for (int i = s->first; i < s->last; ++i) TRY(body(mode_of(i)));
     } else {
         // everything the captured launches bake in: geometry, caller pointers, the models' workspace generations (persist /
         // arena base addresses change when another geometry, a training step or a second sampler re-plans them), this
@@ -604,21 +663,30 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
                 key += kb;
                 for (int d : s->ms.disable_corrector) { snprintf(kb, sizeof(kb), ",d%d", d); key += kb; }
             }
+            if (cached) {  // the buffer the store node writes and the shallow graph reads, and where the decoder meets it
+                snprintf(kb, sizeof(kb), ",C%p,%d", s->d_cache.p, s->cache_depth);
+                key += kb;
+            }
         }
-        if (!s->exec || s->graph_key != key) {
-            if (s->exec) { (void)hipGraphExecDestroy(s->exec); s->exec = nullptr; }
+        if (!s->exec || (cached && !s->exec_shallow) || s->graph_key != key) {
+            s->drop_graphs();
             // workspaces are planned (set_context above), so the captured body performs launches only
-            hipGraph_t graph = nullptr;
-            MRISR_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            int rc = body();
-            hipError_t e = hipStreamEndCapture(st, &graph);
-            if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-            MRISR_CHECK_HIP(e);
-            MRISR_CHECK_HIP(hipGraphInstantiate(&s->exec, graph, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(graph);
+            auto capture = [&](int cache_mode, hipGraphExec_t* exec) -> int {
+                hipGraph_t graph = nullptr;
+                MRISR_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+                int rc = body(cache_mode);
+                hipError_t e = hipStreamEndCapture(st, &graph);
+                if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+                MRISR_CHECK_HIP(e);
+                MRISR_CHECK_HIP(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
+                (void)hipGraphDestroy(graph);
+                return 0;
+            };
+            TRY(capture(cached ? CACHE_STORE : CACHE_NONE, &s->exec));
+            if (cached) TRY(capture(CACHE_USE, &s->exec_shallow));
             s->graph_key = key;
         }
-        for (int i = s->first; i < s->last; ++i) MRISR_CHECK_HIP(hipGraphLaunch(s->exec, st));
+        for (int i = s->first; i < s->last; ++i) MRISR_CHECK_HIP(hipGraphLaunch(mode_of(i) == CACHE_USE ? s->exec_shallow : s->exec, st));
     }
     if (st != user) {
         MRISR_CHECK_HIP(hipEventRecord(s->ev_out, st));

@@ -51,6 +51,17 @@ struct HeadBuf {  // head-major q / k / v^T staging for one (tokens, channels) g
 
 const char* last_error_cstr();
 
+// DeepCache-style feature cache of one UNet forward.  With n = num_skips() and 1 <= depth <= n - 1, decoder stage
+// n - 1 - depth (the up-block resnet that consumes skip s_depth) reads x = the tensor `p` describes ([B, H, W, C] of Model::cache_shape,
+// NHWC, compute dtype).  STORE: the ordinary forward, which also copies that x into p.  USE: the encoder stops after producing s_depth, no
+// mid block runs, and the decoder starts at that stage from p.
+enum { CACHE_NONE = 0, CACHE_STORE = 1, CACHE_USE = 2 };
+struct UNetCache {
+    int mode = CACHE_NONE;
+    int depth = 0;
+    void* p = nullptr;
+};
+
 struct Model {
     mrisr_unet_cfg cfg{};
     bool is_controlnet = false;
@@ -105,12 +116,13 @@ struct Model {
     int finalize(hipStream_t st);
     int num_skips() const;
     int skip_shape(int k, int B, int h, int w, int64_t shape[4]) const;
+    int cache_shape(int depth, int B, int h, int w, int64_t shape[4]) const;  // the cached decoder input of UNetCache: {B, C, H, W}
     const HeadBuf& head_buf(int N, int C) const;
     const HeadBuf& head_buf_for_C(int C) const;
     int ensure_workspace(int B, int h, int w, int L, hipStream_t st);
     int forward_unet(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,
                      const mrisr_tensor* down_res, int n_down, const mrisr_tensor* mid_res,
-                     const mrisr_tensor* intrablock, int n_intra, mrisr_tensor* out, hipStream_t st);
+                     const mrisr_tensor* intrablock, int n_intra, mrisr_tensor* out, hipStream_t st, const UNetCache* cache = nullptr);
     int forward_controlnet(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,
                            const mrisr_tensor* cond, float scale, mrisr_tensor* down_out, int n_down,
                            mrisr_tensor* mid_out, hipStream_t st);

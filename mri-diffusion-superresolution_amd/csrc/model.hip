@@ -522,7 +522,18 @@ int Model::skip_shape(int k, int B, int h, int w, int64_t shape[4]) const {
     shape[3] = w >> s[k].second;
     return 0;
 }
-
+// x of decoder stage q = n - 1 - depth (up block q / (layers + 1), resnet q % (layers + 1)): the previous stage's output - the block's own
+// width, or for the block's first resnet the width of the block below it, after the upsampler - at the resolution of the skip it meets
+int Model::cache_shape(int depth, int B, int h, int w, int64_t shape[4]) const {
+    const int n = num_skips(), per = cfg.layers_per_block + 1;
+    MRISR_REQUIRE(depth >= 1 && depth <= n - 1, "cache depth must lie in 1 .. num_skips - 1");
+    const int q = n - 1 - depth, j = q % per, lvl = cfg.num_levels - 1 - q / per;
+    shape[0] = B;
+    shape[1] = cfg.block_out_channels[j ? lvl : std::min(lvl + 1, cfg.num_levels - 1)];
+    shape[2] = h >> lvl;
+    shape[3] = w >> lvl;
+    return 0;
+}
 
 // ================================================================================================
 // workspace planning
@@ -671,7 +682,7 @@ int Model::build_tproj_table(const long long* ts_dev, int rows, float* scratch, 
 
 int Model::forward_unet(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,
                         const mrisr_tensor* down_res, int n_down, const mrisr_tensor* mid_res,
-                        const mrisr_tensor* intrablock, int n_intra, mrisr_tensor* out, hipStream_t st) {
+                        const mrisr_tensor* intrablock, int n_intra, mrisr_tensor* out, hipStream_t st, const UNetCache* cache) {
     MRISR_REQUIRE(!is_controlnet, "not a UNet handle");
     TRY(check_sample(*this, sample));
     MRISR_REQUIRE(timestep && timestep->dtype == MRISR_I64 && timestep->ndim <= 1, "timestep: device int64, 0-dim or [B]");
@@ -683,12 +694,19 @@ int Model::forward_unet(const mrisr_tensor* sample, const mrisr_tensor* timestep
     const int t_scalar = timestep->ndim == 0 || timestep->shape[0] == 1;
     MRISR_REQUIRE(t_scalar || timestep->shape[0] == B, "timestep length");
     const long long* t = static_cast<const long long*>(timestep->data);
+    const UNetCache fc = cache ? *cache : UNetCache();
+    if (fc.mode != CACHE_NONE) {
+        MRISR_REQUIRE(fc.mode == CACHE_STORE || fc.mode == CACHE_USE, "feature cache mode");
+        MRISR_REQUIRE(fc.depth >= 1 && fc.depth <= num_skips() - 1, "cache depth must lie in 1 .. num_skips - 1");
+        MRISR_REQUIRE(fc.p, "feature cache: null buffer");
+        MRISR_REQUIRE(n_down == 0 && !mid_res, "a feature cache together with ControlNet residuals is not supported");
+    }
     if (cfg.compute_dtype == MRISR_F32) {
         Runner<float> r(*this, st, false);
-        return r.unet_forward(*sample, t, t_scalar, ehs, down_res, n_down, mid_res, intrablock, n_intra, *out);
+        return r.unet_forward(*sample, t, t_scalar, ehs, down_res, n_down, mid_res, intrablock, n_intra, *out, fc);
     }
     Runner<bf16> r(*this, st, false);
-    return r.unet_forward(*sample, t, t_scalar, ehs, down_res, n_down, mid_res, intrablock, n_intra, *out);
+    return r.unet_forward(*sample, t, t_scalar, ehs, down_res, n_down, mid_res, intrablock, n_intra, *out, fc);
 }
 
 int Model::forward_controlnet(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,

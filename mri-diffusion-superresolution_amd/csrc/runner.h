@@ -659,13 +659,16 @@ struct Runner {
     }
 
     // ---- encoder shared by UNet and ControlNet: down blocks (+skips) ----
-    int encoder(Act x, const mrisr_tensor* intrablock, int n_intra, std::vector<Act>* skips, Act* out) {
+    // last_skip >= 0 (a shallow pass over a feature cache): stop once skip s_last_skip is what the full pass would hand the decoder
+    int encoder(Act x, const mrisr_tensor* intrablock, int n_intra, std::vector<Act>* skips, Act* out, int last_skip = -1) {
         skips->push_back(x);
         int ib = 0;
-        for (int i = 0; i < m.cfg.num_levels; ++i) {
+        auto done = [&] { return last_skip >= 0 && (int)skips->size() > last_skip; };
+        for (int i = 0; i < m.cfg.num_levels && !done(); ++i) {
             Level& lv = m.down[i];
             const bool has_attn = !lv.xf.empty();
-            for (size_t j = 0; j < lv.res.size(); ++j) {
+            const int block_last = (int)skips->size() - 1 + (int)lv.res.size() + (lv.has_down ? 1 : 0);  // index of this block's last skip
+            for (size_t j = 0; j < lv.res.size() && !done(); ++j) {
                 Act y, xn_next;
                 xn_next.p = nullptr;
                 if (has_attn) TRY(resnet(lv.res[j], x, nullptr, &y, &lv.xf[j].norm, 1e-6f, &xn_next));
@@ -678,13 +681,14 @@ struct Runner {
                 }
                 skips->push_back(x);
             }
-            if (lv.has_down) {
+            if (lv.has_down && !done()) {
                 Act y;
                 TRY(conv3(x, nullptr, lv.down, 2, 0, nullptr, 0, 1, nullptr, ACT_NONE, &y));
                 x = y;
                 skips->push_back(x);
             }
-            if (!has_attn && ib < n_intra) {
+            // (a shallow pass that stopped inside this block needs none of what follows: the feature lands in a deeper skip)
+            if (!has_attn && ib < n_intra && (last_skip < 0 || last_skip >= block_last)) {
                 // attention-free block: diffusers adds the adapter feature AFTER the block returned, but IN PLACE
                 // (`sample += down_intrablock_additional_residuals.pop(0)`, unet_2d_condition.py forward) on the very
                 // tensor DownBlock2D also returned as res_samples[-1] - so the LAST skip pushed above carries the
@@ -723,9 +727,16 @@ struct Runner {
 
     int unet_forward(const mrisr_tensor& sample, const long long* t_dev, int t_scalar, const mrisr_tensor* ehs,
                      const mrisr_tensor* down_res, int n_down, const mrisr_tensor* mid_res,
-                     const mrisr_tensor* intrablock, int n_intra, const mrisr_tensor& out) {
+                     const mrisr_tensor* intrablock, int n_intra, const mrisr_tensor& out, const UNetCache& fc = UNetCache()) {
         m.arena.reset();
         const int B = (int)sample.shape[0];
+        // feature cache: the decoder is a flat sequence of n = num_skips() stages, stage q consuming skip n - 1 - q
+        const bool store = fc.mode == CACHE_STORE, use = fc.mode == CACHE_USE;
+        const int q0 = m.num_skips() - 1 - fc.depth;  // the stage whose input x is cached
+        if (store || use) {
+            MRISR_REQUIRE(q0 >= 0 && fc.depth >= 1 && fc.p, "feature cache: depth 1 .. num_skips - 1 and a buffer");
+            MRISR_REQUIRE(n_down == 0 && !mid_res, "a feature cache together with ControlNet residuals is not supported");
+        }
         if (ehs) TRY(set_context(*ehs));
         MRISR_REQUIRE(dry || m.ctx_valid, "no encoder_hidden_states given and none cached");
         TRY(time_embed(t_dev, t_scalar, B));
@@ -733,7 +744,7 @@ struct Runner {
         TRY(import_act(sample, &s, false));
         TRY(direct(s, m.conv_in, 1, ACT_NONE, nullptr, &x));
         std::vector<Act> skips;
-        TRY(encoder(x, intrablock, n_intra, &skips, &x));
+        TRY(encoder(x, intrablock, n_intra, &skips, &x, use ? fc.depth : -1));
         if (n_down > 0) {
             MRISR_REQUIRE(n_down == (int)skips.size(), "down_block_additional_residuals count");
             for (int k = 0; k < n_down; ++k) {
@@ -748,11 +759,23 @@ struct Runner {
                 TRY(add_external(skips[k], down_res[k]));
             }
         }
-        TRY(mid(x, &x));
+        if (!use) TRY(mid(x, &x));
         if (mid_res) TRY(add_external(x, *mid_res));
+        int q = 0;
         for (int i = 0; i < m.cfg.num_levels; ++i) {
             Level& lv = m.up[i];
-            for (size_t j = 0; j < lv.res.size(); ++j) {
+            for (size_t j = 0; j < lv.res.size(); ++j, ++q) {
+                if (use && q < q0) continue;
+                if ((store || use) && q == q0) {
+                    int64_t cs[4];
+                    TRY(m.cache_shape(fc.depth, B, (int)sample.shape[2], (int)sample.shape[3], cs));
+                    if (store) {
+                        MRISR_REQUIRE(x.B == cs[0] && x.C == cs[1] && x.H == cs[2] && x.W == cs[3], "feature cache shape");
+                        if (!dry) MRISR_CHECK_HIP(hipMemcpyAsync(fc.p, x.p, x.numel() * sizeof(T), hipMemcpyDeviceToDevice, st));
+                    } else {
+                        x.p = fc.p; x.B = (int)cs[0]; x.C = (int)cs[1]; x.H = (int)cs[2]; x.W = (int)cs[3];
+                    }
+                }
                 Act sk = skips.back();
                 skips.pop_back();
                 Act y, xn_next;
@@ -765,7 +788,7 @@ struct Runner {
                     x = y;
                 }
             }
-            if (lv.has_up) {
+            if (lv.has_up && !(use && q <= q0)) {  // (a cache taken at a block's first stage is taken after the upsampler before it)
                 Act y;
                 TRY(upsample_conv(x, lv, &y));
                 x = y;

@@ -59,7 +59,7 @@ EXPORTS = [
     "mrisr_model_skip_shape", "mrisr_controlnet_forward", "mrisr_controlnet_set_cond", "mrisr_adapter_create",
     "mrisr_adapter_destroy", "mrisr_adapter_set_param", "mrisr_adapter_finalize", "mrisr_adapter_forward",
     "mrisr_resshift_forward", "mrisr_sampler_create", "mrisr_sampler_destroy", "mrisr_sampler_run", "mrisr_sampler_set_range", "mrisr_sampler_set_clip",
-    "mrisr_sampler_set_guidance", "mrisr_sampler_run_guided", "mrisr_op_guided_step", "mrisr_sampler_set_solver", "mrisr_op_multistep_step",
+    "mrisr_sampler_set_guidance", "mrisr_sampler_run_guided", "mrisr_sampler_set_cache", "mrisr_unet_cache_shape", "mrisr_unet_forward_cached", "mrisr_op_guided_step", "mrisr_sampler_set_solver", "mrisr_op_multistep_step",
     "mrisr_adapter_train_prepare", "mrisr_adapter_train_num_trainable", "mrisr_adapter_train_num_tensors",
     "mrisr_adapter_train_tensor_info", "mrisr_adapter_train_bind", "mrisr_adapter_train_refresh", "mrisr_adapter_backward", "mrisr_adapter_backward_level", "mrisr_adapter_train_level_range",
     "mrisr_vae_create", "mrisr_vae_destroy", "mrisr_vae_set_param", "mrisr_vae_num_params", "mrisr_vae_finalize",
@@ -98,6 +98,10 @@ def lib() -> C.CDLL:
         L.mrisr_sampler_set_guidance.argtypes = [C.c_void_p, C.c_float, C.c_float]
         L.mrisr_op_guided_step.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                            C.c_float, C.c_float, C.c_void_p]
+        L.mrisr_sampler_set_cache.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.mrisr_unet_cache_shape.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.mrisr_unet_forward_cached.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
         L.mrisr_sampler_set_solver.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.mrisr_op_multistep_step.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]

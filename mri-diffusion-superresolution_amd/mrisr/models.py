@@ -230,6 +230,45 @@ class UNet2DConditionModel(_DeviceModel):
                                            i_arr if intra else None, len(intra), C.byref(t_o), L.stream_ptr()))
         return _Output(out) if return_dict else (out,)
 
+    def cache_shape(self, depth: int, B: int, h: int, w: int) -> Tuple[int, int, int, int]:
+        """Logical (B, C, H, W) of the feature cache at ``depth`` for h x w latents: the input of the decoder stage that consumes
+        skip ``depth``.  ``forward_cached`` wants it as a [B, H, W, C] tensor of the compute dtype."""
+        s = (C.c_int64 * 4)()
+        L.check(L.lib().mrisr_unet_cache_shape(self._h, int(depth), int(B), int(h), int(w), s))
+        return tuple(int(x) for x in s)
+
+    def forward_cached(self, sample: torch.Tensor, timestep, encoder_hidden_states: Optional[torch.Tensor], cache: torch.Tensor,
+                       depth: int, shallow: bool, down_intrablock_additional_residuals: Optional[Sequence[torch.Tensor]] = None):
+        """One forward with a DeepCache-style feature cache.  ``cache``: contiguous [B, H, W, C] (NHWC) tensor of the compute dtype
+        with (B, C, H, W) = ``cache_shape(depth, ...)``.  ``shallow=False``: the ordinary forward, which also writes ``cache``;
+        ``shallow=True``: only the encoder up to skip ``depth`` and the decoder from the stage that consumes it, started from
+        ``cache``.  Returns the prediction (a tensor, not an output object)."""
+        if not self._finalized:
+            raise L.MrisrError("load_state_dict() first")
+        if sample.ndim != 4 or sample.shape[1] != self.config.in_channels:
+            raise ValueError(f"sample must be [B,{self.config.in_channels},h,w]; got {tuple(sample.shape)}")
+        sample = sample.to(self.device).contiguous()
+        B, _, h, w = sample.shape
+        cb, cc, ch, cw = self.cache_shape(depth, B, h, w)
+        if not torch.is_tensor(cache) or not cache.is_cuda or not cache.is_contiguous():
+            raise ValueError("cache must be a contiguous tensor on the GPU (NHWC)")
+        if cache.dtype != self.compute_dtype:
+            raise ValueError(f"cache must be in the compute dtype {self.compute_dtype}, got {cache.dtype}")
+        if tuple(cache.shape) != (cb, ch, cw, cc):
+            raise ValueError(f"cache must be [B, H, W, C] = {(cb, ch, cw, cc)} for depth {depth}, got {tuple(cache.shape)}")
+        t = self._timestep(timestep, B)
+        ehs = encoder_hidden_states.to(self.device).contiguous() if encoder_hidden_states is not None else None
+        intra = [r.to(self.device).contiguous() for r in (down_intrablock_additional_residuals or [])]
+        out = torch.empty((B, self.config.out_channels, h, w), dtype=sample.dtype, device=self.device)
+        i_arr = L.tensor_array([L.as_tensor(r) for r in intra])
+        t_s, t_t, t_o = L.as_tensor(sample), L.as_tensor(t), L.as_tensor(out)
+        t_e = L.as_tensor(ehs) if ehs is not None else None
+        t_c = L.as_tensor(cache, layout=L.MRISR_NHWC, shape=(cb, cc, ch, cw))
+        L.check(L.lib().mrisr_unet_forward_cached(self._h, C.byref(t_s), C.byref(t_t), C.byref(t_e) if t_e else None,
+                                                  i_arr if intra else None, len(intra), int(depth), 1 if shallow else 0,
+                                                  C.byref(t_c), C.byref(t_o), L.stream_ptr()))
+        return out
+
     def set_context(self, encoder_hidden_states: torch.Tensor, latent_hw: Tuple[int, int]):
         """Pre-compute the cross-attention K/V of a fixed prompt (then pass encoder_hidden_states=None)."""
         ehs = encoder_hidden_states.to(self.device).contiguous()

@@ -114,6 +114,22 @@ def check_solver(kind, solver_order=2, final_sigmas_type="zero", lower_order_fin
     return int(solver_order), final_sigmas_type, disable
 
 
+def check_cache(interval, depth, n_skips, has_controlnet=False):
+    """The argument rules of the sampler's feature cache (``Sampler.set_cache``), on numbers alone (no device is touched); returns
+    the normalised (interval, depth).  ``interval`` >= 1 (1: no cache); 1 <= ``depth`` <= ``n_skips`` - 1; a ControlNet together
+    with ``interval`` > 1 is refused (its shallow pass does not exist).  Raises ``ValueError``."""
+    for name, v in (("interval", interval), ("depth", depth)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"cache {name} must be an int, got {v!r}")
+    if interval < 1:
+        raise ValueError(f"cache interval must be >= 1 (1: no cache), got {interval}")
+    if not 1 <= depth <= n_skips - 1:
+        raise ValueError(f"cache depth must lie in 1..{n_skips - 1}, got {depth}")
+    if interval > 1 and has_controlnet:
+        raise ValueError("a feature cache (interval > 1) together with a ControlNet is not supported")
+    return int(interval), int(depth)
+
+
 class Sampler:
     """Owns a C-ABI sampler (device tables + the captured step graph) for one (unet, controlnet, schedule)."""
 
@@ -170,6 +186,16 @@ class Sampler:
         arr = (C.c_int * max(1, len(disable)))(*disable)
         L.check(L.lib().mrisr_sampler_set_solver(self._h, order, 1 if final == "zero" else 0, 1, arr if disable else None, len(disable)))
         self.solver_order, self.final_sigmas_type, self.disable_corrector = order, final, disable
+
+    def set_cache(self, interval: int = 1, depth: int = 1):
+        """DeepCache-style feature cache for the next ``run`` (Ma et al. 2023).  With ``interval`` N > 1, step i
+        of a run over [first, last) is a full forward when (i - first) % N == 0 and otherwise a shallow one: only the encoder up to
+        skip ``depth`` and the decoder stages from the one that consumes it, started from the deep feature the last full step left.
+        Fewer launches per step for a bounded deviation from the uncached run.  ``interval=1`` (the default) is no cache at all:
+        the step graph and the result of a sampler that never had one.  Changing either value captures the step graphs again."""
+        interval, depth = check_cache(interval, depth, int(L.lib().mrisr_model_num_skips(self.unet._h)), self.controlnet is not None)
+        L.check(L.lib().mrisr_sampler_set_cache(self._h, interval, depth))
+        self.cache_interval, self.cache_depth = interval, depth
 
     def set_range(self, first_step: int, last_step: int):
         """Run only steps [first_step, last_step) of the schedule on the next ``run`` (resume / inspection).  The multistep kinds start
@@ -253,7 +279,8 @@ class Sampler:
 
 @torch.no_grad()
 def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weight_dtype, accelerator, fixed_embeds,
-                   num_inference_steps=20, adapter=None, solver=None, guidance_scale=1.0, guidance_rescale=0.0, uncond_embeds=None):
+                   num_inference_steps=20, adapter=None, solver=None, cache_interval=1, cache_depth=1, guidance_scale=1.0,
+                   guidance_rescale=0.0, uncond_embeds=None):
     """Drop-in for the reference's validation sampler (res_srdiff.py:35-105): same inputs, same PIL panel out.
     The timestep loop is one fused sampler call; the per-step noise is drawn up front from the same global RNG
     stream, in the same order, as the reference's per-step ``torch.randn_like`` calls.  ``adapter`` (a T2I-Adapter):
@@ -261,7 +288,8 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     ``guidance_scale`` / ``guidance_rescale`` / ``uncond_embeds`` (the empty caption's embedding, [1,L,D]): classifier-free
     guidance as in ``Sampler.run``; the defaults leave the result unchanged.  ``solver`` ("unipc" / "dpmsolver++"): sample the panel
     with that LR-anchored deterministic multistep solver (the scheduler's solver options when it carries any) instead of the
-    reference's stochastic step; no step noise is drawn then.  ``None``: the reference's sampler."""
+    reference's stochastic step; no step noise is drawn then.  ``None``: the reference's sampler.  ``cache_interval`` /
+    ``cache_depth``: the feature cache of ``Sampler.set_cache``; the defaults leave the panel unchanged."""
     from PIL import Image
 
     if solver is not None:
@@ -286,6 +314,8 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
         n_noise = 0
     step_noise = torch.stack([torch.randn_like(latents) for _ in range(n_noise)]) if n_noise else None
     sampler = Sampler(unet, noise_scheduler, controlnet, kind=solver if solver is not None else "resshift")
+    if cache_interval != 1 or cache_depth != 1:
+        sampler.set_cache(cache_interval, cache_depth)
     feats = None
     if adapter is not None:
         cond = control_image if tuple(control_image.shape[-2:]) == tuple(lr_raw.shape[-2:]) else \

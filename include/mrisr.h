@@ -511,6 +511,12 @@ int mrisr_op_lora_wgrad(int dtype, const void* P, int ldp, const float* Q, int l
  * the un-interleave happens in the scatter of the reduction */
 int mrisr_op_lora_wgrad_geglu(int dtype, const void* P, int ldp, const float* Q, int ldq, int M, int half, int r, float* out, float scale,
                               void* stream);
+/* The same sums at rank r in {32, 48, ..., 128}.  Q is of type T, with module j's r columns at j * rp where rp is r rounded up to the K tile
+ * of the engine (64 elements in bf16, 32 in f32); the columns past r are padding and are never read out.  ldq >= nmod * rp.  geglu_half > 0
+ * (mode 0, nmod 1, C = 2 * geglu_half): P's columns are in the interleave of ff.net.0.proj and out0's rows in raw order, as above.
+ * bf16 runs on the MFMA pipe (lora_wgrad_hr_kernel), f32 walks the streaming kernel over 16 columns of Q at a time */
+int mrisr_op_lora_wgrad_hr(int dtype, const void* P, int ldp, const void* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN,
+                           float* out0, float* out1, float* out2, float scale, int geglu_half, void* stream);
 /* dst[z][c][r] = src[z][r][c] for r < r_valid, 0 for r_valid <= r < R (T; pitches ld_src >= C, ld_dst >= R; batch strides in elements) */
 int mrisr_op_transpose(int dtype, const void* src, void* dst, int R, int C, int ld_src, int ld_dst, int64_t bs_src, int64_t bs_dst,
                        int batch, int r_valid, void* stream);

@@ -751,17 +751,20 @@ struct LoraWgradArgs {
     const float* Q = nullptr;
     int ldq = 0;
     int M = 0, C = 0, mode = 0, r = 0, nmod = 1, secN = 0, qbase = 0;
+    int rp = 0;    // pitch of a module's columns in Q when it is not r (high rank, f32: lora_wgrad_hr); the passes then walk qbase
     int half = 0;  // mode 0 on ff.net.0.proj: P's columns are (value, gate) interleaved in blocks of 16, out[0] rows are raw
     float* out[3] = {nullptr, nullptr, nullptr};
     float scale = 1.0f;
     float* partial = nullptr;  // [gy][gx * cxb * VE * NQ]
     int cxb = 0, RL = 1, rpb = 0, gx = 1, gy = 1;
 };
-static void lora_wgrad_geom(LoraWgradArgs& a, int VE) {
+// plain: one row interleave per block whatever the width, so the partial tiles are written with plain stores and never folded through LDS
+// atomics - the bits then repeat from launch to launch (the high-rank passes of the f32 engine)
+static void lora_wgrad_geom(LoraWgradArgs& a, int VE, bool plain = false) {
     const int cx = a.C / VE;
     a.gx = (cx + 255) / 256;
     a.cxb = (cx + a.gx - 1) / a.gx;
-    a.RL = 256 / a.cxb;
+    a.RL = plain ? 1 : 256 / a.cxb;
     a.rpb = a.RL * 16;
     a.gy = (a.M + a.rpb - 1) / a.rpb;
     if (a.gy > 512) {
@@ -784,7 +787,7 @@ __global__ __launch_bounds__(256) void lora_wgrad_kernel(const LoraWgradArgs a) 
     const int ch = threadIdx.x % a.cxb, rs = threadIdx.x / a.cxb;
     const int c0 = (blockIdx.x * a.cxb + ch) * VE;
     const bool live = rs < a.RL && c0 < a.C;
-    const int qb = a.mode == 0 ? (live ? (c0 / a.secN) * a.r : 0) : a.qbase;
+    const int qb = a.mode == 0 ? (live ? (c0 / a.secN) * (a.rp ? a.rp : a.r) + a.qbase : 0) : a.qbase;
     const int tile = a.cxb * VE * NQ;
     if (a.RL > 1)
         for (int i = threadIdx.x; i < tile; i += 256) red[i] = 0.f;
@@ -876,15 +879,35 @@ __global__ __launch_bounds__(256) void lora_wgrad_reduce_kernel(const LoraWgradA
     const int c = bx * a.cxb * VE + cl;
     if (c >= a.C) return;
     s *= a.scale;
+    const int rp = a.rp ? a.rp : a.r;
     if (GEGLU) {
-        a.out[0][(size_t)geglu_raw_row(c, a.half) * a.r + q] += s;
+        a.out[0][(size_t)geglu_raw_row(c, a.half) * a.r + a.qbase + q] += s;
     } else if (a.mode == 0) {
         const int j = c / a.secN;
-        if (a.out[j]) a.out[j][(size_t)(c - j * a.secN) * a.r + q] += s;
+        if (a.out[j]) a.out[j][(size_t)(c - j * a.secN) * a.r + a.qbase + q] += s;
     } else {
-        const int qq = a.qbase + q, j = qq / a.r;
-        if (a.out[j]) a.out[j][(size_t)(qq - j * a.r) * a.C + c] += s;
+        const int qq = a.qbase + q, j = qq / rp;
+        if (a.out[j]) a.out[j][(size_t)(qq - j * rp) * a.C + c] += s;
     }
+}
+// one pass of the streaming kernel over nq columns of Q from qbase on, and its reduce
+template <typename T>
+static int lora_wgrad_pass(LoraWgradArgs& a, int nq, int qbase, hipStream_t st) {
+    constexpr int VE = BVec<T>::N;
+    const dim3 grid(a.gx, a.gy);
+    a.qbase = qbase;
+    const size_t smem = a.RL > 1 ? (size_t)a.cxb * VE * nq * sizeof(float) : 0;
+    MRISR_REQUIRE(smem <= 65536, "LoRA wgrad: LDS tile");
+    switch (nq) {
+        case 4: hipLaunchKernelGGL((lora_wgrad_kernel<T, 4>), grid, dim3(256), smem, st, a); break;
+        case 8: hipLaunchKernelGGL((lora_wgrad_kernel<T, 8>), grid, dim3(256), smem, st, a); break;
+        case 12: hipLaunchKernelGGL((lora_wgrad_kernel<T, 12>), grid, dim3(256), smem, st, a); break;
+        default: hipLaunchKernelGGL((lora_wgrad_kernel<T, 16>), grid, dim3(256), smem, st, a); break;
+    }
+    const int total = a.gx * a.cxb * VE * nq;
+    if (a.half) hipLaunchKernelGGL(lora_wgrad_reduce_kernel<true>, dim3((total + 15) / 16), dim3(256), 0, st, a, VE, nq);
+    else hipLaunchKernelGGL(lora_wgrad_reduce_kernel<false>, dim3((total + 15) / 16), dim3(256), 0, st, a, VE, nq);
+    return 0;
 }
 // mode 0: dB of the fused modules of one linear (P = dY [M][nmod*secN], Q = z [M][nmod*r]);
 // mode 1: dA (P = x [M][k], Q = dz [M][nmod*r]).  out[j] == nullptr: module j has no adapter.
@@ -904,27 +927,171 @@ int launch_lora_wgrad(const void* P, int ldp, const float* Q, int ldq, int M, in
     a.half = geglu_half;
     a.partial = scratch;
     lora_wgrad_geom(a, VE);
-    const dim3 grid(a.gx, a.gy);
     const int R = nmod * r;
     ProfScope ps("lora_wgrad", 2.0 * M * (double)C * (mode ? R : r), (double)M * C * sizeof(T), st);
-    auto go = [&](int nq, int qbase) -> int {
-        a.qbase = qbase;
-        const size_t smem = a.RL > 1 ? (size_t)a.cxb * VE * nq * sizeof(float) : 0;
-        MRISR_REQUIRE(smem <= 65536, "LoRA wgrad: LDS tile");
-        switch (nq) {
-            case 4: hipLaunchKernelGGL((lora_wgrad_kernel<T, 4>), grid, dim3(256), smem, st, a); break;
-            case 8: hipLaunchKernelGGL((lora_wgrad_kernel<T, 8>), grid, dim3(256), smem, st, a); break;
-            case 12: hipLaunchKernelGGL((lora_wgrad_kernel<T, 12>), grid, dim3(256), smem, st, a); break;
-            default: hipLaunchKernelGGL((lora_wgrad_kernel<T, 16>), grid, dim3(256), smem, st, a); break;
-        }
-        const int total = a.gx * a.cxb * VE * nq;
-        if (a.half) hipLaunchKernelGGL(lora_wgrad_reduce_kernel<true>, dim3((total + 15) / 16), dim3(256), 0, st, a, VE, nq);
-        else hipLaunchKernelGGL(lora_wgrad_reduce_kernel<false>, dim3((total + 15) / 16), dim3(256), 0, st, a, VE, nq);
-        return 0;
-    };
+    auto go = [&](int nq, int qbase) -> int { return lora_wgrad_pass<T>(a, nq, qbase, st); };
     if (mode == 0) TRY_(go(r, 0));
     else if (R <= 16) TRY_(go(R, 0));
     else for (int j = 0; j < nmod; ++j) TRY_(go(r, j * r));  // wide adapters: one pass per module
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+// ------------------------------------------------------------------------------------------------
+// LoRA weight gradients at rank 32 .. 128: the same sums, out[c][q] (+)= scale * sum_m P[m][c] Q[m][q], with Q in
+// the engine's type and module j's columns at j * rp (rp = r rounded up to the K tile; the columns past r are padding and never read out).
+// bf16: NQ = 64 or more accumulators per channel do not fit the streaming kernel's registers, so the sum runs on the MFMA pipe.  A block owns
+// a slab of rows, 64 channels and 64 columns of Q.  Per 32 rows it stages a [32][64] tile of P and one of Q into LDS as they lie in memory
+// (16 bytes per lane, row-major) and each wave multiplies its 16 channels by the four 16-column blocks of Q on v_mfma_f32_16x16x32_bf16.
+// The contraction index m is the ROW index of both images, so both operands come through ds_read_b64_tr_b16: lane group g (16 lanes) reads
+// the 4-row blocks at rows 4g and 16 + 4g of its 16 columns; A and B use the same row -> k map, which is all the sum needs.  A 32-lane half
+// thus reads 8 consecutive rows; with a pitch of 160 bytes (5 x 32) their eight 32-byte pieces fall on eight different 32-byte bank
+// groups of the 256-byte bank cycle: conflict-free.  Every lane of all four waves issues every transposed read (EXEC all ones): rows past
+// the slab's end and channels past the tile's limit are stored as zeros instead of being branched around.
+// Each block writes its [64][64] f32 partial with plain stores (no global atomics, as above); the reduce kernel sums the slabs and scatters
+// with the three addressings of lora_wgrad_reduce_kernel, skipping the padding columns.
+// f32: the streaming kernel <float, 16>, one pass per 16 columns of Q (rp / qbase in LoraWgradArgs).
+// ------------------------------------------------------------------------------------------------
+struct LoraWgradHrArgs {
+    const bf16* P = nullptr;
+    int ldp = 0;
+    const bf16* Q = nullptr;
+    int ldq = 0;
+    int M = 0, C = 0, mode = 0, r = 0, rp = 0, nmod = 1, secN = 0, half = 0;
+    float* out[3] = {nullptr, nullptr, nullptr};
+    float scale = 1.0f;
+    float* partial = nullptr;  // [gz][tiles][qblk][64][64]
+    LoraHrGeom g;
+};
+constexpr int HR_PITCH = 80;  // bf16 elements per LDS row: 160 bytes
+typedef __attribute__((ext_vector_type(4))) short hr_s4;
+typedef __attribute__((address_space(3))) hr_s4 hr_lds_s4;
+// the 8 k-elements of one lane: rows 4g .. 4g+3 and 16 + 4g .. of column (lane & 15); p is the lane's address in the first block
+__device__ __forceinline__ bf16x8 hr_tr_frag(const bf16* p) {
+    const hr_s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((hr_lds_s4*)(p));
+    const hr_s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((hr_lds_s4*)(p + 16 * HR_PITCH));
+    typedef __attribute__((ext_vector_type(8))) short s8;
+    const s8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8, v);
+}
+__global__ __launch_bounds__(256) void lora_wgrad_hr_kernel(const LoraWgradHrArgs a) {
+    __shared__ __attribute__((aligned(16))) bf16 img[2][2][HR_STEP * HR_PITCH];  // [buffer][P | Q][row][column]
+    int c0, cend, qcol0;
+    lora_wgrad_hr_tile(a.g, a.mode, a.C, a.rp, a.secN, blockIdx.x, blockIdx.y, c0, cend, qcol0);
+    if (!a.out[qcol0 / a.rp]) return;  // a module without an adapter: the whole block, before any transposed read
+    const int t = threadIdx.x;
+    const int srow = t >> 3, sch = (t & 7) * 8;  // staging: one 16-byte chunk of P and one of Q per thread and step
+    const bool pcol = c0 + sch < cend;           // cend - c0 is a multiple of 8: a chunk is inside or outside as a whole
+    const int m_beg = blockIdx.z * a.g.rows, m_end = min(a.M, m_beg + a.g.rows);
+    const int nsteps = (m_end - m_beg + HR_STEP - 1) / HR_STEP;
+    const bf16* pp = a.P + c0 + sch;
+    const bf16* qp = a.Q + qcol0 + sch;
+    const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto fetch = [&](int step, bf16x8& pv, bf16x8& qv) {
+        const int m = m_beg + step * HR_STEP + srow;
+        pv = zero; qv = zero;
+        if (m < m_end) {
+            if (pcol) pv = *reinterpret_cast<const bf16x8*>(pp + (size_t)m * a.ldp);
+            qv = *reinterpret_cast<const bf16x8*>(qp + (size_t)m * a.ldq);
+        }
+    };
+    const int w = t >> 6, l = t & 63, g = l >> 4, li = l & 15;
+    const int roff = (4 * g + (li >> 2)) * HR_PITCH + 4 * (li & 3);
+    f32x4 acc[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+    bf16x8 pv, qv;
+    fetch(0, pv, qv);
+    for (int step = 0; step < nsteps; ++step) {
+        bf16* ip = img[step & 1][0];
+        bf16* iq = img[step & 1][1];
+        *reinterpret_cast<bf16x8*>(ip + srow * HR_PITCH + sch) = pv;
+        *reinterpret_cast<bf16x8*>(iq + srow * HR_PITCH + sch) = qv;
+        __syncthreads();  // the other buffer was last read before the previous step's barrier
+        if (step + 1 < nsteps) fetch(step + 1, pv, qv);
+        const bf16x8 af = hr_tr_frag(ip + roff + 16 * w);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const bf16x8 bf = hr_tr_frag(iq + roff + 16 * s);
+            acc[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc[s], 0, 0, 0);  // D[channel 4g + v][q = li]
+        }
+    }
+    float* dst = a.partial + (((size_t)blockIdx.z * a.g.tiles + blockIdx.x) * a.g.qblk + blockIdx.y) * (HR_TC * HR_TQ);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) dst[(16 * w + 4 * g + v) * HR_TQ + 16 * s + li] = acc[s][v];
+}
+template <bool GEGLU>
+__global__ __launch_bounds__(256) void lora_wgrad_hr_reduce_kernel(const LoraWgradHrArgs a) {
+    const size_t pitch = (size_t)a.g.tiles * a.g.qblk * (HR_TC * HR_TQ);
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= pitch) return;
+    const int ql = (int)(i % HR_TQ), cl = (int)(i / HR_TQ % HR_TC);
+    const int blk = (int)(i / (HR_TC * HR_TQ)), qb = blk % a.g.qblk, tile = blk / a.g.qblk;
+    int c0, cend, qcol0;
+    lora_wgrad_hr_tile(a.g, a.mode, a.C, a.rp, a.secN, tile, qb, c0, cend, qcol0);
+    const int c = c0 + cl, qq = qcol0 + ql, j = qq / a.rp, q = qq - j * a.rp;
+    if (c >= cend || q >= a.r || !a.out[j]) return;  // a ragged tile, a padding column, a module without an adapter
+    const float* p = a.partial + i;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int z = 0;
+    for (; z + 3 < a.g.gz; z += 4) {
+        s0 += p[z * pitch]; s1 += p[(z + 1) * pitch]; s2 += p[(z + 2) * pitch]; s3 += p[(z + 3) * pitch];
+    }
+    for (; z < a.g.gz; ++z) s0 += p[z * pitch];
+    const float s = ((s0 + s1) + (s2 + s3)) * a.scale;
+    if (GEGLU) a.out[0][(size_t)geglu_raw_row(c, a.half) * a.r + q] += s;
+    else if (a.mode == 0) a.out[j][(size_t)(c - j * a.secN) * a.r + q] += s;
+    else a.out[j][(size_t)q * a.C + c] += s;
+}
+size_t lora_wgrad_hr_scratch_bytes(int M, int C, int mode, int r, int nmod, int secN, int elem_size) {
+    if (elem_size != 2) {
+        LoraWgradArgs a;
+        a.M = M; a.C = C;
+        lora_wgrad_geom(a, 16 / elem_size, true);
+        return (size_t)a.gy * a.gx * a.cxb * (16 / elem_size) * 16 * sizeof(float);
+    }
+    return lora_wgrad_hr_partial_floats(lora_wgrad_hr_geom(M, C, mode, lora_hr_rp(r, 2), nmod, secN)) * sizeof(float);
+}
+// P [M][ldp] of T, Q [M][ldq] of T with module j's r columns at j * rp, rp = lora_hr_rp(r, sizeof(T)); modes, out and geglu_half as in
+// launch_lora_wgrad.  scratch: lora_wgrad_hr_scratch_bytes(M, C, mode, r, nmod, secN, sizeof(T)) bytes.
+template <typename T>
+int launch_lora_wgrad_hr(const void* P, int ldp, const void* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN,
+                         float* const out[3], float scale, float* scratch, hipStream_t st, int geglu_half) {
+    constexpr int VE = BVec<T>::N;
+    const int rp = lora_hr_rp(r, (int)sizeof(T));
+    MRISR_REQUIRE(lora_rank_high(r) && nmod >= 1 && nmod <= 3 && (mode == 0 || mode == 1), "LoRA wgrad (high rank): rank 32 .. 128 in steps of 16, <= 3 fused modules");
+    MRISR_REQUIRE(geglu_half == 0 || (mode == 0 && nmod == 1 && geglu_half % 16 == 0 && C == 2 * geglu_half && secN == C && out[0]),
+                  "LoRA wgrad: the GEGLU interleave is for dB of one [2 * half] projection, half a multiple of 16");
+    MRISR_REQUIRE(M >= 1 && C % 8 == 0 && ldp % VE == 0 && ldp >= C && ldq % VE == 0 && ldq >= nmod * rp && scratch, "LoRA wgrad (high rank): pitches / alignment");
+    MRISR_REQUIRE(mode == 1 || (secN % 8 == 0 && C == nmod * secN), "LoRA wgrad (high rank, dB): C = nmod sections of whole vectors");
+    ProfScope ps("lora_wgrad_hr", 2.0 * M * (double)C * (mode ? nmod * r : r), (double)M * C * sizeof(T), st);
+    if constexpr (sizeof(T) == 4) {
+        LoraWgradArgs a;
+        a.P = P; a.ldp = ldp; a.Q = static_cast<const float*>(Q); a.ldq = ldq; a.M = M; a.C = C; a.mode = mode; a.r = r; a.rp = rp;
+        a.nmod = nmod; a.secN = secN;
+        for (int j = 0; j < 3; ++j) a.out[j] = j < nmod ? out[j] : nullptr;
+        a.scale = scale;
+        a.half = geglu_half;
+        a.partial = scratch;
+        lora_wgrad_geom(a, VE, true);
+        for (int j = 0; j < (mode ? nmod : 1); ++j) {
+            if (mode && !a.out[j]) continue;
+            for (int qb = 0; qb < r; qb += 16) TRY_(lora_wgrad_pass<float>(a, 16, j * rp + qb, st));
+        }
+    } else {
+        LoraWgradHrArgs a;
+        a.P = static_cast<const bf16*>(P); a.ldp = ldp; a.Q = static_cast<const bf16*>(Q); a.ldq = ldq; a.M = M; a.C = C; a.mode = mode;
+        a.r = r; a.rp = rp; a.nmod = nmod; a.secN = secN; a.half = geglu_half;
+        for (int j = 0; j < 3; ++j) a.out[j] = j < nmod ? out[j] : nullptr;
+        a.scale = scale;
+        a.partial = scratch;
+        a.g = lora_wgrad_hr_geom(M, C, mode, rp, nmod, secN);
+        hipLaunchKernelGGL(lora_wgrad_hr_kernel, dim3(a.g.tiles, a.g.qblk, a.g.gz), dim3(256), 0, st, a);
+        const size_t total = (size_t)a.g.tiles * a.g.qblk * (HR_TC * HR_TQ);
+        if (a.half) hipLaunchKernelGGL(lora_wgrad_hr_reduce_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(lora_wgrad_hr_reduce_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
+    }
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1437,6 +1604,8 @@ int launch_ema_sched(float* ema, const float* theta, long long n, const float* d
     template int launch_transpose<T>(const void*, void*, int, int, int, int, long long, long long, int, int, hipStream_t);  \
     template int launch_lora_wgrad<T>(const void*, int, const float*, int, int, int, int, int, int, int, float* const[3],   \
                                       float, float*, hipStream_t, int);                                                     \
+    template int launch_lora_wgrad_hr<T>(const void*, int, const void*, int, int, int, int, int, int, int, float* const[3], \
+                                         float, float*, hipStream_t, int);                                                  \
     template int launch_sumpool2<T>(const void*, void*, int, int, int, int, int, hipStream_t);                              \
     template int launch_mse_grad<T>(const void*, const float*, void*, float*, int, int, int, int, hipStream_t);                  \
     template int launch_im2col_all_T<T>(const void*, void*, int, int, int, int, int, int, int, int, int, int, hipStream_t);                    \

@@ -701,6 +701,20 @@ int op_lora_wgrad_t(const void* P, int ldp, const float* Q, int ldq, int M, int 
 }
 
 template <typename T>
+int op_lora_wgrad_hr_t(const void* P, int ldp, const void* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN, float* const out[3],
+                       float scale, int geglu_half, hipStream_t st) {
+    constexpr int VE = 16 / (int)sizeof(T);
+    MRISR_REQUIRE(ldp % VE == 0 && ldq % VE == 0 && ldq >= nmod * lora_hr_rp(r, (int)sizeof(T)),
+                  "LoRA wgrad (high rank): rows in whole 16-byte vectors, Q rows of nmod * rp columns (rp: the rank rounded up to the K tile)");
+    OpScratch sc;
+    float* scratch = static_cast<float*>(sc.alloc(lora_wgrad_hr_scratch_bytes(M, C, mode, r, nmod, secN, sizeof(T))));
+    if (!scratch) return 7;
+    TRY(launch_lora_wgrad_hr<T>(P, ldp, Q, ldq, M, C, mode, r, nmod, secN, out, scale, scratch, st, geglu_half));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+template <typename T>
 int op_conv_wgrad_t(const void* x, int xB, int xH, int xW, int cin_src, const void* dY, int ldy, int col0, int cout_src, int ks, int stride,
                     float* gW, float* gB, int cout, int cin, int geglu_half, hipStream_t st) {
     OpScratch sc;
@@ -827,6 +841,22 @@ int mrisr_op_lora_wgrad_geglu(int dtype, const void* P, int ldp, const float* Q,
     MRISR_REQUIRE(ldq % 4 == 0 && ldq >= r && al16(Q), "LoRA wgrad: Q rows in whole, aligned 16-byte vectors");
     float* const o[3] = {out, nullptr, nullptr};
     return BWD_DISPATCH(dtype, op_lora_wgrad_t, P, ldp, Q, ldq, M, 2 * half, 0, r, 1, 2 * half, o, scale, half, (hipStream_t)stream);
+    API_END
+}
+
+int mrisr_op_lora_wgrad_hr(int dtype, const void* P, int ldp, const void* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN,
+                           float* out0, float* out1, float* out2, float scale, int geglu_half, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    MRISR_REQUIRE(P && Q && M >= 1 && C >= 1 && (mode == 0 || mode == 1), "LoRA wgrad (high rank): null / empty operand, mode 0 / 1");
+    MRISR_REQUIRE(lora_rank_high(r) && nmod >= 1 && nmod <= 3, "LoRA wgrad (high rank): rank 32 .. 128 in steps of 16, <= 3 fused modules");
+    MRISR_REQUIRE(C % 8 == 0 && ldp >= C && al16(P) && al16(Q), "LoRA wgrad (high rank): C a multiple of 8, P rows of at least C, 16-byte aligned operands");
+    MRISR_REQUIRE(mode == 1 || (secN >= 8 && secN % 8 == 0 && C == nmod * secN), "LoRA wgrad (high rank, dB): C = nmod sections of whole vectors");
+    MRISR_REQUIRE(geglu_half == 0 || (mode == 0 && nmod == 1 && geglu_half % 16 == 0 && C == 2 * geglu_half),
+                  "LoRA wgrad (high rank): the GEGLU interleave is for dB of one [2 * half] projection, half a multiple of 16");
+    float* const out[3] = {out0, nmod > 1 ? out1 : nullptr, nmod > 2 ? out2 : nullptr};
+    MRISR_REQUIRE(!geglu_half || out0, "LoRA wgrad (high rank, GEGLU): out");
+    return BWD_DISPATCH(dtype, op_lora_wgrad_hr_t, P, ldp, Q, ldq, M, C, mode, r, nmod, secN, out, scale, geglu_half, (hipStream_t)stream);
     API_END
 }
 

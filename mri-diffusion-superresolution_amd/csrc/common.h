@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <string>
 
+#include "lora_hr.h"
+
 namespace mrisr {
 
 // ---------------------------------------------------------------------------------------------
@@ -314,6 +316,11 @@ __host__ __device__ __forceinline__ int geglu_raw_row(int packed, int half) {
     return ((packed >> 4) & 1) * half + (packed >> 5) * 16 + (packed & 15);
 }
 size_t lora_wgrad_scratch_bytes(int M, int C, int nq, int elem_size);
+// rank 32 .. 128 (lora_hr.h): Q in the engine's type, module j's columns at j * lora_hr_rp(r, sizeof(T))
+template <typename T>
+int launch_lora_wgrad_hr(const void* P, int ldp, const void* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN,
+                         float* const out[3], float scale, float* scratch, hipStream_t st, int geglu_half = 0);
+size_t lora_wgrad_hr_scratch_bytes(int M, int C, int mode, int r, int nmod, int secN, int elem_size);
 template <typename T> int launch_sumpool2(const void* src, void* dst, int B, int H, int W, int C, int accumulate, hipStream_t st);
 template <typename T>
 int launch_mse_grad(const void* pred, const float* tgt, void* dpred, float* loss, int B, int C, int H, int W, hipStream_t st);

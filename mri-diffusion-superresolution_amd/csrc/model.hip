@@ -180,20 +180,30 @@ struct Packer {
         l.geglu_half = geglu ? ntot / 2 : 0;
         l.mod_names = mods;
         for (auto& mod : mods) l.mod_lora.push_back(m.find(mod + ".lora_A.default.weight") ? 1 : 0);
-        const int ktot = k;
         float* lbuf = nullptr;
+        int ktot = k;
         if (any_lora && fused_lora) {
             // one rank-r adapter slot per fused module (modules without an adapter keep zero A rows / B rows)
+            if (!lora_rank_low(rmod) && !lora_rank_high(rmod)) { set_error("LoRA rank 4 / 8 / 12 / 16 or 32 .. 128 in steps of 16: " + mods[0]); err = 6; return l; }
             l.r = rmod;
-            l.R = (int)mods.size() * rmod;
             l.secN = nmod0;
-            l.loraA = m.new_packed((size_t)l.R * k * sizeof(T), true);
-            lbuf = static_cast<float*>(m.new_packed((size_t)ntot * rmod * sizeof(float), true));
-            if (!l.loraA || !lbuf) { err = 4; return l; }
-            l.loraB = lbuf;
-            l.loraB_rw = lbuf;
+            if (lora_rank_high(rmod)) {  // the adapters as extra K columns of the projection
+                if (m.cfg.fp8_linears || m.cfg.fp8_attention || m.cfg.fp8_train) { set_error("LoRA rank above 16 with fp8: the fp8 LoRA rows are a 16-row buffer"); err = 6; return l; }
+                l.rp = lora_hr_rp(rmod, (int)sizeof(T));
+                l.R = lora_hr_Rp(rmod, (int)mods.size(), (int)sizeof(T));
+                ktot = k + l.R;
+                l.loraA = m.new_packed((size_t)l.R * k * sizeof(T), true);
+                if (!l.loraA) { err = 4; return l; }
+            } else {
+                l.R = (int)mods.size() * rmod;
+                l.loraA = m.new_packed((size_t)l.R * k * sizeof(T), true);
+                lbuf = static_cast<float*>(m.new_packed((size_t)ntot * rmod * sizeof(float), true));
+                if (!l.loraA || !lbuf) { err = 4; return l; }
+                l.loraB = lbuf;
+                l.loraB_rw = lbuf;
+            }
         }
-        l.w = m.new_packed((size_t)ntot * ktot * sizeof(T), false);
+        l.w = m.new_packed((size_t)ntot * ktot * sizeof(T), l.rp != 0);
         if (!l.w) { err = 4; return l; }
         bool has_bias = false;
         for (auto& mod : mods) has_bias |= m.find(mod + ".bias") != nullptr;
@@ -224,10 +234,13 @@ struct Packer {
                 const int r = (int)la->shape[0];
                 if (r != l.r || n != l.secN) { set_error("fused LoRA needs the same rank / width for every fused module: " + mod); err = 6; }
                 // A rows -> loraA[rcol .. rcol+r);  (alpha/r) * B -> f32 [n][r] rows of this module (GEGLU: interleaved like the weight rows)
+                if (err) return l;
                 if (launch_pack_rows<T>(static_cast<const float*>(la->data->p), r, k, l.loraA, k, rcol, 0, 0, 0, 1.0f, st)) err = 5;
-                if (launch_pack_rows<float>(static_cast<const float*>(lb->data->p), n, r, lbuf, r, row, 0, geglu ? 1 : 0, n / 2, m.lora_scale, st)) err = 5;
+                if (l.rp) {  // (alpha/r) * B -> columns k + rcol .. of this module's rows of w
+                    if (launch_pack_rows<T>(static_cast<const float*>(lb->data->p), n, r, l.w, ktot, row, lora_hr_wcol(k, rcol / l.rp, l.rp), geglu ? 1 : 0, n / 2, m.lora_scale, st)) err = 5;
+                } else if (launch_pack_rows<float>(static_cast<const float*>(lb->data->p), n, r, lbuf, r, row, 0, geglu ? 1 : 0, n / 2, m.lora_scale, st)) err = 5;
             }
-            if (fused_lora && any_lora) rcol += l.r;
+            if (fused_lora && any_lora) rcol += l.rp ? l.rp : l.r;
             if (const RawParam* b = m.find(mod + ".bias")) {
                 const float* bsrc = static_cast<const float*>(b->data->p);
                 if (geglu) {
@@ -357,7 +370,7 @@ struct Packer {
         }
         // fused middle (xtail.hip xattn_tail_kernel): to_q / to_out of attn2 read their row operand in accumulator order
         if (sizeof(T) == 2 && !err && x.C == 320 && m.cfg.num_heads == 8 && x.q2.n == 320 && x.q2.k == 320 && x.out2.n == 320 && x.out2.k == 320 &&
-            x.out1.n == 320 && x.out1.k == 320 && !m.cfg.fp8_linears) {
+            x.out1.n == 320 && x.out1.k == 320 && !m.cfg.fp8_linears && !x.q2.rp && !x.out2.rp && !x.out1.rp) {
             x.q2p = m.new_packed((size_t)320 * 320 * sizeof(T), false);
             x.out2p = m.new_packed((size_t)320 * 320 * sizeof(T), false);
             if (!x.q2p || !x.out2p) { err = 4; return x; }

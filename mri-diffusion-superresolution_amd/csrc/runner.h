@@ -233,6 +233,25 @@ struct Runner {
             if (!m.keep) m.arena.release(mk);
             return 0;
         }
+        if (lw.rp) {
+            // rank 32 .. 128: z = x A^T is one skinny GEMM (N = R, T-typed), and the adapter is R more K columns of the
+            // projection - y = [x | z] [W | sB]^T through the two-source A operand; every epilogue stays as it is, no lora_* field is set
+            MRISR_REQUIRE(!g.a1 && !g.c1 && !g.w8 && !g.ln_gamma, "high-rank LoRA: a plain one-source projection");
+            T* z = static_cast<T*>(alloc((size_t)M * lw.R * sizeof(T)));
+            if (!z) return 7;
+            if (z_out) *z_out = reinterpret_cast<float*>(z);
+            GemmArgs zg;
+            zg.a0 = x; zg.c0 = lw.k; zg.lda0 = lda;
+            zg.w = lw.loraA; zg.M = M; zg.N = lw.R; zg.K = lw.k;
+            zg.out = z; zg.ldo = lw.R; zg.no_rp = 1;
+            zg.alg_flops = 2.0 * M * (double)lw.R * lw.k;
+            TRY(run_gemm(zg));
+            g.a1 = z; g.c1 = lw.R; g.lda1 = lw.R; g.K = lw.k + lw.R; g.no_rp = 1;
+            g.alg_flops = 2.0 * M * (double)lw.n * g.K;
+            TRY(run_gemm(g));
+            if (!m.keep) m.arena.release(mk);
+            return 0;
+        }
         // LoRA: the rank-r up-projection (alpha/r) B z is accumulated in the projection GEMM's epilogue.  z = x A^T is
         // computed inside the same kernel (bf16 buffer-addressed tiles, un-split); otherwise by one bandwidth-bound
         // pass over x (launch_lora_down) that hands z over through HBM.

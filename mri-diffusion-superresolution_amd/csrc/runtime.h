@@ -92,6 +92,10 @@ struct LinW {  // packed [n][k] in compute dtype, bias f32 (GEGLU: interleaved)
     // already scaled by lora_alpha/r; output column n uses z columns (n / secN) * r .. +r.  loraB / loraBT follow the row order of w
     // (geglu_half: interleaved)
     int r = 0, R = 0, secN = 1;
+    // rank 32 .. 128: rp = r rounded up to the K tile, R = nmod * rp; loraA is [R][k] with module j's rows at j * rp, and
+    // w is [n][k + R]: W, then (alpha/r) B_j in columns k + j * rp on module j's rows.  No loraB / loraAT; wT is [k][n + R] = [W^T | A^T]
+    int rp = 0;
+    int kw() const { return rp ? k + R : k; }  // row pitch of w
     void* loraA = nullptr;
     const float* loraB = nullptr;
     // fp8 copies for the row-panel kernel (cfg.fp8_linears; K = 320 / 640 only): e4m3 rows + one f32 scale per row

@@ -45,6 +45,29 @@ __global__ void lora_refresh_kernel(const float* __restrict__ A, const float* __
     }
 }
 
+// rank 32 .. 128: the same adapter into the packed layout - loraA [R][k], the sB columns of w [n][k + R], loraBT [R][ntot]
+// and the A^T columns of wT [k][ntot + R]; module `slot`'s rank-r block sits at slot * rp (the padding up to rp stays zero)
+template <typename T>
+__global__ void lora_refresh_hr_kernel(const float* __restrict__ A, const float* __restrict__ B, T* loraA, T* w, T* loraBT, T* wT, int r, int rp,
+                                       int R, int k, int n, int ntot, int slot, int row0, float s, int half) {
+    const long long na = (long long)r * k, nb = (long long)n * r;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < na + nb; i += (long long)gridDim.x * 256) {
+        if (i < na) {
+            const int q = (int)(i / k), c = (int)(i - (long long)q * k);
+            const T v = from_f32<T>(A[i]);
+            loraA[(size_t)(slot * rp + q) * k + c] = v;
+            if (wT) wT[(size_t)c * (ntot + R) + ntot + slot * rp + q] = v;  // (no dgrad bank: the context projections)
+        } else {
+            const long long j = i - na;
+            const int c = (int)(j / r), q = (int)(j - (long long)c * r);
+            const T v = from_f32<T>(s * B[j]);
+            const int row = row0 + (half ? geglu_packed_row(c, half) : c);
+            w[(size_t)row * (k + R) + k + slot * rp + q] = v;
+            loraBT[(size_t)(slot * rp + q) * ntot + row] = v;
+        }
+    }
+}
+
 template <typename F>
 static void for_each_xf(Model& m, F f) {
     for (auto& lv : m.down) for (auto& x : lv.xf) f(x);
@@ -93,9 +116,10 @@ static void pack_conv_dgrad(Model& m, ConvW& c, hipStream_t st, int& err) {
 template <typename T>
 static void pack_lin_t(Model& m, LinW& l, bool repack, hipStream_t st, int& err) {
     if (!l.w || (l.wT && !repack)) return;
-    if (!l.wT) l.wT = m.new_packed((size_t)l.n * l.k * sizeof(T), false);
+    const int ldt = l.rp ? l.n + l.R : l.n;  // high rank: [k][n + R] = [W^T | A^T], the A^T columns written by lora_refresh
+    if (!l.wT) l.wT = m.new_packed((size_t)ldt * l.k * sizeof(T), l.rp != 0);
     if (!l.wT) { err = 4; return; }
-    if (launch_transpose<T>(l.w, l.wT, l.n, l.k, l.k, l.n, 0, 0, 1, l.n, st)) err = 5;
+    if (launch_transpose<T>(l.w, l.wT, l.n, l.k, l.kw(), ldt, 0, 0, 1, l.n, st)) err = 5;
 }
 
 template <typename T>
@@ -136,8 +160,8 @@ static int train_prepare_t(Model& m, hipStream_t st) {
         }
         if (!l->loraBT) {
             l->loraBT = m.new_packed((size_t)l->R * l->n * sizeof(T), true);
-            l->loraAT = static_cast<float*>(m.new_packed((size_t)l->k * l->R * sizeof(float), true));
-            if (!l->loraBT || !l->loraAT) return 4;
+            if (!l->rp) l->loraAT = static_cast<float*>(m.new_packed((size_t)l->k * l->R * sizeof(float), true));
+            if (!l->loraBT || (!l->rp && !l->loraAT)) return 4;
         }
     }
     // conv adapters follow ALL linear adapters (whose offsets are therefore the same with and without them): resnets in walk order,
@@ -188,6 +212,15 @@ int Model::lora_refresh(hipStream_t st) {
             const float* B = theta + l->offB[j];
             const long long total = (long long)l->r * l->k + (long long)l->secN * l->r;
             const unsigned blocks = (unsigned)((total + 255) / 256);
+            if (l->rp) {  // the same launch refreshes the sB columns of w and the A^T columns of wT
+                if (cfg.compute_dtype == MRISR_F32)
+                    hipLaunchKernelGGL(lora_refresh_hr_kernel<float>, dim3(blocks), dim3(256), 0, st, A, B, static_cast<float*>(l->loraA), static_cast<float*>(l->w),
+                                       static_cast<float*>(l->loraBT), static_cast<float*>(l->wT), l->r, l->rp, l->R, l->k, l->secN, l->n, (int)j, row0, lora_scale, l->geglu_half);
+                else
+                    hipLaunchKernelGGL(lora_refresh_hr_kernel<bf16>, dim3(blocks), dim3(256), 0, st, A, B, static_cast<bf16*>(l->loraA), static_cast<bf16*>(l->w),
+                                       static_cast<bf16*>(l->loraBT), static_cast<bf16*>(l->wT), l->r, l->rp, l->R, l->k, l->secN, l->n, (int)j, row0, lora_scale, l->geglu_half);
+                continue;
+            }
             if (cfg.compute_dtype == MRISR_F32)
                 hipLaunchKernelGGL(lora_refresh_kernel<float>, dim3(blocks), dim3(256), 0, st, A, B, static_cast<float*>(l->loraA), l->loraAT,
                                    l->loraB_rw, static_cast<float*>(l->loraBT), l->r, l->R, l->k, l->secN, l->n, (int)j, row0, lora_scale, l->geglu_half);
@@ -366,12 +399,48 @@ struct Trainer : Runner<T> {
         GemmArgs g;
         bool in_kernel = false, dx_done = false;
         TRY(wgrad_linear(lw, x, ldx, dY, ldy, M));  // (full-parameter training only)
+        if (lw.rp) {
+            // rank 32 .. 128: dz = dY (sB) is one GEMM on [R][n], dX (+)= [dY | dz] [W | A] one GEMM over K = n + R on wT, and
+            // dB = dY^T z, dA = dz^T x go through lora_wgrad_hr; z and dz are T-typed
+            MRISR_REQUIRE(z && lw.loraBT && m.grad && (!need_dx || lw.wT), "adapter backward state");
+            const int nmod = (int)lw.mod_names.size();
+            T* dzt = static_cast<T*>(alloc((size_t)M * lw.R * sizeof(T)));
+            const size_t sb = std::max(lora_wgrad_hr_scratch_bytes(M, lw.n, 0, lw.r, nmod, lw.secN, sizeof(T)),
+                                       lora_wgrad_hr_scratch_bytes(M, lw.k, 1, lw.r, nmod, lw.secN, sizeof(T)));
+            float* scratch = static_cast<float*>(alloc(sb));
+            if (!dzt || !scratch) return 7;
+            GemmArgs zg;
+            zg.a0 = dY; zg.c0 = lw.n; zg.lda0 = ldy;
+            zg.w = lw.loraBT; zg.M = M; zg.N = lw.R; zg.K = lw.n;
+            zg.out = dzt; zg.ldo = lw.R; zg.no_rp = 1;
+            TRY(R::run_gemm(zg));
+            if (!dry) {
+                float *oA[3] = {nullptr, nullptr, nullptr}, *oB[3] = {nullptr, nullptr, nullptr};
+                for (int j = 0; j < nmod; ++j) {
+                    if (!lw.mod_lora[j]) continue;
+                    oA[j] = m.grad + lw.offA[j];
+                    oB[j] = m.grad + lw.offB[j];
+                }
+                TRY(launch_lora_wgrad_hr<T>(dY, ldy, z, lw.R, M, lw.n, 0, lw.r, nmod, lw.secN, oB, m.lora_scale, scratch, st, lw.geglu_half));
+                TRY(launch_lora_wgrad_hr<T>(x, ldx, dzt, lw.R, M, lw.k, 1, lw.r, nmod, lw.secN, oA, 1.0f, scratch, st));
+            }
+            if (!need_dx) return 0;
+            g.a0 = dY; g.c0 = lw.n; g.lda0 = ldy;
+            g.a1 = dzt; g.c1 = lw.R; g.lda1 = lw.R;
+            g.w = lw.wT; g.M = M; g.N = lw.k; g.K = lw.n + lw.R; g.no_rp = 1;
+            if (acc) { g.resid = dX; g.ldr = lw.k; }
+            g.out = dX; g.ldo = lw.k;
+            return R::run_gemm(g);
+        }
         if (need_dx) {
             MRISR_REQUIRE(lw.wT, "linear dgrad weights");
             g.a0 = dY; g.c0 = lw.n; g.lda0 = ldy;
             g.w = lw.wT; g.M = M; g.N = lw.k; g.K = lw.n;
             if (acc) { g.resid = dX; g.ldr = lw.k; }
             g.out = dX; g.ldo = lw.k;
+            // the row-panel kernel fuses LoRA only at rank 4, as in the forward: a K = 320 / 640 dgrad with R = 8 .. 16 was planned onto
+            // it and then refused at launch
+            if (lw.R && lw.r != 4) g.no_rp = 1;
             TRY(gemm_choose(g, sizeof(T) == 2));
             // as in the forward: dz = dY (s B) can ride along the dgrad GEMM (the <= 16 rows of s B^T as extra weight rows)
             in_kernel = lw.R && sizeof(T) == 2 && lw.R <= 16 && g.splitk == 1 && g.tile >= 14 && lora_in_kernel();

@@ -72,7 +72,7 @@ EXPORTS = [
     "mrisr_prof_enable", "mrisr_prof_reset", "mrisr_prof_report",
     "mrisr_op_conv3x3", "mrisr_op_conv3x3_sc", "mrisr_op_ff_proj", "mrisr_op_linear", "mrisr_op_ln_linear", "mrisr_op_linear_fp8", "mrisr_op_mlp", "mrisr_op_groupnorm", "mrisr_op_layernorm", "mrisr_op_attention",
     "mrisr_op_attention_bwd",
-    "mrisr_op_groupnorm_bwd", "mrisr_op_layernorm_bwd", "mrisr_op_geglu", "mrisr_op_pointwise_bwd", "mrisr_op_lora_wgrad", "mrisr_op_lora_wgrad_geglu",
+    "mrisr_op_groupnorm_bwd", "mrisr_op_layernorm_bwd", "mrisr_op_geglu", "mrisr_op_pointwise_bwd", "mrisr_op_lora_wgrad", "mrisr_op_lora_wgrad_geglu", "mrisr_op_lora_wgrad_hr",
     "mrisr_op_transpose", "mrisr_op_softmax_bwd", "mrisr_op_small_dense_bwd", "mrisr_op_conv_wgrad", "mrisr_op_conv_dgrad",
     "mrisr_op_conv_lora_down", "mrisr_op_conv_lora_dgrad", "mrisr_op_conv3x3_lora",
     "mrisr_fit_create", "mrisr_fit_destroy", "mrisr_fit_set_step", "mrisr_fit_get_step", "mrisr_fit_num_captures", "mrisr_fit_micro",
@@ -113,6 +113,7 @@ def lib() -> C.CDLL:
         L.mrisr_op_pointwise_bwd.argtypes = [I, I, P, P, P, P, Q, I, I, I, I, I, I, I, P]
         L.mrisr_op_lora_wgrad.argtypes = [I, P, I, P, I, I, I, I, I, I, I, P, P, P, F, P]
         L.mrisr_op_lora_wgrad_geglu.argtypes = [I, P, I, P, I, I, I, I, P, F, P]
+        L.mrisr_op_lora_wgrad_hr.argtypes = [I, P, I, P, I, I, I, I, I, I, I, P, P, P, F, I, P]
         L.mrisr_op_transpose.argtypes = [I, P, P, I, I, I, I, Q, Q, I, I, P]
         L.mrisr_op_softmax_bwd.argtypes = [I, P, P, P, I, Q, I, F, P]
         L.mrisr_op_small_dense_bwd.argtypes = [I, I, P, I, P, I, I, I, I, I, P, I, P, P, I, P]

@@ -65,6 +65,22 @@ class _ControlNetOutput:
         self.mid_block_res_sample = mid
 
 
+LORA_RANKS_LOW = (4, 8, 12, 16)
+LORA_RANKS_HIGH = (32, 48, 64, 80, 96, 112, 128)
+
+
+def check_lora_rank(rank, conv: bool = False) -> int:
+    """The ranks an un-merged adapter may have: 4, 8, 12, 16 everywhere; on the linear targets (``to_q`` / ``to_k`` / ``to_v`` / ``to_out.0``,
+    ``ff.net.0.proj``, ``ff.net.2``) also the multiples of 16 from 32 to 128.  ``conv=True``: an adapter on a resnet 3x3
+    conv, which stays at 16 or below.  Pure Python, no device; returns the rank, raises ``ValueError`` otherwise."""
+    ok = LORA_RANKS_LOW if conv else LORA_RANKS_LOW + LORA_RANKS_HIGH
+    if isinstance(rank, bool) or not isinstance(rank, int) or rank not in ok:
+        what = "conv LoRA rank (resnet 3x3 adapters stay at 16 or below)" if conv else "LoRA rank"
+        raise ValueError(f"{what} {rank!r} is not supported: accepted are 4, 8, 12, 16" + ("" if conv else " and the multiples of 16 from 32 to 128 "
+                         "(32, 48, 64, 80, 96, 112, 128)"))
+    return rank
+
+
 def _c_cfg(cfg: UNetConfig, compute_dtype, lora_rank, lora_fused, flash, fp8=False, fp8_attention=False, fp8_train=False) -> L.UNetCfg:
     c = L.UNetCfg()
     c.in_channels, c.out_channels = cfg.in_channels, cfg.out_channels
@@ -100,6 +116,12 @@ class _DeviceModel:
         """``fp8`` / ``fp8_attention`` / ``fp8_train``: BASELINE configs[4] - OCP e4m3 operands on the fp8 MFMA for the K = 320 (``"all"``:
         and 640) projections incl. the LoRA targets, for Q K^T / P V of every attention, and for the FORWARD of the training step
         (backward in bf16, straight through).  Modes of the bf16 engine; off by default."""
+        if lora_rank:  # before anything touches the device: a rank no kernel takes is refused here, not at the first forward
+            check_lora_rank(lora_rank)
+            if lora_rank > LORA_RANKS_LOW[-1] and lora_fused:
+                for flag, on in (("fp8", fp8), ("fp8_attention", fp8_attention), ("fp8_train", fp8_train)):
+                    if on:
+                        raise ValueError(f"lora_rank={lora_rank} cannot be combined with {flag}: the fp8 LoRA rows are a 16-row buffer")
         if not torch.cuda.is_available():
             raise L.MrisrError("mrisr needs an AMD GPU (gfx950); there is no CPU fallback")
         cfg = config if isinstance(config, UNetConfig) else (UNetConfig() if config is None else UNetConfig.from_oracle_like(config))
@@ -160,6 +182,7 @@ class _DeviceModel:
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
         """diffusers key names; peft LoRA keys ``<module>.lora_{A,B}.default.weight``."""
         fn = L.lib().mrisr_model_set_param
+        self._check_adapter_ranks(sd)  # before any GPU work
         for k, v in sd.items():
             # LoRA keys in any of peft's / diffusers' on-disk forms are accepted (adapter name stripped, "base_model.model." or
             # "unet." prefix); everything else must be a diffusers UNet key as is
@@ -172,6 +195,17 @@ class _DeviceModel:
         L.check(L.lib().mrisr_model_finalize(self._h, L.stream_ptr()))  # raises on missing keys
         self._finalized = True
         return self
+
+    def _check_adapter_ranks(self, sd) -> None:
+        """Ranks of the adapters in ``sd``, read from the shapes of their ``lora_A`` tensors ([r, k] on a linear, [r, cin, 3, 3] on a conv)."""
+        for k, v in sd.items():
+            if ".lora_A." not in k or not hasattr(v, "shape"):
+                continue
+            r = int(v.shape[0])
+            check_lora_rank(r, conv=len(v.shape) == 4)
+            if r > LORA_RANKS_LOW[-1] and self._ccfg.lora_fused and self.lora_rank != r:
+                raise ValueError(f"{k}: adapter of rank {r} loaded into a model built with lora_rank={self.lora_rank}, lora_fused=True; "
+                                 f"build the model with lora_rank={r}")
 
     @property
     def num_parameters(self) -> int:

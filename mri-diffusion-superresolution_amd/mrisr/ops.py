@@ -246,6 +246,15 @@ def lora_wgrad(P, Q, M, Cc, mode, r, nmod, secN, outs, scale=1.0, ldp=None, ldq=
                                         mode, r, nmod, secN, _p(outs[0]), _p(outs[1]), _p(outs[2]), scale, L.stream_ptr()))
 
 
+def lora_wgrad_hr(P, Q, M, Cc, mode, r, nmod, secN, outs, scale=1.0, ldp=None, ldq=None, geglu_half=0):
+    """``lora_wgrad`` at rank 32 .. 128 (multiples of 16): P [M, ldp] (T), Q [M, ldq] of the same type with module j's ``r`` columns at
+    ``j * rp``, ``rp`` = ``r`` rounded up to 64 (bf16) / 32 (f32); ``outs`` as there.  ``geglu_half``: dB of ``ff.net.0.proj`` (P's columns
+    in the 16-wide interleave, ``outs[0]`` [2*half, r] in raw row order)."""
+    outs = list(outs) + [None] * (3 - len(outs))
+    L.check(L.lib().mrisr_op_lora_wgrad_hr(_dt(P), _p(P), P.shape[1] if ldp is None else ldp, _p(Q), Q.shape[1] if ldq is None else ldq, M, Cc,
+                                           mode, r, nmod, secN, _p(outs[0]), _p(outs[1]), _p(outs[2]), scale, geglu_half, L.stream_ptr()))
+
+
 def geglu_packed_rows(half: int) -> torch.Tensor:
     """Packed row of every raw row of ``ff.net.0.proj`` ([2*half] rows: value half, then gate half): raw row ``g * half + j`` is stored at
     ``(j >> 4) * 32 + (j & 15) + 16 g`` - (value, gate) interleaved in blocks of 16.  ``packed[perm] = raw`` packs, ``packed[perm]`` unpacks."""

@@ -3,7 +3,7 @@
 SD-1.5 UNet + r=4 LoRA, [B,4,32,32] latents, forward + MSE + backward + all-reduce(flat LoRA grads) + clip + AdamW.
 Not the headline metric (bench.py is) - a secondary line for DESIGN.md.
 
-  python tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--dtype bf16] [--profile] [--lora-ff] [--lora-conv]
+  python tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--dtype bf16] [--profile] [--lora-ff] [--lora-conv] [--lora-rank R]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py --gpus N
 """
 import argparse
@@ -57,6 +57,7 @@ def main():
                                                            "target set)")
     ap.add_argument("--lora-conv", action="store_true", help="rank-4 adapters on conv1 / conv2 of all 22 resnets as well (the attention + resnet-conv "
                                                              "target set; with --lora-ff: attention + feed-forward + resnet convs)")
+    ap.add_argument("--lora-rank", type=int, default=4, help="rank of every adapter (mrisr.check_lora_rank: 4 .. 16, 32 .. 128 in steps of 16; conv adapters up to 16)")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -73,18 +74,19 @@ def main():
     from mrisr import _lib as L
     from mrisr import params as P
     cfg = mrisr.UNetConfig()
+    R = mrisr.check_lora_rank(args.lora_rank, conv=args.lora_conv)
     sd = P.random_state_dict(P.unet_param_shapes(cfg), 20260501, dev)  # same weights on every rank
-    sd.update(P.random_state_dict(P.lora_param_shapes(cfg, 4), 20260504, dev))
+    sd.update(P.random_state_dict(P.lora_param_shapes(cfg, R), 20260504, dev))
     if args.lora_ff:
-        sd.update(P.random_state_dict(P.lora_ff_param_shapes(cfg, 4), 20260505, dev))
+        sd.update(P.random_state_dict(P.lora_ff_param_shapes(cfg, R), 20260505, dev))
     if args.lora_conv:
-        sd.update(P.random_state_dict(P.lora_conv_param_shapes(cfg, 4), 20260508, dev))
+        sd.update(P.random_state_dict(P.lora_conv_param_shapes(cfg, R), 20260508, dev))
     f8 = dict(fp8=True, fp8_attention=True, fp8_train=True) if args.fp8 else {}
     if args.train_controlnet:
         sd = P.random_state_dict(P.unet_param_shapes(cfg), 20260501, dev)
         unet = mrisr.UNet2DConditionModel(cfg, compute_dtype=args.dtype)
     else:
-        unet = mrisr.UNet2DConditionModel(cfg, compute_dtype=args.dtype, lora_rank=4, lora_alpha=4, lora_fused=True, **f8)
+        unet = mrisr.UNet2DConditionModel(cfg, compute_dtype=args.dtype, lora_rank=R, lora_alpha=R, lora_fused=True, **f8)
     unet.load_state_dict(sd)
     tr = mrisr.LoRATrainer(unet, lr=1e-4)
     B, h = args.batch, args.latent
@@ -144,9 +146,9 @@ def main():
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * el / args.steps, 3),
            "dtype": args.dtype + (" (fp8 e4m3 forward: K=320 projections + attention; bf16 backward)" if args.fp8 else ""), "data": "synthetic", "losses": [round(v, 5) for v in losses],
            "workspace_GiB": round(unet.workspace_bytes / 2**30, 2),
-           "config": {"workload": f"SD-1.5 UNet + LoRA r=4 fine-tune step, [{B},4,{h},{h}] per GPU, all-reduce of "
+           "config": {"workload": f"SD-1.5 UNet + LoRA r={R} fine-tune step, [{B},4,{h},{h}] per GPU, all-reduce of "
                                   f"{tr.num_trainable} f32 grads" + (f" + trainable Adapter_XL ({atr.num_trainable} f32 grads)" if atr else "") + (f"; TRAINABLE ControlNet ({ctr.num_trainable} f32 grads), UNet frozen" if ctr else ""),
-                      "adapter_features": bool(intra), "adapter_trained": atr is not None, "lora_ff": bool(args.lora_ff), "lora_conv": bool(args.lora_conv)}}
+                      "adapter_features": bool(intra), "adapter_trained": atr is not None, "lora_rank": R, "lora_ff": bool(args.lora_ff), "lora_conv": bool(args.lora_conv)}}
     if args.profile and rank == 0:
         lib = L.lib()
         lib.mrisr_prof_reset()

@@ -87,6 +87,10 @@ void mrisr_model_destroy(mrisr_model* m);
 int mrisr_model_set_param(mrisr_model* m, const char* key, const float* data, const int64_t* shape, int ndim,
                           int is_device);
 int mrisr_model_set_lora_scale(mrisr_model* m, float scale); /* lora_alpha / r */
+/* use_dora != 0: a DoRA handle (peft use_dora=True).  Every linear that carries lora_A / lora_B must then carry
+ * <module>.lora_magnitude_vector.default.weight [out_features] too, and computes y = b + m / ||W + s B A||_row o (x W^T + s (x A^T) B^T).
+ * Linear targets of a UNet handle only; not with the fp8 modes.  Call before mrisr_model_finalize. */
+int mrisr_model_set_dora(mrisr_model* m, int use_dora);
 /* Re-lays weights out for the kernels (NHWC filter order, fused QKV, GEGLU interleave, LoRA tails, ...).
  * Must be called after the last set_param and before forward; may be called again after updating params. */
 int mrisr_model_finalize(mrisr_model* m, void* stream);
@@ -517,6 +521,17 @@ int mrisr_op_lora_wgrad_geglu(int dtype, const void* P, int ldp, const float* Q,
  * bf16 runs on the MFMA pipe (lora_wgrad_hr_kernel), f32 walks the streaming kernel over 16 columns of Q at a time */
 int mrisr_op_lora_wgrad_hr(int dtype, const void* P, int ldp, const void* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN,
                            float* out0, float* out1, float* out2, float scale, int geglu_half, void* stream);
+/* DoRA.  W [n][k], A [r][k], B [n][r], mag [n]: f32 in PyTorch's row order.  g[dst(j)] = mag[j] / ||W[j,:] + scale (B A)[j,:]||_2 (f32), and row
+ * dst(j) of out (T, pitch ld >= k) = g W[j,:] - or, merged != 0, g (W + scale B A)[j,:] - rounded once from the f32 product.  dst(j) = j, or
+ * with geglu_half > 0 (n = 2 * geglu_half) the 16-wide (value, gate) interleave of ff.net.0.proj.  r: 4 / 8 / 12 / 16 or 32 .. 128 in steps of 16 */
+int mrisr_op_dora_scale(int dtype, const float* W, const float* A, const float* B, const float* mag, float scale, float* g, void* out, int ld,
+                        int n, int k, int r, int geglu_half, int merged, void* stream);
+/* gm[c] += ( sum_m P[m][src(c)] (Y[m][src(c)] - R[m][src(c)]) - bias[src(c)] sum_m P[m][src(c)] ) / mag[c]: the gradient of a DoRA magnitude from
+ * P = dY and the projection's output Y (less the residual R its epilogue added, less its bias).  P, Y, R: T, row-major [M][C] with pitches ldp,
+ * ldy, ldr >= C; R and bias may be NULL; C a multiple of 8.  src(c) = c, or with geglu_half > 0 (C = 2 * geglu_half) the interleaved column of raw
+ * row c: bias is indexed like the columns, gm and mag (f32 [C]) in raw order.  No atomics: the bits repeat from launch to launch */
+int mrisr_op_dora_mag_grad(int dtype, const void* P, int ldp, const void* Y, int ldy, const void* R, int ldr, const float* bias, const float* mag,
+                           float* gm, int M, int C, int geglu_half, void* stream);
 /* dst[z][c][r] = src[z][r][c] for r < r_valid, 0 for r_valid <= r < R (T; pitches ld_src >= C, ld_dst >= R; batch strides in elements) */
 int mrisr_op_transpose(int dtype, const void* src, void* dst, int R, int C, int ld_src, int ld_dst, int64_t bs_src, int64_t bs_dst,
                        int batch, int r_valid, void* stream);

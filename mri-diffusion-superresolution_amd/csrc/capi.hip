@@ -59,6 +59,12 @@ int mrisr_model_set_lora_scale(mrisr_model* m, float scale) {
     m->finalized = false;
     return 0;
 }
+int mrisr_model_set_dora(mrisr_model* m, int use_dora) {
+    MRISR_REQUIRE(m, "null handle");
+    m->dora = use_dora != 0;
+    m->finalized = false;
+    return 0;
+}
 int mrisr_model_finalize(mrisr_model* m, void* stream) {
     API_BEGIN
     MRISR_REQUIRE(m, "null handle");

@@ -715,6 +715,27 @@ int op_lora_wgrad_hr_t(const void* P, int ldp, const void* Q, int ldq, int M, in
 }
 
 template <typename T>
+int op_dora_scale_t(const float* W, const float* A, const float* B, const float* mag, float s, float* g, void* out, int ld, int n, int k, int r,
+                    int geglu_half, int merged, hipStream_t st) {
+    TRY(launch_dora_scale<T>(W, A, B, mag, s, g, out, ld, 0, n, k, r, geglu_half, merged, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+template <typename T>
+int op_dora_mag_grad_t(const void* P, int ldp, const void* Y, int ldy, const void* R, int ldr, const float* bias, const float* mag, float* gm, int M,
+                       int C, int geglu_half, hipStream_t st) {
+    constexpr int VE = 16 / (int)sizeof(T);
+    MRISR_REQUIRE(ldp % VE == 0 && ldy % VE == 0 && (!R || ldr % VE == 0), "DoRA magnitude gradient: row pitches in whole 16-byte vectors");
+    OpScratch sc;
+    float* scratch = static_cast<float*>(sc.alloc(dora_mag_grad_scratch_bytes(M, C, sizeof(T))));
+    if (!scratch) return 7;
+    TRY(launch_dora_mag_grad<T>(P, ldp, Y, ldy, R, ldr, bias, mag, gm, M, C, geglu_half, scratch, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+template <typename T>
 int op_conv_wgrad_t(const void* x, int xB, int xH, int xW, int cin_src, const void* dY, int ldy, int col0, int cout_src, int ks, int stride,
                     float* gW, float* gB, int cout, int cin, int geglu_half, hipStream_t st) {
     OpScratch sc;
@@ -857,6 +878,31 @@ int mrisr_op_lora_wgrad_hr(int dtype, const void* P, int ldp, const void* Q, int
     float* const out[3] = {out0, nmod > 1 ? out1 : nullptr, nmod > 2 ? out2 : nullptr};
     MRISR_REQUIRE(!geglu_half || out0, "LoRA wgrad (high rank, GEGLU): out");
     return BWD_DISPATCH(dtype, op_lora_wgrad_hr_t, P, ldp, Q, ldq, M, C, mode, r, nmod, secN, out, scale, geglu_half, (hipStream_t)stream);
+    API_END
+}
+
+int mrisr_op_dora_scale(int dtype, const float* W, const float* A, const float* B, const float* mag, float scale, float* g, void* out, int ld,
+                        int n, int k, int r, int geglu_half, int merged, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    MRISR_REQUIRE(W && A && B && mag && g && out && n >= 1 && k >= 1, "DoRA scale: null / empty operand");
+    MRISR_REQUIRE(al16(W) && al16(A) && al16(B) && al16(mag) && al16(g) && al16(out), "DoRA scale: 16-byte aligned operands");
+    MRISR_REQUIRE(lora_rank_low(r) || lora_rank_high(r), "DoRA scale: rank 4 / 8 / 12 / 16 or 32 .. 128 in steps of 16");
+    MRISR_REQUIRE(ld >= k, "DoRA scale: the output pitch covers a row");
+    MRISR_REQUIRE(geglu_half == 0 || (geglu_half % 16 == 0 && n == 2 * geglu_half), "DoRA scale: the GEGLU interleave is for n = 2 * half rows, half a multiple of 16");
+    return BWD_DISPATCH(dtype, op_dora_scale_t, W, A, B, mag, scale, g, out, ld, n, k, r, geglu_half, merged ? 1 : 0, (hipStream_t)stream);
+    API_END
+}
+
+int mrisr_op_dora_mag_grad(int dtype, const void* P, int ldp, const void* Y, int ldy, const void* R, int ldr, const float* bias, const float* mag,
+                           float* gm, int M, int C, int geglu_half, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    MRISR_REQUIRE(P && Y && mag && gm && M >= 1 && C >= 1, "DoRA magnitude gradient: null / empty operand");
+    MRISR_REQUIRE(C % 8 == 0 && ldp >= C && ldy >= C && (!R || ldr >= C), "DoRA magnitude gradient: C a multiple of 8, rows of at least C");
+    MRISR_REQUIRE(al16(P) && al16(Y) && al16(R) && al16(bias) && al16(mag) && al16(gm), "DoRA magnitude gradient: 16-byte aligned operands");
+    MRISR_REQUIRE(geglu_half == 0 || (geglu_half % 16 == 0 && C == 2 * geglu_half), "DoRA magnitude gradient: the GEGLU interleave is for C = 2 * half, half a multiple of 16");
+    return BWD_DISPATCH(dtype, op_dora_mag_grad_t, P, ldp, Y, ldy, R, ldr, bias, mag, gm, M, C, geglu_half, (hipStream_t)stream);
     API_END
 }
 

@@ -321,6 +321,27 @@ template <typename T>
 int launch_lora_wgrad_hr(const void* P, int ldp, const void* Q, int ldq, int M, int C, int mode, int r, int nmod, int secN,
                          float* const out[3], float scale, float* scratch, hipStream_t st, int geglu_half = 0);
 size_t lora_wgrad_hr_scratch_bytes(int M, int C, int mode, int r, int nmod, int secN, int elem_size);
+// ---- DoRA (dora.hip) ----
+// g[row_off + dst(j)] = mag[j] / || W[j,:] + s (B A)[j,:] ||, and (out non-null) row row_off + dst(j) of out (T, pitch ld) = g W[j,:] or, merged,
+// g (W + s B A)[j,:].  W [n][k], A [r][k], B [n][r], mag [n]: f32 in PyTorch's row order; dst = the GEGLU interleave when geglu_half > 0
+template <typename T>
+int launch_dora_scale(const float* W, const float* A, const float* B, const float* mag, float s, float* g, void* out, int ld, int row_off, int n,
+                      int k, int r, int geglu_half, int merged, hipStream_t st);
+// dst[(row_off + dst(j)) * ld + col_off + q] = g[row_off + dst(j)] * s * B[j][q]
+template <typename T>
+int launch_dora_pack_b(const float* B, const float* g, float s, void* dst, int ld, int row_off, int col_off, int n, int r, int geglu_half,
+                       hipStream_t st);
+// gm[c] += (sum_m P[m][src(c)] (Y - R)[m][src(c)] - bias[src(c)] sum_m P[m][src(c)]) / mag[c]; R / bias optional; src = the GEGLU interleave
+// (bias is indexed like the columns, gm / mag in raw order).  scratch: dora_mag_grad_scratch_bytes(M, C, sizeof(T)) bytes
+template <typename T>
+int launch_dora_mag_grad(const void* P, int ldp, const void* Y, int ldy, const void* R, int ldr, const float* bias, const float* mag, float* gm,
+                         int M, int C, int geglu_half, float* scratch, hipStream_t st);
+size_t dora_mag_grad_scratch_bytes(int M, int C, int elem_size);
+// the B views of one trained DoRA module, scaled per row (see dora.hip), and this step's dB into the gradient with the same factor
+template <typename T>
+int launch_dora_refresh_b(const float* B, const float* g, float s, float* loraB, void* w, int ldw, int wcol, void* loraBT, int ntot, int bt_row0,
+                          int row0, int n, int r, int geglu_half, hipStream_t st);
+int launch_dora_rowscale_add(const float* tmp, const float* g, float* out, int row0, int n, int r, int geglu_half, hipStream_t st);
 template <typename T> int launch_sumpool2(const void* src, void* dst, int B, int H, int W, int C, int accumulate, hipStream_t st);
 template <typename T>
 int launch_mse_grad(const void* pred, const float* tgt, void* dpred, float* loss, int B, int C, int H, int W, hipStream_t st);

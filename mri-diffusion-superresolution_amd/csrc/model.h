@@ -67,6 +67,7 @@ struct Model {
     bool is_controlnet = false;
     std::map<std::string, RawParam> raw;
     float lora_scale = 1.0f;
+    bool dora = false;  // DoRA handle (mrisr_model_set_dora): every adapted linear carries a magnitude vector
     bool finalized = false;
     std::vector<std::unique_ptr<DevBuf>> packed;
 

@@ -103,6 +103,7 @@ struct Packer {
         const RawParam* lb = la ? m.find(name + ".lora_B.default.weight") : nullptr;
         const bool fused_lora = m.cfg.lora_rank > 0 && m.cfg.lora_fused;
         const int r = la ? (int)la->shape[0] : 0;
+        if (la && m.dora) { set_error("DoRA covers the linear targets only: conv adapter on " + name); err = 6; return c; }
         if (la && lb) {
             if (c.ks != 3 || la->numel() != (int64_t)r * c.cin * 9 || lb->numel() != (int64_t)c.cout * r || (int)lb->shape[0] != c.cout) {
                 set_error("conv LoRA: lora_A [r, cin, 3, 3] / lora_B [cout, r, 1, 1] expected on " + name);
@@ -212,6 +213,10 @@ struct Packer {
             bias = static_cast<float*>(m.new_packed((size_t)ntot * sizeof(float), true));
             if (!bias) { err = 4; return l; }
         }
+        if (m.dora && any_lora && fused_lora) {  // g = m / ||W + s B A|| per packed row (rows of modules without an adapter: unused)
+            l.dora_g = static_cast<float*>(m.new_packed((size_t)ntot * sizeof(float), true));
+            if (!l.dora_g) { err = 4; return l; }
+        }
         int row = 0, rcol = 0;
         for (auto& mod : mods) {
             const RawParam* w = m.find(mod + ".weight");
@@ -219,24 +224,33 @@ struct Packer {
             const float* wsrc = static_cast<const float*>(w->data->p);
             const RawParam* la = m.find(mod + ".lora_A.default.weight");
             const RawParam* lb = m.find(mod + ".lora_B.default.weight");
+            const RawParam* mg = dora_magnitude(mod, la && lb, n);
+            if (err) return l;
             std::unique_ptr<DevBuf> merged;
             if (la && lb && !fused_lora) {
-                // merged mode: W' = W + s * B A, computed in f32 on the device by the f32 GEMM itself
-                merged.reset(new DevBuf());
-                if (merged->reserve((size_t)n * k * sizeof(float), false)) { err = 4; return l; }
-                if (merge_lora(wsrc, static_cast<const float*>(la->data->p), static_cast<const float*>(lb->data->p),
-                               static_cast<float*>(merged->p), n, k, (int)la->shape[0]))
-                    err = 6;
-                wsrc = static_cast<const float*>(merged->p);
+                // merged mode: W' = W + s * B A (DoRA: g (W + s B A)), computed in f32 on the device
+                wsrc = merge_adapter(wsrc, la, lb, mg, merged, n, k);
+                if (!wsrc) return l;
             }
-            if (launch_pack_rows<T>(wsrc, n, k, l.w, ktot, row, 0, geglu ? 1 : 0, n / 2, 1.0f, st)) err = 5;
+            if (mg && fused_lora) {  // DoRA, adapter apart: the rows of this module are g W
+                if (launch_dora_scale<T>(wsrc, static_cast<const float*>(la->data->p), static_cast<const float*>(lb->data->p),
+                                         static_cast<const float*>(mg->data->p), m.lora_scale, l.dora_g, l.w, ktot, row, n, k, (int)la->shape[0],
+                                         geglu ? n / 2 : 0, 0, st))
+                    err = 5;
+            } else if (launch_pack_rows<T>(wsrc, n, k, l.w, ktot, row, 0, geglu ? 1 : 0, n / 2, 1.0f, st)) err = 5;
             if (la && lb && fused_lora) {
                 const int r = (int)la->shape[0];
                 if (r != l.r || n != l.secN) { set_error("fused LoRA needs the same rank / width for every fused module: " + mod); err = 6; }
                 // A rows -> loraA[rcol .. rcol+r);  (alpha/r) * B -> f32 [n][r] rows of this module (GEGLU: interleaved like the weight rows)
                 if (err) return l;
                 if (launch_pack_rows<T>(static_cast<const float*>(la->data->p), r, k, l.loraA, k, rcol, 0, 0, 0, 1.0f, st)) err = 5;
-                if (l.rp) {  // (alpha/r) * B -> columns k + rcol .. of this module's rows of w
+                if (mg) {  // DoRA: g (alpha/r) B, into the same places
+                    if (l.rp ? launch_dora_pack_b<T>(static_cast<const float*>(lb->data->p), l.dora_g, m.lora_scale, l.w, ktot, row,
+                                                     lora_hr_wcol(k, rcol / l.rp, l.rp), n, r, geglu ? n / 2 : 0, st)
+                             : launch_dora_pack_b<float>(static_cast<const float*>(lb->data->p), l.dora_g, m.lora_scale, lbuf, r, row, 0, n, r,
+                                                         geglu ? n / 2 : 0, st))
+                        err = 5;
+                } else if (l.rp) {  // (alpha/r) * B -> columns k + rcol .. of this module's rows of w
                     if (launch_pack_rows<T>(static_cast<const float*>(lb->data->p), n, r, l.w, ktot, row, lora_hr_wcol(k, rcol / l.rp, l.rp), geglu ? 1 : 0, n / 2, m.lora_scale, st)) err = 5;
                 } else if (launch_pack_rows<float>(static_cast<const float*>(lb->data->p), n, r, lbuf, r, row, 0, geglu ? 1 : 0, n / 2, m.lora_scale, st)) err = 5;
             }
@@ -270,6 +284,28 @@ struct Packer {
     }
     // host-side helper for merged mode (load time only): W' = W + s*B*A via a tiny kernel
     int merge_lora(const float* w, const float* A, const float* B, float* out, int n, int k, int r);
+    // the magnitude of a DoRA module (null: not a DoRA module).  A DoRA handle wants one [n] vector on every adapted linear; any other
+    // handle wants none
+    const RawParam* dora_magnitude(const std::string& mod, bool adapted, int n) {
+        const RawParam* mg = m.find(mod + ".lora_magnitude_vector.default.weight");
+        if (mg && !m.dora) { set_error("DoRA magnitude on a handle that is not a DoRA handle (use_dora=True): " + mod); err = 6; return nullptr; }
+        if (!m.dora) return nullptr;
+        if (mg && !adapted) { set_error("DoRA magnitude without lora_A / lora_B: " + mod); err = 6; return nullptr; }
+        if (adapted && !mg) { set_error("DoRA adapter without its lora_magnitude_vector: " + mod); err = 6; return nullptr; }
+        if (mg && (mg->shape.size() != 1 || mg->numel() != n)) { set_error("DoRA magnitude must be [out_features]: " + mod); err = 6; return nullptr; }
+        return mg;
+    }
+    // merged mode: W + s B A - or, DoRA, g (W + s B A) with g = m / ||W + s B A|| per row - in f32 in `hold` (null: error)
+    const float* merge_adapter(const float* w, const RawParam* la, const RawParam* lb, const RawParam* mg, std::unique_ptr<DevBuf>& hold, int n, int k) {
+        hold.reset(new DevBuf());
+        if (hold->reserve(((size_t)n * k + (mg ? n : 0)) * sizeof(float), false)) { err = 4; return nullptr; }  // DoRA: g behind the rows
+        float* out = static_cast<float*>(hold->p);
+        const float *A = static_cast<const float*>(la->data->p), *B = static_cast<const float*>(lb->data->p);
+        const int r = (int)la->shape[0];
+        if (mg ? launch_dora_scale<float>(w, A, B, static_cast<const float*>(mg->data->p), m.lora_scale, out + (size_t)n * k, out, k, 0, n, k, r, 0, 1, st)
+               : merge_lora(w, A, B, out, n, k, r)) { err = 6; return nullptr; }
+        return out;
+    }
     // the f32 weight [n][k] a module multiplies by, as linear() packs it: the master copy, or - an adapter in merged mode (lora_fused = 0) -
     // W + s B A in `hold`
     const float* effective_f32(const std::string& mod, int n, int k, std::unique_ptr<DevBuf>& hold) {
@@ -278,11 +314,9 @@ struct Packer {
         const RawParam* la = m.find(mod + ".lora_A.default.weight");
         const RawParam* lb = m.find(mod + ".lora_B.default.weight");
         if (!(la && lb) || (m.cfg.lora_rank > 0 && m.cfg.lora_fused)) return static_cast<const float*>(w->data->p);
-        hold.reset(new DevBuf());
-        if (hold->reserve((size_t)n * k * sizeof(float), false)) { err = 4; return nullptr; }
-        if (merge_lora(static_cast<const float*>(w->data->p), static_cast<const float*>(la->data->p), static_cast<const float*>(lb->data->p),
-                       static_cast<float*>(hold->p), n, k, (int)la->shape[0])) { err = 6; return nullptr; }
-        return static_cast<const float*>(hold->p);
+        const RawParam* mg = dora_magnitude(mod, true, n);
+        if (err) return nullptr;
+        return merge_adapter(static_cast<const float*>(w->data->p), la, lb, mg, hold, n, k);
     }
 
     ResW resnet(const std::string& name) {
@@ -403,6 +437,10 @@ template <typename T>
 static int finalize_t(Model& m, hipStream_t st) {
     Packer<T> pk(m, st);
     const mrisr_unet_cfg& c = m.cfg;
+    if (m.dora) {
+        MRISR_REQUIRE(!m.is_controlnet, "DoRA on a ControlNet handle is not supported");
+        MRISR_REQUIRE(!c.fp8_linears && !c.fp8_attention && !c.fp8_train, "DoRA cannot be combined with the fp8 modes");
+    }
     if (!m.repacking) m.packed.clear();
     m.temb_mods.clear();
     m.tproj_total = 0;

@@ -111,6 +111,9 @@ struct LinW {  // packed [n][k] in compute dtype, bias f32 (GEGLU: interleaved)
     void* loraBT = nullptr;              // [R][n] compute dtype: (alpha/r) * B^T, zero outside the module's columns
     float* loraAT = nullptr;             // [k][R] f32: A^T (epilogue operand of the dgrad)
     float* loraB_rw = nullptr;           // writable alias of loraB (refreshed from the trainable vector)
+    // DoRA: g = m / ||W + s B A|| per row of w (f32 [n], row order of w); w rows and the B bank are stored scaled by it
+    float* dora_g = nullptr;
+    std::vector<long long> offM;         // offsets of the magnitudes of each module in the flat trainable vector (-1: none)
 };
 
 struct Act {  // NHWC activation (or token rows when H*W is the token count)

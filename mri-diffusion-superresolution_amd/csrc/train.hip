@@ -178,6 +178,20 @@ static int train_prepare_t(Model& m, hipStream_t st) {
         m.trainables.push_back(tb);
         off += tb.numel;
     }
+    // DoRA magnitudes follow ALL lora_A / lora_B tensors (whose offsets therefore do not depend on the flag): 1-D [out_features] per adapted
+    // module, in PyTorch's row order
+    for (LinW* l : m.lora_linears()) {
+        l->offM.assign(l->mod_names.size(), -1);
+        if (!l->dora_g) continue;
+        for (size_t j = 0; j < l->mod_names.size(); ++j) {
+            if (!l->mod_lora[j]) continue;
+            Model::Trainable tm{l->mod_names[j] + ".lora_magnitude_vector.default.weight", off, (long long)l->secN, l->secN, 1};
+            tm.ndim = 1; tm.shape[0] = l->secN; tm.shape[1] = tm.shape[2] = tm.shape[3] = 1;
+            l->offM[j] = off;
+            m.trainables.push_back(tm);
+            off += l->secN;
+        }
+    }
     m.n_trainable = off;
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     m.train_ready = true;
@@ -199,6 +213,28 @@ int Model::train_bind(float* theta_dev, float* grad_dev, hipStream_t st) {
     MRISR_REQUIRE(n_trainable == 0 || (theta_dev && grad_dev), "theta / grad device buffers");
     theta = theta_dev;
     grad = grad_dev;
+    return 0;
+}
+
+// DoRA, after the adapter views of `l` are written from theta: g = m / ||W + s B A|| from the f32 masters, then everything the
+// forward and the backward multiply by carries it - the rows of w (g W), the B views (g s B: loraB / the sB columns, loraBT) and the W^T part
+// of wT.  The A views stay as they are.  Launches only.
+template <typename T>
+static int dora_refresh_t(Model& m, LinW& l, hipStream_t st) {
+    int row0 = 0;
+    for (size_t j = 0; j < l.mod_names.size(); ++j, row0 += l.secN) {
+        if (!l.mod_lora[j]) continue;
+        const RawParam* w = m.find(l.mod_names[j] + ".weight");
+        MRISR_REQUIRE(w && l.offM[j] >= 0 && w->numel() == (int64_t)l.secN * l.k, "DoRA refresh: master weight / magnitude of " + l.mod_names[j]);
+        const float* A = m.theta + l.offA[j];
+        const float* B = m.theta + l.offB[j];
+        TRY(launch_dora_scale<T>(static_cast<const float*>(w->data->p), A, B, m.theta + l.offM[j], m.lora_scale, l.dora_g, l.w, l.kw(), row0, l.secN,
+                                 l.k, l.r, l.geglu_half, 0, st));
+        TRY(launch_dora_refresh_b<T>(B, l.dora_g, m.lora_scale, l.rp ? nullptr : l.loraB_rw, l.rp ? l.w : nullptr, l.kw(),
+                                     l.rp ? lora_hr_wcol(l.k, (int)j, l.rp) : 0, l.loraBT, l.n, (int)j * (l.rp ? l.rp : l.r), row0, l.secN, l.r,
+                                     l.geglu_half, st));
+    }
+    if (l.wT) TRY(launch_transpose<T>(l.w, l.wT, l.n, l.k, l.kw(), l.rp ? l.n + l.R : l.n, 0, 0, 1, l.n, st));
     return 0;
 }
 
@@ -228,6 +264,7 @@ int Model::lora_refresh(hipStream_t st) {
                 hipLaunchKernelGGL(lora_refresh_kernel<bf16>, dim3(blocks), dim3(256), 0, st, A, B, static_cast<bf16*>(l->loraA), l->loraAT,
                                    l->loraB_rw, static_cast<bf16*>(l->loraBT), l->r, l->R, l->k, l->secN, l->n, (int)j, row0, lora_scale, l->geglu_half);
         }
+        if (l->dora_g) TRY(cfg.compute_dtype == MRISR_F32 ? dora_refresh_t<float>(*this, *l, st) : dora_refresh_t<bf16>(*this, *l, st));
         // the fp8 copy of the adapters' A rows (inference through the fp8 projections after training steps)
         if (l->loraA8 && cfg.compute_dtype != MRISR_F32) TRY(launch_quant_rows_fp8(l->loraA, l->R, l->k, l->loraA8, l->loraA_scale, st));
     }
@@ -236,6 +273,15 @@ int Model::lora_refresh(hipStream_t st) {
         const float* B = theta + c->offLB;
         if (cfg.compute_dtype == MRISR_F32) TRY(launch_conv_lora_pack<float>(A, B, lora_scale, c->loraA, c->loraAd, c->loraB, c->loraBT, c->cin, c->cout, c->r, st));
         else TRY(launch_conv_lora_pack<bf16>(A, B, lora_scale, c->loraA, c->loraAd, c->loraB, c->loraBT, c->cin, c->cout, c->r, st));
+    }
+    // the K-permuted copies the fused middle reads (bf16, C = 320) follow the rows of a DoRA projection
+    if (dora) {
+        int rc = 0;
+        for_each_xf(*this, [&](XfW& x) {
+            if (x.q2p && x.q2.dora_g && !rc) rc = launch_pack_mlp_w2(x.q2.w, x.q2p, x.q2.n, x.q2.k, st);
+            if (x.out2p && x.out2.dora_g && !rc) rc = launch_pack_mlp_w2(x.out2.w, x.out2p, x.out2.n, x.out2.k, st);
+        });
+        TRY(rc);
     }
     MRISR_CHECK_HIP(hipGetLastError());
     ctx_valid = false;  // cached cross-attention K / V depend on attn2.to_k / to_v adapters
@@ -260,6 +306,7 @@ struct Trainer : Runner<T> {
     std::set<const void*> live;          // activations downstream of a trainable parameter
     std::vector<std::function<int()>> tape;
     std::map<const XfW*, float*> z_kv;   // adapter down-projections of the cached context K / V
+    std::map<const XfW*, const void*> y_kv;  // DoRA: the context K / V projections as rows [B * L][2C] (the cache itself is head-major)
 
     Trainer(Model& mm, hipStream_t s, bool d) : R(mm, s, d) {}
 
@@ -393,9 +440,42 @@ struct Trainer : Runner<T> {
     }
 
     // backward of y = x W^T + s B (A x):  dX (+)= dY W + (dY s B) A;  dA, dB accumulated into m.grad
+    // DoRA (lw.dora_g): the operands are already the scaled ones, so dz, dA and dX come out right as they are; this call's dB is reduced
+    // into scratch and enters the gradient with row j scaled by g[j] (dora_b_begin / dora_b_end), and the magnitude's gradient needs the
+    // projection's own output: yout (rows [M][n] of pitch ldyo, as the epilogue wrote them) and the residual yres it added (null: none)
+    int dora_b_begin(const LinW& lw, float** tmp) {  // zeroed scratch: module j's [secN][r] block at j * secN * r
+        const size_t bytes = lw.mod_names.size() * (size_t)lw.secN * lw.r * sizeof(float);
+        *tmp = static_cast<float*>(alloc(bytes));
+        if (!*tmp) return 7;
+        return zero(*tmp, bytes);
+    }
+    int dora_b_end(const LinW& lw, const float* tmp) {
+        const int nmod = (int)lw.mod_names.size();
+        const size_t per = (size_t)lw.secN * lw.r;
+        for (int j = 0; j < nmod; ++j)
+            if (lw.mod_lora[j]) TRY(launch_dora_rowscale_add(tmp + j * per, lw.dora_g, m.grad + lw.offB[j], j * lw.secN, lw.secN, lw.r, lw.geglu_half, st));
+        return 0;
+    }
+    int dora_mag_bwd(const LinW& lw, const void* dY, int ldy, int M, const void* yout, int ldyo, const void* yres, int ldres) {
+        MRISR_REQUIRE(yout && m.grad && m.theta, "DoRA backward: the projection's output rows");
+        const int nmod = (int)lw.mod_names.size();
+        float* scratch = static_cast<float*>(alloc(dora_mag_grad_scratch_bytes(M, lw.secN, sizeof(T))));
+        if (!scratch) return 7;
+        if (dry) return 0;
+        for (int j = 0; j < nmod; ++j) {
+            if (!lw.mod_lora[j]) continue;
+            const size_t c0 = (size_t)j * lw.secN;
+            TRY(launch_dora_mag_grad<T>(static_cast<const T*>(dY) + c0, ldy, static_cast<const T*>(yout) + c0, ldyo,
+                                        yres ? static_cast<const T*>(yres) + c0 : nullptr, ldres, lw.b ? lw.b + c0 : nullptr, m.theta + lw.offM[j],
+                                        m.grad + lw.offM[j], M, lw.secN, lw.geglu_half, scratch, st));
+        }
+        return 0;
+    }
     int linear_bwd(const LinW& lw, const void* x, int ldx, const float* z, const void* dY, int ldy, int M, void* dX, bool acc,
-                   bool need_dx) {
+                   bool need_dx, const void* yout = nullptr, int ldyo = 0, const void* yres = nullptr, int ldres = 0) {
         float* dz = nullptr;
+        float* tmpB = nullptr;
+        if (lw.dora_g && lw.R) TRY(dora_mag_bwd(lw, dY, ldy, M, yout, ldyo, yres, ldres));
         GemmArgs g;
         bool in_kernel = false, dx_done = false;
         TRY(wgrad_linear(lw, x, ldx, dY, ldy, M));  // (full-parameter training only)
@@ -409,6 +489,7 @@ struct Trainer : Runner<T> {
                                        lora_wgrad_hr_scratch_bytes(M, lw.k, 1, lw.r, nmod, lw.secN, sizeof(T)));
             float* scratch = static_cast<float*>(alloc(sb));
             if (!dzt || !scratch) return 7;
+            if (lw.dora_g) TRY(dora_b_begin(lw, &tmpB));
             GemmArgs zg;
             zg.a0 = dY; zg.c0 = lw.n; zg.lda0 = ldy;
             zg.w = lw.loraBT; zg.M = M; zg.N = lw.R; zg.K = lw.n;
@@ -419,10 +500,11 @@ struct Trainer : Runner<T> {
                 for (int j = 0; j < nmod; ++j) {
                     if (!lw.mod_lora[j]) continue;
                     oA[j] = m.grad + lw.offA[j];
-                    oB[j] = m.grad + lw.offB[j];
+                    oB[j] = tmpB ? tmpB + (size_t)j * lw.secN * lw.r : m.grad + lw.offB[j];
                 }
                 TRY(launch_lora_wgrad_hr<T>(dY, ldy, z, lw.R, M, lw.n, 0, lw.r, nmod, lw.secN, oB, m.lora_scale, scratch, st, lw.geglu_half));
                 TRY(launch_lora_wgrad_hr<T>(x, ldx, dzt, lw.R, M, lw.k, 1, lw.r, nmod, lw.secN, oA, 1.0f, scratch, st));
+                if (tmpB) TRY(dora_b_end(lw, tmpB));
             }
             if (!need_dx) return 0;
             g.a0 = dY; g.c0 = lw.n; g.lda0 = ldy;
@@ -451,6 +533,7 @@ struct Trainer : Runner<T> {
             const size_t sb = std::max(lora_wgrad_scratch_bytes(M, lw.n, lw.R, sizeof(T)), lora_wgrad_scratch_bytes(M, lw.k, lw.R, sizeof(T)));
             float* scratch = static_cast<float*>(alloc(sb));
             if (!dz || !scratch) return 7;
+            if (lw.dora_g) TRY(dora_b_begin(lw, &tmpB));
             if (in_kernel) {  // the dgrad first: it produces dz for the A gradient
                 g.lora_a = lw.loraBT; g.lora_R = lw.R; g.lora_zout = dz;
                 g.lora_zld = lw.R; g.lora_b = lw.loraAT; g.lora_r = lw.R; g.lora_secN = INT_MAX;
@@ -464,11 +547,12 @@ struct Trainer : Runner<T> {
                 for (int j = 0; j < nmod; ++j) {
                     if (!lw.mod_lora[j]) continue;
                     oA[j] = m.grad + lw.offA[j];
-                    oB[j] = m.grad + lw.offB[j];
+                    oB[j] = tmpB ? tmpB + (size_t)j * lw.secN * lw.r : m.grad + lw.offB[j];
                 }
                 // (ff.net.0.proj: dY columns in the GEGLU interleave, gradient rows in raw order - un-interleaved by the reduce's scatter)
                 TRY(launch_lora_wgrad<T>(dY, ldy, z, lw.R, M, lw.n, 0, lw.r, nmod, lw.secN, oB, m.lora_scale, scratch, st, lw.geglu_half));
                 TRY(launch_lora_wgrad<T>(x, ldx, dz, lw.R, M, lw.k, 1, lw.r, nmod, lw.secN, oA, 1.0f, scratch, st));
+                if (tmpB) TRY(dora_b_end(lw, tmpB));
             }
         }
         if (!need_dx || dx_done) return 0;
@@ -764,6 +848,14 @@ struct Trainer : Runner<T> {
             R::heads_args(&g, hb, q1, 0, k1, 0, vt1, 1, hb.N, hb.npad);
             TRY(R::linear(n1, M, C, xw.qkv, ACT_NONE, nullptr, 0, &g, nullptr, 0, &z_qkv));
         }
+        // DoRA: the magnitude's gradient reads a projection's output as rows; q / k / v survive head-major only, so a DoRA projection runs
+        // once more into rows (and proj_out's output is copied: later stages may add into it in place)
+        T *y_qkv = nullptr, *y_q2 = nullptr, *y_po = nullptr;
+        if (xw.qkv.dora_g) {
+            y_qkv = rows(3 * C);
+            if (!y_qkv) return 7;
+            TRY(R::linear(n1, M, C, xw.qkv, ACT_NONE, nullptr, 0, nullptr, y_qkv, 3 * C));
+        }
         AttnRec a1;
         a1.q = q1; a1.k = k1; a1.vt = vt1; a1.nk = hb.N; a1.nkpad = hb.npad;
         TRY(attention_t(hb, &a1, ao1));
@@ -774,6 +866,11 @@ struct Trainer : Runner<T> {
             R::heads_args(&g, hb, q2, 0, nullptr, 0, nullptr, 0, hb.N, hb.npad);
             TRY(R::linear(n2, M, C, xw.q2, ACT_NONE, nullptr, 0, &g, nullptr, 0, &z_q2));
         }
+        if (xw.q2.dora_g) {
+            y_q2 = rows(C);
+            if (!y_q2) return 7;
+            TRY(R::linear(n2, M, C, xw.q2, ACT_NONE, nullptr, 0, nullptr, y_q2, C));
+        }
         AttnRec a2;
         a2.q = q2; a2.k = xw.kc; a2.vt = xw.vtc; a2.nk = m.ctx_len; a2.nkpad = m.ctx_pad;
         TRY(attention_t(hb, &a2, ao2));
@@ -783,6 +880,11 @@ struct Trainer : Runner<T> {
         if (!dry) TRY(launch_geglu_fwd<T>(ffpre, ff, M, 4 * C, st));
         TRY(R::linear(ff, M, 4 * C, xw.ff2, ACT_NONE, t2, C, nullptr, t3, C, &z_f2));
         TRY(R::linear(t3, M, C, xw.proj_out, ACT_NONE, x.p, C, nullptr, o.p, C, &z_po));
+        if (xw.proj_out.dora_g) {
+            y_po = rows(C);
+            if (!y_po) return 7;
+            if (!dry) MRISR_CHECK_HIP(hipMemcpyAsync(y_po, o.p, (size_t)M * C * sizeof(T), hipMemcpyDeviceToDevice, st));
+        }
         *out = o;
         const bool x_live = is_live(x);
         if (!x_live && !has_lora(xw) && !full()) return 0;
@@ -790,6 +892,7 @@ struct Trainer : Runner<T> {
         const XfW* xp = &xw;
         const HeadBuf hbv = hb;
         float* zkv = z_kv.count(&xw) ? z_kv[&xw] : nullptr;
+        const void* ykv = y_kv.count(&xw) ? y_kv[&xw] : nullptr;
         tape.push_back([=]() -> int {
             const XfW& w = *xp;
             auto it = slots.find(o.p);
@@ -804,35 +907,35 @@ struct Trainer : Runner<T> {
             T* dkv = want_kv ? brows(Bc, 2 * C) : nullptr;
             if (!dt || !dn || !dao || !dq || !dff || !dpre || !dqkv || (want_kv && !dkv)) return 7;
             // o = proj_out(t3) + x
-            TRY(linear_bwd(w.proj_out, t3, C, z_po, dO, C, M, dt, false, true));
+            TRY(linear_bwd(w.proj_out, t3, C, z_po, dO, C, M, dt, false, true, y_po, C, x.p, C));
             // t3 = t2 + ff2(geglu(ff1(LN3(t2))))
-            TRY(linear_bwd(w.ff2, ff, 4 * C, z_f2, dt, C, M, dff, false, true));
+            TRY(linear_bwd(w.ff2, ff, 4 * C, z_f2, dt, C, M, dff, false, true, t3, C, t2, C));
             if (!dry) TRY(launch_geglu_bwd<T>(ffpre, dff, dpre, M, 4 * C, st));
-            TRY(linear_bwd(w.ff1, n3, C, z_f1, dpre, 8 * C, M, dn, false, true));
+            TRY(linear_bwd(w.ff1, n3, C, z_f1, dpre, 8 * C, M, dn, false, true, ffpre, 8 * C));
             TRY(ln_affine(t2, dn, w.ln3, M, C));
             if (!dry) TRY(launch_layernorm_bwd<T>(t2, dn, dt, w.ln3.g, M, C, 1e-5f, 1, st));
             // t2 = t1 + out2(attn(q2(LN2(t1)), K_ctx, V_ctx))
-            TRY(linear_bwd(w.out2, ao2, C, z_o2, dt, C, M, dao, false, true));
+            TRY(linear_bwd(w.out2, ao2, C, z_o2, dt, C, M, dao, false, true, t2, C, t1, C));
             TRY(attention_bwd(hbv, a2, dao, dq, C, dkv, dkv ? dkv + C : nullptr, 2 * C));
-            if (dkv) TRY(linear_bwd(w.kv2, m.ctx_rows, m.cfg.cross_attention_dim, zkv, dkv, 2 * C, Bc, nullptr, false, false));
-            TRY(linear_bwd(w.q2, n2, C, z_q2, dq, C, M, dn, false, true));
+            if (dkv) TRY(linear_bwd(w.kv2, m.ctx_rows, m.cfg.cross_attention_dim, zkv, dkv, 2 * C, Bc, nullptr, false, false, ykv, 2 * C));
+            TRY(linear_bwd(w.q2, n2, C, z_q2, dq, C, M, dn, false, true, y_q2, C));
             TRY(ln_affine(t1, dn, w.ln2, M, C));
             if (!dry) TRY(launch_layernorm_bwd<T>(t1, dn, dt, w.ln2.g, M, C, 1e-5f, 1, st));
             // t1 = t0 + out1(attn(qkv(LN1(t0))))
-            TRY(linear_bwd(w.out1, ao1, C, z_o1, dt, C, M, dao, false, true));
+            TRY(linear_bwd(w.out1, ao1, C, z_o1, dt, C, M, dao, false, true, t1, C, t0, C));
             TRY(attention_bwd(hbv, a1, dao, dqkv, 3 * C, dqkv + C, dqkv + 2 * C, 3 * C));
-            TRY(linear_bwd(w.qkv, n1, C, z_qkv, dqkv, 3 * C, M, dn, false, true));
+            TRY(linear_bwd(w.qkv, n1, C, z_qkv, dqkv, 3 * C, M, dn, false, true, y_qkv, 3 * C));
             TRY(ln_affine(t0, dn, w.ln1, M, C));
             if (!dry) TRY(launch_layernorm_bwd<T>(t0, dn, dt, w.ln1.g, M, C, 1e-5f, 1, st));
             // t0 = proj_in(GN(x))
             if (sx) {
-                TRY(linear_bwd(w.proj_in, xn.p, C, z_pi, dt, C, M, dn, false, true));
+                TRY(linear_bwd(w.proj_in, xn.p, C, z_pi, dt, C, M, dn, false, true, t0, C));
                 TRY(gn_affine(x, dn, w.norm, false, 1e-6f, gp, gns));
                 TRY(gn_bwd(x, nullptr, w.norm, false, 1e-6f, gp, gns, dn, sx->g, sx->written, nullptr, false));
                 sx->written = true;
                 if (!dry) TRY(launch_add_inplace<T>(sx->g, dO, (long long)x.numel(), st));
             } else if (w.proj_in.R) {
-                TRY(linear_bwd(w.proj_in, xn.p, C, z_pi, dt, C, M, nullptr, false, false));
+                TRY(linear_bwd(w.proj_in, xn.p, C, z_pi, dt, C, M, nullptr, false, false, t0, C));
             }
             m.arena.release(mk);
             return 0;
@@ -856,6 +959,11 @@ struct Trainer : Runner<T> {
             float* z = nullptr;
             rc = R::linear(m.ctx_rows, m.ws_B * m.ctx_len, m.cfg.cross_attention_dim, x.kv2, ACT_NONE, nullptr, 0, &g, nullptr, 0, &z);
             z_kv[&x] = z;
+            if (!rc && x.kv2.dora_g) {
+                void* y = alloc((size_t)m.ws_B * m.ctx_len * x.kv2.n * sizeof(T));
+                rc = y ? R::linear(m.ctx_rows, m.ws_B * m.ctx_len, m.cfg.cross_attention_dim, x.kv2, ACT_NONE, nullptr, 0, nullptr, y, x.kv2.n) : 7;
+                y_kv[&x] = y;
+            }
         });
         m.ctx_valid = false;  // the cache belongs to this step's adapters only
         return rc;

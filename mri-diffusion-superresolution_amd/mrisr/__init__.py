@@ -4,6 +4,7 @@ Importing the package does not need a GPU; constructing a model or calling an op
 ``MrisrError`` when the HIP library or device is missing.  There is no CPU fallback anywhere in this package."""
 from ._lib import LIB_PATH, MrisrError  # noqa: F401
 from .models import Adapter_XL, ControlNetModel, UNet2DConditionModel, UNetConfig, check_lora_rank  # noqa: F401
+from .models import check_dora, dora_magnitude_init, lora_scaling  # noqa: F401
 from .pipeline import (Sampler, check_cache, check_guidance, check_solver, decode_to_vis, get_res_shifting_latents, log_validation,  # noqa: F401
                        prepare_condition_image)
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler,  # noqa: F401

@@ -54,7 +54,7 @@ _lib: Optional[C.CDLL] = None
 # every symbol include/mrisr.h declares (tests check the .so exports all of them)
 EXPORTS = [
     "mrisr_last_error", "mrisr_version", "mrisr_unet_create", "mrisr_controlnet_create", "mrisr_model_destroy",
-    "mrisr_model_set_param", "mrisr_model_set_lora_scale", "mrisr_model_finalize", "mrisr_model_num_params",
+    "mrisr_model_set_param", "mrisr_model_set_lora_scale", "mrisr_model_set_dora", "mrisr_model_finalize", "mrisr_model_num_params",
     "mrisr_model_workspace_bytes", "mrisr_unet_forward", "mrisr_model_set_context", "mrisr_model_num_skips",
     "mrisr_model_skip_shape", "mrisr_controlnet_forward", "mrisr_controlnet_set_cond", "mrisr_adapter_create",
     "mrisr_adapter_destroy", "mrisr_adapter_set_param", "mrisr_adapter_finalize", "mrisr_adapter_forward",
@@ -72,7 +72,7 @@ EXPORTS = [
     "mrisr_prof_enable", "mrisr_prof_reset", "mrisr_prof_report",
     "mrisr_op_conv3x3", "mrisr_op_conv3x3_sc", "mrisr_op_ff_proj", "mrisr_op_linear", "mrisr_op_ln_linear", "mrisr_op_linear_fp8", "mrisr_op_mlp", "mrisr_op_groupnorm", "mrisr_op_layernorm", "mrisr_op_attention",
     "mrisr_op_attention_bwd",
-    "mrisr_op_groupnorm_bwd", "mrisr_op_layernorm_bwd", "mrisr_op_geglu", "mrisr_op_pointwise_bwd", "mrisr_op_lora_wgrad", "mrisr_op_lora_wgrad_geglu", "mrisr_op_lora_wgrad_hr",
+    "mrisr_op_groupnorm_bwd", "mrisr_op_layernorm_bwd", "mrisr_op_geglu", "mrisr_op_pointwise_bwd", "mrisr_op_lora_wgrad", "mrisr_op_lora_wgrad_geglu", "mrisr_op_lora_wgrad_hr", "mrisr_op_dora_scale", "mrisr_op_dora_mag_grad",
     "mrisr_op_transpose", "mrisr_op_softmax_bwd", "mrisr_op_small_dense_bwd", "mrisr_op_conv_wgrad", "mrisr_op_conv_dgrad",
     "mrisr_op_conv_lora_down", "mrisr_op_conv_lora_dgrad", "mrisr_op_conv3x3_lora",
     "mrisr_fit_create", "mrisr_fit_destroy", "mrisr_fit_set_step", "mrisr_fit_get_step", "mrisr_fit_num_captures", "mrisr_fit_micro",
@@ -114,6 +114,9 @@ def lib() -> C.CDLL:
         L.mrisr_op_lora_wgrad.argtypes = [I, P, I, P, I, I, I, I, I, I, I, P, P, P, F, P]
         L.mrisr_op_lora_wgrad_geglu.argtypes = [I, P, I, P, I, I, I, I, P, F, P]
         L.mrisr_op_lora_wgrad_hr.argtypes = [I, P, I, P, I, I, I, I, I, I, I, P, P, P, F, I, P]
+        L.mrisr_op_dora_scale.argtypes = [I, P, P, P, P, F, P, P, I, I, I, I, I, I, P]
+        L.mrisr_op_dora_mag_grad.argtypes = [I, P, I, P, I, P, I, P, P, P, I, I, I, P]
+        L.mrisr_model_set_dora.argtypes = [P, I]
         L.mrisr_op_transpose.argtypes = [I, P, P, I, I, I, I, Q, Q, I, I, P]
         L.mrisr_op_softmax_bwd.argtypes = [I, P, P, P, I, Q, I, F, P]
         L.mrisr_op_small_dense_bwd.argtypes = [I, I, P, I, P, I, I, I, I, I, P, I, P, P, I, P]

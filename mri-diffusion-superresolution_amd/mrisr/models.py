@@ -13,6 +13,7 @@ state-dict key names) and marshal device pointers.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -81,6 +82,81 @@ def check_lora_rank(rank, conv: bool = False) -> int:
     return rank
 
 
+def lora_scaling(rank, alpha, use_rslora: bool = False) -> float:
+    """The factor ``s`` of ``y = x W^T + s (x A^T) B^T``: ``lora_alpha / r`` (peft's default) or, ``use_rslora``, ``lora_alpha / sqrt(r)``
+    (rank-stabilised LoRA).  1.0 without a rank or without an alpha.  Pure Python, no device."""
+    if not rank or alpha is None:
+        return 1.0
+    return float(alpha) / (math.sqrt(rank) if use_rslora else rank)
+
+
+DORA_KEY = ".lora_magnitude_vector.default.weight"  # in memory, after the module name (peft >= 0.10; older: without ".weight")
+DORA_LINEAR_TARGETS = ("to_q", "to_k", "to_v", "to_out.0", "ff.net.0.proj", "ff.net.2", "proj_in", "proj_out")
+
+
+def check_dora(sd, use_dora: bool, is_controlnet: bool = False, fp8=False, fp8_attention: bool = False, fp8_train: bool = False) -> None:
+    """What a DoRA handle (``use_dora=True``) accepts, checked on the state dict alone: pure Python, no device; raises
+    ``ValueError``.  ``sd`` in any accepted key spelling (``lora_keys_from_disk`` normalises it); values need only a ``shape``.
+
+    * ``use_dora`` with ``fp8`` / ``fp8_attention`` / ``fp8_train``, or on a ControlNet handle: refused;
+    * a magnitude key without ``use_dora``: refused (the message names ``use_dora=True``);
+    * every module with ``lora_A`` / ``lora_B`` is a linear target and carries a magnitude of shape ``[out_features]``, and every
+      magnitude has its ``lora_A`` / ``lora_B``; a conv adapter (``conv1`` / ``conv2``) is refused."""
+    from .train import lora_keys_from_disk
+    sd = lora_keys_from_disk(dict(sd or {}))
+    mags = {k[: -len(DORA_KEY)]: v for k, v in sd.items() if k.endswith(DORA_KEY)}
+    if not use_dora:
+        if mags:
+            raise ValueError(f"{next(iter(mags))}: the state dict carries DoRA magnitudes (lora_magnitude_vector); build the model with use_dora=True")
+        return
+    for flag, on in (("fp8", fp8), ("fp8_attention", fp8_attention), ("fp8_train", fp8_train)):
+        if on:
+            raise ValueError(f"use_dora=True cannot be combined with {flag}: the fp8 weight copies do not carry the magnitude")
+    if is_controlnet:
+        raise ValueError("use_dora=True is not supported on a ControlNetModel: DoRA covers the UNet's linear targets")
+    mods = {}
+    for k, v in sd.items():
+        for ab in ("lora_A", "lora_B"):
+            if k.endswith(f".{ab}.default.weight"):
+                mods.setdefault(k[: -len(f".{ab}.default.weight")], {})[ab] = v
+    for m, ab in mods.items():
+        a, b = ab.get("lora_A"), ab.get("lora_B")
+        if m.endswith(("conv1", "conv2")) or (hasattr(a, "shape") and len(a.shape) == 4 and tuple(a.shape[2:]) != (1, 1)):
+            raise ValueError(f"{m}: a conv adapter in a use_dora=True state dict; DoRA covers the linear targets only")
+        if not m.endswith(DORA_LINEAR_TARGETS):
+            raise ValueError(f"{m}: not a DoRA target; accepted are {', '.join(DORA_LINEAR_TARGETS)}")
+        if m not in mags:
+            raise ValueError(f"{m}: lora_A / lora_B without {m}{DORA_KEY} in a use_dora=True state dict")
+    for m, v in mags.items():
+        ab = mods.get(m, {})
+        if "lora_A" not in ab or "lora_B" not in ab:
+            raise ValueError(f"{m}: a DoRA magnitude without its lora_A / lora_B")
+        n = int(ab["lora_B"].shape[0]) if hasattr(ab["lora_B"], "shape") else None
+        if hasattr(v, "shape") and (len(v.shape) != 1 or (n is not None and int(v.shape[0]) != n)):
+            raise ValueError(f"{m}: the DoRA magnitude must have shape [{n}] (one per output row), got {tuple(v.shape)}")
+
+
+def dora_magnitude_init(params, lora_state_dict, scale: float) -> Dict[str, torch.Tensor]:
+    """peft's DoRA initialisation, ``m = ||W + s B A||`` per output row, for every linear adapter of ``lora_state_dict``: f32 from f32 inputs,
+    rows in PyTorch's order (``ff.net.0.proj``: value half, then gate half).  Pure torch, runs on the CPU.  With these magnitudes the scale
+    ``m / ||W + s B A||`` is 1 and the DoRA model is the LoRA model of the same ``A`` / ``B``."""
+    from .train import lora_keys_from_disk
+    lora = lora_keys_from_disk(dict(lora_state_dict))
+    out = {}
+    for ka, a in lora.items():
+        if not ka.endswith(".lora_A.default.weight"):
+            continue
+        m = ka[: -len(".lora_A.default.weight")]
+        b = lora[m + ".lora_B.default.weight"]
+        w = params[m + ".weight"] if m + ".weight" in params else params[m + ".base_layer.weight"]
+        if a.ndim == 4 and tuple(a.shape[2:]) != (1, 1):
+            raise ValueError(f"{m}: DoRA covers the linear targets only, not conv adapters")
+        w2 = w.detach().to(torch.float32).reshape(w.shape[0], -1)
+        ba = b.detach().to(torch.float32).reshape(w.shape[0], -1) @ a.detach().to(torch.float32).reshape(a.shape[0], -1)
+        out[m + DORA_KEY] = torch.linalg.vector_norm(w2 + float(scale) * ba, dim=1)
+    return out
+
+
 def _c_cfg(cfg: UNetConfig, compute_dtype, lora_rank, lora_fused, flash, fp8=False, fp8_attention=False, fp8_train=False) -> L.UNetCfg:
     c = L.UNetCfg()
     c.in_channels, c.out_channels = cfg.in_channels, cfg.out_channels
@@ -112,10 +188,17 @@ class _DeviceModel:
 
     def __init__(self, config=None, compute_dtype="bf16", lora_rank: int = 0, lora_alpha: Optional[float] = None,
                  lora_fused: bool = True, flash_attention: bool = True, device="cuda", fp8=False, fp8_attention: bool = False,
-                 fp8_train: bool = False):
+                 fp8_train: bool = False, use_dora: bool = False, use_rslora: bool = False):
         """``fp8`` / ``fp8_attention`` / ``fp8_train``: BASELINE configs[4] - OCP e4m3 operands on the fp8 MFMA for the K = 320 (``"all"``:
         and 640) projections incl. the LoRA targets, for Q K^T / P V of every attention, and for the FORWARD of the training step
-        (backward in bf16, straight through).  Modes of the bf16 engine; off by default."""
+        (backward in bf16, straight through).  Modes of the bf16 engine; off by default.
+
+        ``use_rslora``: the LoRA scale is ``lora_alpha / sqrt(r)`` (``lora_scaling``).  ``use_dora``: the adapters are DoRA adapters - every
+        adapted linear carries a magnitude vector (``check_dora``).  Merged (``lora_fused=False``) is the form for
+        inference; un-merged the model also trains: ``LoRATrainer`` / ``fit`` then carry the magnitudes as 1-D trainable tensors after all
+        ``lora_A`` / ``lora_B``."""
+        self.use_dora, self.use_rslora = bool(use_dora), bool(use_rslora)
+        check_dora({}, self.use_dora, self._create == "mrisr_controlnet_create", fp8, fp8_attention, fp8_train)  # before any device work
         if lora_rank:  # before anything touches the device: a rank no kernel takes is refused here, not at the first forward
             check_lora_rank(lora_rank)
             if lora_rank > LORA_RANKS_LOW[-1] and lora_fused:
@@ -129,7 +212,7 @@ class _DeviceModel:
         self.device = torch.device(device)
         self.compute_dtype = L.torch_dtype(L.dtype_id(compute_dtype))
         self.lora_rank = lora_rank
-        self.lora_scale = (lora_alpha / lora_rank) if (lora_rank and lora_alpha is not None) else 1.0
+        self.lora_scale = lora_scaling(lora_rank, lora_alpha, use_rslora)
         self._params: Dict[str, torch.Tensor] = {}
         self._h = C.c_void_p()
         if (fp8 or fp8_attention or fp8_train) and L.dtype_id(compute_dtype) != L.MRISR_BF16:
@@ -183,15 +266,18 @@ class _DeviceModel:
         """diffusers key names; peft LoRA keys ``<module>.lora_{A,B}.default.weight``."""
         fn = L.lib().mrisr_model_set_param
         self._check_adapter_ranks(sd)  # before any GPU work
+        check_dora(sd, self.use_dora, self._create == "mrisr_controlnet_create", self.fp8, self.fp8_attention, self.fp8_train)
         for k, v in sd.items():
             # LoRA keys in any of peft's / diffusers' on-disk forms are accepted (adapter name stripped, "base_model.model." or
             # "unet." prefix); everything else must be a diffusers UNet key as is
-            if ".lora_A." in k or ".lora_B." in k:
+            if ".lora_A." in k or ".lora_B." in k or ".lora_magnitude_vector" in k:
                 from .train import lora_keys_from_disk
                 k = next(iter(lora_keys_from_disk({k: None})))
             self._params[k] = v
             L.push_param(fn, self._h, k, v)
         L.check(L.lib().mrisr_model_set_lora_scale(self._h, C.c_float(self.lora_scale)))
+        if self.use_dora:
+            L.check(L.lib().mrisr_model_set_dora(self._h, 1))
         L.check(L.lib().mrisr_model_finalize(self._h, L.stream_ptr()))  # raises on missing keys
         self._finalized = True
         return self

@@ -255,6 +255,27 @@ def lora_wgrad_hr(P, Q, M, Cc, mode, r, nmod, secN, outs, scale=1.0, ldp=None, l
                                            mode, r, nmod, secN, _p(outs[0]), _p(outs[1]), _p(outs[2]), scale, geglu_half, L.stream_ptr()))
 
 
+def dora_scale(W, A, B, mag, scale, dtype, ld=None, geglu_half=0, merged=False):
+    """``mrisr_op_dora_scale``: W [n, k], A [r, k], B [n, r], mag [n] f32 (raw row order) -> (g f32 [n], rows [n, ld] of ``dtype``), both in
+    the row order of the packed weight (``geglu_half``: the 16-wide interleave, ``geglu_packed_rows``).  Row ``dst(j)`` holds ``g W[j]`` or,
+    ``merged``, ``g (W + scale B A)[j]`` in its first k columns; the columns beyond k keep what ``rows`` was filled with (NaN)."""
+    n, k = W.shape
+    ld = k if ld is None else ld
+    g = torch.full((n,), float("nan"), dtype=torch.float32, device=W.device)
+    rows = torch.full((n, ld), float("nan"), dtype=dtype, device=W.device)
+    L.check(L.lib().mrisr_op_dora_scale(L.dtype_id(dtype), _p(W), _p(A), _p(B), _p(mag), scale, _p(g), _p(rows), ld, n, k, A.shape[0], geglu_half,
+                                        1 if merged else 0, L.stream_ptr()))
+    return g, rows
+
+
+def dora_mag_grad(P, Y, mag, gm, M, Cc, R=None, bias=None, ldp=None, ldy=None, ldr=None, geglu_half=0):
+    """``mrisr_op_dora_mag_grad``: adds ``(sum_m P (Y - R) - bias sum_m P) / mag`` into ``gm`` (f32 [C]).  P, Y, R: [M, ld*] of one dtype."""
+    L.check(L.lib().mrisr_op_dora_mag_grad(_dt(P), _p(P), P.shape[1] if ldp is None else ldp, _p(Y), Y.shape[1] if ldy is None else ldy, _p(R),
+                                           0 if R is None else (R.shape[1] if ldr is None else ldr), _p(bias), _p(mag), _p(gm), M, Cc, geglu_half,
+                                           L.stream_ptr()))
+    return gm
+
+
 def geglu_packed_rows(half: int) -> torch.Tensor:
     """Packed row of every raw row of ``ff.net.0.proj`` ([2*half] rows: value half, then gate half): raw row ``g * half + j`` is stored at
     ``(j >> 4) * 32 + (j & 15) + 16 g`` - (value, gate) interleaved in blocks of 16.  ``packed[perm] = raw`` packs, ``packed[perm]`` unpacks."""

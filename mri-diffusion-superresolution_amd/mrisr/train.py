@@ -46,7 +46,8 @@ def lora_keys_to_disk(sd: Dict[str, torch.Tensor], key_format: str = "peft") -> 
     if key_format == "memory":
         return dict(sd)
     pre = _KEY_PREFIX[key_format]
-    return {pre + k.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B."): v for k, v in sd.items()}
+    return {pre + k.replace(".lora_A.default.", ".lora_A.").replace(".lora_B.default.", ".lora_B.")
+            .replace(".lora_magnitude_vector.default.", ".lora_magnitude_vector."): v for k, v in sd.items()}
 
 
 def lora_keys_from_disk(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -60,6 +61,12 @@ def lora_keys_from_disk(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         for ab in ("lora_A", "lora_B"):
             if k.endswith(f".{ab}.weight"):
                 k = k[:-len(f".{ab}.weight")] + f".{ab}.default.weight"
+        # DoRA magnitudes: "<module>.lora_magnitude_vector[.default][.weight]" (older peft wrote a bare parameter, without ".weight")
+        mv = ".lora_magnitude_vector"
+        for tail in (mv + ".default.weight", mv + ".default", mv + ".weight", mv):
+            if k.endswith(tail):
+                k = k[:-len(tail)] + mv + ".default.weight"
+                break
         out[k] = v
     return out
 

@@ -3,7 +3,7 @@
 SD-1.5 UNet + r=4 LoRA, [B,4,32,32] latents, forward + MSE + backward + all-reduce(flat LoRA grads) + clip + AdamW.
 Not the headline metric (bench.py is) - a secondary line for DESIGN.md.
 
-  python tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--dtype bf16] [--profile] [--lora-ff] [--lora-conv] [--lora-rank R]
+  python tools/bench_train.py [--batch 32] [--steps 5] [--warmup 2] [--dtype bf16] [--profile] [--lora-ff] [--lora-conv] [--lora-rank R] [--dora]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py --gpus N
 """
 import argparse
@@ -58,6 +58,8 @@ def main():
     ap.add_argument("--lora-conv", action="store_true", help="rank-4 adapters on conv1 / conv2 of all 22 resnets as well (the attention + resnet-conv "
                                                              "target set; with --lora-ff: attention + feed-forward + resnet convs)")
     ap.add_argument("--lora-rank", type=int, default=4, help="rank of every adapter (mrisr.check_lora_rank: 4 .. 16, 32 .. 128 in steps of 16; conv adapters up to 16)")
+    ap.add_argument("--dora", action="store_true", help="DoRA adapters (use_dora=True, DESIGN section 19) on the linear targets: magnitudes at their "
+                                                        "initial value, trained with lora_A / lora_B; not with --lora-conv / --fp8")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -82,6 +84,9 @@ def main():
     if args.lora_conv:
         sd.update(P.random_state_dict(P.lora_conv_param_shapes(cfg, R), 20260508, dev))
     f8 = dict(fp8=True, fp8_attention=True, fp8_train=True) if args.fp8 else {}
+    if args.dora:  # peft's initialisation, m = ||W + s B A|| per row (s = lora_alpha / r = 1 here)
+        sd.update(mrisr.dora_magnitude_init(sd, {k: v for k, v in sd.items() if ".lora_" in k}, 1.0))
+        f8["use_dora"] = True
     if args.train_controlnet:
         sd = P.random_state_dict(P.unet_param_shapes(cfg), 20260501, dev)
         unet = mrisr.UNet2DConditionModel(cfg, compute_dtype=args.dtype)
@@ -148,7 +153,8 @@ def main():
            "workspace_GiB": round(unet.workspace_bytes / 2**30, 2),
            "config": {"workload": f"SD-1.5 UNet + LoRA r={R} fine-tune step, [{B},4,{h},{h}] per GPU, all-reduce of "
                                   f"{tr.num_trainable} f32 grads" + (f" + trainable Adapter_XL ({atr.num_trainable} f32 grads)" if atr else "") + (f"; TRAINABLE ControlNet ({ctr.num_trainable} f32 grads), UNet frozen" if ctr else ""),
-                      "adapter_features": bool(intra), "adapter_trained": atr is not None, "lora_rank": R, "lora_ff": bool(args.lora_ff), "lora_conv": bool(args.lora_conv)}}
+                      "adapter_features": bool(intra), "adapter_trained": atr is not None, "lora_rank": R, "lora_ff": bool(args.lora_ff), "lora_conv": bool(args.lora_conv),
+                      "dora": bool(args.dora)}}
     if args.profile and rank == 0:
         lib = L.lib()
         lib.mrisr_prof_reset()

@@ -12,8 +12,12 @@ extern "C" {
 #endif
 
 /* GEMM planner overrides (0 restores the planner): a split-K factor for every GEMM that can be split; one kernel
- * configuration for every GEMM; a specialised kernel (halo conv 41-45, weight-stationary 50-52, row-panel 60+) wherever
- * it is eligible. */
+ * configuration (a tile id) for every GEMM; a kernel of a specialised family (halo conv, 256-row halo conv, weight-stationary,
+ * row-panel) wherever it is eligible.  The tile ids, their families and template parameters are the lines of the tile
+ * registry in csrc/gemm.hip (TILES); nothing outside that file knows a tile number.  A forced tile that does not take a
+ * launch's form is refused with the reason, except that f32 / 2 GiB operands, 2 x 2 / sub-pixel convs and splits on a family
+ * without split-K move to the default tile of the family that takes them (gemm.hip: tile_for_launch), and that a launch with
+ * a 1x1 tail leaves a forced tile that cannot carry it to the planner. */
 void mrisr_debug_force_split(int splitk);
 void mrisr_debug_force_tile(int tile);
 void mrisr_debug_prefer_tile(int tile);

@@ -87,6 +87,13 @@ static int op_conv3x3_t(const mrisr_tensor* x, const mrisr_tensor* x2, const flo
 }
 
 extern "C" void mrisr_debug_force_tile(int t);
+// one tile forced for the GEMMs of one op call: the planner is back when the scope ends, however it ends
+struct ForcedTile {
+    explicit ForcedTile(int t) { mrisr_debug_force_tile(t); }
+    ~ForcedTile() { mrisr_debug_force_tile(0); }
+    ForcedTile(const ForcedTile&) = delete;
+    ForcedTile& operator=(const ForcedTile&) = delete;
+};
 
 // conv3x3(x) + bias + (W_sc [xs | xs2] + b_sc): a resnet's conv2 with its 1x1 conv_shortcut.  fused: ONE launch over K = [9 Cin | Cs] on the
 // concatenated bank (the shortcut as the 1x1 tail of the K loop, summed bias); otherwise the two launches it replaces - the shortcut GEMM
@@ -136,18 +143,15 @@ static int op_conv3x3_sc_t(const mrisr_tensor* x, const mrisr_tensor* x2, const 
         MRISR_CHECK_HIP(hipStreamSynchronize(st));
         g.w = w9.p; g.K = (int)K9; g.bias = bias; g.resid = y->data; g.ldr = cout;
     }
-    mrisr_debug_force_tile(tile);
+    ForcedTile forced(tile);
     g.splitk = splitk;
-    int rc = 0;
-    if (splitk <= 0) { g.splitk = 1; rc = gemm_choose(g, true); }
-    else if (tile <= 0) { const int sk = splitk; rc = gemm_choose(g, true); g.splitk = sk; }
-    if (!rc && g.splitk > 1) {
-        rc = part.reserve((size_t)g.splitk * g.M * g.N * sizeof(float), false);
+    if (splitk <= 0) { g.splitk = 1; TRY(gemm_choose(g, true)); }
+    else if (!tile) { const int sk = splitk; TRY(gemm_choose(g, true)); g.splitk = sk; }
+    if (g.splitk > 1) {
+        TRY(part.reserve((size_t)g.splitk * g.M * g.N * sizeof(float), false));
         g.partial = static_cast<float*>(part.p);
     }
-    if (!rc) rc = launch_gemm<T>(g, st);
-    mrisr_debug_force_tile(0);
-    if (rc) return rc;
+    TRY(launch_gemm<T>(g, st));
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -170,7 +174,6 @@ static int op_ff_proj_t(const mrisr_tensor* h, const mrisr_tensor* t, const mris
     MRISR_REQUIRE(t->shape[0] == M && x->shape[0] == M && x->shape[1] == C && y->shape[0] == M && y->shape[1] == C, "ff.net.2 + proj_out: row shapes");
     MRISR_REQUIRE(C % 64 == 0 && K4 % 64 == 0, "ff.net.2 + proj_out: widths that are multiples of 64");
     DevBuf bank, bsum, w2p, wpp, mid, part;
-    int rc = 0;
     if (fused) {
         const int Kt = K4 + C;
         TRY(bank.reserve((size_t)C * Kt * sizeof(T), false));
@@ -182,8 +185,8 @@ static int op_ff_proj_t(const mrisr_tensor* h, const mrisr_tensor* t, const mris
         g.a1 = t->data; g.c1 = C; g.lda1 = C;
         g.w = bank.p; g.M = M; g.N = C; g.K = Kt; g.bias = static_cast<const float*>(bsum.p);
         g.resid = x->data; g.ldr = C; g.out = y->data; g.ldo = C; g.no_rp = 1;
-        mrisr_debug_force_tile(tile);
-        rc = run_planned(g, part, st);
+        ForcedTile forced(tile);
+        TRY(run_planned(g, part, st));
     } else {
         TRY(w2p.reserve((size_t)C * K4 * sizeof(T), false));
         TRY(wpp.reserve((size_t)C * C * sizeof(T), false));
@@ -195,13 +198,11 @@ static int op_ff_proj_t(const mrisr_tensor* h, const mrisr_tensor* t, const mris
         g1.resid = t->data; g1.ldr = C; g1.out = mid.p; g1.ldo = C;
         g2.a0 = mid.p; g2.c0 = C; g2.lda0 = C; g2.w = wpp.p; g2.M = M; g2.N = C; g2.K = C; g2.bias = bp;
         g2.resid = x->data; g2.ldr = C; g2.out = y->data; g2.ldo = C;
-        mrisr_debug_force_tile(tile);
-        rc = run_planned(g1, part, st);
-        if (!rc) rc = hipStreamSynchronize(st) != hipSuccess;  // (`part` is reused)
-        if (!rc) rc = run_planned(g2, part, st);
+        ForcedTile forced(tile);
+        TRY(run_planned(g1, part, st));
+        MRISR_CHECK_HIP(hipStreamSynchronize(st));  // (`part` is reused)
+        TRY(run_planned(g2, part, st));
     }
-    mrisr_debug_force_tile(0);
-    if (rc) return rc;
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -312,18 +313,15 @@ static int op_conv3x3_lora_t(const mrisr_tensor* x, const float* w, const float*
     if (resid) { g.resid = resid->data; g.ldr = cout; }
     g.out = y->data; g.ldo = cout;
     g.lora_z = static_cast<const float*>(zb.p); g.lora_zld = r; g.lora_b = static_cast<const float*>(sb.p); g.lora_r = r; g.lora_secN = cout;
-    mrisr_debug_force_tile(tile);
+    ForcedTile forced(tile);
     g.splitk = splitk;
-    int rc = 0;
-    if (splitk <= 0) { g.splitk = 1; rc = gemm_choose(g, sizeof(T) == 2); }
-    else if (tile <= 0) { const int sk = splitk; rc = gemm_choose(g, sizeof(T) == 2); g.splitk = sk; }
-    if (!rc && g.splitk > 1) {
-        rc = part.reserve((size_t)g.splitk * g.M * g.N * sizeof(float), false);
+    if (splitk <= 0) { g.splitk = 1; TRY(gemm_choose(g, sizeof(T) == 2)); }
+    else if (!tile) { const int sk = splitk; TRY(gemm_choose(g, sizeof(T) == 2)); g.splitk = sk; }
+    if (g.splitk > 1) {
+        TRY(part.reserve((size_t)g.splitk * g.M * g.N * sizeof(float), false));
         g.partial = static_cast<float*>(part.p);
     }
-    if (!rc) rc = launch_gemm<T>(g, st);
-    mrisr_debug_force_tile(0);
-    if (rc) return rc;
+    TRY(launch_gemm<T>(g, st));
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -342,12 +340,9 @@ int mrisr_op_conv3x3(const mrisr_tensor* x, const mrisr_tensor* x2, const float*
     TRY(op_dtype_ok(x));
     TRY(gemm_prepare());
     MRISR_REQUIRE(x->layout == MRISR_NHWC && y && y->layout == MRISR_NHWC && y->dtype == x->dtype, "NHWC in/out, same dtype");
-    mrisr_debug_force_tile(tile);
-    int rc = x->dtype == MRISR_F32
-                 ? op_conv3x3_t<float>(x, x2, w_oihw_dev, bias_dev, cout, stride, upsample, act, splitk, y, (hipStream_t)stream)
-                 : op_conv3x3_t<bf16>(x, x2, w_oihw_dev, bias_dev, cout, stride, upsample, act, splitk, y, (hipStream_t)stream);
-    mrisr_debug_force_tile(0);
-    return rc;
+    ForcedTile forced(tile);
+    return x->dtype == MRISR_F32 ? op_conv3x3_t<float>(x, x2, w_oihw_dev, bias_dev, cout, stride, upsample, act, splitk, y, (hipStream_t)stream)
+                                 : op_conv3x3_t<bf16>(x, x2, w_oihw_dev, bias_dev, cout, stride, upsample, act, splitk, y, (hipStream_t)stream);
     API_END
 }
 
@@ -403,15 +398,13 @@ int mrisr_op_linear(const mrisr_tensor* x, const float* w_dev, const float* bias
     g.a0 = x->data; g.c0 = K; g.lda0 = K; g.w = wp.p; g.M = M; g.N = n; g.K = K; g.bias = bias; g.act = act;
     g.out = y->data; g.ldo = (int)y->shape[1];
     g.splitk = splitk;
-    if (splitk <= 0) { g.splitk = 1; mrisr_debug_force_tile(tile); TRY(gemm_choose(g, !f32)); }
+    ForcedTile forced(tile);
+    if (splitk <= 0) { g.splitk = 1; TRY(gemm_choose(g, !f32)); }
     if (g.splitk > 1) {
         TRY(part.reserve((size_t)g.splitk * M * n * sizeof(float), false));
         g.partial = static_cast<float*>(part.p);
     }
-    mrisr_debug_force_tile(tile);
-    int rc = f32 ? launch_gemm<float>(g, st) : launch_gemm<bf16>(g, st);
-    mrisr_debug_force_tile(0);
-    if (rc) return rc;
+    TRY(f32 ? launch_gemm<float>(g, st) : launch_gemm<bf16>(g, st));
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
     API_END
@@ -1104,13 +1097,13 @@ extern "C" int mrisr_bench_gemm(int M, int N, int K, int conv, int B, int H, int
     g.w = wb.p; g.M = M; g.N = N; g.K = K; g.bias = (const float*)bias.p; g.out = ob.p; g.ldo = N;
     if (const char* e = getenv("MRISR_BENCH_NOSTORE")) { if (e[0] == '1') g.out_mode = OUT_NONE; }  // experiment: epilogue without the store
     g.splitk = splitk;
-    if (splitk <= 0) { g.splitk = 1; mrisr_debug_force_tile(tile); TRY(gemm_choose(g, true)); }
+    ForcedTile forced(tile);
+    if (splitk <= 0) { g.splitk = 1; TRY(gemm_choose(g, true)); }
     if (g.splitk > 1) {
         TRY(part.reserve((size_t)g.splitk * M * N * 4, false));
         g.partial = (float*)part.p;
     }
-    mrisr_debug_force_tile(tile);
-    for (int i = 0; i < 2; ++i) { int rc = launch_gemm<bf16>(g, st); if (rc) { mrisr_debug_force_tile(0); return rc; } }
+    for (int i = 0; i < 2; ++i) TRY(launch_gemm<bf16>(g, st));
     hipEvent_t e0, e1;
     MRISR_CHECK_HIP(hipEventCreate(&e0));
     MRISR_CHECK_HIP(hipEventCreate(&e1));
@@ -1118,7 +1111,6 @@ extern "C" int mrisr_bench_gemm(int M, int N, int K, int conv, int B, int H, int
     for (int i = 0; i < iters; ++i) (void)launch_gemm<bf16>(g, st);
     MRISR_CHECK_HIP(hipEventRecord(e1, st));
     MRISR_CHECK_HIP(hipEventSynchronize(e1));
-    mrisr_debug_force_tile(0);
     float ms = 0.f;
     MRISR_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
     *ms_out = ms / iters;

@@ -220,6 +220,8 @@ bool xattn_tail_ok(int C, int heads, int M, int ntok, int nk);
 size_t xattn_tail_kv_bytes(int B);
 int launch_pack_xattn_kv(const void* kc, const void* vtc, void* dst, int B, int ctx_pad, int dpad, int nk, hipStream_t st);
 int launch_xattn_tail(const XTailArgs& x, hipStream_t st);
+// the tile with this id computes a LoRA down-projection z = x A^T of total rank R (r per module) inside the kernel (gemm.hip: the tile registry)
+bool gemm_tile_lora_in_kernel(int tile, int r, int R);
 int gemm_rp_tile(const GemmArgs& g);  // row-panel kernel id for this (plain, short-K, bf16) GEMM, 0 if it is not eligible
 bool gemm_sc_tail_ok(const GemmArgs& g);  // the launch (with its 1x1 tail fields set) has the form the two tail-capable kernel families take
 bool sc_fused_enabled();                  // resnet shortcut as conv2's 1x1 tail (MRISR_SC_FUSED, default 1; mrisr_debug_sc_fused)

@@ -2782,13 +2782,154 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs g) {
 }
 
 // ---- host side -----------------------------------------------------------------------------------
+// ---- the tile registry: one line per kernel configuration ------------------------------------------
+// Everything the host knows about a tile id is its line here or a constexpr function of that line (below); the switch in launch_gemm
+// and gemm_prepare are generated from the same list.  A new tile is one new line.
+//   X(id, family, p0, p1, p2, p3, p4, eff, cand)
+//   F32 / BL / HALO / HALO8 (the tiled families): p = BM, BN, WGM, WGN, NSTAGE - the kernels' template parameters (HALO8: BN and NSTAGE,
+//       256 rows on 4 x 2 waves are fixed in gemm_halo8_kernel)
+//   WS: p = KS, NB   (K = 32 KS, slab of 16 NB output columns)
+//   RP: p = KS, NF, FP8, NW   (K = 32 KS; weight chunks of 16 NF output columns x K: 40 KB bf16, 20 / 40 KB fp8; NW waves = 32 NW-row panels)
+//   eff:  relative main-loop efficiency for the cost model, measured with tools/gemm_sweep.py (profiles/r01_gemm_sweep.log); 0: not ranked
+//   cand: the plan-time autotuner times it.  NOT candidates, all kept, tested and reachable through mrisr_debug_force_tile:
+//       27, 29-31 never won a shape (profiles/r01_gemm_sweep_tiles.log);
+//       32-39, the counted rings: on the shapes they were built for - level-2 linears, M = 2,048 - they tie or lose: 64 x 64: 16.7 us
+//       with 2 stages, 17.1 with 3, 24.4 with 4 (LDS then admits 2 workgroups per CU instead of 5); these GEMMs move 210 MB through LDS
+//       in 16.7 us = 12.6 TB/s, i.e. they sit at the L2 -> LDS bandwidth, not on a latency chain: profiles/r02i_ring_probe.log;
+//       50-52, weight-stationary: correct, but 30-60 % slower than the tiled kernels on every shape they fit
+//       (profiles/r01b_ws_sweep.log: one A fragment per wave makes them LDS-read bound);
+//       62, 63: fp8 operands are a property of the launch (packed weights), never a tuner choice
+enum class Fam { F32, BL, HALO, HALO8, WS, RP };
+#define TILES(X)                                   \
+    X(1, F32, 128, 128, 2, 2, 2, 0.75, false)      \
+    X(2, F32, 256, 64, 4, 1, 2, 0.65, false)       \
+    X(3, F32, 128, 64, 2, 2, 2, 0.60, false)       \
+    X(4, F32, 64, 64, 2, 2, 2, 0.45, false)        \
+    X(14, BL, 128, 128, 2, 2, 2, 1.00, true)       \
+    X(15, BL, 256, 64, 4, 1, 2, 0.90, true)        \
+    X(16, BL, 128, 64, 2, 2, 2, 0.88, true)        \
+    X(17, BL, 64, 64, 2, 2, 2, 0.60, true)         \
+    X(18, BL, 64, 128, 2, 2, 2, 0.86, true)        \
+    X(25, BL, 128, 160, 2, 2, 2, 0, true)          \
+    X(26, BL, 64, 160, 2, 2, 2, 0, true)           \
+    X(27, BL, 160, 160, 2, 2, 2, 0, false)         \
+    X(28, BL, 128, 192, 2, 2, 2, 0, true)          \
+    X(29, BL, 192, 128, 2, 2, 2, 0, false)         \
+    X(30, BL, 160, 128, 2, 2, 2, 0, false)         \
+    X(31, BL, 96, 160, 2, 2, 2, 0, false)          \
+    X(32, BL, 64, 64, 2, 2, 4, 0, false)           \
+    X(33, BL, 64, 64, 2, 2, 3, 0, false)           \
+    X(34, BL, 64, 128, 2, 2, 3, 0, false)          \
+    X(35, BL, 128, 64, 2, 2, 3, 0, false)          \
+    X(36, BL, 128, 128, 2, 2, 3, 0, false)         \
+    X(37, BL, 128, 160, 2, 2, 4, 0, false)         \
+    X(38, BL, 128, 128, 2, 2, 4, 0, false)         \
+    X(39, BL, 64, 160, 2, 2, 3, 0, false)          \
+    X(41, HALO, 128, 160, 2, 2, 2, 0, true)        \
+    X(42, HALO, 128, 128, 2, 2, 2, 0, true)        \
+    X(43, HALO, 64, 160, 2, 2, 2, 0, true)         \
+    X(44, HALO, 128, 192, 2, 2, 2, 0, true)        \
+    X(45, HALO, 256, 64, 4, 1, 2, 0, true)         \
+    X(46, HALO8, 256, 160, 4, 2, 2, 0, false)      \
+    X(47, HALO8, 256, 160, 4, 2, 3, 0, false)      \
+    X(48, HALO8, 256, 160, 4, 2, 4, 0, false)      \
+    X(50, WS, 10, 10, 0, 0, 0, 0, false)           \
+    X(51, WS, 10, 8, 0, 0, 0, 0, false)            \
+    X(52, WS, 20, 4, 0, 0, 0, 0, false)            \
+    X(60, RP, 10, 4, 0, 4, 0, 0, true)             \
+    X(61, RP, 20, 2, 0, 4, 0, 0, true)             \
+    X(62, RP, 10, 4, 1, 4, 0, 0, false)            \
+    X(63, RP, 20, 4, 1, 2, 0, 0, false)            \
+    X(64, RP, 20, 2, 0, 2, 0, 0, true)             \
+    X(65, RP, 10, 4, 0, 2, 0, 0, true)
+// how a line becomes a launcher instantiation
+#define TILE_LAUNCH_F32(a, b, c, d, e) launch_cfg<T, a, b, c, d>
+#define TILE_LAUNCH_BL(a, b, c, d, e) launch_bl<a, b, c, d, e>
+#define TILE_LAUNCH_HALO(a, b, c, d, e) launch_halo<a, b, c, d>
+#define TILE_LAUNCH_HALO8(a, b, c, d, e) launch_halo8<b, e>
+#define TILE_LAUNCH_WS(a, b, c, d, e) launch_ws<a, b>
+#define TILE_LAUNCH_RP(a, b, c, d, e) launch_rp<a, b, (c) != 0, d>
+
+struct Tile {
+    int id;
+    Fam fam;
+    int p[5];
+    double eff;
+    bool cand;
+    constexpr bool tiled() const { return fam == Fam::F32 || fam == Fam::BL || fam == Fam::HALO || fam == Fam::HALO8; }
+    constexpr int bm() const { return tiled() ? p[0] : (fam == Fam::WS ? 64 : 32 * p[3]); }
+    constexpr int bn() const { return tiled() ? p[1] : 16 * p[1]; }
+    constexpr int nstage() const { return tiled() ? p[4] : 1; }
+    constexpr int ks() const { return tiled() ? 0 : p[0]; }  // WS / RP: K = 32 KS
+    constexpr bool fp8() const { return fam == Fam::RP && p[2] != 0; }
+    constexpr int nw() const { return fam == Fam::RP ? p[3] : 0; }  // RP: waves per workgroup
+    // 16-row / 16-column MFMA fragments of one wave
+    constexpr int mfrag() const { return tiled() ? p[0] / p[2] / 16 : 0; }
+    constexpr int nfrag() const { return tiled() ? p[1] / p[3] / 16 : p[1]; }
+    // the GEGLU epilogue pairs a (u, gate) fragment: an even number of fragments per wave along N (the kernels' `if constexpr`)
+    constexpr bool pairs_geglu() const { return nfrag() % 2 == 0; }
+    constexpr bool ring() const { return fam == Fam::BL && nstage() > 2; }  // counted vmcnt ring: every DMA instruction fully in range
+    // gemm_bl_kernel in its 2-stage form: the only gather that knows the 2 x 2 / sub-pixel conv forms
+    constexpr bool knows_gather2x2() const { return fam == Fam::BL && nstage() == 2; }
+    // the 1x1 tail of a 3x3 conv (GemmArgs::s0 ...): the 2-stage buffer-addressed kernel and the 4-wave halo kernel
+    constexpr bool carries_tail() const { return knows_gather2x2() || fam == Fam::HALO; }
+    constexpr bool splits() const { return tiled(); }  // split-K (blockIdx.y): not the weight-stationary / row-panel kernels
+    constexpr bool reduces_in_kernel() const { return (fam == Fam::BL || fam == Fam::HALO) && mfrag() * nfrag() <= 20; }  // as the kernels' `if constexpr`
+    // z = x A^T inside the kernel: up to this adapter rank (0: never); the row-panel kernel only in the rank-4-per-module form
+    constexpr int lora_max_rank() const { return fam == Fam::BL || fam == Fam::WS || fam == Fam::RP ? 16 : 0; }
+    constexpr bool lora_rank4_only() const { return fam == Fam::RP; }
+};
+#define X(id, fam, a, b, c, d, e, eff, cand) {id, Fam::fam, {a, b, c, d, e}, eff, cand},
+static constexpr Tile kTiles[] = {TILES(X)};
+#undef X
+static constexpr const Tile* find_tile(int id) {
+    for (const Tile& t : kTiles)
+        if (t.id == id) return &t;
+    return nullptr;
+}
+// where a launch goes when the tile forced on it is of a family that does not take its form (tile_for_launch)
+static constexpr int kTileF32 = 1, kTileBL = 14, kTileGather2x2 = 25;
+static constexpr bool registry_ok() {
+    for (const Tile& a : kTiles) {
+        if (a.id <= 0 || find_tile(a.id) != &a) return false;  // ids unique
+        if (a.cand && a.fam == Fam::F32) return false;          // the tuner times bf16 launches
+    }
+    return find_tile(kTileF32)->fam == Fam::F32 && find_tile(kTileBL)->knows_gather2x2() && find_tile(kTileGather2x2)->knows_gather2x2();
+}
+static_assert(registry_ok(), "tile registry: unique ids, bf16 candidates, default tiles of the right family");
+
+bool gemm_tile_lora_in_kernel(int tile, int r, int R) {
+    const Tile* t = find_tile(tile);
+    return t && R >= 1 && R <= t->lora_max_rank() && (!t->lora_rank4_only() || r == 4);
+}
+
 // M tiles per group of the tile order (MRISR_GROUP_M overrides; 1 = the old N-first order).  8 measured best over the whole
 // step (same box, graph replay: 53.9 slices/s vs 53.0 for N-first; a per-grid sqrt(T * BN / BM) model: 53.1 vs 53.6): profiles/r01e_group_m.log
-static int auto_group_m(int ntm, int ntn, int BM, int BN) {
-    (void)ntn; (void)BM; (void)BN;
+static int auto_group_m(int ntm) {
     static const int env = [] { const char* e = getenv("MRISR_GROUP_M"); return e ? atoi(e) : 8; }();
     return std::max(1, std::min(env, ntm));
 }
+// grid of a tiled launch; sets the tile order the kernel decodes it with
+static dim3 tile_grid(GemmArgs& g, int BM, int BN) {
+    const int ntn = (g.N + BN - 1) / BN, ntm = (g.M + BM - 1) / BM;
+    g.group_m = auto_group_m(ntm);
+    return dim3(ntn * ntm, g.splitk, g.batch);
+}
+// profiler scope of a launch: class `base`, under MRISR_PROF_SHAPES "<base> <tag> M= N= K= s= b=" (tag null: one class per tile).  Work
+// and traffic default to 2 M N K and to elt (a_el + M N) + w_elt N K bytes per batch, a_el being the A elements the family counts
+static ProfScope gemm_scope(const GemmArgs& g, const std::string& base, const char* tag, double a_el, int elt, int w_elt, hipStream_t st) {
+    if (!prof_enabled()) return ProfScope(base.c_str(), 0.0, 0.0, st);
+    const char* name = base.c_str();
+    if (tag && prof_shapes()) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "%s %s M=%d N=%d K=%d s=%d b=%d", name, tag, g.M, g.N, g.K, g.splitk, g.batch);
+        name = prof_intern(buf);
+    }
+    const double fl = g.alg_flops != 0.0 ? g.alg_flops : 2.0 * g.M * (double)g.N * g.K * g.batch;
+    const double by = g.alg_bytes != 0.0 ? g.alg_bytes : g.batch * (elt * (a_el + (double)g.M * g.N) + w_elt * ((double)g.N * g.K));
+    return ProfScope(name, fl, by, st);
+}
+static double conv_a_elements(const GemmArgs& g, bool with_tail) { return (double)g.B * g.Hin * g.Win * (g.c0 + g.c1 + (with_tail ? g.cs0 + g.cs1 : 0)); }
 
 template <typename T, int BM, int BN, int WGM, int WGN>
 static int prepare_cfg() {
@@ -2801,38 +2942,20 @@ static int prepare_cfg() {
     }
     return 0;
 }
-template <typename T>
-static int prepare_all() {
-    if (prepare_cfg<T, 128, 128, 2, 2>()) return 1;
-    if (prepare_cfg<T, 256, 64, 4, 1>()) return 1;
-    if (prepare_cfg<T, 128, 64, 2, 2>()) return 1;
-    if (prepare_cfg<T, 64, 64, 2, 2>()) return 1;
-    return 0;
-}
 template <typename T, int BM, int BN, int WGM, int WGN>
-static int launch_cfg(const GemmArgs& g, hipStream_t st) {
+static int launch_cfg(GemmArgs& g, hipStream_t st) {
     constexpr int smem = 2 * (BM + BN) * 128;
     auto kern = gemm_kernel<T, BM, BN, WGM, WGN>;
     if (prepare_cfg<T, BM, BN, WGM, WGN>()) return 1;
-    const int ntn = (g.N + BN - 1) / BN, ntm = (g.M + BM - 1) / BM;
-    const_cast<GemmArgs&>(g).group_m = auto_group_m(ntm, ntn, BM, BN);
-    dim3 grid(ntn * ntm, g.splitk, g.batch);
-    static const std::string pname = std::string("gemm_") + (sizeof(T) == 2 ? "bf16_" : "f32_") + std::to_string(BM) + "x" + std::to_string(BN);
-    double fl = g.alg_flops, by = g.alg_bytes;
-    if (prof_enabled()) {
-        if (fl == 0.0) fl = 2.0 * g.M * (double)g.N * g.K * g.batch;
-        if (by == 0.0) {
-            const double a_el = g.conv ? (double)g.B * g.Hin * g.Win * (g.c0 + g.c1) : (double)g.M * g.K;
-            by = sizeof(T) * g.batch * (a_el + (double)g.N * g.K + (double)g.M * g.N);
-        }
-    }
-    ProfScope ps(pname.c_str(), fl, by, st);
+    const dim3 grid = tile_grid(g, BM, BN);
+    static const std::string base = std::string("gemm_") + (sizeof(T) == 2 ? "bf16_" : "f32_") + std::to_string(BM) + "x" + std::to_string(BN);
+    ProfScope ps = gemm_scope(g, base, nullptr, g.conv ? conv_a_elements(g, false) : (double)g.M * g.K, sizeof(T), sizeof(T), st);
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, g, (const char*)zero_page());
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-static int g_force_tile = 0;  // test hook: 0 auto, 1..4 small-kernel configs, 5..9 ring-kernel configs
+static int g_force_tile = 0;  // test hook: 0 = the planner, else this tile id for every GEMM
 extern "C" void mrisr_debug_force_tile(int t) { g_force_tile = t; }
 
 template <int BM, int BN, int WGM, int WGN, int NSTAGE>
@@ -2848,79 +2971,19 @@ static int prepare_bl() {
     return 0;
 }
 template <int BM, int BN, int WGM, int WGN, int NSTAGE>
-static int launch_bl(const GemmArgs& g, hipStream_t st) {
+static int launch_bl(GemmArgs& g, hipStream_t st) {
     constexpr int smem = NSTAGE * (BM + BN) * 128;
     constexpr int smem_l = NSTAGE * ((BM + BN) * 128 + 16 * 128);
     if (prepare_bl<BM, BN, WGM, WGN, NSTAGE>()) return 1;
-    if (NSTAGE > 2)
-        MRISR_REQUIRE(!g.conv && !g.c1 && !g.a1 && g.batch == 1 && (g.splitk == 1 || (g.K / 64) / g.splitk >= NSTAGE) && g.M % BM == 0 && g.N % BN == 0,
-                      "counted-ring GEMM: plain single-source GEMM that tiles exactly; split: at least NSTAGE K tiles per split");
-    const int ntn = (g.N + BN - 1) / BN, ntm = (g.M + BM - 1) / BM;
-    const_cast<GemmArgs&>(g).group_m = auto_group_m(ntm, ntn, BM, BN);
-    dim3 grid(ntn * ntm, g.splitk, g.batch);
-    static const std::string base_name = std::string("gemm_bf16_bl") + std::to_string(BM) + "x" + std::to_string(BN) + (NSTAGE > 2 ? "d" + std::to_string(NSTAGE) : std::string());
-    std::string pname = base_name;
-    if (prof_enabled() && prof_shapes()) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "%s %s M=%d N=%d K=%d s=%d b=%d", base_name.c_str(), g.conv ? (g.cs0 ? "convsc" : (g.ups ? "convup" : (g.stride == 2 ? "convs2" : "conv"))) : "lin",
-                 g.M, g.N, g.K, g.splitk, g.batch);
-        pname = buf;
-    }
-    double fl = g.alg_flops, by = g.alg_bytes;
-    if (prof_enabled()) {
-        if (fl == 0.0) fl = 2.0 * g.M * (double)g.N * g.K * g.batch;
-        if (by == 0.0) {
-            const double a_el = g.conv ? (double)g.B * g.Hin * g.Win * (g.c0 + g.c1 + g.cs0 + g.cs1) : (double)g.M * g.K;
-            by = 2.0 * g.batch * (a_el + (double)g.N * g.K + (double)g.M * g.N);
-        }
-    }
-    ProfScope ps(prof_intern(pname), fl, by, st);
-    if (g.lora_a) {
-        MRISR_REQUIRE(g.splitk == 1 && !g.conv && g.c1 == 0 && g.lora_R >= 1 && g.lora_R <= 16 && g.lora_b && g.act != ACT_GEGLU,
-                      "in-kernel LoRA down-projection: plain un-split GEMM, R <= 16");
-        hipLaunchKernelGGL((gemm_bl_kernel<BM, BN, WGM, WGN, NSTAGE, true>), grid, dim3(256), smem_l, st, g);
-    } else {
-        hipLaunchKernelGGL((gemm_bl_kernel<BM, BN, WGM, WGN, NSTAGE, false>), grid, dim3(256), smem, st, g);
-    }
+    const dim3 grid = tile_grid(g, BM, BN);
+    static const std::string base = std::string("gemm_bf16_bl") + std::to_string(BM) + "x" + std::to_string(BN) + (NSTAGE > 2 ? "d" + std::to_string(NSTAGE) : std::string());
+    ProfScope ps = gemm_scope(g, base, g.conv ? (g.cs0 ? "convsc" : (g.ups ? "convup" : (g.stride == 2 ? "convs2" : "conv"))) : "lin",
+                              g.conv ? conv_a_elements(g, true) : (double)g.M * g.K, 2, 2, st);
+    if (g.lora_a) hipLaunchKernelGGL((gemm_bl_kernel<BM, BN, WGM, WGN, NSTAGE, true>), grid, dim3(256), smem_l, st, g);
+    else hipLaunchKernelGGL((gemm_bl_kernel<BM, BN, WGM, WGN, NSTAGE, false>), grid, dim3(256), smem, st, g);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
-// buffer-addressed configurations: id -> <BM, BN, WGM, WGN>
-#define BL_CFGS(X)             \
-    X(14, 128, 128, 2, 2, 2)   \
-    X(15, 256, 64, 4, 1, 2)    \
-    X(16, 128, 64, 2, 2, 2)    \
-    X(17, 64, 64, 2, 2, 2)     \
-    X(18, 64, 128, 2, 2, 2)    \
-    X(25, 128, 160, 2, 2, 2)   \
-    X(26, 64, 160, 2, 2, 2)    \
-    X(27, 160, 160, 2, 2, 2)   \
-    X(28, 128, 192, 2, 2, 2)   \
-    X(29, 192, 128, 2, 2, 2)   \
-    X(30, 160, 128, 2, 2, 2)   \
-    X(31, 96, 160, 2, 2, 2)    \
-    X(32, 64, 64, 2, 2, 4)     \
-    X(33, 64, 64, 2, 2, 3)     \
-    X(34, 64, 128, 2, 2, 3)    \
-    X(35, 128, 64, 2, 2, 3)    \
-    X(36, 128, 128, 2, 2, 3)   \
-    X(37, 128, 160, 2, 2, 4)   \
-    X(38, 128, 128, 2, 2, 4)   \
-    X(39, 64, 160, 2, 2, 3)
-
-static int prepare_bls() {
-#define X(id, bm, bn, wm, wn, ns) if (prepare_bl<bm, bn, wm, wn, ns>()) return 1;
-    BL_CFGS(X)
-#undef X
-    return 0;
-}
-// halo-conv configurations: id -> <BM, BN, WGM, WGN>
-#define HALO_CFGS(X)        \
-    X(41, 128, 160, 2, 2)   \
-    X(42, 128, 128, 2, 2)   \
-    X(43, 64, 160, 2, 2)    \
-    X(44, 128, 192, 2, 2)   \
-    X(45, 256, 64, 4, 1)
 
 static size_t halo_smem(const GemmArgs& g, int BM, int BN) {
     const int TH = BM / g.Win;
@@ -2928,18 +2991,8 @@ static size_t halo_smem(const GemmArgs& g, int BM, int BN) {
     const size_t patch = (npix * 8 + 255) / 256 * 4096;  // whole 256-lane DMA rounds
     return patch + 2 * (size_t)BN * 128;
 }
-// eligibility of the halo kernel for a conv launch with M tile BM
-static bool halo_ok(const GemmArgs& g, int BM) {
-    if (!g.conv || g.stride != 1 || g.ups != 0 || g.zstuff || g.batch != 1 || g.pad != 1) return false;
-    if (g.Win % 8 != 0 || g.Win > 64 || BM % g.Win != 0) return false;  // (a 16-pixel fragment may span two image rows: prow is per pixel)
-    if ((g.Hin * g.Win) % BM != 0 || g.M % BM != 0 || g.Hout != g.Hin || g.Wout != g.Win) return false;
-    const int npix = (BM / g.Win + 2) * (g.Win + 2);
-    const int pit_max = BM >= 256 ? 13 : (BM >= 128 ? 9 : 6);
-    return (npix * 8 + 255) / 256 <= pit_max && g.N % 4 == 0;
-}
 template <int BM, int BN, int WGM, int WGN>
-static int launch_halo(const GemmArgs& g, hipStream_t st) {
-    MRISR_REQUIRE(halo_ok(g, BM), "halo conv kernel: unsupported geometry");
+static int launch_halo(GemmArgs& g, hipStream_t st) {
     const size_t smem = halo_smem(g, BM, BN);
     MRISR_REQUIRE(smem <= 160 * 1024, "halo conv kernel: LDS");
     static size_t attr = 0;
@@ -2947,51 +3000,16 @@ static int launch_halo(const GemmArgs& g, hipStream_t st) {
         MRISR_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_halo_kernel<BM, BN, WGM, WGN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(96 * 1024)));
         attr = 96 * 1024;
     }
-    const int ntn = (g.N + BN - 1) / BN, ntm = g.M / BM;
-    const_cast<GemmArgs&>(g).group_m = auto_group_m(ntm, ntn, BM, BN);
-    dim3 grid(ntn * ntm, g.splitk, 1);
-    static const std::string base_name = std::string("gemm_bf16_halo") + std::to_string(BM) + "x" + std::to_string(BN);
-    std::string pname = base_name;
-    if (prof_enabled() && prof_shapes()) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "%s %s M=%d N=%d K=%d s=%d b=%d", base_name.c_str(), g.cs0 ? "convsc" : "conv", g.M, g.N, g.K, g.splitk, g.batch);
-        pname = buf;
-    }
-    double fl = g.alg_flops, by = g.alg_bytes;
-    if (prof_enabled()) {
-        if (fl == 0.0) fl = 2.0 * g.M * (double)g.N * g.K;
-        if (by == 0.0) by = 2.0 * ((double)g.B * g.Hin * g.Win * (g.c0 + g.c1 + g.cs0 + g.cs1) + (double)g.N * g.K + (double)g.M * g.N);
-    }
-    ProfScope ps(prof_intern(pname), fl, by, st);
+    const dim3 grid = tile_grid(g, BM, BN);
+    static const std::string base = std::string("gemm_bf16_halo") + std::to_string(BM) + "x" + std::to_string(BN);
+    ProfScope ps = gemm_scope(g, base, g.cs0 ? "convsc" : "conv", conv_a_elements(g, true), 2, 2, st);
     hipLaunchKernelGGL((gemm_halo_kernel<BM, BN, WGM, WGN>), grid, dim3(256), smem, st, g);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
-static int halo_bm(int tile) {
-    switch (tile) {
-#define X(id, bm, bn, wm, wn) case id: return bm;
-        HALO_CFGS(X)
-#undef X
-    }
-    return 0;
-}
-
-// 256-row halo kernel (eight waves): id -> <BN, weight stages>
-#define HALO8_CFGS(X) \
-    X(46, 160, 2)     \
-    X(47, 160, 3)     \
-    X(48, 160, 4)
-static bool is_halo8(int tile) { return tile >= 46 && tile <= 48; }
-static bool halo8_ok(const GemmArgs& g) {
-    if (!g.conv || g.stride != 1 || g.ups != 0 || g.zstuff || g.batch != 1 || g.pad != 1) return false;
-    if (g.Win % 8 != 0 || g.Win > 64 || 256 % g.Win != 0) return false;
-    if ((g.Hin * g.Win) % 256 != 0 || g.M % 256 != 0 || g.Hout != g.Hin || g.Wout != g.Win) return false;
-    const int npix = (256 / g.Win + 2) * (g.Win + 2);
-    return (npix * 8 + 511) / 512 <= 7 && g.N % 4 == 0;
-}
+// 256-row halo kernel (eight waves)
 template <int BN, int NSTAGE>
-static int launch_halo8(const GemmArgs& g, hipStream_t st) {
-    MRISR_REQUIRE(halo8_ok(g), "256-row halo conv kernel: unsupported geometry");
+static int launch_halo8(GemmArgs& g, hipStream_t st) {
     const int npix = (256 / g.Win + 2) * (g.Win + 2);
     const size_t smem = (size_t)((npix * 8 + 511) / 512) * 8192 + (size_t)NSTAGE * ((BN * 8 + 511) / 512) * 8192;
     MRISR_REQUIRE(smem <= 160 * 1024, "256-row halo conv kernel: LDS");
@@ -3000,59 +3018,18 @@ static int launch_halo8(const GemmArgs& g, hipStream_t st) {
         MRISR_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_halo8_kernel<BN, NSTAGE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr = true;
     }
-    const int ntn = (g.N + BN - 1) / BN, ntm = g.M / 256;
-    const_cast<GemmArgs&>(g).group_m = auto_group_m(ntm, ntn, 256, BN);
-    dim3 grid(ntn * ntm, g.splitk, 1);
-    static const std::string base_name = std::string("gemm_bf16_halo256x") + std::to_string(BN) + "r" + std::to_string(NSTAGE);
-    std::string pname = base_name;
-    if (prof_enabled() && prof_shapes()) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "%s conv M=%d N=%d K=%d s=%d b=%d", base_name.c_str(), g.M, g.N, g.K, g.splitk, g.batch);
-        pname = buf;
-    }
-    double fl = g.alg_flops, by = g.alg_bytes;
-    if (prof_enabled()) {
-        if (fl == 0.0) fl = 2.0 * g.M * (double)g.N * g.K;
-        if (by == 0.0) by = 2.0 * ((double)g.B * g.Hin * g.Win * (g.c0 + g.c1) + (double)g.N * g.K + (double)g.M * g.N);
-    }
-    ProfScope ps(prof_intern(pname), fl, by, st);
+    const dim3 grid = tile_grid(g, 256, BN);
+    static const std::string base = std::string("gemm_bf16_halo256x") + std::to_string(BN) + "r" + std::to_string(NSTAGE);
+    ProfScope ps = gemm_scope(g, base, "conv", conv_a_elements(g, false), 2, 2, st);
     hipLaunchKernelGGL((gemm_halo8_kernel<BN, NSTAGE>), grid, dim3(512), smem, st, g);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-// weight-stationary configurations: id -> <KS, NB>   (K = 32*KS, slab of 16*NB output columns)
-#define WS_CFGS(X)   \
-    X(50, 10, 10)    \
-    X(51, 10, 8)     \
-    X(52, 20, 4)
-
-static void ws_dims(int tile, int* ks, int* nb) {
-    *ks = *nb = 0;
-    switch (tile) {
-#define X(id, k, n) case id: *ks = k; *nb = n; break;
-        WS_CFGS(X)
-#undef X
-    }
-}
-static bool ws_ok(const GemmArgs& g, int tile) {
-    int ks, nb;
-    ws_dims(tile, &ks, &nb);
-    if (!ks || g.conv || g.c1 || g.batch != 1 || g.a1) return false;
-    if (g.K != 32 * ks || g.N % (16 * nb) != 0 || g.M % 64 != 0 || g.lda0 % 8 != 0) return false;
-    if (g.act == ACT_GEGLU && (nb & 1)) return false;
-    if (g.out_mode == OUT_NONE) return false;
-    return true;
-}
 template <int KS, int NB>
-static int launch_ws(const GemmArgs& g, hipStream_t st) {
+static int launch_ws(GemmArgs& g, hipStream_t st) {
     constexpr int K = KS * 32, BN = NB * 16, WP = K * 2 + 16;
-    MRISR_REQUIRE(g.splitk == 1, "weight-stationary kernel: no split-K");
-    MRISR_REQUIRE(!g.conv && !g.c1 && !g.a1 && g.batch == 1 && g.K == K && g.N % BN == 0 && g.M % 64 == 0 && g.lda0 % 8 == 0 &&
-                      (g.act != ACT_GEGLU || NB % 2 == 0),
-                  "weight-stationary kernel: plain rows, K = 32*KS, N a multiple of the slab, M a multiple of 64");
     const bool lora = g.lora_a != nullptr;
-    if (lora) MRISR_REQUIRE(g.lora_R >= 1 && g.lora_R <= 16 && g.lora_b && g.act != ACT_GEGLU, "in-kernel LoRA down-projection: R <= 16");
     const size_t smem = (size_t)(BN + (lora ? 16 : 0)) * WP + (lora ? 4 * 16 * 16 * sizeof(float) : 0);
     static bool attr = false;
     if (!attr) {
@@ -3065,88 +3042,18 @@ static int launch_ws(const GemmArgs& g, hipStream_t st) {
     int rgroups = 256 / slabs;
     if (rgroups < 1) rgroups = 1;
     if (rgroups > nblk) rgroups = nblk;
-    static const std::string base_name = std::string("gemm_bf16_ws") + std::to_string(K) + "x" + std::to_string(BN);
-    std::string pname = base_name;
-    if (prof_enabled() && prof_shapes()) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "%s lin M=%d N=%d K=%d s=1 b=1", base_name.c_str(), g.M, g.N, g.K);
-        pname = buf;
-    }
-    double fl = g.alg_flops, by = g.alg_bytes;
-    if (prof_enabled()) {
-        if (fl == 0.0) fl = 2.0 * g.M * (double)g.N * g.K;
-        if (by == 0.0) by = 2.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N);
-    }
-    ProfScope ps(prof_intern(pname), fl, by, st);
+    static const std::string base = std::string("gemm_bf16_ws") + std::to_string(K) + "x" + std::to_string(BN);
+    ProfScope ps = gemm_scope(g, base, "lin", (double)g.M * g.K, 2, 2, st);
     if (lora) hipLaunchKernelGGL((gemm_ws_kernel<KS, NB, true>), dim3(slabs * rgroups), dim3(256), smem, st, g, rgroups);
     else hipLaunchKernelGGL((gemm_ws_kernel<KS, NB, false>), dim3(slabs * rgroups), dim3(256), smem, st, g, rgroups);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-// row-panel configurations: id -> <KS, NF, FP8, NW>   (K = 32*KS; weight chunks of 16*NF output columns x K: 40 KB bf16, 20 / 40 KB
-// fp8; NW waves = 32*NW-row panels)
-#define RP_CFGS(X)           \
-    X(60, 10, 4, false, 4)   \
-    X(64, 20, 2, false, 2)   \
-    X(61, 20, 2, false, 4)   \
-    X(62, 10, 4, true, 4)    \
-    X(63, 20, 4, true, 2)    \
-    X(65, 10, 4, false, 2)
-
-static void rp_dims(int tile, int* ks, int* nf, bool* fp8, int* nw = nullptr) {
-    *ks = *nf = 0;
-    *fp8 = false;
-    switch (tile) {
-#define X(id, k, n, f, w) case id: *ks = k; *nf = n; *fp8 = f; if (nw) *nw = w; break;
-        RP_CFGS(X)
-#undef X
-    }
-}
-static bool rp_ok(const GemmArgs& g, int tile) {
-    int ks, nf;
-    bool fp8;
-    rp_dims(tile, &ks, &nf, &fp8);
-    const int bn = nf * 16;
-    if (!ks || g.no_rp || g.conv || g.c1 || g.a1 || g.batch != 1 || g.heads != 1 || g.splitk > 1) return false;
-    if (g.K != 32 * ks || g.lda0 % 8 != 0 || g.N % 16 != 0 || g.M < 1) return false;
-    if (g.alpha != 1.0f || g.rowvec || g.lora_z || (!g.bias && (size_t)g.N * sizeof(float) > kZeroPageBytes)) return false;
-    if (fp8 != (g.w8 != nullptr)) return false;  // fp8 operands are a property of the launch (packed weights), never a tuner choice
-    if (fp8 && (!g.w_scale || (g.lora_a && (!g.lora_a8 || !g.lora_a_scale)))) return false;
-    if (g.act == ACT_GEGLU) {
-        if (g.N % 32 != 0 || (nf & 1) || g.out_mode != OUT_ROWS || g.ldo % 8 != 0 || g.resid) return false;
-    } else if (g.act != ACT_NONE) {
-        return false;
-    } else if (g.out_mode == OUT_ROWS) {
-        if (g.ldo % 8 != 0 || (g.resid && g.ldr % 8 != 0)) return false;
-    } else if (g.out_mode == OUT_HEADS) {
-        // head-major sections: every chunk inside one section, everything 8-aligned (16-byte pieces), no residual
-        if (g.secC <= 0 || g.secC % bn != 0 || ((g.N | g.M | g.hd | g.secC | g.dpad | g.npad | g.ntok) & 7) != 0 || g.resid) return false;
-    } else {
-        return false;
-    }
-    if (g.lora_a && (g.lora_r != 4 || g.lora_R > 16 || !g.lora_b || g.act == ACT_GEGLU)) return false;
-    return (long long)g.M * g.lda0 * 2 < 0x7FFFFFFFll && (long long)g.N * g.K * 2 < 0x7FFFFFFFll;
-}
-// the row-panel configuration for this K when the caller must have one (LayerNorm prologue, fp8 operands; 0: none).  bf16,
-// K = 640: the 4-wave form wins on wide outputs (N = 1920: 33 vs 36 us, N = 5120: 62 vs 83 us at M = 8192) although it spills a
-// few registers, the 2-wave form on N = 640 (16.3 vs 20.0 us): tools/probes/rp_probe3.sh
-int gemm_rp_tile(const GemmArgs& g) {
-    static const int env = [] { const char* e = getenv("MRISR_RP"); return e ? atoi(e) : 1; }();
-    if (!env) return 0;
-    if (g.w8) return g.K == 320 ? (rp_ok(g, 62) ? 62 : 0) : (rp_ok(g, 63) ? 63 : 0);
-    if (g.K == 320) return rp_ok(g, 60) ? 60 : 0;
-    if (g.K == 640) {
-        const int first = g.N > 640 ? 61 : 64, second = g.N > 640 ? 64 : 61;
-        return rp_ok(g, first) ? first : (rp_ok(g, second) ? second : 0);
-    }
-    return 0;
-}
 template <int KS, int NF, bool FP8, int NW>
-static int launch_rp(int tile_id, const GemmArgs& g, hipStream_t st) {
+static int launch_rp(GemmArgs& g, hipStream_t st) {
     constexpr int K = KS * 32, BN = NF * 16, BM = 32 * NW;
     constexpr int smem = (FP8 && KS == 10) ? 81920 : 2 * BN * K * (FP8 ? 1 : 2);  // (fp8, K = 320: room for the bf16 row panel on its way in)
-    MRISR_REQUIRE(rp_ok(g, tile_id), "row-panel kernel: plain un-split bf16 row GEMM with K = 32*KS (fp8: packed weights + scales)");
     static bool attr = false;
     if (!attr) {
         MRISR_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_rp_kernel<KS, NF, false, 0, FP8, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
@@ -3159,27 +3066,14 @@ static int launch_rp(int tile_id, const GemmArgs& g, hipStream_t st) {
     static const int ys_env = [] { const char* e = getenv("MRISR_RP_YSPLIT"); return e ? atoi(e) : 0; }();
     int ysplit = ys_env > 0 ? ys_env : (512 + panels / 2) / panels;  // ~2 workgroups per CU
     ysplit = std::max(1, std::min(ysplit, nchunks));
-    static const std::string base_name = std::string(FP8 ? "gemm_fp8_rp" : "gemm_bf16_rp") + std::to_string(K) + "x" + std::to_string(BN) + (NW == 2 ? "w2" : "");
-    std::string pname = base_name;
-    if (prof_enabled() && prof_shapes()) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "%s lin%s M=%d N=%d K=%d s=1 b=1", base_name.c_str(), g.ln_gamma ? "+ln" : "", g.M, g.N, g.K);
-        pname = buf;
-    }
-    double fl = g.alg_flops, by = g.alg_bytes;
-    if (prof_enabled()) {
-        if (fl == 0.0) fl = 2.0 * g.M * (double)g.N * g.K;
-        if (by == 0.0) by = 2.0 * ((double)g.M * g.K + (double)g.M * g.N) + (FP8 ? 1.0 : 2.0) * (double)g.N * g.K;
-    }
-    ProfScope ps(prof_intern(pname), fl, by, st);
+    static const std::string base = std::string(FP8 ? "gemm_fp8_rp" : "gemm_bf16_rp") + std::to_string(K) + "x" + std::to_string(BN) + (NW == 2 ? "w2" : "");
+    ProfScope ps = gemm_scope(g, base, g.ln_gamma ? "lin+ln" : "lin", (double)g.M * g.K, 2, FP8 ? 1 : 2, st);
     const dim3 grid(panels, ysplit);
     static const int pt_rp = [] { const char* e = getenv("MRISR_PRETOUCH_RP"); return e ? atoi(e) : 1; }();
-    if (!pt_rp) const_cast<GemmArgs&>(g).pretouch = 0;
+    if (!pt_rp) g.pretouch = 0;
     const bool lora = g.lora_a != nullptr;
-    if (!g.bias) {  // the kernel loads its chunk's bias unconditionally (straight-line code around the wait counts): zeros
-        MRISR_REQUIRE((size_t)g.N * sizeof(float) <= kZeroPageBytes, "row-panel kernel without bias: N beyond the zero page");
-        const_cast<GemmArgs&>(g).bias = static_cast<const float*>(zero_page());
-    }
+    // the kernel loads its chunk's bias unconditionally (straight-line code around the wait counts): zeros (tile_admits: N within the page)
+    if (!g.bias) g.bias = static_cast<const float*>(zero_page());
     if (g.ln_gamma) {
         MRISR_REQUIRE(g.ln_beta, "LayerNorm prologue: gamma and beta");
         if (lora) hipLaunchKernelGGL((gemm_rp_kernel<KS, NF, true, 1, FP8, NW>), grid, dim3(64 * NW), smem, st, g);
@@ -3192,40 +3086,14 @@ static int launch_rp(int tile_id, const GemmArgs& g, hipStream_t st) {
     return 0;
 }
 
-// counted-ring configurations (NSTAGE > 2): plain single-source GEMMs that tile exactly (every DMA instruction fully in range)
-static bool ring_ok(const GemmArgs& g, int tile) {
-    int bm = 0, bn = 0, ns = 0;
-    switch (tile) {
-#define X(id, m_, n_, wm, wn, st) case id: bm = m_; bn = n_; ns = st; break;
-        BL_CFGS(X)
-#undef X
-    }
-    if (ns <= 2) return true;
-    if (g.conv || g.c1 || g.a1 || g.batch != 1) return false;
-    return g.M % bm == 0 && g.N % bn == 0 && g.K >= 64 * ns;
-}
-
+// ---- may this launch run on this tile? ---------------------------------------------------------------
 // buffer descriptors address at most 2^31 bytes per operand
 static bool bl_ok(const GemmArgs& g) {
     const long long a_rows = g.conv ? (long long)g.B * g.Hin * g.Win : (long long)g.M;
     const long long lim = 0x7FFFFFFFll;
     return a_rows * g.lda0 * 2 < lim && a_rows * (long long)g.lda1 * 2 < lim && (long long)g.N * g.K * 2 < lim;
 }
-
-// ---- 1x1 tail of a 3x3 conv (GemmArgs::s0 ...) ----
-// kernel families that carry it: gemm_bl_kernel in its 2-stage form and the 4-wave gemm_halo_kernel.  Not the counted rings (32-39), halo8
-// (46-48), the weight-stationary / row-panel kernels or the f32 gemm_kernel.
-static bool sc_tail_tile(int tile) {
-    switch (tile) {
-#define X(id, bm, bn, wm, wn, ns) case id: return ns == 2;
-        BL_CFGS(X)
-#undef X
-#define X(id, bm, bn, wm, wn) case id: return true;
-        HALO_CFGS(X)
-#undef X
-    }
-    return false;
-}
+// 1x1 tail of a 3x3 conv (GemmArgs::s0 ...): the form the kernels that carry it (Tile::carries_tail) take
 bool gemm_sc_tail_ok(const GemmArgs& g) {
     if (!g.conv || g.kw != 3 || g.subpix || g.stride != 1 || g.ups || g.zstuff || g.pad != 1 || g.batch != 1) return false;
     if (g.Hout != g.Hin || g.Wout != g.Win || g.act == ACT_GEGLU || g.lora_a) return false;
@@ -3233,6 +3101,97 @@ bool gemm_sc_tail_ok(const GemmArgs& g) {
     if (g.lds0 < g.cs0 || (g.s1 && g.lds1 < g.cs1) || (g.lds0 & 7) || (g.lds1 & 7)) return false;
     const long long a_rows = (long long)g.B * g.Hin * g.Win, lim = 0x7FFFFFFFll;
     return bl_ok(g) && a_rows * g.lds0 * 2 < lim && a_rows * (long long)g.lds1 * 2 < lim;
+}
+// LDS-halo conv kernels: stride-1 3x3, whole BM-row tiles per image, the patch within pit_max 16-byte transfers per thread of nt
+static bool halo_geometry_ok(const GemmArgs& g, int BM, int nt, int pit_max) {
+    if (!g.conv || g.stride != 1 || g.ups != 0 || g.zstuff || g.batch != 1 || g.pad != 1) return false;
+    if (g.Win % 8 != 0 || g.Win > 64 || BM % g.Win != 0) return false;  // (a 16-pixel fragment may span two image rows: prow is per pixel)
+    if ((g.Hin * g.Win) % BM != 0 || g.M % BM != 0 || g.Hout != g.Hin || g.Wout != g.Win) return false;
+    const int npix = (BM / g.Win + 2) * (g.Win + 2);
+    return (npix * 8 + nt - 1) / nt <= pit_max && g.N % 4 == 0;
+}
+// row-panel kernels: plain un-split bf16 row GEMMs with K = 32 KS (fp8: packed weights + scales)
+static bool rp_form_ok(const GemmArgs& g, const Tile& t) {
+    if (g.no_rp || g.heads != 1 || g.lda0 % 8 != 0 || g.N % 16 != 0 || g.M < 1) return false;
+    if (g.alpha != 1.0f || g.rowvec || g.lora_z || (!g.bias && (size_t)g.N * sizeof(float) > kZeroPageBytes)) return false;
+    if (t.fp8() != (g.w8 != nullptr)) return false;  // fp8 operands are a property of the launch (packed weights), never a tuner choice
+    if (t.fp8() && (!g.w_scale || (g.lora_a && (!g.lora_a8 || !g.lora_a_scale)))) return false;
+    if (g.act == ACT_GEGLU) {
+        if (g.N % 32 != 0 || g.out_mode != OUT_ROWS || g.ldo % 8 != 0 || g.resid) return false;
+    } else if (g.act != ACT_NONE) {
+        return false;
+    } else if (g.out_mode == OUT_ROWS) {
+        if (g.ldo % 8 != 0 || (g.resid && g.ldr % 8 != 0)) return false;
+    } else if (g.out_mode == OUT_HEADS) {
+        // head-major sections: every chunk inside one section, everything 8-aligned (16-byte pieces), no residual
+        if (g.secC <= 0 || g.secC % t.bn() != 0 || ((g.N | g.M | g.hd | g.secC | g.dpad | g.npad | g.ntok) & 7) != 0 || g.resid) return false;
+    } else {
+        return false;
+    }
+    return true;
+}
+// THE eligibility rule: the tuner's candidate filter, gemm_choose and launch_gemm all ask it; `why` (optional) receives the reason of a refusal
+static bool tile_admits(const GemmArgs& g, bool is_bf16, int tile, const char** why) {
+    auto no = [why](const char* reason) { if (why) *why = reason; return false; };
+    const Tile* t = find_tile(tile);
+    if (!t) return no("no such tile id");
+    if (t->fam != Fam::F32 && !(is_bf16 && bl_ok(g))) return no("f32, or an operand of 2 GiB and more: the f32-capable tiled kernels only");
+    if ((g.kw != 3 || g.subpix) && !t->knows_gather2x2()) return no("2 x 2 / sub-pixel conv: only the 2-stage buffer-addressed kernel's gather knows these forms");
+    if (g.cs0 || g.cs1 || g.s0 || g.s1) {
+        if (!t->carries_tail()) return no("1x1 tail: only the 2-stage buffer-addressed kernels and the 4-wave halo kernels carry it");
+        if (!is_bf16 || !gemm_sc_tail_ok(g)) return no("1x1 tail: bf16 stride-1 3x3 conv, channel counts multiples of 64, operands below 2 GiB");
+    }
+    if (g.act == ACT_GEGLU && !t->pairs_geglu())
+        return no("GEGLU epilogue: this tile has an odd number of fragments per wave along N, so no (u, gate) fragment pairing");
+    if (g.splitk > 1 && !t->splits()) return no("the weight-stationary and row-panel kernels have no split-K");
+    if (g.lora_a && !(g.splitk <= 1 && !g.conv && g.c1 == 0 && g.lora_b && g.act != ACT_GEGLU && gemm_tile_lora_in_kernel(tile, g.lora_r, g.lora_R)))
+        return no("in-kernel LoRA down-projection: plain un-split GEMM on a buffer-addressed, weight-stationary or row-panel tile, R <= 16 (row-panel: rank 4 per module)");
+    const bool plain = !g.conv && !g.c1 && !g.a1 && g.batch == 1;
+    switch (t->fam) {
+        case Fam::F32: break;
+        case Fam::BL:
+            if (t->ring() && !(plain && g.M % t->bm() == 0 && g.N % t->bn() == 0 && (g.splitk == 1 || (g.K / 64) / g.splitk >= t->nstage())))
+                return no("counted-ring GEMM: plain single-source GEMM that tiles exactly; split: at least NSTAGE K tiles per split");
+            break;
+        case Fam::HALO:
+            if (!halo_geometry_ok(g, t->bm(), 256, t->bm() >= 256 ? 13 : (t->bm() >= 128 ? 9 : 6))) return no("halo conv kernel: unsupported geometry");
+            break;
+        case Fam::HALO8:
+            if (!halo_geometry_ok(g, t->bm(), 512, 7)) return no("256-row halo conv kernel: unsupported geometry");
+            break;
+        case Fam::WS:
+            if (!(plain && g.K == 32 * t->ks() && g.N % t->bn() == 0 && g.M % 64 == 0 && g.lda0 % 8 == 0 && g.out_mode != OUT_NONE))
+                return no("weight-stationary kernel: plain rows, K = 32*KS, N a multiple of the slab, M a multiple of 64");
+            break;
+        case Fam::RP:
+            if (!(plain && g.K == 32 * t->ks() && rp_form_ok(g, *t)))
+                return no("row-panel kernel: plain un-split bf16 row GEMM with K = 32*KS (fp8: packed weights + scales)");
+            break;
+    }
+    return true;
+}
+// A tile named for a whole model (mrisr_debug_force_tile, a table row) meets launches of a form its family does not take.  These three
+// move silently to the default tile of the family that does - f32 or a large operand, a 2 x 2 / sub-pixel conv, a split on a family
+// that cannot split; anything else tile_admits refuses.  gemm_choose and launch_gemm both pass through here.
+static int tile_for_launch(const GemmArgs& g, bool is_bf16, int tile) {
+    const bool bl = is_bf16 && bl_ok(g);
+    const Tile* t = find_tile(tile);
+    if (!t || (t->fam != Fam::F32 && !bl)) t = find_tile(kTileF32);
+    if ((g.kw != 3 || g.subpix) && !t->knows_gather2x2()) t = find_tile(kTileGather2x2);
+    if (g.splitk > 1 && !t->splits()) t = find_tile(bl ? kTileBL : kTileF32);
+    return t->id;
+}
+// the row-panel configuration for this K when the caller must have one (LayerNorm prologue, fp8 operands; 0: none).  bf16,
+// K = 640: the 4-wave form wins on wide outputs (N = 1920: 33 vs 36 us, N = 5120: 62 vs 83 us at M = 8192) although it spills a
+// few registers, the 2-wave form on N = 640 (16.3 vs 20.0 us): tools/probes/rp_probe3.sh.  Elsewhere the 4-wave form where there is one.
+int gemm_rp_tile(const GemmArgs& g) {
+    static const int env = [] { const char* e = getenv("MRISR_RP"); return e ? atoi(e) : 1; }();
+    if (!env) return 0;
+    const int want_nw = (!g.w8 && g.K == 640 && g.N <= 640) ? 2 : 4;
+    int best = 0;
+    for (const Tile& t : kTiles)
+        if (t.fam == Fam::RP && (!best || t.nw() == want_nw) && tile_admits(g, true, t.id, nullptr)) best = t.id;
+    return best;
 }
 static int g_sc_fused = -1;  // test hook: -1 = MRISR_SC_FUSED (default 1), 0 off, 1 on
 extern "C" void mrisr_debug_sc_fused(int on) { g_sc_fused = on; ++g_plan_salt; }
@@ -3248,34 +3207,36 @@ bool ff_proj_fused_enabled() {
 }
 
 // ---- tile / split-K planner ------------------------------------------------------------------
-struct TileCfg { int id, bm, bn; double eff; bool bl; };
-// eff: relative main-loop efficiency measured with tools/gemm_sweep.py (profiles/r01_gemm_sweep.log)
-static const TileCfg kTiles[] = {
-    {14, 128, 128, 1.00, true}, {15, 256, 64, 0.90, true}, {16, 128, 64, 0.88, true}, {18, 64, 128, 0.86, true},
-    {17, 64, 64, 0.60, true},
-    {1, 128, 128, 0.75, false}, {2, 256, 64, 0.65, false}, {3, 128, 64, 0.60, false}, {4, 64, 64, 0.45, false},
-};
 static double g_tile_eff[32] = {0};
 extern "C" void mrisr_debug_set_tile_eff(int id, double eff) { if (id >= 0 && id < 32) g_tile_eff[id] = eff; }
+
+// Which split-K factors s > 1 a tile is considered with: two measured policies, not one rule.
+// cost model: at least 6 K tiles per split
+static bool plan_admits_split(const GemmArgs& g, int s, int nkt) { return g.act != ACT_GEGLU && nkt / s >= 6; }
+// autotuner: at least 4 K tiles per split, at most 4096 128 x 128 tiles' worth of workgroups; the counted rings, the families without
+// split-K and the 2 x 2 / sub-pixel forms are timed un-split only
+static bool tune_admits_split(const GemmArgs& g, const Tile& t, int s, int nkt, long long t128) {
+    return g.act != ACT_GEGLU && nkt / s >= 4 && t128 * s <= 4096 && t.splits() && !t.ring() && g.kw == 3 && !g.subpix;
+}
 
 // cost model: rounds of (2 workgroups x 256 CUs) x time of one workgroup (MFMA work / efficiency + fixed prologue /
 // epilogue latency), plus the split-K slab traffic.  Only the ranking matters.
 static void plan(const GemmArgs& g, bool is_bf16, int fixed_split, int* tile_out, int* split_out) {
     const double cu_flops = 1.0e15 / 256.0 * 1e-6;  // FLOP per microsecond per CU at the kernel's practical rate
     double best = 1e300;
-    int bt = is_bf16 ? 14 : 1, bs = 1;
+    int bt = is_bf16 ? kTileBL : kTileF32, bs = 1;
     const int nkt = g.K / (is_bf16 ? 64 : 32);
-    const bool use_bl = is_bf16 && bl_ok(g);
-    for (const TileCfg& t : kTiles) {
-        if (t.bl != use_bl) continue;
+    const Fam fam = is_bf16 && bl_ok(g) ? Fam::BL : Fam::F32;
+    for (const Tile& t : kTiles) {
+        if (t.fam != fam || t.eff <= 0) continue;
         const double eff = g_tile_eff[t.id] > 0 ? g_tile_eff[t.id] : t.eff;
-        const long long tiles = (long long)((g.M + t.bm - 1) / t.bm) * ((g.N + t.bn - 1) / t.bn) * g.batch;
+        const long long tiles = (long long)((g.M + t.bm() - 1) / t.bm()) * ((g.N + t.bn() - 1) / t.bn()) * g.batch;
         for (int s = 1; s <= 32; s *= 2) {
             if (fixed_split > 0 && s != fixed_split) continue;
-            if (s > 1 && (g.act == ACT_GEGLU || nkt / s < 6)) break;
+            if (s > 1 && !plan_admits_split(g, s, nkt)) break;
             const long long blocks = tiles * s;
             const long long rounds = (blocks + 511) / 512;
-            const double wg_us = 2.0 * t.bm * t.bn * ((double)g.K / s) / (cu_flops * eff) * 2.0 + 4.0;
+            const double wg_us = 2.0 * t.bm() * t.bn() * ((double)g.K / s) / (cu_flops * eff) * 2.0 + 4.0;
             double cost = rounds * wg_us;
             if (s > 1) cost += 2.0 + (double)g.M * g.N * g.batch * (4.0 * s * 2 + 2) / 3.0e6;  // slab write+read
             if (cost < best) { best = cost; bt = t.id; bs = s; }
@@ -3377,7 +3338,7 @@ static int tune(const GemmArgs& g0, int* tile_out, int* split_out) {
     const int nkt = g.K / 64;
     const long long t128 = (long long)((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch;
     double best = 1e30;
-    int bt = 14, bs = 1;
+    int bt = kTileBL, bs = 1;
     hipEvent_t e0, e1;
     MRISR_CHECK_HIP(hipEventCreate(&e0));
     MRISR_CHECK_HIP(hipEventCreate(&e1));
@@ -3387,30 +3348,19 @@ static int tune(const GemmArgs& g0, int* tile_out, int* split_out) {
     MRISR_CHECK_HIP(hipEventCreate(&t0));
     MRISR_CHECK_HIP(hipEventCreate(&t1));
     MRISR_CHECK_HIP(hipEventRecord(t0, nullptr));
-    // 50-52 (weight-stationary short-K kernels) are NOT candidates: correct, but 30-60 % slower than the tiled kernels on
-    // every shape they fit (profiles/r01b_ws_sweep.log: one A fragment per wave makes them LDS-read bound); kept for the record
-    // (32-36, the counted-ring variants, are NOT candidates: on the shapes they were built for - level-2 linears, M = 2,048 - they
-    // tie or lose: 64 x 64: 16.7 us with 2 stages, 17.1 with 3, 24.4 with 4 (LDS then admits 2 workgroups per CU instead of 5);
-    // these GEMMs move 210 MB through LDS in 16.7 us = 12.6 TB/s, i.e. they sit at the L2 -> LDS bandwidth, not on a latency chain:
-    // profiles/r02i_ring_probe.log.  Kept, tested, reachable through mrisr_debug_force_tile.)
-    static const int cand[] = {14, 15, 16, 17, 18, 25, 26, 28, 41, 42, 43, 44, 45, 60, 61, 64, 65};  // (62, 63: fp8 operands, chosen by the launch, not the tuner)  // 27, 29-31 never won a shape (profiles/r01_gemm_sweep_tiles.log)
-    for (int tile : cand) {
-        const bool deep = false;
+    // the candidates: the registry's `cand` column, in its order (the first of equals wins)
+    for (const Tile& t : kTiles) {
+        if (!t.cand) continue;
+        const int tile = t.id;
         {   // debugging aid: MRISR_TUNE_SKIP="41,43" removes candidates
             static const std::string skip = [] { const char* e = getenv("MRISR_TUNE_SKIP"); return std::string(e ? e : ""); }();
             if (!skip.empty() && ("," + skip + ",").find("," + std::to_string(tile) + ",") != std::string::npos) continue;
         }
-        if (tile >= 32 && tile <= 39 && !ring_ok(g, tile)) continue;  // counted-ring variants: exact plain GEMMs only
-        if (g.cs0 && !sc_tail_tile(tile)) continue;  // a 1x1 tail: the 2-stage tiled and 4-wave halo kernels only
-        if (is_halo8(tile)) { if (!halo8_ok(g)) continue; }
-        else if (tile >= 40 && tile < 50 && !halo_ok(g, halo_bm(tile))) continue;  // LDS-halo conv kernels: stride-1 3x3, whole tiles per image
-        if (tile >= 50 && tile < 60 && !ws_ok(g, tile)) continue;  // weight-stationary kernels: short-K plain GEMMs that tile exactly
-        if (tile >= 60 && !rp_ok(g, tile)) continue;  // row-panel kernels: K = 320 / 640 row GEMMs
-        // 5 fragments per wave along N (BN = 160): no (u, gate) pairing for the GEGLU epilogue
-        if ((tile == 25 || tile == 26 || tile == 27 || tile == 31) && g.act == ACT_GEGLU) continue;
-        if (deep && t128 >= 2048) continue;  // plenty of workgroups per CU: the 2-stage structure wins (sweep)
+        // (g.splitk is still the last split timed for the previous candidate, so a row-panel candidate that follows a split one is
+        // refused here - as it always was; the shipped table was tuned with it)
+        if (!tile_admits(g, true, tile, nullptr)) continue;
         for (int s = 1; s <= 32; s *= 2) {
-            if (s > 1 && (g.act == ACT_GEGLU || nkt / s < 4 || t128 * s > 4096 || tile >= 50 || (tile >= 32 && tile <= 39) || g.kw != 3 || g.subpix)) break;
+            if (s > 1 && !tune_admits_split(g, t, s, nkt, t128)) break;
             const size_t pbytes = s > 1 ? (size_t)s * g.M * g.N * 4 * zb : 0;
             if (pbytes > ((size_t)1 << 30)) break;
             if (s > 1 && g_ts.reserve(4, pbytes, false)) return 1;
@@ -3454,7 +3404,6 @@ static int tune(const GemmArgs& g0, int* tile_out, int* split_out) {
     return 0;
 }
 
-// Chooses tile + split-K for g (sets g.tile / g.splitk).  Deterministic per signature within a process.
 static int g_force_split = 0;  // test hook: split-K factor for every GEMM that can be split (exercises the reduce kernel's epilogue)
 extern "C" void mrisr_debug_force_split(int s) { g_force_split = s; }
 // test hook / MRISR_GEMM_FLAGS: 8 = LoRA up-projection in the scalar epilogue instead of the matrix cores, 16 = head-major outputs
@@ -3467,11 +3416,11 @@ int xattn_tail_flags() { return g_gemm_flags; }
 extern "C" void mrisr_debug_set_tuned(const char* key, int tile, int split) { g_tuned[key] = {tile, split}; }
 int g_subpix_override = -1;
 extern "C" void mrisr_debug_subpix(int min_rows) { g_subpix_override = min_rows; }
-static int g_prefer_tile = 0;  // test hook: use this specialised kernel (halo 41-45 / weight-stationary 50-52) wherever it is eligible
+static int g_prefer_tile = 0;  // test hook: use this tile of a specialised family (halo, 256-row halo, weight-stationary, row-panel) wherever it is eligible
 extern "C" void mrisr_debug_prefer_tile(int t) { g_prefer_tile = t; }
 
+// Chooses tile + split-K for g (sets g.tile / g.splitk).  Deterministic per signature within a process.
 int gemm_choose(GemmArgs& g, bool is_bf16) {
-    int t = 0, s = 1;
     if (g.ln_gamma || g.w8) {  // a fused LayerNorm prologue / fp8 operands exist only in the row-panel kernel (the caller checked gemm_rp_tile)
         g.tile = gemm_rp_tile(g);
         g.splitk = 1;
@@ -3480,40 +3429,51 @@ int gemm_choose(GemmArgs& g, bool is_bf16) {
     }
     const bool sc_tail = g.cs0 || g.s0;
     if (sc_tail) MRISR_REQUIRE(is_bf16 && gemm_sc_tail_ok(g), "1x1 tail: bf16 stride-1 3x3 conv, channel counts multiples of 64");
-    // (a forced / preferred kernel that cannot carry a 1x1 tail is not taken for a launch that has one: the planner decides)
-    if (g_force_tile && !(sc_tail && !(sc_tail_tile(g_force_tile) && (g_force_tile < 40 || halo_ok(g, halo_bm(g_force_tile)))))) { g.tile = g_force_tile; if (g.splitk < 1) g.splitk = 1; return 0; }
-    if (g_prefer_tile && !(sc_tail && !sc_tail_tile(g_prefer_tile)) && is_bf16 && bl_ok(g) &&
-        ((g_prefer_tile >= 60 && rp_ok(g, g_prefer_tile)) || (g_prefer_tile >= 50 && g_prefer_tile < 60 && ws_ok(g, g_prefer_tile)) || (g_prefer_tile >= 40 && g_prefer_tile < 50 && (is_halo8(g_prefer_tile) ? halo8_ok(g) : halo_ok(g, halo_bm(g_prefer_tile)))))) {
-        g.tile = g_prefer_tile;
-        g.splitk = 1;
-        return 0;
+    if (g_force_tile) {
+        if (g.splitk < 1) g.splitk = 1;
+        const int t = tile_for_launch(g, is_bf16, g_force_tile);
+        const char* why = nullptr;
+        const bool admitted = tile_admits(g, is_bf16, t, &why);
+        // (a forced kernel that cannot carry a 1x1 tail is not taken for a launch that has one: the planner decides)
+        if (!sc_tail) MRISR_REQUIRE(admitted, why);
+        if (admitted) { g.tile = t; return 0; }
     }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    g.splitk = 1;
+    // a preferred kernel is one of the specialised families, taken wherever it is eligible
+    if (const Tile* p = find_tile(g_prefer_tile)) {
+        if (p->fam != Fam::F32 && p->fam != Fam::BL && tile_admits(g, is_bf16, p->id, nullptr)) { g.tile = p->id; return 0; }
+    }
+    int t = 0, s = 1;
     if (is_bf16 && bl_ok(g) && autotune_enabled()) {
         if (tune(g, &t, &s)) return 1;
     } else {
         plan(g, is_bf16, 0, &t, &s);
     }
-    (void)cs;
-    if ((t >= 60 && !rp_ok(g, t)) || (t >= 32 && t <= 39 && (!ring_ok(g, t) || s > 1)) || (is_halo8(t) && !halo8_ok(g))) plan(g, is_bf16, 0, &t, &s);  // (a table entry tuned without this launch's operand forms)
-    if (sc_tail && !(sc_tail_tile(t) && (t < 40 || halo_ok(g, halo_bm(t))))) plan(g, true, 0, &t, &s);  // (a table row naming a kernel without the tail: the cost model picks among 14-18)
-    if (g_force_split > 1 && g.act != ACT_GEGLU && g.K / (is_bf16 ? 64 : 32) >= g_force_split && !g.lora_a) {
-        s = g_force_split;
-        if (t >= 50) t = is_bf16 ? 14 : 1;
-    }
-    g.tile = t;
     g.splitk = s;
+    if (!tile_admits(g, is_bf16, tile_for_launch(g, is_bf16, t), nullptr)) {  // (a table entry tuned without this launch's operand forms: the cost model picks)
+        plan(g, is_bf16, 0, &t, &s);
+        g.splitk = s;
+    }
+    if (g_force_split > 1 && g.act != ACT_GEGLU && g.K / (is_bf16 ? 64 : 32) >= g_force_split && !g.lora_a) g.splitk = g_force_split;
+    g.tile = tile_for_launch(g, is_bf16, t);
     return 0;
 }
 
 int gemm_prepare() {
     if (init_zero_page()) return 1;
-    if (prepare_all<float>()) return 1;
-    if (prepare_all<bf16>()) return 1;
+    // launch attributes of the instantiations that are set ahead of the first launch (the other families set theirs on first use)
+#define TILE_PREPARE_F32(a, b, c, d, e) (prepare_cfg<float, a, b, c, d>() || prepare_cfg<bf16, a, b, c, d>())
+#define TILE_PREPARE_BL(a, b, c, d, e) prepare_bl<a, b, c, d, e>()
+#define TILE_PREPARE_HALO(a, b, c, d, e) 0
+#define TILE_PREPARE_HALO8(a, b, c, d, e) 0
+#define TILE_PREPARE_WS(a, b, c, d, e) 0
+#define TILE_PREPARE_RP(a, b, c, d, e) 0
+#define X(id, fam, a, b, c, d, e, eff, cand) if (TILE_PREPARE_##fam(a, b, c, d, e)) return 1;
+    TILES(X)
+#undef X
     if (direct_conv_prepare()) return 1;
     if (xattn_tail_prepare()) return 1;
-    if (mlp_fused_prepare()) return 1;
-    return prepare_bls();
+    return mlp_fused_prepare();
 }
 
 // per-stream arrival counters for the in-kernel split-K reduction: launches on one stream are ordered and every launch leaves its
@@ -3523,14 +3483,7 @@ int gemm_prepare() {
 // 10.92 vs 10.82 ms per denoising step in the replayed graph (41 fewer launches, but every workgroup's agent-scope release is an L2
 // write-back and the last arriver's tail is latency-bound); launched eagerly the split GEMMs take 3-4x longer (M=512 s=8 conv: 33 ->
 // 138 us), profiles/r02m_splitk_inkernel.log.  Kept as a tested alternative (tests/test_gpu_ops.py::test_splitk_reduced_inside_the_gemm_kernel).
-static bool tile_reduces_in_kernel(int tile) {
-#define X(id, bm, bn, wm, wn, ...) if (tile == id) return ((bm) / (wm) / 16) * ((bn) / (wn) / 16) <= 20;  // as the kernels' `if constexpr`
-    BL_CFGS(X)
-    HALO_CFGS(X)
-#undef X
-    return false;
-}
-static long long tile_count(int, const GemmArgs& g) { return (long long)((g.M + 63) / 64) * ((g.N + 63) / 64); }  // upper bound: no tile is smaller than 64 x 64
+static long long tile_count(const GemmArgs& g) { return (long long)((g.M + 63) / 64) * ((g.N + 63) / 64); }  // upper bound: no tile is smaller than 64 x 64
 static constexpr int kSkCounters = 16384;
 static int g_sk_inkernel = -1;  // test hook: 0 = the separate reduce kernel, 1 = in-kernel, -1 = MRISR_SK_INKERNEL (default 0)
 extern "C" void mrisr_debug_sk_inkernel(int on) { g_sk_inkernel = on; }
@@ -3552,8 +3505,10 @@ static unsigned* sk_counters_for(hipStream_t st) {
 }
 
 template <typename T>
-int launch_gemm(const GemmArgs& g, hipStream_t st) {
+int launch_gemm(const GemmArgs& g_in, hipStream_t st) {
+    constexpr bool is_bf16 = sizeof(T) == 2;
     constexpr int BK = 128 / (int)sizeof(T);
+    GemmArgs g = g_in;  // what this function and the launchers fill in (stage_out, dbg, pretouch, sk_counters, group_m, a zero bias) stays out of the caller's struct
     MRISR_REQUIRE(g.K % BK == 0, "K must be a multiple of the 128-byte K tile");
     MRISR_REQUIRE(g.N % 4 == 0, "N must be a multiple of 4");
     MRISR_REQUIRE(g.c0 % BK == 0 && g.c1 % BK == 0, "channel extents must be multiples of the K tile");
@@ -3563,53 +3518,34 @@ int launch_gemm(const GemmArgs& g, hipStream_t st) {
     if (g.conv) { MRISR_REQUIRE(g.K == g.kw * g.kw * (g.c0 + g.c1) + g.cs0 + g.cs1 && (g.kw == 3 || g.kw == 2), "conv K"); }
     else { MRISR_REQUIRE(g.K == g.c0 + g.c1, "plain K"); }
     if (g.kw != 3 || g.subpix) {
-        MRISR_REQUIRE(sizeof(T) == 2 && g.conv && !g.c1 && g.stride == 1 && !g.ups && !g.zstuff && g.splitk == 1 && (!g.subpix || g.batch == 4),
+        MRISR_REQUIRE(is_bf16 && g.conv && !g.c1 && g.stride == 1 && !g.ups && !g.zstuff && g.splitk == 1 && (!g.subpix || g.batch == 4),
                       "2 x 2 / sub-pixel conv: bf16 buffer-addressed kernels, single source, stride 1, un-split, four parity batches");
     }
+    int tile = g.tile ? g.tile : g_force_tile, s;
+    if (!tile) plan(g, is_bf16, g.splitk, &tile, &s);
+    tile = tile_for_launch(g, is_bf16, tile);
+    const char* why = nullptr;
+    MRISR_REQUIRE(tile_admits(g, is_bf16, tile, &why), why);
     static const int stage_env = [] { const char* e = getenv("MRISR_STAGE_OUT"); return e ? atoi(e) : 2; }();  // 0 off, 1 tiled kernels, 2 + halo kernels (default), 3: as 2 but residual added before staging
-    const_cast<GemmArgs&>(g).stage_out = stage_env;
-    const_cast<GemmArgs&>(g).dbg = g_gemm_flags;
-    int tile = g.tile ? g.tile : g_force_tile, s = g.splitk;
-    if (!tile) plan(g, sizeof(T) == 2, g.splitk, &tile, &s);
-    if ((sizeof(T) != 2 || !bl_ok(g)) && tile > 4) tile = 1;
-    if ((g.kw != 3 || g.subpix) && !(tile >= 14 && tile <= 31)) tile = 25;  // only gemm_bl_kernel's gather knows these forms
-    if (g.cs0 || g.cs1 || g.s0 || g.s1) {
-        MRISR_REQUIRE(sizeof(T) == 2 && gemm_sc_tail_ok(g), "1x1 tail: bf16 stride-1 3x3 conv, channel counts multiples of 64, operands below 2 GiB");
-        MRISR_REQUIRE(sc_tail_tile(tile) && (tile < 40 || halo_ok(g, halo_bm(tile))), "1x1 tail: only the 2-stage tiled kernels (14-31) and the 4-wave halo kernels (41-45) carry it");
-    }
-    // split-K: the bf16 DMA kernels (tiled and halo) finish the reduction themselves
+    g.stage_out = stage_env;
+    g.dbg = g_gemm_flags;
     {   // cold-weight pre-touch: matrices of at least MRISR_PRETOUCH_MIN_KB (default 512; 0 ... 1024 measure the same); MRISR_PRETOUCH=0 turns it off
         static const int on = [] { const char* e = getenv("MRISR_PRETOUCH"); return e ? atoi(e) : 1; }();
         static const long long min_b = [] { const char* e = getenv("MRISR_PRETOUCH_MIN_KB"); return (e ? atoll(e) : 512ll) * 1024; }();
         static const int cap = [] { const char* e = getenv("MRISR_PRETOUCH_CAP"); return e ? atoi(e) : 32; }();  // 1-KiB pieces per wave at most
-        const_cast<GemmArgs&>(g).pretouch = (on && sizeof(T) == 2 && g.batch == 1 && (long long)g.N * g.K * 2 >= min_b) ? cap : 0;
+        g.pretouch = (on && is_bf16 && g.batch == 1 && (long long)g.N * g.K * 2 >= min_b) ? cap : 0;
     }
-    const_cast<GemmArgs&>(g).sk_counters = nullptr;
-    if (g.splitk > 1 && sizeof(T) == 2 && !g.defer_reduce && tile_reduces_in_kernel(tile) && !g.cs0) {
-        const long long ntiles = tile_count(tile, g) * (long long)g.batch;
-        if (ntiles > 0 && ntiles <= kSkCounters) const_cast<GemmArgs&>(g).sk_counters = sk_counters_for(st);
+    // split-K: the bf16 DMA kernels (tiled and halo) can finish the reduction themselves
+    g.sk_counters = nullptr;
+    if (g.splitk > 1 && is_bf16 && !g.defer_reduce && find_tile(tile)->reduces_in_kernel() && !g.cs0) {
+        const long long ntiles = tile_count(g) * (long long)g.batch;
+        if (ntiles > 0 && ntiles <= kSkCounters) g.sk_counters = sk_counters_for(st);
     }
-    int rc;
+    int rc = 1;
     switch (tile) {
-        case 2: rc = launch_cfg<T, 256, 64, 4, 1>(g, st); break;
-        case 3: rc = launch_cfg<T, 128, 64, 2, 2>(g, st); break;
-        case 4: rc = launch_cfg<T, 64, 64, 2, 2>(g, st); break;
-#define X(id, bm, bn, wm, wn, ns) case id: rc = launch_bl<bm, bn, wm, wn, ns>(g, st); break;
-        BL_CFGS(X)
+#define X(id, fam, a, b, c, d, e, eff, cand) case id: rc = TILE_LAUNCH_##fam(a, b, c, d, e)(g, st); break;
+        TILES(X)
 #undef X
-#define X(id, bm, bn, wm, wn) case id: rc = launch_halo<bm, bn, wm, wn>(g, st); break;
-        HALO_CFGS(X)
-#undef X
-#define X(id, bn, ns) case id: rc = launch_halo8<bn, ns>(g, st); break;
-        HALO8_CFGS(X)
-#undef X
-#define X(id, ks, nb) case id: rc = launch_ws<ks, nb>(g, st); break;
-        WS_CFGS(X)
-#undef X
-#define X(id, ks, nf, f8, nw) case id: rc = launch_rp<ks, nf, f8, nw>(id, g, st); break;
-        RP_CFGS(X)
-#undef X
-        default: rc = launch_cfg<T, 128, 128, 2, 2>(g, st); break;
     }
     if (rc) return rc;
     if (g.splitk > 1 && !g.sk_counters && !g.defer_reduce) return launch_splitk_reduce<T>(g, st);

@@ -260,7 +260,7 @@ struct Runner {
         float* z = static_cast<float*>(alloc((size_t)M * lw.R * sizeof(float)));
         if (!z) return 7;
         if (z_out) *z_out = z;
-        const bool in_kernel = sizeof(T) == 2 && lw.R <= 16 && g.splitk == 1 && g.tile >= 14 && lora_in_kernel() && (g.tile < 60 || lw.r == 4);
+        const bool in_kernel = sizeof(T) == 2 && g.splitk == 1 && lora_in_kernel() && gemm_tile_lora_in_kernel(g.tile, lw.r, lw.R);
         MRISR_REQUIRE(in_kernel || !g.ln_gamma, "fused LayerNorm needs the in-kernel LoRA form");
         if (in_kernel) {
             g.lora_a = lw.loraA; g.lora_R = lw.R; g.lora_zout = z_out ? z : nullptr;

@@ -525,7 +525,7 @@ struct Trainer : Runner<T> {
             if (lw.R && lw.r != 4) g.no_rp = 1;
             TRY(gemm_choose(g, sizeof(T) == 2));
             // as in the forward: dz = dY (s B) can ride along the dgrad GEMM (the <= 16 rows of s B^T as extra weight rows)
-            in_kernel = lw.R && sizeof(T) == 2 && lw.R <= 16 && g.splitk == 1 && g.tile >= 14 && lora_in_kernel();
+            in_kernel = sizeof(T) == 2 && g.splitk == 1 && lora_in_kernel() && gemm_tile_lora_in_kernel(g.tile, lw.r, lw.R);
         }
         if (lw.R) {
             MRISR_REQUIRE(z && lw.loraBT && lw.loraAT && m.grad, "adapter backward state");

@@ -78,32 +78,22 @@ struct AdRunner {
         x.p = alloc(x.numel() * sizeof(T));
         return x;
     }
-    int gemm(GemmArgs& g) {  // plans split-K (the partial sums live in the arena) and, unless dry, launches
-        TRY(gemm_choose(g, sizeof(T) == 2));
-        if (g.splitk > 1) {
-            g.partial = static_cast<float*>(alloc((size_t)g.splitk * g.M * g.N * sizeof(float)));
-            if (!g.partial) return 7;
-        }
-        if (dry) return 0;
-        return launch_gemm<T>(g, st);
-    }
+    // plans split-K (the partial sums live in the arena) and, unless dry, launches
+    int gemm(GemmArgs& g) { return gemm_run<T>(g, st, dry, [this](size_t n) { return alloc(n); }); }
     int conv(const Act& x, const ConvW& cw, int stride, int act, const Act* resid, Act* out) {
         MRISR_REQUIRE(cw.cin == x.C, "adapter conv channel mismatch");
         const int Ho = (x.H - 1) / stride + 1, Wo = (x.W - 1) / stride + 1;
         *out = new_act(x.B, cw.ks == 3 ? Ho : x.H, cw.ks == 3 ? Wo : x.W, cw.cout);
         if (!out->p) return 7;
         GemmArgs g;
-        g.a0 = x.p; g.c0 = x.C; g.lda0 = x.C;
-        g.w = cw.w; g.N = cw.cout; g.bias = cw.b; g.act = act;
+        ga_rows(g, x);
         if (cw.ks == 3) {
-            g.conv = 1; g.B = x.B; g.Hin = x.H; g.Win = x.W; g.Hout = Ho; g.Wout = Wo; g.stride = stride;
-            g.M = x.B * Ho * Wo; g.K = 9 * x.C;
+            ga_conv3(g, x, stride); ga_weight(g, cw.w, x.B * Ho * Wo, cw.cout, 9 * x.C);
         } else {
             MRISR_REQUIRE(stride == 1, "1x1 conv stride");
-            g.M = (int)x.rows(); g.K = x.C;
+            ga_weight(g, cw.w, (int)x.rows(), cw.cout, x.C);
         }
-        if (resid) { g.resid = resid->p; g.ldr = resid->C; }
-        g.out = out->p; g.ldo = cw.cout;
+        g.bias = cw.b; g.act = act; ga_resid(g, resid); ga_out(g, out->p, cw.cout);
         return gemm(g);
     }
     // ---- backward building blocks: the two composites of train_ops.h on this arena ----
@@ -117,10 +107,8 @@ struct AdRunner {
             return conv_dgrad_run<T>(st, dry, [this](GemmArgs& g) { return gemm(g); }, dy.p, dy.B, dy.H, dy.W, cw.cout, cw.cin, cw.wd, up,
                                      dx->p, resid ? resid->p : nullptr, resid ? resid->C : 0);
         GemmArgs g;
-        g.a0 = dy.p; g.c0 = cw.cout; g.lda0 = cw.cout;
-        g.w = cw.wd; g.M = (int)dy.rows(); g.N = cw.cin; g.K = cw.cout;
-        if (resid) { g.resid = resid->p; g.ldr = resid->C; }
-        g.out = dx->p; g.ldo = cw.cin;
+        ga_rows(g, dy.p, cw.cout, cw.cout); ga_weight(g, cw.wd, (int)dy.rows(), cw.cin, cw.cout); ga_resid(g, resid);
+        ga_out(g, dx->p, cw.cin);
         return gemm(g);
     }
     // dW, db of y = conv(x), accumulated into the bound gradient vector

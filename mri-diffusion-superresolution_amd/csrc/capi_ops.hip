@@ -15,6 +15,29 @@ using namespace mrisr;
 // =================================================================================================
 // single-op entry points (parity tests drive the very kernels the models launch)
 // =================================================================================================
+namespace {
+struct OpScratch {  // scratch of one call: freed when the entry returns (after its stream synchronisation)
+    std::vector<std::unique_ptr<DevBuf>> bufs;
+    void* alloc(size_t bytes, bool zero = false) {
+        bufs.emplace_back(new DevBuf());
+        if (bufs.back()->reserve(bytes ? bytes : 1, zero)) return nullptr;
+        return bufs.back()->p;
+    }
+};
+template <typename T>
+int op_gemm_run(OpScratch& sc, hipStream_t st, GemmArgs& g) {  // Runner::run_gemm on scratch buffers
+    return gemm_run<T>(g, st, false, [&sc](size_t n) { return sc.alloc(n); });
+}
+// honour a caller's split-K, else plan (a ForcedTile in scope applies either way); replan: with a split-K given, the planner still picks the
+// tile.  The slabs come from `part`; the caller launches.
+template <typename T>
+int op_plan(GemmArgs& g, int splitk, bool replan, DevBuf& part) {
+    g.splitk = splitk;
+    if (splitk <= 0) { g.splitk = 1; TRY(gemm_choose(g, sizeof(T) == 2)); }
+    else if (replan) { TRY(gemm_choose(g, sizeof(T) == 2)); g.splitk = splitk; }
+    return gemm_alloc_partial(g, devbuf_alloc(part));
+}
+}  // namespace
 template <typename T>
 __global__ void rows_to_heads_kernel(const T* x, T* dst, int B, int N, int H, int hd, int npad, int dpad, int tr) {
     const long long total = (long long)B * N * H * hd;
@@ -56,31 +79,21 @@ static int op_conv3x3_t(const mrisr_tensor* x, const mrisr_tensor* x2, const flo
         TRY(planes.reserve((size_t)4 * B * H * W * cout * sizeof(T), false));
         TRY(launch_pack_conv_subpix<T>(w, sp.p, cout, Cin, st));
         GemmArgs g;
-        g.a0 = x->data; g.c0 = C0; g.lda0 = C0;
-        g.conv = 1; g.B = B; g.Hin = H; g.Win = W; g.Hout = H; g.Wout = W; g.stride = 1;
-        g.kw = 2; g.subpix = 1; g.batch = 4; g.w_bs = (long long)cout * 4 * Cin; g.o_bs = (long long)B * H * W * cout;
-        g.w = sp.p; g.M = B * H * W; g.N = cout; g.K = 4 * Cin; g.bias = bias; g.out = planes.p; g.ldo = cout;
-        TRY(gemm_choose(g, true));
-        TRY(launch_gemm<T>(g, st));
+        ga_rows(g, x->data, C0, C0); ga_conv3(g, B, H, W); g.kw = 2; g.subpix = 1;
+        ga_batch(g, 4, 0, (long long)cout * 4 * Cin, (long long)B * H * W * cout); ga_weight(g, sp.p, B * H * W, cout, 4 * Cin);
+        g.bias = bias; ga_out(g, planes.p, cout);
+        TRY(gemm_run<T>(g, st, false, devbuf_alloc(part)));  // (un-split: a 2 x 2 conv takes no split-K)
         TRY(launch_subpix_shuffle<T>(planes.p, y->data, B, H, W, cout, st));
         MRISR_CHECK_HIP(hipStreamSynchronize(st));
         return 0;
     }
     GemmArgs g;
-    g.a0 = x->data; g.c0 = C0; g.lda0 = C0;
-    if (x2) { g.a1 = x2->data; g.c1 = C1; g.lda1 = C1; }
-    const int Hc = H << ups, Wc = W << ups;
-    g.conv = 1; g.B = B; g.Hin = H; g.Win = W; g.Hout = (Hc - 1) / stride + 1; g.Wout = (Wc - 1) / stride + 1;
-    g.stride = stride; g.ups = ups;
+    ga_rows(g, x->data, C0, C0);
+    if (x2) ga_rows2(g, x2->data, C1, C1);
+    ga_conv3(g, B, H, W, stride, ups);
     MRISR_REQUIRE(y->shape[1] == cout && y->shape[2] == g.Hout && y->shape[3] == g.Wout, "conv output shape");
-    g.w = wp.p; g.M = B * g.Hout * g.Wout; g.N = cout; g.K = 9 * Cin; g.bias = bias; g.act = act;
-    g.out = y->data; g.ldo = cout;
-    g.splitk = splitk;
-    if (splitk <= 0) { g.splitk = 1; TRY(gemm_choose(g, sizeof(T) == 2)); }
-    if (g.splitk > 1) {
-        TRY(part.reserve((size_t)g.splitk * g.M * g.N * sizeof(float), false));
-        g.partial = static_cast<float*>(part.p);
-    }
+    ga_weight(g, wp.p, B * g.Hout * g.Wout, cout, 9 * Cin); g.bias = bias; g.act = act; ga_out(g, y->data, cout);
+    TRY(op_plan<T>(g, splitk, false, part));
     TRY(launch_gemm<T>(g, st));
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
@@ -116,10 +129,10 @@ static int op_conv3x3_sc_t(const mrisr_tensor* x, const mrisr_tensor* x2, const 
     TRY(launch_pack_conv3x3<T>(w, w9.p, cout, Cin, 3, st));
     TRY(launch_pack_rows<T>(w_sc, cout, Cs, wsc.p, Cs, 0, 0, 0, 0, 1.0f, st));
     GemmArgs g;
-    g.a0 = x->data; g.c0 = C0; g.lda0 = C0;
-    if (x2) { g.a1 = x2->data; g.c1 = C1; g.lda1 = C1; }
-    g.conv = 1; g.B = B; g.Hin = H; g.Win = W; g.Hout = H; g.Wout = W;
-    g.M = B * H * W; g.N = cout; g.out = y->data; g.ldo = cout;
+    ga_rows(g, x->data, C0, C0);
+    if (x2) ga_rows2(g, x2->data, C1, C1);
+    ga_conv3(g, B, H, W); ga_out(g, y->data, cout);
+    const int M = B * H * W;
     if (fused) {
         TRY(bank.reserve((size_t)cout * Kt * sizeof(T), false));
         TRY(bsum.reserve((size_t)cout * sizeof(float), false));
@@ -128,29 +141,21 @@ static int op_conv3x3_sc_t(const mrisr_tensor* x, const mrisr_tensor* x2, const 
                                          hipMemcpyDeviceToDevice, st));
         MRISR_CHECK_HIP(hipMemcpyAsync(bsum.p, bias, (size_t)cout * sizeof(float), hipMemcpyDeviceToDevice, st));
         TRY(launch_add_inplace<float>(bsum.p, bias_sc, cout, st));
-        g.s0 = xs->data; g.cs0 = S0; g.lds0 = S0;
-        if (xs2) { g.s1 = xs2->data; g.cs1 = S1; g.lds1 = S1; }
-        g.w = bank.p; g.K = (int)Kt; g.bias = static_cast<const float*>(bsum.p);
+        ga_tail(g, xs->data, S0, S0);
+        if (xs2) ga_tail2(g, xs2->data, S1, S1);
+        ga_weight(g, bank.p, M, cout, (int)Kt); g.bias = static_cast<const float*>(bsum.p);
     } else {
         GemmArgs s;
-        s.a0 = xs->data; s.c0 = S0; s.lda0 = S0;
-        if (xs2) { s.a1 = xs2->data; s.c1 = S1; s.lda1 = S1; }
-        s.w = wsc.p; s.M = g.M; s.N = cout; s.K = Cs; s.bias = bias_sc; s.out = y->data; s.ldo = cout;
-        TRY(gemm_choose(s, true));
+        ga_rows(s, xs->data, S0, S0);
+        if (xs2) ga_rows2(s, xs2->data, S1, S1);
+        ga_weight(s, wsc.p, M, cout, Cs); s.bias = bias_sc; ga_out(s, y->data, cout);
         DevBuf spart;
-        if (s.splitk > 1) { TRY(spart.reserve((size_t)s.splitk * s.M * s.N * sizeof(float), false)); s.partial = static_cast<float*>(spart.p); }
-        TRY(launch_gemm<T>(s, st));
+        TRY(gemm_run<T>(s, st, false, devbuf_alloc(spart)));
         MRISR_CHECK_HIP(hipStreamSynchronize(st));
-        g.w = w9.p; g.K = (int)K9; g.bias = bias; g.resid = y->data; g.ldr = cout;
+        ga_weight(g, w9.p, M, cout, (int)K9); g.bias = bias; ga_resid(g, y->data, cout);
     }
     ForcedTile forced(tile);
-    g.splitk = splitk;
-    if (splitk <= 0) { g.splitk = 1; TRY(gemm_choose(g, true)); }
-    else if (!tile) { const int sk = splitk; TRY(gemm_choose(g, true)); g.splitk = sk; }
-    if (g.splitk > 1) {
-        TRY(part.reserve((size_t)g.splitk * g.M * g.N * sizeof(float), false));
-        g.partial = static_cast<float*>(part.p);
-    }
+    TRY(op_plan<T>(g, splitk, !tile, part));
     TRY(launch_gemm<T>(g, st));
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
@@ -159,14 +164,7 @@ static int op_conv3x3_sc_t(const mrisr_tensor* x, const mrisr_tensor* x2, const 
 // (h W2^T + b2 + t) Wp^T + bp + x: a transformer block's ff.net.2 followed by the transformer's proj_out.  fused: ONE launch over K = [K4 | C]
 // on the composed bank [Wp W2 | Wp] (launch_compose_ff_proj), sources h and t, bias Wp b2 + bp, residual x; otherwise the two launches it
 // replaces (the intermediate rounded to bf16).  Every launch is planned by gemm_choose (`tile` and mrisr_debug_force_split apply).
-static int run_planned(GemmArgs& g, DevBuf& part, hipStream_t st) {
-    TRY(gemm_choose(g, true));
-    if (g.splitk > 1) {
-        TRY(part.reserve((size_t)g.splitk * g.M * g.N * sizeof(float), false));
-        g.partial = static_cast<float*>(part.p);
-    }
-    return launch_gemm<bf16>(g, st);
-}
+static int run_planned(GemmArgs& g, DevBuf& part, hipStream_t st) { return gemm_run<bf16>(g, st, false, devbuf_alloc(part)); }
 static int op_ff_proj_t(const mrisr_tensor* h, const mrisr_tensor* t, const mrisr_tensor* x, const float* w2, const float* b2, const float* wp,
                         const float* bp, int tile, int fused, mrisr_tensor* y, hipStream_t st) {
     typedef bf16 T;
@@ -181,10 +179,8 @@ static int op_ff_proj_t(const mrisr_tensor* h, const mrisr_tensor* t, const mris
         TRY(launch_compose_ff_proj(wp, w2, b2, bp, bank.p, Kt, static_cast<float*>(bsum.p), C, K4, st));
         TRY(launch_pack_rows<T>(wp, C, C, bank.p, Kt, 0, K4, 0, 0, 1.0f, st));
         GemmArgs g;
-        g.a0 = h->data; g.c0 = K4; g.lda0 = K4;
-        g.a1 = t->data; g.c1 = C; g.lda1 = C;
-        g.w = bank.p; g.M = M; g.N = C; g.K = Kt; g.bias = static_cast<const float*>(bsum.p);
-        g.resid = x->data; g.ldr = C; g.out = y->data; g.ldo = C; g.no_rp = 1;
+        ga_rows(g, h->data, K4, K4); ga_rows2(g, t->data, C, C); ga_weight(g, bank.p, M, C, Kt); g.bias = static_cast<const float*>(bsum.p);
+        ga_resid(g, x->data, C); ga_out(g, y->data, C); g.no_rp = 1;
         ForcedTile forced(tile);
         TRY(run_planned(g, part, st));
     } else {
@@ -194,10 +190,11 @@ static int op_ff_proj_t(const mrisr_tensor* h, const mrisr_tensor* t, const mris
         TRY(launch_pack_rows<T>(w2, C, K4, w2p.p, K4, 0, 0, 0, 0, 1.0f, st));
         TRY(launch_pack_rows<T>(wp, C, C, wpp.p, C, 0, 0, 0, 0, 1.0f, st));
         GemmArgs g1, g2;
-        g1.a0 = h->data; g1.c0 = K4; g1.lda0 = K4; g1.w = w2p.p; g1.M = M; g1.N = C; g1.K = K4; g1.bias = b2;
-        g1.resid = t->data; g1.ldr = C; g1.out = mid.p; g1.ldo = C;
-        g2.a0 = mid.p; g2.c0 = C; g2.lda0 = C; g2.w = wpp.p; g2.M = M; g2.N = C; g2.K = C; g2.bias = bp;
-        g2.resid = x->data; g2.ldr = C; g2.out = y->data; g2.ldo = C;
+        auto linear = [&](GemmArgs& g, const void* a, int k, const void* w, const float* b, const void* resid, void* out) {
+            ga_rows(g, a, k, k); ga_weight(g, w, M, C, k); g.bias = b; ga_resid(g, resid, C); ga_out(g, out, C);
+        };
+        linear(g1, h->data, K4, w2p.p, b2, t->data, mid.p);
+        linear(g2, mid.p, C, wpp.p, bp, x->data, y->data);
         ForcedTile forced(tile);
         TRY(run_planned(g1, part, st));
         MRISR_CHECK_HIP(hipStreamSynchronize(st));  // (`part` is reused)
@@ -215,7 +212,7 @@ static int op_attention_t(const mrisr_tensor* q, const mrisr_tensor* k, const mr
     constexpr int BK = 128 / (int)sizeof(T);
     const bool use_flash = flash && sizeof(T) == 2;
     const int dpad = round_up(hd, use_flash ? 32 : BK), npad = round_up(N, 64), nkpad = round_up(Nk, 64);
-    DevBuf qb, kb, vb, sb, pb;
+    DevBuf qb, kb, vb;
     TRY(qb.reserve((size_t)B * H * npad * dpad * sizeof(T), true));
     TRY(kb.reserve((size_t)B * H * nkpad * dpad * sizeof(T), true));
     TRY(vb.reserve((size_t)B * H * dpad * nkpad * sizeof(T), true));
@@ -227,38 +224,22 @@ static int op_attention_t(const mrisr_tensor* q, const mrisr_tensor* k, const mr
     conv(k, kb.p, Nk, nkpad, 0);
     conv(v, vb.p, Nk, nkpad, 1);
     MRISR_CHECK_HIP(hipGetLastError());
-    const float scale = 1.0f / sqrtf((float)hd);
+    // from here on the core the models run (gemm_args.h), on scratch buffers
+    OpScratch sc;
+    auto scratch = [&sc](size_t n) { return sc.alloc(n); };
+    AttnGeom geo;
+    geo.B = B; geo.H = H; geo.N = N; geo.npad = npad; geo.hd = hd; geo.dpad = dpad; geo.nk = Nk; geo.nkpad = nkpad;
     if (use_flash) {
+        const bool fp8 = flash == 2;  // fp8 (OCP e4m3) Q K^T and P V
         AttnArgs a;
-        a.q = qb.p; a.k = kb.p; a.vt = vb.p; a.out = out->data;
-        a.B = B; a.H = H; a.nq = N; a.nk = Nk; a.nkpad = nkpad; a.hd = hd; a.dpad = dpad; a.scale = scale;
-        if (flash == 2) {  // fp8 (OCP e4m3) Q K^T and P V
-            DevBuf k8, v8, sc;
-            TRY(k8.reserve((size_t)B * H * nkpad * dpad, false));
-            TRY(v8.reserve((size_t)B * H * nkpad * dpad, false));
-            TRY(sc.reserve((size_t)B * H * 4 * sizeof(float), false));
-            a.k8 = k8.p; a.vt8 = v8.p; a.f8_scales = static_cast<float*>(sc.p);
-            TRY(launch_attention_fp8(a, st));
-            MRISR_CHECK_HIP(hipStreamSynchronize(st));
-        } else {
-            TRY(launch_attention_bf16(a, st));
-        }
+        TRY(attn_flash_args(a, geo, qb.p, kb.p, vb.p, out->data, nullptr, fp8, scratch));
+        TRY(attn_flash_launch(a, fp8, false, st));
     } else {
-        const int BH = B * H;
-        TRY(sb.reserve((size_t)BH * N * nkpad * sizeof(float), false));
-        void* P = sb.p;
-        if (sizeof(T) == 2) { TRY(pb.reserve((size_t)BH * N * nkpad * sizeof(T), false)); P = pb.p; }
-        GemmArgs g;
-        g.a0 = qb.p; g.c0 = dpad; g.lda0 = dpad; g.a_bs = (long long)npad * dpad;
-        g.w = kb.p; g.w_bs = (long long)nkpad * dpad; g.M = N; g.N = nkpad; g.K = dpad; g.batch = BH; g.alpha = scale;
-        g.out_mode = OUT_F32; g.out = sb.p; g.ldo = nkpad; g.o_bs = (long long)N * nkpad;
-        TRY(launch_gemm<T>(g, st));
-        TRY(launch_softmax_rows<T>(static_cast<const float*>(sb.p), nkpad, P, nkpad, (long long)BH * N, Nk, st));
-        GemmArgs o;
-        o.a0 = P; o.c0 = nkpad; o.lda0 = nkpad; o.a_bs = (long long)N * nkpad;
-        o.w = vb.p; o.w_bs = (long long)dpad * nkpad; o.M = N; o.N = hd; o.K = nkpad; o.batch = BH;
-        o.heads = H; o.o_bs = (long long)N * C; o.o_hs = hd; o.out = out->data; o.ldo = C;
-        TRY(launch_gemm<T>(o, st));
+        const size_t cnt = (size_t)B * H * N * nkpad;
+        float* S = static_cast<float*>(sc.alloc(cnt * sizeof(float)));
+        void* P = sizeof(T) == 2 ? sc.alloc(cnt * sizeof(T)) : S;
+        if (!S || !P) return 7;
+        TRY(attn_materialised<T>(geo, qb.p, kb.p, vb.p, S, P, out->data, false, st, [&](GemmArgs& g) { return op_gemm_run<T>(sc, st, g); }));
     }
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
@@ -306,24 +287,23 @@ static int op_conv3x3_lora_t(const mrisr_tensor* x, const float* w, const float*
     if (sbytes) TRY(scr.reserve(sbytes, false));
     TRY(launch_conv_lora_down<T>(x->data, av.p, static_cast<float*>(zb.p), B, H, W, Cin, r, static_cast<float*>(scr.p), st));
     GemmArgs g;
-    g.a0 = x->data; g.c0 = Cin; g.lda0 = Cin;
-    g.conv = 1; g.B = B; g.Hin = H; g.Win = W; g.Hout = H; g.Wout = W;
-    g.w = wp.p; g.M = M; g.N = cout; g.K = 9 * Cin; g.bias = bias;
-    if (rowvec) { g.rowvec = rowvec; g.rowvec_ld = cout; g.rowvec_div = H * W; }
-    if (resid) { g.resid = resid->data; g.ldr = cout; }
-    g.out = y->data; g.ldo = cout;
-    g.lora_z = static_cast<const float*>(zb.p); g.lora_zld = r; g.lora_b = static_cast<const float*>(sb.p); g.lora_r = r; g.lora_secN = cout;
+    ga_rows(g, x->data, Cin, Cin); ga_conv3(g, B, H, W); ga_weight(g, wp.p, M, cout, 9 * Cin); g.bias = bias;
+    if (rowvec) ga_rowvec(g, rowvec, cout, H * W);
+    if (resid) ga_resid(g, resid->data, cout);
+    ga_out(g, y->data, cout); ga_lora_epilogue(g, static_cast<const float*>(zb.p), r, static_cast<const float*>(sb.p), r, cout);
     ForcedTile forced(tile);
-    g.splitk = splitk;
-    if (splitk <= 0) { g.splitk = 1; TRY(gemm_choose(g, sizeof(T) == 2)); }
-    else if (!tile) { const int sk = splitk; TRY(gemm_choose(g, sizeof(T) == 2)); g.splitk = sk; }
-    if (g.splitk > 1) {
-        TRY(part.reserve((size_t)g.splitk * g.M * g.N * sizeof(float), false));
-        g.partial = static_cast<float*>(part.p);
-    }
+    TRY(op_plan<T>(g, splitk, !tile, part));
     TRY(launch_gemm<T>(g, st));
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
+}
+
+// y = act(x W^T + bias) on row tensors (K = x's width, the output pitch y's)
+static GemmArgs op_linear_args(const mrisr_tensor* x, const void* w, int n, const float* bias, int act, const mrisr_tensor* y) {
+    const int K = (int)x->shape[1];
+    GemmArgs g;
+    ga_rows(g, x->data, K, K); ga_weight(g, w, (int)x->shape[0], n, K); g.bias = bias; g.act = act; ga_out(g, y->data, (int)y->shape[1]);
+    return g;
 }
 
 extern "C" {
@@ -394,16 +374,9 @@ int mrisr_op_linear(const mrisr_tensor* x, const float* w_dev, const float* bias
         TRY(launch_pack_bias_geglu(bias_dev, static_cast<float*>(bp.p), n / 2, st));
         bias = static_cast<const float*>(bp.p);
     }
-    GemmArgs g;
-    g.a0 = x->data; g.c0 = K; g.lda0 = K; g.w = wp.p; g.M = M; g.N = n; g.K = K; g.bias = bias; g.act = act;
-    g.out = y->data; g.ldo = (int)y->shape[1];
-    g.splitk = splitk;
+    GemmArgs g = op_linear_args(x, wp.p, n, bias, act, y);
     ForcedTile forced(tile);
-    if (splitk <= 0) { g.splitk = 1; TRY(gemm_choose(g, !f32)); }
-    if (g.splitk > 1) {
-        TRY(part.reserve((size_t)g.splitk * M * n * sizeof(float), false));
-        g.partial = static_cast<float*>(part.p);
-    }
+    TRY(f32 ? op_plan<float>(g, splitk, false, part) : op_plan<bf16>(g, splitk, false, part));
     TRY(f32 ? launch_gemm<float>(g, st) : launch_gemm<bf16>(g, st));
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
@@ -429,9 +402,7 @@ int mrisr_op_ln_linear(const mrisr_tensor* x, const float* gamma_dev, const floa
         TRY(launch_pack_bias_geglu(bias_dev, static_cast<float*>(bp.p), n / 2, st));
         bias = static_cast<const float*>(bp.p);
     }
-    GemmArgs g;
-    g.a0 = x->data; g.c0 = K; g.lda0 = K; g.w = wp.p; g.M = M; g.N = n; g.K = K; g.bias = bias; g.act = act;
-    g.out = y->data; g.ldo = (int)y->shape[1];
+    GemmArgs g = op_linear_args(x, wp.p, n, bias, act, y);
     MRISR_REQUIRE(gemm_rp_tile(g) != 0, "LayerNorm prologue: the row-panel kernel does not take this shape (K = 320 / 640, N % 16 == 0)");
     g.ln_gamma = gamma_dev; g.ln_beta = beta_dev; g.ln_eps = 1e-5f;
     TRY(gemm_choose(g, true));
@@ -495,9 +466,7 @@ int mrisr_op_linear_fp8(const mrisr_tensor* x, const float* gamma_dev, const flo
         TRY(launch_pack_bias_geglu(bias_dev, static_cast<float*>(bp.p), n / 2, st));
         bias = static_cast<const float*>(bp.p);
     }
-    GemmArgs g;
-    g.a0 = x->data; g.c0 = K; g.lda0 = K; g.w = wp.p; g.M = M; g.N = n; g.K = K; g.bias = bias; g.act = act;
-    g.out = y->data; g.ldo = (int)y->shape[1];
+    GemmArgs g = op_linear_args(x, wp.p, n, bias, act, y);
     g.w8 = w8.p; g.w_scale = static_cast<const float*>(ws.p);
     MRISR_REQUIRE(gemm_rp_tile(g) != 0, "fp8 operands: the row-panel kernel does not take this shape (K = 320 / 640, N % 16 == 0)");
     if (gamma_dev) { g.ln_gamma = gamma_dev; g.ln_beta = beta_dev; g.ln_eps = 1e-5f; }
@@ -615,29 +584,11 @@ extern "C" int mrisr_op_attention_bwd(const mrisr_tensor* q, const mrisr_tensor*
 // the caller's device pointers.  Every argument the kernels index or vector-load by is checked before the first launch.
 // =================================================================================================
 namespace {
-struct OpScratch {  // scratch of one call: freed when the entry returns (after its stream synchronisation)
-    std::vector<std::unique_ptr<DevBuf>> bufs;
-    void* alloc(size_t bytes, bool zero = false) {
-        bufs.emplace_back(new DevBuf());
-        if (bufs.back()->reserve(bytes ? bytes : 1, zero)) return nullptr;
-        return bufs.back()->p;
-    }
-};
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline int bwd_dtype_ok(int dtype) {
     MRISR_REQUIRE(dtype == MRISR_F32 || dtype == MRISR_BF16, "backward ops: f32 or bf16 operands");
     return 0;
 }
-template <typename T>
-int op_gemm_run(OpScratch& sc, hipStream_t st, GemmArgs& g) {  // Runner::run_gemm on scratch buffers
-    TRY(gemm_choose(g, sizeof(T) == 2));
-    if (g.splitk > 1) {
-        g.partial = static_cast<float*>(sc.alloc((size_t)g.splitk * g.batch * g.M * g.N * sizeof(float)));
-        if (!g.partial) return 7;
-    }
-    return launch_gemm<T>(g, st);
-}
-
 template <typename T>
 int op_groupnorm_bwd_t(const void* x0, int c0, const void* x1, int c1, int B, int HW, const float* gamma, const float* beta, int groups,
                        float eps, int silu, const void* dy, void* dx0, int acc0, void* dx1, int acc1, float* g_gamma, float* g_beta,
@@ -1086,23 +1037,16 @@ extern "C" int mrisr_bench_gemm(int M, int N, int K, int conv, int B, int H, int
     hipLaunchKernelGGL(fill_random_bf16_kernel, dim3(2048), dim3(256), 0, st, (bf16*)a0.p, a_rows * c0, 1u);
     if (c1) hipLaunchKernelGGL(fill_random_bf16_kernel, dim3(2048), dim3(256), 0, st, (bf16*)a1.p, a_rows * c1, 2u);
     hipLaunchKernelGGL(fill_random_bf16_kernel, dim3(2048), dim3(256), 0, st, (bf16*)wb.p, (long long)N * K, 3u);
-    g.a0 = a0.p; g.c0 = c0; g.lda0 = c0;
-    if (c1) { g.a1 = a1.p; g.c1 = c1; g.lda1 = c1; }
+    ga_rows(g, a0.p, c0, c0);
+    if (c1) ga_rows2(g, a1.p, c1, c1);
     if (conv) {
-        const int Hc = H << ups, Wc = W << ups;
-        g.conv = 1; g.B = B; g.Hin = H; g.Win = W; g.Hout = (Hc - 1) / stride + 1; g.Wout = (Wc - 1) / stride + 1;
-        g.stride = stride; g.ups = ups;
+        ga_conv3(g, B, H, W, stride, ups);
         MRISR_REQUIRE(M == B * g.Hout * g.Wout, "bench conv M");
     }
-    g.w = wb.p; g.M = M; g.N = N; g.K = K; g.bias = (const float*)bias.p; g.out = ob.p; g.ldo = N;
+    ga_weight(g, wb.p, M, N, K); g.bias = (const float*)bias.p; ga_out(g, ob.p, N);
     if (const char* e = getenv("MRISR_BENCH_NOSTORE")) { if (e[0] == '1') g.out_mode = OUT_NONE; }  // experiment: epilogue without the store
-    g.splitk = splitk;
     ForcedTile forced(tile);
-    if (splitk <= 0) { g.splitk = 1; TRY(gemm_choose(g, true)); }
-    if (g.splitk > 1) {
-        TRY(part.reserve((size_t)g.splitk * M * N * 4, false));
-        g.partial = (float*)part.p;
-    }
+    TRY(op_plan<bf16>(g, splitk, false, part));
     for (int i = 0; i < 2; ++i) TRY(launch_gemm<bf16>(g, st));
     hipEvent_t e0, e1;
     MRISR_CHECK_HIP(hipEventCreate(&e0));

@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "api.h"
+#include "gemm_args.h"
 #include "model.h"
 
 namespace mrisr {
@@ -66,15 +67,8 @@ struct Runner {
         return launch_groupnorm<T>(a, st);
     }
 
-    int run_gemm(GemmArgs& g) {
-        TRY(gemm_choose(g, sizeof(T) == 2));
-        if (g.splitk > 1) {
-            g.partial = static_cast<float*>(alloc((size_t)g.splitk * g.batch * g.M * g.N * sizeof(float)));
-            if (!g.partial) return 7;
-        }
-        if (dry) return 0;
-        return launch_gemm<T>(g, st);
-    }
+    auto arena_alloc() { return [this](size_t n) { return alloc(n); }; }
+    int run_gemm(GemmArgs& g) { return gemm_run<T>(g, st, dry, arena_alloc()); }
 
     // 3x3 conv (pad 1) over NHWC, optional second concat source, stride, nearest-x2 upsample of the input
     // lz: the down-projection z of the conv's LoRA adapter (conv_lora_z): s B z joins in the epilogue
@@ -82,23 +76,21 @@ struct Runner {
               int rowvec_div, const Act* resid, int act, Act* out, const float* lz = nullptr) {
         const int Cin = x.C + (x1 ? x1->C : 0);
         MRISR_REQUIRE(cw.cin == Cin && cw.ks == 3, "conv3x3 weight mismatch");
-        const int Hc = x.H << ups, Wc = x.W << ups;
-        const int Ho = (Hc - 1) / stride + 1, Wo = (Wc - 1) / stride + 1;
-        *out = new_act(x.B, Ho, Wo, cw.cout);
+        GemmArgs g = conv3_args(x, x1, cw, stride, ups, rowvec, rowvec_ld, rowvec_div, resid, act);
+        *out = new_act(x.B, g.Hout, g.Wout, cw.cout);
         if (!out->p) return 7;
-        GemmArgs g;
-        g.a0 = x.p; g.c0 = x.C; g.lda0 = x.C;
-        if (x1) { g.a1 = x1->p; g.c1 = x1->C; g.lda1 = x1->C; }
-        g.conv = 1; g.B = x.B; g.Hin = x.H; g.Win = x.W; g.Hout = Ho; g.Wout = Wo; g.stride = stride; g.ups = ups;
-        g.w = cw.w; g.M = x.B * Ho * Wo; g.N = cw.cout; g.K = 9 * Cin;
-        g.bias = cw.b; g.rowvec = rowvec; g.rowvec_ld = rowvec_ld; g.rowvec_div = rowvec_div; g.act = act;
-        if (resid) { g.resid = resid->p; g.ldr = resid->C; }
-        g.out = out->p; g.ldo = cw.cout;
-        if (lz) lora_epilogue(g, cw, lz);
+        g.out = out->p;
+        if (lz) ga_lora_epilogue(g, cw, lz);
         return run_gemm(g);
     }
-    static void lora_epilogue(GemmArgs& g, const ConvW& cw, const float* z) {
-        g.lora_z = z; g.lora_zld = cw.r; g.lora_b = cw.loraB; g.lora_r = cw.r; g.lora_secN = cw.cout;
+    // the launch of conv3 / conv3_gn but for its output pointer
+    static GemmArgs conv3_args(const Act& x, const Act* x1, const ConvW& cw, int stride, int ups, const float* rowvec, int rowvec_ld,
+                               int rowvec_div, const Act* resid, int act) {
+        GemmArgs g;
+        ga_rows(g, x); ga_rows2(g, x1); ga_conv3(g, x, stride, ups);
+        ga_weight(g, cw.w, x.B * g.Hout * g.Wout, cw.cout, 9 * (x.C + (x1 ? x1->C : 0))); g.bias = cw.b; g.act = act;
+        ga_rowvec(g, rowvec, rowvec_ld, rowvec_div); ga_resid(g, resid); g.ldo = cw.cout;
+        return g;
     }
     // z [M][r] f32 = conv3x3(x, lora_A) of an adapted conv (lora_conv.hip): stays allocated for the conv's epilogue (training: the backward)
     int conv_lora_z(const Act& x, const ConvW& cw, float** z) {
@@ -119,17 +111,10 @@ struct Runner {
                  const NormW& nw, bool silu, float eps, Act* raw, Act* out) {
         const int Cin = x.C + (x1 ? x1->C : 0);
         MRISR_REQUIRE(cw.cin == Cin && cw.ks == 3 && nw.c == cw.cout, "conv3x3 + GroupNorm weight mismatch");
-        GemmArgs g;
-        g.a0 = x.p; g.c0 = x.C; g.lda0 = x.C;
-        if (x1) { g.a1 = x1->p; g.c1 = x1->C; g.lda1 = x1->C; }
-        g.conv = 1; g.B = x.B; g.Hin = x.H; g.Win = x.W; g.Hout = x.H; g.Wout = x.W; g.stride = 1; g.ups = 0;
-        g.w = cw.w; g.M = x.B * x.H * x.W; g.N = cw.cout; g.K = 9 * Cin;
-        g.bias = cw.b; g.rowvec = rowvec; g.rowvec_ld = rowvec_ld; g.rowvec_div = rowvec_div; g.act = ACT_NONE;
-        if (resid) { g.resid = resid->p; g.ldr = resid->C; }
-        g.ldo = cw.cout;
+        GemmArgs g = conv3_args(x, x1, cw, 1, 0, rowvec, rowvec_ld, rowvec_div, resid, ACT_NONE);
         bool fuse = sizeof(T) == 2 && !m.keep && groupnorm_slabs_ok(cw.cout, m.cfg.norm_num_groups, x.H * x.W);
         if (fuse) {
-            g.out = reinterpret_cast<void*>(0x1000);  // (never written: the slabs are the output) - the planner only looks at the signature
+            g.out = kUnallocated;  // (never written: the slabs are the output)
             TRY(gemm_choose(g, true));
             fuse = g.splitk > 1;
         }
@@ -149,8 +134,8 @@ struct Runner {
         a.gamma = nw.g; a.beta = nw.b; a.silu = silu ? 1 : 0; a.y = out->p;
         a.nsplit = groupnorm_nsplit(a.B, a.HW);
         a.partial = static_cast<float*>(alloc((size_t)a.B * a.nsplit * a.groups * 2 * sizeof(float)));
-        g.partial = static_cast<float*>(alloc((size_t)g.splitk * g.M * g.N * sizeof(float)));
-        if (!a.partial || !g.partial) return 7;
+        TRY(gemm_alloc_partial(g, arena_alloc()));
+        if (!a.partial) return 7;
         if (dry) return 0;
         g.defer_reduce = 1;
         TRY(launch_gemm<T>(g, st));
@@ -182,11 +167,8 @@ struct Runner {
         T* planes = static_cast<T*>(alloc((size_t)4 * plane * sizeof(T)));
         if (!planes) return 7;
         GemmArgs g;
-        g.a0 = x.p; g.c0 = x.C; g.lda0 = x.C;
-        g.conv = 1; g.B = x.B; g.Hin = x.H; g.Win = x.W; g.Hout = x.H; g.Wout = x.W; g.stride = 1; g.ups = 0;
-        g.kw = 2; g.subpix = 1; g.batch = 4; g.a_bs = 0; g.w_bs = (long long)cw.cout * 4 * cw.cin; g.o_bs = plane;
-        g.w = lv.up_sp; g.M = (int)x.rows(); g.N = cw.cout; g.K = 4 * x.C; g.bias = cw.b;
-        g.out = planes; g.ldo = cw.cout;
+        ga_rows(g, x); ga_conv3(g, x); g.kw = 2; g.subpix = 1; ga_batch(g, 4, 0, (long long)cw.cout * 4 * cw.cin, plane);
+        ga_weight(g, lv.up_sp, (int)x.rows(), cw.cout, 4 * x.C); g.bias = cw.b; ga_out(g, planes, cw.cout);
         g.alg_flops = 2.0 * 4.0 * g.M * (double)g.N * g.K;
         TRY(run_gemm(g));
         if (!dry) TRY(launch_subpix_shuffle<T>(planes, out->p, x.B, x.H, x.W, cw.cout, st));
@@ -202,11 +184,9 @@ struct Runner {
                void* out, int ldo, float** z_out = nullptr, const NormW* ln = nullptr, void* ln_scratch = nullptr) {
         GemmArgs g = custom ? *custom : GemmArgs();
         const size_t mk = m.arena.mark();
-        g.a0 = x; g.c0 = lw.k; g.lda0 = lda;
-        g.w = lw.w; g.M = M; g.N = lw.n; g.K = lw.k;
-        g.alg_flops = 2.0 * M * (double)lw.n * (lw.k + lw.r);
-        g.bias = lw.b; g.act = act; g.resid = resid; g.ldr = ldr;
-        if (g.out_mode != OUT_HEADS) { g.out = out; g.ldo = ldo; }
+        ga_rows(g, x, lw.k, lda); ga_weight(g, lw.w, M, lw.n, lw.k); g.alg_flops = 2.0 * M * (double)lw.n * (lw.k + lw.r);
+        g.bias = lw.b; g.act = act; ga_resid(g, resid, ldr);
+        if (g.out_mode != OUT_HEADS) ga_out(g, out, ldo);
         // the row-panel kernel fuses LoRA only in the in-kernel rank-4 form
         if (lw.R && !(lw.r == 4 && lw.R <= 16 && lora_in_kernel())) g.no_rp = 1;
         // fp8 operands (cfg.fp8_linears; the training forward only with cfg.fp8_train): when the row-panel fp8 kernel takes this launch
@@ -241,13 +221,10 @@ struct Runner {
             if (!z) return 7;
             if (z_out) *z_out = reinterpret_cast<float*>(z);
             GemmArgs zg;
-            zg.a0 = x; zg.c0 = lw.k; zg.lda0 = lda;
-            zg.w = lw.loraA; zg.M = M; zg.N = lw.R; zg.K = lw.k;
-            zg.out = z; zg.ldo = lw.R; zg.no_rp = 1;
+            ga_rows(zg, x, lw.k, lda); ga_weight(zg, lw.loraA, M, lw.R, lw.k); ga_out(zg, z, lw.R); zg.no_rp = 1;
             zg.alg_flops = 2.0 * M * (double)lw.R * lw.k;
             TRY(run_gemm(zg));
-            g.a1 = z; g.c1 = lw.R; g.lda1 = lw.R; g.K = lw.k + lw.R; g.no_rp = 1;
-            g.alg_flops = 2.0 * M * (double)lw.n * g.K;
+            ga_rows2(g, z, lw.R, lw.R); g.K = lw.k + lw.R; g.no_rp = 1; g.alg_flops = 2.0 * M * (double)lw.n * g.K;
             TRY(run_gemm(g));
             if (!m.keep) m.arena.release(mk);
             return 0;
@@ -255,7 +232,7 @@ struct Runner {
         // LoRA: the rank-r up-projection (alpha/r) B z is accumulated in the projection GEMM's epilogue.  z = x A^T is
         // computed inside the same kernel (bf16 buffer-addressed tiles, un-split); otherwise by one bandwidth-bound
         // pass over x (launch_lora_down) that hands z over through HBM.
-        g.lora_zld = lw.R; g.lora_b = lw.loraB; g.lora_r = lw.r; g.lora_secN = lw.secN;
+        ga_lora_epilogue(g, nullptr, lw.R, lw.loraB, lw.r, lw.secN);  // (z: below, once the plan says which form)
         TRY(gemm_choose(g, sizeof(T) == 2));
         float* z = static_cast<float*>(alloc((size_t)M * lw.R * sizeof(float)));
         if (!z) return 7;
@@ -268,11 +245,7 @@ struct Runner {
             if (!dry) TRY(launch_lora_down<T>(x, lda, lw.loraA, z, M, lw.k, lw.R, st));
             g.lora_z = z;
         }
-        if (g.splitk > 1) {
-            g.partial = static_cast<float*>(alloc((size_t)g.splitk * g.batch * g.M * g.N * sizeof(float)));
-            if (!g.partial) return 7;
-        }
-        if (!dry) TRY(launch_gemm<T>(g, st));
+        TRY(gemm_finish<T>(g, st, dry, arena_alloc()));
         if (!m.keep) m.arena.release(mk);
         return 0;
     }
@@ -300,22 +273,15 @@ struct Runner {
         TRY(gn(t->h, nullptr, r.n2, true, m.cfg.norm_eps, &t->hn, &t->p2, &t->ns2));
         Act res = x;
         if (r.has_sc) {
-            GemmArgs g;
-            if (x1) { g.a1 = x1->p; g.c1 = x1->C; g.lda1 = x1->C; }
-            g.a0 = x.p; g.c0 = x.C; g.lda0 = x.C;
-            g.w = r.sc.w; g.M = (int)x.rows(); g.N = r.cout; g.K = r.cin; g.bias = r.sc.b; g.out = o.p; g.ldo = r.cout;
+            GemmArgs g = resnet_shortcut_args(x, x1, r.sc.w, r.sc.b, r.cin, r.cout, o.p);
             TRY(run_gemm(g));
             res = o;
         } else {
             MRISR_REQUIRE(!x1, "concat input requires a shortcut conv");
         }
         if (r.c2.r) TRY(conv_lora_z(t->hn, r.c2, &t->z2));
-        GemmArgs g;
-        g.a0 = t->hn.p; g.c0 = t->hn.C; g.lda0 = t->hn.C;
-        g.conv = 1; g.B = x.B; g.Hin = x.H; g.Win = x.W; g.Hout = x.H; g.Wout = x.W;
-        g.w = r.c2.w; g.M = (int)x.rows(); g.N = r.cout; g.K = 9 * r.cout; g.bias = r.c2.b;
-        g.resid = res.p; g.ldr = r.cout; g.out = o.p; g.ldo = r.cout;
-        if (t->z2) lora_epilogue(g, r.c2, t->z2);
+        GemmArgs g = resnet_conv2_args(t->hn.p, x.B, x.H, x.W, r.cout, r.c2.w, r.c2.b, res.p, o.p);
+        if (t->z2) ga_lora_epilogue(g, r.c2, t->z2);
         return run_gemm(g);
     }
 
@@ -339,21 +305,11 @@ struct Runner {
         GroupNormArgs a2;
         // the 1x1 shortcut as the tail of conv2's K loop (bf16 inference): conv2(h) + b2 + (W_sc x + b_sc) is one GEMM over K = [9 cout | cin]
         // on the bank built at finalize, bias b2 + b_sc, no residual - the shortcut's output is never written or read back
-        GemmArgs gt;
-        gt.c0 = r.cout; gt.lda0 = r.cout; gt.a0 = reinterpret_cast<void*>(0x1000);
-        gt.conv = 1; gt.B = x.B; gt.Hin = x.H; gt.Win = x.W; gt.Hout = x.H; gt.Wout = x.W;
-        gt.s0 = x.p; gt.cs0 = x.C; gt.lds0 = x.C;
-        if (x1) { gt.s1 = x1->p; gt.cs1 = x1->C; gt.lds1 = x1->C; }
-        gt.w = r.c2sc; gt.M = (int)x.rows(); gt.N = r.cout; gt.K = 9 * r.cout + r.cin; gt.bias = r.b2sc;
-        gt.out = o.p; gt.ldo = r.cout;
+        GemmArgs gt = resnet_conv2_args(kUnallocated, x.B, x.H, x.W, r.cout, r.c2sc, r.b2sc, nullptr, o.p, r.cin, &x, x1);
         const bool sc_tail = sizeof(T) == 2 && !m.keep && r.has_sc && r.c2sc && sc_fused_enabled() && x.C + (x1 ? x1->C : 0) == r.cin && gemm_sc_tail_ok(gt);
         if (next && next_out && sizeof(T) == 2 && !m.keep && next->c == r.cout && groupnorm_slabs_ok(r.cout, m.cfg.norm_num_groups, x.H * x.W)) {
-            g2.c0 = r.cout; g2.lda0 = r.cout;
-            g2.conv = 1; g2.B = x.B; g2.Hin = x.H; g2.Win = x.W; g2.Hout = x.H; g2.Wout = x.W;
-            g2.w = r.c2.w; g2.M = (int)x.rows(); g2.N = r.cout; g2.K = 9 * r.cout; g2.bias = r.c2.b;
-            g2.a0 = reinterpret_cast<void*>(0x1000); g2.resid = reinterpret_cast<void*>(0x1000); g2.ldr = r.cout;
-            g2.out = reinterpret_cast<void*>(0x1000); g2.ldo = r.cout;
-            if (sc_tail) g2 = gt;  // (the planner sees the fused K and the launch without a residual)
+            g2 = sc_tail ? gt  // (the planner sees the fused K and the launch without a residual)
+                         : resnet_conv2_args(kUnallocated, x.B, x.H, x.W, r.cout, r.c2.w, r.c2.b, kUnallocated, kUnallocated);
             TRY(gemm_choose(g2, true));
             fuse2 = g2.splitk > 1;
             if (fuse2) {
@@ -373,10 +329,7 @@ struct Runner {
             res.p = nullptr;  // (no residual: the shortcut rides in conv2's K loop)
         } else if (r.has_sc) {
             // 1x1 shortcut on the (concatenated) raw input, written straight into the output buffer
-            GemmArgs g;
-            if (x1) { g.a1 = x1->p; g.c1 = x1->C; g.lda1 = x1->C; }
-            g.a0 = x.p; g.c0 = x.C; g.lda0 = x.C;
-            g.w = r.sc.w; g.M = (int)x.rows(); g.N = r.cout; g.K = r.cin; g.bias = r.sc.b; g.out = o.p; g.ldo = r.cout;
+            GemmArgs g = resnet_shortcut_args(x, x1, r.sc.w, r.sc.b, r.cin, r.cout, o.p);
             MRISR_REQUIRE(r.sc.R == 0, "shortcut has no LoRA");
             TRY(run_gemm(g));
             res = o;
@@ -386,8 +339,7 @@ struct Runner {
         // conv2 + bias + residual -> o (in place when res == o: each element is read then written by one lane)
         if (fuse2) {
             g2.a0 = hn.p; g2.resid = res.p; g2.out = o.p;
-            g2.partial = static_cast<float*>(alloc((size_t)g2.splitk * g2.M * g2.N * sizeof(float)));
-            if (!g2.partial) return 7;
+            TRY(gemm_alloc_partial(g2, arena_alloc()));
             if (!dry) {
                 g2.defer_reduce = 1;
                 TRY(launch_gemm<T>(g2, st));
@@ -401,11 +353,7 @@ struct Runner {
             gt.a0 = hn.p;
             TRY(run_gemm(gt));
         } else {
-            GemmArgs g;
-            g.a0 = hn.p; g.c0 = hn.C; g.lda0 = hn.C;
-            g.conv = 1; g.B = x.B; g.Hin = x.H; g.Win = x.W; g.Hout = x.H; g.Wout = x.W;
-            g.w = r.c2.w; g.M = (int)x.rows(); g.N = r.cout; g.K = 9 * r.cout; g.bias = r.c2.b;
-            g.resid = res.p; g.ldr = r.cout; g.out = o.p; g.ldo = r.cout;
+            GemmArgs g = resnet_conv2_args(hn.p, x.B, x.H, x.W, r.cout, r.c2.w, r.c2.b, res.p, o.p);
             TRY(run_gemm(g));
         }
         if (!m.keep) m.arena.release(mk);
@@ -414,49 +362,32 @@ struct Runner {
     }
 
     // ---- attention core on head-major operands ----
+    static AttnGeom attn_geom(const HeadBuf& hb, int nk, int nkpad) {
+        AttnGeom s;
+        s.B = hb.B; s.H = hb.H; s.N = hb.N; s.npad = hb.npad; s.hd = hb.hd; s.dpad = hb.dpad; s.nk = nk; s.nkpad = nkpad;
+        return s;
+    }
     int attention(const HeadBuf& hb, const void* k, const void* vt, int nk, int nkpad, void* out_rows) {
-        const int BH = hb.B * hb.H;
-        const float scale = 1.0f / sqrtf((float)hb.hd);
-        if (m.cfg.flash_attention && sizeof(T) == 2) {
-            AttnArgs a;
-            a.q = hb.q; a.k = k; a.vt = vt; a.out = out_rows;
-            a.B = hb.B; a.H = hb.H; a.nq = hb.N; a.nk = nk; a.nkpad = nkpad; a.hd = hb.hd; a.dpad = hb.dpad;
-            a.scale = scale;
-            if (m.cfg.fp8_attention) {  // BASELINE configs[4]: e4m3 Q K^T and P V; scratch for the quantised K / V^T + per-head scales
-                const size_t mk8 = m.arena.mark();
-                a.k8 = alloc((size_t)BH * nkpad * hb.dpad);
-                a.vt8 = alloc((size_t)BH * nkpad * hb.dpad);
-                a.f8_scales = static_cast<float*>(alloc((size_t)BH * 4 * sizeof(float)));
-                if (!a.k8 || !a.vt8 || !a.f8_scales) return 7;
-                const int rc = dry ? 0 : launch_attention_fp8(a, st);
-                if (!m.keep) m.arena.release(mk8);
-                return rc;
-            }
-            if (dry) return 0;
-            return launch_attention_bf16(a, st);
-        }
+        const AttnGeom s = attn_geom(hb, nk, nkpad);
         const size_t mk = m.arena.mark();
-        float* S = static_cast<float*>(alloc((size_t)BH * hb.N * nkpad * sizeof(float)));
+        if (m.cfg.flash_attention && sizeof(T) == 2) {
+            const bool fp8 = m.cfg.fp8_attention;  // BASELINE configs[4]: e4m3 Q K^T and P V; scratch for the quantised K / V^T + per-head scales
+            AttnArgs a;
+            TRY(attn_flash_args(a, s, hb.q, k, vt, out_rows, nullptr, fp8, arena_alloc()));
+            const int rc = attn_flash_launch(a, fp8, dry, st);
+            if (!m.keep) m.arena.release(mk);
+            return rc;
+        }
+        // (inference keeps neither S nor P)
+        const size_t cnt = (size_t)s.B * s.H * s.N * nkpad;
+        float* S = static_cast<float*>(alloc(cnt * sizeof(float)));
         if (!S) return 7;
         void* P = S;
         if (sizeof(T) == 2) {
-            P = alloc((size_t)BH * hb.N * nkpad * sizeof(T));
+            P = alloc(cnt * sizeof(T));
             if (!P) return 7;
         }
-        GemmArgs g;
-        g.a0 = hb.q; g.c0 = hb.dpad; g.lda0 = hb.dpad; g.a_bs = (long long)hb.npad * hb.dpad;
-        g.w = k; g.w_bs = (long long)nkpad * hb.dpad;
-        g.M = hb.N; g.N = nkpad; g.K = hb.dpad; g.batch = BH; g.alpha = scale;
-        g.out_mode = OUT_F32; g.out = S; g.ldo = nkpad; g.o_bs = (long long)hb.N * nkpad;
-        TRY(run_gemm(g));
-        if (!dry) TRY(launch_softmax_rows<T>(S, nkpad, P, nkpad, (long long)BH * hb.N, nk, st));
-        GemmArgs o;
-        o.a0 = P; o.c0 = nkpad; o.lda0 = nkpad; o.a_bs = (long long)hb.N * nkpad;
-        o.w = vt; o.w_bs = (long long)hb.dpad * nkpad;
-        o.M = hb.N; o.N = hb.hd; o.K = nkpad; o.batch = BH;
-        o.heads = hb.H; o.o_bs = (long long)hb.N * hb.H * hb.hd; o.o_hs = hb.hd;
-        o.out = out_rows; o.ldo = hb.H * hb.hd;
-        TRY(run_gemm(o));
+        TRY(attn_materialised<T>(s, hb.q, k, vt, S, P, out_rows, dry, st, [this](GemmArgs& g) { return run_gemm(g); }));
         if (!m.keep) m.arena.release(mk);
         return 0;
     }
@@ -565,10 +496,8 @@ struct Runner {
                 // ff.net.2 and proj_out as one GEMM over K = [4C | C] on the bank built at finalize:
                 // o = ff (Wp W2)^T + t Wp^T + (Wp b2 + bp) + x - the block's output t' = ff2(ff) + t is never written or read back
                 GemmArgs g;
-                g.a0 = ff; g.c0 = 4 * C; g.lda0 = 4 * C;
-                g.a1 = t; g.c1 = C; g.lda1 = C;
-                g.w = xw.ffpo; g.M = M; g.N = C; g.K = 5 * C; g.bias = xw.bffpo;
-                g.resid = x.p; g.ldr = C; g.out = o.p; g.ldo = C;
+                ga_rows(g, ff, 4 * C, 4 * C); ga_rows2(g, t, C, C); ga_weight(g, xw.ffpo, M, C, 5 * C); g.bias = xw.bffpo;
+                ga_resid(g, x.p, C); ga_out(g, o.p, C);
                 g.no_rp = 1;  // (two sources: not a row-panel launch)
                 g.alg_flops = 2.0 * M * (double)C * (5 * C);
                 TRY(run_gemm(g));

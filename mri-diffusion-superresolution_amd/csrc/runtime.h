@@ -1,5 +1,6 @@
 // Host-side runtime pieces shared by model.hip / capi.hip / adapter.hip: device buffers, the bump arena, packed weights.
 #pragma once
+#include <cstdint>
 #include <map>
 #include <memory>
 #include <string>
@@ -32,6 +33,12 @@ struct DevBuf {
     }
 };
 
+// "No buffer yet": a non-null address that is never dereferenced.  The dry pass of the arena hands out offsets from it, and a GEMM that is
+// planned before its buffers are allocated carries kUnallocated in their place: gemm_choose decides from the signature of a launch, and
+// WHICH operands exist (a residual, an output) is part of that signature.
+constexpr uintptr_t kUnallocatedAddr = 0x1000;
+static void* const kUnallocated = reinterpret_cast<void*>(kUnallocatedAddr);
+
 // Bump allocator with stack discipline.  In `dry` mode it only tracks the peak, so one dry pass of the
 // forward sizes the workspace exactly and every later pass reproduces the same addresses (hipGraph-safe).
 struct Arena {
@@ -43,7 +50,7 @@ struct Arena {
         const size_t a = (off + 255) & ~(size_t)255;
         off = a + bytes;
         if (off > peak) peak = off;
-        if (dry) return reinterpret_cast<void*>(0x1000 + a);  // non-null placeholder, never dereferenced
+        if (dry) return reinterpret_cast<void*>(kUnallocatedAddr + a);
         if (off > buf.bytes) return nullptr;
         return static_cast<char*>(buf.p) + a;
     }

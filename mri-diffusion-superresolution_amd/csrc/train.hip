@@ -476,14 +476,29 @@ struct Trainer : Runner<T> {
         float* dz = nullptr;
         float* tmpB = nullptr;
         if (lw.dora_g && lw.R) TRY(dora_mag_bwd(lw, dY, ldy, M, yout, ldyo, yres, ldres));
-        GemmArgs g;
         bool in_kernel = false, dx_done = false;
         TRY(wgrad_linear(lw, x, ldx, dY, ldy, M));  // (full-parameter training only)
+        const int nmod = (int)lw.mod_names.size();
+        // where dA / dB of each adapted module go (DoRA: dB into tmpB first); valid once tmpB is decided
+        float *oA[3] = {nullptr, nullptr, nullptr}, *oB[3] = {nullptr, nullptr, nullptr};
+        auto grad_table = [&] {
+            for (int j = 0; j < nmod; ++j) {
+                if (!lw.mod_lora[j]) continue;
+                oA[j] = m.grad + lw.offA[j];
+                oB[j] = tmpB ? tmpB + (size_t)j * lw.secN * lw.r : m.grad + lw.offB[j];
+            }
+        };
+        // dX (+)= dY W: the dgrad on wT (rank 32 .. 128: its second source and K are added below)
+        GemmArgs g;
+        if (need_dx) {
+            ga_rows(g, dY, lw.n, ldy); ga_weight(g, lw.wT, M, lw.k, lw.n);
+            if (acc) ga_resid(g, dX, lw.k);
+            ga_out(g, dX, lw.k);
+        }
         if (lw.rp) {
             // rank 32 .. 128: dz = dY (sB) is one GEMM on [R][n], dX (+)= [dY | dz] [W | A] one GEMM over K = n + R on wT, and
             // dB = dY^T z, dA = dz^T x go through lora_wgrad_hr; z and dz are T-typed
             MRISR_REQUIRE(z && lw.loraBT && m.grad && (!need_dx || lw.wT), "adapter backward state");
-            const int nmod = (int)lw.mod_names.size();
             T* dzt = static_cast<T*>(alloc((size_t)M * lw.R * sizeof(T)));
             const size_t sb = std::max(lora_wgrad_hr_scratch_bytes(M, lw.n, 0, lw.r, nmod, lw.secN, sizeof(T)),
                                        lora_wgrad_hr_scratch_bytes(M, lw.k, 1, lw.r, nmod, lw.secN, sizeof(T)));
@@ -491,35 +506,20 @@ struct Trainer : Runner<T> {
             if (!dzt || !scratch) return 7;
             if (lw.dora_g) TRY(dora_b_begin(lw, &tmpB));
             GemmArgs zg;
-            zg.a0 = dY; zg.c0 = lw.n; zg.lda0 = ldy;
-            zg.w = lw.loraBT; zg.M = M; zg.N = lw.R; zg.K = lw.n;
-            zg.out = dzt; zg.ldo = lw.R; zg.no_rp = 1;
+            ga_rows(zg, dY, lw.n, ldy); ga_weight(zg, lw.loraBT, M, lw.R, lw.n); ga_out(zg, dzt, lw.R); zg.no_rp = 1;
             TRY(R::run_gemm(zg));
             if (!dry) {
-                float *oA[3] = {nullptr, nullptr, nullptr}, *oB[3] = {nullptr, nullptr, nullptr};
-                for (int j = 0; j < nmod; ++j) {
-                    if (!lw.mod_lora[j]) continue;
-                    oA[j] = m.grad + lw.offA[j];
-                    oB[j] = tmpB ? tmpB + (size_t)j * lw.secN * lw.r : m.grad + lw.offB[j];
-                }
+                grad_table();
                 TRY(launch_lora_wgrad_hr<T>(dY, ldy, z, lw.R, M, lw.n, 0, lw.r, nmod, lw.secN, oB, m.lora_scale, scratch, st, lw.geglu_half));
                 TRY(launch_lora_wgrad_hr<T>(x, ldx, dzt, lw.R, M, lw.k, 1, lw.r, nmod, lw.secN, oA, 1.0f, scratch, st));
                 if (tmpB) TRY(dora_b_end(lw, tmpB));
             }
             if (!need_dx) return 0;
-            g.a0 = dY; g.c0 = lw.n; g.lda0 = ldy;
-            g.a1 = dzt; g.c1 = lw.R; g.lda1 = lw.R;
-            g.w = lw.wT; g.M = M; g.N = lw.k; g.K = lw.n + lw.R; g.no_rp = 1;
-            if (acc) { g.resid = dX; g.ldr = lw.k; }
-            g.out = dX; g.ldo = lw.k;
+            ga_rows2(g, dzt, lw.R, lw.R); g.K = lw.n + lw.R; g.no_rp = 1;
             return R::run_gemm(g);
         }
         if (need_dx) {
             MRISR_REQUIRE(lw.wT, "linear dgrad weights");
-            g.a0 = dY; g.c0 = lw.n; g.lda0 = ldy;
-            g.w = lw.wT; g.M = M; g.N = lw.k; g.K = lw.n;
-            if (acc) { g.resid = dX; g.ldr = lw.k; }
-            g.out = dX; g.ldo = lw.k;
             // the row-panel kernel fuses LoRA only at rank 4, as in the forward: a K = 320 / 640 dgrad with R = 8 .. 16 was planned onto
             // it and then refused at launch
             if (lw.R && lw.r != 4) g.no_rp = 1;
@@ -535,20 +535,13 @@ struct Trainer : Runner<T> {
             if (!dz || !scratch) return 7;
             if (lw.dora_g) TRY(dora_b_begin(lw, &tmpB));
             if (in_kernel) {  // the dgrad first: it produces dz for the A gradient
-                g.lora_a = lw.loraBT; g.lora_R = lw.R; g.lora_zout = dz;
-                g.lora_zld = lw.R; g.lora_b = lw.loraAT; g.lora_r = lw.R; g.lora_secN = INT_MAX;
+                g.lora_a = lw.loraBT; g.lora_R = lw.R; g.lora_zout = dz; ga_lora_epilogue(g, nullptr, lw.R, lw.loraAT, lw.R, INT_MAX);
                 if (!dry) TRY(launch_gemm<T>(g, st));
                 dx_done = true;
             }
             if (!dry) {
                 if (!in_kernel) TRY(launch_lora_down<T>(dY, ldy, lw.loraBT, dz, M, lw.n, lw.R, st));
-                const int nmod = (int)lw.mod_names.size();
-                float *oA[3] = {nullptr, nullptr, nullptr}, *oB[3] = {nullptr, nullptr, nullptr};
-                for (int j = 0; j < nmod; ++j) {
-                    if (!lw.mod_lora[j]) continue;
-                    oA[j] = m.grad + lw.offA[j];
-                    oB[j] = tmpB ? tmpB + (size_t)j * lw.secN * lw.r : m.grad + lw.offB[j];
-                }
+                grad_table();
                 // (ff.net.0.proj: dY columns in the GEGLU interleave, gradient rows in raw order - un-interleaved by the reduce's scatter)
                 TRY(launch_lora_wgrad<T>(dY, ldy, z, lw.R, M, lw.n, 0, lw.r, nmod, lw.secN, oB, m.lora_scale, scratch, st, lw.geglu_half));
                 TRY(launch_lora_wgrad<T>(x, ldx, dz, lw.R, M, lw.k, 1, lw.r, nmod, lw.secN, oA, 1.0f, scratch, st));
@@ -556,13 +549,8 @@ struct Trainer : Runner<T> {
             }
         }
         if (!need_dx || dx_done) return 0;
-        if (dz) { g.lora_z = dz; g.lora_zld = lw.R; g.lora_b = lw.loraAT; g.lora_r = lw.R; g.lora_secN = INT_MAX; }
-        if (g.splitk > 1) {
-            g.partial = static_cast<float*>(alloc((size_t)g.splitk * g.batch * g.M * g.N * sizeof(float)));
-            if (!g.partial) return 7;
-        }
-        if (dry) return 0;
-        return launch_gemm<T>(g, st);
+        if (dz) ga_lora_epilogue(g, dz, lw.R, lw.loraAT, lw.R, INT_MAX);
+        return gemm_finish<T>(g, st, dry, R::arena_alloc());
     }
 
     struct AttnRec {
@@ -576,31 +564,20 @@ struct Trainer : Runner<T> {
     };
     bool flash() const { return sizeof(T) == 2 && m.cfg.flash_attention; }
 
-    // materialised attention that keeps P for the backward
+    // the shared attention core (gemm_args.h), keeping what the backward needs: the log-sum-exp (flash) or P (materialised; S is released)
     int attention_t(const HeadBuf& hb, AttnRec* a, void* out_rows) {
-        const int BH = hb.B * hb.H;
-        const float scale = 1.0f / sqrtf((float)hb.hd);
+        const AttnGeom s = R::attn_geom(hb, a->nk, a->nkpad);
         a->out = out_rows;
         if (flash()) {
-            float* lse = static_cast<float*>(alloc((size_t)BH * hb.npad * sizeof(float)));
+            float* lse = static_cast<float*>(alloc((size_t)s.B * s.H * hb.npad * sizeof(float)));
             if (!lse) return 7;
             a->lse = lse;
+            const bool fp8 = m.cfg.fp8_attention && m.cfg.fp8_train;  // fp8 forward, bf16 backward from the same log-sum-exp (straight through)
             AttnArgs fa;
-            fa.q = a->q; fa.k = a->k; fa.vt = a->vt; fa.out = out_rows;
-            fa.B = hb.B; fa.H = hb.H; fa.nq = hb.N; fa.nk = a->nk; fa.nkpad = a->nkpad; fa.hd = hb.hd; fa.dpad = hb.dpad;
-            fa.scale = scale; fa.lse = lse;
-            if (m.cfg.fp8_attention && m.cfg.fp8_train) {  // fp8 forward, bf16 backward from the same log-sum-exp (straight through)
-                fa.k8 = alloc((size_t)BH * a->nkpad * hb.dpad);
-                fa.vt8 = alloc((size_t)BH * a->nkpad * hb.dpad);
-                fa.f8_scales = static_cast<float*>(alloc((size_t)BH * 4 * sizeof(float)));
-                if (!fa.k8 || !fa.vt8 || !fa.f8_scales) return 7;
-                if (dry) return 0;
-                return launch_attention_fp8(fa, st);
-            }
-            if (dry) return 0;
-            return launch_attention_bf16(fa, st);
+            TRY(attn_flash_args(fa, s, a->q, a->k, a->vt, out_rows, lse, fp8, R::arena_alloc()));
+            return attn_flash_launch(fa, fp8, dry, st);
         }
-        const size_t cnt = (size_t)BH * hb.N * a->nkpad;
+        const size_t cnt = (size_t)s.B * s.H * hb.N * a->nkpad;
         float* S;
         void* P;
         size_t mk = 0;
@@ -613,20 +590,7 @@ struct Trainer : Runner<T> {
             S = static_cast<float*>(alloc(cnt * sizeof(float)));
         }
         if (!S || !P) return 7;
-        GemmArgs g;
-        g.a0 = a->q; g.c0 = hb.dpad; g.lda0 = hb.dpad; g.a_bs = (long long)hb.npad * hb.dpad;
-        g.w = a->k; g.w_bs = (long long)a->nkpad * hb.dpad;
-        g.M = hb.N; g.N = a->nkpad; g.K = hb.dpad; g.batch = BH; g.alpha = scale;
-        g.out_mode = OUT_F32; g.out = S; g.ldo = a->nkpad; g.o_bs = (long long)hb.N * a->nkpad;
-        TRY(R::run_gemm(g));
-        if (!dry) TRY(launch_softmax_rows<T>(S, a->nkpad, P, a->nkpad, (long long)BH * hb.N, a->nk, st));
-        GemmArgs o;
-        o.a0 = P; o.c0 = a->nkpad; o.lda0 = a->nkpad; o.a_bs = (long long)hb.N * a->nkpad;
-        o.w = a->vt; o.w_bs = (long long)hb.dpad * a->nkpad;
-        o.M = hb.N; o.N = hb.hd; o.K = a->nkpad; o.batch = BH;
-        o.heads = hb.H; o.o_bs = (long long)hb.N * hb.H * hb.hd; o.o_hs = hb.hd;
-        o.out = out_rows; o.ldo = hb.H * hb.hd;
-        TRY(R::run_gemm(o));
+        TRY(attn_materialised<T>(s, a->q, a->k, a->vt, S, P, out_rows, dry, st, [this](GemmArgs& g) { return R::run_gemm(g); }));
         if (sizeof(T) == 2) m.arena.release(mk);
         a->P = P;
         return 0;
@@ -677,19 +641,15 @@ struct Trainer : Runner<T> {
         }
         {   // dP = dOh V^T
             GemmArgs g;
-            g.a0 = dOh; g.c0 = dpad; g.lda0 = dpad; g.a_bs = (long long)npad * dpad;
-            g.w = V; g.w_bs = (long long)nkpad * dpad;
-            g.M = N; g.N = nkpad; g.K = dpad; g.batch = BH;
-            g.out_mode = OUT_F32; g.out = dP; g.ldo = nkpad; g.o_bs = (long long)N * nkpad;
+            ga_rows(g, dOh, dpad, dpad); ga_weight(g, V, N, nkpad, dpad);
+            ga_batch(g, BH, (long long)npad * dpad, (long long)nkpad * dpad, (long long)N * nkpad); ga_out_f32(g, dP, nkpad);
             TRY(R::run_gemm(g));
         }
         if (!dry) TRY(launch_softmax_bwd<T>(a.P, dP, dS, nkpad, (long long)BH * N, nk, scale, st));
         {   // dQ = dS K  (W operand = K^T)
             GemmArgs g;
-            g.a0 = dS; g.c0 = nkpad; g.lda0 = nkpad; g.a_bs = (long long)N * nkpad;
-            g.w = Kt; g.w_bs = (long long)dpad * nkpad;
-            g.M = N; g.N = hb.hd; g.K = nkpad; g.batch = BH;
-            g.heads = hb.H; g.o_bs = (long long)N * ldq; g.o_hs = hb.hd; g.out = dq; g.ldo = ldq;
+            ga_rows(g, dS, nkpad, nkpad); ga_weight(g, Kt, N, hb.hd, nkpad);
+            ga_batch_heads(g, BH, (long long)N * nkpad, (long long)dpad * nkpad, hb.H, (long long)N * ldq, hb.hd); ga_out(g, dq, ldq);
             TRY(R::run_gemm(g));
         }
         if (!dk) return 0;
@@ -703,10 +663,8 @@ struct Trainer : Runner<T> {
                 TRY(launch_transpose<T>(w_src, Wt, npad, dpad, dpad, npad, (long long)npad * dpad, (long long)dpad * npad, BH, npad, st));
             }
             GemmArgs g;
-            g.a0 = At; g.c0 = npad; g.lda0 = npad; g.a_bs = (long long)nkpad * npad;
-            g.w = Wt; g.w_bs = (long long)dpad * npad;
-            g.M = nk; g.N = hb.hd; g.K = npad; g.batch = BH;
-            g.heads = hb.H; g.o_bs = (long long)nk * ldkv; g.o_hs = hb.hd; g.out = out; g.ldo = ldkv;
+            ga_rows(g, At, npad, npad); ga_weight(g, Wt, nk, hb.hd, npad);
+            ga_batch_heads(g, BH, (long long)nkpad * npad, (long long)dpad * npad, hb.H, (long long)nk * ldkv, hb.hd); ga_out(g, out, ldkv);
             return R::run_gemm(g);
         };
         TRY(kv_grad(dS, a.q, dk));
@@ -801,16 +759,13 @@ struct Trainer : Runner<T> {
                 // 1x1 shortcut over the concatenated input: one dgrad GEMM per source, accumulated in place
                 const T* wT = static_cast<const T*>(rr.sc.wT);
                 MRISR_REQUIRE(wT, "shortcut dgrad weights");
-                GemmArgs g;
-                g.a0 = dO; g.c0 = rr.cout; g.lda0 = rr.cout; g.w = wT; g.M = (int)x.rows(); g.N = x.C; g.K = rr.cout;
-                g.resid = s0->g; g.ldr = x.C; g.out = s0->g; g.ldo = x.C;
-                TRY(R::run_gemm(g));
-                if (s1) {
-                    GemmArgs g1;
-                    g1.a0 = dO; g1.c0 = rr.cout; g1.lda0 = rr.cout; g1.w = wT + (size_t)x.C * rr.cout; g1.M = (int)x.rows();
-                    g1.N = x1v.C; g1.K = rr.cout; g1.resid = s1->g; g1.ldr = x1v.C; g1.out = s1->g; g1.ldo = x1v.C;
-                    TRY(R::run_gemm(g1));
-                }
+                auto source_dgrad = [&](const T* w, int c, void* gx) -> int {
+                    GemmArgs g;
+                    ga_rows(g, dO, rr.cout, rr.cout); ga_weight(g, w, (int)x.rows(), c, rr.cout); ga_resid(g, gx, c); ga_out(g, gx, c);
+                    return R::run_gemm(g);
+                };
+                TRY(source_dgrad(wT, x.C, s0->g));
+                if (s1) TRY(source_dgrad(wT + (size_t)x.C * rr.cout, x1v.C, s1->g));
             } else if (!dry) {
                 TRY(launch_add_inplace<T>(s0->g, dO, (long long)x.numel(), st));
             }

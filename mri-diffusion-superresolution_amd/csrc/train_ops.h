@@ -5,7 +5,7 @@
 #pragma once
 #include <functional>
 
-#include "common.h"
+#include "gemm_args.h"
 
 namespace mrisr {
 
@@ -38,9 +38,7 @@ int conv_wgrad_run(hipStream_t st, bool dry, const TrainAllocFn& alloc, const Tr
         if ((rc = launch_im2col_all_T<T>(x, xT, xB, xH, xW, cin_src, Ho, Wo, stride, ks / 2, ks, Mpad, st)) != 0) return rc;
     }
     GemmArgs g;
-    g.a0 = dyT; g.c0 = Mpad; g.lda0 = Mpad;
-    g.w = xT; g.M = cout_src; g.N = ncol; g.K = Mpad;
-    g.out_mode = OUT_F32; g.out = tmp; g.ldo = ncol;
+    ga_rows(g, dyT, Mpad, Mpad); ga_weight(g, xT, cout_src, ncol, Mpad); ga_out_f32(g, tmp, ncol);
     if (int rc = run_gemm(g)) return rc;
     if (!dry && gW) return launch_wgrad_accum_gen(tmp, ncol, cin_src, gW, cout, cin, taps, geglu_half, st);
     return 0;
@@ -64,11 +62,9 @@ int conv_dgrad_run(hipStream_t st, bool dry, const TrainGemmFn& run_gemm, const 
         return launch_direct_conv<T>(a, st);
     }
     GemmArgs g;
-    g.a0 = dy; g.c0 = cout; g.lda0 = cout;
-    g.conv = 1; g.B = B; g.Hin = H; g.Win = W; g.Hout = Ho; g.Wout = Wo; g.stride = 1; g.ups = mode; g.zstuff = mode;
-    g.w = wd; g.M = B * Ho * Wo; g.N = cin; g.K = 9 * cout;
-    if (resid) { g.resid = resid; g.ldr = ldr; }
-    g.out = out; g.ldo = cin;
+    ga_rows(g, dy, cout, cout); ga_conv3(g, B, H, W, 1, mode, 1, mode); ga_weight(g, wd, B * Ho * Wo, cin, 9 * cout);
+    if (resid) ga_resid(g, resid, ldr);
+    ga_out(g, out, cin);
     return run_gemm(g);
 }
 

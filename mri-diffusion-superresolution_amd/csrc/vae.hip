@@ -190,10 +190,9 @@ struct VaeRunner : Runner<T> {
         *out = new_act(x.B, x.H / 2, x.W / 2, cw.cout);
         if (!out->p) return 7;
         GemmArgs g;
-        g.a0 = x.p; g.c0 = x.C; g.lda0 = x.C;
-        g.conv = 1; g.B = x.B; g.Hin = x.H; g.Win = x.W; g.Hout = x.H / 2; g.Wout = x.W / 2; g.stride = 2; g.pad = 0;
-        g.w = cw.w; g.M = x.B * g.Hout * g.Wout; g.N = cw.cout; g.K = 9 * x.C; g.bias = cw.b;
-        g.out = out->p; g.ldo = cw.cout;
+        ga_rows(g, x);
+        ga_conv3(g, x, 2, 0, 0);  // (H, W even: Hout = H / 2)
+        ga_weight(g, cw.w, x.B * g.Hout * g.Wout, cw.cout, 9 * x.C); g.bias = cw.b; ga_out(g, out->p, cw.cout);
         return R::run_gemm(g);
     }
 
@@ -207,17 +206,11 @@ struct VaeRunner : Runner<T> {
         TRY(R::gn(h, nullptr, r.n2, true, eps(), &hn));
         Act res = x;
         if (r.has_sc) {
-            GemmArgs g;
-            g.a0 = x.p; g.c0 = x.C; g.lda0 = x.C;
-            g.w = r.sc.w; g.M = (int)x.rows(); g.N = r.cout; g.K = r.cin; g.bias = r.sc.b; g.out = o.p; g.ldo = r.cout;
+            GemmArgs g = resnet_shortcut_args(x, nullptr, r.sc.w, r.sc.b, r.cin, r.cout, o.p);
             TRY(R::run_gemm(g));
             res = o;
         }
-        GemmArgs g;
-        g.a0 = hn.p; g.c0 = hn.C; g.lda0 = hn.C;
-        g.conv = 1; g.B = x.B; g.Hin = x.H; g.Win = x.W; g.Hout = x.H; g.Wout = x.W;
-        g.w = r.c2.w; g.M = (int)x.rows(); g.N = r.cout; g.K = 9 * r.cout; g.bias = r.c2.b;
-        g.resid = res.p; g.ldr = r.cout; g.out = o.p; g.ldo = r.cout;
+        GemmArgs g = resnet_conv2_args(hn.p, x.B, x.H, x.W, r.cout, r.c2.w, r.c2.b, res.p, o.p);
         TRY(R::run_gemm(g));
         m.arena.release(mk);
         *out = o;

@@ -465,6 +465,25 @@ int mrisr_op_ln_linear(const mrisr_tensor* x_rows, const float* gamma_dev, const
  * in ONE kernel at C = 320 (bf16): w1 = ff.net.0.proj.weight [2*hidden][320], w2 = ff.net.2.weight [320][hidden], f32 on the device */
 int mrisr_op_mlp(const mrisr_tensor* x_rows, const float* gamma_dev, const float* beta_dev, const float* w1_dev, const float* b1_dev,
                  const float* w2_dev, const float* b2_dev, int hidden, int residual, mrisr_tensor* y_rows, void* stream);
+/* the same kernel with its continuation, the transformer's proj_out and outer residual (MlpArgs::wp / bp / xres / out2):
+ * y = ([x +] FF2(GEGLU(FF1(LayerNorm(x))))) Wp^T + bp + xres, wp = proj_out.weight [320][320] f32 (bp may be NULL), xres / y bf16 [M][320];
+ * the feed-forward output itself is not returned.  M must be a multiple of 128 (whole row panels), else the call is refused */
+int mrisr_op_mlp_proj(const mrisr_tensor* x_rows, const float* gamma_dev, const float* beta_dev, const float* w1_dev, const float* b1_dev,
+                      const float* w2_dev, const float* b2_dev, int hidden, int residual, const float* wp_dev, const float* bp_dev,
+                      const mrisr_tensor* xres_rows, mrisr_tensor* y_rows, void* stream);
+/* the row-local middle of BasicTransformerBlock at C = 320, 8 heads, in ONE kernel (csrc/xtail.hip), in place on t:
+ *   x1 = attn1.to_out(ao) + t;  q = attn2.to_q(LayerNorm2(x1));  o = softmax(q K^T / sqrt(40)) V per head;  t <- attn2.to_out(o) + x1
+ * ao [M][ldao], t [M][ldt] bf16 (the tensors' second extent is the row pitch: >= 320, a multiple of 8; columns >= 320 are neither read nor
+ * written); ntok tokens per image (a multiple of 128 dividing M); w1 / wq / w2 [320][320], gamma / beta [320] f32 on the device, biases
+ * may be NULL; k, v the already projected prompt rows, bf16 [M / ntok][>= nk][320], of which the first nk (1 .. 80) are keys.  lora_r = 4:
+ * a rank-4 adapter (A [4][320], B [320][4], f32) on each of the three projections, all scaled by lora_scale; lora_r = 0: all six NULL.
+ * Weights, K / V and adapters are packed as the models pack them, on buffers of the call; anything the kernel is not written for is
+ * refused before the first launch */
+int mrisr_op_xattn_tail(const mrisr_tensor* ao_rows, mrisr_tensor* t_rows, int ntok, const float* w1_dev, const float* b1_dev,
+                        const float* gamma_dev, const float* beta_dev, const float* wq_dev, const float* bq_dev, const float* w2_dev,
+                        const float* b2_dev, const mrisr_tensor* k, const mrisr_tensor* v, int nk, const float* a1_dev, const float* lb1_dev,
+                        const float* aq_dev, const float* lbq_dev, const float* a2_dev, const float* lb2_dev, int lora_r, float lora_scale,
+                        void* stream);
 /* the fp8 form of the same projection (BASELINE configs[4]): weights quantised to OCP e4m3 with one scale per output channel, the
  * rows with one scale per row inside the kernel, f32 accumulate; gamma_dev / beta_dev NULL = no LayerNorm prologue */
 int mrisr_op_linear_fp8(const mrisr_tensor* x_rows, const float* gamma_dev, const float* beta_dev, const float* w_dev,

@@ -445,6 +445,113 @@ int mrisr_op_mlp(const mrisr_tensor* x, const float* gamma_dev, const float* bet
     API_END
 }
 
+int mrisr_op_mlp_proj(const mrisr_tensor* x, const float* gamma_dev, const float* beta_dev, const float* w1_dev, const float* b1_dev,
+                      const float* w2_dev, const float* b2_dev, int hidden, int residual, const float* wp_dev, const float* bp_dev,
+                      const mrisr_tensor* xres, mrisr_tensor* y, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(x && xres && y && gamma_dev && beta_dev && w1_dev && w2_dev && wp_dev, "null argument");
+    MRISR_REQUIRE(x->dtype == MRISR_BF16 && xres->dtype == MRISR_BF16 && y->dtype == MRISR_BF16 && x->ndim == 2 && xres->ndim == 2 && y->ndim == 2,
+                  "bf16 rows in/out");
+    TRY(gemm_prepare());
+    hipStream_t st = (hipStream_t)stream;
+    const int M = (int)x->shape[0], C = (int)x->shape[1];
+    MRISR_REQUIRE(mlp_fused_ok(C, hidden, C), "fused feed-forward: C = 320 rows in and out, hidden % 32 == 0");
+    MRISR_REQUIRE(xres->shape[0] == M && xres->shape[1] == C && y->shape[0] == M && y->shape[1] == C, "fused feed-forward + proj_out: row shapes");
+    MRISR_REQUIRE(M > 0 && M % 128 == 0, "fused feed-forward + proj_out: whole 128-row panels");
+    DevBuf w1p, b1p, w2b, w2p, wpb, wpp, ff;
+    TRY(w1p.reserve((size_t)2 * hidden * C * 2, false));
+    TRY(w2b.reserve((size_t)C * hidden * 2, false));
+    TRY(w2p.reserve((size_t)C * hidden * 2, false));
+    TRY(wpb.reserve((size_t)C * C * 2, false));
+    TRY(wpp.reserve((size_t)C * C * 2, false));
+    TRY(ff.reserve((size_t)M * C * 2, false));  // (MlpArgs::out: required, never stored in this form)
+    TRY(launch_pack_rows<bf16>(w1_dev, 2 * hidden, C, w1p.p, C, 0, 0, 1, hidden, 1.0f, st));
+    TRY(launch_pack_rows<bf16>(w2_dev, C, hidden, w2b.p, hidden, 0, 0, 0, 0, 1.0f, st));
+    TRY(launch_pack_mlp_w2(w2b.p, w2p.p, C, hidden, st));
+    TRY(launch_pack_rows<bf16>(wp_dev, C, C, wpb.p, C, 0, 0, 0, 0, 1.0f, st));
+    TRY(launch_pack_mlp_w2(wpb.p, wpp.p, C, C, st));
+    const float* b1 = nullptr;
+    if (b1_dev) {
+        TRY(b1p.reserve((size_t)2 * hidden * sizeof(float), false));
+        TRY(launch_pack_bias_geglu(b1_dev, static_cast<float*>(b1p.p), hidden, st));
+        b1 = static_cast<const float*>(b1p.p);
+    }
+    MlpArgs a;
+    a.x = x->data; a.ldx = C; a.M = M; a.ln_gamma = gamma_dev; a.ln_beta = beta_dev; a.ln_eps = 1e-5f;
+    a.w1 = w1p.p; a.b1 = b1; a.w2p = w2p.p; a.b2 = b2_dev;
+    a.resid = residual ? x->data : nullptr; a.ldr = C; a.out = ff.p; a.ldo = C; a.C = C; a.H = hidden; a.N2 = C;
+    a.wp = wpp.p; a.bp = bp_dev; a.xres = xres->data; a.ldxr = C; a.out2 = y->data; a.ldo2 = C;
+    TRY(launch_mlp_fused(a, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
+int mrisr_op_xattn_tail(const mrisr_tensor* ao, mrisr_tensor* t, int ntok, const float* w1_dev, const float* b1_dev, const float* gamma_dev,
+                        const float* beta_dev, const float* wq_dev, const float* bq_dev, const float* w2_dev, const float* b2_dev,
+                        const mrisr_tensor* k, const mrisr_tensor* v, int nk, const float* a1_dev, const float* lb1_dev, const float* aq_dev,
+                        const float* lbq_dev, const float* a2_dev, const float* lb2_dev, int lora_r, float lora_scale, void* stream) {
+    API_BEGIN
+    typedef bf16 T;
+    constexpr int C = 320, H = 8, hd = 40;
+    MRISR_REQUIRE(ao && t && k && v && w1_dev && gamma_dev && beta_dev && wq_dev && w2_dev, "null argument");
+    MRISR_REQUIRE(ao->dtype == MRISR_BF16 && t->dtype == MRISR_BF16 && k->dtype == MRISR_BF16 && v->dtype == MRISR_BF16, "xattn tail: bf16 rows");
+    MRISR_REQUIRE(ao->ndim == 2 && t->ndim == 2 && k->ndim == 3 && v->ndim == 3, "xattn tail: ao, t [M][ld]; k, v [B][keys][320]");
+    const int M = (int)ao->shape[0], ldao = (int)ao->shape[1], ldt = (int)t->shape[1], B = (int)k->shape[0], nkbuf = (int)k->shape[1];
+    MRISR_REQUIRE(t->shape[0] == M && ldao >= C && ldt >= C && ldao % 8 == 0 && ldt % 8 == 0, "xattn tail: row shapes (pitches >= 320, multiples of 8)");
+    MRISR_REQUIRE(ntok > 0 && xattn_tail_ok(C, H, M, ntok, nk), "xattn tail: C = 320, 8 heads, whole 128-row panels inside one image, 1 .. 80 keys");
+    MRISR_REQUIRE(B == M / ntok && k->shape[2] == C && v->shape[0] == B && v->shape[1] == nkbuf && v->shape[2] == C && nk <= nkbuf,
+                  "xattn tail: k, v [M / ntok][>= nk][320]");
+    const int nad = (a1_dev != nullptr) + (lb1_dev != nullptr) + (aq_dev != nullptr) + (lbq_dev != nullptr) + (a2_dev != nullptr) + (lb2_dev != nullptr);
+    MRISR_REQUIRE((lora_r == 0 && nad == 0) || (lora_r == 4 && nad == 6), "xattn tail: rank-4 adapters on all three projections, or none");
+    TRY(gemm_prepare());
+    hipStream_t st = (hipStream_t)stream;
+    // the packing of Packer::xf (model.hip) and Runner::project_context (runner.h), on buffers of this call
+    const int dpad = 64, ctx_pad = round_up(nkbuf, 64);
+    DevBuf w1p, wqb, wqp, w2b, w2p, kc, vtc, kvp, ab[3], lbb[3];
+    TRY(w1p.reserve((size_t)C * C * sizeof(T), false));
+    TRY(wqb.reserve((size_t)C * C * sizeof(T), false));
+    TRY(wqp.reserve((size_t)C * C * sizeof(T), false));
+    TRY(w2b.reserve((size_t)C * C * sizeof(T), false));
+    TRY(w2p.reserve((size_t)C * C * sizeof(T), false));
+    TRY(kc.reserve((size_t)B * H * ctx_pad * dpad * sizeof(T), true));
+    TRY(vtc.reserve((size_t)B * H * dpad * ctx_pad * sizeof(T), true));
+    TRY(kvp.reserve(xattn_tail_kv_bytes(B), false));
+    TRY(launch_pack_rows<T>(w1_dev, C, C, w1p.p, C, 0, 0, 0, 0, 1.0f, st));
+    TRY(launch_pack_rows<T>(wq_dev, C, C, wqb.p, C, 0, 0, 0, 0, 1.0f, st));
+    TRY(launch_pack_rows<T>(w2_dev, C, C, w2b.p, C, 0, 0, 0, 0, 1.0f, st));
+    TRY(launch_pack_mlp_w2(wqb.p, wqp.p, C, C, st));
+    TRY(launch_pack_mlp_w2(w2b.p, w2p.p, C, C, st));
+    hipLaunchKernelGGL(rows_to_heads_kernel<T>, dim3(1024), dim3(256), 0, st, static_cast<const T*>(k->data), static_cast<T*>(kc.p), B, nkbuf, H, hd,
+                       ctx_pad, dpad, 0);
+    hipLaunchKernelGGL(rows_to_heads_kernel<T>, dim3(1024), dim3(256), 0, st, static_cast<const T*>(v->data), static_cast<T*>(vtc.p), B, nkbuf, H, hd,
+                       ctx_pad, dpad, 1);
+    MRISR_CHECK_HIP(hipGetLastError());
+    TRY(launch_pack_xattn_kv(kc.p, vtc.p, kvp.p, B, ctx_pad, dpad, nk, st));
+    if (lora_r) {
+        const float* A[3] = {a1_dev, aq_dev, a2_dev};
+        const float* Bm[3] = {lb1_dev, lbq_dev, lb2_dev};
+        for (int i = 0; i < 3; ++i) {
+            TRY(ab[i].reserve((size_t)lora_r * C * sizeof(T), false));
+            TRY(lbb[i].reserve((size_t)C * lora_r * sizeof(float), false));
+            TRY(launch_pack_rows<T>(A[i], lora_r, C, ab[i].p, C, 0, 0, 0, 0, 1.0f, st));
+            TRY(launch_pack_rows<float>(Bm[i], C, lora_r, lbb[i].p, lora_r, 0, 0, 0, 0, lora_scale, st));
+        }
+    }
+    XTailArgs a;
+    a.ao = ao->data; a.ldao = ldao; a.t = t->data; a.ldt = ldt; a.M = M; a.ntok = ntok;
+    a.w1 = w1p.p; a.b1 = b1_dev; a.a1 = ab[0].p; a.lb1 = static_cast<const float*>(lbb[0].p);
+    a.ln_g = gamma_dev; a.ln_b = beta_dev; a.ln_eps = 1e-5f;
+    a.wq = wqp.p; a.bq = bq_dev; a.aq = ab[1].p; a.lbq = static_cast<const float*>(lbb[1].p);
+    a.kvp = kvp.p; a.nk = nk; a.scale = 1.0f / sqrtf((float)hd);
+    a.w2 = w2p.p; a.b2 = b2_dev; a.a2 = ab[2].p; a.lb2 = static_cast<const float*>(lbb[2].p);
+    a.lora_r = lora_r;
+    TRY(launch_xattn_tail(a, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
 int mrisr_op_linear_fp8(const mrisr_tensor* x, const float* gamma_dev, const float* beta_dev, const float* w_dev, const float* bias_dev,
                         int n, int act, mrisr_tensor* y, void* stream) {
     API_BEGIN

@@ -70,7 +70,7 @@ EXPORTS = [
     "mrisr_train_prepare", "mrisr_train_num_trainable", "mrisr_train_num_tensors", "mrisr_train_tensor_info", "mrisr_train_tensor_shape",
     "mrisr_train_bind", "mrisr_train_refresh", "mrisr_train_step", "mrisr_train_set_intrablock_grads", "mrisr_train_set_controlnet_residuals", "mrisr_controlnet_train_prepare", "mrisr_controlnet_train_num_trainable", "mrisr_controlnet_train_num_tensors", "mrisr_controlnet_train_tensor_info", "mrisr_controlnet_train_bind", "mrisr_controlnet_train_refresh", "mrisr_controlnet_train_forward", "mrisr_controlnet_train_backward", "mrisr_optim_sumsq", "mrisr_optim_adamw", "mrisr_optim_ema",
     "mrisr_prof_enable", "mrisr_prof_reset", "mrisr_prof_report",
-    "mrisr_op_conv3x3", "mrisr_op_conv3x3_sc", "mrisr_op_ff_proj", "mrisr_op_linear", "mrisr_op_ln_linear", "mrisr_op_linear_fp8", "mrisr_op_mlp", "mrisr_op_groupnorm", "mrisr_op_layernorm", "mrisr_op_attention",
+    "mrisr_op_conv3x3", "mrisr_op_conv3x3_sc", "mrisr_op_ff_proj", "mrisr_op_linear", "mrisr_op_ln_linear", "mrisr_op_linear_fp8", "mrisr_op_mlp", "mrisr_op_mlp_proj", "mrisr_op_xattn_tail", "mrisr_op_groupnorm", "mrisr_op_layernorm", "mrisr_op_attention",
     "mrisr_op_attention_bwd",
     "mrisr_op_groupnorm_bwd", "mrisr_op_layernorm_bwd", "mrisr_op_geglu", "mrisr_op_pointwise_bwd", "mrisr_op_lora_wgrad", "mrisr_op_lora_wgrad_geglu", "mrisr_op_lora_wgrad_hr", "mrisr_op_dora_scale", "mrisr_op_dora_mag_grad",
     "mrisr_op_transpose", "mrisr_op_softmax_bwd", "mrisr_op_small_dense_bwd", "mrisr_op_conv_wgrad", "mrisr_op_conv_dgrad",
@@ -125,6 +125,8 @@ def lib() -> C.CDLL:
         L.mrisr_op_conv_lora_down.argtypes = [I, P, I, I, I, I, P, I, P, I, P]
         L.mrisr_op_conv_lora_dgrad.argtypes = [I, P, I, I, I, I, P, I, P, I, P]
         L.mrisr_op_conv3x3_lora.argtypes = [P, P, P, P, P, I, F, P, P, I, I, I, P, P]
+        L.mrisr_op_mlp_proj.argtypes = [P, P, P, P, P, P, P, I, I, P, P, P, P, P]
+        L.mrisr_op_xattn_tail.argtypes = [P, P, I] + [P] * 10 + [I] + [P] * 6 + [I, F, P]
         L.mrisr_resize_scratch_bytes.restype = C.c_size_t
         L.mrisr_resize_scratch_bytes.argtypes = [C.c_int] * 6
         L.mrisr_resize_slices.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -101,19 +101,60 @@ def ln_linear(x, gamma, beta, weight, bias=None, act=L.ACT_NONE):
     return y
 
 
-def mlp(x, gamma, beta, w1, b1, w2, b2, residual=True):
+def mlp(x, gamma, beta, w1, b1, w2, b2, residual=True, wp=None, bp=None, xres=None):
     """x + FF2(GEGLU(FF1(LayerNorm(x)))) in one kernel (bf16 rows of width 320; the hidden activation stays on-chip):
-    w1 [2H][320] = diffusers ff.net.0.proj.weight (value half then gate half), w2 [320][H] = ff.net.2.weight."""
+    w1 [2H][320] = diffusers ff.net.0.proj.weight (value half then gate half), w2 [320][H] = ff.net.2.weight.
+    With ``wp`` [320][320] (and ``xres`` [M][320], optionally ``bp``) the kernel's continuation runs as well and ITS result is
+    returned: (the above) wp^T + bp + xres, the transformer's proj_out and outer residual (whole 128-row panels only)."""
     x = x.contiguous()
     f = lambda t: t.detach().to(torch.float32).contiguous() if t is not None else None
-    ga, be, w1f, b1f, w2f, b2f = (f(t) for t in (gamma, beta, w1, b1, w2, b2))
+    ga, be, w1f, b1f, w2f, b2f, wpf, bpf = (f(t) for t in (gamma, beta, w1, b1, w2, b2, wp, bp))
     hidden = w2f.shape[1]
     y = torch.empty((x.shape[0], w2f.shape[0]), dtype=x.dtype, device=x.device)
     tx, ty = L.as_tensor(x), L.as_tensor(y)
     p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    if wp is not None or bp is not None or xres is not None:
+        if wp is None or xres is None:
+            raise L.MrisrError("mlp: the proj_out continuation needs wp and xres")
+        if wpf.shape != (y.shape[1], y.shape[1]) or (bpf is not None and bpf.shape != (y.shape[1],)):
+            raise L.MrisrError("mlp: wp [320][320], bp [320]")
+        xr = xres.contiguous()
+        txr = L.as_tensor(xr)
+        L.check(L.lib().mrisr_op_mlp_proj(C.byref(tx), p(ga), p(be), p(w1f), p(b1f), p(w2f), p(b2f), hidden, 1 if residual else 0,
+                                          p(wpf), p(bpf), C.byref(txr), C.byref(ty), L.stream_ptr()))
+        return y
     L.check(L.lib().mrisr_op_mlp(C.byref(tx), p(ga), p(be), p(w1f), p(b1f), p(w2f), p(b2f), hidden, 1 if residual else 0,
                                  C.byref(ty), L.stream_ptr()))
     return y
+
+
+def xattn_tail(ao, t, ntok, w1, b1, gamma, beta, wq, bq, w2, b2, k, v, nk=None, lora=None, lora_scale=1.0):
+    """The row-local middle of a C = 320 transformer block in one kernel (csrc/xtail.hip):
+    x1 = ao w1^T + b1 + t;  q = LayerNorm(x1; gamma, beta) wq^T + bq;  o = softmax(q k^T / sqrt(40)) v over 8 heads;
+    returns o w2^T + b2 + x1.  ao [M][ldao], t [M][ldt] bf16 rows whose second extent is the row pitch (>= 320, columns beyond 320
+    are padding); the kernel works in place on ``t``, so a clone of it is passed and returned, padding included.  ``ntok`` tokens
+    per image; k, v the projected prompt rows, bf16 [M / ntok][keys][320], of which the first ``nk`` (default: all) are attended
+    to.  ``lora``: three rank-4 adapters ((A1, B1), (Aq, Bq), (A2, B2)), A [4][320], B [320][4], all scaled by ``lora_scale``;
+    a pair may be None, which the library refuses unless all three are."""
+    ao, k, v = ao.contiguous(), k.contiguous(), v.contiguous()
+    out = t.contiguous().clone()
+    f = lambda a: a.detach().to(torch.float32).contiguous() if a is not None else None
+    w1f, b1f, gaf, bef, wqf, bqf, w2f, b2f = (f(a) for a in (w1, b1, gamma, beta, wq, bq, w2, b2))
+    if lora is not None and len(lora) != 3:
+        raise L.MrisrError("xattn_tail: lora is three (A, B) pairs, for attn1.to_out, attn2.to_q and attn2.to_out")
+    ad = [f(a) for pair in (lora or ()) for a in (pair if pair is not None else (None, None))] or [None] * 6
+    rank = next((int(a.shape[0]) for a in ad[0::2] if a is not None), 0)
+    # (the library sees pointers only: what it will read through them is checked here)
+    if any(a.shape != (320, 320) for a in (w1f, wqf, w2f)) or any(a.shape != (320,) for a in (b1f, gaf, bef, bqf, b2f) if a is not None):
+        raise L.MrisrError("xattn_tail: weights [320][320], vectors [320]")
+    if any(a is not None and a.shape != s for pair in zip(ad[0::2], ad[1::2]) for a, s in zip(pair, ((rank, 320), (320, rank)))):
+        raise L.MrisrError("xattn_tail: adapters A [r][320], B [320][r], one rank")
+    tao, tt, tk, tv = (L.as_tensor(a) for a in (ao, out, k, v))
+    p = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+    L.check(L.lib().mrisr_op_xattn_tail(C.byref(tao), C.byref(tt), int(ntok), p(w1f), p(b1f), p(gaf), p(bef), p(wqf), p(bqf), p(w2f), p(b2f),
+                                        C.byref(tk), C.byref(tv), int(k.shape[1] if nk is None else nk), *(p(a) for a in ad), rank,
+                                        float(lora_scale), L.stream_ptr()))
+    return out
 
 
 def linear_fp8(x, weight, bias=None, act=L.ACT_NONE, gamma=None, beta=None):

@@ -1,6 +1,7 @@
 """The fused row-local middle of the C = 320 transformer blocks (csrc/xtail.hip: attn1.to_out + residual -> LayerNorm2 -> attn2.to_q ->
 cross-attention over the cached prompt K / V -> attn2.to_out + residual in ONE launch) against (a) the four separate launches it
-replaces and (b) the CPU oracle (oracle/unet.py, diffusers' BasicTransformerBlock restated; call site res_srdiff.py:73-78)."""
+replaces and (b) the CPU oracle (oracle/unet.py, diffusers' BasicTransformerBlock restated; call site res_srdiff.py:73-78).
+The kernel on its own, element-wise against float64 at shapes and operands a UNet forward cannot reach: test_gpu_xtail_op.py."""
 import ctypes as C
 import json
 

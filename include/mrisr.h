@@ -223,6 +223,27 @@ int mrisr_sampler_run_guided(mrisr_sampler* s, mrisr_tensor* latents, const mris
                              const mrisr_tensor* step_noise, const mrisr_tensor* ehs2, const mrisr_tensor* cond2,
                              const mrisr_tensor* intrablock2, int n_intrablock, int use_graph, void* stream);
 
+/* ---- tiled sampling (MultiDiffusion, Bar-Tal et al. 2023, with the Gaussian weights of Mixture of Diffusers, Jimenez 2023) -------
+ * The latent canvas [NB, C, H, W] is cut into overlapping tiles, the forward runs on the tile batch [NB*T, C, t_h, t_w] and the tile
+ * predictions are blended back before the reverse step, which stays on the canvas.  All sizes in latent pixels.
+ * Grid, per axis (extent n, tile t, overlap o, 0 <= o < t): t_eff = min(t, n); one tile at 0 if n <= t; else stride s = t - o,
+ * k = ceil((n - t) / s) + 1 tiles, origin i = min(i s, n - t): the last tile is pulled back to end at n.  T = k_y k_x, tile index
+ * ti = ty k_x + tx, row of the tile batch r = b T + ti (sample-major; b over the forward's rows: 2B in a guided run).
+ * Window, per axis, length t_eff: uniform 1, or gaussian w[i] = exp(-((i - (t_eff-1)/2) / t_eff)^2 / (2 * 0.01)).  The normalised table
+ * is nw[tile][i] = w[i] / (sum over the tiles covering origin + i of w[their local index]), float64 rounded once to f32; a pixel one
+ * tile covers gets exactly 1.  Blend: eps[b,c,y,x] = sum over covering (ty, tx), ty then tx ascending, of
+ * (nwy[ty][y - oy[ty]] * nwx[tx][x - ox[tx]]) * et[r, c, y - oy[ty], x - ox[tx]] - a gather per element, no atomics. */
+typedef enum { MRISR_TILE_UNIFORM = 0, MRISR_TILE_GAUSSIAN = 1 } mrisr_tile_window;
+/* One axis on the host (no GPU call): origins[n_tiles], weights[n_tiles][min(tile, extent)].  origins / weights may be NULL to ask
+ * for n_tiles alone (never more than extent). */
+int mrisr_tile_tables(int extent, int tile, int overlap, int window, int* origins, float* weights, int* n_tiles);
+/* Tiles for the next runs; tile_h == 0 turns them off (the default).  tile and overlap must be multiples of d = 2^(num_levels-1),
+ * tile >= d, 0 <= overlap < tile.  Refused while a feature cache is set (and mrisr_sampler_set_cache refuses interval > 1 while tiles
+ * are set).  A run whose grid has T == 1 (tile >= canvas on both axes) is the plain run.  With T > 1, mrisr_sampler_run / _run_guided
+ * take ehs [NB*T, L, D], cond [NB*T, 3, 8 t_h, 8 t_w] and intrablock features [NB*T, ...] at tile geometry (rows sample-major as
+ * above); latents, lr_latents and step_noise stay canvas-shaped, and h, w of the canvas must be multiples of d. */
+int mrisr_sampler_set_tiles(mrisr_sampler* s, int tile_h, int tile_w, int overlap_h, int overlap_w, int window);
+
 /* ---- T2I-Adapter training (in BASELINE config 3 the adapter runs, and is differentiated, every step)
  * Same ownership model as the LoRA step: the caller owns ONE flat f32 vector of all adapter parameters (PyTorch layouts,
  * state-dict keys via tensor_info) and its gradient.  After train_prepare / train_bind, mrisr_adapter_forward keeps what the
@@ -600,6 +621,14 @@ int mrisr_op_guided_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const
 int mrisr_op_multistep_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const mrisr_tensor* eps, const mrisr_tensor* lr,
                             mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot, float guidance_scale,
                             float guidance_rescale, void* stream);
+
+/* the two kernels of tiled sampling alone, on explicit tables: x [NB,C,H,W] f32 NCHW, xt [NB*ky*kx, C, tile_h, tile_w] f32 NCHW;
+ * origins_y / origins_x: host int[ky] / [kx]; weights_y / weights_x: host f32 [ky][tile_h] / [kx][tile_w] (normalised tables).  Refused
+ * before any launch: null or misaligned (4-byte) pointers, shape mismatches, origins that do not start at 0, increase, leave no gap
+ * and end at extent - tile.  gather copies canvas -> tiles; blend sums tiles -> canvas as mrisr_sampler_set_tiles describes. */
+int mrisr_op_tile_gather(const mrisr_tensor* x, mrisr_tensor* xt, const int* origins_y, int ky, const int* origins_x, int kx, void* stream);
+int mrisr_op_tile_blend(const mrisr_tensor* xt, mrisr_tensor* x, const int* origins_y, int ky, const int* origins_x, int kx,
+                        const float* weights_y, const float* weights_x, void* stream);
 
 #ifdef __cplusplus
 }

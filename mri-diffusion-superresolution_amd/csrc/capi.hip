@@ -302,6 +302,11 @@ struct mrisr_sampler {
     // shallow (reads it) otherwise; interval 1 = no cache: the body, the key and the graph without it
     int cache_interval = 1, cache_depth = 1;
     DevBuf d_cache;
+    // tiled sampling: tile_h == 0 is off.  A run whose grid has more than one tile gathers the state into d_xt
+    // [NB*T, C, t_h, t_w], runs the forward there into d_et and blends d_et into d_eps; the grid and the window tables live in d_tiles
+    int tile_h = 0, tile_w = 0, tile_oh = 0, tile_ow = 0, tile_window = MRISR_TILE_GAUSSIAN;
+    TilePlan tiles;
+    DevBuf d_tiles, d_xt, d_et;
     hipGraphExec_t exec = nullptr;
     hipGraphExec_t exec_shallow = nullptr;  // cache_interval > 1: exec is the full + store step, this the shallow one
     std::string graph_key;
@@ -433,9 +438,29 @@ int mrisr_sampler_set_cache(mrisr_sampler* s, int interval, int depth) {
     MRISR_REQUIRE(interval >= 1, "cache interval must be >= 1 (1: no cache)");
     MRISR_REQUIRE(depth >= 1 && depth <= s->unet->num_skips() - 1, "cache depth must lie in 1 .. num_skips - 1");
     MRISR_REQUIRE(interval == 1 || !s->cnet, "a feature cache together with a ControlNet is not supported");
+    MRISR_REQUIRE(interval == 1 || s->tile_h == 0, "a feature cache together with tiles is not supported");
     if (interval != s->cache_interval || depth != s->cache_depth) s->drop_graphs();  // the next run captures again
     s->cache_interval = interval;
     s->cache_depth = depth;
+    return 0;
+}
+
+int mrisr_sampler_set_tiles(mrisr_sampler* s, int tile_h, int tile_w, int overlap_h, int overlap_w, int window) {
+    MRISR_REQUIRE(s, "null sampler");
+    if (tile_h == 0) {  // off: the body, the key and the graph without tiles
+        if (s->tile_h) s->drop_graphs();
+        s->tile_h = s->tile_w = s->tile_oh = s->tile_ow = 0;
+        return 0;
+    }
+    const int d = 1 << (s->unet->cfg.num_levels - 1);  // the UNet's own divisibility rule for h and w
+    MRISR_REQUIRE(tile_h >= d && tile_w >= d && tile_h % d == 0 && tile_w % d == 0, "tile: a multiple of 2^(num_levels-1), at least that");
+    MRISR_REQUIRE(overlap_h >= 0 && overlap_w >= 0 && overlap_h < tile_h && overlap_w < tile_w && overlap_h % d == 0 && overlap_w % d == 0,
+                  "overlap: a multiple of 2^(num_levels-1) in 0 .. tile - 1");
+    MRISR_REQUIRE(window == MRISR_TILE_UNIFORM || window == MRISR_TILE_GAUSSIAN, "window: MRISR_TILE_UNIFORM or MRISR_TILE_GAUSSIAN");
+    MRISR_REQUIRE(s->cache_interval == 1, "tiles together with a feature cache are not supported");
+    if (tile_h != s->tile_h || tile_w != s->tile_w || overlap_h != s->tile_oh || overlap_w != s->tile_ow || window != s->tile_window)
+        s->drop_graphs();
+    s->tile_h = tile_h; s->tile_w = tile_w; s->tile_oh = overlap_h; s->tile_ow = overlap_w; s->tile_window = window;
     return 0;
 }
 
@@ -466,7 +491,7 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
     Model& U = *s->unet;
     const int B = (int)latents->shape[0], h = (int)latents->shape[2], w = (int)latents->shape[3];
     const int L = (int)ehs->shape[1];
-    const int NB = guided ? 2 * B : B;  // rows of every forward
+    const int NB = guided ? 2 * B : B;  // rows of every forward (of the canvas; a tiled run multiplies them by T)
     const long long per = (long long)latents->shape[1] * h * w;
     const long long n = (long long)B * per;
     const int cdt = U.cfg.compute_dtype;
@@ -475,7 +500,35 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
     // lr[i], noise[step * n + i] for i < n without bounds
     auto numel = [](const mrisr_tensor* t) { long long k = 1; for (int i = 0; i < t->ndim; ++i) k *= t->shape[i]; return k; };
     MRISR_REQUIRE(latents->shape[1] == U.cfg.in_channels, "latents channels vs the UNet's in_channels");
-    if (!guided)
+    // tiles: the grid of this canvas.  T == 1 (or tiles off) is the plain run; otherwise the forwards see FB = NB * T rows of fh x fw
+    const int Cl = (int)latents->shape[1];
+    bool tiled = false;
+    if (s->tile_h) {
+        MRISR_REQUIRE(B > 0 && h > 0 && w > 0, "tiled run: empty latents");
+        const int d = 1 << (U.cfg.num_levels - 1);
+        MRISR_REQUIRE(h % d == 0 && w % d == 0, "tiled run: h and w of the latents must be multiples of 2^(num_levels-1)");
+        TRY(s->tiles.build(h, w, s->tile_h, s->tile_w, s->tile_oh, s->tile_ow, s->tile_window));
+        TRY(s->tiles.check());
+        tiled = s->tiles.T() > 1;
+    }
+    const int T = tiled ? s->tiles.T() : 1;
+    const int fh = tiled ? s->tiles.th : h, fw = tiled ? s->tiles.tw : w;
+    if (tiled) MRISR_REQUIRE((long long)NB * T * Cl * fh * fw < (1ll << 31), "tiled run: the tile batch is too large");
+    const int FB = NB * T;  // rows of every forward
+    if (tiled) {
+        MRISR_REQUIRE(!cached, "tiles together with a feature cache are not supported");
+        MRISR_REQUIRE(ehs->ndim == 3 && ehs->shape[0] == FB && ehs->shape[2] == U.cfg.cross_attention_dim,
+                      "tiled run: encoder_hidden_states must be [NB*T, L, cross_attention_dim]: every forward row's context T times, sample-major");
+        if (cond) MRISR_REQUIRE(cond->ndim == 4 && cond->shape[0] == FB && cond->shape[2] == 8 * fh && cond->shape[3] == 8 * fw,
+                                "tiled run: controlnet_cond must be [NB*T, C, 8 t_h, 8 t_w]: the image cropped per tile");
+        for (int i = 0; i < n_intrablock; ++i) {
+            const mrisr_tensor& f = intrablock[i];
+            const long long r = f.ndim == 4 && f.shape[2] > 0 ? fh / f.shape[2] : 0;
+            MRISR_REQUIRE(f.ndim == 4 && f.shape[0] == FB && r >= 1 && (r & (r - 1)) == 0 && r <= (1ll << (U.cfg.num_levels - 1)) && f.shape[2] * r == fh &&
+                              f.shape[3] * r == fw,
+                          "tiled run: adapter features must be [NB*T, ...] at tile geometry: every feature cropped per tile");
+        }
+    } else if (!guided)
         MRISR_REQUIRE(ehs->ndim == 3 && ehs->shape[0] == B && ehs->shape[2] == U.cfg.cross_attention_dim,
                       "encoder_hidden_states must be [B, L, cross_attention_dim] with the latents' batch");
     else
@@ -484,9 +537,10 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
     if (guided) MRISR_REQUIRE(B > 0 && per % 4 == 0, "guided run: C*h*w of the latents must be a multiple of 4");
     if (s->multistep()) MRISR_REQUIRE(B > 0 && per % 4 == 0, "multistep solvers: C*h*w of the latents must be a multiple of 4");
     if (lr_latents) MRISR_REQUIRE(lr_latents->dtype == MRISR_F32 && numel(lr_latents) == n, "lr_latents: f32, same shape as latents");
-    if (cond) MRISR_REQUIRE(cond->ndim == 4 && cond->shape[0] == NB && cond->shape[2] == 8 * h && cond->shape[3] == 8 * w,
-                            guided ? "guided run: controlnet_cond must be [2B, C, 8h, 8w] (the [B] images twice)"
-                                   : "controlnet_cond must be [B, C, 8h, 8w] with the latents' batch");
+    if (cond && !tiled)
+        MRISR_REQUIRE(cond->ndim == 4 && cond->shape[0] == NB && cond->shape[2] == 8 * h && cond->shape[3] == 8 * w,
+                      guided ? "guided run: controlnet_cond must be [2B, C, 8h, 8w] (the [B] images twice)"
+                             : "controlnet_cond must be [B, C, 8h, 8w] with the latents' batch");
     {
         int need = 0;  // slabs read: one per step, indexed by the step's position in the schedule, when its sigma != 0
         for (int i = s->first; i < s->last; ++i)
@@ -497,7 +551,7 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
             MRISR_REQUIRE(numel(step_noise) / n >= need, "step_noise has fewer slabs than the last stochastic step needs");
         }
     }
-    for (int i = 0; i < n_intrablock; ++i)
+    for (int i = 0; i < n_intrablock && !tiled; ++i)
         MRISR_REQUIRE(intrablock[i].ndim == 4 && intrablock[i].shape[0] == NB,
                       guided ? "guided run: adapter features must be [2B, ...] (the [B] features twice)"
                              : "adapter features must carry the latents' batch");
@@ -516,13 +570,13 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
 
     // ---- one-time (per run) timestep-invariant work: context projections, condition embedding, features ----
     TRY(gemm_prepare());
-    TRY(U.set_context(ehs, NB, h, w, st));
+    TRY(U.set_context(ehs, FB, fh, fw, st));
     std::vector<mrisr_tensor> down_t;
     mrisr_tensor mid_t{};
     int ns = 0;
     if (s->cnet) {
         Model& C = *s->cnet;
-        TRY(C.set_context(ehs, NB, h, w, st));
+        TRY(C.set_context(ehs, FB, fh, fw, st));
         TRY(C.set_cond(cond, L, st));
         ns = C.num_skips();
         s->res_bufs.resize(ns + 1);
@@ -530,7 +584,7 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
         for (int k = 0; k <= ns; ++k) {
             mrisr_tensor t{};
             t.ndim = 4; t.dtype = cdt; t.layout = MRISR_NHWC;
-            C.skip_shape(k, NB, h, w, t.shape);
+            C.skip_shape(k, FB, fh, fw, t.shape);
             if (!s->res_bufs[k]) s->res_bufs[k].reset(new DevBuf());
             TRY(s->res_bufs[k]->reserve((size_t)t.shape[0] * t.shape[1] * t.shape[2] * t.shape[3] * esz, false));
             t.data = s->res_bufs[k]->p;
@@ -553,6 +607,17 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
         intra[i].dtype = cdt;
     }
     TRY(s->d_eps.reserve((size_t)NB * per * sizeof(float), false));
+    TileGrid tg;
+    if (tiled) {
+        // the table is uploaded before any capture; the graph reads it from d_tiles at every replay.  s->tiles is pageable and rebuilt by the
+        // next run: like the copy of ms_rows below, this relies on the runtime staging the copy before hipMemcpyAsync returns
+        const size_t tile_elems = (size_t)FB * Cl * fh * fw;
+        TRY(s->d_tiles.reserve(s->tiles.bytes(), false));
+        TRY(s->d_xt.reserve(tile_elems * sizeof(float), false));
+        TRY(s->d_et.reserve(tile_elems * sizeof(float), false));
+        MRISR_CHECK_HIP(hipMemcpyAsync(s->d_tiles.p, s->tiles.words.data(), s->tiles.bytes(), hipMemcpyHostToDevice, st));
+        tg = s->tiles.grid(s->d_tiles.p);
+    }
     UNetCache fc;
     if (cached) {  // reserved here, before any capture; written by the first step of every run before anything reads it
         int64_t cs[4];
@@ -612,18 +677,22 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
     tt.data = s->d_curt.p; tt.dtype = MRISR_I64; tt.ndim = 0;
     mrisr_tensor xin = *latents;  // what the forwards read
     if (guided) { xin.shape[0] = NB; xin.data = s->d_x2.p; }
+    const float* canvas = static_cast<const float*>(xin.data);  // [NB, C, h, w]: what a tiled step gathers from
+    if (tiled) { xin.shape[0] = FB; xin.shape[2] = fh; xin.shape[3] = fw; xin.data = s->d_xt.p; }
     mrisr_tensor eps_t = xin;
-    eps_t.data = s->d_eps.p;
+    eps_t.data = tiled ? s->d_et.p : s->d_eps.p;
     const int* step = static_cast<const int*>(s->d_step.p);
 
     auto body = [&](int cache_mode) -> int {
         fc.mode = cache_mode;
         hipLaunchKernelGGL(load_t_kernel, dim3(1), dim3(1), 0, st, static_cast<long long*>(s->d_curt.p),
                            static_cast<const long long*>(s->d_ts.p), step);
+        if (tiled) TRY(launch_tile_gather(canvas, static_cast<float*>(s->d_xt.p), tg, NB, Cl, st));
         if (s->cnet)
             TRY(s->cnet->forward_controlnet(&xin, &tt, nullptr, nullptr, 1.0f, down_t.data(), ns, &mid_t, st));
         TRY(U.forward_unet(&xin, &tt, nullptr, s->cnet ? down_t.data() : nullptr, ns, s->cnet ? &mid_t : nullptr,
                            intra.data(), n_intrablock, &eps_t, st, cached ? &fc : nullptr));
+        if (tiled) TRY(launch_tile_blend(static_cast<const float*>(s->d_et.p), static_cast<float*>(s->d_eps.p), tg, NB, Cl, st));
         if (guided)
             TRY(launch_guided_step(s->kind, (float*)latents->data, (float*)s->d_x2.p, (const float*)s->d_eps.p,
                                    lr_latents ? (const float*)lr_latents->data : nullptr, step_noise ? (const float*)step_noise->data : nullptr,
@@ -671,6 +740,11 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
             }
             if (cached) {  // the buffer the store node writes and the shallow graph reads, and where the decoder meets it
                 snprintf(kb, sizeof(kb), ",C%p,%d", s->d_cache.p, s->cache_depth);
+                key += kb;
+            }
+            if (tiled) {  // the geometry and the window the two kernels take by value or read from the table, the table and the tile batch buffers
+                snprintf(kb, sizeof(kb), ",T%d,%d,%d,%d,%d,%p,%p,%p", s->tile_h, s->tile_w, s->tile_oh, s->tile_ow, s->tile_window, s->d_tiles.p,
+                         s->d_xt.p, s->d_et.p);
                 key += kb;
             }
         }

@@ -1074,6 +1074,61 @@ int mrisr_op_conv3x3_lora(const mrisr_tensor* x, const float* w_oihw_dev, const 
     API_END
 }
 
+// ---- tiled sampling: the gather and the blend alone, on explicit origin / weight arrays (uploaded to a scratch table for the call) ----
+static int op_tile_plan(const mrisr_tensor* x, const mrisr_tensor* xt, const int* oy, int ky, const int* ox, int kx, const float* wy,
+                        const float* wx, TilePlan* p) {
+    MRISR_REQUIRE(x && xt && x->data && xt->data && oy && ox, "tile op: null argument");
+    MRISR_REQUIRE(x->ndim == 4 && xt->ndim == 4 && x->dtype == MRISR_F32 && xt->dtype == MRISR_F32 && x->layout == MRISR_NCHW &&
+                  xt->layout == MRISR_NCHW, "tile op: canvas and tile batch must be f32 NCHW [.., C, H, W]");
+    MRISR_REQUIRE((reinterpret_cast<uintptr_t>(x->data) & 3) == 0 && (reinterpret_cast<uintptr_t>(xt->data) & 3) == 0, "tile op: misaligned pointer");
+    for (int d = 0; d < 4; ++d)
+        MRISR_REQUIRE(x->shape[d] > 0 && xt->shape[d] > 0 && x->shape[d] < (1ll << 31) && xt->shape[d] < (1ll << 31), "tile op: empty tensor");
+    MRISR_REQUIRE(ky > 0 && kx > 0 && ky <= x->shape[2] && kx <= x->shape[3], "tile op: tile counts");
+    MRISR_REQUIRE(xt->shape[0] == x->shape[0] * ky * kx && xt->shape[1] == x->shape[1],
+                  "tile op: the tile batch must be [NB * ky * kx, C, tile_h, tile_w] for a canvas [NB, C, H, W]");
+    p->H = (int)x->shape[2]; p->W = (int)x->shape[3]; p->th = (int)xt->shape[2]; p->tw = (int)xt->shape[3];
+    p->oy.assign(oy, oy + ky);
+    p->ox.assign(ox, ox + kx);
+    if (wy && wx && p->th <= p->H && p->tw <= p->W) {
+        p->nwy.assign(wy, wy + (size_t)ky * p->th);
+        p->nwx.assign(wx, wx + (size_t)kx * p->tw);
+    } else {  // the gather reads no weights
+        p->nwy.assign((size_t)ky * p->th, 1.f);
+        p->nwx.assign((size_t)kx * p->tw, 1.f);
+    }
+    TRY(p->check());
+    p->pack();
+    return 0;
+}
+int mrisr_op_tile_gather(const mrisr_tensor* x, mrisr_tensor* xt, const int* origins_y, int ky, const int* origins_x, int kx, void* stream) {
+    API_BEGIN
+    TilePlan p;
+    TRY(op_tile_plan(x, xt, origins_y, ky, origins_x, kx, nullptr, nullptr, &p));
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf tab;
+    TRY(tab.reserve(p.bytes(), false));
+    MRISR_CHECK_HIP(hipMemcpyAsync(tab.p, p.words.data(), p.bytes(), hipMemcpyHostToDevice, st));
+    TRY(launch_tile_gather((const float*)x->data, (float*)xt->data, p.grid(tab.p), (int)x->shape[0], (int)x->shape[1], st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));  // the table is freed on return
+    return 0;
+    API_END
+}
+int mrisr_op_tile_blend(const mrisr_tensor* xt, mrisr_tensor* x, const int* origins_y, int ky, const int* origins_x, int kx,
+                        const float* weights_y, const float* weights_x, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(weights_y && weights_x, "tile blend: null weight table");
+    TilePlan p;
+    TRY(op_tile_plan(x, xt, origins_y, ky, origins_x, kx, weights_y, weights_x, &p));
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf tab;
+    TRY(tab.reserve(p.bytes(), false));
+    MRISR_CHECK_HIP(hipMemcpyAsync(tab.p, p.words.data(), p.bytes(), hipMemcpyHostToDevice, st));
+    TRY(launch_tile_blend((const float*)xt->data, (float*)x->data, p.grid(tab.p), (int)x->shape[0], (int)x->shape[1], st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
 }  // extern "C"
 #undef BWD_DISPATCH
 

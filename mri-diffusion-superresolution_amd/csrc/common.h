@@ -521,4 +521,18 @@ int launch_resshift_forward(const float* hr, const float* lr, const float* noise
                             const long long* t, int t_is_scalar, float* out, int B, long long per_sample,
                             hipStream_t st);
 
+// tiled sampling (tiles.hip): the canvas [NB, C, H, W] against the tile batch [NB * ky * kx, C, th, tw], both f32 NCHW.  oy / ox: the ky / kx
+// increasing tile origins, nwy [ky][th] / nwx [kx][tw]: the normalised per-axis window tables (all four on the device).  vec4: tw, W and every
+// x origin are multiples of 4 - the 16-byte path (taken when the bases are aligned too)
+struct TileGrid {
+    int H = 0, W = 0, th = 0, tw = 0, ky = 0, kx = 0;
+    const int* oy = nullptr;
+    const int* ox = nullptr;
+    const float* nwy = nullptr;
+    const float* nwx = nullptr;
+    bool vec4 = false;
+};
+int launch_tile_gather(const float* x, float* xt, const TileGrid& g, int NB, int C, hipStream_t st);
+int launch_tile_blend(const float* et, float* eps, const TileGrid& g, int NB, int C, hipStream_t st);
+
 }  // namespace mrisr

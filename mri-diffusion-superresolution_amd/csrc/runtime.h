@@ -132,4 +132,22 @@ struct Act {  // NHWC activation (or token rows when H*W is the token count)
 
 inline int dtype_size(int dt) { return dt == MRISR_F32 ? 4 : (dt == MRISR_I64 ? 8 : 2); }
 
+// ---- tiled sampling (tiles.hip) ----
+// one axis of the grid: increasing origins and the normalised window table [n_tiles][min(t, n)] (float64, rounded once to f32)
+int tile_axis(int n, int t, int o, int window, std::vector<int>& origins, std::vector<float>& weights);
+// both axes on the host, and their image as ONE small device upload: [oy | ox | pad][nwy | pad][nwx], each part on a 16-byte boundary
+struct TilePlan {
+    int H = 0, W = 0, th = 0, tw = 0;
+    std::vector<int> oy, ox;
+    std::vector<float> nwy, nwx;
+    std::vector<uint32_t> words;
+    size_t off_nwy = 0, off_nwx = 0;
+    int T() const { return (int)(oy.size() * ox.size()); }
+    int build(int H_, int W_, int tile_h, int tile_w, int overlap_h, int overlap_w, int window);  // the grid rule and the window
+    int check();  // origins in range, increasing and covering; table sizes (explicit arrays of the single-op entries)
+    void pack();
+    size_t bytes() const { return words.size() * sizeof(uint32_t); }
+    TileGrid grid(const void* dev) const;  // dev: where `words` was uploaded
+};
+
 }  // namespace mrisr

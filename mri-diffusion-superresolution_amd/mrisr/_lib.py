@@ -15,6 +15,7 @@ MRISR_F32, MRISR_BF16, MRISR_F16, MRISR_I64 = 0, 1, 2, 3
 MRISR_NCHW, MRISR_NHWC = 0, 1
 STEP_DDIM, STEP_RESSHIFT, STEP_DDPM, STEP_UNIPC, STEP_DPMSOLVERPP = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_GEGLU = 0, 1, 2, 3
+TILE_WINDOWS = {"uniform": 0, "gaussian": 1}
 
 _DT = {torch.float32: MRISR_F32, torch.bfloat16: MRISR_BF16, torch.float16: MRISR_F16, torch.int64: MRISR_I64}
 
@@ -60,6 +61,7 @@ EXPORTS = [
     "mrisr_adapter_destroy", "mrisr_adapter_set_param", "mrisr_adapter_finalize", "mrisr_adapter_forward",
     "mrisr_resshift_forward", "mrisr_sampler_create", "mrisr_sampler_destroy", "mrisr_sampler_run", "mrisr_sampler_set_range", "mrisr_sampler_set_clip",
     "mrisr_sampler_set_guidance", "mrisr_sampler_run_guided", "mrisr_sampler_set_cache", "mrisr_unet_cache_shape", "mrisr_unet_forward_cached", "mrisr_op_guided_step", "mrisr_sampler_set_solver", "mrisr_op_multistep_step",
+    "mrisr_tile_tables", "mrisr_sampler_set_tiles", "mrisr_op_tile_gather", "mrisr_op_tile_blend",
     "mrisr_adapter_train_prepare", "mrisr_adapter_train_num_trainable", "mrisr_adapter_train_num_tensors",
     "mrisr_adapter_train_tensor_info", "mrisr_adapter_train_bind", "mrisr_adapter_train_refresh", "mrisr_adapter_backward", "mrisr_adapter_backward_level", "mrisr_adapter_train_level_range",
     "mrisr_vae_create", "mrisr_vae_destroy", "mrisr_vae_set_param", "mrisr_vae_num_params", "mrisr_vae_finalize",
@@ -127,6 +129,10 @@ def lib() -> C.CDLL:
         L.mrisr_op_conv3x3_lora.argtypes = [P, P, P, P, P, I, F, P, P, I, I, I, P, P]
         L.mrisr_op_mlp_proj.argtypes = [P, P, P, P, P, P, P, I, I, P, P, P, P, P]
         L.mrisr_op_xattn_tail.argtypes = [P, P, I] + [P] * 10 + [I] + [P] * 6 + [I, F, P]
+        L.mrisr_tile_tables.argtypes = [I, I, I, I, P, P, P]
+        L.mrisr_sampler_set_tiles.argtypes = [P, I, I, I, I, I]
+        L.mrisr_op_tile_gather.argtypes = [P, P, P, I, P, I, P]
+        L.mrisr_op_tile_blend.argtypes = [P, P, P, I, P, I, P, P, P]
         L.mrisr_resize_scratch_bytes.restype = C.c_size_t
         L.mrisr_resize_scratch_bytes.argtypes = [C.c_int] * 6
         L.mrisr_resize_slices.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

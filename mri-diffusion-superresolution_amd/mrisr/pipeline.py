@@ -130,6 +130,56 @@ def check_cache(interval, depth, n_skips, has_controlnet=False):
     return int(interval), int(depth)
 
 
+TILE_WINDOWS = tuple(L.TILE_WINDOWS)
+
+
+def check_tiles(tile, overlap, window, divisor, has_cache=False):
+    """The argument rules of tiled sampling (``Sampler.set_tiles``), on numbers alone (no device is touched); returns the normalised
+    (t_h, t_w, o_h, o_w, window).  ``tile`` / ``overlap``: an int or a (h, w) pair, in latent pixels, multiples of ``divisor``
+    (the UNet's own rule for h and w, 2^(levels-1)); tile >= divisor; 0 <= overlap < tile; ``window`` "gaussian" or "uniform"; a
+    feature cache together with tiles is refused.  Raises ``ValueError`` naming the offending argument."""
+    def pair(name, v):
+        vs = tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+        if len(vs) != 2 or any(isinstance(a, bool) or not isinstance(a, (int, np.integer)) for a in vs):
+            raise ValueError(f"{name} must be an int or a pair of ints (h, w), got {v!r}")
+        return int(vs[0]), int(vs[1])
+
+    d = int(divisor)
+    t_h, t_w = pair("tile", tile)
+    o_h, o_w = pair("overlap", overlap)
+    for t in (t_h, t_w):
+        if t < d or t % d:
+            raise ValueError(f"tile must be a multiple of {d} (latent pixels) and at least {d}, got {tile!r}")
+    for t, o in ((t_h, o_h), (t_w, o_w)):
+        if o < 0 or o >= t or o % d:
+            raise ValueError(f"overlap must be a multiple of {d} in 0 .. tile - 1, got {overlap!r} for tile {tile!r}")
+    if window not in TILE_WINDOWS:
+        raise ValueError(f"window must be one of {TILE_WINDOWS}, got {window!r}")
+    if has_cache:
+        raise ValueError("tiles together with a feature cache (cache interval > 1) are not supported")
+    return t_h, t_w, o_h, o_w, window
+
+
+def tile_tables(extent, tile, overlap, window="gaussian"):
+    """One axis of the tile grid and its blend window, from the library's own host routine (``mrisr_tile_tables``; no GPU):
+    (origins: list[int], weights: f32 tensor [n_tiles, min(tile, extent)]), the weights normalised over the covering tiles."""
+    if window not in TILE_WINDOWS:
+        raise ValueError(f"window must be one of {TILE_WINDOWS}, got {window!r}")
+    lib, wid = L.lib(), L.TILE_WINDOWS[window]
+    k = C.c_int(0)
+    L.check(lib.mrisr_tile_tables(int(extent), int(tile), int(overlap), wid, None, None, C.byref(k)))
+    origins = (C.c_int * k.value)()
+    weights = torch.empty((k.value, min(int(tile), int(extent))), dtype=torch.float32)
+    L.check(lib.mrisr_tile_tables(int(extent), int(tile), int(overlap), wid, origins, C.c_void_p(weights.data_ptr()), C.byref(k)))
+    return list(origins), weights
+
+
+def _tile_crops(x, ys, xs, s_h, s_w):
+    """[N, C, H, W] -> [N*T, C, s_h, s_w]: the crop at every (y, x) of ys x xs (y-major) of every row, sample-major."""
+    crops = [x[..., y:y + s_h, xx:xx + s_w] for y in ys for xx in xs]
+    return torch.stack(crops, dim=1).flatten(0, 1).contiguous()
+
+
 class Sampler:
     """Owns a C-ABI sampler (device tables + the captured step graph) for one (unet, controlnet, schedule)."""
 
@@ -155,6 +205,7 @@ class Sampler:
             if len(scheduler.timesteps) > 1 and not bool((scheduler.timesteps[1:] < scheduler.timesteps[:-1]).all()):
                 raise ValueError("multistep solvers need strictly decreasing timesteps")
         self.unet, self.controlnet, self.kind = unet, controlnet, kind
+        self.tiles = None  # (t_h, t_w, o_h, o_w, window) once set_tiles turned tiling on
         ts = scheduler.timesteps.detach().cpu().to(torch.int64).numpy().copy()
         ac = scheduler.alphas_cumprod.detach().cpu().to(torch.float32).numpy().copy()
         self.n_steps = len(ts)
@@ -194,8 +245,66 @@ class Sampler:
         Fewer launches per step for a bounded deviation from the uncached run.  ``interval=1`` (the default) is no cache at all:
         the step graph and the result of a sampler that never had one.  Changing either value captures the step graphs again."""
         interval, depth = check_cache(interval, depth, int(L.lib().mrisr_model_num_skips(self.unet._h)), self.controlnet is not None)
+        if interval > 1 and getattr(self, "tiles", None) is not None:
+            raise ValueError("a feature cache (interval > 1) together with tiles is not supported")
         L.check(L.lib().mrisr_sampler_set_cache(self._h, interval, depth))
         self.cache_interval, self.cache_depth = interval, depth
+
+    @property
+    def divisor(self) -> int:
+        """The UNet's divisibility rule for the latents' h and w: 2^(levels-1)."""
+        return 2 ** (len(self.unet.config.block_out_channels) - 1)
+
+    def set_tiles(self, tile=None, overlap=0, window: str = "gaussian"):
+        """Tiled sampling for the next ``run`` (MultiDiffusion with Mixture-of-Diffusers' Gaussian weights).  The
+        latent canvas is cut into tiles of ``tile`` latent pixels (an int or (h, w)) that overlap by ``overlap``; every step runs ONE
+        forward on the batch of all tiles (``tile_rows`` tells how many rows that is) and blends the tile predictions with ``window``
+        ("gaussian" / "uniform") before the reverse step, which stays on the canvas.  Callers keep passing canvas-shaped arguments.
+        ``tile=None`` (the default) turns tiling off: the step graph and the result of a sampler that never had it; so does a tile that
+        covers the canvas.  Not together with a feature cache."""
+        if tile is None:
+            L.check(L.lib().mrisr_sampler_set_tiles(self._h, 0, 0, 0, 0, 0))
+            self.tiles = None
+            return
+        t_h, t_w, o_h, o_w, window = check_tiles(tile, overlap, window, self.divisor, getattr(self, "cache_interval", 1) > 1)
+        L.check(L.lib().mrisr_sampler_set_tiles(self._h, t_h, t_w, o_h, o_w, L.TILE_WINDOWS[window]))
+        self.tiles = (t_h, t_w, o_h, o_w, window)
+
+    def _tile_plan(self, h: int, w: int):
+        """(origins_y, origins_x, t_h, t_w) of a canvas of h x w latents, or None when the run is not tiled (off, or one tile)."""
+        if getattr(self, "tiles", None) is None:
+            return None
+        t_h, t_w, o_h, o_w, window = self.tiles
+        d = self.divisor
+        if h <= 0 or w <= 0 or h % d or w % d:
+            raise ValueError(f"tiled sampling needs latents whose h and w are multiples of {d}, got {h} x {w}")
+        oy, ox = tile_tables(h, t_h, o_h, window)[0], tile_tables(w, t_w, o_w, window)[0]
+        return None if len(oy) * len(ox) == 1 else (oy, ox, min(t_h, h), min(t_w, w))
+
+    def tile_rows(self, B: int, h: int, w: int, guided: bool = False) -> int:
+        """Rows of the forward a run on [B, C, h, w] latents uses: B (2B when ``guided``) times the number of tiles."""
+        plan = self._tile_plan(int(h), int(w))
+        return int(B) * (2 if guided else 1) * (len(plan[0]) * len(plan[1]) if plan else 1)
+
+    def _tile_operands(self, plan, h, w, ehs, cond, feats):
+        """The timestep-invariant operands of a tiled run, once per run: context rows T times, the condition image cropped per tile at
+        8 x origin, every adapter feature (computed ONCE on the whole canvas condition) cropped per tile at origin / its scale."""
+        oy, ox, t_h, t_w = plan
+        d = self.divisor
+        if cond is not None and tuple(cond.shape[-2:]) != (8 * h, 8 * w):
+            raise ValueError(f"controlnet_cond must be [B, C, {8 * h}, {8 * w}] for latents of {h} x {w}, got {tuple(cond.shape)}")
+        scales = []
+        for f in feats:
+            r = h // f.shape[2] if f.ndim == 4 and 0 < f.shape[2] <= h else 0
+            if r < 1 or r > d or r & (r - 1) or f.shape[2] * r != h or f.shape[3] * r != w:
+                raise ValueError(f"adapter features must be [B, C, h / s, w / s] of the {h} x {w} latents with s a power of two <= {d}, "
+                                 f"got {tuple(f.shape)}")
+            scales.append(r)
+        ehs = ehs.repeat_interleave(len(oy) * len(ox), dim=0).contiguous()
+        if cond is not None:
+            cond = _tile_crops(cond, [8 * y for y in oy], [8 * x for x in ox], 8 * t_h, 8 * t_w)
+        feats = [_tile_crops(f, [y // r for y in oy], [x // r for x in ox], t_h // r, t_w // r) for f, r in zip(feats, scales)]
+        return ehs, cond, feats
 
     def set_range(self, first_step: int, last_step: int):
         """Run only steps [first_step, last_step) of the schedule on the next ``run`` (resume / inspection).  The multistep kinds start
@@ -223,10 +332,15 @@ class Sampler:
                 raise ValueError("the multistep solvers need [B,C,h,w] latents with C*h*w a multiple of 4")
             if lr_latents is not None and tuple(lr_latents.shape) != tuple(latents.shape):
                 raise ValueError(f"lr_latents must have the latents' shape {tuple(latents.shape)}, got {tuple(lr_latents.shape)}")
+        plan = None
+        if self.tiles is not None:  # a tiled run: the canvas and everything shaped after it is checked here, before any launch
+            if latents.ndim != 4:
+                raise ValueError("tiled sampling needs [B,C,h,w] latents")
+            plan = self._tile_plan(latents.shape[2], latents.shape[3])
         if check_guidance(guidance_scale, guidance_rescale, encoder_hidden_states.shape,
                           None if uncond_hidden_states is None else uncond_hidden_states.shape, latents.shape[0]):
             return self._run_guided(latents, encoder_hidden_states, uncond_hidden_states, lr_latents, step_noise, controlnet_cond,
-                                    adapter_features, use_graph, float(guidance_scale), float(guidance_rescale))
+                                    adapter_features, use_graph, float(guidance_scale), float(guidance_rescale), plan)
         dev = latents.device
         ehs = encoder_hidden_states.to(dev).contiguous()
         if ehs.shape[0] != latents.shape[0]:
@@ -235,6 +349,10 @@ class Sampler:
         nz = step_noise.to(dev, torch.float32).contiguous() if step_noise is not None else None
         cond = controlnet_cond.to(dev).contiguous() if controlnet_cond is not None else None
         feats = [f.to(dev).contiguous() for f in (adapter_features or [])]
+        if plan is not None:
+            if (cond is not None and cond.shape[0] != latents.shape[0]) or any(f.shape[0] != latents.shape[0] for f in feats):
+                raise ValueError(f"controlnet_cond and adapter features must carry the latents' batch {latents.shape[0]}")
+            ehs, cond, feats = self._tile_operands(plan, latents.shape[2], latents.shape[3], ehs, cond, feats)
         keep = (ehs, lr, nz, cond, feats)  # noqa: F841  keep alive until the stream has consumed them
         t_lat, t_e = L.as_tensor(latents), L.as_tensor(ehs)
         t_lr = L.as_tensor(lr) if lr is not None else None
@@ -248,7 +366,8 @@ class Sampler:
         self._keep = keep
         return latents
 
-    def _run_guided(self, latents, ehs_c, ehs_u, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, g, phi):
+    def _run_guided(self, latents, ehs_c, ehs_u, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, g, phi,
+                    plan=None):
         B, dev = latents.shape[0], latents.device
         if int(np.prod(latents.shape[1:])) % 4:
             raise ValueError("guided sampling needs C*h*w of the latents to be a multiple of 4")
@@ -263,6 +382,8 @@ class Sampler:
         nz = step_noise.to(dev, torch.float32).contiguous() if step_noise is not None else None
         cond2 = torch.cat([controlnet_cond.to(dev)] * 2).contiguous() if controlnet_cond is not None else None
         feats2 = [torch.cat([f.to(dev)] * 2).contiguous() for f in (adapter_features or [])]
+        if plan is not None:  # the 2B rows, then their tiles: row (b, ti) of the forward is b * T + ti
+            ehs2, cond2, feats2 = self._tile_operands(plan, latents.shape[2], latents.shape[3], ehs2, cond2, feats2)
         keep = (ehs2, lr, nz, cond2, feats2)
         t_lat, t_e = L.as_tensor(latents), L.as_tensor(ehs2)
         t_lr = L.as_tensor(lr) if lr is not None else None
@@ -279,8 +400,8 @@ class Sampler:
 
 @torch.no_grad()
 def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weight_dtype, accelerator, fixed_embeds,
-                   num_inference_steps=20, adapter=None, solver=None, cache_interval=1, cache_depth=1, guidance_scale=1.0,
-                   guidance_rescale=0.0, uncond_embeds=None):
+                   num_inference_steps=20, adapter=None, solver=None, cache_interval=1, cache_depth=1, tile=None, tile_overlap=0,
+                   tile_window="gaussian", guidance_scale=1.0, guidance_rescale=0.0, uncond_embeds=None):
     """Drop-in for the reference's validation sampler (res_srdiff.py:35-105): same inputs, same PIL panel out.
     The timestep loop is one fused sampler call; the per-step noise is drawn up front from the same global RNG
     stream, in the same order, as the reference's per-step ``torch.randn_like`` calls.  ``adapter`` (a T2I-Adapter):
@@ -289,7 +410,8 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     guidance as in ``Sampler.run``; the defaults leave the result unchanged.  ``solver`` ("unipc" / "dpmsolver++"): sample the panel
     with that LR-anchored deterministic multistep solver (the scheduler's solver options when it carries any) instead of the
     reference's stochastic step; no step noise is drawn then.  ``None``: the reference's sampler.  ``cache_interval`` /
-    ``cache_depth``: the feature cache of ``Sampler.set_cache``; the defaults leave the panel unchanged."""
+    ``cache_depth``: the feature cache of ``Sampler.set_cache``; the defaults leave the panel unchanged.  ``tile`` / ``tile_overlap`` /
+    ``tile_window``: tiled sampling as in ``Sampler.set_tiles`` (latent pixels); the defaults leave the panel unchanged."""
     from PIL import Image
 
     if solver is not None:
@@ -316,6 +438,8 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     sampler = Sampler(unet, noise_scheduler, controlnet, kind=solver if solver is not None else "resshift")
     if cache_interval != 1 or cache_depth != 1:
         sampler.set_cache(cache_interval, cache_depth)
+    if tile is not None:
+        sampler.set_tiles(tile, tile_overlap, tile_window)
     feats = None
     if adapter is not None:
         cond = control_image if tuple(control_image.shape[-2:]) == tuple(lr_raw.shape[-2:]) else \

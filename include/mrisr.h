@@ -91,6 +91,14 @@ int mrisr_model_set_lora_scale(mrisr_model* m, float scale); /* lora_alpha / r *
  * <module>.lora_magnitude_vector.default.weight [out_features] too, and computes y = b + m / ||W + s B A||_row o (x W^T + s (x A^T) B^T).
  * Linear targets of a UNet handle only; not with the fp8 modes.  Call before mrisr_model_finalize. */
 int mrisr_model_set_dora(mrisr_model* m, int use_dora);
+/* Perturbed-attention guidance state of a UNet handle (contract: "perturbed-attention guidance" below).  Until it is cleared, every
+ * mrisr_unet_forward treats samples first_sample .. first_sample + n_samples - 1 of its batch as PERTURBED: in transformer block i (forward
+ * order: down blocks, mid, up blocks; i < mrisr_model_num_transformer_blocks) with bit i of block_mask set, their attn1 returns
+ * to_out.0(to_v(norm1(h))) - the attention map is the identity.  The other samples, attn2, the feed-forward and the other blocks are
+ * untouched.  n_samples == 0 or block_mask == 0 clears the state.  Refused: a ControlNet handle, a UNet built with fp8_attention, a mask
+ * bit beyond the last block; a forward whose batch does not hold the range, a cached forward (mrisr_unet_forward_cached) and a training
+ * step are refused while the state is set.  The workspace is planned per state.  mrisr_sampler_run_pag sets and clears it itself. */
+int mrisr_model_set_pag(mrisr_model* m, uint32_t block_mask, int first_sample, int n_samples);
 /* Re-lays weights out for the kernels (NHWC filter order, fused QKV, GEGLU interleave, LoRA tails, ...).
  * Must be called after the last set_param and before forward; may be called again after updating params. */
 int mrisr_model_finalize(mrisr_model* m, void* stream);
@@ -109,6 +117,8 @@ int mrisr_unet_forward(mrisr_model* m, const mrisr_tensor* sample, const mrisr_t
 /* Pre-compute the cross-attention K/V projections of a fixed prompt embedding (timestep-invariant). */
 int mrisr_model_set_context(mrisr_model* m, const mrisr_tensor* ehs, int latent_h, int latent_w, void* stream);
 int mrisr_model_num_skips(const mrisr_model* m);
+/* transformer blocks of the handle, in forward order: down_blocks.i.attentions.j, mid_block.attentions.0, up_blocks.i.attentions.j (16 for SD-1.5) */
+int mrisr_model_num_transformer_blocks(const mrisr_model* m);
 /* shape {B,C,H,W} of skip k for a latent of h x w (k == num_skips -> the mid block tensor) */
 int mrisr_model_skip_shape(const mrisr_model* m, int k, int B, int h, int w, int64_t shape[4]);
 
@@ -222,6 +232,35 @@ int mrisr_sampler_set_guidance(mrisr_sampler* s, float guidance_scale, float gui
 int mrisr_sampler_run_guided(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents,
                              const mrisr_tensor* step_noise, const mrisr_tensor* ehs2, const mrisr_tensor* cond2,
                              const mrisr_tensor* intrablock2, int n_intrablock, int use_graph, void* stream);
+
+/* ---- perturbed-attention guidance (PAG; Ahn et al. 2024, "Self-Rectifying Diffusion Sampling with Perturbed-Attention Guidance") -----
+ * Off unless mrisr_sampler_run_pag is called.  PAG needs no unconditional prompt: every step also predicts eps_p, the network's output
+ * with the self-attention map of the applied blocks replaced by the identity (mrisr_model_set_pag: attn1 = to_out.0(to_v(norm1(h))), the
+ * LoRA / DoRA terms of to_v and to_out.0 included; attn2, the feed-forward, the other blocks, ControlNet residuals and adapter features are
+ * the conditional ones), and extrapolates away from it.  With s = pag_scale >= 0, g = guidance_scale, phi = guidance_rescale:
+ *     PAG alone      (with_cfg == 0, forward of 2B rows [eps_p; eps_c]):         e = eps_c + s (eps_c - eps_p)
+ *     PAG with CFG   (with_cfg != 0, forward of 3B rows [eps_p; eps_u; eps_c]):  e = eps_u + g (eps_c - eps_u) + s (eps_c - eps_p)
+ *     phi > 0:  e = e (phi std_b(eps_c) / std_b(e) + (1 - phi))     exactly the rule of mrisr_sampler_set_guidance (unbiased, per sample,
+ *                                                                    a sample with std_b(e) == 0 is left as it is)
+ *     x = the sampler's own DDIM / Res-SRDiff / DDPM / UniPC / DPM-Solver++ update of x with e
+ * Row order: PERTURBED rows first, CONDITIONAL rows last.  PAG alone is therefore the guided step with eps_0 := eps_p and g := 1 + s; the
+ * unperturbed samples are one contiguous range (one attention launch per applied block); with tiles, sample b owns tile rows b T .. b T + T - 1
+ * and the perturbed range is [0, B T).  Perturbed rows of ehsK carry the CONDITIONAL context; condK / intrablockK repeat the [B] operands K
+ * times.  block_mask: bit i = transformer block i in forward order (mrisr_model_num_transformer_blocks).  g and phi are those of
+ * mrisr_sampler_set_guidance (g is ignored by PAG alone).  s is a launch constant: no per-step (adaptive) scale.  Refused before any launch:
+ * s < 0 or not finite, s > 0 with an empty mask, a mask bit beyond the last block, a run with an empty mask, a feature cache with
+ * interval > 1, a UNet built with fp8_attention, C*h*w of the latents not a multiple of 4.  During the run the UNet handle carries the pag
+ * state of samples [0, B T); it is cleared when the call returns, also on an error.  The step graphs are keyed on (K, block_mask, s): a
+ * change captures again, and mrisr_sampler_run / _run_guided keep their graphs' keys.  s == 0 is valid here and yields eps_c at the cost of
+ * the larger forward; callers that want "off" call mrisr_sampler_run / _run_guided. */
+int mrisr_sampler_set_pag(mrisr_sampler* s, uint32_t block_mask, float pag_scale);
+/* As mrisr_sampler_run, with ehsK [K B, L, D], condK [K B, 3, 8h, 8w] or NULL and every intrablockK feature [K B, ...], K = 2 (with_cfg == 0)
+ * or 3; tiled: K B T rows, sample-major.  ControlNet runs on all K B rows, unperturbed. */
+int mrisr_sampler_run_pag(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents, const mrisr_tensor* step_noise,
+                          const mrisr_tensor* ehsK, const mrisr_tensor* condK, const mrisr_tensor* intrablockK, int n_intrablock, int with_cfg,
+                          int use_graph, void* stream);
+/* step graphs this sampler has captured so far (a run whose key matches the previous one captures nothing) */
+int mrisr_sampler_num_captures(const mrisr_sampler* s);
 
 /* ---- tiled sampling (MultiDiffusion, Bar-Tal et al. 2023, with the Gaussian weights of Mixture of Diffusers, Jimenez 2023) -------
  * The latent canvas [NB, C, H, W] is cut into overlapping tiles, the forward runs on the tile batch [NB*T, C, t_h, t_w] and the tile
@@ -572,6 +611,11 @@ int mrisr_op_dora_scale(int dtype, const float* W, const float* A, const float* 
  * row c: bias is indexed like the columns, gm and mag (f32 [C]) in raw order.  No atomics: the bits repeat from launch to launch */
 int mrisr_op_dora_mag_grad(int dtype, const void* P, int ldp, const void* Y, int ldy, const void* R, int ldr, const float* bias, const float* mag,
                            float* gm, int M, int C, int geglu_half, void* stream);
+/* identity attention (the perturbed rows of mrisr_model_set_pag): vt [B*H][dpad][npad] (T, head-major v^T) -> token rows out [B][N][H*hd]
+ * for samples first_sample .. first_sample + n_samples - 1: out[b][t][h*hd + d] = vt[b*H + h][d][t].  A copy: pad columns never reach out, rows
+ * of other samples are not written.  Refused before any launch: null or misaligned pointers, npad < N, dpad < hd, a range outside B. */
+int mrisr_op_attn_identity(int dtype, const void* vt, void* out, int B, int H, int N, int hd, int npad, int dpad, int first_sample, int n_samples,
+                           void* stream);
 /* dst[z][c][r] = src[z][r][c] for r < r_valid, 0 for r_valid <= r < R (T; pitches ld_src >= C, ld_dst >= R; batch strides in elements) */
 int mrisr_op_transpose(int dtype, const void* src, void* dst, int R, int C, int ld_src, int ld_dst, int64_t bs_src, int64_t bs_dst,
                        int batch, int r_valid, void* stream);
@@ -612,6 +656,17 @@ int mrisr_op_conv3x3_lora(const mrisr_tensor* x, const float* w_oihw_dev, const 
 int mrisr_op_guided_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const mrisr_tensor* eps2, const mrisr_tensor* lr,
                          const mrisr_tensor* noise, const float* coef_row_host, float clip, float guidance_scale,
                          float guidance_rescale, void* stream);
+
+/* the three-way fused step of mrisr_sampler_run_pag (with_cfg) alone: as mrisr_op_guided_step with x3 [3B] (receives the new x in all three
+ * thirds) and eps3 [3B] = [eps_p; eps_u; eps_c]; pag_scale == 0 gives mrisr_op_guided_step's result on [eps_u; eps_c] */
+int mrisr_op_pag_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x3, const mrisr_tensor* eps3, const mrisr_tensor* lr,
+                      const mrisr_tensor* noise, const float* coef_row_host, float clip, float guidance_scale, float pag_scale,
+                      float guidance_rescale, void* stream);
+
+/* the same for the multistep kinds: mrisr_op_multistep_step's guided form (hist, xc, row_host, solver_order, slot as there) with x3 / eps3 [3B] */
+int mrisr_op_pag_multistep_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x3, const mrisr_tensor* eps3, const mrisr_tensor* lr,
+                                mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot, float guidance_scale,
+                                float pag_scale, float guidance_rescale, void* stream);
 
 /* the fused multistep step (MRISR_STEP_UNIPC / MRISR_STEP_DPMSOLVERPP) alone: x [B,C,h,w] f32 (in place), eps [B,C,h,w], lr or NULL,
  * hist [solver_order][B,C,h,w] f32 (x0 predictions; slot `slot` % solver_order is written, the prediction k steps back is read from

@@ -65,6 +65,23 @@ int mrisr_model_set_dora(mrisr_model* m, int use_dora) {
     m->finalized = false;
     return 0;
 }
+int mrisr_model_set_pag(mrisr_model* m, unsigned block_mask, int first_sample, int n_samples) {
+    MRISR_REQUIRE(m, "null handle");
+    if (n_samples == 0 || block_mask == 0) {  // off
+        MRISR_REQUIRE(n_samples >= 0 && first_sample >= 0, "pag: the sample range must not be negative");
+        m->pag = PagState();
+        return 0;
+    }
+    MRISR_REQUIRE(!m->is_controlnet, "pag: perturbed-attention guidance belongs to the UNet, not to a ControlNet handle");
+    MRISR_REQUIRE(!m->cfg.fp8_attention, "pag: not supported on a UNet built with fp8_attention");
+    MRISR_REQUIRE(!m->keep, "pag: a training forward is being recorded");
+    MRISR_REQUIRE(first_sample >= 0 && n_samples > 0, "pag: the sample range must not be negative");
+    const int nb = m->num_transformer_blocks();
+    MRISR_REQUIRE(nb >= 32 || (block_mask >> nb) == 0, "pag: block_mask selects blocks the UNet does not have (mrisr_model_num_transformer_blocks)");
+    m->pag.mask = block_mask; m->pag.first = first_sample; m->pag.count = n_samples;
+    return 0;
+}
+int mrisr_model_num_transformer_blocks(const mrisr_model* m) { return m ? m->num_transformer_blocks() : 0; }
 int mrisr_model_finalize(mrisr_model* m, void* stream) {
     API_BEGIN
     MRISR_REQUIRE(m, "null handle");
@@ -284,6 +301,9 @@ struct mrisr_sampler {
     int kind = 0, n_steps = 0, first = 0, last = 0;
     float clip = 0.f;
     float guidance_scale = 1.f, guidance_rescale = 0.f;  // classifier-free guidance of mrisr_sampler_run_guided
+    unsigned pag_mask = 0;  // perturbed-attention guidance of mrisr_sampler_run_pag: the applied transformer blocks and the scale
+    float pag_scale = 0.f;
+    int n_captures = 0;     // step graphs captured so far (mrisr_sampler_num_captures)
     std::vector<float> sigma;  // host copy of each step's noise coefficient (which steps read a step_noise slab)
     DevBuf d_ts, d_coef, d_step, d_curt, d_eps;
     // multistep kinds: solver options, the clamped alphas_cumprod on the grid (+ alphas_cumprod[0]), the host rows of the current range,
@@ -294,7 +314,7 @@ struct mrisr_sampler {
     DevBuf d_hist, d_xc;
     bool multistep() const { return kind > MRISR_STEP_DDPM; }
     void rebuild_rows() { if (multistep()) ms_rows = build_multistep_rows(kind, ms, ms_abar, n_steps, first); }
-    DevBuf d_x2;  // guided runs: the [2B] f32 latents the forwards read (both halves = the state; the guided step keeps them current)
+    DevBuf d_x2;  // guided / pag runs: the [K B] f32 latents the forwards read (every part = the state; the fused step keeps them current)
     DevBuf tp_unet, tp_cnet;  // per-run time-embedding tables [scratch | n_steps x tproj_total] (f32)
     std::vector<std::unique_ptr<DevBuf>> res_bufs;   // ControlNet -> UNet residuals (NHWC, compute dtype)
     std::vector<std::unique_ptr<DevBuf>> intra_bufs;  // adapter features converted once
@@ -473,12 +493,26 @@ int mrisr_sampler_set_guidance(mrisr_sampler* s, float guidance_scale, float gui
     return 0;
 }
 
-// the body of mrisr_sampler_run (guided = false: B rows everywhere) and mrisr_sampler_run_guided (the forwards see NB = 2B rows:
-// ehs / cond / intrablock carry 2B, the latents are read from the staging buffer; the state, the LR anchor and the noise stay [B])
+int mrisr_sampler_set_pag(mrisr_sampler* s, unsigned block_mask, float pag_scale) {
+    MRISR_REQUIRE(s, "null sampler");
+    MRISR_REQUIRE(std::isfinite(pag_scale) && pag_scale >= 0.f, "pag_scale must be finite and >= 0");
+    const int nb = s->unet->num_transformer_blocks();
+    MRISR_REQUIRE(nb >= 32 || (block_mask >> nb) == 0, "pag: block_mask selects blocks the UNet does not have (mrisr_model_num_transformer_blocks)");
+    MRISR_REQUIRE(pag_scale == 0.f || block_mask != 0, "pag: pag_scale > 0 needs at least one applied block in block_mask");
+    s->pag_mask = block_mask;  // both are part of the graph key of the next mrisr_sampler_run_pag
+    s->pag_scale = pag_scale;
+    return 0;
+}
+int mrisr_sampler_num_captures(const mrisr_sampler* s) { return s ? s->n_captures : 0; }
+
+// the body of mrisr_sampler_run (K = 1: B rows everywhere), mrisr_sampler_run_guided (K = 2) and mrisr_sampler_run_pag (pag: K = 2 or 3):
+// the forwards see NB = K B rows - ehs / cond / intrablock carry K B, the latents are read from the staging buffer; the state, the LR
+// anchor and the noise stay [B]
 static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents,
                             const mrisr_tensor* step_noise, const mrisr_tensor* ehs, const mrisr_tensor* cond,
-                            const mrisr_tensor* intrablock, int n_intrablock, int use_graph, void* stream, bool guided) {
+                            const mrisr_tensor* intrablock, int n_intrablock, int use_graph, void* stream, int K, bool pag = false) {
     API_BEGIN
+    const bool guided = K > 1;
     MRISR_REQUIRE(s && latents && ehs, "null argument");
     MRISR_REQUIRE(latents->ndim == 4 && latents->dtype == MRISR_F32 && latents->layout == MRISR_NCHW, "latents: f32 NCHW");
     MRISR_REQUIRE(s->kind != MRISR_STEP_RESSHIFT || lr_latents, "Res-SRDiff needs the LR anchor latents");
@@ -486,12 +520,19 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
     MRISR_REQUIRE(!s->cnet || cond, "ControlNet needs the condition image");
     const bool cached = s->cache_interval > 1;
     MRISR_REQUIRE(!cached || !s->cnet, "a feature cache together with a ControlNet is not supported");
+    if (pag) {
+        MRISR_REQUIRE(K == 2 || K == 3, "pag run: the forward has 2B rows (pag alone) or 3B rows (with classifier-free guidance)");
+        MRISR_REQUIRE(s->pag_mask != 0, "pag run: no applied block (mrisr_sampler_set_pag)");
+        MRISR_REQUIRE(!cached, "pag run: a feature cache with interval > 1 is not supported (the shallow pass skips the blocks pag perturbs)");
+        MRISR_REQUIRE(!s->unet->cfg.fp8_attention, "pag run: not supported on a UNet built with fp8_attention");
+        MRISR_REQUIRE(!s->unet->keep, "pag run: a training forward is being recorded");
+    }
     hipStream_t user = (hipStream_t)stream;
     hipStream_t st = user;
     Model& U = *s->unet;
     const int B = (int)latents->shape[0], h = (int)latents->shape[2], w = (int)latents->shape[3];
     const int L = (int)ehs->shape[1];
-    const int NB = guided ? 2 * B : B;  // rows of every forward (of the canvas; a tiled run multiplies them by T)
+    const int NB = K * B;  // rows of every forward (of the canvas; a tiled run multiplies them by T)
     const long long per = (long long)latents->shape[1] * h * w;
     const long long n = (long long)B * per;
     const int cdt = U.cfg.compute_dtype;
@@ -533,13 +574,16 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
                       "encoder_hidden_states must be [B, L, cross_attention_dim] with the latents' batch");
     else
         MRISR_REQUIRE(ehs->ndim == 3 && ehs->shape[0] == NB && ehs->shape[2] == U.cfg.cross_attention_dim,
-                      "guided run: encoder_hidden_states must be [2B, L, cross_attention_dim]: B unconditional rows, then B conditional rows");
-    if (guided) MRISR_REQUIRE(B > 0 && per % 4 == 0, "guided run: C*h*w of the latents must be a multiple of 4");
+                      pag ? "pag run: encoder_hidden_states must be [K B, L, cross_attention_dim]: B perturbed rows first, B conditional rows last"
+                          : "guided run: encoder_hidden_states must be [2B, L, cross_attention_dim]: B unconditional rows, then B conditional rows");
+    if (guided) MRISR_REQUIRE(B > 0 && per % 4 == 0, pag ? "pag run: C*h*w of the latents must be a multiple of 4"
+                                                         : "guided run: C*h*w of the latents must be a multiple of 4");
     if (s->multistep()) MRISR_REQUIRE(B > 0 && per % 4 == 0, "multistep solvers: C*h*w of the latents must be a multiple of 4");
     if (lr_latents) MRISR_REQUIRE(lr_latents->dtype == MRISR_F32 && numel(lr_latents) == n, "lr_latents: f32, same shape as latents");
     if (cond && !tiled)
         MRISR_REQUIRE(cond->ndim == 4 && cond->shape[0] == NB && cond->shape[2] == 8 * h && cond->shape[3] == 8 * w,
-                      guided ? "guided run: controlnet_cond must be [2B, C, 8h, 8w] (the [B] images twice)"
+                      pag ? "pag run: controlnet_cond must be [K B, C, 8h, 8w] (the [B] images K times)"
+                      : guided ? "guided run: controlnet_cond must be [2B, C, 8h, 8w] (the [B] images twice)"
                              : "controlnet_cond must be [B, C, 8h, 8w] with the latents' batch");
     {
         int need = 0;  // slabs read: one per step, indexed by the step's position in the schedule, when its sigma != 0
@@ -553,7 +597,8 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
     }
     for (int i = 0; i < n_intrablock && !tiled; ++i)
         MRISR_REQUIRE(intrablock[i].ndim == 4 && intrablock[i].shape[0] == NB,
-                      guided ? "guided run: adapter features must be [2B, ...] (the [B] features twice)"
+                      pag ? "pag run: adapter features must be [K B, ...] (the [B] features K times)"
+                      : guided ? "guided run: adapter features must be [2B, ...] (the [B] features twice)"
                              : "adapter features must carry the latents' batch");
 
     if (use_graph && user == nullptr) {
@@ -568,6 +613,17 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
         MRISR_CHECK_HIP(hipStreamWaitEvent(st, s->ev_in, 0));
     }
 
+    // perturbed rows first: samples [0, B) of the forward, [0, B T) of a tiled one.  Set before the workspace is planned (the plan and
+    // its key see it), cleared when this call returns, also on an error path: plain forwards on the handle stay unperturbed
+    struct PagGuard {
+        Model* m = nullptr;
+        ~PagGuard() { if (m) m->pag = PagState(); }
+    } pguard;
+    if (pag) {
+        MRISR_REQUIRE(!U.pag.on(), "pag run: the UNet handle already carries a pag state (mrisr_model_set_pag); clear it first");
+        pguard.m = &U;
+        U.pag.mask = s->pag_mask; U.pag.first = 0; U.pag.count = B * T;
+    }
     // ---- one-time (per run) timestep-invariant work: context projections, condition embedding, features ----
     TRY(gemm_prepare());
     TRY(U.set_context(ehs, FB, fh, fw, st));
@@ -627,10 +683,10 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
         fc.p = s->d_cache.p;
     }
     if (guided) {
-        // [x; x] once per run; from then on the guided step itself writes every new state to both halves
-        TRY(s->d_x2.reserve((size_t)2 * n * sizeof(float), false));
-        MRISR_CHECK_HIP(hipMemcpyAsync(s->d_x2.p, latents->data, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
-        MRISR_CHECK_HIP(hipMemcpyAsync(static_cast<float*>(s->d_x2.p) + n, latents->data, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        // [x; x] ([x; x; x]) once per run; from then on the fused step itself writes every new state to every part
+        TRY(s->d_x2.reserve((size_t)K * n * sizeof(float), false));
+        for (int k = 0; k < K; ++k)
+            MRISR_CHECK_HIP(hipMemcpyAsync(static_cast<float*>(s->d_x2.p) + (size_t)k * n, latents->data, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     // the time embedding of every step of this run, once (it depends on the timestep only): sinusoid -> MLP -> the 22 per-resnet projections for
     // all rows at once instead of three GEMVs over 50 MB of weights in every step.  MRISR_TEMB_TABLE=0 / mrisr_debug_temb_table(0): per step.
@@ -693,7 +749,17 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
         TRY(U.forward_unet(&xin, &tt, nullptr, s->cnet ? down_t.data() : nullptr, ns, s->cnet ? &mid_t : nullptr,
                            intra.data(), n_intrablock, &eps_t, st, cached ? &fc : nullptr));
         if (tiled) TRY(launch_tile_blend(static_cast<const float*>(s->d_et.p), static_cast<float*>(s->d_eps.p), tg, NB, Cl, st));
-        if (guided)
+        if (K == 3)
+            TRY(launch_pag_step(s->kind, (float*)latents->data, (float*)s->d_x2.p, (const float*)s->d_eps.p,
+                                lr_latents ? (const float*)lr_latents->data : nullptr, step_noise ? (const float*)step_noise->data : nullptr,
+                                (const float*)s->d_coef.p, step, s->clip, s->guidance_scale, s->pag_scale, s->guidance_rescale, B, per, st, hist, xc,
+                                s->ms.order));
+        else if (pag)  // [eps_p; eps_c]: the guided step with eps_0 := eps_p and g := 1 + s
+            TRY(launch_guided_step(s->kind, (float*)latents->data, (float*)s->d_x2.p, (const float*)s->d_eps.p,
+                                   lr_latents ? (const float*)lr_latents->data : nullptr, step_noise ? (const float*)step_noise->data : nullptr,
+                                   (const float*)s->d_coef.p, step, s->clip, 1.f + s->pag_scale, s->guidance_rescale, B, per, st, hist, xc,
+                                   s->ms.order));
+        else if (guided)
             TRY(launch_guided_step(s->kind, (float*)latents->data, (float*)s->d_x2.p, (const float*)s->d_eps.p,
                                    lr_latents ? (const float*)lr_latents->data : nullptr, step_noise ? (const float*)step_noise->data : nullptr,
                                    (const float*)s->d_coef.p, step, s->clip, s->guidance_scale, s->guidance_rescale, B, per, st, hist, xc,
@@ -733,6 +799,10 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
                 snprintf(kb, sizeof(kb), ",G%p,%a,%a", s->d_x2.p, (double)s->guidance_scale, (double)s->guidance_rescale);
                 key += kb;
             }
+            if (pag) {  // the row count, the applied blocks (also in the UNet's workspace generation) and the scale the step takes by value
+                snprintf(kb, sizeof(kb), ",P%d,%x,%a", K, s->pag_mask, (double)s->pag_scale);
+                key += kb;
+            }
             if (s->multistep()) {  // the ring, the corrected state and the solver order the step takes by value; the other options live in the rows
                 snprintf(kb, sizeof(kb), ",M%p,%p,%d,%d,%d", (void*)hist, (void*)xc, s->ms.order, s->ms.final_zero, s->ms.lower_order_final);
                 key += kb;
@@ -760,6 +830,7 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
                 MRISR_CHECK_HIP(e);
                 MRISR_CHECK_HIP(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
                 (void)hipGraphDestroy(graph);
+                ++s->n_captures;
                 return 0;
             };
             TRY(capture(cached ? CACHE_STORE : CACHE_NONE, &s->exec));
@@ -779,12 +850,49 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
 int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents,
                       const mrisr_tensor* step_noise, const mrisr_tensor* ehs, const mrisr_tensor* cond,
                       const mrisr_tensor* intrablock, int n_intrablock, int use_graph, void* stream) {
-    return sampler_run_impl(s, latents, lr_latents, step_noise, ehs, cond, intrablock, n_intrablock, use_graph, stream, false);
+    return sampler_run_impl(s, latents, lr_latents, step_noise, ehs, cond, intrablock, n_intrablock, use_graph, stream, 1);
 }
 int mrisr_sampler_run_guided(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents,
                              const mrisr_tensor* step_noise, const mrisr_tensor* ehs2, const mrisr_tensor* cond2,
                              const mrisr_tensor* intrablock2, int n_intrablock, int use_graph, void* stream) {
-    return sampler_run_impl(s, latents, lr_latents, step_noise, ehs2, cond2, intrablock2, n_intrablock, use_graph, stream, true);
+    return sampler_run_impl(s, latents, lr_latents, step_noise, ehs2, cond2, intrablock2, n_intrablock, use_graph, stream, 2);
+}
+int mrisr_sampler_run_pag(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents, const mrisr_tensor* step_noise,
+                          const mrisr_tensor* ehsK, const mrisr_tensor* condK, const mrisr_tensor* intrablockK, int n_intrablock, int with_cfg,
+                          int use_graph, void* stream) {
+    return sampler_run_impl(s, latents, lr_latents, step_noise, ehsK, condK, intrablockK, n_intrablock, use_graph, stream, with_cfg ? 3 : 2, true);
+}
+
+// the three-way step alone, on caller buffers (parity test): as mrisr_op_guided_step with x3 / eps3 [3B] = [perturbed; uncond; cond]
+int mrisr_op_pag_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x3, const mrisr_tensor* eps3, const mrisr_tensor* lr,
+                      const mrisr_tensor* noise, const float* coef_row_host, float clip, float guidance_scale, float pag_scale,
+                      float guidance_rescale, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(x && x3 && eps3 && coef_row_host, "pag step: null argument");
+    MRISR_REQUIRE(step_kind >= MRISR_STEP_DDIM && step_kind <= MRISR_STEP_DDPM, "pag step: unknown step kind");
+    auto numel = [](const mrisr_tensor* t) { long long k = 1; for (int i = 0; i < t->ndim; ++i) k *= t->shape[i]; return k; };
+    MRISR_REQUIRE(x->ndim == 4 && x->dtype == MRISR_F32 && x->shape[0] > 0, "pag step: x must be f32 [B, C, h, w]");
+    const int B = (int)x->shape[0];
+    const long long n = numel(x), per = n / B;
+    MRISR_REQUIRE(x3->dtype == MRISR_F32 && numel(x3) == 3 * n, "pag step: the staging buffer must be f32 [3B, C, h, w]");
+    MRISR_REQUIRE(eps3->dtype == MRISR_F32 && numel(eps3) == 3 * n, "pag step: eps3 must be f32 [3B, C, h, w]");
+    if (lr) MRISR_REQUIRE(lr->dtype == MRISR_F32 && numel(lr) == n, "pag step: lr must be f32 [B, C, h, w]");
+    if (noise) MRISR_REQUIRE(noise->dtype == MRISR_F32 && numel(noise) == n, "pag step: noise must be one f32 [B, C, h, w] slab");
+    hipStream_t st = (hipStream_t)stream;
+    const int width = step_kind == MRISR_STEP_DDIM ? 2 : (step_kind == MRISR_STEP_RESSHIFT ? 4 : 5);
+    float row[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    std::copy(coef_row_host, coef_row_host + width, row);
+    DevBuf d_row, d_step;
+    TRY(d_row.reserve(sizeof(row), false));
+    TRY(d_step.reserve(16, true));  // zeroed: step 0 = the one row, the one noise slab
+    MRISR_CHECK_HIP(hipMemcpyAsync(d_row.p, row, sizeof(row), hipMemcpyHostToDevice, st));
+    MRISR_CHECK_HIP(hipMemsetAsync(d_step.p, 0, 16, st));
+    TRY(launch_pag_step(step_kind, (float*)x->data, (float*)x3->data, (const float*)eps3->data, lr ? (const float*)lr->data : nullptr,
+                        noise ? (const float*)noise->data : nullptr, (const float*)d_row.p, (const int*)d_step.p, clip, guidance_scale, pag_scale,
+                        guidance_rescale, B, per, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
 }
 
 // the guided step alone, on caller buffers (parity test): coef_row_host is this step kind's coefficient row (2 / 4 / 5 floats)
@@ -814,6 +922,41 @@ int mrisr_op_guided_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const
     TRY(launch_guided_step(step_kind, (float*)x->data, (float*)x2->data, (const float*)eps2->data, lr ? (const float*)lr->data : nullptr,
                            noise ? (const float*)noise->data : nullptr, (const float*)d_row.p, (const int*)d_step.p, clip,
                            guidance_scale, guidance_rescale, B, per, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
+// the three-way step of the multistep kinds alone, on caller buffers (parity test): mrisr_op_multistep_step's guided form with x3 / eps3 [3B]
+int mrisr_op_pag_multistep_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x3, const mrisr_tensor* eps3, const mrisr_tensor* lr,
+                                mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot, float guidance_scale,
+                                float pag_scale, float guidance_rescale, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(x && x3 && eps3 && hist && row_host, "pag multistep step: null argument");
+    MRISR_REQUIRE(step_kind == MRISR_STEP_UNIPC || step_kind == MRISR_STEP_DPMSOLVERPP, "pag multistep step: UniPC or DPM-Solver++");
+    MRISR_REQUIRE(solver_order >= 1 && solver_order <= 3 && slot >= 0 && slot < 1024, "pag multistep step: solver order 1..3, slot 0..1023");
+    MRISR_REQUIRE((step_kind == MRISR_STEP_UNIPC) == (xc != nullptr), "pag multistep step: the corrected-state buffer belongs to UniPC");
+    auto numel = [](const mrisr_tensor* t) { long long k = 1; for (int i = 0; i < t->ndim; ++i) k *= t->shape[i]; return k; };
+    MRISR_REQUIRE(x->ndim == 4 && x->dtype == MRISR_F32 && x->shape[0] > 0, "pag multistep step: x must be f32 [B, C, h, w]");
+    const int B = (int)x->shape[0];
+    const long long n = numel(x), per = n / B;
+    MRISR_REQUIRE(per % 4 == 0, "pag multistep step: C*h*w must be a multiple of 4");
+    MRISR_REQUIRE(eps3->dtype == MRISR_F32 && numel(eps3) == 3 * n, "pag multistep step: eps3 must be f32 [3B, C, h, w]");
+    MRISR_REQUIRE(x3->dtype == MRISR_F32 && numel(x3) == 3 * n, "pag multistep step: the staging buffer must be f32 [3B, C, h, w]");
+    if (lr) MRISR_REQUIRE(lr->dtype == MRISR_F32 && numel(lr) == n, "pag multistep step: lr must be f32 [B, C, h, w]");
+    MRISR_REQUIRE(hist->dtype == MRISR_F32 && numel(hist) == (long long)solver_order * n, "pag multistep step: hist must be f32 [order, B, C, h, w]");
+    if (xc) MRISR_REQUIRE(xc->dtype == MRISR_F32 && numel(xc) == n, "pag multistep step: xc must be f32 [B, C, h, w]");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<float> rows((size_t)(slot + 1) * 16, 0.f);
+    std::copy(row_host, row_host + 16, rows.begin() + (size_t)slot * 16);
+    DevBuf d_rows, d_step;
+    TRY(d_rows.reserve(sizeof(float) * rows.size(), false));
+    TRY(d_step.reserve(16, true));
+    MRISR_CHECK_HIP(hipMemcpyAsync(d_rows.p, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice, st));
+    MRISR_CHECK_HIP(hipMemcpyAsync(d_step.p, &slot, sizeof(int), hipMemcpyHostToDevice, st));
+    TRY(launch_pag_step(step_kind, (float*)x->data, (float*)x3->data, (const float*)eps3->data, lr ? (const float*)lr->data : nullptr, nullptr,
+                        (const float*)d_rows.p, (const int*)d_step.p, 0.f, guidance_scale, pag_scale, guidance_rescale, B, per, st,
+                        (float*)hist->data, xc ? (float*)xc->data : nullptr, solver_order));
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
     API_END

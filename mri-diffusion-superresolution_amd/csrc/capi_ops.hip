@@ -972,6 +972,18 @@ int mrisr_op_transpose(int dtype, const void* src, void* dst, int R, int C, int 
     API_END
 }
 
+int mrisr_op_attn_identity(int dtype, const void* vt, void* out, int B, int H, int N, int hd, int npad, int dpad, int first_sample, int n_samples,
+                           void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    hipStream_t st = (hipStream_t)stream;
+    // (the launcher refuses null / misaligned pointers, npad < N, dpad < hd and a range outside B before it launches)
+    TRY(BWD_DISPATCH(dtype, launch_attn_identity, vt, out, B, H, N, hd, npad, dpad, first_sample, n_samples, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
 int mrisr_op_softmax_bwd(int dtype, const void* p, const float* dp, void* ds, int ld, int64_t rows, int nk, float scale, void* stream) {
     API_BEGIN
     TRY(bwd_dtype_ok(dtype));

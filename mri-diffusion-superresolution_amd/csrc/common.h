@@ -300,6 +300,10 @@ template <typename T> int launch_geglu_bwd(const void* pre, const void* dout, vo
 template <typename T> int launch_geglu_fwd(const void* pre, void* out, long long M, int half, hipStream_t st);
 template <typename T>
 int launch_rows_to_heads(const void* x, int ldx, int col_off, void* dst, int B, int N, int H, int hd, int npad, int dpad, hipStream_t st);
+// identity attention (pag.hip): the reverse of the layout above for samples [b0, b0 + nb) - vt [B*H][dpad][npad] -> token rows
+// out [B][N][H*hd]; rows of the other samples are not touched
+template <typename T>
+int launch_attn_identity(const void* vt, void* out, int B, int H, int N, int hd, int npad, int dpad, int b0, int nb, hipStream_t st);
 template <typename T>
 int launch_softmax_bwd(const void* p, const float* dp, void* ds, int ld, long long rows, int nk, float scale, hipStream_t st);
 template <typename T>
@@ -511,6 +515,12 @@ int launch_advance_step(int* step_idx, hipStream_t st);
 int launch_guided_step(int kind, float* x, float* x2, const float* eps2, const float* lr, const float* noise, const float* coef_table,
                        const int* step_idx, float clip, float g, float phi, int B, long long per, hipStream_t st, float* hist = nullptr,
                        float* xc = nullptr, int order = 0);
+//   perturbed-attention guidance with classifier-free guidance: eps3 = [perturbed rows; uncond rows; cond rows] of a [3B] forward ->
+//   e = eps_u + g (eps_c - eps_u) + s (eps_c - eps_p), rescaled against eps_c as above -> the same update; the new x goes to x [B] and to
+//   all three thirds of the staging buffer x3 [3B].  (PAG alone is launch_guided_step on [eps_p; eps_c] with g = 1 + s.)
+int launch_pag_step(int kind, float* x, float* x3, const float* eps3, const float* lr, const float* noise, const float* coef_table,
+                    const int* step_idx, float clip, float g, float s, float phi, int B, long long per, hipStream_t st, float* hist = nullptr,
+                    float* xc = nullptr, int order = 0);
 //   multistep step (MRISR_STEP_UNIPC / MRISR_STEP_DPMSOLVERPP): rows of 16 floats (misc.hip), hist = `order` slabs of n floats (the x0
 //   predictions, slot step % order), xc = the previous corrected state (UniPC) or nullptr; lr (or nullptr) anchors the state: the solver
 //   runs on x - lr.  n must be a multiple of 4.  The guided form is launch_guided_step with the same three buffers.

@@ -1051,17 +1051,22 @@ int launch_multistep_step(float* x, const float* eps, const float* lr, const flo
     return 0;
 }
 // the update of one float4 piece of a guided step with the guided prediction e: the step kinds above, or the multistep step
+// (third: the staging buffer of a [3B] forward has one more part to keep current - the three-way step below)
 __device__ __forceinline__ void guided_apply4(int kind, const StepRow& r, const float* msrow, const MsBuf& ms, int s, float clip, float* x,
-                                              float* x2, const float* lr, const float* noise, long long n, long long i, float4 e) {
+                                              float* x2, const float* lr, const float* noise, long long n, long long i, float4 e,
+                                              bool third = false) {
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 xv = reinterpret_cast<const float4*>(x)[i];
     const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
+    float4 v;
     if (msrow) {
-        store_x3(x, x2, n, i, multistep_value4(msrow, ms, s, n, i, xv, e, l));
+        v = multistep_value4(msrow, ms, s, n, i, xv, e, l);
     } else {
         const float4 nz = noise ? reinterpret_cast<const float4*>(noise)[i] : z4;
-        store_x3(x, x2, n, i, step_value4(kind, r, clip, xv, e, l, nz, noise != nullptr));
+        v = step_value4(kind, r, clip, xv, e, l, nz, noise != nullptr);
     }
+    store_x3(x, x2, n, i, v);
+    if (third) reinterpret_cast<float4*>(x2 + 2 * n)[i] = v;
 }
 
 __global__ __launch_bounds__(256) void guided_step_kernel(int kind, float* x, float* x2, const float* eps2, const float* lr,
@@ -1198,6 +1203,136 @@ int launch_guided_step(int kind, float* x, float* x2, const float* eps2, const f
             hipLaunchKernelGGL(guided_step_rescale_reread_kernel, dim3(B), dim3(GS_THREADS), 0, st, kind, x, x2, eps2, lr, noise,
                                coef_table, step_idx, clip, g, phi, B, (int)per, ms);
 #undef MRISR_GS
+    }
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+// ------------------------------------------------------------------------------------------------
+// three-way step (perturbed-attention guidance together with classifier-free guidance): the guided step above for the [3B] output
+// eps3 = [eps_p; eps_u; eps_c] (perturbed rows first, conditional rows last),
+//   e = eps_u + g (eps_c - eps_u) + s (eps_c - eps_p);   phi > 0: e *= phi std_b(eps_c) / std_b(e) + (1 - phi)
+// in the same three forms (grid-stride; one workgroup per sample with the rows in registers; re-reading), the same degenerate-sample
+// guard, the same update through guided_apply4 - and the new x to all three thirds of the staging buffer.  s == 0 is the guided step.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float4 pag_guide4(float4 ep, float4 eu, float4 ec, float g, float s) {
+    // explicit fused multiply-adds: the guided part is then the very operation guide4 compiles to in the guided step's kernels (one
+    // rounding), whatever the compiler would contract here, so that s == 0 reproduces their bits
+    const float4 e = make_float4(fmaf(g, ec.x - eu.x, eu.x), fmaf(g, ec.y - eu.y, eu.y), fmaf(g, ec.z - eu.z, eu.z), fmaf(g, ec.w - eu.w, eu.w));
+    return make_float4(fmaf(s, ec.x - ep.x, e.x), fmaf(s, ec.y - ep.y, e.y), fmaf(s, ec.z - ep.z, e.z), fmaf(s, ec.w - ep.w, e.w));
+}
+__global__ __launch_bounds__(256) void pag_step_kernel(int kind, float* x, float* x3, const float* eps3, const float* lr, const float* noise_base,
+                                                       const float* coef, const int* step, float clip, float g, float sp, long long n, MsBuf ms) {
+    const int s = *step;
+    const StepRow r = load_step_row(kind, coef, s);
+    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
+    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256) {
+        const float4 ep = reinterpret_cast<const float4*>(eps3)[i], eu = reinterpret_cast<const float4*>(eps3 + n)[i];
+        const float4 ec = reinterpret_cast<const float4*>(eps3 + 2 * n)[i];
+        guided_apply4(kind, r, msrow, ms, s, clip, x, x3, lr, noise, n, i, pag_guide4(ep, eu, ec, g, sp), true);
+    }
+}
+template <int ITEMS>
+__global__ __launch_bounds__(GS_THREADS) void pag_step_rescale_kernel(int kind, float* x, float* x3, const float* eps3, const float* lr,
+                                                                      const float* noise_base, const float* coef, const int* step, float clip,
+                                                                      float g, float sp, float phi, int B, int per, MsBuf ms) {
+    __shared__ float red[2 * GS_THREADS / 64];
+    const int s = *step;
+    const StepRow r = load_step_row(kind, coef, s);
+    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
+    const long long n = (long long)B * per;
+    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
+    const long long base4 = (long long)blockIdx.x * (per >> 2);
+    const int per4 = per >> 2;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 e[ITEMS], c[ITEMS];
+    float sc = 0.f, se = 0.f;
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int j = threadIdx.x + k * GS_THREADS;
+        e[k] = z4; c[k] = z4;
+        if (j < per4) {
+            const float4 ep = reinterpret_cast<const float4*>(eps3)[base4 + j], eu = reinterpret_cast<const float4*>(eps3 + n)[base4 + j];
+            c[k] = reinterpret_cast<const float4*>(eps3 + 2 * n)[base4 + j];
+            e[k] = pag_guide4(ep, eu, c[k], g, sp);
+            sc += sum4(c[k]); se += sum4(e[k]);
+        }
+    }
+    block_sum2(sc, se, red);
+    const float mc = sc / (float)per, me = se / (float)per;
+    float qc = 0.f, qe = 0.f;
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k)
+        if (threadIdx.x + k * GS_THREADS < per4) { qc += ssq4(c[k], mc); qe += ssq4(e[k], me); }
+    block_sum2(qc, qe, red);
+    const float f = rescale_factor(qc, qe, me, per, phi);
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int j = threadIdx.x + k * GS_THREADS;
+        if (j < per4) guided_apply4(kind, r, msrow, ms, s, clip, x, x3, lr, noise, n, base4 + j, scale4(e[k], f), true);
+    }
+}
+__global__ __launch_bounds__(GS_THREADS) void pag_step_rescale_reread_kernel(int kind, float* x, float* x3, const float* eps3, const float* lr,
+                                                                             const float* noise_base, const float* coef, const int* step,
+                                                                             float clip, float g, float sp, float phi, int B, int per, MsBuf ms) {
+    __shared__ float red[2 * GS_THREADS / 64];
+    const int s = *step;
+    const StepRow r = load_step_row(kind, coef, s);
+    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
+    const long long n = (long long)B * per;
+    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
+    const long long base4 = (long long)blockIdx.x * (per >> 2);
+    const int per4 = per >> 2;
+    const float4* pp = reinterpret_cast<const float4*>(eps3) + base4;
+    const float4* pu = reinterpret_cast<const float4*>(eps3 + n) + base4;
+    const float4* pc = reinterpret_cast<const float4*>(eps3 + 2 * n) + base4;
+    float sc = 0.f, se = 0.f;
+    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 c = pc[j]; sc += sum4(c); se += sum4(pag_guide4(pp[j], pu[j], c, g, sp)); }
+    block_sum2(sc, se, red);
+    const float mc = sc / (float)per, me = se / (float)per;
+    float qc = 0.f, qe = 0.f;
+    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 c = pc[j]; qc += ssq4(c, mc); qe += ssq4(pag_guide4(pp[j], pu[j], c, g, sp), me); }
+    block_sum2(qc, qe, red);
+    const float f = rescale_factor(qc, qe, me, per, phi);
+    for (int j = threadIdx.x; j < per4; j += GS_THREADS)
+        guided_apply4(kind, r, msrow, ms, s, clip, x, x3, lr, noise, n, base4 + j, scale4(pag_guide4(pp[j], pu[j], pc[j], g, sp), f), true);
+}
+int launch_pag_step(int kind, float* x, float* x3, const float* eps3, const float* lr, const float* noise, const float* coef_table,
+                    const int* step_idx, float clip, float g, float sp, float phi, int B, long long per, hipStream_t st, float* hist, float* xc,
+                    int order) {
+    MRISR_REQUIRE(kind >= MRISR_STEP_DDIM && kind <= MRISR_STEP_DPMSOLVERPP, "pag step: unknown step kind");
+    const bool multistep = kind > MRISR_STEP_DDPM;
+    const MsBuf ms{multistep ? hist : nullptr, multistep && kind == MRISR_STEP_UNIPC ? xc : nullptr, multistep ? order : 0};
+    if (multistep) {
+        if (int rc = check_multistep(x, eps3, lr, ms, (long long)B * per)) return rc;
+        MRISR_REQUIRE(kind != MRISR_STEP_UNIPC || xc, "pag step: UniPC needs the corrected-state buffer");
+    }
+    MRISR_REQUIRE(x && x3 && eps3 && coef_table && step_idx && B > 0 && per > 0, "pag step: null operand");
+    MRISR_REQUIRE(per % 4 == 0 && per < (1ll << 31), "pag step: the per-sample size must be a multiple of 4");
+    MRISR_REQUIRE(phi >= 0.f && phi <= 1.f, "pag step: guidance_rescale must lie in [0, 1]");
+    MRISR_REQUIRE(std::isfinite(sp) && sp >= 0.f, "pag step: pag_scale must be finite and >= 0");
+    MRISR_REQUIRE(kind != MRISR_STEP_RESSHIFT || lr, "pag step: Res-SRDiff needs the LR anchor latents");
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    MRISR_REQUIRE(al16(x) && al16(x3) && al16(eps3) && al16(lr) && al16(noise), "pag step: operands must be 16-byte aligned");
+    const long long n = (long long)B * per;
+    if (kind != MRISR_STEP_RESSHIFT && !multistep) lr = nullptr;
+    if (kind == MRISR_STEP_DDIM || multistep) noise = nullptr;
+    // eps3 three times, x in, four stores of x; multistep: + `order` history reads, one history write, xc in and out
+    ProfScope ps("sampler_step", 0.0, (32.0 + (lr ? 4.0 : 0.0) + (multistep ? 4.0 * order + 4.0 + (ms.xc ? 8.0 : 0.0) : 0.0)) * n, st);
+    if (phi == 0.f) {
+        hipLaunchKernelGGL(pag_step_kernel, dim3(nblocks(n >> 2)), dim3(256), 0, st, kind, x, x3, eps3, lr, noise, coef_table, step_idx, clip, g,
+                           sp, n, ms);
+    } else {
+#define MRISR_PS(ITEMS)                                                                                                           \
+    hipLaunchKernelGGL(pag_step_rescale_kernel<ITEMS>, dim3(B), dim3(GS_THREADS), 0, st, kind, x, x3, eps3, lr, noise, coef_table, \
+                       step_idx, clip, g, sp, phi, B, (int)per, ms)
+        if (per <= 4 * GS_THREADS) MRISR_PS(1);
+        else if (per <= 8 * GS_THREADS) MRISR_PS(2);
+        else if (per <= 16 * GS_THREADS) MRISR_PS(4);
+        else
+            hipLaunchKernelGGL(pag_step_rescale_reread_kernel, dim3(B), dim3(GS_THREADS), 0, st, kind, x, x3, eps3, lr, noise, coef_table,
+                               step_idx, clip, g, sp, phi, B, (int)per, ms);
+#undef MRISR_PS
     }
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;

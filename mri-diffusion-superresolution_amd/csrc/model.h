@@ -34,6 +34,7 @@ struct XfW {
     // literal and training paths
     void* ffpo = nullptr;
     const float* bffpo = nullptr;
+    int index = -1;  // position among the handle's transformer blocks in forward order (down, mid, up): the block's bit in PagState::mask
 };
 struct Level {
     std::vector<ResW> res;
@@ -62,6 +63,15 @@ struct UNetCache {
     void* p = nullptr;
 };
 
+// Perturbed-attention guidance: in the transformer blocks whose bit is set in `mask`, self-attention of samples
+// [first, first + count) is the identity map - their attention output is their own value rows - and the other samples attend as usual.
+// count == 0: off.  Part of the workspace key: the dry pass plans the attention launches of the remaining samples.
+struct PagState {
+    unsigned mask = 0;
+    int first = 0, count = 0;
+    bool on() const { return count > 0 && mask != 0; }
+};
+
 struct Model {
     mrisr_unet_cfg cfg{};
     bool is_controlnet = false;
@@ -69,6 +79,7 @@ struct Model {
     float lora_scale = 1.0f;
     bool dora = false;  // DoRA handle (mrisr_model_set_dora): every adapted linear carries a magnitude vector
     bool finalized = false;
+    PagState pag;       // mrisr_model_set_pag: honoured by every forward_unet until cleared
     std::vector<std::unique_ptr<DevBuf>> packed;
 
     // packed modules
@@ -116,6 +127,7 @@ struct Model {
     void* new_packed(size_t bytes, bool zero);
     int finalize(hipStream_t st);
     int num_skips() const;
+    int num_transformer_blocks() const;
     int skip_shape(int k, int B, int h, int w, int64_t shape[4]) const;
     int cache_shape(int depth, int B, int h, int w, int64_t shape[4]) const;  // the cached decoder input of UNetCache: {B, C, H, W}
     const HeadBuf& head_buf(int N, int C) const;

@@ -558,6 +558,12 @@ int Model::num_skips() const {
     for (int i = 0; i < cfg.num_levels; ++i) n += cfg.layers_per_block + (i < cfg.num_levels - 1 ? 1 : 0);
     return n;
 }
+int Model::num_transformer_blocks() const {
+    int n = 1;  // mid
+    for (int i = 0; i < cfg.num_levels; ++i)
+        if (cfg.attn_levels[i]) n += cfg.layers_per_block + (is_controlnet ? 0 : cfg.layers_per_block + 1);
+    return n;
+}
 int Model::skip_shape(int k, int B, int h, int w, int64_t shape[4]) const {
     std::vector<std::pair<int, int>> s;  // (channels, level)
     s.push_back({cfg.block_out_channels[0], 0});
@@ -635,6 +641,7 @@ static int plan_t(Model& m, int B, int h, int w, int L, hipStream_t st) {
     xfs.push_back(&m.mid_xf);
     for (auto& lv : m.up) for (auto& x : lv.xf) xfs.push_back(&x);
     std::vector<size_t> xoffs;
+    for (size_t i = 0; i < xfs.size(); ++i) xfs[i]->index = (int)i;  // forward order: the block's bit in PagState::mask
     for (XfW* x : xfs) {
         const HeadBuf& hb = m.head_buf_for_C(x->C);
         const size_t kb = (size_t)B * hb.H * m.ctx_pad * hb.dpad * sizeof(T);
@@ -706,9 +713,11 @@ int Model::ensure_workspace(int B, int h, int w, int L, hipStream_t st) {
     MRISR_REQUIRE(finalized, "call mrisr_model_finalize first");
     const int div = 1 << (cfg.num_levels - 1);
     MRISR_REQUIRE(h % div == 0 && w % div == 0, "latent size must be divisible by 2^(levels-1)");
-    char key[96];
+    char key[128];
     // (plan salt: the debug toggles that change WHAT the forward allocates - mrisr_debug_gn_slabs - bump it, so that the next forward re-plans)
-    snprintf(key, sizeof(key), "%d,%d,%d,%d,%d,s%d", B, h, w, L, keep ? 1 : 0, g_plan_salt);
+    // (perturbed-attention guidance: the attention launches of an applied block cover fewer samples - other shapes to plan)
+    snprintf(key, sizeof(key), "%d,%d,%d,%d,%d,s%d,p%x:%d:%d", B, h, w, L, keep ? 1 : 0, g_plan_salt, pag.on() ? pag.mask : 0u,
+             pag.on() ? pag.first : 0, pag.on() ? pag.count : 0);
     if (ws_key == key) return 0;
     int rc = cfg.compute_dtype == MRISR_F32 ? plan_t<float>(*this, B, h, w, L, st) : plan_t<bf16>(*this, B, h, w, L, st);
     if (rc) return rc;
@@ -741,6 +750,11 @@ int Model::forward_unet(const mrisr_tensor* sample, const mrisr_tensor* timestep
     const int B = (int)sample->shape[0], h = (int)sample->shape[2], w = (int)sample->shape[3];
     const int L = ehs ? (int)ehs->shape[1] : ctx_len;
     MRISR_REQUIRE(L > 0, "no encoder_hidden_states given and none cached");
+    if (pag.on()) {  // before the plan: nothing is launched for a state this batch cannot honour
+        MRISR_REQUIRE(pag.first + pag.count <= B, "perturbed-attention guidance: the perturbed samples lie outside the batch");
+        MRISR_REQUIRE(!cache || cache->mode == CACHE_NONE, "perturbed-attention guidance together with a feature cache is not supported");
+        MRISR_REQUIRE(!keep, "perturbed-attention guidance: not while a training forward is being recorded");
+    }
     TRY(ensure_workspace(B, h, w, L, st));
     const int t_scalar = timestep->ndim == 0 || timestep->shape[0] == 1;
     MRISR_REQUIRE(t_scalar || timestep->shape[0] == B, "timestep length");

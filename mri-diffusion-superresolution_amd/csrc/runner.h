@@ -392,6 +392,28 @@ struct Runner {
         return 0;
     }
 
+    // self-attention of one block into token rows `ao`.  Perturbed-attention guidance (Model::pag): in an applied block the perturbed
+    // samples take their own value rows (one transpose of v^T, no attention work) and the samples before / after them attend as usual,
+    // each range one launch on a view of the head buffers offset by whole samples
+    int self_attention(const XfW& xw, const HeadBuf& hb, T* ao) {
+        const PagState& pg = m.pag;
+        if (!pg.on() || xw.index < 0 || !((pg.mask >> xw.index) & 1u)) return attention(hb, hb.k, hb.vt, hb.N, hb.npad, ao);
+        MRISR_REQUIRE(!m.keep, "perturbed-attention guidance: not while a training forward is being recorded");
+        MRISR_REQUIRE(!m.cfg.fp8_attention, "perturbed-attention guidance: not with fp8_attention");
+        MRISR_REQUIRE(pg.first >= 0 && pg.first + pg.count <= hb.B, "perturbed-attention guidance: the perturbed samples lie outside the batch");
+        if (!dry) TRY(launch_attn_identity<T>(hb.vt, ao, hb.B, hb.H, hb.N, hb.hd, hb.npad, hb.dpad, pg.first, pg.count, st));
+        const int range[2][2] = {{0, pg.first}, {pg.first + pg.count, hb.B - pg.first - pg.count}};
+        for (auto& r : range) {
+            if (r[1] <= 0) continue;
+            const size_t off = (size_t)r[0] * hb.H * hb.npad * hb.dpad * sizeof(T);
+            HeadBuf v = hb;
+            v.B = r[1];
+            v.q = static_cast<char*>(hb.q) + off; v.k = static_cast<char*>(hb.k) + off; v.vt = static_cast<char*>(hb.vt) + off;
+            TRY(attention(v, v.k, v.vt, hb.N, hb.npad, ao + (size_t)r[0] * hb.N * hb.H * hb.hd));
+        }
+        return 0;
+    }
+
     void heads_args(GemmArgs* g, const HeadBuf& hb, void* s0, int tr0, void* s1, int tr1, void* s2, int tr2, int ntok,
                     int npad) {
         g->out_mode = OUT_HEADS;
@@ -445,7 +467,7 @@ struct Runner {
             heads_args(&g, hb, hb.q, 0, hb.k, 0, hb.vt, 1, hb.N, hb.npad);
             TRY(linear(t, M, C, xw.qkv, ACT_NONE, nullptr, 0, &g, nullptr, 0, nullptr, &xw.ln1, nrm));
         }
-        TRY(attention(hb, hb.k, hb.vt, hb.N, hb.npad, ao));
+        TRY(self_attention(xw, hb, ao));
         if (fused_middle(xw, hb, M)) {
             XTailArgs a;
             a.ao = ao; a.ldao = C; a.t = t; a.ldt = C; a.M = M; a.ntok = hb.N;

@@ -8,6 +8,8 @@ from .models import check_dora, dora_magnitude_init, lora_scaling  # noqa: F401
 from .pipeline import (Sampler, check_cache, check_guidance, check_solver, decode_to_vis, get_res_shifting_latents, log_validation,  # noqa: F401
                        prepare_condition_image)
 from .pipeline import check_tiles, tile_tables  # noqa: F401
+from .pipeline import check_pag  # noqa: F401
+from .models import transformer_block_names  # noqa: F401
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler,  # noqa: F401
                          UniPCMultistepScheduler)
 from .train import LoRATrainer, cosine_lr  # noqa: F401

@@ -61,6 +61,8 @@ EXPORTS = [
     "mrisr_adapter_destroy", "mrisr_adapter_set_param", "mrisr_adapter_finalize", "mrisr_adapter_forward",
     "mrisr_resshift_forward", "mrisr_sampler_create", "mrisr_sampler_destroy", "mrisr_sampler_run", "mrisr_sampler_set_range", "mrisr_sampler_set_clip",
     "mrisr_sampler_set_guidance", "mrisr_sampler_run_guided", "mrisr_sampler_set_cache", "mrisr_unet_cache_shape", "mrisr_unet_forward_cached", "mrisr_op_guided_step", "mrisr_sampler_set_solver", "mrisr_op_multistep_step",
+    "mrisr_model_set_pag", "mrisr_model_num_transformer_blocks", "mrisr_sampler_set_pag", "mrisr_sampler_run_pag", "mrisr_sampler_num_captures",
+    "mrisr_op_attn_identity", "mrisr_op_pag_step", "mrisr_op_pag_multistep_step",
     "mrisr_tile_tables", "mrisr_sampler_set_tiles", "mrisr_op_tile_gather", "mrisr_op_tile_blend",
     "mrisr_adapter_train_prepare", "mrisr_adapter_train_num_trainable", "mrisr_adapter_train_num_tensors",
     "mrisr_adapter_train_tensor_info", "mrisr_adapter_train_bind", "mrisr_adapter_train_refresh", "mrisr_adapter_backward", "mrisr_adapter_backward_level", "mrisr_adapter_train_level_range",
@@ -133,6 +135,14 @@ def lib() -> C.CDLL:
         L.mrisr_sampler_set_tiles.argtypes = [P, I, I, I, I, I]
         L.mrisr_op_tile_gather.argtypes = [P, P, P, I, P, I, P]
         L.mrisr_op_tile_blend.argtypes = [P, P, P, I, P, I, P, P, P]
+        L.mrisr_model_set_pag.argtypes = [P, C.c_uint32, I, I]
+        L.mrisr_model_num_transformer_blocks.argtypes = [P]
+        L.mrisr_sampler_set_pag.argtypes = [P, C.c_uint32, F]
+        L.mrisr_sampler_run_pag.argtypes = [P, P, P, P, P, P, P, I, I, I, P]
+        L.mrisr_sampler_num_captures.argtypes = [P]
+        L.mrisr_op_attn_identity.argtypes = [I, P, P, I, I, I, I, I, I, I, I, P]
+        L.mrisr_op_pag_step.argtypes = [I, P, P, P, P, P, P, F, F, F, F, P]
+        L.mrisr_op_pag_multistep_step.argtypes = [I, P, P, P, P, P, P, P, I, I, F, F, F, P]
         L.mrisr_resize_scratch_bytes.restype = C.c_size_t
         L.mrisr_resize_scratch_bytes.argtypes = [C.c_int] * 6
         L.mrisr_resize_slices.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

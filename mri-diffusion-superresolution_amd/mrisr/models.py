@@ -55,6 +55,19 @@ class UNetConfig:
                    conditioning_embedding_out_channels=tuple(getattr(cfg, "cond_embed_channels", (16, 32, 96, 256))))
 
 
+def transformer_block_names(cfg) -> List[str]:
+    """The transformer blocks of a UNet of config ``cfg`` (a ``UNetConfig`` or anything ``UNetConfig.from_oracle_like`` reads), in
+    forward order: ``down_blocks.i.attentions.j``, ``mid_block.attentions.0``, ``up_blocks.i.attentions.j`` - 16 for SD-1.5.  Pure
+    Python, no device."""
+    cfg = cfg if isinstance(cfg, UNetConfig) else UNetConfig.from_oracle_like(cfg)
+    attn = [t.startswith("CrossAttn") for t in cfg.down_block_types]
+    n = len(attn)
+    names = [f"down_blocks.{i}.attentions.{j}" for i in range(n) if attn[i] for j in range(cfg.layers_per_block)]
+    names.append("mid_block.attentions.0")
+    names += [f"up_blocks.{i}.attentions.{j}" for i in range(n) if attn[n - 1 - i] for j in range(cfg.layers_per_block + 1)]
+    return names
+
+
 class _Output:
     def __init__(self, sample):
         self.sample = sample
@@ -349,6 +362,19 @@ class UNet2DConditionModel(_DeviceModel):
                                            d_arr if down else None, len(down), C.byref(t_m) if t_m else None,
                                            i_arr if intra else None, len(intra), C.byref(t_o), L.stream_ptr()))
         return _Output(out) if return_dict else (out,)
+
+    def transformer_block_names(self) -> List[str]:
+        """The UNet's transformer blocks in forward order (``transformer_block_names``): entry i is bit i of a PAG block mask."""
+        names = transformer_block_names(self.config)
+        if len(names) != int(L.lib().mrisr_model_num_transformer_blocks(self._h)):
+            raise L.MrisrError("transformer block count differs between the Python config and the device model")
+        return names
+
+    def set_pag(self, block_mask: int = 0, first_sample: int = 0, n_samples: int = 0):
+        """Perturbed-attention state of this handle (``mrisr_model_set_pag``): until cleared, every forward
+        replaces ``attn1`` of samples [first_sample, first_sample + n_samples) in the blocks of ``block_mask`` by
+        ``to_out.0(to_v(norm1(h)))``.  No arguments: cleared.  ``Sampler.run(pag_scale=...)`` manages it by itself."""
+        L.check(L.lib().mrisr_model_set_pag(self._h, int(block_mask), int(first_sample), int(n_samples)))
 
     def cache_shape(self, depth: int, B: int, h: int, w: int) -> Tuple[int, int, int, int]:
         """Logical (B, C, H, W) of the feature cache at ``depth`` for h x w latents: the input of the decoder stage that consumes

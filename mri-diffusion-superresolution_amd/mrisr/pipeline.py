@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .models import ControlNetModel, UNet2DConditionModel
+from .models import ControlNetModel, UNet2DConditionModel, transformer_block_names
 
 
 def get_res_shifting_latents(hr_latents, lr_latents, timesteps, scheduler, noise=None):
@@ -89,6 +89,49 @@ def check_guidance(guidance_scale, guidance_rescale, ehs_shape, uncond_shape, ba
             raise ValueError("guidance_rescale > 0 needs active guidance: guidance_scale != 1")
         return False
     return True
+
+
+def check_pag(pag_scale, applied_layers, block_names, has_cache=False, fp8_attention=False) -> int:
+    """The argument rules of perturbed-attention guidance (``Sampler.run(pag_scale=, pag_applied_layers=)``), on
+    numbers and names alone (no device is touched).  Returns the block mask - bit i = ``block_names[i]``, the UNet's transformer blocks
+    in forward order (``transformer_block_names``) - or 0 when ``pag_scale == 0``: PAG off, the plain call is taken.
+
+    ``applied_layers``: a prefix or a tuple of prefixes; a prefix selects every block whose name starts with it at a component
+    boundary (``"mid"`` stands for ``"mid_block"``; ``"down_blocks.2"``, ``"up_blocks.1.attentions.0"``).  Raises ``ValueError`` naming
+    the argument: ``pag_scale`` negative or not finite; an entry that selects nothing; with ``pag_scale > 0`` an empty tuple, a feature
+    cache with interval > 1 (its shallow pass skips the blocks PAG perturbs) or a UNet built with ``fp8_attention``."""
+    try:
+        s = float(pag_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"pag_scale must be a number >= 0, got {pag_scale!r}") from None
+    if isinstance(pag_scale, bool) or not np.isfinite(s) or s < 0.0:
+        raise ValueError(f"pag_scale must be finite and >= 0, got {pag_scale!r}")
+    layers = (applied_layers,) if isinstance(applied_layers, str) else tuple(applied_layers if applied_layers is not None else ())
+    names = list(block_names)
+    mask = 0
+    for entry in layers:
+        if not isinstance(entry, str) or not entry:
+            raise ValueError(f"pag_applied_layers: every entry must be a non-empty string, got {entry!r}")
+        parts = entry.split(".")
+        if parts[0] == "mid":
+            parts[0] = "mid_block"
+        hit = [i for i, n in enumerate(names) if n.split(".")[:len(parts)] == parts]
+        if not hit:
+            raise ValueError(f"pag_applied_layers: {entry!r} selects no transformer block; the blocks are {', '.join(names)}")
+        for i in hit:
+            mask |= 1 << i
+    if s == 0.0:
+        return 0
+    if len(names) > 32:
+        raise ValueError(f"pag_scale > 0: at most 32 transformer blocks fit the block mask, the UNet has {len(names)}")
+    if not layers:
+        raise ValueError("pag_applied_layers must name at least one block when pag_scale > 0")
+    if has_cache:
+        raise ValueError("pag_scale > 0 together with a feature cache (cache interval > 1) is not supported: the shallow pass skips the "
+                         "blocks PAG perturbs")
+    if fp8_attention:
+        raise ValueError("pag_scale > 0 is not supported on a UNet built with fp8_attention")
+    return mask
 
 
 MULTISTEP_KINDS = ("unipc", "dpmsolver++")
@@ -206,6 +249,7 @@ class Sampler:
                 raise ValueError("multistep solvers need strictly decreasing timesteps")
         self.unet, self.controlnet, self.kind = unet, controlnet, kind
         self.tiles = None  # (t_h, t_w, o_h, o_w, window) once set_tiles turned tiling on
+        self.cache_interval, self.cache_depth = 1, 1  # set_cache changes them
         ts = scheduler.timesteps.detach().cpu().to(torch.int64).numpy().copy()
         ac = scheduler.alphas_cumprod.detach().cpu().to(torch.float32).numpy().copy()
         self.n_steps = len(ts)
@@ -314,10 +358,16 @@ class Sampler:
 
     def run(self, latents: torch.Tensor, encoder_hidden_states: torch.Tensor, lr_latents: Optional[torch.Tensor] = None,
             step_noise: Optional[torch.Tensor] = None, controlnet_cond: Optional[torch.Tensor] = None,
-            adapter_features: Optional[Sequence[torch.Tensor]] = None, use_graph: bool = True,
-            guidance_scale: float = 1.0, guidance_rescale: float = 0.0,
+            adapter_features: Optional[Sequence[torch.Tensor]] = None, pag_scale: float = 0.0, pag_applied_layers=("mid",),
+            use_graph: bool = True, guidance_scale: float = 1.0, guidance_rescale: float = 0.0,
             uncond_hidden_states: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Advance ``latents`` [B,C,h,w] (f32, updated IN PLACE) through every timestep.
+
+        Perturbed-attention guidance (Ahn et al. 2024): with ``pag_scale`` s > 0 every step also predicts eps_p -
+        the same network with the self-attention map of the blocks ``pag_applied_layers`` selects (``check_pag``) replaced by the identity
+        - in the same forward (perturbed rows first: 2B rows, 3B with classifier-free guidance) and steps with
+        eps = eps_u + g (eps_c - eps_u) + s (eps_c - eps_p) (eps_u := eps_c without CFG), then the ``guidance_rescale`` rule.  No
+        unconditional prompt is needed.  ``pag_scale=0`` (the default) is the call without it.  Not with a feature cache.
 
         Classifier-free guidance: with ``uncond_hidden_states`` ([1,L,D] or [B,L,D]) and ``guidance_scale`` g != 1 every step runs
         ONE forward of 2B rows (unconditional rows first) and the fused guided step: eps = eps_u + g (eps_c - eps_u), then, for
@@ -337,6 +387,11 @@ class Sampler:
             if latents.ndim != 4:
                 raise ValueError("tiled sampling needs [B,C,h,w] latents")
             plan = self._tile_plan(latents.shape[2], latents.shape[3])
+        pag_mask = check_pag(pag_scale, pag_applied_layers, transformer_block_names(self.unet.config),
+                             self.cache_interval > 1, self.unet.fp8_attention)
+        if pag_mask:
+            return self._run_pag(latents, encoder_hidden_states, uncond_hidden_states, lr_latents, step_noise, controlnet_cond,
+                                 adapter_features, use_graph, guidance_scale, guidance_rescale, float(pag_scale), pag_mask, plan)
         if check_guidance(guidance_scale, guidance_rescale, encoder_hidden_states.shape,
                           None if uncond_hidden_states is None else uncond_hidden_states.shape, latents.shape[0]):
             return self._run_guided(latents, encoder_hidden_states, uncond_hidden_states, lr_latents, step_noise, controlnet_cond,
@@ -366,8 +421,26 @@ class Sampler:
         self._keep = keep
         return latents
 
+    def _run_pag(self, latents, ehs_c, ehs_u, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, g, guidance_rescale,
+                 s, mask, plan=None):
+        """The PAG run: the rows [perturbed; conditional] or, with active classifier-free guidance, [perturbed; unconditional;
+        conditional]; perturbed rows carry the conditional context.  Everything is checked before anything is launched."""
+        B, phi = latents.shape[0], float(guidance_rescale)
+        if not 0.0 <= phi <= 1.0:
+            raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale!r}")
+        # (with PAG the rescale rule needs no active classifier-free guidance: check_guidance sees phi only when CFG can be active)
+        cfg_given = ehs_u is not None and float(g) != 1.0
+        with_cfg = check_guidance(g, phi if cfg_given else 0.0, ehs_c.shape, None if ehs_u is None else ehs_u.shape, B)
+        if latents.ndim != 4 or int(np.prod(latents.shape[1:])) % 4:
+            raise ValueError("pag_scale > 0 needs [B,C,h,w] latents with C*h*w a multiple of 4")
+        if ehs_c.ndim != 3 or ehs_c.shape[0] not in (1, B):
+            raise ValueError(f"encoder_hidden_states must be [1, L, D] or [{B}, L, D], got {tuple(ehs_c.shape)}")
+        contexts = (ehs_c, ehs_u, ehs_c) if with_cfg else (ehs_c, ehs_c)
+        return self._run_guided(latents, None, None, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, float(g), phi,
+                                plan, contexts=contexts, pag=(mask, s, 1 if with_cfg else 0))
+
     def _run_guided(self, latents, ehs_c, ehs_u, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, g, phi,
-                    plan=None):
+                    plan=None, contexts=None, pag=None):
         B, dev = latents.shape[0], latents.device
         if int(np.prod(latents.shape[1:])) % 4:
             raise ValueError("guided sampling needs C*h*w of the latents to be a multiple of 4")
@@ -377,11 +450,14 @@ class Sampler:
             if f.shape[0] != B:
                 raise ValueError(f"adapter features must carry the latents' batch {B}, got {tuple(f.shape)}")
         # timestep-invariant plumbing, once per run: [unconditional rows; conditional rows] (diffusers' order), images and features twice
-        ehs2 = torch.cat([e.to(dev).expand(B, -1, -1) for e in (ehs_u, ehs_c)]).contiguous()
+        # (a PAG run: `contexts` = [perturbed; (unconditional;) conditional], images and features K times)
+        contexts = contexts if contexts is not None else (ehs_u, ehs_c)
+        K = len(contexts)
+        ehs2 = torch.cat([e.to(dev).expand(B, -1, -1) for e in contexts]).contiguous()
         lr = lr_latents.to(dev, torch.float32).contiguous() if lr_latents is not None else None
         nz = step_noise.to(dev, torch.float32).contiguous() if step_noise is not None else None
-        cond2 = torch.cat([controlnet_cond.to(dev)] * 2).contiguous() if controlnet_cond is not None else None
-        feats2 = [torch.cat([f.to(dev)] * 2).contiguous() for f in (adapter_features or [])]
+        cond2 = torch.cat([controlnet_cond.to(dev)] * K).contiguous() if controlnet_cond is not None else None
+        feats2 = [torch.cat([f.to(dev)] * K).contiguous() for f in (adapter_features or [])]
         if plan is not None:  # the 2B rows, then their tiles: row (b, ti) of the forward is b * T + ti
             ehs2, cond2, feats2 = self._tile_operands(plan, latents.shape[2], latents.shape[3], ehs2, cond2, feats2)
         keep = (ehs2, lr, nz, cond2, feats2)
@@ -391,6 +467,13 @@ class Sampler:
         t_c = L.as_tensor(cond2) if cond2 is not None else None
         f_arr = L.tensor_array([L.as_tensor(f) for f in feats2])
         L.check(L.lib().mrisr_sampler_set_guidance(self._h, g, phi))
+        if pag is not None:
+            L.check(L.lib().mrisr_sampler_set_pag(self._h, pag[0], pag[1]))
+            L.check(L.lib().mrisr_sampler_run_pag(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None,
+                                                  C.byref(t_nz) if t_nz else None, C.byref(t_e), C.byref(t_c) if t_c else None,
+                                                  f_arr if feats2 else None, len(feats2), pag[2], 1 if use_graph else 0, L.stream_ptr()))
+            self._keep = keep
+            return latents
         L.check(L.lib().mrisr_sampler_run_guided(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None,
                                                  C.byref(t_nz) if t_nz else None, C.byref(t_e), C.byref(t_c) if t_c else None,
                                                  f_arr if feats2 else None, len(feats2), 1 if use_graph else 0, L.stream_ptr()))
@@ -401,7 +484,8 @@ class Sampler:
 @torch.no_grad()
 def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weight_dtype, accelerator, fixed_embeds,
                    num_inference_steps=20, adapter=None, solver=None, cache_interval=1, cache_depth=1, tile=None, tile_overlap=0,
-                   tile_window="gaussian", guidance_scale=1.0, guidance_rescale=0.0, uncond_embeds=None):
+                   tile_window="gaussian", pag_scale=0.0, pag_applied_layers=("mid",), guidance_scale=1.0, guidance_rescale=0.0,
+                   uncond_embeds=None):
     """Drop-in for the reference's validation sampler (res_srdiff.py:35-105): same inputs, same PIL panel out.
     The timestep loop is one fused sampler call; the per-step noise is drawn up front from the same global RNG
     stream, in the same order, as the reference's per-step ``torch.randn_like`` calls.  ``adapter`` (a T2I-Adapter):
@@ -411,7 +495,8 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     with that LR-anchored deterministic multistep solver (the scheduler's solver options when it carries any) instead of the
     reference's stochastic step; no step noise is drawn then.  ``None``: the reference's sampler.  ``cache_interval`` /
     ``cache_depth``: the feature cache of ``Sampler.set_cache``; the defaults leave the panel unchanged.  ``tile`` / ``tile_overlap`` /
-    ``tile_window``: tiled sampling as in ``Sampler.set_tiles`` (latent pixels); the defaults leave the panel unchanged."""
+    ``tile_window``: tiled sampling as in ``Sampler.set_tiles`` (latent pixels); the defaults leave the panel unchanged.
+    ``pag_scale`` / ``pag_applied_layers``: perturbed-attention guidance as in ``Sampler.run``; the defaults leave the panel unchanged."""
     from PIL import Image
 
     if solver is not None:
@@ -448,7 +533,8 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     sampler.run(latents, fixed_embeds[0:1], lr_latents=lr_anchor, step_noise=step_noise,
                 controlnet_cond=control_image if controlnet is not None else None, adapter_features=feats,
                 guidance_scale=guidance_scale, guidance_rescale=guidance_rescale,
-                uncond_hidden_states=uncond_embeds[0:1] if uncond_embeds is not None else None)
+                uncond_hidden_states=uncond_embeds[0:1] if uncond_embeds is not None else None, pag_scale=pag_scale,
+                pag_applied_layers=pag_applied_layers)
     gen_vis = decode_to_vis(latents.to(weight_dtype), vae)
     hr_vis = decode_to_vis(hr_raw, vae, is_latent=False)
     lr_vis = decode_to_vis(lr_raw, vae, is_latent=False)

@@ -99,6 +99,15 @@ int mrisr_model_set_dora(mrisr_model* m, int use_dora);
  * bit beyond the last block; a forward whose batch does not hold the range, a cached forward (mrisr_unet_forward_cached) and a training
  * step are refused while the state is set.  The workspace is planned per state.  mrisr_sampler_run_pag sets and clears it itself. */
 int mrisr_model_set_pag(mrisr_model* m, uint32_t block_mask, int first_sample, int n_samples);
+/* FreeU state of a UNet handle (contract: "FreeU" below; diffusers' UNet2DConditionModel.enable_freeu(s1, s2, b1, b2)).  While on,
+ * every mrisr_unet_forward and every sampler step on the handle applies, in each resnet stage of up block k in {0, 1} (forward order;
+ * stage 0 takes (b1, s1), stage 1 takes (b2, s2); an up block the UNet does not have is skipped) and before hidden and skip are
+ * concatenated:  hidden[:, :Ch / 2] *= b   and   skip = fourier_filter(skip, threshold = 1, scale = s).  on == 0 clears the state (the
+ * four values are ignored) and leaves the forward as it was: same launches, same workspace, same bits.  Refused: a ControlNet handle, a
+ * value that is negative or not finite; mrisr_unet_forward_cached, a sampler run with a cache interval > 1, mrisr_sampler_set_cache with
+ * interval > 1 and a training step are refused while the state is on.  The state is part of the workspace key and of the sampler's graph
+ * key: a change plans and captures again. */
+int mrisr_model_set_freeu(mrisr_model* m, int on, float s1, float s2, float b1, float b2);
 /* Re-lays weights out for the kernels (NHWC filter order, fused QKV, GEGLU interleave, LoRA tails, ...).
  * Must be called after the last set_param and before forward; may be called again after updating params. */
 int mrisr_model_finalize(mrisr_model* m, void* stream);
@@ -261,6 +270,21 @@ int mrisr_sampler_run_pag(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_t
                           int use_graph, void* stream);
 /* step graphs this sampler has captured so far (a run whose key matches the previous one captures nothing) */
 int mrisr_sampler_num_captures(const mrisr_sampler* s);
+
+/* ---- FreeU (Si et al. 2023, "FreeU: Free Lunch in Diffusion U-Net"; the rule of diffusers' apply_freeu / fourier_filter) -----------
+ * Off unless mrisr_model_set_freeu turned it on.  It rebalances the two inputs of the first two decoder blocks: the backbone half of the
+ * hidden tensor is amplified by b, and the lowest spatial frequencies of the skip tensor - the one that already carries ControlNet
+ * residuals and adapter features - are scaled by s.  Stage k is up block k in forward order (diffusers' resolution_idx rule, not the
+ * original repository's channel-count rule).  FreeU v2's structure-aware backbone map is not implemented: b is a plain scalar.
+ * fourier_filter, per (sample, channel) plane of H x W pixels: fftn, fftshift, the block [H/2-1 : H/2+1, W/2-1 : W/2+1] times s,
+ * ifftshift, ifftn, real part.  The block holds the frequencies ky in {0, H-1}, kx in {0, W-1} as distinct residues (H == 1 or W == 1
+ * leaves one on that axis; H == 2 leaves both), so with X the forward DFT
+ *     y = x + (s - 1) / (H W) Re( sum over those <= 4 (ky, kx) of X(ky, kx) exp(+2 pi i (ky y / H + kx x / W)) )
+ * which is what the kernel evaluates: sums in f32 (also for bf16 activations, as diffusers filters in f32), the result rounded once to the
+ * activation dtype, no atomics - the bits repeat, and a graph replay equals the eager run.  One launch per decoder stage, six per
+ * forward of a UNet with layers_per_block == 2.  Works with every step kind, classifier-free guidance, perturbed-attention guidance (the
+ * perturbed rows are filtered like the others), tiles (per-tile planes), ControlNet residuals, adapter features, LoRA / DoRA and the
+ * fp8 modes.  Not with the feature cache and not in a training step. */
 
 /* ---- tiled sampling (MultiDiffusion, Bar-Tal et al. 2023, with the Gaussian weights of Mixture of Diffusers, Jimenez 2023) -------
  * The latent canvas [NB, C, H, W] is cut into overlapping tiles, the forward runs on the tile batch [NB*T, C, t_h, t_w] and the tile
@@ -616,6 +640,12 @@ int mrisr_op_dora_mag_grad(int dtype, const void* P, int ldp, const void* Y, int
  * of other samples are not written.  Refused before any launch: null or misaligned pointers, npad < N, dpad < hd, a range outside B. */
 int mrisr_op_attn_identity(int dtype, const void* vt, void* out, int B, int H, int N, int hd, int npad, int dpad, int first_sample, int n_samples,
                            void* stream);
+/* FreeU on one decoder stage's operands alone (the launch mrisr_model_set_freeu adds): NHWC hidden [B][H][W][Ch] and skip [B][H][W][Cs]
+ * of `dtype`; hidden_out = hidden with channels [0, Ch / 2) times b, skip_out = fourier_filter(skip, 1, s).  An out pointer may equal its
+ * in pointer (in place); buffers must not overlap otherwise.  Refused before any launch: null or not 16-byte aligned pointers, B, H or
+ * W < 1 (or H, W > 1024), Ch % 16 != 0, Cs % 8 != 0, b or s negative or not finite. */
+int mrisr_op_freeu(int dtype, const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs,
+                   float b, float s, void* stream);
 /* dst[z][c][r] = src[z][r][c] for r < r_valid, 0 for r_valid <= r < R (T; pitches ld_src >= C, ld_dst >= R; batch strides in elements) */
 int mrisr_op_transpose(int dtype, const void* src, void* dst, int R, int C, int ld_src, int ld_dst, int64_t bs_src, int64_t bs_dst,
                        int batch, int r_valid, void* stream);

@@ -81,6 +81,22 @@ int mrisr_model_set_pag(mrisr_model* m, unsigned block_mask, int first_sample, i
     m->pag.mask = block_mask; m->pag.first = first_sample; m->pag.count = n_samples;
     return 0;
 }
+int mrisr_model_set_freeu(mrisr_model* m, int on, float s1, float s2, float b1, float b2) {
+    MRISR_REQUIRE(m, "null handle");
+    if (!on) {
+        m->freeu = FreeUState();
+        return 0;
+    }
+    MRISR_REQUIRE(!m->is_controlnet, "freeu: FreeU belongs to the UNet's decoder, not to a ControlNet handle");
+    MRISR_REQUIRE(!m->keep, "freeu: a training forward is being recorded");
+    MRISR_REQUIRE(std::isfinite(s1) && s1 >= 0.f, "freeu: s1 must be finite and >= 0");
+    MRISR_REQUIRE(std::isfinite(s2) && s2 >= 0.f, "freeu: s2 must be finite and >= 0");
+    MRISR_REQUIRE(std::isfinite(b1) && b1 >= 0.f, "freeu: b1 must be finite and >= 0");
+    MRISR_REQUIRE(std::isfinite(b2) && b2 >= 0.f, "freeu: b2 must be finite and >= 0");
+    m->freeu.on = true;
+    m->freeu.s[0] = s1; m->freeu.s[1] = s2; m->freeu.b[0] = b1; m->freeu.b[1] = b2;
+    return 0;
+}
 int mrisr_model_num_transformer_blocks(const mrisr_model* m) { return m ? m->num_transformer_blocks() : 0; }
 int mrisr_model_finalize(mrisr_model* m, void* stream) {
     API_BEGIN
@@ -120,6 +136,7 @@ int mrisr_unet_forward_cached(mrisr_model* m, const mrisr_tensor* sample, const 
     API_BEGIN
     MRISR_REQUIRE(m && sample && cache, "null argument");
     MRISR_REQUIRE(!m->is_controlnet, "not a UNet handle");
+    MRISR_REQUIRE(!m->freeu.on, "FreeU together with a feature cache is not supported (mrisr_model_set_freeu)");
     MRISR_REQUIRE(sample->ndim == 4, "sample must be [B, in_channels, h, w]");
     int64_t cs[4];
     TRY(m->cache_shape(depth, (int)sample->shape[0], (int)sample->shape[2], (int)sample->shape[3], cs));
@@ -459,6 +476,7 @@ int mrisr_sampler_set_cache(mrisr_sampler* s, int interval, int depth) {
     MRISR_REQUIRE(depth >= 1 && depth <= s->unet->num_skips() - 1, "cache depth must lie in 1 .. num_skips - 1");
     MRISR_REQUIRE(interval == 1 || !s->cnet, "a feature cache together with a ControlNet is not supported");
     MRISR_REQUIRE(interval == 1 || s->tile_h == 0, "a feature cache together with tiles is not supported");
+    MRISR_REQUIRE(interval == 1 || !s->unet->freeu.on, "a feature cache together with FreeU is not supported (mrisr_model_set_freeu)");
     if (interval != s->cache_interval || depth != s->cache_depth) s->drop_graphs();  // the next run captures again
     s->cache_interval = interval;
     s->cache_depth = depth;
@@ -520,6 +538,8 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
     MRISR_REQUIRE(!s->cnet || cond, "ControlNet needs the condition image");
     const bool cached = s->cache_interval > 1;
     MRISR_REQUIRE(!cached || !s->cnet, "a feature cache together with a ControlNet is not supported");
+    MRISR_REQUIRE(!cached || !s->unet->freeu.on, "a feature cache with interval > 1 together with FreeU is not supported (mrisr_model_set_freeu)");
+    MRISR_REQUIRE(!s->unet->freeu.on || !s->unet->keep, "FreeU: a training forward is being recorded");
     if (pag) {
         MRISR_REQUIRE(K == 2 || K == 3, "pag run: the forward has 2B rows (pag alone) or 3B rows (with classifier-free guidance)");
         MRISR_REQUIRE(s->pag_mask != 0, "pag run: no applied block (mrisr_sampler_set_pag)");
@@ -801,6 +821,10 @@ static int sampler_run_impl(mrisr_sampler* s, mrisr_tensor* latents, const mrisr
             }
             if (pag) {  // the row count, the applied blocks (also in the UNet's workspace generation) and the scale the step takes by value
                 snprintf(kb, sizeof(kb), ",P%d,%x,%a", K, s->pag_mask, (double)s->pag_scale);
+                key += kb;
+            }
+            if (U.freeu.on) {  // the four scalars the decoder's FreeU launches take by value (also in the UNet's workspace generation)
+                snprintf(kb, sizeof(kb), ",F%a,%a,%a,%a", (double)U.freeu.s[0], (double)U.freeu.s[1], (double)U.freeu.b[0], (double)U.freeu.b[1]);
                 key += kb;
             }
             if (s->multistep()) {  // the ring, the corrected state and the solver order the step takes by value; the other options live in the rows

@@ -984,6 +984,18 @@ int mrisr_op_attn_identity(int dtype, const void* vt, void* out, int B, int H, i
     API_END
 }
 
+int mrisr_op_freeu(int dtype, const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs, float b,
+                   float s, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    hipStream_t st = (hipStream_t)stream;
+    // (the launcher refuses null / misaligned pointers, an empty geometry, Ch % 16, Cs % 8 and bad scalars before it launches)
+    TRY(BWD_DISPATCH(dtype, launch_freeu, hidden, skip, hidden_out, skip_out, B, H, W, Ch, Cs, b, s, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
 int mrisr_op_softmax_bwd(int dtype, const void* p, const float* dp, void* ds, int ld, int64_t rows, int nk, float scale, void* stream) {
     API_BEGIN
     TRY(bwd_dtype_ok(dtype));

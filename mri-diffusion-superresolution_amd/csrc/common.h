@@ -304,6 +304,11 @@ int launch_rows_to_heads(const void* x, int ldx, int col_off, void* dst, int B, 
 // out [B][N][H*hd]; rows of the other samples are not touched
 template <typename T>
 int launch_attn_identity(const void* vt, void* out, int B, int H, int N, int hd, int npad, int dpad, int b0, int nb, hipStream_t st);
+// FreeU on one decoder stage's operands (freeu.hip): NHWC hidden [B][H][W][Ch] -> channels [0, Ch/2) times b; skip [B][H][W][Cs] ->
+// diffusers' fourier_filter(threshold 1, scale s) per (sample, channel) plane.  An out pointer may equal its in pointer
+template <typename T>
+int launch_freeu(const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs, float b, float s,
+                 hipStream_t st);
 template <typename T>
 int launch_softmax_bwd(const void* p, const float* dp, void* ds, int ld, long long rows, int nk, float scale, hipStream_t st);
 template <typename T>

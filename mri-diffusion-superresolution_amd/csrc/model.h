@@ -72,6 +72,13 @@ struct PagState {
     bool on() const { return count > 0 && mask != 0; }
 };
 
+// FreeU (diffusers' enable_freeu): in every resnet stage of up block k in {0, 1} the first half of the hidden
+// channels is scaled by b[k] and the skip tensor's lowest spatial frequencies by s[k], before the concat.  Part of the workspace key.
+struct FreeUState {
+    bool on = false;
+    float s[2] = {1.f, 1.f}, b[2] = {1.f, 1.f};
+};
+
 struct Model {
     mrisr_unet_cfg cfg{};
     bool is_controlnet = false;
@@ -80,6 +87,7 @@ struct Model {
     bool dora = false;  // DoRA handle (mrisr_model_set_dora): every adapted linear carries a magnitude vector
     bool finalized = false;
     PagState pag;       // mrisr_model_set_pag: honoured by every forward_unet until cleared
+    FreeUState freeu;   // mrisr_model_set_freeu: honoured by every forward_unet until cleared
     std::vector<std::unique_ptr<DevBuf>> packed;
 
     // packed modules

@@ -713,11 +713,15 @@ int Model::ensure_workspace(int B, int h, int w, int L, hipStream_t st) {
     MRISR_REQUIRE(finalized, "call mrisr_model_finalize first");
     const int div = 1 << (cfg.num_levels - 1);
     MRISR_REQUIRE(h % div == 0 && w % div == 0, "latent size must be divisible by 2^(levels-1)");
-    char key[128];
+    char key[256];
     // (plan salt: the debug toggles that change WHAT the forward allocates - mrisr_debug_gn_slabs - bump it, so that the next forward re-plans)
     // (perturbed-attention guidance: the attention launches of an applied block cover fewer samples - other shapes to plan)
     snprintf(key, sizeof(key), "%d,%d,%d,%d,%d,s%d,p%x:%d:%d", B, h, w, L, keep ? 1 : 0, g_plan_salt, pag.on() ? pag.mask : 0u,
              pag.on() ? pag.first : 0, pag.on() ? pag.count : 0);
+    if (freeu.on) {  // FreeU: six more launches in the decoder, their four scalars taken by value
+        const size_t n = strlen(key);
+        snprintf(key + n, sizeof(key) - n, ",f%a:%a:%a:%a", (double)freeu.s[0], (double)freeu.s[1], (double)freeu.b[0], (double)freeu.b[1]);
+    }
     if (ws_key == key) return 0;
     int rc = cfg.compute_dtype == MRISR_F32 ? plan_t<float>(*this, B, h, w, L, st) : plan_t<bf16>(*this, B, h, w, L, st);
     if (rc) return rc;
@@ -754,6 +758,10 @@ int Model::forward_unet(const mrisr_tensor* sample, const mrisr_tensor* timestep
         MRISR_REQUIRE(pag.first + pag.count <= B, "perturbed-attention guidance: the perturbed samples lie outside the batch");
         MRISR_REQUIRE(!cache || cache->mode == CACHE_NONE, "perturbed-attention guidance together with a feature cache is not supported");
         MRISR_REQUIRE(!keep, "perturbed-attention guidance: not while a training forward is being recorded");
+    }
+    if (freeu.on) {  // likewise before the plan
+        MRISR_REQUIRE(!cache || cache->mode == CACHE_NONE, "FreeU together with a feature cache is not supported");
+        MRISR_REQUIRE(!keep, "FreeU: not while a training forward is being recorded");
     }
     TRY(ensure_workspace(B, h, w, L, st));
     const int t_scalar = timestep->ndim == 0 || timestep->shape[0] == 1;

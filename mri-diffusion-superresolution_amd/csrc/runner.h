@@ -695,6 +695,19 @@ struct Runner {
         return 0;
     }
 
+    // FreeU on the two operands of one decoder resnet of up block 0 or 1, before the resnet's GroupNorm and conv gather concatenate them:
+    // one launch, both tensors in place.  By now every other reader has run - a skip also fed the encoder blocks after it, the last one
+    // the mid block, the hidden tensor nothing but this stage - and the states that would read them later are refused while FreeU is on:
+    // the feature cache (its stored input, which a shallow step hands in again as x) and a recorded training forward (its tape).  A skip
+    // that carries ControlNet residuals or adapter features is filtered with them, as in diffusers
+    int freeu(const Act& x, const Act& sk, float b, float s) {
+        MRISR_REQUIRE(!m.keep, "FreeU: not while a training forward is being recorded");
+        MRISR_REQUIRE(x.B == sk.B && x.H == sk.H && x.W == sk.W, "FreeU: hidden and skip geometry differ");
+        MRISR_REQUIRE(x.C % 16 == 0 && sk.C % 8 == 0, "FreeU: hidden channels must be a multiple of 16, skip channels of 8");
+        if (dry) return 0;
+        return launch_freeu<T>(x.p, sk.p, x.p, sk.p, x.B, x.H, x.W, x.C, sk.C, b, s, st);
+    }
+
     int unet_forward(const mrisr_tensor& sample, const long long* t_dev, int t_scalar, const mrisr_tensor* ehs,
                      const mrisr_tensor* down_res, int n_down, const mrisr_tensor* mid_res,
                      const mrisr_tensor* intrablock, int n_intra, const mrisr_tensor& out, const UNetCache& fc = UNetCache()) {
@@ -748,6 +761,7 @@ struct Runner {
                 }
                 Act sk = skips.back();
                 skips.pop_back();
+                if (m.freeu.on && i < 2) TRY(freeu(x, sk, m.freeu.b[i], m.freeu.s[i]));
                 Act y, xn_next;
                 xn_next.p = nullptr;
                 if (!lv.xf.empty()) TRY(resnet(lv.res[j], x, &sk, &y, &lv.xf[j].norm, 1e-6f, &xn_next));

@@ -1517,6 +1517,7 @@ int Model::train_plan(const mrisr_tensor* sample, const mrisr_tensor* timestep, 
     const int B = (int)sample->shape[0], h = (int)sample->shape[2], w = (int)sample->shape[3];
     const int t_scalar = timestep->ndim == 0 || timestep->shape[0] == 1;
     MRISR_REQUIRE(!pag.on(), "a training forward cannot be recorded while perturbed-attention guidance is set (mrisr_model_set_pag)");
+    MRISR_REQUIRE(!freeu.on, "a training forward cannot be recorded while FreeU is on (mrisr_model_set_freeu)");
     keep = true;
     int rc = ensure_workspace(B, h, w, (int)ehs->shape[1], st);
     if (!rc) {
@@ -1539,6 +1540,7 @@ int Model::train_step(const mrisr_tensor* sample, const mrisr_tensor* timestep, 
     const int t_scalar = timestep->ndim == 0 || timestep->shape[0] == 1;
     MRISR_REQUIRE(t_scalar || timestep->shape[0] == B, "timestep length");
     MRISR_REQUIRE(!pag.on(), "a training forward cannot be recorded while perturbed-attention guidance is set (mrisr_model_set_pag)");
+    MRISR_REQUIRE(!freeu.on, "a training forward cannot be recorded while FreeU is on (mrisr_model_set_freeu)");
     keep = true;
     int rc = ensure_workspace(B, h, w, (int)ehs->shape[1], st);
     if (!rc) {

@@ -68,6 +68,32 @@ def transformer_block_names(cfg) -> List[str]:
     return names
 
 
+def check_freeu(s1, s2, b1, b2) -> Tuple[float, float, float, float]:
+    """The argument rules of FreeU (``UNet2DConditionModel.enable_freeu``) on numbers alone (no device is touched):
+    each of ``s1``, ``s2``, ``b1``, ``b2`` must be a finite number >= 0.  Returns them as floats in that order; raises ``ValueError``
+    naming the bad argument."""
+    out = []
+    for name, v in (("s1", s1), ("s2", s2), ("b1", b1), ("b2", b2)):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"freeu: {name} must be a number >= 0, got {v!r}") from None
+        if isinstance(v, bool) or not math.isfinite(f) or f < 0.0:
+            raise ValueError(f"freeu: {name} must be finite and >= 0, got {v!r}")
+        out.append(f)
+    return tuple(out)
+
+
+def freeu_stage_names(cfg) -> List[str]:
+    """The resnets whose inputs FreeU rebalances in a UNet of config ``cfg`` (a ``UNetConfig`` or anything
+    ``UNetConfig.from_oracle_like`` reads), in forward order: ``up_blocks.k.resnets.j`` for k in {0, 1} (diffusers' ``resolution_idx``
+    rule; stage k = up block k takes (b1, s1) for k = 0 and (b2, s2) for k = 1) and j < layers_per_block + 1.  An up block the UNet
+    does not have is skipped.  Pure Python, no device."""
+    cfg = cfg if isinstance(cfg, UNetConfig) else UNetConfig.from_oracle_like(cfg)
+    n = len(cfg.down_block_types)
+    return [f"up_blocks.{k}.resnets.{j}" for k in range(min(2, n)) for j in range(cfg.layers_per_block + 1)]
+
+
 class _Output:
     def __init__(self, sample):
         self.sample = sample
@@ -375,6 +401,26 @@ class UNet2DConditionModel(_DeviceModel):
         replaces ``attn1`` of samples [first_sample, first_sample + n_samples) in the blocks of ``block_mask`` by
         ``to_out.0(to_v(norm1(h)))``.  No arguments: cleared.  ``Sampler.run(pag_scale=...)`` manages it by itself."""
         L.check(L.lib().mrisr_model_set_pag(self._h, int(block_mask), int(first_sample), int(n_samples)))
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU (Si et al. 2023; diffusers' ``enable_freeu``, same names and order): until ``disable_freeu``, every
+        forward and every sampler step on this UNet scales, in the resnets of ``freeu_stage_names`` and before hidden and skip are
+        concatenated, the first half of the hidden channels by ``b1`` (up block 0) / ``b2`` (up block 1) and the lowest spatial
+        frequencies of the skip tensor by ``s1`` / ``s2`` (diffusers' ``fourier_filter``, threshold 1).  The diffusers docs suggest
+        ``(0.9, 0.2, 1.5, 1.6)`` for SD-1.5.  Not with the feature cache, not in a training step."""
+        vals = check_freeu(s1, s2, b1, b2)  # before the library is touched
+        L.check(L.lib().mrisr_model_set_freeu(self._h, 1, *[C.c_float(v) for v in vals]))
+        self._freeu = vals
+
+    def disable_freeu(self):
+        """Turns FreeU off: the forward is the one of before, bit for bit, with the same launches and workspace."""
+        L.check(L.lib().mrisr_model_set_freeu(self._h, 0, C.c_float(1.0), C.c_float(1.0), C.c_float(1.0), C.c_float(1.0)))
+        self._freeu = None
+
+    @property
+    def freeu(self) -> Optional[Tuple[float, float, float, float]]:
+        """``(s1, s2, b1, b2)`` while FreeU is on, else ``None``."""
+        return getattr(self, "_freeu", None)
 
     def cache_shape(self, depth: int, B: int, h: int, w: int) -> Tuple[int, int, int, int]:
         """Logical (B, C, H, W) of the feature cache at ``depth`` for h x w latents: the input of the decoder stage that consumes

@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .models import ControlNetModel, UNet2DConditionModel, transformer_block_names
+from .models import ControlNetModel, UNet2DConditionModel, check_freeu, transformer_block_names
 
 
 def get_res_shifting_latents(hr_latents, lr_latents, timesteps, scheduler, noise=None):
@@ -289,6 +289,8 @@ class Sampler:
         Fewer launches per step for a bounded deviation from the uncached run.  ``interval=1`` (the default) is no cache at all:
         the step graph and the result of a sampler that never had one.  Changing either value captures the step graphs again."""
         interval, depth = check_cache(interval, depth, int(L.lib().mrisr_model_num_skips(self.unet._h)), self.controlnet is not None)
+        if interval > 1 and getattr(self.unet, "freeu", None) is not None:
+            raise ValueError("a feature cache (interval > 1) together with FreeU (unet.enable_freeu) is not supported")
         if interval > 1 and getattr(self, "tiles", None) is not None:
             raise ValueError("a feature cache (interval > 1) together with tiles is not supported")
         L.check(L.lib().mrisr_sampler_set_cache(self._h, interval, depth))
@@ -363,6 +365,9 @@ class Sampler:
             uncond_hidden_states: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Advance ``latents`` [B,C,h,w] (f32, updated IN PLACE) through every timestep.
 
+        FreeU needs no argument: a UNet with ``enable_freeu`` applies it in every step, with every option below
+        except the feature cache.
+
         Perturbed-attention guidance (Ahn et al. 2024): with ``pag_scale`` s > 0 every step also predicts eps_p -
         the same network with the self-attention map of the blocks ``pag_applied_layers`` selects (``check_pag``) replaced by the identity
         - in the same forward (perturbed rows first: 2B rows, 3B with classifier-free guidance) and steps with
@@ -382,6 +387,8 @@ class Sampler:
                 raise ValueError("the multistep solvers need [B,C,h,w] latents with C*h*w a multiple of 4")
             if lr_latents is not None and tuple(lr_latents.shape) != tuple(latents.shape):
                 raise ValueError(f"lr_latents must have the latents' shape {tuple(latents.shape)}, got {tuple(lr_latents.shape)}")
+        if self.cache_interval > 1 and getattr(self.unet, "freeu", None) is not None:  # (the UNet carries the FreeU state; run takes no argument)
+            raise ValueError("FreeU (unet.enable_freeu) together with a feature cache (cache interval > 1) is not supported")
         plan = None
         if self.tiles is not None:  # a tiled run: the canvas and everything shaped after it is checked here, before any launch
             if latents.ndim != 4:
@@ -484,8 +491,8 @@ class Sampler:
 @torch.no_grad()
 def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weight_dtype, accelerator, fixed_embeds,
                    num_inference_steps=20, adapter=None, solver=None, cache_interval=1, cache_depth=1, tile=None, tile_overlap=0,
-                   tile_window="gaussian", pag_scale=0.0, pag_applied_layers=("mid",), guidance_scale=1.0, guidance_rescale=0.0,
-                   uncond_embeds=None):
+                   tile_window="gaussian", pag_scale=0.0, pag_applied_layers=("mid",), freeu=None, guidance_scale=1.0,
+                   guidance_rescale=0.0, uncond_embeds=None):
     """Drop-in for the reference's validation sampler (res_srdiff.py:35-105): same inputs, same PIL panel out.
     The timestep loop is one fused sampler call; the per-step noise is drawn up front from the same global RNG
     stream, in the same order, as the reference's per-step ``torch.randn_like`` calls.  ``adapter`` (a T2I-Adapter):
@@ -496,8 +503,16 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     reference's stochastic step; no step noise is drawn then.  ``None``: the reference's sampler.  ``cache_interval`` /
     ``cache_depth``: the feature cache of ``Sampler.set_cache``; the defaults leave the panel unchanged.  ``tile`` / ``tile_overlap`` /
     ``tile_window``: tiled sampling as in ``Sampler.set_tiles`` (latent pixels); the defaults leave the panel unchanged.
-    ``pag_scale`` / ``pag_applied_layers``: perturbed-attention guidance as in ``Sampler.run``; the defaults leave the panel unchanged."""
+    ``pag_scale`` / ``pag_applied_layers``: perturbed-attention guidance as in ``Sampler.run``; the defaults leave the panel unchanged.
+    ``freeu``: a ``(s1, s2, b1, b2)`` tuple turns FreeU on (``unet.enable_freeu``) for this validation run; the UNet's previous FreeU
+    state is restored afterwards, also on an error.  ``None``: the UNet's own state is used as it is."""
     from PIL import Image
+
+    freeu_vals = None
+    if freeu is not None:
+        if len(tuple(freeu)) != 4:
+            raise ValueError(f"freeu must be a (s1, s2, b1, b2) tuple, got {freeu!r}")
+        freeu_vals = check_freeu(*freeu)
 
     if solver is not None:
         check_solver(solver, getattr(noise_scheduler, "solver_order", 2), getattr(noise_scheduler, "final_sigmas_type", "zero"),
@@ -520,21 +535,31 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     if solver is not None:
         n_noise = 0
     step_noise = torch.stack([torch.randn_like(latents) for _ in range(n_noise)]) if n_noise else None
-    sampler = Sampler(unet, noise_scheduler, controlnet, kind=solver if solver is not None else "resshift")
-    if cache_interval != 1 or cache_depth != 1:
-        sampler.set_cache(cache_interval, cache_depth)
-    if tile is not None:
-        sampler.set_tiles(tile, tile_overlap, tile_window)
-    feats = None
-    if adapter is not None:
-        cond = control_image if tuple(control_image.shape[-2:]) == tuple(lr_raw.shape[-2:]) else \
-            prepare_condition_image(lr_raw, tuple(lr_raw.shape[-2:]))
-        feats = adapter(cond.to(torch.float32))
-    sampler.run(latents, fixed_embeds[0:1], lr_latents=lr_anchor, step_noise=step_noise,
-                controlnet_cond=control_image if controlnet is not None else None, adapter_features=feats,
-                guidance_scale=guidance_scale, guidance_rescale=guidance_rescale,
-                uncond_hidden_states=uncond_embeds[0:1] if uncond_embeds is not None else None, pag_scale=pag_scale,
-                pag_applied_layers=pag_applied_layers)
+    freeu_prev = unet.freeu
+    if freeu_vals is not None:
+        unet.enable_freeu(*freeu_vals)
+    try:
+        sampler = Sampler(unet, noise_scheduler, controlnet, kind=solver if solver is not None else "resshift")
+        if cache_interval != 1 or cache_depth != 1:
+            sampler.set_cache(cache_interval, cache_depth)
+        if tile is not None:
+            sampler.set_tiles(tile, tile_overlap, tile_window)
+        feats = None
+        if adapter is not None:
+            cond = control_image if tuple(control_image.shape[-2:]) == tuple(lr_raw.shape[-2:]) else \
+                prepare_condition_image(lr_raw, tuple(lr_raw.shape[-2:]))
+            feats = adapter(cond.to(torch.float32))
+        sampler.run(latents, fixed_embeds[0:1], lr_latents=lr_anchor, step_noise=step_noise,
+                    controlnet_cond=control_image if controlnet is not None else None, adapter_features=feats,
+                    guidance_scale=guidance_scale, guidance_rescale=guidance_rescale,
+                    uncond_hidden_states=uncond_embeds[0:1] if uncond_embeds is not None else None, pag_scale=pag_scale,
+                    pag_applied_layers=pag_applied_layers)
+    finally:
+        if freeu_vals is not None:
+            if freeu_prev is None:
+                unet.disable_freeu()
+            else:
+                unet.enable_freeu(*freeu_prev)
     gen_vis = decode_to_vis(latents.to(weight_dtype), vae)
     hr_vis = decode_to_vis(hr_raw, vae, is_latent=False)
     lr_vis = decode_to_vis(lr_raw, vae, is_latent=False)

@@ -505,7 +505,10 @@ int launch_compose_ff_proj(const float* wp, const float* w2, const float* b2, co
 template <typename T> int launch_fill_zero(void* p, long long n, hipStream_t st);
 // packed bf16 rows -> OCP e4m3 rows + one f32 scale per row (amax / 448)
 int launch_quant_rows_fp8(const void* src_bf16, int rows, int cols, void* dst8, float* scales, hipStream_t st);
-// sampler steps (f32 state, NCHW like the reference's latents)
+
+// ---------------------------------------------------------------------------------------------
+// sampler steps (sampler.hip; f32 state, NCHW like the reference's latents)
+// ---------------------------------------------------------------------------------------------
 //   ddim: x = cx*x + ce*eps;   coefficients read from a device table indexed by *step_idx
 int launch_ddim_step(float* x, const float* eps, const float* coef_table, const int* step_idx, long long n,
                      hipStream_t st);
@@ -515,18 +518,15 @@ int launch_ddpm_step(float* x, const float* eps, const float* noise, const float
 int launch_resshift_step(float* x, const float* eps, const float* lr, const float* noise, const float* coef_table,
                          const int* step_idx, long long n, hipStream_t st);
 int launch_advance_step(int* step_idx, hipStream_t st);
-//   classifier-free guidance: eps2 = [uncond rows; cond rows] of a [2B] forward -> guided (and rescaled) eps -> the step above of kind
-//   `kind`; the new x goes to x [B] and to both halves of the staging buffer x2 [2B].  `per` = elements per sample (multiple of 4)
-int launch_guided_step(int kind, float* x, float* x2, const float* eps2, const float* lr, const float* noise, const float* coef_table,
-                       const int* step_idx, float clip, float g, float phi, int B, long long per, hipStream_t st, float* hist = nullptr,
-                       float* xc = nullptr, int order = 0);
-//   perturbed-attention guidance with classifier-free guidance: eps3 = [perturbed rows; uncond rows; cond rows] of a [3B] forward ->
-//   e = eps_u + g (eps_c - eps_u) + s (eps_c - eps_p), rescaled against eps_c as above -> the same update; the new x goes to x [B] and to
-//   all three thirds of the staging buffer x3 [3B].  (PAG alone is launch_guided_step on [eps_p; eps_c] with g = 1 + s.)
-int launch_pag_step(int kind, float* x, float* x3, const float* eps3, const float* lr, const float* noise, const float* coef_table,
-                    const int* step_idx, float clip, float g, float s, float phi, int B, long long per, hipStream_t st, float* hist = nullptr,
-                    float* xc = nullptr, int order = 0);
-//   multistep step (MRISR_STEP_UNIPC / MRISR_STEP_DPMSOLVERPP): rows of 16 floats (misc.hip), hist = `order` slabs of n floats (the x0
+//   the guided step on the K parts of a [K B] forward's output epsK -> guided (and rescaled by phi against the conditional part) eps ->
+//   the step above of kind `kind`; the new x goes to x [B] and to all K parts of the staging buffer xK [K B].  `per` = elements per sample
+//   (multiple of 4).  K = 2, classifier-free guidance: [uncond rows; cond rows], e = eps_u + g (eps_c - eps_u); s is not read.  K = 3,
+//   perturbed-attention guidance with it: [perturbed rows; uncond rows; cond rows], e = eps_u + g (eps_c - eps_u) + s (eps_c - eps_p).
+//   (PAG alone is K = 2 on [eps_p; eps_c] with g = 1 + s.)
+int launch_guided_step(int K, int kind, float* x, float* xK, const float* epsK, const float* lr, const float* noise, const float* coef_table,
+                       const int* step_idx, float clip, float g, float s, float phi, int B, long long per, hipStream_t st,
+                       float* hist = nullptr, float* xc = nullptr, int order = 0);
+//   multistep step (MRISR_STEP_UNIPC / MRISR_STEP_DPMSOLVERPP): rows of 16 floats (sampler.hip), hist = `order` slabs of n floats (the x0
 //   predictions, slot step % order), xc = the previous corrected state (UniPC) or nullptr; lr (or nullptr) anchors the state: the solver
 //   runs on x - lr.  n must be a multiple of 4.  The guided form is launch_guided_step with the same three buffers.
 int launch_multistep_step(float* x, const float* eps, const float* lr, const float* coef_table, const int* step_idx, float* hist, float* xc,

@@ -1,6 +1,5 @@
 // Small / bandwidth-bound kernels: time-embedding GEMV, direct convolutions for tiny channel counts,
-// NCHW<->NHWC boundary conversion, weight packers, and the fused sampler steps.
-#include "../../include/mrisr.h"  // mrisr_step_kind (the guided step serves all three)
+// NCHW<->NHWC boundary conversion, weight packers.  (The fused sampler steps live in sampler.hip.)
 #include "common.h"
 #include "prof.h"
 
@@ -859,514 +858,12 @@ int launch_fill_zero(void* p, long long n, hipStream_t st) {
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-// sampler steps: one fused elementwise kernel per step, coefficients from a device table indexed by a
-// device-resident step counter (so one captured hipGraph replays for every step, and the reference's
-// host sync on `prev_t > 0` (res_srdiff.py:92) disappears: sigma is simply 0 on the last row).
-// ------------------------------------------------------------------------------------------------
-__global__ void ddim_step_kernel(float* x, const float* eps, const float* coef, const int* step, long long n) {
-    const int s = *step;
-    const float cx = coef[2 * s], ce = coef[2 * s + 1];
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-        x[i] = cx * x[i] + ce * eps[i];
-}
-int launch_ddim_step(float* x, const float* eps, const float* coef_table, const int* step_idx, long long n,
-                     hipStream_t st) {
-    ProfScope ps("sampler_step", 0.0, 12.0 * n, st);
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(nblocks(n)), dim3(256), 0, st, x, eps, coef_table, step_idx, n);
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-__global__ void resshift_step_kernel(float* x, const float* eps, const float* lr, const float* noise_base,
-                                     const float* coef, const int* step, long long n) {
-    const int s = *step;
-    const float* noise = noise_base ? noise_base + (size_t)s * n : nullptr;  // one [n] slab per stochastic step
-    // row = {sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sigma}
-    const float sat = coef[4 * s], s1mat = coef[4 * s + 1], sap = coef[4 * s + 2], sig = coef[4 * s + 3];
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float l = lr[i];
-        const float x0 = (x[i] - (1.f - sat) * l - s1mat * eps[i]) / sat;
-        float v = sap * x0 + (1.f - sap) * l;
-        if (sig != 0.f && noise) v += sig * noise[i];
-        x[i] = v;
-    }
-}
-int launch_resshift_step(float* x, const float* eps, const float* lr, const float* noise, const float* coef_table,
-                         const int* step_idx, long long n, hipStream_t st) {
-    ProfScope ps("sampler_step", 0.0, 20.0 * n, st);
-    hipLaunchKernelGGL(resshift_step_kernel, dim3(nblocks(n)), dim3(256), 0, st, x, eps, lr, noise, coef_table,
-                       step_idx, n);
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-__global__ void ddpm_step_kernel(float* x, const float* eps, const float* noise_base, const float* coef, const int* step, float clip,
-                                 long long n) {
-    const int s = *step;
-    const float* noise = noise_base ? noise_base + (size_t)s * n : nullptr;
-    // row = {1/sqrt(abar_t), sqrt(1-abar_t)/sqrt(abar_t), x0 coefficient, x_t coefficient, sigma}
-    const float ia = coef[8 * s], ie = coef[8 * s + 1], c0 = coef[8 * s + 2], cx = coef[8 * s + 3], sig = coef[8 * s + 4];
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float xv = x[i];
-        float x0 = ia * xv - ie * eps[i];
-        if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
-        float v = c0 * x0 + cx * xv;
-        if (sig != 0.f && noise) v += sig * noise[i];
-        x[i] = v;
-    }
-}
-int launch_ddpm_step(float* x, const float* eps, const float* noise, const float* coef_table, const int* step_idx, float clip,
-                     long long n, hipStream_t st) {
-    ProfScope ps("sampler_step", 0.0, 16.0 * n, st);
-    hipLaunchKernelGGL(ddpm_step_kernel, dim3(nblocks(n)), dim3(256), 0, st, x, eps, noise, coef_table, step_idx, clip, n);
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-// ------------------------------------------------------------------------------------------------
-// guided step (classifier-free guidance): ONE launch that combines the two halves of a [2B] UNet output,
-//   e = eps_u + g (eps_c - eps_u);   phi > 0:  e *= phi std_b(eps_c) / std_b(e) + (1 - phi)   (per sample b, n-1 as torch.std),
-// applies the DDIM / Res-SRDiff / DDPM update above to x with e, and writes the new x to the caller's latents and to both halves
-// of the [2B] staging buffer the next forward reads.  eps2 rows 0..B-1 are unconditional, B..2B-1 conditional (diffusers' order).
-//   phi == 0: grid-stride over float4 pieces.
-//   phi  > 0: one workgroup of 1024 threads per sample; up to 16 Ki elements per sample both eps rows stay in registers (ITEMS
-//             float4 pieces per thread): means, then centred sums of squares (wave shuffle -> LDS over the 16 waves), then the
-//             update - eps2 is read once.  Larger samples take the re-reading kernel (three passes over eps2; correct, not fast).
-// A sample whose guided prediction has no spread (centred sum of squares below f32 resolution of its mean, or per == 1) is left
-// unrescaled, so an all-equal prediction cannot produce inf / NaN.
-// ------------------------------------------------------------------------------------------------
-struct StepRow { float a, b, c, d, sig; };
-__device__ __forceinline__ StepRow load_step_row(int kind, const float* coef, int s) {
-    StepRow r{0.f, 0.f, 0.f, 0.f, 0.f};
-    if (kind > MRISR_STEP_DDPM) return r;  // multistep kinds read their own 16-float row (multistep_value4)
-    if (kind == MRISR_STEP_DDIM) { r.a = coef[2 * s]; r.b = coef[2 * s + 1]; }
-    else if (kind == MRISR_STEP_RESSHIFT) { r.a = coef[4 * s]; r.b = coef[4 * s + 1]; r.c = coef[4 * s + 2]; r.sig = coef[4 * s + 3]; }
-    else { r.a = coef[8 * s]; r.b = coef[8 * s + 1]; r.c = coef[8 * s + 2]; r.d = coef[8 * s + 3]; r.sig = coef[8 * s + 4]; }
-    return r;
-}
-// the arithmetic of ddim_step_kernel / resshift_step_kernel / ddpm_step_kernel, one element
-__device__ __forceinline__ float step_value(int kind, const StepRow& r, float clip, float xv, float e, float l, float nz, bool noisy) {
-    if (kind == MRISR_STEP_DDIM) return r.a * xv + r.b * e;
-    float v;
-    if (kind == MRISR_STEP_RESSHIFT) {
-        const float x0 = (xv - (1.f - r.a) * l - r.b * e) / r.a;
-        v = r.c * x0 + (1.f - r.c) * l;
-    } else {
-        float x0 = r.a * xv - r.b * e;
-        if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
-        v = r.c * x0 + r.d * xv;
-    }
-    if (noisy) v += r.sig * nz;
-    return v;
-}
-__device__ __forceinline__ float4 step_value4(int kind, const StepRow& r, float clip, float4 xv, float4 e, float4 l, float4 nz, bool noisy) {
-    return make_float4(step_value(kind, r, clip, xv.x, e.x, l.x, nz.x, noisy), step_value(kind, r, clip, xv.y, e.y, l.y, nz.y, noisy),
-                       step_value(kind, r, clip, xv.z, e.z, l.z, nz.z, noisy), step_value(kind, r, clip, xv.w, e.w, l.w, nz.w, noisy));
-}
-__device__ __forceinline__ float4 guide4(float4 eu, float4 ec, float g) {
-    return make_float4(eu.x + g * (ec.x - eu.x), eu.y + g * (ec.y - eu.y), eu.z + g * (ec.z - eu.z), eu.w + g * (ec.w - eu.w));
-}
-__device__ __forceinline__ float sum4(float4 v) { return (v.x + v.y) + (v.z + v.w); }
-__device__ __forceinline__ float ssq4(float4 v, float m) {
-    const float a = v.x - m, b = v.y - m, c = v.z - m, d = v.w - m;
-    return (a * a + b * b) + (c * c + d * d);
-}
-__device__ __forceinline__ float4 scale4(float4 v, float f) { return make_float4(v.x * f, v.y * f, v.z * f, v.w * f); }
-// x, staging half 0, staging half 1 of one float4 piece
-__device__ __forceinline__ void store_x3(float* x, float* x2, long long n, long long i4, float4 v) {
-    reinterpret_cast<float4*>(x)[i4] = v;
-    reinterpret_cast<float4*>(x2)[i4] = v;
-    reinterpret_cast<float4*>(x2 + n)[i4] = v;
-}
-
-// ------------------------------------------------------------------------------------------------
-// multistep step (UniPC bh2 / DPM-Solver++ 2M, data prediction): ONE launch per step.  Every quantity of a linear multistep
-// step is linear in (z, eps, previous corrected state, history), z = x - LR (LR-anchored run) or x, so the host folds the order
-// schedule, the cold first step, disabled correctors and the final point into one row of 16 floats per step (capi.hip:
-// build_multistep_rows); a zero coefficient switches an absent term off and nothing here branches on the step:
-//   row = { m: z, eps | corrected state: z, eps, xc, h1, h2, h3 | next state: z, eps, xc, h1, h2, h3 | 0, 0 }
-//   m   = the x0 prediction at this step            -> history slot s % R   (h_k = the prediction k steps back, slot (s - k) % R)
-//   zc  = the corrected state (UniPC; else unused)  -> xc
-//   x   = next state + LR
-// The three forms are folded separately down to the raw inputs, so the next state never goes through the ill-conditioned
-// m = (z - sigma eps) / alpha of a high-noise step, and order 1 is the DDIM expression itself.  R = solver_order slabs of n floats;
-// the slot an element overwrites is the one it read as h_R.  The ring and xc are zeroed by the host at the start of a run.
-// ------------------------------------------------------------------------------------------------
-struct MsBuf { float* hist; float* xc; int R; };  // xc == nullptr: no corrector (DPM-Solver++)
-constexpr int MS_ROW = 16;
-__device__ __forceinline__ float4 fma4(float c, float4 v, float4 acc) {
-    return make_float4(fmaf(c, v.x, acc.x), fmaf(c, v.y, acc.y), fmaf(c, v.z, acc.z), fmaf(c, v.w, acc.w));
-}
-// one float4 piece: reads the history and xc, writes history slot s % R and xc, returns the new x
-__device__ __forceinline__ float4 multistep_value4(const float* __restrict__ row, const MsBuf& ms, int s, long long n, long long i,
-                                                   float4 xv, float4 e, float4 l) {
-    const float4 z = make_float4(xv.x - l.x, xv.y - l.y, xv.z - l.z, xv.w - l.w);
-    const int cur = s % ms.R;
-    float4 m = fma4(row[1], e, scale4(z, row[0]));
-    float4 zc = fma4(row[3], e, scale4(z, row[2]));
-    float4 zn = fma4(row[9], e, scale4(z, row[8]));
-    if (ms.xc) {
-        const float4 xc = reinterpret_cast<const float4*>(ms.xc)[i];
-        zc = fma4(row[4], xc, zc);
-        zn = fma4(row[10], xc, zn);
-    }
-#pragma unroll
-    for (int k = 1; k <= 3; ++k) {
-        if (k <= ms.R) {
-            const int slot = (cur + ms.R - (k % ms.R)) % ms.R;
-            const float4 h = reinterpret_cast<const float4*>(ms.hist + (size_t)slot * n)[i];
-            zc = fma4(row[4 + k], h, zc);
-            zn = fma4(row[10 + k], h, zn);
-        }
-    }
-    reinterpret_cast<float4*>(ms.hist + (size_t)cur * n)[i] = m;
-    if (ms.xc) reinterpret_cast<float4*>(ms.xc)[i] = zc;
-    return make_float4(zn.x + l.x, zn.y + l.y, zn.z + l.z, zn.w + l.w);
-}
-__global__ __launch_bounds__(256) void multistep_step_kernel(float* x, const float* eps, const float* lr, const float* coef, const int* step,
-                                                             MsBuf ms, long long n) {
-    const int s = *step;
-    const float* row = coef + (size_t)MS_ROW * s;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256) {
-        const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
-        reinterpret_cast<float4*>(x)[i] =
-            multistep_value4(row, ms, s, n, i, reinterpret_cast<const float4*>(x)[i], reinterpret_cast<const float4*>(eps)[i], l);
-    }
-}
-static int check_multistep(const float* x, const float* eps, const float* lr, const MsBuf& ms, long long n) {
-    MRISR_REQUIRE(x && eps && ms.hist && ms.R >= 1 && ms.R <= 3, "multistep step: null operand or solver order outside 1..3");
-    MRISR_REQUIRE(n > 0 && n % 4 == 0, "multistep step: C*h*w of the latents must be a multiple of 4");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    MRISR_REQUIRE(al16(x) && al16(eps) && al16(lr) && al16(ms.hist) && al16(ms.xc), "multistep step: operands must be 16-byte aligned");
-    return 0;
-}
-int launch_multistep_step(float* x, const float* eps, const float* lr, const float* coef_table, const int* step_idx, float* hist, float* xc,
-                          int order, long long n, hipStream_t st) {
-    const MsBuf ms{hist, xc, order};
-    MRISR_REQUIRE(coef_table && step_idx, "multistep step: null operand");
-    if (int rc = check_multistep(x, eps, lr, ms, n)) return rc;
-    // x in and out, eps, `order` history reads, one history write, xc in and out, lr
-    ProfScope ps("sampler_step", 0.0, (16.0 + 4.0 * order + (xc ? 8.0 : 0.0) + (lr ? 4.0 : 0.0)) * n, st);
-    hipLaunchKernelGGL(multistep_step_kernel, dim3(nblocks(n >> 2)), dim3(256), 0, st, x, eps, lr, coef_table, step_idx, ms, n);
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-// the update of one float4 piece of a guided step with the guided prediction e: the step kinds above, or the multistep step
-// (third: the staging buffer of a [3B] forward has one more part to keep current - the three-way step below)
-__device__ __forceinline__ void guided_apply4(int kind, const StepRow& r, const float* msrow, const MsBuf& ms, int s, float clip, float* x,
-                                              float* x2, const float* lr, const float* noise, long long n, long long i, float4 e,
-                                              bool third = false) {
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
-    float4 v;
-    if (msrow) {
-        v = multistep_value4(msrow, ms, s, n, i, xv, e, l);
-    } else {
-        const float4 nz = noise ? reinterpret_cast<const float4*>(noise)[i] : z4;
-        v = step_value4(kind, r, clip, xv, e, l, nz, noise != nullptr);
-    }
-    store_x3(x, x2, n, i, v);
-    if (third) reinterpret_cast<float4*>(x2 + 2 * n)[i] = v;
-}
-
-__global__ __launch_bounds__(256) void guided_step_kernel(int kind, float* x, float* x2, const float* eps2, const float* lr,
-                                                          const float* noise_base, const float* coef, const int* step, float clip,
-                                                          float g, long long n, MsBuf ms) {
-    const int s = *step;
-    const StepRow r = load_step_row(kind, coef, s);
-    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
-    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256) {
-        const float4 eu = reinterpret_cast<const float4*>(eps2)[i], ec = reinterpret_cast<const float4*>(eps2 + n)[i];
-        guided_apply4(kind, r, msrow, ms, s, clip, x, x2, lr, noise, n, i, guide4(eu, ec, g));
-    }
-}
-
-constexpr int GS_THREADS = 1024;
-// sums of (a, b) over the workgroup, the same value in every thread; `red` holds one pair per wave
-__device__ __forceinline__ void block_sum2(float& a, float& b, float* red) {
-    a = wsum(a);
-    b = wsum(b);
-    __syncthreads();  // the previous round's readers are done with `red`
-    if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = a; red[2 * (threadIdx.x >> 6) + 1] = b; }
-    __syncthreads();
-    float sa = 0.f, sb = 0.f;
-#pragma unroll
-    for (int w = 0; w < GS_THREADS / 64; ++w) { sa += red[2 * w]; sb += red[2 * w + 1]; }
-    a = sa;
-    b = sb;
-}
-// phi std(eps_c) / std(e) + (1 - phi) from the centred sums of squares (the n-1 of both estimates cancels)
-__device__ __forceinline__ float rescale_factor(float qc, float qe, float me, int per, float phi) {
-    if (per < 2 || !(qe > 1e-12f * (float)per * me * me) || !(qe > 0.f)) return 1.f;
-    const float f = phi * sqrtf(qc / qe) + (1.f - phi);
-    return f <= 3.0e38f ? f : 1.f;
-}
-
-template <int ITEMS>
-__global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(int kind, float* x, float* x2, const float* eps2, const float* lr,
-                                                                         const float* noise_base, const float* coef, const int* step,
-                                                                         float clip, float g, float phi, int B, int per, MsBuf ms) {
-    __shared__ float red[2 * GS_THREADS / 64];
-    const int s = *step;
-    const StepRow r = load_step_row(kind, coef, s);
-    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
-    const long long n = (long long)B * per;
-    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
-    const long long base4 = (long long)blockIdx.x * (per >> 2);
-    const int per4 = per >> 2;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 e[ITEMS], c[ITEMS];
-    float sc = 0.f, se = 0.f;
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k) {
-        const int j = threadIdx.x + k * GS_THREADS;
-        e[k] = z4; c[k] = z4;
-        if (j < per4) {
-            const float4 eu = reinterpret_cast<const float4*>(eps2)[base4 + j];
-            c[k] = reinterpret_cast<const float4*>(eps2 + n)[base4 + j];
-            e[k] = guide4(eu, c[k], g);
-            sc += sum4(c[k]); se += sum4(e[k]);
-        }
-    }
-    block_sum2(sc, se, red);
-    const float mc = sc / (float)per, me = se / (float)per;
-    float qc = 0.f, qe = 0.f;
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k)
-        if (threadIdx.x + k * GS_THREADS < per4) { qc += ssq4(c[k], mc); qe += ssq4(e[k], me); }
-    block_sum2(qc, qe, red);
-    const float f = rescale_factor(qc, qe, me, per, phi);
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k) {
-        const int j = threadIdx.x + k * GS_THREADS;
-        if (j < per4) guided_apply4(kind, r, msrow, ms, s, clip, x, x2, lr, noise, n, base4 + j, scale4(e[k], f));
-    }
-}
-// samples too large for the register file: the same three passes, each re-reading eps2
-__global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_reread_kernel(int kind, float* x, float* x2, const float* eps2, const float* lr,
-                                                                                const float* noise_base, const float* coef, const int* step,
-                                                                                float clip, float g, float phi, int B, int per, MsBuf ms) {
-    __shared__ float red[2 * GS_THREADS / 64];
-    const int s = *step;
-    const StepRow r = load_step_row(kind, coef, s);
-    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
-    const long long n = (long long)B * per;
-    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
-    const long long base4 = (long long)blockIdx.x * (per >> 2);
-    const int per4 = per >> 2;
-    const float4* pu = reinterpret_cast<const float4*>(eps2) + base4;
-    const float4* pc = reinterpret_cast<const float4*>(eps2 + n) + base4;
-    float sc = 0.f, se = 0.f;
-    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 c = pc[j]; sc += sum4(c); se += sum4(guide4(pu[j], c, g)); }
-    block_sum2(sc, se, red);
-    const float mc = sc / (float)per, me = se / (float)per;
-    float qc = 0.f, qe = 0.f;
-    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 c = pc[j]; qc += ssq4(c, mc); qe += ssq4(guide4(pu[j], c, g), me); }
-    block_sum2(qc, qe, red);
-    const float f = rescale_factor(qc, qe, me, per, phi);
-    for (int j = threadIdx.x; j < per4; j += GS_THREADS)
-        guided_apply4(kind, r, msrow, ms, s, clip, x, x2, lr, noise, n, base4 + j, scale4(guide4(pu[j], pc[j], g), f));
-}
-int launch_guided_step(int kind, float* x, float* x2, const float* eps2, const float* lr, const float* noise, const float* coef_table,
-                       const int* step_idx, float clip, float g, float phi, int B, long long per, hipStream_t st, float* hist, float* xc,
-                       int order) {
-    MRISR_REQUIRE(kind >= MRISR_STEP_DDIM && kind <= MRISR_STEP_DPMSOLVERPP, "guided step: unknown step kind");
-    const bool multistep = kind > MRISR_STEP_DDPM;
-    const MsBuf ms{multistep ? hist : nullptr, multistep && kind == MRISR_STEP_UNIPC ? xc : nullptr, multistep ? order : 0};
-    if (multistep) {
-        if (int rc = check_multistep(x, eps2, lr, ms, (long long)B * per)) return rc;
-        MRISR_REQUIRE(kind != MRISR_STEP_UNIPC || xc, "guided step: UniPC needs the corrected-state buffer");
-    }
-    MRISR_REQUIRE(x && x2 && eps2 && coef_table && step_idx && B > 0 && per > 0, "guided step: null operand");
-    MRISR_REQUIRE(per % 4 == 0 && per < (1ll << 31), "guided step: the per-sample size must be a multiple of 4");
-    MRISR_REQUIRE(phi >= 0.f && phi <= 1.f, "guided step: guidance_rescale must lie in [0, 1]");
-    MRISR_REQUIRE(kind != MRISR_STEP_RESSHIFT || lr, "guided step: Res-SRDiff needs the LR anchor latents");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    MRISR_REQUIRE(al16(x) && al16(x2) && al16(eps2) && al16(lr) && al16(noise), "guided step: operands must be 16-byte aligned");
-    const long long n = (long long)B * per;
-    if (kind != MRISR_STEP_RESSHIFT && !multistep) lr = nullptr;
-    if (kind == MRISR_STEP_DDIM || multistep) noise = nullptr;
-    // eps2 twice, x in, three stores of x; multistep: + `order` history reads, one history write, xc in and out
-    ProfScope ps("sampler_step", 0.0, (28.0 + (lr ? 4.0 : 0.0) + (multistep ? 4.0 * order + 4.0 + (ms.xc ? 8.0 : 0.0) : 0.0)) * n, st);
-    if (phi == 0.f) {
-        hipLaunchKernelGGL(guided_step_kernel, dim3(nblocks(n >> 2)), dim3(256), 0, st, kind, x, x2, eps2, lr, noise, coef_table, step_idx,
-                           clip, g, n, ms);
-    } else {
-#define MRISR_GS(ITEMS)                                                                                                              \
-    hipLaunchKernelGGL(guided_step_rescale_kernel<ITEMS>, dim3(B), dim3(GS_THREADS), 0, st, kind, x, x2, eps2, lr, noise, coef_table, \
-                       step_idx, clip, g, phi, B, (int)per, ms)
-        if (per <= 4 * GS_THREADS) MRISR_GS(1);
-        else if (per <= 8 * GS_THREADS) MRISR_GS(2);
-        else if (per <= 16 * GS_THREADS) MRISR_GS(4);
-        else
-            hipLaunchKernelGGL(guided_step_rescale_reread_kernel, dim3(B), dim3(GS_THREADS), 0, st, kind, x, x2, eps2, lr, noise,
-                               coef_table, step_idx, clip, g, phi, B, (int)per, ms);
-#undef MRISR_GS
-    }
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-// ------------------------------------------------------------------------------------------------
-// three-way step (perturbed-attention guidance together with classifier-free guidance): the guided step above for the [3B] output
-// eps3 = [eps_p; eps_u; eps_c] (perturbed rows first, conditional rows last),
-//   e = eps_u + g (eps_c - eps_u) + s (eps_c - eps_p);   phi > 0: e *= phi std_b(eps_c) / std_b(e) + (1 - phi)
-// in the same three forms (grid-stride; one workgroup per sample with the rows in registers; re-reading), the same degenerate-sample
-// guard, the same update through guided_apply4 - and the new x to all three thirds of the staging buffer.  s == 0 is the guided step.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float4 pag_guide4(float4 ep, float4 eu, float4 ec, float g, float s) {
-    // explicit fused multiply-adds: the guided part is then the very operation guide4 compiles to in the guided step's kernels (one
-    // rounding), whatever the compiler would contract here, so that s == 0 reproduces their bits
-    const float4 e = make_float4(fmaf(g, ec.x - eu.x, eu.x), fmaf(g, ec.y - eu.y, eu.y), fmaf(g, ec.z - eu.z, eu.z), fmaf(g, ec.w - eu.w, eu.w));
-    return make_float4(fmaf(s, ec.x - ep.x, e.x), fmaf(s, ec.y - ep.y, e.y), fmaf(s, ec.z - ep.z, e.z), fmaf(s, ec.w - ep.w, e.w));
-}
-__global__ __launch_bounds__(256) void pag_step_kernel(int kind, float* x, float* x3, const float* eps3, const float* lr, const float* noise_base,
-                                                       const float* coef, const int* step, float clip, float g, float sp, long long n, MsBuf ms) {
-    const int s = *step;
-    const StepRow r = load_step_row(kind, coef, s);
-    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
-    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256) {
-        const float4 ep = reinterpret_cast<const float4*>(eps3)[i], eu = reinterpret_cast<const float4*>(eps3 + n)[i];
-        const float4 ec = reinterpret_cast<const float4*>(eps3 + 2 * n)[i];
-        guided_apply4(kind, r, msrow, ms, s, clip, x, x3, lr, noise, n, i, pag_guide4(ep, eu, ec, g, sp), true);
-    }
-}
-template <int ITEMS>
-__global__ __launch_bounds__(GS_THREADS) void pag_step_rescale_kernel(int kind, float* x, float* x3, const float* eps3, const float* lr,
-                                                                      const float* noise_base, const float* coef, const int* step, float clip,
-                                                                      float g, float sp, float phi, int B, int per, MsBuf ms) {
-    __shared__ float red[2 * GS_THREADS / 64];
-    const int s = *step;
-    const StepRow r = load_step_row(kind, coef, s);
-    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
-    const long long n = (long long)B * per;
-    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
-    const long long base4 = (long long)blockIdx.x * (per >> 2);
-    const int per4 = per >> 2;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 e[ITEMS], c[ITEMS];
-    float sc = 0.f, se = 0.f;
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k) {
-        const int j = threadIdx.x + k * GS_THREADS;
-        e[k] = z4; c[k] = z4;
-        if (j < per4) {
-            const float4 ep = reinterpret_cast<const float4*>(eps3)[base4 + j], eu = reinterpret_cast<const float4*>(eps3 + n)[base4 + j];
-            c[k] = reinterpret_cast<const float4*>(eps3 + 2 * n)[base4 + j];
-            e[k] = pag_guide4(ep, eu, c[k], g, sp);
-            sc += sum4(c[k]); se += sum4(e[k]);
-        }
-    }
-    block_sum2(sc, se, red);
-    const float mc = sc / (float)per, me = se / (float)per;
-    float qc = 0.f, qe = 0.f;
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k)
-        if (threadIdx.x + k * GS_THREADS < per4) { qc += ssq4(c[k], mc); qe += ssq4(e[k], me); }
-    block_sum2(qc, qe, red);
-    const float f = rescale_factor(qc, qe, me, per, phi);
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k) {
-        const int j = threadIdx.x + k * GS_THREADS;
-        if (j < per4) guided_apply4(kind, r, msrow, ms, s, clip, x, x3, lr, noise, n, base4 + j, scale4(e[k], f), true);
-    }
-}
-__global__ __launch_bounds__(GS_THREADS) void pag_step_rescale_reread_kernel(int kind, float* x, float* x3, const float* eps3, const float* lr,
-                                                                             const float* noise_base, const float* coef, const int* step,
-                                                                             float clip, float g, float sp, float phi, int B, int per, MsBuf ms) {
-    __shared__ float red[2 * GS_THREADS / 64];
-    const int s = *step;
-    const StepRow r = load_step_row(kind, coef, s);
-    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
-    const long long n = (long long)B * per;
-    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
-    const long long base4 = (long long)blockIdx.x * (per >> 2);
-    const int per4 = per >> 2;
-    const float4* pp = reinterpret_cast<const float4*>(eps3) + base4;
-    const float4* pu = reinterpret_cast<const float4*>(eps3 + n) + base4;
-    const float4* pc = reinterpret_cast<const float4*>(eps3 + 2 * n) + base4;
-    float sc = 0.f, se = 0.f;
-    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 c = pc[j]; sc += sum4(c); se += sum4(pag_guide4(pp[j], pu[j], c, g, sp)); }
-    block_sum2(sc, se, red);
-    const float mc = sc / (float)per, me = se / (float)per;
-    float qc = 0.f, qe = 0.f;
-    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 c = pc[j]; qc += ssq4(c, mc); qe += ssq4(pag_guide4(pp[j], pu[j], c, g, sp), me); }
-    block_sum2(qc, qe, red);
-    const float f = rescale_factor(qc, qe, me, per, phi);
-    for (int j = threadIdx.x; j < per4; j += GS_THREADS)
-        guided_apply4(kind, r, msrow, ms, s, clip, x, x3, lr, noise, n, base4 + j, scale4(pag_guide4(pp[j], pu[j], pc[j], g, sp), f), true);
-}
-int launch_pag_step(int kind, float* x, float* x3, const float* eps3, const float* lr, const float* noise, const float* coef_table,
-                    const int* step_idx, float clip, float g, float sp, float phi, int B, long long per, hipStream_t st, float* hist, float* xc,
-                    int order) {
-    MRISR_REQUIRE(kind >= MRISR_STEP_DDIM && kind <= MRISR_STEP_DPMSOLVERPP, "pag step: unknown step kind");
-    const bool multistep = kind > MRISR_STEP_DDPM;
-    const MsBuf ms{multistep ? hist : nullptr, multistep && kind == MRISR_STEP_UNIPC ? xc : nullptr, multistep ? order : 0};
-    if (multistep) {
-        if (int rc = check_multistep(x, eps3, lr, ms, (long long)B * per)) return rc;
-        MRISR_REQUIRE(kind != MRISR_STEP_UNIPC || xc, "pag step: UniPC needs the corrected-state buffer");
-    }
-    MRISR_REQUIRE(x && x3 && eps3 && coef_table && step_idx && B > 0 && per > 0, "pag step: null operand");
-    MRISR_REQUIRE(per % 4 == 0 && per < (1ll << 31), "pag step: the per-sample size must be a multiple of 4");
-    MRISR_REQUIRE(phi >= 0.f && phi <= 1.f, "pag step: guidance_rescale must lie in [0, 1]");
-    MRISR_REQUIRE(std::isfinite(sp) && sp >= 0.f, "pag step: pag_scale must be finite and >= 0");
-    MRISR_REQUIRE(kind != MRISR_STEP_RESSHIFT || lr, "pag step: Res-SRDiff needs the LR anchor latents");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    MRISR_REQUIRE(al16(x) && al16(x3) && al16(eps3) && al16(lr) && al16(noise), "pag step: operands must be 16-byte aligned");
-    const long long n = (long long)B * per;
-    if (kind != MRISR_STEP_RESSHIFT && !multistep) lr = nullptr;
-    if (kind == MRISR_STEP_DDIM || multistep) noise = nullptr;
-    // eps3 three times, x in, four stores of x; multistep: + `order` history reads, one history write, xc in and out
-    ProfScope ps("sampler_step", 0.0, (32.0 + (lr ? 4.0 : 0.0) + (multistep ? 4.0 * order + 4.0 + (ms.xc ? 8.0 : 0.0) : 0.0)) * n, st);
-    if (phi == 0.f) {
-        hipLaunchKernelGGL(pag_step_kernel, dim3(nblocks(n >> 2)), dim3(256), 0, st, kind, x, x3, eps3, lr, noise, coef_table, step_idx, clip, g,
-                           sp, n, ms);
-    } else {
-#define MRISR_PS(ITEMS)                                                                                                           \
-    hipLaunchKernelGGL(pag_step_rescale_kernel<ITEMS>, dim3(B), dim3(GS_THREADS), 0, st, kind, x, x3, eps3, lr, noise, coef_table, \
-                       step_idx, clip, g, sp, phi, B, (int)per, ms)
-        if (per <= 4 * GS_THREADS) MRISR_PS(1);
-        else if (per <= 8 * GS_THREADS) MRISR_PS(2);
-        else if (per <= 16 * GS_THREADS) MRISR_PS(4);
-        else
-            hipLaunchKernelGGL(pag_step_rescale_reread_kernel, dim3(B), dim3(GS_THREADS), 0, st, kind, x, x3, eps3, lr, noise, coef_table,
-                               step_idx, clip, g, sp, phi, B, (int)per, ms);
-#undef MRISR_PS
-    }
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
 __global__ __launch_bounds__(256) void select_row_kernel(const float* __restrict__ table, const int* __restrict__ step, int first, float* __restrict__ out, int n) {
     const float* row = table + (size_t)(*step - first) * n;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) out[i] = row[i];
 }
 int launch_select_row(const float* table, const int* step, int first, float* out, int n, hipStream_t st) {
     hipLaunchKernelGGL(select_row_kernel, dim3((n + 255) / 256), dim3(256), 0, st, table, step, first, out, n);
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-__global__ void advance_step_kernel(int* step) { *step += 1; }
-int launch_advance_step(int* step_idx, hipStream_t st) {
-    hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(1), 0, st, step_idx);
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-__global__ void resshift_forward_kernel(const float* hr, const float* lr, const float* noise, const float* ac,
-                                        const long long* t, int t_is_scalar, float* out, int B, long long per) {
-    const long long n = (long long)B * per;
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int b = (int)(i / per);
-        const float a = ac[t_is_scalar ? t[0] : t[b]];
-        const float ra = sqrtf(a);
-        out[i] = ra * hr[i] + (1.f - ra) * lr[i] + sqrtf(1.f - a) * noise[i];
-    }
-}
-int launch_resshift_forward(const float* hr, const float* lr, const float* noise, const float* alphas_cumprod,
-                            const long long* t, int t_is_scalar, float* out, int B, long long per_sample,
-                            hipStream_t st) {
-    hipLaunchKernelGGL(resshift_forward_kernel, dim3(nblocks((long long)B * per_sample)), dim3(256), 0, st, hr, lr,
-                       noise, alphas_cumprod, t, t_is_scalar, out, B, per_sample);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -1,4 +1,4 @@
-// Host-side runtime pieces shared by model.hip / capi.hip / adapter.hip: device buffers, the bump arena, packed weights.
+// Host-side runtime pieces shared by model.hip / capi.hip / sampler.hip / adapter.hip: device buffers, the bump arena, packed weights.
 #pragma once
 #include <cstdint>
 #include <map>

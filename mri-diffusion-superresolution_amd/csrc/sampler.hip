@@ -1,0 +1,1254 @@
+// The graph sampler: the fused step kernels, the host side that plans one step, captures it into a hipGraph and
+// replays it, every mrisr_sampler_* entry point and the single-step test entries (mrisr_op_*_step).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "api.h"
+#include "model.h"
+#include "prof.h"
+#include "step_plan.h"
+
+namespace mrisr {
+
+__device__ __forceinline__ float wsum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+static inline unsigned nblocks(long long total) {
+    long long b = (total + 255) / 256;
+    return (unsigned)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
+}
+
+// ------------------------------------------------------------------------------------------------
+// sampler steps: one fused elementwise kernel per step, coefficients from a device table indexed by a
+// device-resident step counter (so one captured hipGraph replays for every step, and the reference's
+// host sync on `prev_t > 0` (res_srdiff.py:92) disappears: sigma is simply 0 on the last row).
+// ------------------------------------------------------------------------------------------------
+__global__ void ddim_step_kernel(float* x, const float* eps, const float* coef, const int* step, long long n) {
+    const int s = *step;
+    const float cx = coef[2 * s], ce = coef[2 * s + 1];
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+        x[i] = cx * x[i] + ce * eps[i];
+}
+int launch_ddim_step(float* x, const float* eps, const float* coef_table, const int* step_idx, long long n,
+                     hipStream_t st) {
+    ProfScope ps("sampler_step", 0.0, 12.0 * n, st);
+    hipLaunchKernelGGL(ddim_step_kernel, dim3(nblocks(n)), dim3(256), 0, st, x, eps, coef_table, step_idx, n);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+__global__ void resshift_step_kernel(float* x, const float* eps, const float* lr, const float* noise_base,
+                                     const float* coef, const int* step, long long n) {
+    const int s = *step;
+    const float* noise = noise_base ? noise_base + (size_t)s * n : nullptr;  // one [n] slab per stochastic step
+    // row = {sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sigma}
+    const float sat = coef[4 * s], s1mat = coef[4 * s + 1], sap = coef[4 * s + 2], sig = coef[4 * s + 3];
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float l = lr[i];
+        const float x0 = (x[i] - (1.f - sat) * l - s1mat * eps[i]) / sat;
+        float v = sap * x0 + (1.f - sap) * l;
+        if (sig != 0.f && noise) v += sig * noise[i];
+        x[i] = v;
+    }
+}
+int launch_resshift_step(float* x, const float* eps, const float* lr, const float* noise, const float* coef_table,
+                         const int* step_idx, long long n, hipStream_t st) {
+    ProfScope ps("sampler_step", 0.0, 20.0 * n, st);
+    hipLaunchKernelGGL(resshift_step_kernel, dim3(nblocks(n)), dim3(256), 0, st, x, eps, lr, noise, coef_table,
+                       step_idx, n);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+__global__ void ddpm_step_kernel(float* x, const float* eps, const float* noise_base, const float* coef, const int* step, float clip,
+                                 long long n) {
+    const int s = *step;
+    const float* noise = noise_base ? noise_base + (size_t)s * n : nullptr;
+    // row = {1/sqrt(abar_t), sqrt(1-abar_t)/sqrt(abar_t), x0 coefficient, x_t coefficient, sigma}
+    const float ia = coef[8 * s], ie = coef[8 * s + 1], c0 = coef[8 * s + 2], cx = coef[8 * s + 3], sig = coef[8 * s + 4];
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float xv = x[i];
+        float x0 = ia * xv - ie * eps[i];
+        if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
+        float v = c0 * x0 + cx * xv;
+        if (sig != 0.f && noise) v += sig * noise[i];
+        x[i] = v;
+    }
+}
+int launch_ddpm_step(float* x, const float* eps, const float* noise, const float* coef_table, const int* step_idx, float clip,
+                     long long n, hipStream_t st) {
+    ProfScope ps("sampler_step", 0.0, 16.0 * n, st);
+    hipLaunchKernelGGL(ddpm_step_kernel, dim3(nblocks(n)), dim3(256), 0, st, x, eps, noise, coef_table, step_idx, clip, n);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+// ------------------------------------------------------------------------------------------------
+// guided step (classifier-free guidance): ONE launch that combines the two halves of a [2B] UNet output,
+//   e = eps_u + g (eps_c - eps_u);   phi > 0:  e *= phi std_b(eps_c) / std_b(e) + (1 - phi)   (per sample b, n-1 as torch.std),
+// applies the DDIM / Res-SRDiff / DDPM update above to x with e, and writes the new x to the caller's latents and to both halves
+// of the [2B] staging buffer the next forward reads.  eps2 rows 0..B-1 are unconditional, B..2B-1 conditional (diffusers' order).
+//   phi == 0: grid-stride over float4 pieces.
+//   phi  > 0: one workgroup of 1024 threads per sample; up to 16 Ki elements per sample both eps rows stay in registers (ITEMS
+//             float4 pieces per thread): means, then centred sums of squares (wave shuffle -> LDS over the 16 waves), then the
+//             update - eps2 is read once.  Larger samples take the re-reading kernel (three passes over eps2; correct, not fast).
+// A sample whose guided prediction has no spread (centred sum of squares below f32 resolution of its mean, or per == 1) is left
+// unrescaled, so an all-equal prediction cannot produce inf / NaN.
+// The same kernels, templated on the number of parts K, serve the three-way step of perturbed-attention guidance with classifier-free
+// guidance (K = 3): eps3 = [eps_p; eps_u; eps_c] (perturbed rows first, conditional rows last),
+//   e = eps_u + g (eps_c - eps_u) + s (eps_c - eps_p),
+// the same rescale, degenerate-sample guard and update, the new x to all three thirds of the staging buffer.  s == 0 is the K = 2 step.
+// (PAG alone is the K = 2 step on [eps_p; eps_c] with g = 1 + s.)
+// ------------------------------------------------------------------------------------------------
+struct StepRow { float a, b, c, d, sig; };
+__device__ __forceinline__ StepRow load_step_row(int kind, const float* coef, int s) {
+    StepRow r{0.f, 0.f, 0.f, 0.f, 0.f};
+    if (kind > MRISR_STEP_DDPM) return r;  // multistep kinds read their own 16-float row (multistep_value4)
+    if (kind == MRISR_STEP_DDIM) { r.a = coef[2 * s]; r.b = coef[2 * s + 1]; }
+    else if (kind == MRISR_STEP_RESSHIFT) { r.a = coef[4 * s]; r.b = coef[4 * s + 1]; r.c = coef[4 * s + 2]; r.sig = coef[4 * s + 3]; }
+    else { r.a = coef[8 * s]; r.b = coef[8 * s + 1]; r.c = coef[8 * s + 2]; r.d = coef[8 * s + 3]; r.sig = coef[8 * s + 4]; }
+    return r;
+}
+// the arithmetic of ddim_step_kernel / resshift_step_kernel / ddpm_step_kernel, one element
+__device__ __forceinline__ float step_value(int kind, const StepRow& r, float clip, float xv, float e, float l, float nz, bool noisy) {
+    if (kind == MRISR_STEP_DDIM) return r.a * xv + r.b * e;
+    float v;
+    if (kind == MRISR_STEP_RESSHIFT) {
+        const float x0 = (xv - (1.f - r.a) * l - r.b * e) / r.a;
+        v = r.c * x0 + (1.f - r.c) * l;
+    } else {
+        float x0 = r.a * xv - r.b * e;
+        if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
+        v = r.c * x0 + r.d * xv;
+    }
+    if (noisy) v += r.sig * nz;
+    return v;
+}
+__device__ __forceinline__ float4 step_value4(int kind, const StepRow& r, float clip, float4 xv, float4 e, float4 l, float4 nz, bool noisy) {
+    return make_float4(step_value(kind, r, clip, xv.x, e.x, l.x, nz.x, noisy), step_value(kind, r, clip, xv.y, e.y, l.y, nz.y, noisy),
+                       step_value(kind, r, clip, xv.z, e.z, l.z, nz.z, noisy), step_value(kind, r, clip, xv.w, e.w, l.w, nz.w, noisy));
+}
+// the guided prediction of one float4 piece of a [K B] forward's output, K = 2: [eps_u; eps_c], K = 3: [eps_p; eps_u; eps_c]
+//   e = eps_u + g (eps_c - eps_u)  (+ s (eps_c - eps_p), K = 3);   c = the conditional part, which the rescale rule measures against.
+// Explicit fused multiply-adds: one rounding per term whatever the compiler would contract, so the K = 3 step at s == 0 has the K = 2
+// step's bits.
+template <int K>
+__device__ __forceinline__ float4 guide4(const float* epsK, long long n, long long i, float g, float s, float4& c) {
+    const float4 eu = reinterpret_cast<const float4*>(epsK + (K - 2) * n)[i];
+    c = reinterpret_cast<const float4*>(epsK + (K - 1) * n)[i];
+    const float4 e = make_float4(fmaf(g, c.x - eu.x, eu.x), fmaf(g, c.y - eu.y, eu.y), fmaf(g, c.z - eu.z, eu.z), fmaf(g, c.w - eu.w, eu.w));
+    if (K == 2) return e;
+    const float4 ep = reinterpret_cast<const float4*>(epsK)[i];
+    return make_float4(fmaf(s, c.x - ep.x, e.x), fmaf(s, c.y - ep.y, e.y), fmaf(s, c.z - ep.z, e.z), fmaf(s, c.w - ep.w, e.w));
+}
+__device__ __forceinline__ float sum4(float4 v) { return (v.x + v.y) + (v.z + v.w); }
+__device__ __forceinline__ float ssq4(float4 v, float m) {
+    const float a = v.x - m, b = v.y - m, c = v.z - m, d = v.w - m;
+    return (a * a + b * b) + (c * c + d * d);
+}
+__device__ __forceinline__ float4 scale4(float4 v, float f) { return make_float4(v.x * f, v.y * f, v.z * f, v.w * f); }
+// one float4 piece to x and to every part of the [K B] staging buffer
+template <int K>
+__device__ __forceinline__ void store_parts(float* x, float* xK, long long n, long long i4, float4 v) {
+    reinterpret_cast<float4*>(x)[i4] = v;
+#pragma unroll
+    for (int k = 0; k < K; ++k) reinterpret_cast<float4*>(xK + k * n)[i4] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// multistep step (UniPC bh2 / DPM-Solver++ 2M, data prediction): ONE launch per step.  Every quantity of a linear multistep
+// step is linear in (z, eps, previous corrected state, history), z = x - LR (LR-anchored run) or x, so the host folds the order
+// schedule, the cold first step, disabled correctors and the final point into one row of 16 floats per step
+// (build_multistep_rows below); a zero coefficient switches an absent term off and nothing here branches on the step:
+//   row = { m: z, eps | corrected state: z, eps, xc, h1, h2, h3 | next state: z, eps, xc, h1, h2, h3 | 0, 0 }
+//   m   = the x0 prediction at this step            -> history slot s % R   (h_k = the prediction k steps back, slot (s - k) % R)
+//   zc  = the corrected state (UniPC; else unused)  -> xc
+//   x   = next state + LR
+// The three forms are folded separately down to the raw inputs, so the next state never goes through the ill-conditioned
+// m = (z - sigma eps) / alpha of a high-noise step, and order 1 is the DDIM expression itself.  R = solver_order slabs of n floats;
+// the slot an element overwrites is the one it read as h_R.  The ring and xc are zeroed by the host at the start of a run.
+// ------------------------------------------------------------------------------------------------
+struct MsBuf { float* hist; float* xc; int R; };  // xc == nullptr: no corrector (DPM-Solver++)
+constexpr int MS_ROW = 16;
+__device__ __forceinline__ float4 fma4(float c, float4 v, float4 acc) {
+    return make_float4(fmaf(c, v.x, acc.x), fmaf(c, v.y, acc.y), fmaf(c, v.z, acc.z), fmaf(c, v.w, acc.w));
+}
+// one float4 piece: reads the history and xc, writes history slot s % R and xc, returns the new x
+__device__ __forceinline__ float4 multistep_value4(const float* __restrict__ row, const MsBuf& ms, int s, long long n, long long i,
+                                                   float4 xv, float4 e, float4 l) {
+    const float4 z = make_float4(xv.x - l.x, xv.y - l.y, xv.z - l.z, xv.w - l.w);
+    const int cur = s % ms.R;
+    float4 m = fma4(row[1], e, scale4(z, row[0]));
+    float4 zc = fma4(row[3], e, scale4(z, row[2]));
+    float4 zn = fma4(row[9], e, scale4(z, row[8]));
+    if (ms.xc) {
+        const float4 xc = reinterpret_cast<const float4*>(ms.xc)[i];
+        zc = fma4(row[4], xc, zc);
+        zn = fma4(row[10], xc, zn);
+    }
+#pragma unroll
+    for (int k = 1; k <= 3; ++k) {
+        if (k <= ms.R) {
+            const int slot = (cur + ms.R - (k % ms.R)) % ms.R;
+            const float4 h = reinterpret_cast<const float4*>(ms.hist + (size_t)slot * n)[i];
+            zc = fma4(row[4 + k], h, zc);
+            zn = fma4(row[10 + k], h, zn);
+        }
+    }
+    reinterpret_cast<float4*>(ms.hist + (size_t)cur * n)[i] = m;
+    if (ms.xc) reinterpret_cast<float4*>(ms.xc)[i] = zc;
+    return make_float4(zn.x + l.x, zn.y + l.y, zn.z + l.z, zn.w + l.w);
+}
+__global__ __launch_bounds__(256) void multistep_step_kernel(float* x, const float* eps, const float* lr, const float* coef, const int* step,
+                                                             MsBuf ms, long long n) {
+    const int s = *step;
+    const float* row = coef + (size_t)MS_ROW * s;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256) {
+        const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
+        reinterpret_cast<float4*>(x)[i] =
+            multistep_value4(row, ms, s, n, i, reinterpret_cast<const float4*>(x)[i], reinterpret_cast<const float4*>(eps)[i], l);
+    }
+}
+static int check_multistep(const float* x, const float* eps, const float* lr, const MsBuf& ms, long long n) {
+    MRISR_REQUIRE(x && eps && ms.hist && ms.R >= 1 && ms.R <= 3, "multistep step: null operand or solver order outside 1..3");
+    MRISR_REQUIRE(n > 0 && n % 4 == 0, "multistep step: C*h*w of the latents must be a multiple of 4");
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    MRISR_REQUIRE(al16(x) && al16(eps) && al16(lr) && al16(ms.hist) && al16(ms.xc), "multistep step: operands must be 16-byte aligned");
+    return 0;
+}
+int launch_multistep_step(float* x, const float* eps, const float* lr, const float* coef_table, const int* step_idx, float* hist, float* xc,
+                          int order, long long n, hipStream_t st) {
+    const MsBuf ms{hist, xc, order};
+    MRISR_REQUIRE(coef_table && step_idx, "multistep step: null operand");
+    if (int rc = check_multistep(x, eps, lr, ms, n)) return rc;
+    // x in and out, eps, `order` history reads, one history write, xc in and out, lr
+    ProfScope ps("sampler_step", 0.0, (16.0 + 4.0 * order + (xc ? 8.0 : 0.0) + (lr ? 4.0 : 0.0)) * n, st);
+    hipLaunchKernelGGL(multistep_step_kernel, dim3(nblocks(n >> 2)), dim3(256), 0, st, x, eps, lr, coef_table, step_idx, ms, n);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+// the update of one float4 piece of a guided step with the guided prediction e: the step kinds above, or the multistep step; the
+// new x goes to the caller's latents and to all K parts of the staging buffer
+template <int K>
+__device__ __forceinline__ void guided_apply4(int kind, const StepRow& r, const float* msrow, const MsBuf& ms, int s, float clip, float* x,
+                                              float* xK, const float* lr, const float* noise, long long n, long long i, float4 e) {
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 xv = reinterpret_cast<const float4*>(x)[i];
+    const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
+    float4 v;
+    if (msrow) {
+        v = multistep_value4(msrow, ms, s, n, i, xv, e, l);
+    } else {
+        const float4 nz = noise ? reinterpret_cast<const float4*>(noise)[i] : z4;
+        v = step_value4(kind, r, clip, xv, e, l, nz, noise != nullptr);
+    }
+    store_parts<K>(x, xK, n, i, v);
+}
+constexpr int GS_THREADS = 1024;
+// sums of (a, b) over the workgroup, the same value in every thread; `red` holds one pair per wave
+__device__ __forceinline__ void block_sum2(float& a, float& b, float* red) {
+    a = wsum(a);
+    b = wsum(b);
+    __syncthreads();  // the previous round's readers are done with `red`
+    if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = a; red[2 * (threadIdx.x >> 6) + 1] = b; }
+    __syncthreads();
+    float sa = 0.f, sb = 0.f;
+#pragma unroll
+    for (int w = 0; w < GS_THREADS / 64; ++w) { sa += red[2 * w]; sb += red[2 * w + 1]; }
+    a = sa;
+    b = sb;
+}
+// phi std(eps_c) / std(e) + (1 - phi) from the centred sums of squares (the n-1 of both estimates cancels)
+__device__ __forceinline__ float rescale_factor(float qc, float qe, float me, int per, float phi) {
+    if (per < 2 || !(qe > 1e-12f * (float)per * me * me) || !(qe > 0.f)) return 1.f;
+    const float f = phi * sqrtf(qc / qe) + (1.f - phi);
+    return f <= 3.0e38f ? f : 1.f;
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void guided_step_kernel(int kind, float* x, float* xK, const float* epsK, const float* lr,
+                                                          const float* noise_base, const float* coef, const int* step, float clip,
+                                                          float g, float sp, long long n, MsBuf ms) {
+    const int s = *step;
+    const StepRow r = load_step_row(kind, coef, s);
+    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
+    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256) {
+        float4 c;
+        const float4 e = guide4<K>(epsK, n, i, g, sp, c);
+        guided_apply4<K>(kind, r, msrow, ms, s, clip, x, xK, lr, noise, n, i, e);
+    }
+}
+
+template <int K, int ITEMS>
+__global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(int kind, float* x, float* xK, const float* epsK, const float* lr,
+                                                                         const float* noise_base, const float* coef, const int* step,
+                                                                         float clip, float g, float sp, float phi, int B, int per, MsBuf ms) {
+    __shared__ float red[2 * GS_THREADS / 64];
+    const int s = *step;
+    const StepRow r = load_step_row(kind, coef, s);
+    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
+    const long long n = (long long)B * per;
+    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
+    const long long base4 = (long long)blockIdx.x * (per >> 2);
+    const int per4 = per >> 2;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 e[ITEMS], c[ITEMS];
+    float sc = 0.f, se = 0.f;
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int j = threadIdx.x + k * GS_THREADS;
+        e[k] = z4; c[k] = z4;
+        if (j < per4) {
+            e[k] = guide4<K>(epsK, n, base4 + j, g, sp, c[k]);
+            sc += sum4(c[k]); se += sum4(e[k]);
+        }
+    }
+    block_sum2(sc, se, red);
+    const float mc = sc / (float)per, me = se / (float)per;
+    float qc = 0.f, qe = 0.f;
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k)
+        if (threadIdx.x + k * GS_THREADS < per4) { qc += ssq4(c[k], mc); qe += ssq4(e[k], me); }
+    block_sum2(qc, qe, red);
+    const float f = rescale_factor(qc, qe, me, per, phi);
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int j = threadIdx.x + k * GS_THREADS;
+        if (j < per4) guided_apply4<K>(kind, r, msrow, ms, s, clip, x, xK, lr, noise, n, base4 + j, scale4(e[k], f));
+    }
+}
+// samples too large for the register file: the same three passes, each re-reading epsK
+template <int K>
+__global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_reread_kernel(int kind, float* x, float* xK, const float* epsK, const float* lr,
+                                                                                const float* noise_base, const float* coef, const int* step,
+                                                                                float clip, float g, float sp, float phi, int B, int per, MsBuf ms) {
+    __shared__ float red[2 * GS_THREADS / 64];
+    const int s = *step;
+    const StepRow r = load_step_row(kind, coef, s);
+    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
+    const long long n = (long long)B * per;
+    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
+    const long long base4 = (long long)blockIdx.x * (per >> 2);
+    const int per4 = per >> 2;
+    float4 c;
+    float sc = 0.f, se = 0.f;
+    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 e = guide4<K>(epsK, n, base4 + j, g, sp, c); sc += sum4(c); se += sum4(e); }
+    block_sum2(sc, se, red);
+    const float mc = sc / (float)per, me = se / (float)per;
+    float qc = 0.f, qe = 0.f;
+    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 e = guide4<K>(epsK, n, base4 + j, g, sp, c); qc += ssq4(c, mc); qe += ssq4(e, me); }
+    block_sum2(qc, qe, red);
+    const float f = rescale_factor(qc, qe, me, per, phi);
+    for (int j = threadIdx.x; j < per4; j += GS_THREADS)
+        guided_apply4<K>(kind, r, msrow, ms, s, clip, x, xK, lr, noise, n, base4 + j, scale4(guide4<K>(epsK, n, base4 + j, g, sp, c), f));
+}
+
+template <int K>
+static void launch_guided_kernels(int kind, float* x, float* xK, const float* epsK, const float* lr, const float* noise, const float* coef_table,
+                                  const int* step_idx, float clip, float g, float sp, float phi, int B, long long per, hipStream_t st, MsBuf ms) {
+    const long long n = (long long)B * per;
+    if (phi == 0.f) {
+        hipLaunchKernelGGL(guided_step_kernel<K>, dim3(nblocks(n >> 2)), dim3(256), 0, st, kind, x, xK, epsK, lr, noise, coef_table, step_idx,
+                           clip, g, sp, n, ms);
+        return;
+    }
+#define MRISR_GS(ITEMS)                                                                                                                   \
+    hipLaunchKernelGGL((guided_step_rescale_kernel<K, ITEMS>), dim3(B), dim3(GS_THREADS), 0, st, kind, x, xK, epsK, lr, noise, coef_table, \
+                       step_idx, clip, g, sp, phi, B, (int)per, ms)
+    if (per <= 4 * GS_THREADS) MRISR_GS(1);
+    else if (per <= 8 * GS_THREADS) MRISR_GS(2);
+    else if (per <= 16 * GS_THREADS) MRISR_GS(4);
+    else
+        hipLaunchKernelGGL(guided_step_rescale_reread_kernel<K>, dim3(B), dim3(GS_THREADS), 0, st, kind, x, xK, epsK, lr, noise, coef_table,
+                           step_idx, clip, g, sp, phi, B, (int)per, ms);
+#undef MRISR_GS
+}
+int launch_guided_step(int K, int kind, float* x, float* xK, const float* epsK, const float* lr, const float* noise, const float* coef_table,
+                       const int* step_idx, float clip, float g, float sp, float phi, int B, long long per, hipStream_t st, float* hist,
+                       float* xc, int order) {
+    MRISR_REQUIRE(K == 2 || K == 3, "guided step: 2 or 3 parts");
+    const std::string who = K == 3 ? "pag step: " : "guided step: ";
+    MRISR_REQUIRE(kind >= MRISR_STEP_DDIM && kind <= MRISR_STEP_DPMSOLVERPP, who + "unknown step kind");
+    const bool multistep = kind > MRISR_STEP_DDPM;
+    const MsBuf ms{multistep ? hist : nullptr, multistep && kind == MRISR_STEP_UNIPC ? xc : nullptr, multistep ? order : 0};
+    if (multistep) {
+        if (int rc = check_multistep(x, epsK, lr, ms, (long long)B * per)) return rc;
+        MRISR_REQUIRE(kind != MRISR_STEP_UNIPC || xc, who + "UniPC needs the corrected-state buffer");
+    }
+    MRISR_REQUIRE(x && xK && epsK && coef_table && step_idx && B > 0 && per > 0, who + "null operand");
+    MRISR_REQUIRE(per % 4 == 0 && per < (1ll << 31), who + "the per-sample size must be a multiple of 4");
+    MRISR_REQUIRE(phi >= 0.f && phi <= 1.f, who + "guidance_rescale must lie in [0, 1]");
+    if (K == 3) MRISR_REQUIRE(std::isfinite(sp) && sp >= 0.f, who + "pag_scale must be finite and >= 0");
+    MRISR_REQUIRE(kind != MRISR_STEP_RESSHIFT || lr, who + "Res-SRDiff needs the LR anchor latents");
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    MRISR_REQUIRE(al16(x) && al16(xK) && al16(epsK) && al16(lr) && al16(noise), who + "operands must be 16-byte aligned");
+    const long long n = (long long)B * per;
+    if (kind != MRISR_STEP_RESSHIFT && !multistep) lr = nullptr;
+    if (kind == MRISR_STEP_DDIM || multistep) noise = nullptr;
+    // epsK K times, x in, K + 1 stores of x; multistep: + `order` history reads, one history write, xc in and out
+    ProfScope ps("sampler_step", 0.0, ((K == 3 ? 32.0 : 28.0) + (lr ? 4.0 : 0.0) + (multistep ? 4.0 * order + 4.0 + (ms.xc ? 8.0 : 0.0) : 0.0)) * n, st);
+    if (K == 3) launch_guided_kernels<3>(kind, x, xK, epsK, lr, noise, coef_table, step_idx, clip, g, sp, phi, B, per, st, ms);
+    else launch_guided_kernels<2>(kind, x, xK, epsK, lr, noise, coef_table, step_idx, clip, g, sp, phi, B, per, st, ms);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+__global__ void advance_step_kernel(int* step) { *step += 1; }
+int launch_advance_step(int* step_idx, hipStream_t st) {
+    hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(1), 0, st, step_idx);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+__global__ void resshift_forward_kernel(const float* hr, const float* lr, const float* noise, const float* ac,
+                                        const long long* t, int t_is_scalar, float* out, int B, long long per) {
+    const long long n = (long long)B * per;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int b = (int)(i / per);
+        const float a = ac[t_is_scalar ? t[0] : t[b]];
+        const float ra = sqrtf(a);
+        out[i] = ra * hr[i] + (1.f - ra) * lr[i] + sqrtf(1.f - a) * noise[i];
+    }
+}
+int launch_resshift_forward(const float* hr, const float* lr, const float* noise, const float* alphas_cumprod,
+                            const long long* t, int t_is_scalar, float* out, int B, long long per_sample,
+                            hipStream_t st) {
+    hipLaunchKernelGGL(resshift_forward_kernel, dim3(nblocks((long long)B * per_sample)), dim3(256), 0, st, hr, lr,
+                       noise, alphas_cumprod, t, t_is_scalar, out, B, per_sample);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // namespace mrisr
+
+// =================================================================================================
+// host side: the sampler handle, its setters, the run
+// =================================================================================================
+using namespace mrisr;
+
+struct mrisr_model : public Model {};
+
+__global__ void load_t_kernel(long long* cur_t, const long long* table, const int* step) { *cur_t = table[*step]; }
+
+static int g_temb_table = -1;  // test hook: -1 = MRISR_TEMB_TABLE (default 1), 0 off, 1 on
+extern "C" void mrisr_debug_temb_table(int on) { g_temb_table = on; }
+static bool temb_table_enabled() {
+    static const int env = [] { const char* e = getenv("MRISR_TEMB_TABLE"); return e ? atoi(e) : 1; }();
+    return g_temb_table < 0 ? env != 0 : g_temb_table != 0;
+}
+// ---- multistep solvers (UniPC bh2 / DPM-Solver++ 2M): one row of 16 folded coefficients per step (layout: multistep_value4 above) ----
+// rho of the UniPC predictor / corrector: solves the leading k x k block of R rho = b, rows of R = [r_1 .. r_{p-1}, 1]^(j-1),
+// b_j = (phi_{j+1}-recurrence value) j! / B(h), B(h) = expm1(-h) (bh2); Gaussian elimination with partial pivoting, k <= 3
+static void unipc_rho(const double* rks, int p, double h, int k, double* rho) {
+    const double hh = -h, Bh = std::expm1(hh);
+    double A[3][4];
+    double phik = std::expm1(hh) / hh - 1.0, fact = 1.0;
+    for (int j = 1; j <= p; ++j) {
+        if (j <= k) {
+            for (int c = 0; c < k; ++c) A[j - 1][c] = std::pow(rks[c], j - 1);
+            A[j - 1][k] = phik * fact / Bh;
+        }
+        fact *= j + 1;
+        phik = phik / hh - 1.0 / fact;
+    }
+    for (int c = 0; c < k; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < k; ++r) if (std::fabs(A[r][c]) > std::fabs(A[piv][c])) piv = r;
+        for (int q = 0; q <= k; ++q) std::swap(A[c][q], A[piv][q]);
+        for (int r = c + 1; r < k; ++r) {
+            const double f = A[r][c] / A[c][c];
+            for (int q = c; q <= k; ++q) A[r][q] -= f * A[c][q];
+        }
+    }
+    for (int r = k - 1; r >= 0; --r) {
+        double v = A[r][k];
+        for (int q = r + 1; q < k; ++q) v -= A[r][q] * rho[q];
+        rho[r] = v / A[r][r];
+    }
+}
+struct MultistepOpts {
+    int order = 2;
+    int final_zero = 1;        // 1: the last step lands on alpha = 1, sigma = 0 (diffusers' "zero"); 0: on alphas_cumprod[0] ("sigma_min")
+    int lower_order_final = 1;
+    std::vector<int> disable_corrector;  // UniPC: step indices without a corrector
+};
+// abar: the clamped alphas_cumprod at the n grid timesteps followed by the final point's (ignored when final_zero).  The run starts
+// cold at `first`: order 1 and no corrector there.  All arithmetic in double.
+static std::vector<float> build_multistep_rows(int kind, const MultistepOpts& o, const std::vector<double>& abar, int n, int first) {
+    std::vector<double> al(n + 1), sg(n + 1), lam(n + 1);
+    for (int i = 0; i <= n; ++i) {
+        al[i] = std::sqrt(abar[i]); sg[i] = std::sqrt(1.0 - abar[i]); lam[i] = std::log(al[i] / sg[i]);
+    }
+    if (o.final_zero) { al[n] = 1.0; sg[n] = 0.0; lam[n] = INFINITY; }
+    auto order_at = [&](int i) {  // order of the predictor step from t_i
+        int p = std::min(o.order, i - first + 1);
+        if (kind == MRISR_STEP_UNIPC) { if (o.lower_order_final) p = std::min(p, n - i); }
+        else if (i == n - 1 && ((o.lower_order_final && n < 15) || o.final_zero)) p = 1;
+        return std::max(p, 1);
+    };
+    std::vector<float> rows((size_t)n * 16, 0.f);
+    for (int i = first; i < n; ++i) {
+        const double ma = 1.0 / al[i], mb = -sg[i] / al[i];
+        // corrected state zc = c[0] z + c[1] eps + c[2] xc + c[3..5] h_1..3      (m = ma z + mb eps folded in)
+        double c[6] = {1.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        const bool corr = kind == MRISR_STEP_UNIPC && i > first &&
+                          std::find(o.disable_corrector.begin(), o.disable_corrector.end(), i) == o.disable_corrector.end();
+        if (corr) {
+            const int p = order_at(i - 1);
+            const double h = lam[i] - lam[i - 1], phi1 = std::expm1(-h), Bh = phi1;
+            double rks[3], rho[3] = {0.5, 0.0, 0.0};
+            for (int k = 1; k < p; ++k) rks[k - 1] = (lam[i - 1 - k] - lam[i - 1]) / h;
+            rks[p - 1] = 1.0;
+            if (p > 1) unipc_rho(rks, p, h, p, rho);
+            const double cm = -al[i] * Bh * rho[p - 1];
+            double ch1 = -al[i] * phi1 + al[i] * Bh * rho[p - 1];
+            c[0] = cm * ma; c[1] = cm * mb; c[2] = sg[i] / sg[i - 1];
+            for (int k = 1; k < p; ++k) { c[3 + k] = -al[i] * Bh * rho[k - 1] / rks[k - 1]; ch1 += al[i] * Bh * rho[k - 1] / rks[k - 1]; }
+            c[3] = ch1;
+        }
+        // next state from (zc, m, h_1, h_2)
+        const int p = order_at(i);
+        double pz, pm, ph[3] = {0.0, 0.0, 0.0};
+        if (i == n - 1 && o.final_zero) { pz = 0.0; pm = 1.0; }  // h = inf: the state IS the x0 prediction
+        else {
+            const double h = lam[i + 1] - lam[i], e1 = std::expm1(-h);
+            pz = sg[i + 1] / sg[i];
+            pm = -al[i + 1] * e1;
+            if (kind == MRISR_STEP_UNIPC && p > 1) {
+                double rks[3], rho[3] = {0.5, 0.0, 0.0};
+                for (int k = 1; k < p; ++k) rks[k - 1] = (lam[i - k] - lam[i]) / h;
+                rks[p - 1] = 1.0;
+                if (p > 2) unipc_rho(rks, p, h, p - 1, rho);
+                for (int k = 1; k < p; ++k) { ph[k - 1] = -al[i + 1] * e1 * rho[k - 1] / rks[k - 1]; pm -= ph[k - 1]; }
+            } else if (kind == MRISR_STEP_DPMSOLVERPP && p > 1) {
+                const double r0 = (lam[i] - lam[i - 1]) / h;
+                ph[0] = 0.5 * al[i + 1] * e1 / r0;
+                pm -= ph[0];
+            }
+        }
+        const double nx[6] = {pz * c[0] + pm * ma, pz * c[1] + pm * mb, pz * c[2], pz * c[3] + ph[0], pz * c[4] + ph[1], pz * c[5] + ph[2]};
+        float* r = &rows[(size_t)i * 16];
+        r[0] = (float)ma; r[1] = (float)mb;
+        for (int k = 0; k < 6; ++k) { r[2 + k] = (float)c[k]; r[8 + k] = (float)nx[k]; }
+    }
+    return rows;
+}
+
+struct mrisr_sampler {
+    mrisr_model* unet = nullptr;
+    mrisr_model* cnet = nullptr;
+    int kind = 0, n_steps = 0, first = 0, last = 0;
+    float clip = 0.f;
+    float guidance_scale = 1.f, guidance_rescale = 0.f;  // classifier-free guidance of mrisr_sampler_run_guided
+    unsigned pag_mask = 0;  // perturbed-attention guidance of mrisr_sampler_run_pag: the applied transformer blocks and the scale
+    float pag_scale = 0.f;
+    int n_captures = 0;     // step graphs captured so far (mrisr_sampler_num_captures)
+    std::vector<float> sigma;  // host copy of each step's noise coefficient (which steps read a step_noise slab)
+    DevBuf d_ts, d_coef, d_step, d_curt, d_eps;
+    // multistep kinds: solver options, the clamped alphas_cumprod on the grid (+ alphas_cumprod[0]), the host rows of the current range,
+    // the history ring of `order` x0 predictions and (UniPC) the previous corrected state
+    MultistepOpts ms;
+    std::vector<double> ms_abar;
+    std::vector<float> ms_rows;
+    DevBuf d_hist, d_xc;
+    bool multistep() const { return kind > MRISR_STEP_DDPM; }
+    void rebuild_rows() { if (multistep()) ms_rows = build_multistep_rows(kind, ms, ms_abar, n_steps, first); }
+    DevBuf d_x2;  // guided / pag runs: the [K B] f32 latents the forwards read (every part = the state; the fused step keeps them current)
+    DevBuf tp_unet, tp_cnet;  // per-run time-embedding tables [scratch | n_steps x tproj_total] (f32)
+    std::vector<std::unique_ptr<DevBuf>> res_bufs;   // ControlNet -> UNet residuals (NHWC, compute dtype)
+    std::vector<std::unique_ptr<DevBuf>> intra_bufs;  // adapter features converted once
+    // feature cache: step i of a run over [first, last) is full (and stores the cache) when (i - first) % interval == 0,
+    // shallow (reads it) otherwise; interval 1 = no cache: the body, the plan and the graph without it
+    int cache_interval = 1, cache_depth = 1;
+    DevBuf d_cache;
+    // tiled sampling: tile_h == 0 is off.  A run whose grid has more than one tile gathers the state into d_xt
+    // [NB*T, C, t_h, t_w], runs the forward there into d_et and blends d_et into d_eps; the grid and the window tables live in d_tiles
+    int tile_h = 0, tile_w = 0, tile_oh = 0, tile_ow = 0, tile_window = MRISR_TILE_GAUSSIAN;
+    TilePlan tiles;
+    DevBuf d_tiles, d_xt, d_et;
+    hipGraphExec_t exec = nullptr;
+    hipGraphExec_t exec_shallow = nullptr;  // cache_interval > 1: exec is the full + store step, this the shallow one
+    StepPlan plan = new_step_plan();        // what exec / exec_shallow were captured from
+    void drop_graphs() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (exec_shallow) (void)hipGraphExecDestroy(exec_shallow);
+        exec = exec_shallow = nullptr;
+    }
+    hipStream_t own_stream = nullptr;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    ~mrisr_sampler() {
+        drop_graphs();
+        if (own_stream) (void)hipStreamDestroy(own_stream);
+        if (ev_in) (void)hipEventDestroy(ev_in);
+        if (ev_out) (void)hipEventDestroy(ev_out);
+    }
+};
+
+// The options that exclude each other, every rule once: the first rule that (UNet state, ControlNet attached, cache interval, tiles on,
+// PAG run) violates, or null.  The setters call it with the value they are about to set, the run with what is set; always before any launch.
+static const char* option_conflict(const Model& U, bool has_cnet, int cache_interval, bool tiles_on, bool pag_run) {
+    const bool cached = cache_interval > 1;
+    if (cached && has_cnet) return "a feature cache (interval > 1) together with a ControlNet is not supported";
+    if (cached && tiles_on) return "a feature cache (interval > 1) together with tiles is not supported";
+    if (cached && U.freeu.on) return "a feature cache (interval > 1) together with FreeU is not supported (mrisr_model_set_freeu)";
+    if (cached && pag_run) return "pag run: a feature cache with interval > 1 is not supported (the shallow pass skips the blocks pag perturbs)";
+    if (pag_run && U.cfg.fp8_attention) return "pag run: not supported on a UNet built with fp8_attention";
+    if (pag_run && U.keep) return "pag run: a training forward is being recorded";
+    if (U.freeu.on && U.keep) return "FreeU: a training forward is being recorded";
+    return nullptr;
+}
+
+extern "C" {
+
+int mrisr_sampler_create(mrisr_model* unet, mrisr_model* controlnet, int step_kind, const int64_t* timesteps,
+                         int n_steps, const float* alphas_cumprod, int n_train, mrisr_sampler** out) {
+    API_BEGIN
+    MRISR_REQUIRE(unet && timesteps && alphas_cumprod && out && n_steps > 0, "bad argument");
+    MRISR_REQUIRE(!controlnet || controlnet->cfg.compute_dtype == unet->cfg.compute_dtype, "UNet/ControlNet dtype mismatch");
+    std::unique_ptr<mrisr_sampler> s(new mrisr_sampler());
+    s->unet = unet;
+    s->cnet = controlnet;
+    s->kind = step_kind;
+    s->n_steps = n_steps;
+    s->first = 0;
+    s->last = n_steps;
+    std::vector<long long> ts(timesteps, timesteps + n_steps);
+    MRISR_REQUIRE(step_kind >= MRISR_STEP_DDIM && step_kind <= MRISR_STEP_DPMSOLVERPP, "unknown step kind");
+    std::vector<float> coef((size_t)n_steps * (s->multistep() ? 16 : 8), 0.f);
+    for (int i = 0; i < n_steps; ++i) {
+        const long long t = ts[i];
+        MRISR_REQUIRE(t >= 0 && t < n_train, "timestep out of range");
+        // zero-terminal-SNR tables (rescale_betas_zero_snr, nb ResDif c11:46) end in abar = 0 exactly and "trailing" spacing
+        // samples that entry first: every step divides by sqrt(abar_t) (res_srdiff.py:86), so it is clamped to 2^-24 here
+        // (the reference itself would produce inf)
+        const double a_t = std::max((double)alphas_cumprod[t], 5.9604644775390625e-8);
+        if (s->multistep()) {
+            MRISR_REQUIRE(i == 0 || t < ts[i - 1], "multistep solvers need strictly decreasing timesteps");
+            s->ms_abar.push_back(a_t);
+        } else if (step_kind == MRISR_STEP_DDIM) {
+            // t_prev = t - T/n; alpha_prev = alpha[t_prev] or alpha[0] (set_alpha_to_one=False)
+            const long long tp = t - n_train / n_steps;
+            const double a_p = tp >= 0 ? alphas_cumprod[tp] : alphas_cumprod[0];
+            coef[2 * i] = (float)std::sqrt(a_p / a_t);
+            coef[2 * i + 1] = (float)(std::sqrt(1.0 - a_p) - std::sqrt(a_p * (1.0 - a_t) / a_t));
+        } else if (step_kind == MRISR_STEP_DDPM) {
+            // diffusers DDPMScheduler.step, variance_type "fixed_small" (un-vendored; BASELINE config 1)
+            const long long tp = t - n_train / n_steps;
+            const double a_p = tp >= 0 ? alphas_cumprod[tp] : 1.0;
+            const double al = a_t / a_p, be = 1.0 - al;
+            coef[8 * i] = (float)(1.0 / std::sqrt(a_t));
+            coef[8 * i + 1] = (float)(std::sqrt(1.0 - a_t) / std::sqrt(a_t));
+            coef[8 * i + 2] = (float)(std::sqrt(a_p) * be / (1.0 - a_t));
+            coef[8 * i + 3] = (float)(std::sqrt(al) * (1.0 - a_p) / (1.0 - a_t));
+            coef[8 * i + 4] = t > 0 ? (float)std::sqrt(std::max((1.0 - a_p) / (1.0 - a_t) * be, 1e-20)) : 0.f;
+        } else {
+            // reference res_srdiff.py:83-96: prev_t = timesteps[i+1] or 0; last step uses alpha[0] and no noise
+            const long long tp = i + 1 < n_steps ? ts[i + 1] : 0;
+            const double a_p = alphas_cumprod[tp];
+            coef[4 * i] = (float)std::sqrt(a_t);
+            coef[4 * i + 1] = (float)std::sqrt(1.0 - a_t);
+            coef[4 * i + 2] = (float)std::sqrt(a_p);
+            coef[4 * i + 3] = tp > 0 ? (float)std::sqrt((1.0 - a_p) / (1.0 - a_t) * (1.0 - a_t / a_p)) : 0.f;
+        }
+    }
+    if (s->multistep()) {  // defaults: order 2, diffusers' "zero" final point; mrisr_sampler_set_solver changes them
+        s->ms_abar.push_back(std::max((double)alphas_cumprod[0], 5.9604644775390625e-8));
+        s->rebuild_rows();
+    }
+    s->sigma.assign(n_steps, 0.f);
+    for (int i = 0; i < n_steps && !s->multistep(); ++i)
+        s->sigma[i] = step_kind == MRISR_STEP_DDPM ? coef[8 * i + 4] : (step_kind == MRISR_STEP_RESSHIFT ? coef[4 * i + 3] : 0.f);
+    TRY(s->d_ts.reserve(sizeof(long long) * n_steps, false));
+    TRY(s->d_coef.reserve(sizeof(float) * coef.size(), false));
+    TRY(s->d_step.reserve(16, true));
+    TRY(s->d_curt.reserve(16, true));
+    MRISR_CHECK_HIP(hipMemcpy(s->d_ts.p, ts.data(), sizeof(long long) * n_steps, hipMemcpyHostToDevice));
+    MRISR_CHECK_HIP(hipMemcpy(s->d_coef.p, coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice));
+    *out = s.release();
+    return 0;
+    API_END
+}
+void mrisr_sampler_destroy(mrisr_sampler* s) { delete s; }
+int mrisr_sampler_set_range(mrisr_sampler* s, int first_step, int last_step) {
+    API_BEGIN
+    MRISR_REQUIRE(s && first_step >= 0 && first_step <= last_step && last_step <= s->n_steps, "step range");
+    s->first = first_step;
+    s->last = last_step;
+    s->rebuild_rows();  // multistep kinds start cold at first_step: order 1, no corrector (allocates: hence the guard)
+    return 0;
+    API_END
+}
+
+int mrisr_sampler_set_solver(mrisr_sampler* s, int solver_order, int final_sigmas_zero, int lower_order_final,
+                             const int* disable_corrector, int n_disable) {
+    API_BEGIN
+    MRISR_REQUIRE(s, "null sampler");
+    MRISR_REQUIRE(s->multistep(), "solver options belong to the multistep kinds (UniPC, DPM-Solver++)");
+    MRISR_REQUIRE(solver_order >= 1 && solver_order <= (s->kind == MRISR_STEP_UNIPC ? 3 : 2),
+                  "solver_order: 1..3 for UniPC, 1..2 for DPM-Solver++");
+    MRISR_REQUIRE(lower_order_final == 1, "lower_order_final = false is not implemented");
+    MRISR_REQUIRE(n_disable >= 0 && (n_disable == 0 || disable_corrector), "disable_corrector: a list of step indices");
+    MRISR_REQUIRE(n_disable == 0 || s->kind == MRISR_STEP_UNIPC, "disable_corrector belongs to UniPC");
+    s->ms.order = solver_order;
+    s->ms.final_zero = final_sigmas_zero ? 1 : 0;
+    s->ms.lower_order_final = 1;
+    s->ms.disable_corrector.assign(disable_corrector, disable_corrector + n_disable);
+    s->rebuild_rows();
+    return 0;
+    API_END
+}
+
+int mrisr_sampler_set_clip(mrisr_sampler* s, float clip_sample_range) {
+    MRISR_REQUIRE(s, "null sampler");
+    MRISR_REQUIRE(s->kind == MRISR_STEP_DDPM, "x0 clipping belongs to the DDPM step");
+    if (s->clip != clip_sample_range) s->drop_graphs();  // baked into the graph
+    s->clip = clip_sample_range;
+    return 0;
+}
+
+int mrisr_sampler_set_cache(mrisr_sampler* s, int interval, int depth) {
+    MRISR_REQUIRE(s, "null sampler");
+    MRISR_REQUIRE(interval >= 1, "cache interval must be >= 1 (1: no cache)");
+    MRISR_REQUIRE(depth >= 1 && depth <= s->unet->num_skips() - 1, "cache depth must lie in 1 .. num_skips - 1");
+    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, interval, s->tile_h != 0, false);
+    MRISR_REQUIRE(!conflict, conflict);
+    if (interval != s->cache_interval || depth != s->cache_depth) s->drop_graphs();  // the next run captures again
+    s->cache_interval = interval;
+    s->cache_depth = depth;
+    return 0;
+}
+
+int mrisr_sampler_set_tiles(mrisr_sampler* s, int tile_h, int tile_w, int overlap_h, int overlap_w, int window) {
+    MRISR_REQUIRE(s, "null sampler");
+    if (tile_h == 0) {  // off: the body, the plan and the graph without tiles
+        if (s->tile_h) s->drop_graphs();
+        s->tile_h = s->tile_w = s->tile_oh = s->tile_ow = 0;
+        return 0;
+    }
+    const int d = 1 << (s->unet->cfg.num_levels - 1);  // the UNet's own divisibility rule for h and w
+    MRISR_REQUIRE(tile_h >= d && tile_w >= d && tile_h % d == 0 && tile_w % d == 0, "tile: a multiple of 2^(num_levels-1), at least that");
+    MRISR_REQUIRE(overlap_h >= 0 && overlap_w >= 0 && overlap_h < tile_h && overlap_w < tile_w && overlap_h % d == 0 && overlap_w % d == 0,
+                  "overlap: a multiple of 2^(num_levels-1) in 0 .. tile - 1");
+    MRISR_REQUIRE(window == MRISR_TILE_UNIFORM || window == MRISR_TILE_GAUSSIAN, "window: MRISR_TILE_UNIFORM or MRISR_TILE_GAUSSIAN");
+    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, s->cache_interval, true, false);
+    MRISR_REQUIRE(!conflict, conflict);
+    if (tile_h != s->tile_h || tile_w != s->tile_w || overlap_h != s->tile_oh || overlap_w != s->tile_ow || window != s->tile_window)
+        s->drop_graphs();
+    s->tile_h = tile_h; s->tile_w = tile_w; s->tile_oh = overlap_h; s->tile_ow = overlap_w; s->tile_window = window;
+    return 0;
+}
+
+int mrisr_sampler_set_guidance(mrisr_sampler* s, float guidance_scale, float guidance_rescale) {
+    MRISR_REQUIRE(s, "null sampler");
+    MRISR_REQUIRE(std::isfinite(guidance_scale), "guidance_scale must be finite");
+    MRISR_REQUIRE(guidance_rescale >= 0.f && guidance_rescale <= 1.f, "guidance_rescale must lie in [0, 1]");
+    s->guidance_scale = guidance_scale;  // passed to the step kernel by value: part of the step plan
+    s->guidance_rescale = guidance_rescale;
+    return 0;
+}
+
+int mrisr_sampler_set_pag(mrisr_sampler* s, unsigned block_mask, float pag_scale) {
+    MRISR_REQUIRE(s, "null sampler");
+    MRISR_REQUIRE(std::isfinite(pag_scale) && pag_scale >= 0.f, "pag_scale must be finite and >= 0");
+    const int nb = s->unet->num_transformer_blocks();
+    MRISR_REQUIRE(nb >= 32 || (block_mask >> nb) == 0, "pag: block_mask selects blocks the UNet does not have (mrisr_model_num_transformer_blocks)");
+    MRISR_REQUIRE(pag_scale == 0.f || block_mask != 0, "pag: pag_scale > 0 needs at least one applied block in block_mask");
+    s->pag_mask = block_mask;  // both are part of the step plan of the next mrisr_sampler_run_pag
+    s->pag_scale = pag_scale;
+    return 0;
+}
+int mrisr_sampler_num_captures(const mrisr_sampler* s) { return s ? s->n_captures : 0; }
+
+}  // extern "C"
+
+// ---- one run: mrisr_sampler_run (K = 1: B rows everywhere), mrisr_sampler_run_guided (K = 2) and mrisr_sampler_run_pag (pag: K = 2 or 3).
+// The forwards see NB = K B rows - ehs / cond / intrablock carry K B, the latents are read from the staging buffer; the state, the LR
+// anchor and the noise stay [B].  sampler_run_impl builds the StepPlan of the run piece by piece (run_check, run_operands, run_buffers,
+// run_temb_table), then run_steps captures step_body(plan) - or reuses the graph when the plan is the stored one - and replays it.
+struct RunArgs {
+    mrisr_tensor* latents;
+    const mrisr_tensor *lr, *noise, *ehs, *cond, *intrablock;
+    int n_intrablock, K;
+    bool pag;
+};
+static long long numel(const mrisr_tensor* t) { long long k = 1; for (int i = 0; i < t->ndim; ++i) k *= t->shape[i]; return k; }
+static mrisr_tensor plan_tensor(const PlanTensor& t, int cdt) {
+    mrisr_tensor m{};
+    m.data = const_cast<void*>(t.data); m.dtype = cdt; m.layout = MRISR_NHWC; m.ndim = 4;
+    for (int i = 0; i < 4; ++i) m.shape[i] = t.shape[i];
+    return m;
+}
+
+// argument checks; fills the plan's step configuration
+static int run_check(mrisr_sampler* s, const RunArgs& a, StepPlan& p) {
+    const int K = a.K;
+    const bool guided = K > 1, pag = a.pag;
+    const mrisr_tensor *latents = a.latents, *ehs = a.ehs, *cond = a.cond;
+    MRISR_REQUIRE(s && latents && ehs, "null argument");
+    MRISR_REQUIRE(latents->ndim == 4 && latents->dtype == MRISR_F32 && latents->layout == MRISR_NCHW, "latents: f32 NCHW");
+    MRISR_REQUIRE(s->kind != MRISR_STEP_RESSHIFT || a.lr, "Res-SRDiff needs the LR anchor latents");
+    MRISR_REQUIRE(!s->multistep() || !a.noise, "the multistep solvers are deterministic: step_noise is refused");
+    MRISR_REQUIRE(!s->cnet || cond, "ControlNet needs the condition image");
+    const bool cached = s->cache_interval > 1;
+    if (pag) {
+        MRISR_REQUIRE(K == 2 || K == 3, "pag run: the forward has 2B rows (pag alone) or 3B rows (with classifier-free guidance)");
+        MRISR_REQUIRE(s->pag_mask != 0, "pag run: no applied block (mrisr_sampler_set_pag)");
+    }
+    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, s->cache_interval, s->tile_h != 0, pag);
+    MRISR_REQUIRE(!conflict, conflict);
+    Model& U = *s->unet;
+    const int B = (int)latents->shape[0], h = (int)latents->shape[2], w = (int)latents->shape[3];
+    const int NB = K * B;  // rows of every forward (of the canvas; a tiled run multiplies them by T)
+    const long long per = (long long)latents->shape[1] * h * w;
+    const long long n = (long long)B * per;
+    // every operand the step kernels index is checked against the latents here: the kernels themselves read
+    // lr[i], noise[step * n + i] for i < n without bounds
+    MRISR_REQUIRE(latents->shape[1] == U.cfg.in_channels, "latents channels vs the UNet's in_channels");
+    // tiles: the grid of this canvas.  T == 1 (or tiles off) is the plain run; otherwise the forwards see FB = NB * T rows of fh x fw
+    const int Cl = (int)latents->shape[1];
+    bool tiled = false;
+    if (s->tile_h) {
+        MRISR_REQUIRE(B > 0 && h > 0 && w > 0, "tiled run: empty latents");
+        const int d = 1 << (U.cfg.num_levels - 1);
+        MRISR_REQUIRE(h % d == 0 && w % d == 0, "tiled run: h and w of the latents must be multiples of 2^(num_levels-1)");
+        TRY(s->tiles.build(h, w, s->tile_h, s->tile_w, s->tile_oh, s->tile_ow, s->tile_window));
+        TRY(s->tiles.check());
+        tiled = s->tiles.T() > 1;
+    }
+    const int T = tiled ? s->tiles.T() : 1;
+    const int fh = tiled ? s->tiles.th : h, fw = tiled ? s->tiles.tw : w;
+    if (tiled) MRISR_REQUIRE((long long)NB * T * Cl * fh * fw < (1ll << 31), "tiled run: the tile batch is too large");
+    const int FB = NB * T;  // rows of every forward
+    if (tiled) {
+        MRISR_REQUIRE(ehs->ndim == 3 && ehs->shape[0] == FB && ehs->shape[2] == U.cfg.cross_attention_dim,
+                      "tiled run: encoder_hidden_states must be [NB*T, L, cross_attention_dim]: every forward row's context T times, sample-major");
+        if (cond) MRISR_REQUIRE(cond->ndim == 4 && cond->shape[0] == FB && cond->shape[2] == 8 * fh && cond->shape[3] == 8 * fw,
+                                "tiled run: controlnet_cond must be [NB*T, C, 8 t_h, 8 t_w]: the image cropped per tile");
+        for (int i = 0; i < a.n_intrablock; ++i) {
+            const mrisr_tensor& f = a.intrablock[i];
+            const long long r = f.ndim == 4 && f.shape[2] > 0 ? fh / f.shape[2] : 0;
+            MRISR_REQUIRE(f.ndim == 4 && f.shape[0] == FB && r >= 1 && (r & (r - 1)) == 0 && r <= (1ll << (U.cfg.num_levels - 1)) && f.shape[2] * r == fh &&
+                              f.shape[3] * r == fw,
+                          "tiled run: adapter features must be [NB*T, ...] at tile geometry: every feature cropped per tile");
+        }
+    } else if (!guided)
+        MRISR_REQUIRE(ehs->ndim == 3 && ehs->shape[0] == B && ehs->shape[2] == U.cfg.cross_attention_dim,
+                      "encoder_hidden_states must be [B, L, cross_attention_dim] with the latents' batch");
+    else
+        MRISR_REQUIRE(ehs->ndim == 3 && ehs->shape[0] == NB && ehs->shape[2] == U.cfg.cross_attention_dim,
+                      pag ? "pag run: encoder_hidden_states must be [K B, L, cross_attention_dim]: B perturbed rows first, B conditional rows last"
+                          : "guided run: encoder_hidden_states must be [2B, L, cross_attention_dim]: B unconditional rows, then B conditional rows");
+    if (guided) MRISR_REQUIRE(B > 0 && per % 4 == 0, pag ? "pag run: C*h*w of the latents must be a multiple of 4"
+                                                         : "guided run: C*h*w of the latents must be a multiple of 4");
+    if (s->multistep()) MRISR_REQUIRE(B > 0 && per % 4 == 0, "multistep solvers: C*h*w of the latents must be a multiple of 4");
+    if (a.lr) MRISR_REQUIRE(a.lr->dtype == MRISR_F32 && numel(a.lr) == n, "lr_latents: f32, same shape as latents");
+    if (cond && !tiled)
+        MRISR_REQUIRE(cond->ndim == 4 && cond->shape[0] == NB && cond->shape[2] == 8 * h && cond->shape[3] == 8 * w,
+                      pag ? "pag run: controlnet_cond must be [K B, C, 8h, 8w] (the [B] images K times)"
+                      : guided ? "guided run: controlnet_cond must be [2B, C, 8h, 8w] (the [B] images twice)"
+                             : "controlnet_cond must be [B, C, 8h, 8w] with the latents' batch");
+    {
+        int need = 0;  // slabs read: one per step, indexed by the step's position in the schedule, when its sigma != 0
+        for (int i = s->first; i < s->last; ++i)
+            if (s->sigma[i] != 0.f) need = i + 1;
+        if (a.noise) {
+            MRISR_REQUIRE(a.noise->dtype == MRISR_F32 && a.noise->ndim >= 1 && numel(a.noise) % n == 0,
+                          "step_noise: f32, a stack of latents-shaped slabs");
+            MRISR_REQUIRE(numel(a.noise) / n >= need, "step_noise has fewer slabs than the last stochastic step needs");
+        }
+    }
+    for (int i = 0; i < a.n_intrablock && !tiled; ++i)
+        MRISR_REQUIRE(a.intrablock[i].ndim == 4 && a.intrablock[i].shape[0] == NB,
+                      pag ? "pag run: adapter features must be [K B, ...] (the [B] features K times)"
+                      : guided ? "guided run: adapter features must be [2B, ...] (the [B] features twice)"
+                             : "adapter features must carry the latents' batch");
+    MRISR_REQUIRE(a.n_intrablock >= 0 && a.n_intrablock <= PLAN_MAX_INTRA, "more adapter features than a step plan holds");
+    MRISR_REQUIRE(!s->cnet || s->cnet->num_skips() + 1 <= PLAN_MAX_RES, "more ControlNet residuals than a step plan holds");
+
+    // a field that this configuration's launches do not take stays zero: changing it alone must not capture again
+    p.kind = s->kind; p.K = K; p.pag = pag;
+    p.B = B; p.T = T; p.C = Cl; p.h = h; p.w = w; p.fh = fh; p.fw = fw; p.L = (int)ehs->shape[1];
+    p.cnet = s->cnet != nullptr;
+    p.cdt = U.cfg.compute_dtype;
+    p.first = s->first;
+    p.x = static_cast<float*>(latents->data);
+    p.lr = a.lr ? static_cast<const float*>(a.lr->data) : nullptr;
+    p.noise = a.noise ? static_cast<const float*>(a.noise->data) : nullptr;
+    p.d_coef = static_cast<const float*>(s->d_coef.p);
+    p.d_step = static_cast<int*>(s->d_step.p);
+    p.d_curt = static_cast<long long*>(s->d_curt.p);
+    p.d_ts = static_cast<const long long*>(s->d_ts.p);
+    if (s->kind == MRISR_STEP_DDPM) p.clip = s->clip;
+    if (guided) { p.guidance_scale = s->guidance_scale; p.guidance_rescale = s->guidance_rescale; }
+    if (pag) { p.pag_mask = s->pag_mask; p.pag_scale = s->pag_scale; }
+    if (U.freeu.on) {  // the four scalars the decoder's FreeU launches take by value (also in the UNet's workspace generation)
+        p.freeu = 1;
+        p.freeu_s[0] = U.freeu.s[0]; p.freeu_s[1] = U.freeu.s[1]; p.freeu_b[0] = U.freeu.b[0]; p.freeu_b[1] = U.freeu.b[1];
+    }
+    if (s->multistep()) {
+        p.order = s->ms.order;
+        p.final_zero = s->ms.final_zero; p.lower_order_final = s->ms.lower_order_final;
+        p.n_disabled = (int)s->ms.disable_corrector.size();
+        for (int i = 0; i < p.n_disabled && i < 32; ++i) p.disabled[i] = s->ms.disable_corrector[i];
+    }
+    if (cached) { p.cached = 1; p.cache_depth = s->cache_depth; }
+    if (tiled) {
+        p.tile_h = s->tile_h; p.tile_w = s->tile_w; p.tile_oh = s->tile_oh; p.tile_ow = s->tile_ow; p.tile_window = s->tile_window;
+    }
+    return 0;
+}
+
+// one-time (per run) timestep-invariant work: context projections, condition embedding, ControlNet residual buffers, feature conversion
+static int run_operands(mrisr_sampler* s, const RunArgs& a, StepPlan& p, hipStream_t st) {
+    Model& U = *s->unet;
+    const int FB = p.K * p.B * p.T, esz = dtype_size(p.cdt);
+    TRY(gemm_prepare());
+    TRY(U.set_context(a.ehs, FB, p.fh, p.fw, st));
+    if (s->cnet) {
+        Model& C = *s->cnet;
+        TRY(C.set_context(a.ehs, FB, p.fh, p.fw, st));
+        TRY(C.set_cond(a.cond, p.L, st));
+        p.n_res = C.num_skips();
+        s->res_bufs.resize(p.n_res + 1);
+        for (int k = 0; k <= p.n_res; ++k) {  // the mid residual last
+            int64_t shape[4];
+            C.skip_shape(k, FB, p.fh, p.fw, shape);
+            if (!s->res_bufs[k]) s->res_bufs[k].reset(new DevBuf());
+            TRY(s->res_bufs[k]->reserve((size_t)shape[0] * shape[1] * shape[2] * shape[3] * esz, false));
+            p.res[k].data = s->res_bufs[k]->p;
+            for (int i = 0; i < 4; ++i) p.res[k].shape[i] = shape[i];
+        }
+    }
+    p.n_intra = a.n_intrablock;
+    s->intra_bufs.resize(a.n_intrablock);
+    for (int i = 0; i < a.n_intrablock; ++i) {
+        const mrisr_tensor& f = a.intrablock[i];
+        MRISR_REQUIRE(f.ndim == 4, "adapter feature rank");
+        p.intra[i].data = f.data;
+        for (int k = 0; k < 4; ++k) p.intra[i].shape[k] = f.shape[k];
+        if (f.layout == MRISR_NHWC && f.dtype == p.cdt) continue;
+        if (!s->intra_bufs[i]) s->intra_bufs[i].reset(new DevBuf());
+        TRY(s->intra_bufs[i]->reserve((size_t)f.shape[0] * f.shape[1] * f.shape[2] * f.shape[3] * esz, false));
+        if (p.cdt == MRISR_F32) TRY(launch_nchw_to_nhwc<float>(f.data, f.dtype, s->intra_bufs[i]->p, (int)f.shape[0], (int)f.shape[1], (int)f.shape[2], (int)f.shape[3], st));
+        else TRY(launch_nchw_to_nhwc<bf16>(f.data, f.dtype, s->intra_bufs[i]->p, (int)f.shape[0], (int)f.shape[1], (int)f.shape[2], (int)f.shape[3], st));
+        p.intra[i].data = s->intra_bufs[i]->p;
+    }
+    p.ws_gen_unet = U.ws_gen;
+    p.ws_gen_cnet = s->cnet ? s->cnet->ws_gen : 0ull;
+    return 0;
+}
+
+// the sampler's own buffers: the forward's output, tiles, feature cache, staging, multistep history, the step counter
+static int run_buffers(mrisr_sampler* s, StepPlan& p, hipStream_t st) {
+    Model& U = *s->unet;
+    const int NB = p.K * p.B;
+    const long long per = (long long)p.C * p.h * p.w, n = (long long)p.B * per;
+    TRY(s->d_eps.reserve((size_t)NB * per * sizeof(float), false));
+    p.d_eps = static_cast<float*>(s->d_eps.p);
+    if (p.T > 1) {
+        // the table is uploaded before any capture; the graph reads it from d_tiles at every replay.  s->tiles is pageable and rebuilt by the
+        // next run: like the copy of ms_rows below, this relies on the runtime staging the copy before hipMemcpyAsync returns
+        const size_t tile_elems = (size_t)NB * p.T * p.C * p.fh * p.fw;
+        TRY(s->d_tiles.reserve(s->tiles.bytes(), false));
+        TRY(s->d_xt.reserve(tile_elems * sizeof(float), false));
+        TRY(s->d_et.reserve(tile_elems * sizeof(float), false));
+        MRISR_CHECK_HIP(hipMemcpyAsync(s->d_tiles.p, s->tiles.words.data(), s->tiles.bytes(), hipMemcpyHostToDevice, st));
+        const TileGrid g = s->tiles.grid(s->d_tiles.p);
+        p.tile_oy = g.oy; p.tile_ox = g.ox; p.tile_nwy = g.nwy; p.tile_nwx = g.nwx;
+        p.tile_ky = g.ky; p.tile_kx = g.kx; p.tile_vec4 = g.vec4;
+        p.d_xt = static_cast<float*>(s->d_xt.p); p.d_et = static_cast<float*>(s->d_et.p);
+    }
+    if (p.cached) {  // reserved here, before any capture; written by the first step of every run before anything reads it
+        int64_t cs[4];
+        TRY(U.cache_shape(p.cache_depth, NB, p.h, p.w, cs));
+        TRY(s->d_cache.reserve((size_t)cs[0] * cs[1] * cs[2] * cs[3] * dtype_size(p.cdt), false));
+        p.d_cache = s->d_cache.p;
+    }
+    if (p.K > 1) {
+        // [x; x] ([x; x; x]) once per run; from then on the fused step itself writes every new state to every part
+        TRY(s->d_x2.reserve((size_t)p.K * n * sizeof(float), false));
+        for (int k = 0; k < p.K; ++k)
+            MRISR_CHECK_HIP(hipMemcpyAsync(static_cast<float*>(s->d_x2.p) + (size_t)k * n, p.x, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        p.d_x2 = static_cast<float*>(s->d_x2.p);
+    }
+    if (s->multistep()) {
+        // this range's rows, and a zeroed history: the rows of a cold start carry zero coefficients for the absent terms, and
+        // 0 x (whatever an earlier run or the allocator left) is not 0
+        TRY(s->d_hist.reserve((size_t)p.order * n * sizeof(float), false));
+        MRISR_CHECK_HIP(hipMemsetAsync(s->d_hist.p, 0, (size_t)p.order * n * sizeof(float), st));
+        p.hist = static_cast<float*>(s->d_hist.p);
+        if (s->kind == MRISR_STEP_UNIPC) {
+            TRY(s->d_xc.reserve((size_t)n * sizeof(float), false));
+            MRISR_CHECK_HIP(hipMemsetAsync(s->d_xc.p, 0, (size_t)n * sizeof(float), st));
+            p.xc = static_cast<float*>(s->d_xc.p);
+        }
+        // ms_rows is pageable and may be rebuilt (set_solver / set_range) right after this call returns: like the copy of s->first
+        // below, this relies on the runtime staging a pageable host-to-device copy before hipMemcpyAsync returns
+        MRISR_CHECK_HIP(hipMemcpyAsync(s->d_coef.p, s->ms_rows.data(), sizeof(float) * s->ms_rows.size(), hipMemcpyHostToDevice, st));
+    }
+    MRISR_CHECK_HIP(hipMemsetAsync(s->d_step.p, 0, 16, st));
+    MRISR_CHECK_HIP(hipMemcpyAsync(s->d_step.p, &s->first, sizeof(int), hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// the time embedding of every step of this run, once (it depends on the timestep only): sinusoid -> MLP -> the 22 per-resnet projections for
+// all rows at once instead of three GEMVs over 50 MB of weights in every step.  MRISR_TEMB_TABLE=0 / mrisr_debug_temb_table(0): per step.
+// Leaves the models pointing at the tables: the caller's guard clears that when the run returns.
+static int run_temb_table(mrisr_sampler* s, StepPlan& p, hipStream_t st) {
+    if (!temb_table_enabled()) return 0;
+    const int rows = s->last - s->first;
+    auto build = [&](Model& M, DevBuf& buf) -> int {
+        const size_t scratch = (size_t)64 * M.cfg.block_out_channels[0] * 9;
+        TRY(buf.reserve((scratch + (size_t)rows * M.tproj_total) * sizeof(float), false));
+        float* sc = static_cast<float*>(buf.p);
+        TRY(M.build_tproj_table(static_cast<const long long*>(s->d_ts.p) + s->first, rows, sc, sc + scratch, st));
+        M.tproj_table = sc + scratch; M.tproj_step = static_cast<const int*>(s->d_step.p); M.tproj_first = s->first;
+        return 0;
+    };
+    TRY(build(*s->unet, s->tp_unet));
+    p.tproj_unet = s->unet->tproj_table;
+    if (s->cnet) { TRY(build(*s->cnet, s->tp_cnet)); p.tproj_cnet = s->cnet->tproj_table; }
+    return 0;
+}
+
+// ONE step: everything here comes from the plan (C: the ControlNet when p.cnet).  Workspaces are planned (set_context in run_operands), so
+// a captured body performs launches only.
+static int step_body(const StepPlan& p, Model& U, Model* C, int cache_mode, hipStream_t st) {
+    const int NB = p.K * p.B, FB = NB * p.T;
+    const long long per = (long long)p.C * p.h * p.w, n = (long long)p.B * per;
+    const bool tiled = p.T > 1;
+    mrisr_tensor tt{};
+    tt.data = p.d_curt; tt.dtype = MRISR_I64; tt.ndim = 0;
+    const float* canvas = p.K > 1 ? p.d_x2 : p.x;  // [NB, C, h, w]: what the forwards read, or what a tiled step gathers from
+    mrisr_tensor xin{};                            // what the forwards read
+    xin.data = tiled ? p.d_xt : const_cast<float*>(canvas);
+    xin.dtype = MRISR_F32; xin.layout = MRISR_NCHW; xin.ndim = 4;
+    xin.shape[0] = FB; xin.shape[1] = p.C; xin.shape[2] = p.fh; xin.shape[3] = p.fw;
+    mrisr_tensor eps_t = xin;
+    eps_t.data = tiled ? p.d_et : p.d_eps;
+    TileGrid tg;
+    if (tiled) {
+        tg.H = p.h; tg.W = p.w; tg.th = p.fh; tg.tw = p.fw; tg.ky = p.tile_ky; tg.kx = p.tile_kx;
+        tg.oy = p.tile_oy; tg.ox = p.tile_ox; tg.nwy = p.tile_nwy; tg.nwx = p.tile_nwx;
+        tg.vec4 = p.tile_vec4 != 0;
+    }
+    mrisr_tensor res[PLAN_MAX_RES], intra[PLAN_MAX_INTRA];
+    for (int k = 0; k <= p.n_res && p.cnet; ++k) res[k] = plan_tensor(p.res[k], p.cdt);
+    for (int i = 0; i < p.n_intra; ++i) intra[i] = plan_tensor(p.intra[i], p.cdt);
+    UNetCache fc;
+    fc.mode = cache_mode; fc.depth = p.cache_depth; fc.p = p.d_cache;
+
+    hipLaunchKernelGGL(load_t_kernel, dim3(1), dim3(1), 0, st, p.d_curt, p.d_ts, static_cast<const int*>(p.d_step));
+    if (tiled) TRY(launch_tile_gather(canvas, p.d_xt, tg, NB, p.C, st));
+    if (p.cnet) TRY(C->forward_controlnet(&xin, &tt, nullptr, nullptr, 1.0f, res, p.n_res, &res[p.n_res], st));
+    TRY(U.forward_unet(&xin, &tt, nullptr, p.cnet ? res : nullptr, p.n_res, p.cnet ? &res[p.n_res] : nullptr, intra, p.n_intra, &eps_t, st,
+                       p.cached ? &fc : nullptr));
+    if (tiled) TRY(launch_tile_blend(p.d_et, p.d_eps, tg, NB, p.C, st));
+    const bool multistep = p.kind > MRISR_STEP_DDPM;
+    if (p.K > 1) {
+        // K = 3: [eps_p; eps_u; eps_c].  K = 2 of a pag run: [eps_p; eps_c], the guided step with eps_u := eps_p and g := 1 + s
+        const float g = p.pag && p.K == 2 ? 1.f + p.pag_scale : p.guidance_scale;
+        TRY(launch_guided_step(p.K, p.kind, p.x, p.d_x2, p.d_eps, p.lr, p.noise, p.d_coef, p.d_step, p.clip, g, p.K == 3 ? p.pag_scale : 0.f,
+                               p.guidance_rescale, p.B, per, st, p.hist, p.xc, p.order));
+    } else if (multistep)
+        TRY(launch_multistep_step(p.x, p.d_eps, p.lr, p.d_coef, p.d_step, p.hist, p.xc, p.order, n, st));
+    else if (p.kind == MRISR_STEP_DDIM)
+        TRY(launch_ddim_step(p.x, p.d_eps, p.d_coef, p.d_step, n, st));
+    else if (p.kind == MRISR_STEP_DDPM)
+        TRY(launch_ddpm_step(p.x, p.d_eps, p.noise, p.d_coef, p.d_step, p.clip, n, st));
+    else
+        TRY(launch_resshift_step(p.x, p.d_eps, p.lr, p.noise, p.d_coef, p.d_step, n, st));
+    return launch_advance_step(p.d_step, st);
+}
+
+// capture and replay: the stored graphs serve this run exactly when they were captured from an equal plan
+static int run_steps(mrisr_sampler* s, const StepPlan& p, int use_graph, hipStream_t st) {
+    Model& U = *s->unet;
+    const bool cached = p.cached != 0;
+    auto mode_of = [&](int i) { return !cached ? CACHE_NONE : ((i - s->first) % s->cache_interval == 0 ? CACHE_STORE : CACHE_USE); };
+    if (!use_graph) {
+        for (int i = s->first; i < s->last; ++i) TRY(step_body(p, U, s->cnet, mode_of(i), st));
+        return 0;
+    }
+    if (!s->exec || (cached && !s->exec_shallow) || !same_plan(s->plan, p)) {
+        s->drop_graphs();
+        auto capture = [&](int cache_mode, hipGraphExec_t* exec) -> int {
+            hipGraph_t graph = nullptr;
+            MRISR_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+            int rc = step_body(p, U, s->cnet, cache_mode, st);
+            hipError_t e = hipStreamEndCapture(st, &graph);
+            if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+            MRISR_CHECK_HIP(e);
+            MRISR_CHECK_HIP(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
+            (void)hipGraphDestroy(graph);
+            ++s->n_captures;
+            return 0;
+        };
+        TRY(capture(cached ? CACHE_STORE : CACHE_NONE, &s->exec));
+        if (cached) TRY(capture(CACHE_USE, &s->exec_shallow));
+        s->plan = p;
+    }
+    for (int i = s->first; i < s->last; ++i) MRISR_CHECK_HIP(hipGraphLaunch(mode_of(i) == CACHE_USE ? s->exec_shallow : s->exec, st));
+    return 0;
+}
+
+static int sampler_run_impl(mrisr_sampler* s, const RunArgs& a, int use_graph, void* stream) {
+    API_BEGIN
+    StepPlan p = new_step_plan();
+    TRY(run_check(s, a, p));
+    hipStream_t user = (hipStream_t)stream;
+    hipStream_t st = user;
+    if (use_graph && user == nullptr) {
+        // the legacy default stream cannot be captured: run on an internal stream fenced by events
+        if (!s->own_stream) {
+            MRISR_CHECK_HIP(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
+            MRISR_CHECK_HIP(hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming));
+            MRISR_CHECK_HIP(hipEventCreateWithFlags(&s->ev_out, hipEventDisableTiming));
+        }
+        st = s->own_stream;
+        MRISR_CHECK_HIP(hipEventRecord(s->ev_in, user));
+        MRISR_CHECK_HIP(hipStreamWaitEvent(st, s->ev_in, 0));
+    }
+    Model& U = *s->unet;
+    // perturbed rows first: samples [0, B) of the forward, [0, B T) of a tiled one.  Set before the workspace is planned (the plan and
+    // its key see it), cleared when this call returns, also on an error path: plain forwards on the handle stay unperturbed
+    struct PagGuard {
+        Model* m = nullptr;
+        ~PagGuard() { if (m) m->pag = PagState(); }
+    } pguard;
+    if (a.pag) {
+        MRISR_REQUIRE(!U.pag.on(), "pag run: the UNet handle already carries a pag state (mrisr_model_set_pag); clear it first");
+        pguard.m = &U;
+        U.pag.mask = s->pag_mask; U.pag.first = 0; U.pag.count = p.B * p.T;
+    }
+    TRY(run_operands(s, a, p, st));
+    TRY(run_buffers(s, p, st));
+    struct TableGuard {  // the models must not keep pointing at this sampler's table after the run (plain forward calls compute their own)
+        Model* a = nullptr; Model* b = nullptr;
+        ~TableGuard() { if (a) a->tproj_table = nullptr; if (b) b->tproj_table = nullptr; }
+    } tguard;
+    tguard.a = &U; tguard.b = s->cnet;
+    TRY(run_temb_table(s, p, st));
+    TRY(run_steps(s, p, use_graph, st));
+    if (st != user) {
+        MRISR_CHECK_HIP(hipEventRecord(s->ev_out, st));
+        MRISR_CHECK_HIP(hipStreamWaitEvent(user, s->ev_out, 0));
+    }
+    return 0;
+    API_END
+}
+
+// ---- the single-step test entries: one static helper behind the four.  K = 1: the plain multistep step; K = 2 / 3: the guided / three-way
+// step on caller buffers xK / epsK [K B].  row_host holds `width` floats (this step kind's row), placed at row `slot` of a zeroed table; the
+// kernel sees the step counter `slot`.  hist / xc: the multistep kinds' ring and corrected state.
+static int op_step(const char* who, int K, int step_kind, mrisr_tensor* x, mrisr_tensor* xK, const mrisr_tensor* epsK, const mrisr_tensor* lr,
+                   const mrisr_tensor* noise, const float* row_host, int width, int slot, mrisr_tensor* hist, mrisr_tensor* xc, int solver_order,
+                   float clip, float g, float sp, float phi, void* stream) {
+    const std::string w = std::string(who) + ": ", sK = std::to_string(K);
+    const std::string eps_name = K == 3 ? "eps3" : (K == 2 ? "eps2" : "eps");
+    const bool multistep = hist != nullptr;
+    MRISR_REQUIRE(x->ndim == 4 && x->dtype == MRISR_F32 && x->shape[0] > 0, w + "x must be f32 [B, C, h, w]");
+    const int B = (int)x->shape[0];
+    const long long n = numel(x), per = n / B;
+    if (multistep) MRISR_REQUIRE(per % 4 == 0, w + "C*h*w must be a multiple of 4");
+    MRISR_REQUIRE(epsK->dtype == MRISR_F32 && numel(epsK) == K * n, w + eps_name + " must be f32 [" + (K > 1 ? sK : "") + "B, C, h, w]");
+    if (xK) MRISR_REQUIRE(xK->dtype == MRISR_F32 && numel(xK) == K * n, w + "the staging buffer must be f32 [" + sK + "B, C, h, w]");
+    if (lr) MRISR_REQUIRE(lr->dtype == MRISR_F32 && numel(lr) == n, w + "lr must be f32 [B, C, h, w]");
+    if (noise) MRISR_REQUIRE(noise->dtype == MRISR_F32 && numel(noise) == n, w + "noise must be one f32 [B, C, h, w] slab");
+    if (multistep) MRISR_REQUIRE(hist->dtype == MRISR_F32 && numel(hist) == (long long)solver_order * n, w + "hist must be f32 [order, B, C, h, w]");
+    if (xc) MRISR_REQUIRE(xc->dtype == MRISR_F32 && numel(xc) == n, w + "xc must be f32 [B, C, h, w]");
+    hipStream_t st = (hipStream_t)stream;
+    const int pitch = multistep ? 16 : 8;
+    std::vector<float> rows((size_t)(slot + 1) * pitch, 0.f);
+    std::copy(row_host, row_host + width, rows.begin() + (size_t)slot * pitch);
+    DevBuf d_rows, d_step;
+    TRY(d_rows.reserve(sizeof(float) * rows.size(), false));
+    TRY(d_step.reserve(16, true));
+    MRISR_CHECK_HIP(hipMemcpyAsync(d_rows.p, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice, st));
+    MRISR_CHECK_HIP(hipMemsetAsync(d_step.p, 0, 16, st));
+    MRISR_CHECK_HIP(hipMemcpyAsync(d_step.p, &slot, sizeof(int), hipMemcpyHostToDevice, st));
+    float* h = hist ? (float*)hist->data : nullptr;
+    float* c = xc ? (float*)xc->data : nullptr;
+    if (K > 1)
+        TRY(launch_guided_step(K, step_kind, (float*)x->data, (float*)xK->data, (const float*)epsK->data, lr ? (const float*)lr->data : nullptr,
+                               noise ? (const float*)noise->data : nullptr, (const float*)d_rows.p, (const int*)d_step.p, clip, g, sp, phi, B, per,
+                               st, h, c, solver_order));
+    else
+        TRY(launch_multistep_step((float*)x->data, (const float*)epsK->data, lr ? (const float*)lr->data : nullptr, (const float*)d_rows.p,
+                                  (const int*)d_step.p, h, c, solver_order, n, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+static int row_width(int step_kind) { return step_kind == MRISR_STEP_DDIM ? 2 : (step_kind == MRISR_STEP_RESSHIFT ? 4 : 5); }
+
+extern "C" {
+
+int mrisr_sampler_run(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents,
+                      const mrisr_tensor* step_noise, const mrisr_tensor* ehs, const mrisr_tensor* cond,
+                      const mrisr_tensor* intrablock, int n_intrablock, int use_graph, void* stream) {
+    return sampler_run_impl(s, RunArgs{latents, lr_latents, step_noise, ehs, cond, intrablock, n_intrablock, 1, false}, use_graph, stream);
+}
+int mrisr_sampler_run_guided(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents,
+                             const mrisr_tensor* step_noise, const mrisr_tensor* ehs2, const mrisr_tensor* cond2,
+                             const mrisr_tensor* intrablock2, int n_intrablock, int use_graph, void* stream) {
+    return sampler_run_impl(s, RunArgs{latents, lr_latents, step_noise, ehs2, cond2, intrablock2, n_intrablock, 2, false}, use_graph, stream);
+}
+int mrisr_sampler_run_pag(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_tensor* lr_latents, const mrisr_tensor* step_noise,
+                          const mrisr_tensor* ehsK, const mrisr_tensor* condK, const mrisr_tensor* intrablockK, int n_intrablock, int with_cfg,
+                          int use_graph, void* stream) {
+    return sampler_run_impl(s, RunArgs{latents, lr_latents, step_noise, ehsK, condK, intrablockK, n_intrablock, with_cfg ? 3 : 2, true}, use_graph,
+                            stream);
+}
+
+// the guided step alone, on caller buffers (parity test): coef_row_host is this step kind's coefficient row (2 / 4 / 5 floats)
+int mrisr_op_guided_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const mrisr_tensor* eps2, const mrisr_tensor* lr,
+                         const mrisr_tensor* noise, const float* coef_row_host, float clip, float guidance_scale,
+                         float guidance_rescale, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(x && x2 && eps2 && coef_row_host, "guided step: null argument");
+    MRISR_REQUIRE(step_kind >= MRISR_STEP_DDIM && step_kind <= MRISR_STEP_DDPM, "guided step: unknown step kind");
+    return op_step("guided step", 2, step_kind, x, x2, eps2, lr, noise, coef_row_host, row_width(step_kind), 0, nullptr, nullptr, 0, clip,
+                   guidance_scale, 0.f, guidance_rescale, stream);
+    API_END
+}
+// the three-way step alone: as mrisr_op_guided_step with x3 / eps3 [3B] = [perturbed; uncond; cond]
+int mrisr_op_pag_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x3, const mrisr_tensor* eps3, const mrisr_tensor* lr,
+                      const mrisr_tensor* noise, const float* coef_row_host, float clip, float guidance_scale, float pag_scale,
+                      float guidance_rescale, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(x && x3 && eps3 && coef_row_host, "pag step: null argument");
+    MRISR_REQUIRE(step_kind >= MRISR_STEP_DDIM && step_kind <= MRISR_STEP_DDPM, "pag step: unknown step kind");
+    return op_step("pag step", 3, step_kind, x, x3, eps3, lr, noise, coef_row_host, row_width(step_kind), 0, nullptr, nullptr, 0, clip,
+                   guidance_scale, pag_scale, guidance_rescale, stream);
+    API_END
+}
+// the multistep step alone (parity test): row_host = one 16-float row; slot = the step counter the kernel sees; x2 given: the guided form
+int mrisr_op_multistep_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const mrisr_tensor* eps, const mrisr_tensor* lr,
+                            mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot, float guidance_scale,
+                            float guidance_rescale, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(x && eps && hist && row_host, "multistep step: null argument");
+    MRISR_REQUIRE(step_kind == MRISR_STEP_UNIPC || step_kind == MRISR_STEP_DPMSOLVERPP, "multistep step: UniPC or DPM-Solver++");
+    MRISR_REQUIRE(solver_order >= 1 && solver_order <= 3 && slot >= 0 && slot < 1024, "multistep step: solver order 1..3, slot 0..1023");
+    MRISR_REQUIRE((step_kind == MRISR_STEP_UNIPC) == (xc != nullptr), "multistep step: the corrected-state buffer belongs to UniPC");
+    return op_step("multistep step", x2 ? 2 : 1, step_kind, x, x2, eps, lr, nullptr, row_host, 16, slot, hist, xc, solver_order, 0.f, guidance_scale,
+                   0.f, guidance_rescale, stream);
+    API_END
+}
+// the three-way step of the multistep kinds alone: mrisr_op_multistep_step's guided form with x3 / eps3 [3B]
+int mrisr_op_pag_multistep_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x3, const mrisr_tensor* eps3, const mrisr_tensor* lr,
+                                mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot, float guidance_scale,
+                                float pag_scale, float guidance_rescale, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(x && x3 && eps3 && hist && row_host, "pag multistep step: null argument");
+    MRISR_REQUIRE(step_kind == MRISR_STEP_UNIPC || step_kind == MRISR_STEP_DPMSOLVERPP, "pag multistep step: UniPC or DPM-Solver++");
+    MRISR_REQUIRE(solver_order >= 1 && solver_order <= 3 && slot >= 0 && slot < 1024, "pag multistep step: solver order 1..3, slot 0..1023");
+    MRISR_REQUIRE((step_kind == MRISR_STEP_UNIPC) == (xc != nullptr), "pag multistep step: the corrected-state buffer belongs to UniPC");
+    return op_step("pag multistep step", 3, step_kind, x, x3, eps3, lr, nullptr, row_host, 16, slot, hist, xc, solver_order, 0.f, guidance_scale,
+                   pag_scale, guidance_rescale, stream);
+    API_END
+}
+
+}  // extern "C"

@@ -289,12 +289,17 @@ class Sampler:
         Fewer launches per step for a bounded deviation from the uncached run.  ``interval=1`` (the default) is no cache at all:
         the step graph and the result of a sampler that never had one.  Changing either value captures the step graphs again."""
         interval, depth = check_cache(interval, depth, int(L.lib().mrisr_model_num_skips(self.unet._h)), self.controlnet is not None)
+        self._check_cache_with(interval)
+        L.check(L.lib().mrisr_sampler_set_cache(self._h, interval, depth))
+        self.cache_interval, self.cache_depth = interval, depth
+
+    def _check_cache_with(self, interval: int):
+        """What a feature cache of ``interval`` excludes on this sampler as it stands: FreeU on the UNet (which carries that state; ``run``
+        takes no argument for it) and tiles.  ``set_cache`` asks with the interval it is about to set, ``run`` with the one that is set."""
         if interval > 1 and getattr(self.unet, "freeu", None) is not None:
             raise ValueError("a feature cache (interval > 1) together with FreeU (unet.enable_freeu) is not supported")
         if interval > 1 and getattr(self, "tiles", None) is not None:
             raise ValueError("a feature cache (interval > 1) together with tiles is not supported")
-        L.check(L.lib().mrisr_sampler_set_cache(self._h, interval, depth))
-        self.cache_interval, self.cache_depth = interval, depth
 
     @property
     def divisor(self) -> int:
@@ -387,8 +392,7 @@ class Sampler:
                 raise ValueError("the multistep solvers need [B,C,h,w] latents with C*h*w a multiple of 4")
             if lr_latents is not None and tuple(lr_latents.shape) != tuple(latents.shape):
                 raise ValueError(f"lr_latents must have the latents' shape {tuple(latents.shape)}, got {tuple(lr_latents.shape)}")
-        if self.cache_interval > 1 and getattr(self.unet, "freeu", None) is not None:  # (the UNet carries the FreeU state; run takes no argument)
-            raise ValueError("FreeU (unet.enable_freeu) together with a feature cache (cache interval > 1) is not supported")
+        self._check_cache_with(self.cache_interval)
         plan = None
         if self.tiles is not None:  # a tiled run: the canvas and everything shaped after it is checked here, before any launch
             if latents.ndim != 4:
@@ -403,30 +407,8 @@ class Sampler:
                           None if uncond_hidden_states is None else uncond_hidden_states.shape, latents.shape[0]):
             return self._run_guided(latents, encoder_hidden_states, uncond_hidden_states, lr_latents, step_noise, controlnet_cond,
                                     adapter_features, use_graph, float(guidance_scale), float(guidance_rescale), plan)
-        dev = latents.device
-        ehs = encoder_hidden_states.to(dev).contiguous()
-        if ehs.shape[0] != latents.shape[0]:
-            ehs = ehs.expand(latents.shape[0], -1, -1).contiguous()
-        lr = lr_latents.to(dev, torch.float32).contiguous() if lr_latents is not None else None
-        nz = step_noise.to(dev, torch.float32).contiguous() if step_noise is not None else None
-        cond = controlnet_cond.to(dev).contiguous() if controlnet_cond is not None else None
-        feats = [f.to(dev).contiguous() for f in (adapter_features or [])]
-        if plan is not None:
-            if (cond is not None and cond.shape[0] != latents.shape[0]) or any(f.shape[0] != latents.shape[0] for f in feats):
-                raise ValueError(f"controlnet_cond and adapter features must carry the latents' batch {latents.shape[0]}")
-            ehs, cond, feats = self._tile_operands(plan, latents.shape[2], latents.shape[3], ehs, cond, feats)
-        keep = (ehs, lr, nz, cond, feats)  # noqa: F841  keep alive until the stream has consumed them
-        t_lat, t_e = L.as_tensor(latents), L.as_tensor(ehs)
-        t_lr = L.as_tensor(lr) if lr is not None else None
-        # step noise is [n_stochastic_steps, B, C, h, w]: described to the C ABI as a stack of [B,C,h,w] slabs
-        t_nz = L.as_tensor(nz, shape=(nz.shape[0] * nz.shape[1],) + tuple(nz.shape[2:])) if nz is not None else None
-        t_c = L.as_tensor(cond) if cond is not None else None
-        f_arr = L.tensor_array([L.as_tensor(f) for f in feats])
-        L.check(L.lib().mrisr_sampler_run(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None,
-                                          C.byref(t_nz) if t_nz else None, C.byref(t_e), C.byref(t_c) if t_c else None,
-                                          f_arr if feats else None, len(feats), 1 if use_graph else 0, L.stream_ptr()))
-        self._keep = keep
-        return latents
+        return self._launch(L.lib().mrisr_sampler_run, latents, (encoder_hidden_states,), lr_latents, step_noise, controlnet_cond,
+                            adapter_features, use_graph, plan)
 
     def _run_pag(self, latents, ehs_c, ehs_u, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, g, guidance_rescale,
                  s, mask, plan=None):
@@ -443,47 +425,55 @@ class Sampler:
         if ehs_c.ndim != 3 or ehs_c.shape[0] not in (1, B):
             raise ValueError(f"encoder_hidden_states must be [1, L, D] or [{B}, L, D], got {tuple(ehs_c.shape)}")
         contexts = (ehs_c, ehs_u, ehs_c) if with_cfg else (ehs_c, ehs_c)
-        return self._run_guided(latents, None, None, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, float(g), phi,
-                                plan, contexts=contexts, pag=(mask, s, 1 if with_cfg else 0))
 
-    def _run_guided(self, latents, ehs_c, ehs_u, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, g, phi,
-                    plan=None, contexts=None, pag=None):
-        B, dev = latents.shape[0], latents.device
+        def setup():
+            L.check(L.lib().mrisr_sampler_set_guidance(self._h, float(g), phi))
+            L.check(L.lib().mrisr_sampler_set_pag(self._h, mask, s))
+        return self._launch(L.lib().mrisr_sampler_run_pag, latents, contexts, lr_latents, step_noise, controlnet_cond, adapter_features,
+                            use_graph, plan, setup, (1 if with_cfg else 0,))
+
+    def _run_guided(self, latents, ehs_c, ehs_u, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, g, phi, plan=None):
         if int(np.prod(latents.shape[1:])) % 4:
             raise ValueError("guided sampling needs C*h*w of the latents to be a multiple of 4")
-        if controlnet_cond is not None and controlnet_cond.shape[0] != B:
-            raise ValueError(f"controlnet_cond must carry the latents' batch {B}, got {tuple(controlnet_cond.shape)}")
-        for f in (adapter_features or []):
-            if f.shape[0] != B:
-                raise ValueError(f"adapter features must carry the latents' batch {B}, got {tuple(f.shape)}")
-        # timestep-invariant plumbing, once per run: [unconditional rows; conditional rows] (diffusers' order), images and features twice
-        # (a PAG run: `contexts` = [perturbed; (unconditional;) conditional], images and features K times)
-        contexts = contexts if contexts is not None else (ehs_u, ehs_c)
-        K = len(contexts)
-        ehs2 = torch.cat([e.to(dev).expand(B, -1, -1) for e in contexts]).contiguous()
+        return self._launch(L.lib().mrisr_sampler_run_guided, latents, (ehs_u, ehs_c), lr_latents, step_noise, controlnet_cond,
+                            adapter_features, use_graph, plan, lambda: L.check(L.lib().mrisr_sampler_set_guidance(self._h, g, phi)))
+
+    def _launch(self, entry, latents, contexts, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, plan, setup=None,
+                extra=()):
+        """The one path into the library: ``entry`` is ``mrisr_sampler_run`` (one context), ``mrisr_sampler_run_guided`` ([unconditional;
+        conditional], diffusers' order) or ``mrisr_sampler_run_pag`` ([perturbed; (unconditional;) conditional]); ``extra`` are the
+        entry's arguments between the feature count and ``use_graph``; ``setup`` runs once every Python-side check has passed.
+        Timestep-invariant plumbing, once per run: each of the K contexts at B rows, images and features K times, then their tiles."""
+        B, dev, K = latents.shape[0], latents.device, len(contexts)
+        feats = list(adapter_features or [])
+        if K > 1 or plan is not None:  # (the plain untiled call leaves a wrong batch to the library's own check)
+            if controlnet_cond is not None and controlnet_cond.shape[0] != B:
+                raise ValueError(f"controlnet_cond must carry the latents' batch {B}, got {tuple(controlnet_cond.shape)}")
+            for f in feats:
+                if f.shape[0] != B:
+                    raise ValueError(f"adapter features must carry the latents' batch {B}, got {tuple(f.shape)}")
+
+        def rows(t):  # [B] -> [K B]
+            return (t.to(dev) if K == 1 else torch.cat([t.to(dev)] * K)).contiguous()
+        parts = [e.to(dev) if e.shape[0] == B else e.to(dev).expand(B, -1, -1) for e in contexts]
+        ehs = (parts[0] if K == 1 else torch.cat(parts)).contiguous()
         lr = lr_latents.to(dev, torch.float32).contiguous() if lr_latents is not None else None
         nz = step_noise.to(dev, torch.float32).contiguous() if step_noise is not None else None
-        cond2 = torch.cat([controlnet_cond.to(dev)] * K).contiguous() if controlnet_cond is not None else None
-        feats2 = [torch.cat([f.to(dev)] * K).contiguous() for f in (adapter_features or [])]
-        if plan is not None:  # the 2B rows, then their tiles: row (b, ti) of the forward is b * T + ti
-            ehs2, cond2, feats2 = self._tile_operands(plan, latents.shape[2], latents.shape[3], ehs2, cond2, feats2)
-        keep = (ehs2, lr, nz, cond2, feats2)
-        t_lat, t_e = L.as_tensor(latents), L.as_tensor(ehs2)
+        cond = rows(controlnet_cond) if controlnet_cond is not None else None
+        feats = [rows(f) for f in feats]
+        if plan is not None:  # the K B rows, then their tiles: row (b, ti) of the forward is b * T + ti
+            ehs, cond, feats = self._tile_operands(plan, latents.shape[2], latents.shape[3], ehs, cond, feats)
+        keep = (ehs, lr, nz, cond, feats)  # kept alive until the stream has consumed them
+        t_lat, t_e = L.as_tensor(latents), L.as_tensor(ehs)
         t_lr = L.as_tensor(lr) if lr is not None else None
+        # step noise is [n_stochastic_steps, B, C, h, w]: described to the C ABI as a stack of [B,C,h,w] slabs
         t_nz = L.as_tensor(nz, shape=(nz.shape[0] * nz.shape[1],) + tuple(nz.shape[2:])) if nz is not None else None
-        t_c = L.as_tensor(cond2) if cond2 is not None else None
-        f_arr = L.tensor_array([L.as_tensor(f) for f in feats2])
-        L.check(L.lib().mrisr_sampler_set_guidance(self._h, g, phi))
-        if pag is not None:
-            L.check(L.lib().mrisr_sampler_set_pag(self._h, pag[0], pag[1]))
-            L.check(L.lib().mrisr_sampler_run_pag(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None,
-                                                  C.byref(t_nz) if t_nz else None, C.byref(t_e), C.byref(t_c) if t_c else None,
-                                                  f_arr if feats2 else None, len(feats2), pag[2], 1 if use_graph else 0, L.stream_ptr()))
-            self._keep = keep
-            return latents
-        L.check(L.lib().mrisr_sampler_run_guided(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None,
-                                                 C.byref(t_nz) if t_nz else None, C.byref(t_e), C.byref(t_c) if t_c else None,
-                                                 f_arr if feats2 else None, len(feats2), 1 if use_graph else 0, L.stream_ptr()))
+        t_c = L.as_tensor(cond) if cond is not None else None
+        f_arr = L.tensor_array([L.as_tensor(f) for f in feats])
+        if setup is not None:
+            setup()
+        L.check(entry(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None, C.byref(t_nz) if t_nz else None, C.byref(t_e),
+                      C.byref(t_c) if t_c else None, f_arr if feats else None, len(feats), *extra, 1 if use_graph else 0, L.stream_ptr()))
         self._keep = keep
         return latents
 

@@ -186,7 +186,7 @@ class _MultistepScheduler(DDPMScheduler):
             z' (next state)       = r[8] z + r[9] eps + r[10] xc + r[11] h_1 + r[12] h_2 + r[13] h_3
 
         Order schedule, the cold first step, disabled correctors and the final point are folded in: an absent term has a zero
-        coefficient.  The C library builds the same rows (capi.hip, build_multistep_rows) and rounds them to f32."""
+        coefficient.  The C library builds the same rows (sampler.hip, build_multistep_rows) and rounds them to f32."""
         al, sg, lam = self.grid()
         n = len(self.timesteps)
         rows = np.zeros((n, 16), dtype=np.float64)

@@ -87,7 +87,8 @@ def kernel_cases():
 
 
 # (1, 4, 72): 20736 elements per sample, above the 16 Ki the registers hold - the re-reading kernel
-@pytest.mark.parametrize("B,Cc,h", [(1, 4, 16), (3, 4, 32), (32, 4, 32), (2, 4, 64), (8, 1, 32), (1, 4, 72)])
+# (2, 4, 40): 6400 elements per sample - the two-pieces-per-thread kernel (4096 < per <= 8192), 1600 pieces on 1024 threads: a masked tail
+@pytest.mark.parametrize("B,Cc,h", [(1, 4, 16), (3, 4, 32), (32, 4, 32), (2, 4, 64), (8, 1, 32), (1, 4, 72), (2, 4, 40)])
 def test_guided_step_kernel_matches_float64_formulae(B, Cc, h):
     gen = torch.Generator().manual_seed(7000 + B * 100 + h)
     x = torch.randn((B, Cc, h, h), generator=gen).cuda()

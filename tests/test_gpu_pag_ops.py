@@ -133,7 +133,8 @@ def ref_pag_step(kind, x, eps3, row, g, s, phi, lr=None, noise=None, clip=0.0):
 
 
 # (1, 4, 72): 20736 elements per sample, above the 16 Ki the registers hold - the re-reading variant
-@pytest.mark.parametrize("B,Cc,h", [(1, 4, 16), (3, 4, 32), (2, 4, 64), (1, 4, 72)])
+# (2, 4, 40): 6400 elements per sample - the two-pieces-per-thread variant (4096 < per <= 8192), 1600 pieces on 1024 threads: a masked tail
+@pytest.mark.parametrize("B,Cc,h", [(1, 4, 16), (3, 4, 32), (2, 4, 64), (1, 4, 72), (2, 4, 40)])
 def test_pag_step_kernel_matches_float64_formulae(B, Cc, h):
     gen = torch.Generator().manual_seed(2700 + B * 100 + h)
     x = torch.randn((B, Cc, h, h), generator=gen).cuda()

@@ -541,6 +541,13 @@ int mrisr_op_ff_proj(const mrisr_tensor* h_rows, const mrisr_tensor* t_rows, con
                      const float* b2_dev, const float* wp_dev, const float* bp_dev, int tile, int fused, mrisr_tensor* y_rows, void* stream);
 int mrisr_op_linear(const mrisr_tensor* x_rows, const float* w_dev, const float* bias_dev, int n, int act,
                     int splitk, int tile, mrisr_tensor* y_rows, void* stream);
+/* a projection with everything its epilogue carries in the models (bf16 rows): y = x W^T + bias + rowvec[m / (M / rowvec_rows)] +
+ * lora_scale B (A x) + resid.  rowvec f32 [rowvec_rows][n] (rowvec_rows divides M; 1 = one row for every output row), A [lora_r][K],
+ * B [n][lora_r] f32 (lora_r = 0: no adapter, both NULL; an adapter takes no split-K); bias, rowvec and resid may be NULL; resid
+ * [M][>= n] may be y itself (in place) */
+int mrisr_op_linear_resid(const mrisr_tensor* x_rows, const float* w_dev, const float* bias_dev, int n, const float* rowvec_dev,
+                          int rowvec_rows, const float* lora_a_dev, const float* lora_b_dev, int lora_r, float lora_scale,
+                          const mrisr_tensor* resid_rows, int splitk, int tile, mrisr_tensor* y_rows, void* stream);
 /* y = LayerNorm(x; gamma, beta, eps 1e-5) W^T + bias with the normalisation as a prologue of the row-panel GEMM kernel (bf16;
  * K = 320 or 640, n % 16 == 0) - the form the transformer blocks use for norm1/2/3 -> to_q|k|v / to_q / ff.net.0.proj */
 int mrisr_op_ln_linear(const mrisr_tensor* x_rows, const float* gamma_dev, const float* beta_dev, const float* w_dev,
@@ -669,7 +676,7 @@ int mrisr_op_conv_dgrad(int dtype, const void* dy, int B, int H, int W, int cout
  * conv_lora_down: z [B*H*W][r] f32 = conv3x3(x, A) on NHWC x of `dtype`; route 0 = planned, else 100 * (waves per pixel group: 1 or 4) +
  * K slabs (bf16).  conv_lora_dgrad: dx NHWC [B][H][W][cin] of `dtype` (+)= the transposed conv of dz [B*H*W][r] f32 (r in 4 / 8 / 12 / 16).
  * conv3x3_lora: y = conv3x3(x, W) + bias + rowvec[image] + scale * B conv3x3(x, A) + resid as the down-projection followed by the conv with
- * the rank-r term in its epilogue; rowvec_dev ([B][cout] f32) and resid may be null; splitk / tile force the conv's plan as in mrisr_op_conv3x3. */
+ * the rank-r term in its epilogue; rowvec_dev ([B][cout] f32) and resid may be null; r = 0 (a_dev, b_dev null): no adapter; splitk / tile force the conv's plan as in mrisr_op_conv3x3. */
 int mrisr_op_conv_lora_down(int dtype, const void* x_nhwc, int B, int H, int W, int cin, const float* a_dev, int r, float* z, int route,
                             void* stream);
 int mrisr_op_conv_lora_dgrad(int dtype, const float* dz, int B, int H, int W, int r, const float* a_dev, int cin, void* dx_nhwc, int accumulate,

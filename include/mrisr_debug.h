@@ -23,8 +23,17 @@ void mrisr_debug_force_tile(int tile);
 void mrisr_debug_prefer_tile(int tile);
 /* bit flags: 8 = rank-4 LoRA up-projection in the scalar epilogue instead of on the matrix cores; 16 = head-major outputs
  * stored straight from the accumulator layout instead of through LDS; 2048 = every GEMM workgroup fills its LDS allocation with
- * 0xFF bytes (NaN) before its first LDS-DMA, so that a read that runs ahead of its DMA cannot return plausible stale data */
+ * 0xFF bytes (NaN) before its first LDS-DMA, so that a read that runs ahead of its DMA cannot return plausible stale data;
+ * 64 = the plain staged epilogue of the tiled and halo GEMM kernels (alpha * acc + bias [+ time row] into the LDS tile) runs
+ * through the generic per-fragment epilogue, as it did, instead of its own few lines (the same operations: bit-identical outputs) */
 void mrisr_debug_gemm_flags(int flags);
+/* probe (tools/probes/bl_stamps.py): dev_buf = 256 slots of (8 + 8 * 1024) u64.  Every eager launch of tile id `tile` on the tiled
+ * 2-stage kernel or the 4-wave halo kernel takes the next slot (the counted-ring tiles carry no stamps; launches past the last slot are not
+ * stamped): 8 words describing the launch (M, N, K, workgroups, 1 residual | 2 in-kernel LoRA | 4 conv | 8 1x1 tail, split-K, gemm flags, 1), then per workgroup (the
+ * first 1024) 8 clock stamps (shader-clock ticks) of wave 0: entry, offsets and descriptors ready, first stage landed, K loop done, bias / LoRA
+ * ready, tile staged in LDS, residual loaded (written by the staged row copy-out only: 0 for head-major and unstaged outputs), last store
+ * issued.  Workgroups past the first 1024 write nothing.  NULL (default) = off; each call restarts at slot 0 */
+void mrisr_debug_gemm_stamps(void* dev_buf, int tile);
 /* cost-model efficiency of one tile id (only used when the autotuner is off) */
 void mrisr_debug_set_tile_eff(int tile, double eff);
 /* override one entry of the in-process tile table (key as in the MRISR_TUNE_CACHE file) */

@@ -279,18 +279,21 @@ static int op_conv3x3_lora_t(const mrisr_tensor* x, const float* w, const float*
     DevBuf wp, av, sb, zb, scr, part;
     TRY(wp.reserve((size_t)cout * Cin * 9 * sizeof(T), false));
     TRY(launch_pack_conv3x3<T>(w, wp.p, cout, Cin, 3, st));
-    TRY(av.reserve((size_t)r * 9 * Cin * sizeof(T), false));
-    TRY(sb.reserve((size_t)cout * r * sizeof(float), false));
-    TRY(zb.reserve((size_t)M * r * sizeof(float), false));
-    TRY(launch_conv_lora_pack<T>(A, Bm, scale, av.p, nullptr, static_cast<float*>(sb.p), nullptr, Cin, cout, r, st));
-    const size_t sbytes = conv_lora_down_scratch_bytes(M, Cin, r, sizeof(T));
-    if (sbytes) TRY(scr.reserve(sbytes, false));
-    TRY(launch_conv_lora_down<T>(x->data, av.p, static_cast<float*>(zb.p), B, H, W, Cin, r, static_cast<float*>(scr.p), st));
+    if (r > 0) {  // (r = 0: the conv with its row vector and residual alone)
+        TRY(av.reserve((size_t)r * 9 * Cin * sizeof(T), false));
+        TRY(sb.reserve((size_t)cout * r * sizeof(float), false));
+        TRY(zb.reserve((size_t)M * r * sizeof(float), false));
+        TRY(launch_conv_lora_pack<T>(A, Bm, scale, av.p, nullptr, static_cast<float*>(sb.p), nullptr, Cin, cout, r, st));
+        const size_t sbytes = conv_lora_down_scratch_bytes(M, Cin, r, sizeof(T));
+        if (sbytes) TRY(scr.reserve(sbytes, false));
+        TRY(launch_conv_lora_down<T>(x->data, av.p, static_cast<float*>(zb.p), B, H, W, Cin, r, static_cast<float*>(scr.p), st));
+    }
     GemmArgs g;
     ga_rows(g, x->data, Cin, Cin); ga_conv3(g, B, H, W); ga_weight(g, wp.p, M, cout, 9 * Cin); g.bias = bias;
     if (rowvec) ga_rowvec(g, rowvec, cout, H * W);
     if (resid) ga_resid(g, resid->data, cout);
-    ga_out(g, y->data, cout); ga_lora_epilogue(g, static_cast<const float*>(zb.p), r, static_cast<const float*>(sb.p), r, cout);
+    ga_out(g, y->data, cout);
+    if (r > 0) ga_lora_epilogue(g, static_cast<const float*>(zb.p), r, static_cast<const float*>(sb.p), r, cout);
     ForcedTile forced(tile);
     TRY(op_plan<T>(g, splitk, !tile, part));
     TRY(launch_gemm<T>(g, st));
@@ -378,6 +381,51 @@ int mrisr_op_linear(const mrisr_tensor* x, const float* w_dev, const float* bias
     ForcedTile forced(tile);
     TRY(f32 ? op_plan<float>(g, splitk, false, part) : op_plan<bf16>(g, splitk, false, part));
     TRY(f32 ? launch_gemm<float>(g, st) : launch_gemm<bf16>(g, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
+// y = x W^T + bias + rowvec[m / (M / rowvec_rows)] + s B (A x) + resid on bf16 rows: a projection with everything its epilogue can carry, as
+// Runner::linear builds it (the adapter's z = x A^T inside the kernel where the tile computes it, else by launch_lora_down).  resid may be y.
+int mrisr_op_linear_resid(const mrisr_tensor* x, const float* w_dev, const float* bias_dev, int n, const float* rowvec_dev, int rowvec_rows,
+                          const float* lora_a_dev, const float* lora_b_dev, int lora_r, float lora_scale, const mrisr_tensor* resid, int splitk,
+                          int tile, mrisr_tensor* y, void* stream) {
+    API_BEGIN
+    typedef bf16 T;
+    MRISR_REQUIRE(x && y && w_dev && x->dtype == MRISR_BF16 && y->dtype == MRISR_BF16 && x->ndim == 2 && y->ndim == 2, "linear + residual: bf16 rows in/out");
+    MRISR_REQUIRE(!resid || (resid->dtype == MRISR_BF16 && resid->ndim == 2 && resid->shape[0] == x->shape[0] && resid->shape[1] >= n), "residual rows");
+    TRY(gemm_prepare());
+    hipStream_t st = (hipStream_t)stream;
+    const int M = (int)x->shape[0], K = (int)x->shape[1];
+    MRISR_REQUIRE(!rowvec_dev || (rowvec_rows >= 1 && M % rowvec_rows == 0), "row vector: rows dividing M");
+    MRISR_REQUIRE(lora_r == 0 || (lora_r >= 1 && lora_r <= 16 && lora_a_dev && lora_b_dev && splitk <= 1), "adapter: rank 1 .. 16, A and B, un-split");
+    DevBuf wp, part, av, sb, zb;
+    TRY(wp.reserve((size_t)n * K * sizeof(T), false));
+    TRY(launch_pack_rows<T>(w_dev, n, K, wp.p, K, 0, 0, 0, 0, 1.0f, st));
+    GemmArgs g = op_linear_args(x, wp.p, n, bias_dev, ACT_NONE, y);
+    if (rowvec_dev) ga_rowvec(g, rowvec_dev, n, M / rowvec_rows);
+    if (resid) ga_resid(g, resid->data, (int)resid->shape[1]);
+    ForcedTile forced(tile);
+    if (!lora_r) {
+        TRY(op_plan<T>(g, splitk, false, part));
+    } else {
+        TRY(av.reserve((size_t)lora_r * K * sizeof(T), false));
+        TRY(sb.reserve((size_t)n * lora_r * sizeof(float), false));
+        TRY(zb.reserve((size_t)M * lora_r * sizeof(float), false));
+        TRY(launch_pack_rows<T>(lora_a_dev, lora_r, K, av.p, K, 0, 0, 0, 0, 1.0f, st));
+        TRY(launch_pack_rows<float>(lora_b_dev, n, lora_r, sb.p, lora_r, 0, 0, 0, 0, lora_scale, st));
+        ga_lora_epilogue(g, nullptr, lora_r, static_cast<const float*>(sb.p), lora_r, n);
+        g.no_rp = 1;
+        TRY(op_plan<T>(g, 0, false, part));
+        if (g.splitk == 1 && gemm_tile_lora_in_kernel(g.tile, lora_r, lora_r)) {
+            g.lora_a = av.p; g.lora_R = lora_r;
+        } else {
+            TRY(launch_lora_down<T>(x->data, K, av.p, static_cast<float*>(zb.p), M, K, lora_r, st));
+            g.lora_z = static_cast<const float*>(zb.p);
+        }
+    }
+    TRY(launch_gemm<T>(g, st));
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
     API_END
@@ -1085,13 +1133,13 @@ int mrisr_op_conv3x3_lora(const mrisr_tensor* x, const float* w_oihw_dev, const 
     API_BEGIN
     TRY(op_dtype_ok(x));
     TRY(gemm_prepare());
-    MRISR_REQUIRE(w_oihw_dev && a_dev && b_dev && y, "conv3x3 + LoRA: null argument");
+    MRISR_REQUIRE(w_oihw_dev && y && (r == 0 || (a_dev && b_dev)), "conv3x3 + LoRA: null argument");
     MRISR_REQUIRE(x->layout == MRISR_NHWC && y->layout == MRISR_NHWC && y->dtype == x->dtype && (!resid || (resid->layout == MRISR_NHWC && resid->dtype == x->dtype)),
                   "NHWC in/out, same dtype");
     MRISR_REQUIRE(y->shape[0] == x->shape[0] && y->shape[1] == cout && y->shape[2] == x->shape[2] && y->shape[3] == x->shape[3], "conv output shape");
     MRISR_REQUIRE(!resid || (resid->shape[0] == y->shape[0] && resid->shape[1] == cout && resid->shape[2] == y->shape[2] && resid->shape[3] == y->shape[3]),
                   "residual of the output's shape");
-    MRISR_REQUIRE(r >= 1 && r <= 16 && x->shape[1] % (x->dtype == MRISR_F32 ? 32 : 64) == 0 && cout % 4 == 0, "conv3x3 + LoRA: rank <= 16, whole K tiles");
+    MRISR_REQUIRE(r >= 0 && r <= 16 && x->shape[1] % (x->dtype == MRISR_F32 ? 32 : 64) == 0 && cout % 4 == 0, "conv3x3 + LoRA: rank <= 16, whole K tiles");
     hipStream_t st = (hipStream_t)stream;
     return x->dtype == MRISR_F32 ? op_conv3x3_lora_t<float>(x, w_oihw_dev, bias_dev, a_dev, b_dev, r, scale, rowvec_dev, resid, cout, splitk, tile, y, st)
                                  : op_conv3x3_lora_t<bf16>(x, w_oihw_dev, bias_dev, a_dev, b_dev, r, scale, rowvec_dev, resid, cout, splitk, tile, y, st);

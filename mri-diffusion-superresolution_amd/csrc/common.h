@@ -142,6 +142,10 @@ struct GemmArgs {
     int act = ACT_NONE;
     const void* resid = nullptr;    // + resid[m][n] (T), pitch ldr; added after the activation
     int ldr = 0;
+    // 1: the residual joins the f32 value ahead of the ONE rounding on every tile.  A staged tile otherwise rounds to T, adds the residual on its
+    // way out and rounds again (what inference has always computed); a gradient accumulated through `resid` must not depend on which tile and
+    // split the tuner happened to time fastest for its shape.  Host side only: launch_gemm turns it into stage_out = 3 for the launch
+    int resid_exact = 0;
     int out_mode = OUT_ROWS;
     void* out = nullptr;            // OUT_ROWS: T [M][ldo]; OUT_F32: float [M][ldo]
     int ldo = 0;
@@ -176,6 +180,9 @@ struct GemmArgs {
     int no_rp = 0;    // the caller's operand forms rule the row-panel kernel out (e.g. LoRA of a rank it does not fuse)
     int group_m = 1;  // M tiles per group of the tile order (set by the launchers: auto_group_m; MRISR_GROUP_M)
     int dbg = 0;  // cross-check switches (mrisr_debug_gemm_flags): 8 scalar LoRA up-projection, 16 unstaged head-major stores
+    // probe (mrisr_debug_gemm_stamps; set by launch_gemm, null = off): this launch's slot of the stamp buffer - 8 u64 describing the launch,
+    // then 8 clock stamps per workgroup written by wave 0 of gemm_bl_kernel / gemm_halo_kernel at their phase boundaries
+    unsigned long long* stamps = nullptr;
 };
 
 template <typename T> int launch_gemm(const GemmArgs& g, hipStream_t st);

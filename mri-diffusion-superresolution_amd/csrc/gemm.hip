@@ -228,6 +228,26 @@ __device__ __forceinline__ void preload_cols(const GemmArgs& g, int nbase, float
     }
 }
 
+// The same operands as register vectors: every load issued before the first add, with no branch between them (the form above branches
+// around each load and adds fragment by fragment - NFR round trips when the loads miss).  The same sums b + t, except that an absent operand
+// is skipped where the form above adds +0.0: a bias element that is exactly -0.0 stays -0.0 here and becomes +0.0 there, which shows in an
+// output only where alpha * acc is -0.0 as well (+0.0 there, -0.0 here).  Both settings of mrisr_debug_gemm_flags & 64 use this form: the
+// flag switches the epilogue that follows, not the preload, so the bit-equality tests compare epilogues, not this corner.
+template <int NFR>
+__device__ __forceinline__ void preload_cols(const GemmArgs& g, int nbase, f32x4 (&pb)[NFR]) {
+    const bool fold = g.rowvec && g.rowvec_div >= g.M;
+#pragma unroll
+    for (int i = 0; i < NFR; ++i) pb[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (g.bias) {
+#pragma unroll
+        for (int i = 0; i < NFR; ++i) pb[i] = *reinterpret_cast<const f32x4*>(g.bias + min(nbase + i * 16, g.N - 4));
+    }
+    if (fold) {
+#pragma unroll
+        for (int i = 0; i < NFR; ++i) pb[i] += *reinterpret_cast<const f32x4*>(g.rowvec + min(nbase + i * 16, g.N - 4));
+    }
+}
+
 // ---- MFMA wrappers -------------------------------------------------------------------------------
 template <typename T> struct Frag;
 template <> struct Frag<bf16> { typedef bf16x8 type; };
@@ -256,6 +276,30 @@ __device__ __forceinline__ void lds_poison(char* smem_base, int nthreads) {
     __syncthreads();
 }
 static int gemm_flags_now();
+
+// Probe (mrisr_debug_gemm_stamps, tools/probes/bl_stamps.py): every launch of the stamped tile id gets one slot of the caller's buffer -
+// kStampHdr u64 that describe the launch (written by workgroup 0), then 8 clock stamps (s_memtime: shader-clock ticks) per workgroup, written by lane 0
+// of wave 0 with ordinary global stores.  Returns that workgroup's 8 words (a uniform value: it stays in scalar registers); null when the
+// launch is not stamped.  The kernels call it at every stamp instead of keeping the pointer: nothing of the probe is live across their K loops.
+static constexpr int kStampHdr = 8, kStampWgs = 1024, kStampSlotWords = kStampHdr + 8 * kStampWgs, kStampSlots = 256;
+__device__ __forceinline__ unsigned long long* gemm_stamp_slot(const GemmArgs& g, bool header) {
+    if (!g.stamps) return nullptr;
+    const unsigned wg = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+    if (header && wg == 0 && threadIdx.x == 0) {
+        g.stamps[0] = (unsigned long long)g.M; g.stamps[1] = (unsigned long long)g.N; g.stamps[2] = (unsigned long long)g.K;
+        g.stamps[3] = (unsigned long long)gridDim.x * gridDim.y * gridDim.z;
+        g.stamps[4] = (g.resid ? 1u : 0u) | (g.lora_a ? 2u : 0u) | (g.conv ? 4u : 0u) | (g.cs0 ? 8u : 0u);
+        g.stamps[5] = (unsigned long long)g.splitk; g.stamps[6] = (unsigned long long)(unsigned)g.dbg; g.stamps[7] = 1ull;
+    }
+    return wg < (unsigned)kStampWgs ? g.stamps + kStampHdr + (size_t)wg * 8 : nullptr;
+}
+// word k (0 .. 7) of this workgroup's stamps, or null: the ONLY way to an address inside the stamp buffer.  Workgroups past kStampWgs and
+// launches that are not stamped get null here and must store nothing (never offset the null).
+__device__ __forceinline__ unsigned long long* gemm_stamp_word(const GemmArgs& g, int k, bool header = false) {
+    unsigned long long* const slot = gemm_stamp_slot(g, header);
+    return slot ? slot + k : nullptr;
+}
+static_assert(kStampSlotWords == kStampHdr + 8 * kStampWgs, "a slot: the header, then 8 words for each of the first kStampWgs workgroups");
 
 template <typename T, int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(256) void gemm_kernel(const GemmArgs g, const char* __restrict__ zero) {
@@ -503,7 +547,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmArgs g, const char*
 // =================================================================================================
 // staged epilogue: the tile sits in LDS as [BM][pitch] T; write it out row by row, 16 bytes per lane
 template <int BM, int BN, int NT = 256>
-__device__ __forceinline__ void copy_out_tile(const GemmArgs& g, const bf16* otile, int pitch, int m0, int n0, int z, bool add_resid) {
+__device__ __forceinline__ void copy_out_tile(const GemmArgs& g, const bf16* otile, int pitch, int m0, int n0, int z, bool add_resid,
+                                              unsigned long long* stamp_resid = nullptr) {
     __syncthreads();
     constexpr int CPR = BN / 8;  // 16-byte chunks per tile row
     bf16* out = reinterpret_cast<bf16*>(g.out) + (size_t)z * g.o_bs;
@@ -520,6 +565,10 @@ __device__ __forceinline__ void copy_out_tile(const GemmArgs& g, const bf16* oti
             const int row = idx / CPR, ch = idx - row * CPR;
             const int m = m0 + row, n = n0 + ch * 8;
             if (res && idx < TOTAL && m < g.M && n + 8 <= g.N) rv[u] = *reinterpret_cast<const bf16x8*>(res + (size_t)m * g.ldr + n);
+        }
+        if (stamp_resid && it0 == 0 && threadIdx.x == 0) {  // probe (gemm_stamp_word(g, 6), or null): the first batch's residual pieces are in registers
+            if (res) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            *stamp_resid = __builtin_readcyclecounter();
         }
 #pragma unroll
         for (int u = 0; u < BATCH; ++u) {
@@ -681,6 +730,16 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int z = blockIdx.z;
     const int split = blockIdx.y;
+    auto stamp = [&](int k, bool drain = false) {  // probe: off unless this launch is stamped
+        if constexpr (NSTAGE == 2) {  // (the counted rings carry no stamps: nothing of the probe in their register budget)
+            unsigned long long* const stp = gemm_stamp_word(g, k, k == 0);
+            if (stp && tid == 0) {
+                if (drain) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (a phase that ends with loads in flight: until they are back)
+                *stp = __builtin_readcyclecounter();
+            }
+        }
+    };
+    stamp(0);
     if (g.dbg & 2048) lds_poison(smem, (int)blockDim.x);
 
     const int ntn = (g.N + BN - 1) / BN;
@@ -905,12 +964,15 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
         }
     };
 
+    stamp(1);
+
     if constexpr (NSTAGE == 2) {
         if (kt_beg < kt_end) {
             if (g.pretouch) pretouch_weights(rw, (long long)g.N * g.K * 2, smem + STAGE, wave, lane, g.pretouch);
             stage(kt_beg, 0);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
+            stamp(2);
             int cur = 0;
             const bool halves = (g.dbg & 16384) != 0;
             for (int kt = kt_beg; kt < kt_end; ++kt) {
@@ -949,6 +1011,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
             // (their MFMAs consumed them; lgkmcnt(0) makes it explicit) before any wave passes this barrier.
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
+            if (kt == kt_beg) stamp(2);
             if (kt + NSTAGE - 1 < kt_end) stage(kt + NSTAGE - 1, (slot + NSTAGE - 1) % NSTAGE);
             compute(slot, []() {});
             slot = slot + 1 == NSTAGE ? 0 : slot + 1;
@@ -956,6 +1019,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
         __syncthreads();  // the epilogue reuses the stage buffers
     }
 
+    stamp(3);
     float* zlds = reinterpret_cast<float*>(smem);  // [BM][16] f32: z rows of this tile (the stages are drained)
     if (LORA) {
         if (zwave) {
@@ -1010,8 +1074,20 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
                 return;
         }
     }
-    float pb[NF][4];
-    preload_cols<NF>(g, n0 + wn0 + fg * 4, pb);
+    // (the counted rings keep the form they had - float rows, fragment by fragment - and with it their register count)
+    constexpr bool kRing = NSTAGE > 2;
+    f32x4 pb[kRing ? 1 : NF];
+    float pbr[kRing ? NF : 1][4];
+    if constexpr (kRing) preload_cols<NF>(g, n0 + wn0 + fg * 4, pbr);
+    else preload_cols<NF>(g, n0 + wn0 + fg * 4, pb);
+    auto cols = [&](int i, float (&o)[4]) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if constexpr (kRing) o[r] = pbr[i][r];
+            else o[r] = pb[i][r];
+        }
+    };
+    stamp(4, true);
     if (g.act == ACT_GEGLU) {
         if constexpr (NF % 2 == 0) {
 #pragma unroll
@@ -1023,10 +1099,13 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
                     if (m < g.M && n < g.N) {
                         float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
                         float vg[4] = {acc[i + 1][j][0], acc[i + 1][j][1], acc[i + 1][j][2], acc[i + 1][j][3]};
-                        epilogue4<T>(g, z, m, n, v, vg, nullptr, nullptr, false, true, nullptr, 0, 0, 0, pb[i], pb[i + 1]);
+                        float bu[4], bg[4];
+                        cols(i, bu); cols(i + 1, bg);
+                        epilogue4<T>(g, z, m, n, v, vg, nullptr, nullptr, false, true, nullptr, 0, 0, 0, bu, bg);
                     }
                 }
         }
+        stamp(7);
         return;
     }
     // plain row outputs leave through LDS: the accumulator layout gives every lane 8 bytes of a row (32-byte runs per
@@ -1045,21 +1124,58 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
                   g.batch == 1;
         htr = (sec == 0 ? g.sec_tr[0] : (sec == 1 ? g.sec_tr[1] : g.sec_tr[2])) != 0;
     }
+    // The plain staged form - alpha * acc + column operands [+ the image's time row] into the LDS tile, as rows or as a [token][channel]
+    // head-major section; LoRA already on the matrix cores, the residual left to the copy-out pass - is what nearly every projection and conv
+    // of a denoising step runs, and it goes through its own few lines: epilogue4 decides the
+    // same thing once per fragment over some thirty uniform branches on launch fields re-read from the kernel arguments, 8,000 instructions
+    // after the last MFMA in the 64 x 160 instantiation, and the clock stamps put that loop at 20,000 ticks of a 62,000-tick workgroup there
+    // (K = 640: longer than the K loop; profiles/bl_stamps.log).  The same operations in the same order as epilogue4 takes for this form;
+    // mrisr_debug_gemm_flags & 64 sends it through epilogue4 again.
+    // (the counted rings keep epilogue4: the extra path costs their LoRA forms a wave per SIMD in registers, and no table row picks them)
+    const bool plain_epi = !kRing && !(g.dbg & 64) && (staged || (hstaged && !htr)) && g.act == ACT_NONE && !g.lora_z && !(LORA && !lora_mma) &&
+                           (!g.resid || resid_later);
+    if constexpr (!kRing) {
+        if (plain_epi) {
+            const float alpha = g.alpha;
+            const bool rows_rv = g.rowvec && g.rowvec_div < g.M;  // a time row per image (else folded into pb)
 #pragma unroll
-    for (int i = 0; i < NF; ++i)
+            for (int i = 0; i < NF; ++i)
 #pragma unroll
-        for (int j = 0; j < MF; ++j) {
-            const int m = m0 + wm0 + j * 16 + fr;
-            const int n = n0 + wn0 + i * 16 + fg * 4;
-            if (m < g.M && n < g.N) {
-                float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-                epilogue4<T>(g, z, m, n, v, nullptr, LORA && !lora_mma ? zlds + (m - m0) * 16 : nullptr,
-                             staged || (hstaged && !htr) ? otile + (m - m0) * OPITCH + (n - n0) : nullptr, resid_later, true,
-                             hstaged && htr ? otile : nullptr, m - m0, n - n0, BM + 8, pb[i]);
-            }
+                for (int j = 0; j < MF; ++j) {
+                    const int ml = wm0 + j * 16 + fr, nl = wn0 + i * 16 + fg * 4;
+                    if (m0 + ml < g.M && n0 + nl < g.N) {
+                        f32x4 a = acc[i][j];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) a[r] = a[r] * alpha + pb[i][r];
+                        if (rows_rv) a += *reinterpret_cast<const f32x4*>(g.rowvec + (size_t)((m0 + ml) / g.rowvec_div) * g.rowvec_ld + n0 + nl);
+                        const bf16x4 o = {(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3]};
+                        *reinterpret_cast<bf16x4*>(otile + ml * OPITCH + nl) = o;
+                    }
+                }
         }
-    if (staged) copy_out_tile<BM, BN>(g, otile, OPITCH, m0, n0, z, resid_later);
+    }
+    if (!plain_epi) {
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+            for (int j = 0; j < MF; ++j) {
+                const int m = m0 + wm0 + j * 16 + fr;
+                const int n = n0 + wn0 + i * 16 + fg * 4;
+                if (m < g.M && n < g.N) {
+                    float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+                    float pbi[4];
+                    cols(i, pbi);
+                    epilogue4<T>(g, z, m, n, v, nullptr, LORA && !lora_mma ? zlds + (m - m0) * 16 : nullptr,
+                                 staged || (hstaged && !htr) ? otile + (m - m0) * OPITCH + (n - n0) : nullptr, resid_later, true,
+                                 hstaged && htr ? otile : nullptr, m - m0, n - n0, BM + 8, pbi);
+                }
+            }
+    }
+    stamp(5);
+    // (stamp 6 is written inside copy_out_tile only: a launch that is not staged as rows leaves it zero, and the probe tells them apart by that)
+    if (staged) copy_out_tile<BM, BN>(g, otile, OPITCH, m0, n0, z, resid_later, NSTAGE == 2 ? gemm_stamp_word(g, 6) : nullptr);
     else if (hstaged) copy_out_heads<BM, BN>(g, otile, m0, n0, htr);
+    stamp(7);
 }
 
 // =================================================================================================
@@ -1086,6 +1202,14 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int split = blockIdx.y;
+    auto stamp = [&](int k, bool drain = false) {  // probe, as in gemm_bl_kernel (the same eight points)
+        unsigned long long* const stp = gemm_stamp_word(g, k, k == 0);
+        if (stp && tid == 0) {
+            if (drain) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            *stp = __builtin_readcyclecounter();
+        }
+    };
+    stamp(0);
     if (g.dbg & 2048) lds_poison(smem, (int)blockDim.x);
     const int Wd = g.Win, Hd = g.Hin;
     const int TH = BM / Wd, PW = Wd + 2;
@@ -1259,6 +1383,8 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
         }
     };
 
+    stamp(1);
+
     if (ch_beg < ch_end || sc_beg < sc_end) {
         int cur = 0;
         if (g.pretouch) pretouch_weights(rw, (long long)g.N * g.K * 2, wbase + WSTAGE, wave, lane, g.pretouch);
@@ -1268,6 +1394,7 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
             stage_patch(ch);  // the previous chunk's last tap ended with a barrier: the patch buffer is free
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
+            if (ch == ch_beg) stamp(2);
             if (g.dbg & 1024) {
                 // probe (MRISR_GEMM_FLAGS=1024; results are wrong): what GroupNorm + SiLU applied in the CONSUMER would cost - one LDS -> VALU -> LDS pass over
                 // the staged patch per 64-channel chunk (scale / shift per channel from LDS-resident vectors would come on top)
@@ -1305,6 +1432,7 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
             cur ^= 1;
         }
     }
+    stamp(3);
 
     if (g.splitk > 1) {
         float* part = g.partial + (size_t)split * (size_t)g.M * g.N;
@@ -1329,21 +1457,46 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
     T* otile = reinterpret_cast<T*>(smem);
     const bool staged = g.out_mode == OUT_ROWS && (g.ldo & 7) == 0 && (size_t)BM * OPITCH * 2 <= (size_t)pit * 4096 + 2 * WSTAGE && g.stage_out > 1;
     const bool resid_later = staged && g.resid != nullptr && (g.ldr & 7) == 0 && g.stage_out < 3;
-    float pb[NF][4];
+    f32x4 pb[NF];
     preload_cols<NF>(g, n0 + wn0 + fg * 4, pb);
+    stamp(4, true);
+    // the plain staged form on its own few lines, as in gemm_bl_kernel (see there; flag 64 = through epilogue4): conv2 + residual, the shortcut-fused conv2
+    const bool plain_epi = !(g.dbg & 64) && staged && g.act == ACT_NONE && !g.lora_z && (!g.resid || resid_later);
+    if (plain_epi) {
+        const float alpha = g.alpha;
+        const bool rows_rv = g.rowvec && g.rowvec_div < g.M;  // conv1: a time row per image (else folded into pb)
 #pragma unroll
-    for (int i = 0; i < NF; ++i)
+        for (int i = 0; i < NF; ++i)
 #pragma unroll
-        for (int j = 0; j < MF; ++j) {
-            const int m = m0 + wm0 + j * 16 + fr;
-            const int n = n0 + wn0 + i * 16 + fg * 4;
-            if (m < g.M && n < g.N) {
-                float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-                epilogue4<T>(g, 0, m, n, v, nullptr, nullptr, staged ? otile + (m - m0) * OPITCH + (n - n0) : nullptr, resid_later, true, nullptr,
-                             0, 0, 0, pb[i]);
+            for (int j = 0; j < MF; ++j) {
+                const int ml = wm0 + j * 16 + fr, nl = wn0 + i * 16 + fg * 4;
+                if (m0 + ml < g.M && n0 + nl < g.N) {
+                    f32x4 a = acc[i][j];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) a[r] = a[r] * alpha + pb[i][r];
+                    if (rows_rv) a += *reinterpret_cast<const f32x4*>(g.rowvec + (size_t)((m0 + ml) / g.rowvec_div) * g.rowvec_ld + n0 + nl);
+                    const bf16x4 o = {(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3]};
+                    *reinterpret_cast<bf16x4*>(otile + ml * OPITCH + nl) = o;
+                }
             }
-        }
-    if (staged) copy_out_tile<BM, BN>(g, otile, OPITCH, m0, n0, 0, resid_later);
+    } else {
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+            for (int j = 0; j < MF; ++j) {
+                const int m = m0 + wm0 + j * 16 + fr;
+                const int n = n0 + wn0 + i * 16 + fg * 4;
+                if (m < g.M && n < g.N) {
+                    float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+                    const float pbi[4] = {pb[i][0], pb[i][1], pb[i][2], pb[i][3]};
+                    epilogue4<T>(g, 0, m, n, v, nullptr, nullptr, staged ? otile + (m - m0) * OPITCH + (n - n0) : nullptr, resid_later, true, nullptr,
+                                 0, 0, 0, pbi);
+                }
+            }
+    }
+    stamp(5);
+    if (staged) copy_out_tile<BM, BN>(g, otile, OPITCH, m0, n0, 0, resid_later, gemm_stamp_word(g, 6));
+    stamp(7);
 }
 
 // =================================================================================================
@@ -3407,10 +3560,20 @@ static int tune(const GemmArgs& g0, int* tile_out, int* split_out) {
 static int g_force_split = 0;  // test hook: split-K factor for every GEMM that can be split (exercises the reduce kernel's epilogue)
 extern "C" void mrisr_debug_force_split(int s) { g_force_split = s; }
 // test hook / MRISR_GEMM_FLAGS: 8 = LoRA up-projection in the scalar epilogue instead of the matrix cores, 16 = head-major outputs
-// stored straight from the accumulator layout instead of through LDS (the older code paths, kept as cross-checks)
+// stored straight from the accumulator layout instead of through LDS (the older code paths, kept as cross-checks); 64 = the plain staged
+// epilogue of the tiled and halo kernels goes through the generic epilogue4 instead of its own few lines
 static int g_gemm_flags = [] { const char* e = getenv("MRISR_GEMM_FLAGS"); return e ? atoi(e) : 0; }();
 extern "C" void mrisr_debug_gemm_flags(int f) { g_gemm_flags = f; }
 static int gemm_flags_now() { return g_gemm_flags; }
+// probe: every launch of tile id `tile` on gemm_bl_kernel / gemm_halo_kernel fills the next slot of dev_buf (kStampSlots slots of kStampSlotWords
+// u64: see gemm_stamp_slot; launches past the last slot are not stamped); NULL = off.  Eager launches only: a captured graph would keep the slot.
+static unsigned long long* g_stamp_buf = nullptr;
+static int g_stamp_tile = 0, g_stamp_next = 0;
+extern "C" void mrisr_debug_gemm_stamps(void* dev_buf, int tile) {
+    g_stamp_buf = static_cast<unsigned long long*>(dev_buf);
+    g_stamp_tile = tile;
+    g_stamp_next = 0;
+}
 int xattn_tail_flags() { return g_gemm_flags; }
 // tools/table_search.py: overrides one entry of the tile table in this process (key as in the table file)
 extern "C" void mrisr_debug_set_tuned(const char* key, int tile, int split) { g_tuned[key] = {tile, split}; }
@@ -3527,8 +3690,11 @@ int launch_gemm(const GemmArgs& g_in, hipStream_t st) {
     const char* why = nullptr;
     MRISR_REQUIRE(tile_admits(g, is_bf16, tile, &why), why);
     static const int stage_env = [] { const char* e = getenv("MRISR_STAGE_OUT"); return e ? atoi(e) : 2; }();  // 0 off, 1 tiled kernels, 2 + halo kernels (default), 3: as 2 but residual added before staging
-    g.stage_out = stage_env;
+    // (resid_exact: the residual ahead of the one rounding - form 3 where rows are staged at all, else unstaged; the kernels read stage_out only)
+    g.stage_out = g.resid_exact ? (stage_env >= 2 ? 3 : 0) : stage_env;
     g.dbg = g_gemm_flags;
+    g.stamps = nullptr;
+    if (g_stamp_buf && tile == g_stamp_tile && g_stamp_next < kStampSlots) g.stamps = g_stamp_buf + (size_t)(g_stamp_next++) * kStampSlotWords;
     {   // cold-weight pre-touch: matrices of at least MRISR_PRETOUCH_MIN_KB (default 512; 0 ... 1024 measure the same); MRISR_PRETOUCH=0 turns it off
         static const int on = [] { const char* e = getenv("MRISR_PRETOUCH"); return e ? atoi(e) : 1; }();
         static const long long min_b = [] { const char* e = getenv("MRISR_PRETOUCH_MIN_KB"); return (e ? atoll(e) : 512ll) * 1024; }();

@@ -63,7 +63,7 @@ int conv_dgrad_run(hipStream_t st, bool dry, const TrainGemmFn& run_gemm, const 
     }
     GemmArgs g;
     ga_rows(g, dy, cout, cout); ga_conv3(g, B, H, W, 1, mode, 1, mode); ga_weight(g, wd, B * Ho * Wo, cin, 9 * cout);
-    if (resid) ga_resid(g, resid, ldr);
+    if (resid) { ga_resid(g, resid, ldr); g.resid_exact = 1; }  // dX += ...: one rounding whatever kernel the planner picks
     ga_out(g, out, cin);
     return run_gemm(g);
 }

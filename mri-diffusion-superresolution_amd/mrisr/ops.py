@@ -87,6 +87,24 @@ def linear(x, weight, bias=None, act=L.ACT_NONE, splitk=0, tile=0):
     return y
 
 
+def linear_resid(x, weight, bias=None, rowvec=None, lora_a=None, lora_b=None, lora_scale=1.0, resid=None, out=None, splitk=0, tile=0):
+    """x [M,K] bf16, weight [N,K] -> x weight^T + bias + rowvec[m // (M // R)] + lora_scale * lora_b (lora_a x) + resid: a projection with all
+    its epilogue operands.  rowvec [R,N] f32 (R divides M; R = 1: one row for every output row), lora_a [r,K], lora_b [N,r], resid [M,N]
+    bf16.  ``out``: the output tensor; passing ``resid`` itself runs the projection in place."""
+    x = x.contiguous()
+    f = lambda a: a.detach().to(torch.float32).contiguous() if a is not None else None
+    w, b, rv, la, lb = (f(a) for a in (weight, bias, rowvec, lora_a, lora_b))
+    n = w.shape[0]
+    y = out if out is not None else torch.empty((x.shape[0], n), dtype=x.dtype, device=x.device)
+    tx, ty = L.as_tensor(x), L.as_tensor(y)
+    tr = L.as_tensor(resid) if resid is not None else None
+    p = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+    L.check(L.lib().mrisr_op_linear_resid(C.byref(tx), p(w), p(b), n, p(rv), rv.shape[0] if rv is not None else 0, p(la), p(lb),
+                                          la.shape[0] if la is not None else 0, C.c_float(lora_scale), C.byref(tr) if tr is not None else None,
+                                          splitk, tile, C.byref(ty), L.stream_ptr()))
+    return y
+
+
 def ln_linear(x, gamma, beta, weight, bias=None, act=L.ACT_NONE):
     """LayerNorm(x) W^T + bias, the normalisation fused into the row-panel GEMM (bf16, K = 320 / 640)."""
     x = x.contiguous()
@@ -404,7 +422,7 @@ def conv_lora_dgrad(dz, A, B, H, W, dtype=torch.float32, dx=None, acc=False):
 
 def conv3x3_lora(x, weight, bias, A, Bm, scale, rowvec=None, resid=None, splitk=0, tile=0):
     """conv3x3(x, weight) + bias + rowvec[b, :, None, None] + scale * lora_B(lora_A(x)) + resid on NCHW x (f32 / bf16): the conv with the
-    adapter's rank-r term in its epilogue.  A [r,cin,3,3], Bm [cout,r,1,1], rowvec [B,cout] f32."""
+    adapter's rank-r term in its epilogue.  A [r,cin,3,3], Bm [cout,r,1,1], rowvec [B,cout] f32.  A = Bm = None: no adapter."""
     xb, tx = _nhwc(x)
     tr = None
     if resid is not None:
@@ -415,6 +433,6 @@ def conv3x3_lora(x, weight, bias, A, Bm, scale, rowvec=None, resid=None, splitk=
     cout = w.shape[0]
     yb = torch.empty((Bn, H, W, cout), dtype=x.dtype, device=x.device)
     ty = L.as_tensor(yb, L.MRISR_NHWC, shape=(Bn, cout, H, W))
-    L.check(L.lib().mrisr_op_conv3x3_lora(C.byref(tx), _p(w), _p(b), _p(a), _p(bm), a.shape[0], float(scale), _p(rv),
+    L.check(L.lib().mrisr_op_conv3x3_lora(C.byref(tx), _p(w), _p(b), _p(a), _p(bm), a.shape[0] if a is not None else 0, float(scale), _p(rv),
                                           C.byref(tr) if tr is not None else None, cout, splitk, tile, C.byref(ty), L.stream_ptr()))
     return yb.permute(0, 3, 1, 2)

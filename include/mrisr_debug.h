@@ -30,10 +30,16 @@ void mrisr_debug_gemm_flags(int flags);
 /* probe (tools/probes/bl_stamps.py): dev_buf = 256 slots of (8 + 8 * 1024) u64.  Every eager launch of tile id `tile` on the tiled
  * 2-stage kernel or the 4-wave halo kernel takes the next slot (the counted-ring tiles carry no stamps; launches past the last slot are not
  * stamped): 8 words describing the launch (M, N, K, workgroups, 1 residual | 2 in-kernel LoRA | 4 conv | 8 1x1 tail, split-K, gemm flags, 1), then per workgroup (the
- * first 1024) 8 clock stamps (shader-clock ticks) of wave 0: entry, offsets and descriptors ready, first stage landed, K loop done, bias / LoRA
+ * first 1024) 8 clock stamps (shader-clock ticks) of wave 0: entry, head finished and stage-0 DMA all issued, first stage landed, K loop done, bias / LoRA
  * ready, tile staged in LDS, residual loaded (written by the staged row copy-out only: 0 for head-major and unstaged outputs), last store
  * issued.  Workgroups past the first 1024 write nothing.  NULL (default) = off; each call restarts at slot 0 */
 void mrisr_debug_gemm_stamps(void* dev_buf, int tile);
+/* M tiles per group of the tiled kernels' tile order for every later launch; > 0: this value, NOT clamped to the launch's M tiles (a group
+ * larger than the grid, short last groups); 0 (default): MRISR_GROUP_M, else 8, clamped.  The order changes no output bit */
+void mrisr_debug_group_m(int group_m);
+/* 1: mrisr_op_conv3x3 with stride 2 (even H, W) pads the low side with 0 instead of 1 - the (0,1,0,1) padding of the VAE encoder's
+ * down-samplers - so that the op reaches that form of the tiled kernels' gather; 0 (default): pad 1 */
+void mrisr_debug_op_conv_pad0(int on);
 /* cost-model efficiency of one tile id (only used when the autotuner is off) */
 void mrisr_debug_set_tile_eff(int tile, double eff);
 /* override one entry of the in-process tile table (key as in the MRISR_TUNE_CACHE file) */

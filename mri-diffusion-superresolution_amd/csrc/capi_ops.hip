@@ -52,6 +52,11 @@ __global__ void rows_to_heads_kernel(const T* x, T* dst, int B, int N, int H, in
     }
 }
 
+// test hook: mrisr_op_conv3x3 with stride 2 pads the low side with 0 instead of 1 (diffusers' Downsample2D(padding=0), asymmetric (0,1,0,1):
+// the VAE encoder's down-sampler form, which no op reaches otherwise); even H and W, so the output shape is the same
+static int g_op_conv_pad0 = 0;
+extern "C" void mrisr_debug_op_conv_pad0(int on) { g_op_conv_pad0 = on; }
+
 template <typename T>
 static int op_conv3x3_t(const mrisr_tensor* x, const mrisr_tensor* x2, const float* w, const float* bias, int cout,
                         int stride, int ups, int act, int splitk, mrisr_tensor* y, hipStream_t st) {
@@ -90,7 +95,9 @@ static int op_conv3x3_t(const mrisr_tensor* x, const mrisr_tensor* x2, const flo
     GemmArgs g;
     ga_rows(g, x->data, C0, C0);
     if (x2) ga_rows2(g, x2->data, C1, C1);
-    ga_conv3(g, B, H, W, stride, ups);
+    const bool pad0 = g_op_conv_pad0 && stride == 2 && !ups;
+    if (pad0) MRISR_REQUIRE(H % 2 == 0 && W % 2 == 0, "stride-2 conv with pad 0: even H and W");
+    ga_conv3(g, B, H, W, stride, ups, pad0 ? 0 : 1);
     MRISR_REQUIRE(y->shape[1] == cout && y->shape[2] == g.Hout && y->shape[3] == g.Wout, "conv output shape");
     ga_weight(g, wp.p, B * g.Hout * g.Wout, cout, 9 * Cin); g.bias = bias; g.act = act; ga_out(g, y->data, cout);
     TRY(op_plan<T>(g, splitk, false, part));

@@ -13,6 +13,7 @@
 //    GEGLU gate, residual) is per-lane and the store is one 8/16-byte word per (m, 4n);
 //  * bf16 path: v_mfma_f32_16x16x32_bf16;  f32 parity path: v_mfma_f32_16x16x4_f32 (exact f32 FMA chain).
 #include "common.h"
+#include "gemm_head.h"
 #include "prof.h"
 
 #include <cstdio>
@@ -281,6 +282,8 @@ static int gemm_flags_now();
 // kStampHdr u64 that describe the launch (written by workgroup 0), then 8 clock stamps (s_memtime: shader-clock ticks) per workgroup, written by lane 0
 // of wave 0 with ordinary global stores.  Returns that workgroup's 8 words (a uniform value: it stays in scalar registers); null when the
 // launch is not stamped.  The kernels call it at every stamp instead of keeping the pointer: nothing of the probe is live across their K loops.
+// The eight points: 0 entry, 1 head finished and the stage-0 DMA all issued (pre-touch, weights, activations / patch), 2 first stage landed,
+// 3 K loop done, 4 bias / LoRA ready, 5 tile staged in LDS, 6 first residual batch loaded (copy_out_tile only), 7 last store issued.
 static constexpr int kStampHdr = 8, kStampWgs = 1024, kStampSlotWords = kStampHdr + 8 * kStampWgs, kStampSlots = 256;
 __device__ __forceinline__ unsigned long long* gemm_stamp_slot(const GemmArgs& g, bool header) {
     if (!g.stamps) return nullptr;
@@ -664,6 +667,18 @@ __device__ __forceinline__ void pretouch_weights(const __amdgpu_buffer_rsrc_t& r
     }
 }
 
+// the same shares from the launch head (gemm_head.h: the host has done the two divisions); gemm_bl_kernel and gemm_halo_kernel
+__device__ __forceinline__ void pretouch_weights_head(const __amdgpu_buffer_rsrc_t& rw, const GemmHead& h, char* scratch, int wave, int lane) {
+    const unsigned wg = blockIdx.x + blockIdx.y * (h.ntn * h.ntm);  // (gridDim.x = ntn * ntm)
+    const unsigned pieces = (h.ext_w + 1023u) >> 10;                // (admitted weights are below 2 GiB: the extent is not clamped)
+    const unsigned first = wg * h.pt_per_wg + (unsigned)wave * h.pt_per_wave;
+    for (unsigned i = 0; i < h.pt_per_wave; ++i) {
+        const unsigned pc = first + i;
+        const unsigned off = pc < pieces ? (pc << 10) + (unsigned)lane * 16u : BL_OOB;
+        bl16(rw, scratch + ((wave * 2 + (i & 1)) << 10), off, 0u);
+    }
+}
+
 // NSTAGE = 2: double buffer, one drain (vmcnt(0)) + barrier per K tile; two workgroups share a CU and hide each other's
 // load latency.  Deeper rings with a counted vmcnt were tried twice (8-wave kernels, and 3-stage 4-wave variants on
 // in-range shapes) and lost every time (profiles/r01_gemm_sweep_incl_deep_stages.log, profiles/r01b_ws_sweep.log); note that
@@ -709,7 +724,7 @@ __device__ __forceinline__ bool splitk_last_arriver(const GemmArgs& g, f32x4 (&a
 }
 
 template <int BM, int BN, int WGM, int WGN, int NSTAGE, bool LORA>
-__global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  // 2 waves / SIMD: two workgroups per CU hide each other's loads
+__global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmHead hd, const GemmArgs g) {  // 2 waves / SIMD: two workgroups per CU hide each other's loads
     // NSTAGE 3 / 4 (round 2): a ring with a COUNTED vmcnt - NSTAGE - 1 K tiles in flight per workgroup.  For the shapes whose
     // whole grid is resident at once (level-2 linears: M = 2,048, 640 workgroups of 64 x 64 = 2.5 per CU) the run time is the
     // length of ONE workgroup's chain of K-step latencies (20 steps x ~1 us); nothing else can overlap it, so the chain itself
@@ -730,52 +745,56 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int z = blockIdx.z;
     const int split = blockIdx.y;
+    // The launch head (gemm_head.h): the first two lines of the kernel arguments, read ONCE - pinned to scalar registers here, so that the loads
+    // go out together under one wait - and nothing of it is read from the arguments again.  It holds what the host knows ahead of the launch
+    // and every workgroup used to work out for itself: descriptor extents, tile counts, the split shares, the pre-touch shares, and the
+    // multipliers that replace the divisions by launch constants (exact over every non-negative int: tools/gemm_head_check.cpp).
+    GemmHead h = hd;
+    asm volatile("" : "+s"(h.w), "+s"(h.a0), "+s"(h.a1), "+s"(h.ext_w), "+s"(h.ext_a0), "+s"(h.ext_a1), "+s"(h.flags), "+s"(h.rows), "+s"(h.N),
+                 "+s"(h.wpitch), "+s"(h.lda0), "+s"(h.lda1), "+s"(h.c0));
+    asm volatile("" : "+s"(h.ntn), "+s"(h.ntm), "+s"(h.group_m), "+s"(h.mul_pg), "+s"(h.mul_gm), "+s"(h.mul_last), "+s"(h.shifts), "+s"(h.per),
+                 "+s"(h.Ct), "+s"(h.pt_per_wg), "+s"(h.pt_per_wave), "+s"(h.mul_hw), "+s"(h.mul_wd));
+    const void* lora_a = nullptr;  // (the adapter rows ride with the stage's weight DMA: their two fields come in with the head)
+    int lora_R = 0;
+    if constexpr (LORA) {
+        lora_a = g.lora_a;
+        lora_R = g.lora_R;
+        asm volatile("" : "+s"(lora_a), "+s"(lora_R));
+    }
+    const bool conv = (h.flags & GH_CONV) != 0;
     auto stamp = [&](int k, bool drain = false) {  // probe: off unless this launch is stamped
         if constexpr (NSTAGE == 2) {  // (the counted rings carry no stamps: nothing of the probe in their register budget)
-            unsigned long long* const stp = gemm_stamp_word(g, k, k == 0);
-            if (stp && tid == 0) {
-                if (drain) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (a phase that ends with loads in flight: until they are back)
-                *stp = __builtin_readcyclecounter();
+            if (k <= 1 ? (h.flags & GH_STAMPED) != 0 : g.stamps != nullptr) {  // (past the head from the arguments again: nothing of the probe is live across the K loop)
+                unsigned long long* const stp = gemm_stamp_word(g, k, k == 0);
+                if (stp && tid == 0) {
+                    if (drain) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (a phase that ends with loads in flight: until they are back)
+                    *stp = __builtin_readcyclecounter();
+                }
             }
         }
     };
     stamp(0);
-    if (g.dbg & 2048) lds_poison(smem, (int)blockDim.x);
+    if (h.flags & 2048u) lds_poison(smem, (int)blockDim.x);
 
-    const int ntn = (g.N + BN - 1) / BN;
-    const int ntm = (g.M + BM - 1) / BM;
-    const int nblk = ntn * ntm;
-    int logical;
-    {
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7, q = nblk >> 3, r = nblk & 7;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    // grouped order: within a group of `group_m` M tiles walk M first, so the workgroups that run together on an XCD share
-    // their weight tiles (group_m ways) as well as their activation tiles through that XCD's L2 (N-first order re-streamed
-    // the whole weight matrix once per M tile: 3-6x the algorithmic bytes on the wide-N and deep-K layers)
-    int tn, tm;
-    {
-        const int GM = g.group_m > 1 ? g.group_m : 1;
-        const int per_group = GM * ntn;
-        const int grp = logical / per_group;
-        const int first_m = grp * GM;
-        const int gsz = min(GM, ntm - first_m);
-        const int within = logical - grp * per_group;
-        tm = first_m + within % gsz;
-        tn = within / gsz;
-    }
+    // tile coordinates: the XCD remap, then the grouped order - within a group of `group_m` M tiles walk M first, so the workgroups that run
+    // together on an XCD share their weight tiles (group_m ways) as well as their activation tiles through that XCD's L2 (N-first order
+    // re-streamed the whole weight matrix once per M tile: 3-6x the algorithmic bytes on the wide-N and deep-K layers)
+    uint32_t tm_u, tn_u;
+    gh_tile_coords(h, blockIdx.x, tm_u, tn_u);
+    const int tm = (int)tm_u, tn = (int)tn_u;
     const int m0 = tm * BM, n0 = tn * BN;
+    int kt_beg, kt_end;
+    gh_split_range(h.per, h.wpitch >> 7, (uint32_t)split, kt_beg, kt_end);
 
-    const T* a0p = reinterpret_cast<const T*>(g.a0) + (size_t)z * g.a_bs;
-    const T* a1p = reinterpret_cast<const T*>(g.a1);
-    const T* wp = reinterpret_cast<const T*>(g.w) + (size_t)z * g.w_bs;
-    const long long a_rows = g.conv ? (long long)g.B * g.Hin * g.Win : (long long)g.M;
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(wp, (unsigned)min((long long)g.N * g.K * 2, 0x7FFFFFFFll));
-    const __amdgpu_buffer_rsrc_t ra0 = make_rsrc(a0p, (unsigned)min(a_rows * g.lda0 * 2, 0x7FFFFFFFll));
-    const __amdgpu_buffer_rsrc_t ra1 = make_rsrc(a1p ? (const void*)a1p : (const void*)a0p,
-                                                 a1p ? (unsigned)min(a_rows * g.lda1 * 2, 0x7FFFFFFFll) : 0u);
-
+    // ---- the weight side first: its descriptor and offsets need n0 only, and the stage-0 weight DMA (with the cold-weight pre-touch in
+    // front of it) leaves before any activation address is worked out ----
+    const T* wp = reinterpret_cast<const T*>(h.w);
+    const T* a0p = reinterpret_cast<const T*>(h.a0);
+    if (h.flags & GH_BATCHED) {
+        wp += (size_t)z * g.w_bs;
+        a0p += (size_t)z * g.a_bs;
+    }
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(wp, h.ext_w);
     const int lrow = tid >> 3, pch = tid & 7;
     unsigned wvo[W_IT];
 #pragma unroll
@@ -783,8 +802,38 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
         const int row = it * 32 + lrow;
         const int n = n0 + row;
         const int c = pch ^ (row & 7);
-        wvo[it] = n < g.N ? (unsigned)(((size_t)n * g.K + c * 8) * 2) : BL_OOB;
+        wvo[it] = (unsigned)n < h.N ? (unsigned)n * h.wpitch + (unsigned)c * 16u : BL_OOB;
     }
+    // adapter rows (LORA): waves 0 and 1 each bring 8 of the 16 rows of every K tile
+    const __amdgpu_buffer_rsrc_t rl = make_rsrc(LORA ? lora_a : (const void*)wp, LORA ? (unsigned)lora_R * h.wpitch : 0u);
+    unsigned lvo = BL_OOB;
+    if (LORA && (wave < 2 || NSTAGE > 2)) {  // ring variants: waves 2, 3 re-issue the two pieces (same bytes, same LDS addresses) so
+                                             // that every wave's vmcnt sees the same number of DMA instructions per stage
+        const int row = (wave & 1) * 8 + (lane >> 3);
+        const int c = (lane & 7) ^ (row & 7);
+        if (row < lora_R) lvo = (unsigned)row * h.wpitch + (unsigned)c * 16u;
+        // ring variants: no out-of-range lanes (a FULLY out-of-range piece - rows 8..15 at R <= 8 - would retire out of order and
+        // break the counted wait); the rows >= R then carry a copy of row R - 1, whose z columns only ever meet zero B entries
+        else if (NSTAGE > 2) lvo = (unsigned)(lora_R - 1) * h.wpitch + (unsigned)c * 16u;
+    }
+    auto stage_w = [&](int kt, int buf) {
+        char* sb = smem + buf * STAGE;
+        const unsigned k0b = (unsigned)kt * BK * 2;
+#pragma unroll
+        for (int it = 0; it < W_IT; ++it) bl16(rw, sb + BM * 128 + (it * 256 + wave * 64) * 16, wvo[it], k0b);
+        if (LORA && (wave < 2 || NSTAGE > 2)) bl16(rl, sb + (BM + BN) * 128 + (wave & 1) * 64 * 16, lvo, k0b);
+    };
+    if (kt_beg < kt_end) {
+        if constexpr (NSTAGE == 2) {
+            if (h.pt_per_wave) pretouch_weights_head(rw, h, smem + STAGE, wave, lane);
+        }
+        stage_w(kt_beg, 0);
+    }
+
+    // ---- the activation side: row offsets, then the stage-0 activation DMA ----
+    const T* a1p = reinterpret_cast<const T*>(h.a1);
+    const __amdgpu_buffer_rsrc_t ra0 = make_rsrc(a0p, h.ext_a0);
+    const __amdgpu_buffer_rsrc_t ra1 = make_rsrc(a1p ? (const void*)a1p : (const void*)a0p, h.ext_a1);
     // A rows: byte offsets into the current source for the current segment (plain: fixed for each source)
     unsigned avo[A_IT], avo1[A_IT];
     int ab[A_IT], ay[A_IT], ax[A_IT];  // conv: b*Hin, oy*stride-1, ox*stride-1  (ab < 0: row outside the matrix)
@@ -793,49 +842,36 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
         const int row = it * 32 + lrow;
         const int m = m0 + row;
         const int c = pch ^ (row & 7);
-        const bool ok = m < g.M;
+        const bool ok = (unsigned)m < h.rows;
         avo[it] = avo1[it] = BL_OOB;
         ab[it] = -1;
         ay[it] = ax[it] = 0;
-        if (!g.conv) {
+        if (!conv) {
             if (ok) {
-                avo[it] = (unsigned)(((size_t)m * g.lda0 + c * 8) * 2);
-                avo1[it] = (unsigned)(((size_t)m * g.lda1 + c * 8) * 2);
+                avo[it] = ((unsigned)m * h.lda0 + (unsigned)c * 8u) * 2u;
+                avo1[it] = ((unsigned)m * h.lda1 + (unsigned)c * 8u) * 2u;
             }
         } else if (ok) {
-            const int hw = g.Hout * g.Wout;
-            const int b = m / hw;
-            const int rem = m - b * hw;
-            const int oy = rem / g.Wout;
-            ab[it] = b * g.Hin;
-            ay[it] = oy * g.stride - g.pad + (g.subpix ? (z >> 1) : 0);  // sub-pixel up-sampling: the window of parity (py, px) starts py / px later
-            ax[it] = (rem - oy * g.Wout) * g.stride - g.pad + (g.subpix ? (z & 1) : 0);
+            uint32_t b, oy, ox;
+            gh_row_pixel(h, (uint32_t)m, (uint32_t)(g.Hout * g.Wout), (uint32_t)g.Wout, b, oy, ox);
+            const bool subpix = (h.flags & GH_SUBPIX) != 0;
+            ab[it] = (int)b * g.Hin;
+            ay[it] = (int)oy * g.stride - g.pad + (subpix ? (z >> 1) : 0);  // sub-pixel up-sampling: the window of parity (py, px) starts py / px later
+            ax[it] = (int)ox * g.stride - g.pad + (subpix ? (z & 1) : 0);
         }
     }
     const int acb = pch * 16;  // physical chunk byte offset is applied through `c` below for conv rows
-    // adapter rows (LORA): waves 0 and 1 each bring 8 of the 16 rows of every K tile
-    const __amdgpu_buffer_rsrc_t rl = make_rsrc(LORA ? g.lora_a : (const void*)wp, LORA ? (unsigned)((long long)g.lora_R * g.K * 2) : 0u);
-    unsigned lvo = BL_OOB;
-    if (LORA && (wave < 2 || NSTAGE > 2)) {  // ring variants: waves 2, 3 re-issue the two pieces (same bytes, same LDS addresses) so
-                                             // that every wave's vmcnt sees the same number of DMA instructions per stage
-        const int row = (wave & 1) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ (row & 7);
-        if (row < g.lora_R) lvo = (unsigned)(((size_t)row * g.K + c * 8) * 2);
-        // ring variants: no out-of-range lanes (a FULLY out-of-range piece - rows 8..15 at R <= 8 - would retire out of order and
-        // break the counted wait); the rows >= R then carry a copy of row R - 1, whose z columns only ever meet zero B entries
-        else if (NSTAGE > 2) lvo = (unsigned)(((size_t)(g.lora_R - 1) * g.K + c * 8) * 2);
-    }
-
-    const int nkt = g.K / BK;
-    const int per = (nkt + g.splitk - 1) / g.splitk;
-    const int kt_beg = split * per;
-    const int kt_end = min(nkt, kt_beg + per);
-    const int Ct = g.c0 + g.c1;
-    const int Hc = g.Hin << g.ups, Wc = g.Win << g.ups;
+    const long long a_rows = conv ? (long long)g.B * g.Hin * g.Win : (long long)h.rows;  // (the tail sources' descriptors)
+    const int Ct = (int)h.Ct;
+    const int ups = (h.flags & GH_UPS) ? g.ups : 0;  // (the gather's own fields - Hin, Win, stride, pad, kw, ups - stay in GemmArgs: conv launches only)
+    const bool zstuff = (h.flags & GH_ZSTUFF) != 0;
     // conv walk state (uniform): current tap and channel position; seg_key identifies (tap, source)
     int tap = 0, cc = 0, seg_key = -1;
-    const int ntaps = g.kw * g.kw;  // tap == ntaps: the 1x1 tail segment (only a launch with g.cs0 has K steps there)
-    if (g.conv) {
+    int Hc = 0, Wc = 0, ntaps = 0;  // tap == ntaps: the 1x1 tail segment (only a launch with g.cs0 has K steps there)
+    if (conv) {
+        Hc = g.Hin << ups;
+        Wc = g.Win << ups;
+        ntaps = g.kw * g.kw;
         const int k0 = kt_beg * BK;
         tap = min(k0 / Ct, ntaps);
         cc = k0 - tap * Ct;
@@ -846,29 +882,22 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
     // time in the VMEM queue overlaps MFMAs already issued) costs this kernel 2.3 % of the whole step (10.10 -> 10.33 ms, same box,
     // profiles/r03z_bl_ab.log): with two workgroups per CU the other workgroup already fills the stall, and the later issue shortens the
     // time the tile has to land.  Off.
-    auto stage_w = [&](int kt, int buf) {
-        char* sb = smem + buf * STAGE;
-        const unsigned k0b = (unsigned)kt * BK * 2;
-#pragma unroll
-        for (int it = 0; it < W_IT; ++it) bl16(rw, sb + BM * 128 + (it * 256 + wave * 64) * 16, wvo[it], k0b);
-        if (LORA && (wave < 2 || NSTAGE > 2)) bl16(rl, sb + (BM + BN) * 128 + (wave & 1) * 64 * 16, lvo, k0b);
-    };
     auto stage_a = [&](int kt, int buf) {
         char* sb = smem + buf * STAGE;
         const unsigned k0b = (unsigned)kt * BK * 2;
-        if (!g.conv) {
-            const bool second = kt * BK >= g.c0;
+        if (!conv) {
+            const bool second = kt * BK >= (int)h.c0;
             if (!second) {
 #pragma unroll
                 for (int it = 0; it < A_IT; ++it) bl16(ra0, sb + (it * 256 + wave * 64) * 16, avo[it], k0b);
             } else {
-                const unsigned kb = (unsigned)(kt * BK - g.c0) * 2;
+                const unsigned kb = (unsigned)(kt * BK - (int)h.c0) * 2;
 #pragma unroll
                 for (int it = 0; it < A_IT; ++it) bl16(ra1, sb + (it * 256 + wave * 64) * 16, avo1[it], kb);
             }
         } else {
             const bool tail = tap >= ntaps;  // (uniform) past the last tap: the 1x1 tail, its pixel is the window's centre (oy, ox)
-            const int cfirst = tail ? +g.cs0 : +g.c0;
+            const int cfirst = tail ? +g.cs0 : (int)h.c0;
             const bool second = cc >= cfirst;
             const int key = tap * 2 + (second ? 1 : 0);
             if (key != seg_key) {  // new (tap, source) segment: refresh the per-lane offsets (uniform branch)
@@ -881,8 +910,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
                     const int row = it * 32 + lrow;
                     const int c = pch ^ (row & 7);
                     const int iy = ay[it] + ky, ix = ax[it] + kx;
-                    const bool ok = ab[it] >= 0 && iy >= 0 && iy < Hc && ix >= 0 && ix < Wc && (!g.zstuff || ((iy | ix) & 1) == 0);
-                    const unsigned pix = (unsigned)((ab[it] + (iy >> g.ups)) * g.Win + (ix >> g.ups));
+                    const bool ok = ab[it] >= 0 && iy >= 0 && iy < Hc && ix >= 0 && ix < Wc && (!zstuff || ((iy | ix) & 1) == 0);
+                    const unsigned pix = (unsigned)((ab[it] + (iy >> ups)) * g.Win + (ix >> ups));
                     avo[it] = ok ? (pix * (unsigned)ld + (unsigned)c * 8u) * 2u : BL_OOB;
                 }
             }
@@ -907,6 +936,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
     };
     auto stage = [&](int kt, int buf) { stage_w(kt, buf); stage_a(kt, buf); };
     (void)acb;
+    if (kt_beg < kt_end) stage_a(kt_beg, 0);
+    stamp(1);  // head finished, stage 0 all issued; what follows - adapter slab, accumulators, fragment offsets - runs under its flight
 
     f32x4 acc[NF][MF];
 #pragma unroll
@@ -964,13 +995,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
         }
     };
 
-    stamp(1);
-
     if constexpr (NSTAGE == 2) {
         if (kt_beg < kt_end) {
-            if (g.pretouch) pretouch_weights(rw, (long long)g.N * g.K * 2, smem + STAGE, wave, lane, g.pretouch);
-            stage(kt_beg, 0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (stage 0 and the pre-touch pieces left in the head; the adapter slab loads too)
             __syncthreads();
             stamp(2);
             int cur = 0;
@@ -994,7 +1021,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
         constexpr int PER = A_IT + W_IT + (LORA ? 1 : 0);  // DMA instructions per lane and stage (uniform over the waves)
         static_assert(PER * (NSTAGE - 2) <= 63, "vmcnt range");
 #pragma unroll
-        for (int s = 0; s < NSTAGE - 1; ++s)
+        for (int s = 1; s < NSTAGE - 1; ++s)  // (stage 0 left in the head, whole and on every wave: the counts per stage stay uniform)
             if (kt_beg + s < kt_end) stage(kt_beg + s, s);
         int slot = 0;
         for (int kt = kt_beg; kt < kt_end; ++kt) {
@@ -1187,7 +1214,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bl_kernel(const GemmArgs g) {  //
 // Weights stay double buffered per tap; the K order (ky, kx, cin) of the packed filter bank is unchanged.
 // =================================================================================================
 template <int BM, int BN, int WGM, int WGN>
-__global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
+__global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmHead hd, const GemmArgs g) {
     typedef bf16 T;
     constexpr int BK = 64;
     constexpr int W_IT = BN / 32;
@@ -1202,58 +1229,53 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int split = blockIdx.y;
+    // the launch head, read once (see gemm_bl_kernel)
+    GemmHead h = hd;
+    asm volatile("" : "+s"(h.w), "+s"(h.a0), "+s"(h.a1), "+s"(h.ext_w), "+s"(h.ext_a0), "+s"(h.ext_a1), "+s"(h.flags), "+s"(h.rows), "+s"(h.N),
+                 "+s"(h.wpitch), "+s"(h.lda0), "+s"(h.lda1), "+s"(h.c0));
+    asm volatile("" : "+s"(h.ntn), "+s"(h.ntm), "+s"(h.group_m), "+s"(h.mul_pg), "+s"(h.mul_gm), "+s"(h.mul_last), "+s"(h.shifts), "+s"(h.per),
+                 "+s"(h.Ct), "+s"(h.pt_per_wg), "+s"(h.pt_per_wave), "+s"(h.mul_hw), "+s"(h.mul_wd));
+    asm volatile("" : "+s"(h.mul_pw), "+s"(h.geom), "+s"(h.per_sc));
     auto stamp = [&](int k, bool drain = false) {  // probe, as in gemm_bl_kernel (the same eight points)
-        unsigned long long* const stp = gemm_stamp_word(g, k, k == 0);
-        if (stp && tid == 0) {
-            if (drain) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            *stp = __builtin_readcyclecounter();
+        if (k <= 1 ? (h.flags & GH_STAMPED) != 0 : g.stamps != nullptr) {
+            unsigned long long* const stp = gemm_stamp_word(g, k, k == 0);
+            if (stp && tid == 0) {
+                if (drain) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                *stp = __builtin_readcyclecounter();
+            }
         }
     };
     stamp(0);
-    if (g.dbg & 2048) lds_poison(smem, (int)blockDim.x);
-    const int Wd = g.Win, Hd = g.Hin;
-    const int TH = BM / Wd, PW = Wd + 2;
+    if (h.flags & 2048u) lds_poison(smem, (int)blockDim.x);
+    const int Wd = (int)(h.geom & 255u), Hd = (int)h.rows;
+    const int TH = (int)(h.geom >> 8 & 255u), PW = (int)(h.geom >> 16 & 255u);
     const int npix = (TH + 2) * PW;
-    const int pit = (npix * 8 + 255) / 256;
+    const int pit = (int)(h.geom >> 24);
     char* patch = smem;
     char* wbase = smem + pit * 4096;  // whole DMA rounds: lanes past the last patch pixel still write (zeros)
 
-    const int ntn = (g.N + BN - 1) / BN;
-    const int ntm = g.M / BM;
-    const int nblk = ntn * ntm;
-    int logical;
-    {
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7, q = nblk >> 3, r = nblk & 7;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    // grouped order: within a group of `group_m` M tiles walk M first, so the workgroups that run together on an XCD share
-    // their weight tiles (group_m ways) as well as their activation tiles through that XCD's L2 (N-first order re-streamed
-    // the whole weight matrix once per M tile: 3-6x the algorithmic bytes on the wide-N and deep-K layers)
-    int tn, tm;
-    {
-        const int GM = g.group_m > 1 ? g.group_m : 1;
-        const int per_group = GM * ntn;
-        const int grp = logical / per_group;
-        const int first_m = grp * GM;
-        const int gsz = min(GM, ntm - first_m);
-        const int within = logical - grp * per_group;
-        tm = first_m + within % gsz;
-        tn = within / gsz;
-    }
+    // tile coordinates: as in gemm_bl_kernel (the XCD remap, then the grouped order)
+    uint32_t tm_u, tn_u;
+    gh_tile_coords(h, blockIdx.x, tm_u, tn_u);
+    const int tm = (int)tm_u, tn = (int)tn_u;
     const int m0 = tm * BM, n0 = tn * BN;
-    const int img = m0 / (Hd * Wd);
-    const int y0 = (m0 - img * Hd * Wd) / Wd;  // first output row of the tile inside its image
+    const int Ct = (int)h.Ct;
+    const int nch = Ct / BK;                       // 64-channel chunks over both sources
+    int ch_beg, ch_end;
+    gh_split_range(h.per, (uint32_t)nch, (uint32_t)split, ch_beg, ch_end);
+    // 1x1 tail (g.cs0 > 0): its 64-channel chunks are dealt to the splits the same way; a split runs them after its 3x3 chunks
+    int sc_beg = 0, sc_end = 0;
+    if (h.flags & GH_TAIL) {
+        const int nsc = (int)(h.wpitch >> 7) - 9 * nch;  // K = 9 Ct + cs0 + cs1
+        sc_beg = min(nsc, split * (int)h.per_sc);
+        sc_end = min(nsc, sc_beg + (int)h.per_sc);
+    }
 
-    const T* a0p = reinterpret_cast<const T*>(g.a0);
-    const T* a1p = reinterpret_cast<const T*>(g.a1);
-    const T* wp = reinterpret_cast<const T*>(g.w);
-    const long long a_rows = (long long)g.B * Hd * Wd;
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(wp, (unsigned)min((long long)g.N * g.K * 2, 0x7FFFFFFFll));
-    const __amdgpu_buffer_rsrc_t ra0 = make_rsrc(a0p, (unsigned)min(a_rows * g.lda0 * 2, 0x7FFFFFFFll));
-    const __amdgpu_buffer_rsrc_t ra1 = make_rsrc(a1p ? (const void*)a1p : (const void*)a0p,
-                                                 a1p ? (unsigned)min(a_rows * g.lda1 * 2, 0x7FFFFFFFll) : 0u);
-
+    // ---- the weight side first (as in gemm_bl_kernel): pre-touch and the first weight tile leave before any patch address exists ----
+    const T* a0p = reinterpret_cast<const T*>(h.a0);
+    const T* a1p = reinterpret_cast<const T*>(h.a1);
+    const T* wp = reinterpret_cast<const T*>(h.w);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(wp, h.ext_w);
     // weight rows: as in the plain kernel
     const int lrow = tid >> 3, pch = tid & 7;
     unsigned wvo[W_IT];
@@ -1262,46 +1284,8 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
         const int row = it * 32 + lrow;
         const int n = n0 + row;
         const int c = pch ^ (row & 7);
-        wvo[it] = n < g.N ? (unsigned)(((size_t)n * g.K + c * 8) * 2) : BL_OOB;
+        wvo[it] = (unsigned)n < h.N ? (unsigned)n * h.wpitch + (unsigned)c * 16u : BL_OOB;
     }
-    // patch transfers: transfer t = it*256 + tid carries chunk (t & 7) of patch pixel (t >> 3)
-    unsigned pvo0[PIT_MAX], pvo1[PIT_MAX];
-#pragma unroll
-    for (int it = 0; it < PIT_MAX; ++it) {
-        const int t = it * 256 + tid;
-        const int pp = t >> 3;
-        const int c = (t & 7) ^ (pp & 7);
-        const int hy = pp / PW, hx = pp - hy * PW;
-        const int iy = y0 - 1 + hy, ix = hx - 1;
-        const bool ok = pp < npix && iy >= 0 && iy < Hd && ix >= 0 && ix < Wd;
-        const unsigned pix = (unsigned)((img * Hd + iy) * Wd + ix);
-        pvo0[it] = ok ? (pix * (unsigned)g.lda0 + (unsigned)c * 8u) * 2u : BL_OOB;
-        pvo1[it] = ok ? (pix * (unsigned)g.lda1 + (unsigned)c * 8u) * 2u : BL_OOB;
-    }
-
-    const int Ct = g.c0 + g.c1;
-    const int nch = Ct / BK;                       // 64-channel chunks over both sources
-    const int per = (nch + g.splitk - 1) / g.splitk;
-    const int ch_beg = split * per, ch_end = min(nch, ch_beg + per);
-    // 1x1 tail (g.cs0 > 0): its 64-channel chunks are dealt to the splits the same way; a split runs them after its 3x3 chunks
-    const int nsc = (g.cs0 + g.cs1) / BK;
-    const int per_sc = (nsc + g.splitk - 1) / g.splitk;
-    const int sc_beg = min(nsc, split * per_sc), sc_end = min(nsc, sc_beg + per_sc);
-    const __amdgpu_buffer_rsrc_t rs0 = make_rsrc(g.s0 ? g.s0 : (const void*)a0p, g.s0 ? (unsigned)min(a_rows * g.lds0 * 2, 0x7FFFFFFFll) : 0u);
-    const __amdgpu_buffer_rsrc_t rs1 = make_rsrc(g.s1 ? g.s1 : (const void*)a0p, g.s1 ? (unsigned)min(a_rows * g.lds1 * 2, 0x7FFFFFFFll) : 0u);
-
-    auto stage_patch = [&](int ch) {
-        const int cc = ch * BK;
-        const bool second = cc >= g.c0;
-        const unsigned chb = (unsigned)(second ? cc - g.c0 : cc) * 2;
-#pragma unroll
-        for (int it = 0; it < PIT_MAX; ++it) {
-            if (it < pit) {
-                if (!second) bl16(ra0, patch + (it * 256 + wave * 64) * 16, pvo0[it], chb);
-                else bl16(ra1, patch + (it * 256 + wave * 64) * 16, pvo1[it], chb);
-            }
-        }
-    };
     auto stage_w = [&](int ch, int tap, int buf) {
         char* sb = wbase + buf * WSTAGE;
         const unsigned kb = (unsigned)(tap * Ct + ch * BK) * 2;
@@ -1316,6 +1300,56 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
 #pragma unroll
         for (int it = 0; it < W_IT; ++it) bl16(rw, sb + (it * 256 + wave * 64) * 16, wvo[it], kb);
     };
+    const bool any_work = ch_beg < ch_end || sc_beg < sc_end;
+    if (any_work) {
+        if (h.pt_per_wave) pretouch_weights_head(rw, h, wbase + WSTAGE, wave, lane);
+        if (ch_beg < ch_end) stage_w(ch_beg, 0, 0);
+        else stage_w_sc(sc_beg, 0);
+    }
+
+    // ---- the patch: this tile's image and first row, the offsets of its transfers, the first chunk's DMA ----
+    const int hw = Hd * Wd;
+    const int img = (int)magic_div((uint32_t)m0, h.mul_hw, gh_shift(h, GH_SH_HW));
+    const int y0 = (int)gh_div_wd(h, (uint32_t)(m0 - img * hw));  // first output row of the tile inside its image
+    const __amdgpu_buffer_rsrc_t ra0 = make_rsrc(a0p, h.ext_a0);
+    const __amdgpu_buffer_rsrc_t ra1 = make_rsrc(a1p ? (const void*)a1p : (const void*)a0p, h.ext_a1);
+    // patch transfers: transfer t = it*256 + tid carries chunk (t & 7) of patch pixel (t >> 3)
+    unsigned pvo0[PIT_MAX], pvo1[PIT_MAX];
+#pragma unroll
+    for (int it = 0; it < PIT_MAX; ++it) {
+        const int t = it * 256 + tid;
+        const int pp = t >> 3;
+        const int c = (t & 7) ^ (pp & 7);
+        const int hy = (int)gh_div_pw(h, (uint32_t)pp), hx = pp - hy * PW;
+        const int iy = y0 - 1 + hy, ix = hx - 1;
+        const bool ok = pp < npix && iy >= 0 && iy < Hd && ix >= 0 && ix < Wd;
+        const unsigned pix = (unsigned)((img * Hd + iy) * Wd + ix);
+        pvo0[it] = ok ? (pix * h.lda0 + (unsigned)c * 8u) * 2u : BL_OOB;
+        pvo1[it] = ok ? (pix * h.lda1 + (unsigned)c * 8u) * 2u : BL_OOB;
+    }
+
+    auto stage_patch = [&](int ch) {
+        const int cc = ch * BK;
+        const bool second = cc >= (int)h.c0;
+        const unsigned chb = (unsigned)(second ? cc - (int)h.c0 : cc) * 2;
+#pragma unroll
+        for (int it = 0; it < PIT_MAX; ++it) {
+            if (it < pit) {
+                if (!second) bl16(ra0, patch + (it * 256 + wave * 64) * 16, pvo0[it], chb);
+                else bl16(ra1, patch + (it * 256 + wave * 64) * 16, pvo1[it], chb);
+            }
+        }
+    };
+    if (ch_beg < ch_end) stage_patch(ch_beg);
+    stamp(1);  // head finished, stage 0 (pre-touch, first weight tile, first patch) all issued
+
+    // the tail sources' descriptors (their fields stay in GemmArgs: launches with a tail only, and not before the first DMA)
+    const bool has_tail = (h.flags & GH_TAIL) != 0;
+    const long long a_rows = has_tail ? (long long)g.B * Hd * Wd : 0ll;
+    const void* const s0p = has_tail ? g.s0 : nullptr;
+    const void* const s1p = has_tail ? g.s1 : nullptr;
+    const __amdgpu_buffer_rsrc_t rs0 = make_rsrc(s0p ? s0p : (const void*)a0p, s0p ? (unsigned)min(a_rows * g.lds0 * 2, 0x7FFFFFFFll) : 0u);
+    const __amdgpu_buffer_rsrc_t rs1 = make_rsrc(s1p ? s1p : (const void*)a0p, s1p ? (unsigned)min(a_rows * g.lds1 * 2, 0x7FFFFFFFll) : 0u);
     unsigned spix[PIT_MAX];  // source pixel of each transfer (centre rows of the patch), ~0u outside: set up after the 3x3 phases (sc_setup)
     auto sc_setup = [&]() {
 #pragma unroll
@@ -1323,7 +1357,7 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
             int t = it * 256 + tid;
             asm volatile("" : "+v"(t));  // (keeps this arithmetic out of the 3x3 phases: merged with the pvo0 / pvo1 set-up it would hold registers across them)
             const int pp = t >> 3;
-            const int hy = pp / PW, hx = pp - hy * PW;
+            const int hy = (int)gh_div_pw(h, (uint32_t)pp), hx = pp - hy * PW;
             const bool ok = hy >= 1 && hy <= TH && hx >= 1 && hx <= Wd;  // (rows y0 .. y0 + TH - 1 lie inside the image: whole tiles per image)
             spix[it] = ok ? (unsigned)((img * Hd + y0 - 1 + hy) * Wd + hx - 1) : ~0u;
         }
@@ -1357,7 +1391,7 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
 #pragma unroll
     for (int j = 0; j < MF; ++j) {
         const int p = wm0 + j * 16 + fr;
-        const int ty = p / Wd, tx = p - ty * Wd;
+        const int ty = (int)gh_div_wd(h, (uint32_t)p), tx = p - ty * Wd;
         prow[j] = ty * PW + tx;
     }
 
@@ -1383,15 +1417,10 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs g) {
         }
     };
 
-    stamp(1);
-
-    if (ch_beg < ch_end || sc_beg < sc_end) {
+    if (any_work) {
         int cur = 0;
-        if (g.pretouch) pretouch_weights(rw, (long long)g.N * g.K * 2, wbase + WSTAGE, wave, lane, g.pretouch);
-        if (ch_beg < ch_end) stage_w(ch_beg, 0, 0);
-        else stage_w_sc(sc_beg, 0);
         for (int ch = ch_beg; ch < ch_end; ++ch) {
-            stage_patch(ch);  // the previous chunk's last tap ended with a barrier: the patch buffer is free
+            if (ch != ch_beg) stage_patch(ch);  // the previous chunk's last tap ended with a barrier: the patch buffer is free (the first chunk's left in the head)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             if (ch == ch_beg) stamp(2);
@@ -3058,8 +3087,11 @@ bool gemm_tile_lora_in_kernel(int tile, int r, int R) {
 
 // M tiles per group of the tile order (MRISR_GROUP_M overrides; 1 = the old N-first order).  8 measured best over the whole
 // step (same box, graph replay: 53.9 slices/s vs 53.0 for N-first; a per-grid sqrt(T * BN / BM) model: 53.1 vs 53.6): profiles/r01e_group_m.log
+static int g_group_m = 0;  // test hook: > 0 = this group size for every tiled launch, NOT clamped to the launch's M tiles (a group larger than ntm)
+extern "C" void mrisr_debug_group_m(int gm) { g_group_m = gm; }
 static int auto_group_m(int ntm) {
     static const int env = [] { const char* e = getenv("MRISR_GROUP_M"); return e ? atoi(e) : 8; }();
+    if (g_group_m > 0) return g_group_m;
     return std::max(1, std::min(env, ntm));
 }
 // grid of a tiled launch; sets the tile order the kernel decodes it with
@@ -3108,6 +3140,19 @@ static int launch_cfg(GemmArgs& g, hipStream_t st) {
     return 0;
 }
 
+// the launch head of the tiled and halo kernels (gemm_head.h), filled once per launch from the finished GemmArgs (after tile_grid: group_m)
+static GemmHead gemm_head_for(const GemmArgs& g, int BM, int BN, bool halo) {
+    GemmHeadIn in;
+    in.w = g.w; in.a0 = g.a0; in.a1 = g.a1;
+    in.M = g.M; in.N = g.N; in.K = g.K; in.c0 = g.c0; in.c1 = g.c1; in.lda0 = g.lda0; in.lda1 = g.lda1;
+    in.conv = g.conv; in.B = g.B; in.Hin = g.Hin; in.Win = g.Win; in.Hout = g.Hout; in.Wout = g.Wout;
+    in.ups = g.ups; in.zstuff = g.zstuff; in.subpix = g.subpix;
+    in.cs0 = g.cs0; in.cs1 = g.cs1; in.splitk = g.splitk; in.batch = g.batch; in.group_m = g.group_m;
+    in.pretouch = g.pretouch; in.dbg = g.dbg; in.stamped = g.stamps != nullptr;
+    in.BM = BM; in.BN = BN; in.halo = halo;
+    return make_gemm_head(in);
+}
+
 static int g_force_tile = 0;  // test hook: 0 = the planner, else this tile id for every GEMM
 extern "C" void mrisr_debug_force_tile(int t) { g_force_tile = t; }
 
@@ -3132,8 +3177,9 @@ static int launch_bl(GemmArgs& g, hipStream_t st) {
     static const std::string base = std::string("gemm_bf16_bl") + std::to_string(BM) + "x" + std::to_string(BN) + (NSTAGE > 2 ? "d" + std::to_string(NSTAGE) : std::string());
     ProfScope ps = gemm_scope(g, base, g.conv ? (g.cs0 ? "convsc" : (g.ups ? "convup" : (g.stride == 2 ? "convs2" : "conv"))) : "lin",
                               g.conv ? conv_a_elements(g, true) : (double)g.M * g.K, 2, 2, st);
-    if (g.lora_a) hipLaunchKernelGGL((gemm_bl_kernel<BM, BN, WGM, WGN, NSTAGE, true>), grid, dim3(256), smem_l, st, g);
-    else hipLaunchKernelGGL((gemm_bl_kernel<BM, BN, WGM, WGN, NSTAGE, false>), grid, dim3(256), smem, st, g);
+    const GemmHead hd = gemm_head_for(g, BM, BN, false);
+    if (g.lora_a) hipLaunchKernelGGL((gemm_bl_kernel<BM, BN, WGM, WGN, NSTAGE, true>), grid, dim3(256), smem_l, st, hd, g);
+    else hipLaunchKernelGGL((gemm_bl_kernel<BM, BN, WGM, WGN, NSTAGE, false>), grid, dim3(256), smem, st, hd, g);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -3156,7 +3202,7 @@ static int launch_halo(GemmArgs& g, hipStream_t st) {
     const dim3 grid = tile_grid(g, BM, BN);
     static const std::string base = std::string("gemm_bf16_halo") + std::to_string(BM) + "x" + std::to_string(BN);
     ProfScope ps = gemm_scope(g, base, g.cs0 ? "convsc" : "conv", conv_a_elements(g, true), 2, 2, st);
-    hipLaunchKernelGGL((gemm_halo_kernel<BM, BN, WGM, WGN>), grid, dim3(256), smem, st, g);
+    hipLaunchKernelGGL((gemm_halo_kernel<BM, BN, WGM, WGN>), grid, dim3(256), smem, st, gemm_head_for(g, BM, BN, true), g);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -1,9 +1,11 @@
 """Where the tiled (gemm_bl_kernel) and halo (gemm_halo_kernel) GEMMs spend their time: clock stamps (s_memtime: shader-clock ticks, about 2.1 per ns under load) written by wave 0 of
 every workgroup at eight phase boundaries (mrisr_debug_gemm_stamps), on the bench workload (SD-1.5 + rank-4 LoRA, B = 32, 32 x 32 latents,
 the shipped tile table).  Two eager denoising steps per run: the first warms up, the second is stamped - the launches see their operands as
-cold as a model step leaves them.  Prints the median ticks per phase over all workgroups of all launches of three signatures: for the
-kernels as they were (mrisr_debug_gemm_flags(64): every fragment through the generic epilogue4) and with the plain staged epilogue.
-Usage (GPU box): python tools/probes/bl_stamps.py"""
+cold as a model step leaves them.  Prints the median ticks per phase over all workgroups of all launches of three signatures, with the plain
+staged epilogue (flags 0) and, with --generic, also through the generic epilogue4 (mrisr_debug_gemm_flags(64)).  Stamp 1 is "head finished,
+stage-0 DMA all issued" (before the launch head it was "offsets and descriptors ready", the DMA still to be issued), so the
+figure to compare across builds is entry -> first stage landed (stamp 2 - stamp 0), printed on its own line.
+Usage (GPU box): python tools/probes/bl_stamps.py [--generic]"""
 import ctypes as C
 import os
 import sys
@@ -26,7 +28,7 @@ SIGNATURES = [
     ("bl64x64 M=2048 N=K=1280 +LoRA", 17, 2048, 1280, 1280, LORA),
     ("halo128x160 conv2 level 0 (M=32768 N=320 K=2880) +resid", 41, 32768, 320, 2880, RESID | CONV),
 ]
-PHASES = ["offsets, descriptors", "first stage lands", "K loop", "LoRA z, bias ready", "epilogue into LDS", "residual loaded", "add + stores issued"]
+PHASES = ["head, stage-0 DMA issued", "first stage lands", "K loop", "LoRA z, bias ready", "epilogue into LDS", "residual loaded", "add + stores issued"]
 
 B = 32
 cfg = mrisr.UNetConfig()
@@ -61,7 +63,7 @@ def stamped_step(tile, flags):
 
 for name, tile, M, N, K, bits in SIGNATURES:
     print(f"== {name} (tile {tile})")
-    for label, flags in (("generic epilogue, as before (flag 64)", 64), ("plain staged epilogue (flags 0)", 0)):
+    for label, flags in ((("generic epilogue (flag 64)", 64),) if "--generic" in sys.argv[1:] else ()) + (("plain staged epilogue (flags 0)", 0),):
         s = stamped_step(tile, flags)
         rows = []
         for k in range(SLOTS):
@@ -81,5 +83,6 @@ for name, tile, M, N, K, bits in SIGNATURES:
         med = d.median(0).values
         tot = (st[:, 7] - st[:, 0]).median()
         print(f"  {label}: {len(rows)} launches, {st.shape[0]} workgroups; median ticks per phase, whole workgroup {tot:.0f}")
+        print(f"    {'entry -> first stage landed':24s} median {(st[:, 2] - st[:, 0]).median():7.0f}   mean {(st[:, 2] - st[:, 0]).mean():8.1f}")
         for nm, v, mean in zip(PHASES, med.tolist(), d.mean(0).tolist()):
             print(f"    {nm:24s} median {v:7.0f}   mean {mean:8.1f}")

@@ -256,7 +256,8 @@ int mrisr_sampler_run_guided(mrisr_sampler* s, mrisr_tensor* latents, const mris
  * unperturbed samples are one contiguous range (one attention launch per applied block); with tiles, sample b owns tile rows b T .. b T + T - 1
  * and the perturbed range is [0, B T).  Perturbed rows of ehsK carry the CONDITIONAL context; condK / intrablockK repeat the [B] operands K
  * times.  block_mask: bit i = transformer block i in forward order (mrisr_model_num_transformer_blocks).  g and phi are those of
- * mrisr_sampler_set_guidance (g is ignored by PAG alone).  s is a launch constant: no per-step (adaptive) scale.  Refused before any launch:
+ * mrisr_sampler_set_guidance (g is ignored by PAG alone).  s is a launch constant here; a per-step (adaptive) scale comes from
+ * mrisr_sampler_set_schedule.  Refused before any launch:
  * s < 0 or not finite, s > 0 with an empty mask, a mask bit beyond the last block, a run with an empty mask, a feature cache with
  * interval > 1, a UNet built with fp8_attention, C*h*w of the latents not a multiple of 4.  During the run the UNet handle carries the pag
  * state of samples [0, B T); it is cleared when the call returns, also on an error.  The step graphs are keyed on (K, block_mask, s): a
@@ -285,6 +286,24 @@ int mrisr_sampler_num_captures(const mrisr_sampler* s);
  * forward of a UNet with layers_per_block == 2.  Works with every step kind, classifier-free guidance, perturbed-attention guidance (the
  * perturbed rows are filtered like the others), tiles (per-tile planes), ControlNet residuals, adapter features, LoRA / DoRA and the
  * fp8 modes.  Not with the feature cache and not in a training step. */
+
+/* ---- per-step schedule of the guidance and FreeU strengths --------------------------------------------------------------------------
+ * Off unless mrisr_sampler_set_schedule set a table.  One f32 row of 8 per step of the sampler's schedule, row i for step i (an absolute
+ * index, like the coefficient rows: mrisr_sampler_set_range keeps its meaning):
+ *     { g, s, phi, freeu_s1, freeu_s2, freeu_b1, freeu_b2, 0 }       g = guidance_scale, s = pag_scale, phi = guidance_rescale
+ * The neutral row {1, 0, 0, 1, 1, 1, 1, 0} makes the guided prediction the conditional one and FreeU the identity.  The sampler owns the
+ * device table (reserved once, uploaded on the run's stream before the first step); the fused step kernels read g, s, phi from row
+ * *step and the FreeU launches their two scalars, with ordinary loads behind the load of the step counter.  The values are NOT part of
+ * the graph key: a run whose table has other values replays the stored graph.  Part of the key are the table's address and two flags:
+ * "some row has phi > 0" (the rescale kernel runs for every step; a row with phi == 0 gets the factor exactly 1) and "FreeU reads the
+ * table" (the UNet has FreeU on; its own four values are then not read).  The run kind is still decided by the entry point called -
+ * plain, guided (K = 2), PAG alone (K = 2, the kernel forms g = 1 + s), PAG with CFG (K = 3) - and the scalars of
+ * mrisr_sampler_set_guidance / _set_pag (the block mask apart) are not read while a table is set.  A neutral step costs a guided step.
+ * rows_host NULL / n_rows 0 clears the table.  Refused before any device work, the message naming the field: n_rows != n_steps, a value
+ * that is not finite, s < 0, phi outside [0, 1], a FreeU value < 0.  Refused by the run before any launch: FreeU columns other than 1
+ * while the UNet has FreeU off; rows with s > 0 in a run that is not a PAG run; rows with g != 1 in a run with no unconditional half.
+ * Everything the runs refuse without a table stays refused. */
+int mrisr_sampler_set_schedule(mrisr_sampler* s, const float* rows_host, int n_rows);
 
 /* ---- tiled sampling (MultiDiffusion, Bar-Tal et al. 2023, with the Gaussian weights of Mixture of Diffusers, Jimenez 2023) -------
  * The latent canvas [NB, C, H, W] is cut into overlapping tiles, the forward runs on the tile batch [NB*T, C, t_h, t_w] and the tile
@@ -653,6 +672,10 @@ int mrisr_op_attn_identity(int dtype, const void* vt, void* out, int B, int H, i
  * W < 1 (or H, W > 1024), Ch % 16 != 0, Cs % 8 != 0, b or s negative or not finite. */
 int mrisr_op_freeu(int dtype, const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs,
                    float b, float s, void* stream);
+/* the same launch with (b, s) of stage `stage` (0: b1, s1; 1: b2, s2) read by the kernel from row `slot` of a host schedule table of n_rows
+ * rows (mrisr_sampler_set_schedule's layout and value checks; uploaded here) */
+int mrisr_op_freeu_scheduled(int dtype, const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs,
+                             int stage, const float* sched_host, int n_rows, int slot, void* stream);
 /* dst[z][c][r] = src[z][r][c] for r < r_valid, 0 for r_valid <= r < R (T; pitches ld_src >= C, ld_dst >= R; batch strides in elements) */
 int mrisr_op_transpose(int dtype, const void* src, void* dst, int R, int C, int ld_src, int ld_dst, int64_t bs_src, int64_t bs_dst,
                        int batch, int r_valid, void* stream);
@@ -704,6 +727,16 @@ int mrisr_op_pag_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x3, const mr
 int mrisr_op_pag_multistep_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x3, const mrisr_tensor* eps3, const mrisr_tensor* lr,
                                 mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot, float guidance_scale,
                                 float pag_scale, float guidance_rescale, void* stream);
+
+/* the guided step with g, s, phi read from a schedule table (mrisr_sampler_set_schedule) alone: K = 2 with pag_alone == 0 is
+ * mrisr_op_guided_step's step on [eps_u; eps_c], K = 2 with pag_alone != 0 the step on [eps_p; eps_c] with g = 1 + s of the row, K = 3
+ * mrisr_op_pag_step's, for every step kind.  The kernel sees the step counter `slot` and reads row `slot` of sched_host (n_rows rows of 8
+ * floats, uploaded here); the rescale kernel runs iff some row has phi > 0.  row_host: the kind's coefficient row (2 / 4 / 5 floats, or 16
+ * for the multistep kinds, which take hist / xc / solver_order as mrisr_op_multistep_step does and NULL otherwise).  noise: NULL or
+ * slot + 1 slabs [B,C,h,w] - the step reads slab `slot`.  xK / epsK: [K B,C,h,w]. */
+int mrisr_op_scheduled_step(int step_kind, int K, int pag_alone, mrisr_tensor* x, mrisr_tensor* xK, const mrisr_tensor* epsK, const mrisr_tensor* lr,
+                            const mrisr_tensor* noise, mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot,
+                            float clip, const float* sched_host, int n_rows, void* stream);
 
 /* the fused multistep step (MRISR_STEP_UNIPC / MRISR_STEP_DPMSOLVERPP) alone: x [B,C,h,w] f32 (in place), eps [B,C,h,w], lr or NULL,
  * hist [solver_order][B,C,h,w] f32 (x0 predictions; slot `slot` % solver_order is written, the prediction k steps back is read from

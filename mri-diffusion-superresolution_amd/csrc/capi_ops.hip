@@ -1051,6 +1051,28 @@ int mrisr_op_freeu(int dtype, const void* hidden, const void* skip, void* hidden
     API_END
 }
 
+// one FreeU stage with (b, s) of up block `stage` read by the kernel from row `slot` of a host schedule table (uploaded here)
+int mrisr_op_freeu_scheduled(int dtype, const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs,
+                             int stage, const float* sched_host, int n_rows, int slot, void* stream) {
+    API_BEGIN
+    TRY(bwd_dtype_ok(dtype));
+    hipStream_t st = (hipStream_t)stream;
+    MRISR_REQUIRE(stage == 0 || stage == 1, "freeu: stage 0 (s1, b1) or 1 (s2, b2)");
+    MRISR_REQUIRE(sched_host && n_rows >= 1 && n_rows <= 65536, "freeu: a schedule table of 1 .. 65536 rows");
+    MRISR_REQUIRE(slot >= 0 && slot < n_rows, "freeu: slot outside the schedule table");
+    TRY(check_schedule_rows(sched_host, n_rows));
+    DevBuf d_sched, d_step;
+    TRY(d_sched.reserve(sizeof(float) * 8 * (size_t)n_rows, false));
+    TRY(d_step.reserve(16, true));
+    MRISR_CHECK_HIP(hipMemcpyAsync(d_sched.p, sched_host, sizeof(float) * 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
+    MRISR_CHECK_HIP(hipMemcpyAsync(d_step.p, &slot, sizeof(int), hipMemcpyHostToDevice, st));
+    TRY(BWD_DISPATCH(dtype, launch_freeu_sched, hidden, skip, hidden_out, skip_out, B, H, W, Ch, Cs, static_cast<const float*>(d_sched.p),
+                     static_cast<const int*>(d_step.p), 5 + stage, 3 + stage, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
 int mrisr_op_softmax_bwd(int dtype, const void* p, const float* dp, void* ds, int ld, int64_t rows, int nk, float scale, void* stream) {
     API_BEGIN
     TRY(bwd_dtype_ok(dtype));

@@ -316,6 +316,10 @@ int launch_attn_identity(const void* vt, void* out, int B, int H, int N, int hd,
 template <typename T>
 int launch_freeu(const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs, float b, float s,
                  hipStream_t st);
+// the same launch with b and s read in the kernel from row *step of a schedule table [n][8] (device): columns col_b and col_s (3..6)
+template <typename T>
+int launch_freeu_sched(const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs,
+                       const float* sched, const int* step, int col_b, int col_s, hipStream_t st);
 template <typename T>
 int launch_softmax_bwd(const void* p, const float* dp, void* ds, int ld, long long rows, int nk, float scale, hipStream_t st);
 template <typename T>
@@ -530,9 +534,16 @@ int launch_advance_step(int* step_idx, hipStream_t st);
 //   (multiple of 4).  K = 2, classifier-free guidance: [uncond rows; cond rows], e = eps_u + g (eps_c - eps_u); s is not read.  K = 3,
 //   perturbed-attention guidance with it: [perturbed rows; uncond rows; cond rows], e = eps_u + g (eps_c - eps_u) + s (eps_c - eps_p).
 //   (PAG alone is K = 2 on [eps_p; eps_c] with g = 1 + s.)
+//   sched (device, [n][8], or nullptr): the kernel reads {g, s, phi} from sched[8 * *step_idx + 0..2] instead of the three arguments
+//   (DESIGN.md section 29); pag_alone: K = 2 on [eps_p; eps_c], the kernel forms g = 1 + s of the row; sched_phi: some row has phi > 0 -
+//   the rescale kernel is launched (a row with phi == 0 gives the factor exactly 1 there).  The rows were checked by whoever built the table.
 int launch_guided_step(int K, int kind, float* x, float* xK, const float* epsK, const float* lr, const float* noise, const float* coef_table,
                        const int* step_idx, float clip, float g, float s, float phi, int B, long long per, hipStream_t st,
-                       float* hist = nullptr, float* xc = nullptr, int order = 0);
+                       float* hist = nullptr, float* xc = nullptr, int order = 0, const float* sched = nullptr, int sched_phi = 0,
+                       int pag_alone = 0);
+//   the checks of a host schedule table [n_rows][8] = {g, s, phi, freeu s1, s2, b1, b2, 0}, before any device work: every value finite,
+//   s >= 0, phi in [0, 1], the FreeU values >= 0.  0, or an error code with the message naming the row and the field
+int check_schedule_rows(const float* rows, int n_rows);
 //   multistep step (MRISR_STEP_UNIPC / MRISR_STEP_DPMSOLVERPP): rows of 16 floats (sampler.hip), hist = `order` slabs of n floats (the x0
 //   predictions, slot step % order), xc = the previous corrected state (UniPC) or nullptr; lr (or nullptr) anchors the state: the solver
 //   runs on x - lr.  n must be a multiple of 4.  The guided form is launch_guided_step with the same three buffers.

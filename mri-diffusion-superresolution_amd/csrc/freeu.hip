@@ -19,6 +19,10 @@
 // between the passes orders all reads of pass 1 before any write, so skip_out may be skip.  The twiddles come from sincospif, once per
 // workgroup, and live in LDS.  The workgroups after the skip's scale the backbone half in 16-byte pieces, one element read and written
 // by one lane (hidden_out may be hidden).
+//
+// The two scalars come by value, or - a run with a per-step schedule - from row *step of the sampler's schedule table
+// [n_steps][8]: columns col_b and col_s, read with ordinary loads by every thread (one cache line, uniform over the launch).  The row
+// (b, s) = (1, 1) changes no bit: v * 1 is exact and (s - 1) / (H W) is 0, so the correction term is 0 * t.
 #include <algorithm>
 #include <cmath>
 
@@ -35,10 +39,16 @@ constexpr int FU_MAX_HW = 1024;           // largest H and W (the twiddle tables
 
 template <typename T>
 __global__ __launch_bounds__(FU_THREADS) void freeu_kernel(const T* hid, const T* skip, T* hid_out, T* skip_out, int H, int W, int Ch, int Cs, float bscale, float s,
-                                                           int skip_blocks, int cs_chunks, int hid_blocks, long long hid_vecs, int hid_cw) {
+                                                           int skip_blocks, int cs_chunks, int hid_blocks, long long hid_vecs, int hid_cw,
+                                                           const float* sched, const int* step, int col_b, int col_s) {
     constexpr int VE = 16 / (int)sizeof(T);
     union Vec { uint4 q; T e[VE]; };
     extern __shared__ float fu_lds[];
+    if (sched) {
+        const float* row = sched + 8 * (size_t)*step;
+        bscale = row[col_b];
+        s = row[col_s];
+    }
     if ((int)blockIdx.x >= skip_blocks) {
         // ---- backbone: hid_cw channels of every pixel row (Ch / 2 in place, Ch out of place), the first Ch / 2 scaled
         const int vpr = hid_cw / VE, half = Ch / 2;
@@ -128,9 +138,10 @@ __global__ __launch_bounds__(FU_THREADS) void freeu_kernel(const T* hid, const T
     }
 }
 
+// b, s by value (sched == nullptr) or from the schedule table (sched, step, col_b, col_s)
 template <typename T>
-int launch_freeu(const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs, float b, float s,
-                 hipStream_t st) {
+static int launch_freeu_impl(const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs, float b,
+                             float s, const float* sched, const int* step, int col_b, int col_s, hipStream_t st) {
     constexpr int VE = 16 / (int)sizeof(T);
     MRISR_REQUIRE(hidden && skip && hidden_out && skip_out, "freeu: null operand");
     MRISR_REQUIRE(((reinterpret_cast<uintptr_t>(hidden) | reinterpret_cast<uintptr_t>(skip) | reinterpret_cast<uintptr_t>(hidden_out) |
@@ -139,7 +150,10 @@ int launch_freeu(const void* hidden, const void* skip, void* hidden_out, void* s
     MRISR_REQUIRE(H <= FU_MAX_HW && W <= FU_MAX_HW, "freeu: H and W at most 1024");
     MRISR_REQUIRE(Ch >= 16 && Ch % 16 == 0, "freeu: the hidden channels must be a multiple of 16");
     MRISR_REQUIRE(Cs >= 8 && Cs % 8 == 0, "freeu: the skip channels must be a multiple of 8");
-    MRISR_REQUIRE(std::isfinite(b) && b >= 0.f && std::isfinite(s) && s >= 0.f, "freeu: b and s must be finite and >= 0");
+    if (sched)  // the values were checked when the table was set (mrisr_sampler_set_schedule)
+        MRISR_REQUIRE(step && col_b >= 3 && col_b <= 6 && col_s >= 3 && col_s <= 6, "freeu: schedule table without a step counter, or a column outside 3..6");
+    else
+        MRISR_REQUIRE(std::isfinite(b) && b >= 0.f && std::isfinite(s) && s >= 0.f, "freeu: b and s must be finite and >= 0");
     const int cs_chunks = (Cs / VE + FU_CV - 1) / FU_CV;
     const long long skip_blocks = (long long)B * cs_chunks;
     const int hid_cw = hidden_out == hidden ? Ch / 2 : Ch;
@@ -150,11 +164,24 @@ int launch_freeu(const void* hidden, const void* skip, void* hidden_out, void* s
     ProfScope ps("freeu", 0.0, (double)B * H * W * (3.0 * Cs + 2.0 * hid_cw) * sizeof(T), st);
     hipLaunchKernelGGL(freeu_kernel<T>, dim3((unsigned)(skip_blocks + hid_blocks)), dim3(FU_THREADS), lds, st, static_cast<const T*>(hidden),
                        static_cast<const T*>(skip), static_cast<T*>(hidden_out), static_cast<T*>(skip_out), H, W, Ch, Cs, b, s, (int)skip_blocks,
-                       cs_chunks, (int)hid_blocks, hid_vecs, hid_cw);
+                       cs_chunks, (int)hid_blocks, hid_vecs, hid_cw, sched, step, col_b, col_s);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
+template <typename T>
+int launch_freeu(const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs, float b, float s,
+                 hipStream_t st) {
+    return launch_freeu_impl<T>(hidden, skip, hidden_out, skip_out, B, H, W, Ch, Cs, b, s, nullptr, nullptr, 0, 0, st);
+}
+template <typename T>
+int launch_freeu_sched(const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs,
+                       const float* sched, const int* step, int col_b, int col_s, hipStream_t st) {
+    MRISR_REQUIRE(sched && step, "freeu: null schedule table or step counter");
+    return launch_freeu_impl<T>(hidden, skip, hidden_out, skip_out, B, H, W, Ch, Cs, 1.f, 1.f, sched, step, col_b, col_s, st);
+}
 template int launch_freeu<float>(const void*, const void*, void*, void*, int, int, int, int, int, float, float, hipStream_t);
 template int launch_freeu<bf16>(const void*, const void*, void*, void*, int, int, int, int, int, float, float, hipStream_t);
+template int launch_freeu_sched<float>(const void*, const void*, void*, void*, int, int, int, int, int, const float*, const int*, int, int, hipStream_t);
+template int launch_freeu_sched<bf16>(const void*, const void*, void*, void*, int, int, int, int, int, const float*, const int*, int, int, hipStream_t);
 
 }  // namespace mrisr

@@ -74,9 +74,14 @@ struct PagState {
 
 // FreeU (diffusers' enable_freeu): in every resnet stage of up block k in {0, 1} the first half of the hidden
 // channels is scaled by b[k] and the skip tensor's lowest spatial frequencies by s[k], before the concat.  Part of the workspace key.
+// sched / step: a sampler run with a per-step schedule points them at its table [n_steps][8] and its step counter for
+// the duration of the run; the launches then read (s1, s2, b1, b2) from columns 3..6 of row *step and the key carries a marker instead
+// of the four values.  Null outside such a run.
 struct FreeUState {
     bool on = false;
     float s[2] = {1.f, 1.f}, b[2] = {1.f, 1.f};
+    const float* sched = nullptr;
+    const int* step = nullptr;
 };
 
 struct Model {

@@ -718,9 +718,10 @@ int Model::ensure_workspace(int B, int h, int w, int L, hipStream_t st) {
     // (perturbed-attention guidance: the attention launches of an applied block cover fewer samples - other shapes to plan)
     snprintf(key, sizeof(key), "%d,%d,%d,%d,%d,s%d,p%x:%d:%d", B, h, w, L, keep ? 1 : 0, g_plan_salt, pag.on() ? pag.mask : 0u,
              pag.on() ? pag.first : 0, pag.on() ? pag.count : 0);
-    if (freeu.on) {  // FreeU: six more launches in the decoder, their four scalars taken by value
+    if (freeu.on) {  // FreeU: six more launches in the decoder, their four scalars taken by value - or read from a sampler's schedule table
         const size_t n = strlen(key);
-        snprintf(key + n, sizeof(key) - n, ",f%a:%a:%a:%a", (double)freeu.s[0], (double)freeu.s[1], (double)freeu.b[0], (double)freeu.b[1]);
+        if (freeu.sched) snprintf(key + n, sizeof(key) - n, ",fT");
+        else snprintf(key + n, sizeof(key) - n, ",f%a:%a:%a:%a", (double)freeu.s[0], (double)freeu.s[1], (double)freeu.b[0], (double)freeu.b[1]);
     }
     if (ws_key == key) return 0;
     int rc = cfg.compute_dtype == MRISR_F32 ? plan_t<float>(*this, B, h, w, L, st) : plan_t<bf16>(*this, B, h, w, L, st);

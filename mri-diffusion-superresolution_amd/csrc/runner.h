@@ -700,12 +700,15 @@ struct Runner {
     // the mid block, the hidden tensor nothing but this stage - and the states that would read them later are refused while FreeU is on:
     // the feature cache (its stored input, which a shallow step hands in again as x) and a recorded training forward (its tape).  A skip
     // that carries ControlNet residuals or adapter features is filtered with them, as in diffusers
-    int freeu(const Act& x, const Act& sk, float b, float s) {
+    // A run with a per-step schedule (m.freeu.sched): the kernel reads (b, s) of up block i from row *step of the sampler's table
+    int freeu(const Act& x, const Act& sk, int i) {
         MRISR_REQUIRE(!m.keep, "FreeU: not while a training forward is being recorded");
         MRISR_REQUIRE(x.B == sk.B && x.H == sk.H && x.W == sk.W, "FreeU: hidden and skip geometry differ");
         MRISR_REQUIRE(x.C % 16 == 0 && sk.C % 8 == 0, "FreeU: hidden channels must be a multiple of 16, skip channels of 8");
         if (dry) return 0;
-        return launch_freeu<T>(x.p, sk.p, x.p, sk.p, x.B, x.H, x.W, x.C, sk.C, b, s, st);
+        if (m.freeu.sched)
+            return launch_freeu_sched<T>(x.p, sk.p, x.p, sk.p, x.B, x.H, x.W, x.C, sk.C, m.freeu.sched, m.freeu.step, 5 + i, 3 + i, st);
+        return launch_freeu<T>(x.p, sk.p, x.p, sk.p, x.B, x.H, x.W, x.C, sk.C, m.freeu.b[i], m.freeu.s[i], st);
     }
 
     int unet_forward(const mrisr_tensor& sample, const long long* t_dev, int t_scalar, const mrisr_tensor* ehs,
@@ -761,7 +764,7 @@ struct Runner {
                 }
                 Act sk = skips.back();
                 skips.pop_back();
-                if (m.freeu.on && i < 2) TRY(freeu(x, sk, m.freeu.b[i], m.freeu.s[i]));
+                if (m.freeu.on && i < 2) TRY(freeu(x, sk, i));
                 Act y, xn_next;
                 xn_next.p = nullptr;
                 if (!lv.xf.empty()) TRY(resnet(lv.res[j], x, &sk, &y, &lv.xf[j].norm, 1e-6f, &xn_next));

@@ -101,8 +101,21 @@ int launch_ddpm_step(float* x, const float* eps, const float* noise, const float
 //   e = eps_u + g (eps_c - eps_u) + s (eps_c - eps_p),
 // the same rescale, degenerate-sample guard and update, the new x to all three thirds of the staging buffer.  s == 0 is the K = 2 step.
 // (PAG alone is the K = 2 step on [eps_p; eps_c] with g = 1 + s.)
+// Per-step schedule: with a table `sched` [n_steps][8] the kernels read {g, s, phi} from row *step, columns 0..2,
+// behind the load of *step - ordinary loads, uniform over the launch - and ignore the three launch constants; pag_alone: g := 1 + s of the
+// row.  Whether the rescale kernel runs is still the host's choice (some row has phi > 0); a row with phi == 0 gives the factor
+// 0 * r + 1 == 1 there, and a non-finite r is caught by the degenerate-sample guard.
 // ------------------------------------------------------------------------------------------------
 struct StepRow { float a, b, c, d, sig; };
+// the three guidance scalars of this step: the launch constants, or row s of the schedule table
+__device__ __forceinline__ void load_guidance(const float* sched, int s, int pag_alone, float& g, float& sp, float& phi) {
+    if (!sched) return;
+    const float* q = sched + 8 * (size_t)s;
+    const float qs = q[1];
+    g = pag_alone ? 1.f + qs : q[0];
+    sp = pag_alone ? 0.f : qs;
+    phi = q[2];
+}
 __device__ __forceinline__ StepRow load_step_row(int kind, const float* coef, int s) {
     StepRow r{0.f, 0.f, 0.f, 0.f, 0.f};
     if (kind > MRISR_STEP_DDPM) return r;  // multistep kinds read their own 16-float row (multistep_value4)
@@ -271,8 +284,10 @@ __device__ __forceinline__ float rescale_factor(float qc, float qe, float me, in
 template <int K>
 __global__ __launch_bounds__(256) void guided_step_kernel(int kind, float* x, float* xK, const float* epsK, const float* lr,
                                                           const float* noise_base, const float* coef, const int* step, float clip,
-                                                          float g, float sp, long long n, MsBuf ms) {
+                                                          float g, float sp, long long n, MsBuf ms, const float* sched, int pag_alone) {
     const int s = *step;
+    float phi = 0.f;  // not read here
+    load_guidance(sched, s, pag_alone, g, sp, phi);
     const StepRow r = load_step_row(kind, coef, s);
     const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
     const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
@@ -286,9 +301,11 @@ __global__ __launch_bounds__(256) void guided_step_kernel(int kind, float* x, fl
 template <int K, int ITEMS>
 __global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(int kind, float* x, float* xK, const float* epsK, const float* lr,
                                                                          const float* noise_base, const float* coef, const int* step,
-                                                                         float clip, float g, float sp, float phi, int B, int per, MsBuf ms) {
+                                                                         float clip, float g, float sp, float phi, int B, int per, MsBuf ms,
+                                                                         const float* sched, int pag_alone) {
     __shared__ float red[2 * GS_THREADS / 64];
     const int s = *step;
+    load_guidance(sched, s, pag_alone, g, sp, phi);
     const StepRow r = load_step_row(kind, coef, s);
     const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
     const long long n = (long long)B * per;
@@ -325,9 +342,11 @@ __global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(int kin
 template <int K>
 __global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_reread_kernel(int kind, float* x, float* xK, const float* epsK, const float* lr,
                                                                                 const float* noise_base, const float* coef, const int* step,
-                                                                                float clip, float g, float sp, float phi, int B, int per, MsBuf ms) {
+                                                                                float clip, float g, float sp, float phi, int B, int per, MsBuf ms,
+                                                                                const float* sched, int pag_alone) {
     __shared__ float red[2 * GS_THREADS / 64];
     const int s = *step;
+    load_guidance(sched, s, pag_alone, g, sp, phi);
     const StepRow r = load_step_row(kind, coef, s);
     const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
     const long long n = (long long)B * per;
@@ -349,27 +368,28 @@ __global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_reread_kernel(
 
 template <int K>
 static void launch_guided_kernels(int kind, float* x, float* xK, const float* epsK, const float* lr, const float* noise, const float* coef_table,
-                                  const int* step_idx, float clip, float g, float sp, float phi, int B, long long per, hipStream_t st, MsBuf ms) {
+                                  const int* step_idx, float clip, float g, float sp, float phi, int B, long long per, hipStream_t st, MsBuf ms,
+                                  const float* sched, int sched_phi, int pag_alone) {
     const long long n = (long long)B * per;
-    if (phi == 0.f) {
+    if (sched ? !sched_phi : phi == 0.f) {
         hipLaunchKernelGGL(guided_step_kernel<K>, dim3(nblocks(n >> 2)), dim3(256), 0, st, kind, x, xK, epsK, lr, noise, coef_table, step_idx,
-                           clip, g, sp, n, ms);
+                           clip, g, sp, n, ms, sched, pag_alone);
         return;
     }
 #define MRISR_GS(ITEMS)                                                                                                                   \
     hipLaunchKernelGGL((guided_step_rescale_kernel<K, ITEMS>), dim3(B), dim3(GS_THREADS), 0, st, kind, x, xK, epsK, lr, noise, coef_table, \
-                       step_idx, clip, g, sp, phi, B, (int)per, ms)
+                       step_idx, clip, g, sp, phi, B, (int)per, ms, sched, pag_alone)
     if (per <= 4 * GS_THREADS) MRISR_GS(1);
     else if (per <= 8 * GS_THREADS) MRISR_GS(2);
     else if (per <= 16 * GS_THREADS) MRISR_GS(4);
     else
         hipLaunchKernelGGL(guided_step_rescale_reread_kernel<K>, dim3(B), dim3(GS_THREADS), 0, st, kind, x, xK, epsK, lr, noise, coef_table,
-                           step_idx, clip, g, sp, phi, B, (int)per, ms);
+                           step_idx, clip, g, sp, phi, B, (int)per, ms, sched, pag_alone);
 #undef MRISR_GS
 }
 int launch_guided_step(int K, int kind, float* x, float* xK, const float* epsK, const float* lr, const float* noise, const float* coef_table,
                        const int* step_idx, float clip, float g, float sp, float phi, int B, long long per, hipStream_t st, float* hist,
-                       float* xc, int order) {
+                       float* xc, int order, const float* sched, int sched_phi, int pag_alone) {
     MRISR_REQUIRE(K == 2 || K == 3, "guided step: 2 or 3 parts");
     const std::string who = K == 3 ? "pag step: " : "guided step: ";
     MRISR_REQUIRE(kind >= MRISR_STEP_DDIM && kind <= MRISR_STEP_DPMSOLVERPP, who + "unknown step kind");
@@ -381,8 +401,13 @@ int launch_guided_step(int K, int kind, float* x, float* xK, const float* epsK, 
     }
     MRISR_REQUIRE(x && xK && epsK && coef_table && step_idx && B > 0 && per > 0, who + "null operand");
     MRISR_REQUIRE(per % 4 == 0 && per < (1ll << 31), who + "the per-sample size must be a multiple of 4");
-    MRISR_REQUIRE(phi >= 0.f && phi <= 1.f, who + "guidance_rescale must lie in [0, 1]");
-    if (K == 3) MRISR_REQUIRE(std::isfinite(sp) && sp >= 0.f, who + "pag_scale must be finite and >= 0");
+    if (sched) {  // the three scalars are not read: the rows were checked when the table was built
+        MRISR_REQUIRE(!pag_alone || K == 2, who + "pag alone is the step on 2 parts");
+        MRISR_REQUIRE((reinterpret_cast<uintptr_t>(sched) & 3) == 0, who + "the schedule table must be 4-byte aligned");
+    } else {
+        MRISR_REQUIRE(phi >= 0.f && phi <= 1.f, who + "guidance_rescale must lie in [0, 1]");
+        if (K == 3) MRISR_REQUIRE(std::isfinite(sp) && sp >= 0.f, who + "pag_scale must be finite and >= 0");
+    }
     MRISR_REQUIRE(kind != MRISR_STEP_RESSHIFT || lr, who + "Res-SRDiff needs the LR anchor latents");
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     MRISR_REQUIRE(al16(x) && al16(xK) && al16(epsK) && al16(lr) && al16(noise), who + "operands must be 16-byte aligned");
@@ -391,8 +416,8 @@ int launch_guided_step(int K, int kind, float* x, float* xK, const float* epsK, 
     if (kind == MRISR_STEP_DDIM || multistep) noise = nullptr;
     // epsK K times, x in, K + 1 stores of x; multistep: + `order` history reads, one history write, xc in and out
     ProfScope ps("sampler_step", 0.0, ((K == 3 ? 32.0 : 28.0) + (lr ? 4.0 : 0.0) + (multistep ? 4.0 * order + 4.0 + (ms.xc ? 8.0 : 0.0) : 0.0)) * n, st);
-    if (K == 3) launch_guided_kernels<3>(kind, x, xK, epsK, lr, noise, coef_table, step_idx, clip, g, sp, phi, B, per, st, ms);
-    else launch_guided_kernels<2>(kind, x, xK, epsK, lr, noise, coef_table, step_idx, clip, g, sp, phi, B, per, st, ms);
+    if (K == 3) launch_guided_kernels<3>(kind, x, xK, epsK, lr, noise, coef_table, step_idx, clip, g, sp, phi, B, per, st, ms, sched, sched_phi, 0);
+    else launch_guided_kernels<2>(kind, x, xK, epsK, lr, noise, coef_table, step_idx, clip, g, sp, phi, B, per, st, ms, sched, sched_phi, pag_alone);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -418,6 +443,20 @@ int launch_resshift_forward(const float* hr, const float* lr, const float* noise
     hipLaunchKernelGGL(resshift_forward_kernel, dim3(nblocks((long long)B * per_sample)), dim3(256), 0, st, hr, lr,
                        noise, alphas_cumprod, t, t_is_scalar, out, B, per_sample);
     MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// the checks a schedule table passes before anything touches the device: 0, or the error code with the message set
+int check_schedule_rows(const float* rows, int n_rows) {
+    static const char* const names[8] = {"guidance_scale (g)", "pag_scale (s)", "guidance_rescale (phi)", "freeu_s1", "freeu_s2", "freeu_b1", "freeu_b2", "the padding column"};
+    for (int i = 0; i < n_rows; ++i) {
+        const float* r = rows + 8 * (size_t)i;
+        for (int c = 0; c < 8; ++c)
+            MRISR_REQUIRE(std::isfinite(r[c]), "schedule: row " + std::to_string(i) + ": " + names[c] + " is not finite");
+        MRISR_REQUIRE(r[1] >= 0.f, "schedule: row " + std::to_string(i) + ": pag_scale (s) must be >= 0");
+        MRISR_REQUIRE(r[2] >= 0.f && r[2] <= 1.f, "schedule: row " + std::to_string(i) + ": guidance_rescale (phi) must lie in [0, 1]");
+        for (int c = 3; c < 7; ++c) MRISR_REQUIRE(r[c] >= 0.f, "schedule: row " + std::to_string(i) + ": " + names[c] + " must be >= 0");
+    }
     return 0;
 }
 
@@ -545,6 +584,12 @@ struct mrisr_sampler {
     unsigned pag_mask = 0;  // perturbed-attention guidance of mrisr_sampler_run_pag: the applied transformer blocks and the scale
     float pag_scale = 0.f;
     int n_captures = 0;     // step graphs captured so far (mrisr_sampler_num_captures)
+    // per-step schedule (mrisr_sampler_set_schedule): host rows [n_steps][8] (empty: none - the scalars above rule), the
+    // device table every run with a schedule uploads them to (reserved once, so its address is the same for every such run), and what
+    // the checks and the kernel choice need of the values: some row with phi > 0 / s > 0 / g != 1 / FreeU columns other than 1
+    std::vector<float> sched;
+    DevBuf d_sched;
+    bool sched_phi = false, sched_s = false, sched_g = false, sched_freeu = false;
     std::vector<float> sigma;  // host copy of each step's noise coefficient (which steps read a step_noise slab)
     DevBuf d_ts, d_coef, d_step, d_curt, d_eps;
     // multistep kinds: solver options, the clamped alphas_cumprod on the grid (+ alphas_cumprod[0]), the host rows of the current range,
@@ -761,6 +806,31 @@ int mrisr_sampler_set_pag(mrisr_sampler* s, unsigned block_mask, float pag_scale
 }
 int mrisr_sampler_num_captures(const mrisr_sampler* s) { return s ? s->n_captures : 0; }
 
+int mrisr_sampler_set_schedule(mrisr_sampler* s, const float* rows_host, int n_rows) {
+    API_BEGIN
+    MRISR_REQUIRE(s, "null sampler");
+    if (!rows_host || n_rows == 0) {  // cleared: the launch constants rule again (other plan: the next run captures again)
+        MRISR_REQUIRE(!rows_host && n_rows == 0, "schedule: NULL / 0 clears it; rows need n_rows == n_steps");
+        s->sched.clear();
+        s->sched_phi = s->sched_s = s->sched_g = s->sched_freeu = false;
+        return 0;
+    }
+    MRISR_REQUIRE(n_rows == s->n_steps, "schedule: n_rows must equal the sampler's n_steps (" + std::to_string(s->n_steps) + "), got " + std::to_string(n_rows));
+    if (int rc = check_schedule_rows(rows_host, n_rows)) return rc;
+    TRY(s->d_sched.reserve(sizeof(float) * 8 * (size_t)s->n_steps, false));  // once per sampler: n_rows is always n_steps
+    s->sched.assign(rows_host, rows_host + 8 * (size_t)n_rows);
+    s->sched_phi = s->sched_s = s->sched_g = s->sched_freeu = false;
+    for (int i = 0; i < n_rows; ++i) {
+        const float* r = rows_host + 8 * (size_t)i;
+        s->sched_g |= r[0] != 1.f;
+        s->sched_s |= r[1] > 0.f;
+        s->sched_phi |= r[2] > 0.f;
+        s->sched_freeu |= r[3] != 1.f || r[4] != 1.f || r[5] != 1.f || r[6] != 1.f;
+    }
+    return 0;
+    API_END
+}
+
 }  // extern "C"
 
 // ---- one run: mrisr_sampler_run (K = 1: B rows everywhere), mrisr_sampler_run_guided (K = 2) and mrisr_sampler_run_pag (pag: K = 2 or 3).
@@ -799,6 +869,14 @@ static int run_check(mrisr_sampler* s, const RunArgs& a, StepPlan& p) {
     const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, s->cache_interval, s->tile_h != 0, pag);
     MRISR_REQUIRE(!conflict, conflict);
     Model& U = *s->unet;
+    const bool sched = !s->sched.empty();
+    if (sched) {  // the run kind comes from the entry point; the table only supplies the values, and a value this kind cannot honour is refused
+        MRISR_REQUIRE(U.freeu.on || !s->sched_freeu, "schedule: FreeU columns other than 1 need FreeU on the UNet (mrisr_model_set_freeu)");
+        MRISR_REQUIRE(pag || !s->sched_s, "schedule: rows with pag_scale (s) > 0 need a pag run (mrisr_sampler_run_pag)");
+        MRISR_REQUIRE(K == 3 || (K == 2 && !pag) || !s->sched_g,
+                      "schedule: rows with guidance_scale (g) != 1 need a run with an unconditional half (mrisr_sampler_run_guided, or "
+                      "mrisr_sampler_run_pag with_cfg)");
+    }
     const int B = (int)latents->shape[0], h = (int)latents->shape[2], w = (int)latents->shape[3];
     const int NB = K * B;  // rows of every forward (of the canvas; a tiled run multiplies them by T)
     const long long per = (long long)latents->shape[1] * h * w;
@@ -881,11 +959,21 @@ static int run_check(mrisr_sampler* s, const RunArgs& a, StepPlan& p) {
     p.d_curt = static_cast<long long*>(s->d_curt.p);
     p.d_ts = static_cast<const long long*>(s->d_ts.p);
     if (s->kind == MRISR_STEP_DDPM) p.clip = s->clip;
-    if (guided) { p.guidance_scale = s->guidance_scale; p.guidance_rescale = s->guidance_rescale; }
-    if (pag) { p.pag_mask = s->pag_mask; p.pag_scale = s->pag_scale; }
-    if (U.freeu.on) {  // the four scalars the decoder's FreeU launches take by value (also in the UNet's workspace generation)
-        p.freeu = 1;
-        p.freeu_s[0] = U.freeu.s[0]; p.freeu_s[1] = U.freeu.s[1]; p.freeu_b[0] = U.freeu.b[0]; p.freeu_b[1] = U.freeu.b[1];
+    if (pag) p.pag_mask = s->pag_mask;
+    if (sched && (guided || U.freeu.on)) {
+        // a per-step schedule: the launches take the table's address, never its values - other values, same graph.  What chooses kernels
+        // is here: the rescale kernel (some phi > 0) and FreeU's table mode (the UNet's workspace generation carries a marker for it)
+        p.d_sched = static_cast<const float*>(s->d_sched.p);
+        p.sched_rows = s->n_steps;
+        if (guided) p.sched_phi = s->sched_phi ? 1 : 0;
+        if (U.freeu.on) p.freeu = 2;
+    } else {
+        if (guided) { p.guidance_scale = s->guidance_scale; p.guidance_rescale = s->guidance_rescale; }
+        if (pag) p.pag_scale = s->pag_scale;
+        if (U.freeu.on) {  // the four scalars the decoder's FreeU launches take by value (also in the UNet's workspace generation)
+            p.freeu = 1;
+            p.freeu_s[0] = U.freeu.s[0]; p.freeu_s[1] = U.freeu.s[1]; p.freeu_b[0] = U.freeu.b[0]; p.freeu_b[1] = U.freeu.b[1];
+        }
     }
     if (s->multistep()) {
         p.order = s->ms.order;
@@ -988,6 +1076,12 @@ static int run_buffers(mrisr_sampler* s, StepPlan& p, hipStream_t st) {
         // below, this relies on the runtime staging a pageable host-to-device copy before hipMemcpyAsync returns
         MRISR_CHECK_HIP(hipMemcpyAsync(s->d_coef.p, s->ms_rows.data(), sizeof(float) * s->ms_rows.size(), hipMemcpyHostToDevice, st));
     }
+    if (p.d_sched) {
+        // the schedule's rows, indexed by the absolute step like the coefficient rows; s->sched is pageable and may be replaced
+        // (mrisr_sampler_set_schedule) right after this call returns: staged before hipMemcpyAsync returns, like ms_rows above
+        MRISR_REQUIRE(s->sched.size() == (size_t)8 * s->n_steps && s->d_sched.bytes >= sizeof(float) * s->sched.size(), "schedule table size");
+        MRISR_CHECK_HIP(hipMemcpyAsync(s->d_sched.p, s->sched.data(), sizeof(float) * s->sched.size(), hipMemcpyHostToDevice, st));
+    }
     MRISR_CHECK_HIP(hipMemsetAsync(s->d_step.p, 0, 16, st));
     MRISR_CHECK_HIP(hipMemcpyAsync(s->d_step.p, &s->first, sizeof(int), hipMemcpyHostToDevice, st));
     return 0;
@@ -1049,9 +1143,11 @@ static int step_body(const StepPlan& p, Model& U, Model* C, int cache_mode, hipS
     const bool multistep = p.kind > MRISR_STEP_DDPM;
     if (p.K > 1) {
         // K = 3: [eps_p; eps_u; eps_c].  K = 2 of a pag run: [eps_p; eps_c], the guided step with eps_u := eps_p and g := 1 + s
-        const float g = p.pag && p.K == 2 ? 1.f + p.pag_scale : p.guidance_scale;
+        // with a schedule table the kernel reads the three scalars from row *d_step (and forms 1 + s itself): the plan holds zeros for them
+        const bool pag_alone = p.pag && p.K == 2;
+        const float g = pag_alone ? 1.f + p.pag_scale : p.guidance_scale;
         TRY(launch_guided_step(p.K, p.kind, p.x, p.d_x2, p.d_eps, p.lr, p.noise, p.d_coef, p.d_step, p.clip, g, p.K == 3 ? p.pag_scale : 0.f,
-                               p.guidance_rescale, p.B, per, st, p.hist, p.xc, p.order));
+                               p.guidance_rescale, p.B, per, st, p.hist, p.xc, p.order, p.d_sched, p.sched_phi, pag_alone ? 1 : 0));
     } else if (multistep)
         TRY(launch_multistep_step(p.x, p.d_eps, p.lr, p.d_coef, p.d_step, p.hist, p.xc, p.order, n, st));
     else if (p.kind == MRISR_STEP_DDIM)
@@ -1123,6 +1219,16 @@ static int sampler_run_impl(mrisr_sampler* s, const RunArgs& a, int use_graph, v
         pguard.m = &U;
         U.pag.mask = s->pag_mask; U.pag.first = 0; U.pag.count = p.B * p.T;
     }
+    // FreeU from the schedule table: the UNet's launches read row *d_step for the duration of this run.  Set before the workspace is planned
+    // (its key carries the mode), cleared on every exit path: plain forwards on the handle take their four values by value again
+    struct FreeUGuard {
+        Model* m = nullptr;
+        ~FreeUGuard() { if (m) { m->freeu.sched = nullptr; m->freeu.step = nullptr; } }
+    } fguard;
+    if (p.freeu == 2) {
+        fguard.m = &U;
+        U.freeu.sched = p.d_sched; U.freeu.step = static_cast<const int*>(s->d_step.p);
+    }
     TRY(run_operands(s, a, p, st));
     TRY(run_buffers(s, p, st));
     struct TableGuard {  // the models must not keep pointing at this sampler's table after the run (plain forward calls compute their own)
@@ -1142,10 +1248,11 @@ static int sampler_run_impl(mrisr_sampler* s, const RunArgs& a, int use_graph, v
 
 // ---- the single-step test entries: one static helper behind the four.  K = 1: the plain multistep step; K = 2 / 3: the guided / three-way
 // step on caller buffers xK / epsK [K B].  row_host holds `width` floats (this step kind's row), placed at row `slot` of a zeroed table; the
-// kernel sees the step counter `slot`.  hist / xc: the multistep kinds' ring and corrected state.
+// kernel sees the step counter `slot`.  hist / xc: the multistep kinds' ring and corrected state.  sched_host (K > 1): a schedule table of
+// n_rows rows, uploaded; the kernel reads {g, s, phi} from its row `slot` and g / sp / phi are not read.
 static int op_step(const char* who, int K, int step_kind, mrisr_tensor* x, mrisr_tensor* xK, const mrisr_tensor* epsK, const mrisr_tensor* lr,
                    const mrisr_tensor* noise, const float* row_host, int width, int slot, mrisr_tensor* hist, mrisr_tensor* xc, int solver_order,
-                   float clip, float g, float sp, float phi, void* stream) {
+                   float clip, float g, float sp, float phi, void* stream, const float* sched_host = nullptr, int n_rows = 0, int pag_alone = 0) {
     const std::string w = std::string(who) + ": ", sK = std::to_string(K);
     const std::string eps_name = K == 3 ? "eps3" : (K == 2 ? "eps2" : "eps");
     const bool multistep = hist != nullptr;
@@ -1156,11 +1263,14 @@ static int op_step(const char* who, int K, int step_kind, mrisr_tensor* x, mrisr
     MRISR_REQUIRE(epsK->dtype == MRISR_F32 && numel(epsK) == K * n, w + eps_name + " must be f32 [" + (K > 1 ? sK : "") + "B, C, h, w]");
     if (xK) MRISR_REQUIRE(xK->dtype == MRISR_F32 && numel(xK) == K * n, w + "the staging buffer must be f32 [" + sK + "B, C, h, w]");
     if (lr) MRISR_REQUIRE(lr->dtype == MRISR_F32 && numel(lr) == n, w + "lr must be f32 [B, C, h, w]");
-    if (noise) MRISR_REQUIRE(noise->dtype == MRISR_F32 && numel(noise) == n, w + "noise must be one f32 [B, C, h, w] slab");
+    // (the kernel reads slab `slot` of the noise: the single-slab entries run at slot 0, the scheduled one hands in slot + 1 slabs)
+    if (noise) MRISR_REQUIRE(noise->dtype == MRISR_F32 && numel(noise) == (long long)(slot + 1) * n,
+                             w + (slot ? "noise must be f32 [slot + 1, B, C, h, w]: one slab per step up to this one" : "noise must be one f32 [B, C, h, w] slab"));
     if (multistep) MRISR_REQUIRE(hist->dtype == MRISR_F32 && numel(hist) == (long long)solver_order * n, w + "hist must be f32 [order, B, C, h, w]");
     if (xc) MRISR_REQUIRE(xc->dtype == MRISR_F32 && numel(xc) == n, w + "xc must be f32 [B, C, h, w]");
     hipStream_t st = (hipStream_t)stream;
-    const int pitch = multistep ? 16 : 8;
+    // the table's row pitch of this kind (load_step_row / multistep_value4): at slot 0, where the first-order entries run, any pitch serves
+    const int pitch = multistep ? MS_ROW : (step_kind == MRISR_STEP_DDIM ? 2 : (step_kind == MRISR_STEP_RESSHIFT ? 4 : 8));
     std::vector<float> rows((size_t)(slot + 1) * pitch, 0.f);
     std::copy(row_host, row_host + width, rows.begin() + (size_t)slot * pitch);
     DevBuf d_rows, d_step;
@@ -1169,12 +1279,19 @@ static int op_step(const char* who, int K, int step_kind, mrisr_tensor* x, mrisr
     MRISR_CHECK_HIP(hipMemcpyAsync(d_rows.p, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice, st));
     MRISR_CHECK_HIP(hipMemsetAsync(d_step.p, 0, 16, st));
     MRISR_CHECK_HIP(hipMemcpyAsync(d_step.p, &slot, sizeof(int), hipMemcpyHostToDevice, st));
+    DevBuf d_sched;
+    int sched_phi = 0;
+    if (sched_host) {
+        TRY(d_sched.reserve(sizeof(float) * 8 * (size_t)n_rows, false));
+        MRISR_CHECK_HIP(hipMemcpyAsync(d_sched.p, sched_host, sizeof(float) * 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
+        for (int i = 0; i < n_rows; ++i) sched_phi |= sched_host[8 * (size_t)i + 2] > 0.f ? 1 : 0;
+    }
     float* h = hist ? (float*)hist->data : nullptr;
     float* c = xc ? (float*)xc->data : nullptr;
     if (K > 1)
         TRY(launch_guided_step(K, step_kind, (float*)x->data, (float*)xK->data, (const float*)epsK->data, lr ? (const float*)lr->data : nullptr,
                                noise ? (const float*)noise->data : nullptr, (const float*)d_rows.p, (const int*)d_step.p, clip, g, sp, phi, B, per,
-                               st, h, c, solver_order));
+                               st, h, c, solver_order, (const float*)d_sched.p, sched_phi, pag_alone));
     else
         TRY(launch_multistep_step((float*)x->data, (const float*)epsK->data, lr ? (const float*)lr->data : nullptr, (const float*)d_rows.p,
                                   (const int*)d_step.p, h, c, solver_order, n, st));
@@ -1248,6 +1365,32 @@ int mrisr_op_pag_multistep_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x3
     MRISR_REQUIRE((step_kind == MRISR_STEP_UNIPC) == (xc != nullptr), "pag multistep step: the corrected-state buffer belongs to UniPC");
     return op_step("pag multistep step", 3, step_kind, x, x3, eps3, lr, nullptr, row_host, 16, slot, hist, xc, solver_order, 0.f, guidance_scale,
                    pag_scale, guidance_rescale, stream);
+    API_END
+}
+// the guided step with its three scalars read from a schedule table (parity test): the K = 2 step of classifier-free guidance, the K = 2
+// step of pag alone (pag_alone: g = 1 + s of the row) or the K = 3 step, of any step kind, on caller buffers at step counter `slot`.
+// row_host: this kind's coefficient row (2 / 4 / 5 floats; 16 for the multistep kinds, which also take hist, UniPC xc, and solver_order).
+// sched_host: n_rows rows of 8 floats; the rescale kernel runs iff some row has phi > 0, as in a run
+int mrisr_op_scheduled_step(int step_kind, int K, int pag_alone, mrisr_tensor* x, mrisr_tensor* xK, const mrisr_tensor* epsK, const mrisr_tensor* lr,
+                            const mrisr_tensor* noise, mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot,
+                            float clip, const float* sched_host, int n_rows, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(x && xK && epsK && row_host && sched_host, "scheduled step: null argument");
+    MRISR_REQUIRE(step_kind >= MRISR_STEP_DDIM && step_kind <= MRISR_STEP_DPMSOLVERPP, "scheduled step: unknown step kind");
+    MRISR_REQUIRE(K == 2 || K == 3, "scheduled step: 2 or 3 parts");
+    MRISR_REQUIRE(!pag_alone || K == 2, "scheduled step: pag alone is the step on 2 parts");
+    MRISR_REQUIRE(n_rows >= 1 && n_rows <= 1024 && slot >= 0 && slot < n_rows, "scheduled step: 1..1024 rows, slot inside the table");
+    TRY(check_schedule_rows(sched_host, n_rows));
+    const bool multistep = step_kind > MRISR_STEP_DDPM;
+    if (multistep) {
+        MRISR_REQUIRE(hist && !noise, "scheduled step: the multistep kinds take the history ring and no noise");
+        MRISR_REQUIRE(solver_order >= 1 && solver_order <= 3, "scheduled step: solver order 1..3");
+        MRISR_REQUIRE((step_kind == MRISR_STEP_UNIPC) == (xc != nullptr), "scheduled step: the corrected-state buffer belongs to UniPC");
+    } else
+        MRISR_REQUIRE(!hist && !xc, "scheduled step: hist / xc belong to the multistep kinds");
+    return op_step("scheduled step", K, step_kind, x, xK, epsK, lr, noise, row_host, multistep ? 16 : row_width(step_kind), slot,
+                   multistep ? hist : nullptr, multistep ? xc : nullptr, multistep ? solver_order : 0, clip, 0.f, 0.f, 0.f, stream, sched_host, n_rows,
+                   pag_alone ? 1 : 0);
     API_END
 }
 

@@ -41,6 +41,7 @@ struct StepPlan {
     int* d_step;
     long long* d_curt;
     const long long* d_ts;
+    const float* d_sched;  // per-step schedule table [n_steps][8] = {g, s, phi, freeu s1, s2, b1, b2, 0}, or null: the scalars below rule
     // ---- model state the forwards bake in ----
     unsigned long long ws_gen_unet, ws_gen_cnet;  // workspace generations: persist / arena base addresses
     const float* tproj_unet;                      // per-run time-embedding tables (null: computed per step)
@@ -61,8 +62,11 @@ struct StepPlan {
     int cached, cache_depth;
     int tile_h, tile_w, tile_oh, tile_ow, tile_window;  // the five tile numbers (0: off)
     int tile_ky, tile_kx, tile_vec4;                    // the grid of this canvas; whether the 16-byte path applies
-    int freeu;
+    int freeu;           // 0: off; 1: the four scalars below by value; 2: read from d_sched (the scalars stay zero)
     float freeu_s[2], freeu_b[2];
+    // with d_sched the VALUES of a schedule are not here (guidance_scale, guidance_rescale, pag_scale, freeu_s / freeu_b stay zero): only what
+    // chooses kernels.  sched_phi: some row of the table has phi > 0 - the guided step is the rescale kernel.  sched_rows: the table's rows
+    int sched_phi, sched_rows;
     int first;           // the step the run starts at (the time-embedding table's row 0)
     // ---- policy, not baked in: these live in the uploaded rows; a change captures again because set_solver promises it ----
     int final_zero, lower_order_final;

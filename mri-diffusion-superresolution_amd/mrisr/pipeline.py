@@ -134,6 +134,110 @@ def check_pag(pag_scale, applied_layers, block_names, has_cache=False, fp8_atten
     return mask
 
 
+NEUTRAL_ROW = (1.0, 0.0, 0.0, 1.0, 1.0, 1.0, 1.0, 0.0)  # the guided prediction is the conditional one, FreeU the identity
+SCHEDULE_COLUMNS = ("guidance_scale", "pag_scale", "guidance_rescale", "freeu_s1", "freeu_s2", "freeu_b1", "freeu_b2", "padding")
+FULL_INTERVAL = (0.0, 1.0)
+
+
+def _check_interval(name, interval):
+    try:
+        lo, hi = (float(v) for v in interval)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a (start, end) pair of numbers, got {interval!r}") from None
+    if not (np.isfinite(lo) and np.isfinite(hi)) or not 0.0 <= lo <= hi <= 1.0:
+        raise ValueError(f"{name} must satisfy 0 <= start <= end <= 1, got {interval!r}")
+    return lo, hi
+
+
+def _finite(name, v, lo=None):
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number, got {v!r}") from None
+    if isinstance(v, bool) or not np.isfinite(f):
+        raise ValueError(f"{name} must be finite, got {v!r}")
+    if lo is not None and f < lo:
+        raise ValueError(f"{name} must be >= {lo:g}, got {v!r}")
+    return f
+
+
+def check_schedule(schedule, n_steps) -> np.ndarray:
+    """The rules of an explicit schedule table (``Sampler.run(schedule=)``), on numbers alone (no device is
+    touched): ``[n_steps, 8]`` rows ``{g, s, phi, freeu_s1, freeu_s2, freeu_b1, freeu_b2, 0}``, every value finite, ``s >= 0``,
+    ``0 <= phi <= 1``, the FreeU values ``>= 0``.  Returns it as a contiguous float32 array; raises ``ValueError`` naming the column."""
+    try:
+        a = np.ascontiguousarray(np.asarray(schedule, dtype=np.float32))
+    except (TypeError, ValueError):
+        raise ValueError("schedule must be an array of numbers") from None
+    if a.ndim != 2 or a.shape != (int(n_steps), 8):
+        raise ValueError(f"schedule must have shape [{int(n_steps)}, 8] (one row per step of the sampler), got {list(a.shape)}")
+    for c, name in enumerate(SCHEDULE_COLUMNS):
+        col = a[:, c]
+        if not np.isfinite(col).all():
+            raise ValueError(f"schedule: column {c} ({name}) holds a value that is not finite")
+        if c == 1 and (col < 0).any():
+            raise ValueError("schedule: column 1 (pag_scale) must be >= 0")
+        if c == 2 and ((col < 0) | (col > 1)).any():
+            raise ValueError("schedule: column 2 (guidance_rescale) must lie in [0, 1]")
+        if 3 <= c <= 6 and (col < 0).any():
+            raise ValueError(f"schedule: column {c} ({name}) must be >= 0")
+    return a
+
+
+def step_schedule(timesteps, guidance_scale=1.0, guidance_rescale=0.0, pag_scale=0.0, pag_adaptive_scale=0.0,
+                  guidance_interval=FULL_INTERVAL, pag_interval=FULL_INTERVAL, freeu=None, freeu_interval=FULL_INTERVAL,
+                  num_train_timesteps=1000) -> np.ndarray:
+    """The per-step schedule table of ``Sampler.run(schedule=)`` for the ``n`` steps at ``timesteps``: float32
+    ``[n, 8]``, row i = ``{g, s, phi, freeu_s1, freeu_s2, freeu_b1, freeu_b2, 0}`` of step i.  Pure Python on the CPU.  The rules:
+
+    * Adaptive PAG: ``s_i = max(pag_scale - pag_adaptive_scale * (num_train_timesteps - t_i), 0)`` - the rule of diffusers' PAG mixin
+      with its 1000 generalised (diffusers is not available to this project: the formula is the specification).  The scale decays
+      from the high-noise end and is clamped at 0.
+    * Intervals: step i of n is inside ``(lo, hi)`` iff ``i / n >= lo and (i + 1) / n <= hi`` - diffusers' ``control_guidance_start`` /
+      ``control_guidance_end`` rule; ``0 <= lo <= hi <= 1``.  Outside ``guidance_interval``: ``g = 1``.  Outside ``pag_interval``:
+      ``s = 0``.  Outside ``freeu_interval`` (or with ``freeu=None``): ``(1, 1, 1, 1)``; inside, the ``freeu = (s1, s2, b1, b2)`` values.
+    * A row with ``g == 1`` and ``s == 0`` gets ``phi = 0``: there is nothing to rescale, the prediction is the conditional one.
+    * So a step outside every interval is the neutral row ``{1, 0, 0, 1, 1, 1, 1, 0}``.
+
+    Raises ``ValueError`` for a value that is not finite, ``pag_scale`` or ``pag_adaptive_scale`` < 0, ``guidance_rescale`` outside
+    [0, 1], a negative FreeU value, a timestep outside ``[0, num_train_timesteps)`` or an interval that breaks the rule above."""
+    ts = np.asarray(timesteps.detach().cpu().numpy() if isinstance(timesteps, torch.Tensor) else timesteps)
+    if ts.ndim != 1 or ts.size == 0 or not np.isfinite(ts.astype(np.float64)).all():
+        raise ValueError("timesteps must be a non-empty 1-D sequence of finite numbers")
+    T = int(num_train_timesteps)
+    if T < 1 or (ts < 0).any() or (ts >= T).any():
+        raise ValueError(f"timesteps must lie in [0, num_train_timesteps = {num_train_timesteps!r})")
+    g = _finite("guidance_scale", guidance_scale)
+    phi = _finite("guidance_rescale", guidance_rescale, 0.0)
+    if phi > 1.0:
+        raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale!r}")
+    s0 = _finite("pag_scale", pag_scale, 0.0)
+    ad = _finite("pag_adaptive_scale", pag_adaptive_scale, 0.0)
+    g_iv, p_iv, f_iv = (_check_interval(n, v) for n, v in (("guidance_interval", guidance_interval), ("pag_interval", pag_interval),
+                                                            ("freeu_interval", freeu_interval)))
+    fu = None
+    if freeu is not None:
+        if len(tuple(freeu)) != 4:
+            raise ValueError(f"freeu must be a (s1, s2, b1, b2) tuple, got {freeu!r}")
+        fu = tuple(check_freeu(*freeu))
+    n = int(ts.size)
+
+    def inside(i, iv):
+        return i / n >= iv[0] and (i + 1) / n <= iv[1]
+
+    rows = np.empty((n, 8), dtype=np.float32)
+    for i in range(n):
+        gi = g if inside(i, g_iv) else 1.0
+        si = max(s0 - ad * (T - float(ts[i])), 0.0) if inside(i, p_iv) else 0.0
+        si = float(np.float32(si))
+        pi = 0.0 if (float(np.float32(gi)) == 1.0 and si == 0.0) else phi
+        with np.errstate(over="ignore"):
+            rows[i] = (gi, si, pi) + (fu if fu is not None and inside(i, f_iv) else (1.0, 1.0, 1.0, 1.0)) + (0.0,)
+    if not np.isfinite(rows).all():
+        raise ValueError("a value of the schedule is not finite in float32")
+    return rows
+
+
 MULTISTEP_KINDS = ("unipc", "dpmsolver++")
 
 
@@ -253,6 +357,8 @@ class Sampler:
         ts = scheduler.timesteps.detach().cpu().to(torch.int64).numpy().copy()
         ac = scheduler.alphas_cumprod.detach().cpu().to(torch.float32).numpy().copy()
         self.n_steps = len(ts)
+        self._timesteps, self._n_train = ts, len(ac)  # what ``step_schedule`` needs to build a table for this sampler
+        self._scheduled = False                       # whether the library holds a schedule table from the previous run
         self._h = C.c_void_p()
         L.check(L.lib().mrisr_sampler_create(unet._h, controlnet._h if controlnet is not None else None,
                                              kinds[kind],
@@ -366,9 +472,20 @@ class Sampler:
     def run(self, latents: torch.Tensor, encoder_hidden_states: torch.Tensor, lr_latents: Optional[torch.Tensor] = None,
             step_noise: Optional[torch.Tensor] = None, controlnet_cond: Optional[torch.Tensor] = None,
             adapter_features: Optional[Sequence[torch.Tensor]] = None, pag_scale: float = 0.0, pag_applied_layers=("mid",),
+            pag_adaptive_scale: float = 0.0, guidance_interval=None, pag_interval=None, freeu_interval=None, schedule=None,
             use_graph: bool = True, guidance_scale: float = 1.0, guidance_rescale: float = 0.0,
             uncond_hidden_states: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Advance ``latents`` [B,C,h,w] (f32, updated IN PLACE) through every timestep.
+
+        Per-step strengths: ``pag_adaptive_scale`` (the PAG scale decays as ``step_schedule`` states),
+        ``guidance_interval`` / ``pag_interval`` / ``freeu_interval`` (``(start, end)`` fractions of the run: outside, that control is
+        neutral) build a schedule table with ``step_schedule`` from the scalar arguments - inside an interval these are the values - and
+        the UNet's ``enable_freeu`` state; the captured step reads its strengths from the table, so other values replay the same graph.
+        Each needs its control to be active (``freeu_interval``: FreeU on the UNet).  ``schedule``: an explicit ``[n_steps, 8]`` table
+        (``check_schedule``) instead of those four; the scalar arguments then only choose the kind of run (``pag_scale > 0``: a PAG run;
+        ``uncond_hidden_states`` with ``guidance_scale != 1``: the unconditional half) and their values are not read.  Row i belongs to
+        step i of the schedule also under ``set_range``.  With none of the five the call is the one without a table: same launches,
+        same bits.  A step whose row is neutral still costs a guided step.
 
         FreeU needs no argument: a UNet with ``enable_freeu`` applies it in every step, with every option below
         except the feature cache.
@@ -400,6 +517,9 @@ class Sampler:
             plan = self._tile_plan(latents.shape[2], latents.shape[3])
         pag_mask = check_pag(pag_scale, pag_applied_layers, transformer_block_names(self.unet.config),
                              self.cache_interval > 1, self.unet.fp8_attention)
+        self._pending_schedule = self._build_schedule(schedule, pag_adaptive_scale, guidance_interval, pag_interval, freeu_interval,
+                                                      guidance_scale, guidance_rescale, pag_scale, bool(pag_mask),
+                                                      uncond_hidden_states is not None)
         if pag_mask:
             return self._run_pag(latents, encoder_hidden_states, uncond_hidden_states, lr_latents, step_noise, controlnet_cond,
                                  adapter_features, use_graph, guidance_scale, guidance_rescale, float(pag_scale), pag_mask, plan)
@@ -409,6 +529,41 @@ class Sampler:
                                     adapter_features, use_graph, float(guidance_scale), float(guidance_rescale), plan)
         return self._launch(L.lib().mrisr_sampler_run, latents, (encoder_hidden_states,), lr_latents, step_noise, controlnet_cond,
                             adapter_features, use_graph, plan)
+
+    def _build_schedule(self, schedule, pag_adaptive_scale, guidance_interval, pag_interval, freeu_interval, g, phi, pag_scale, pag_on,
+                        has_uncond):
+        """The schedule table of this ``run`` (float32 [n_steps, 8]) or None: no table, the call of before.  Everything is checked here,
+        before anything is launched."""
+        ad = _finite("pag_adaptive_scale", pag_adaptive_scale, 0.0)
+        ivs = {"guidance_interval": guidance_interval, "pag_interval": pag_interval, "freeu_interval": freeu_interval}
+        ivs = {k: (FULL_INTERVAL if v is None else _check_interval(k, v)) for k, v in ivs.items()}
+        given = [k for k, v in ivs.items() if v != FULL_INTERVAL] + (["pag_adaptive_scale"] if ad > 0.0 else [])
+        if schedule is not None:
+            if given:
+                raise ValueError(f"schedule is an explicit table: it excludes {', '.join(given)}")
+            return check_schedule(schedule, self.n_steps)
+        if not given:
+            return None
+        if (ad > 0.0 or ivs["pag_interval"] != FULL_INTERVAL) and not pag_on:
+            raise ValueError("pag_adaptive_scale / pag_interval need perturbed-attention guidance: pag_scale > 0")
+        if ivs["guidance_interval"] != FULL_INTERVAL and not (has_uncond and float(g) != 1.0):
+            raise ValueError("guidance_interval needs active classifier-free guidance: uncond_hidden_states and guidance_scale != 1")
+        freeu = getattr(self.unet, "freeu", None)
+        if ivs["freeu_interval"] != FULL_INTERVAL and freeu is None:
+            raise ValueError("freeu_interval needs FreeU on the UNet (unet.enable_freeu): it schedules that state's four values")
+        return step_schedule(self._timesteps, guidance_scale=g if has_uncond else 1.0, guidance_rescale=phi, pag_scale=pag_scale,
+                             pag_adaptive_scale=ad, guidance_interval=ivs["guidance_interval"], pag_interval=ivs["pag_interval"],
+                             freeu=freeu, freeu_interval=ivs["freeu_interval"], num_train_timesteps=self._n_train)
+
+    def _apply_schedule(self):
+        """Hands the table of this run to the library, or clears the one an earlier run left there."""
+        table, self._pending_schedule = getattr(self, "_pending_schedule", None), None
+        if table is not None:
+            L.check(L.lib().mrisr_sampler_set_schedule(self._h, table.ctypes.data_as(C.c_void_p), int(table.shape[0])))
+            self._scheduled = True
+        elif getattr(self, "_scheduled", False):
+            L.check(L.lib().mrisr_sampler_set_schedule(self._h, None, 0))
+            self._scheduled = False
 
     def _run_pag(self, latents, ehs_c, ehs_u, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, g, guidance_rescale,
                  s, mask, plan=None):
@@ -472,6 +627,7 @@ class Sampler:
         f_arr = L.tensor_array([L.as_tensor(f) for f in feats])
         if setup is not None:
             setup()
+        self._apply_schedule()
         L.check(entry(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None, C.byref(t_nz) if t_nz else None, C.byref(t_e),
                       C.byref(t_c) if t_c else None, f_arr if feats else None, len(feats), *extra, 1 if use_graph else 0, L.stream_ptr()))
         self._keep = keep
@@ -481,8 +637,9 @@ class Sampler:
 @torch.no_grad()
 def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weight_dtype, accelerator, fixed_embeds,
                    num_inference_steps=20, adapter=None, solver=None, cache_interval=1, cache_depth=1, tile=None, tile_overlap=0,
-                   tile_window="gaussian", pag_scale=0.0, pag_applied_layers=("mid",), freeu=None, guidance_scale=1.0,
-                   guidance_rescale=0.0, uncond_embeds=None):
+                   tile_window="gaussian", pag_scale=0.0, pag_applied_layers=("mid",), freeu=None, pag_adaptive_scale=0.0,
+                   guidance_interval=None, pag_interval=None, freeu_interval=None, guidance_scale=1.0, guidance_rescale=0.0,
+                   uncond_embeds=None):
     """Drop-in for the reference's validation sampler (res_srdiff.py:35-105): same inputs, same PIL panel out.
     The timestep loop is one fused sampler call; the per-step noise is drawn up front from the same global RNG
     stream, in the same order, as the reference's per-step ``torch.randn_like`` calls.  ``adapter`` (a T2I-Adapter):
@@ -495,7 +652,9 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     ``tile_window``: tiled sampling as in ``Sampler.set_tiles`` (latent pixels); the defaults leave the panel unchanged.
     ``pag_scale`` / ``pag_applied_layers``: perturbed-attention guidance as in ``Sampler.run``; the defaults leave the panel unchanged.
     ``freeu``: a ``(s1, s2, b1, b2)`` tuple turns FreeU on (``unet.enable_freeu``) for this validation run; the UNet's previous FreeU
-    state is restored afterwards, also on an error.  ``None``: the UNet's own state is used as it is."""
+    state is restored afterwards, also on an error.  ``None``: the UNet's own state is used as it is.
+    ``pag_adaptive_scale`` / ``guidance_interval`` / ``pag_interval`` / ``freeu_interval``: the per-step strengths of ``Sampler.run``
+    (``step_schedule``); the defaults leave the panel unchanged."""
     from PIL import Image
 
     freeu_vals = None
@@ -543,7 +702,8 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
                     controlnet_cond=control_image if controlnet is not None else None, adapter_features=feats,
                     guidance_scale=guidance_scale, guidance_rescale=guidance_rescale,
                     uncond_hidden_states=uncond_embeds[0:1] if uncond_embeds is not None else None, pag_scale=pag_scale,
-                    pag_applied_layers=pag_applied_layers)
+                    pag_applied_layers=pag_applied_layers, pag_adaptive_scale=pag_adaptive_scale, guidance_interval=guidance_interval,
+                    pag_interval=pag_interval, freeu_interval=freeu_interval)
     finally:
         if freeu_vals is not None:
             if freeu_prev is None:

@@ -305,6 +305,28 @@ int mrisr_sampler_num_captures(const mrisr_sampler* s);
  * Everything the runs refuse without a table stays refused. */
 int mrisr_sampler_set_schedule(mrisr_sampler* s, const float* rows_host, int n_rows);
 
+/* ---- conditioning strength: ControlNet and adapter scale per step, guess mode ---------------------------------------------------------
+ * Off unless mrisr_sampler_set_conditioning set a table: every ControlNet residual and adapter feature is then added at full strength,
+ * with the launches and the bits of before.  One f32 row of 4 per step of the sampler's schedule, row i for step i (an absolute index,
+ * like the coefficient rows and the schedule table above: mrisr_sampler_set_range keeps its meaning):
+ *     { c, a, 0, 0 }       c = ControlNet conditioning scale of the step, a = adapter conditioning scale of the step
+ * The neutral row is {1, 1, 0, 0}.  The sampler owns the device table (reserved once, one address for its life, uploaded on the run's
+ * stream before the first step).  While a table is set the UNet adds the residuals with a multi-tensor scaled add,
+ *     x_k = round_T( fma(f_k, r_k, x_k) )       f_k = w_k * c (residuals) or a (features), the product rounded once in f32,
+ * one launch for the down residuals, one for the mid residual, one per adapter feature; the kernel reads c / a from row *step with ordinary
+ * loads behind the load of the step counter, and reads r_k where the ControlNet's output convolutions wrote it.  The values are NOT part
+ * of the graph key: a run whose table has other values replays the stored graph.  Part of the key: the table's address, guess mode, the
+ * rows of the ControlNet's forward.  A step with c == 0 still runs the ControlNet.
+ * guess_mode != 0 (diffusers' guess_mode): w_k = logspace(-1, 0, n_down + 1)[k], the mid residual last at weight 1 (otherwise w_k = 1).
+ * In mrisr_sampler_run_guided the ControlNet then runs on the B conditional rows only - its input the last B rows of the staging buffer,
+ * its context the last B rows of ehs2, cond2 given at [B] - and its residuals are added to rows [B, 2B) of the UNet's batch; the
+ * unconditional rows get none.  In mrisr_sampler_run guess mode is the weights alone.
+ * rows_host NULL / n_rows 0 clears the table (and guess mode).  Refused before any device work, the message naming row and field:
+ * n_rows != n_steps, a value that is not finite, a non-zero column 2 or 3.  Refused by the run before any launch: rows with c != 1, or
+ * guess mode, on a sampler without a ControlNet; rows with a != 1 in a run without adapter features; guess mode in a PAG run or with
+ * tiles; a table together with a feature cache.  Everything the runs refuse without a table stays refused. */
+int mrisr_sampler_set_conditioning(mrisr_sampler* s, const float* rows_host, int n_rows, int guess_mode);
+
 /* ---- tiled sampling (MultiDiffusion, Bar-Tal et al. 2023, with the Gaussian weights of Mixture of Diffusers, Jimenez 2023) -------
  * The latent canvas [NB, C, H, W] is cut into overlapping tiles, the forward runs on the tile batch [NB*T, C, t_h, t_w] and the tile
  * predictions are blended back before the reverse step, which stays on the canvas.  All sizes in latent pixels.
@@ -676,6 +698,15 @@ int mrisr_op_freeu(int dtype, const void* hidden, const void* skip, void* hidden
  * rows (mrisr_sampler_set_schedule's layout and value checks; uploaded here) */
 int mrisr_op_freeu_scheduled(int dtype, const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs,
                              int stage, const float* sched_host, int n_rows, int slot, void* stream);
+/* the multi-tensor scaled add of the conditioning table alone: for k < n_pairs (1 .. 16), one launch,
+ *     x_k[j] = round_T( fma(f_k, r_k[j], x_k[j]) )    f_k = weights[k] * table[4 * slot + col]  (f32, rounded once); table_host NULL: f_k = weights[k]
+ * on rows [row_lo, row_hi) of x_k, which has per_row[k] elements of `dtype` per row (and at least row_hi rows); r_k has row_hi - row_lo rows.
+ * Rows outside the range are not touched.  table_host: n_rows rows of 4 floats (mrisr_sampler_set_conditioning's layout and checks; uploaded
+ * here); col 0 (c) or 1 (a).  Pairs whose two pointers (x_k at row_lo) are 16-byte aligned run in 16-byte pieces with a scalar tail, the
+ * others element by element.  Refused before any launch: null pointers, pointers not aligned to the element, an empty pair or row range,
+ * a weight that is not finite. */
+int mrisr_op_cond_add(int dtype, int n_pairs, void* const* x, const void* const* r, const int64_t* per_row, const float* weights,
+                      const float* table_host, int n_rows, int slot, int col, int row_lo, int row_hi, void* stream);
 /* dst[z][c][r] = src[z][r][c] for r < r_valid, 0 for r_valid <= r < R (T; pitches ld_src >= C, ld_dst >= R; batch strides in elements) */
 int mrisr_op_transpose(int dtype, const void* src, void* dst, int R, int C, int ld_src, int ld_dst, int64_t bs_src, int64_t bs_dst,
                        int batch, int r_valid, void* stream);

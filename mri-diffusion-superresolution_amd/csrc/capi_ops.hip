@@ -1073,6 +1073,35 @@ int mrisr_op_freeu_scheduled(int dtype, const void* hidden, const void* skip, vo
     API_END
 }
 
+// the multi-tensor scaled add of the conditioning table alone (condctl.hip): x_k += w_k * table[slot][col] * r_k on rows [row_lo, row_hi) of
+// x_k, for n_pairs pairs in one launch; table_host NULL: the factor is w_k
+int mrisr_op_cond_add(int dtype, int n_pairs, void* const* x, const void* const* r, const int64_t* per_row, const float* weights,
+                      const float* table_host, int n_rows, int slot, int col, int row_lo, int row_hi, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(dtype == MRISR_F32 || dtype == MRISR_BF16, "cond add: f32 or bf16 operands");
+    hipStream_t st = (hipStream_t)stream;
+    MRISR_REQUIRE(x && r && per_row && weights && n_pairs >= 1 && n_pairs <= COND_MAX_PAIRS, "cond add: 1 .. 16 pairs with their weights");
+    CondAddArgs a{};
+    DevBuf d_table, d_step;
+    if (table_host) {
+        MRISR_REQUIRE(n_rows >= 1 && n_rows <= 65536 && slot >= 0 && slot < n_rows, "cond add: a table of 1 .. 65536 rows, slot inside it");
+        MRISR_REQUIRE(col == 0 || col == 1, "cond add: column 0 (c) or 1 (a)");
+        TRY(check_conditioning_rows(table_host, n_rows));
+        TRY(d_table.reserve(sizeof(float) * 4 * (size_t)n_rows, false));
+        TRY(d_step.reserve(16, true));
+        MRISR_CHECK_HIP(hipMemcpyAsync(d_table.p, table_host, sizeof(float) * 4 * (size_t)n_rows, hipMemcpyHostToDevice, st));
+        MRISR_CHECK_HIP(hipMemcpyAsync(d_step.p, &slot, sizeof(int), hipMemcpyHostToDevice, st));
+        a.table = static_cast<const float*>(d_table.p); a.step = static_cast<const int*>(d_step.p); a.col = col;
+    }
+    a.n_pairs = n_pairs; a.row_lo = row_lo; a.row_hi = row_hi;
+    for (int k = 0; k < n_pairs; ++k) { a.pair[k].x = x[k]; a.pair[k].r = r[k]; a.pair[k].per = per_row[k]; a.pair[k].w = weights[k]; }
+    // (the launcher refuses null / misaligned pointers, empty pairs, an empty row range and weights that are not finite before it launches)
+    TRY(BWD_DISPATCH(dtype, launch_cond_add, a, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
 int mrisr_op_softmax_bwd(int dtype, const void* p, const float* dp, void* ds, int ld, int64_t rows, int nk, float scale, void* stream) {
     API_BEGIN
     TRY(bwd_dtype_ok(dtype));

@@ -320,6 +320,26 @@ int launch_freeu(const void* hidden, const void* skip, void* hidden_out, void* s
 template <typename T>
 int launch_freeu_sched(const void* hidden, const void* skip, void* hidden_out, void* skip_out, int B, int H, int W, int Ch, int Cs,
                        const float* sched, const int* step, int col_b, int col_s, hipStream_t st);
+// conditioning strength (condctl.hip): one launch of x_k += f_k r_k over up to COND_MAX_PAIRS pairs,
+// f_k = w_k * table[4 * (*step) + col] (table null: f_k = w_k).  Pair k has `per` elements per batch row; the launch adds to rows
+// [row_lo, row_hi) of x_k, and r_k holds row_hi - row_lo rows.  The block is passed to the kernel by value.
+constexpr int COND_MAX_PAIRS = 16;
+struct CondAddPair {
+    void* x;
+    const void* r;
+    long long per;
+    float w;
+    int reserved;
+};
+struct CondAddArgs {
+    CondAddPair pair[COND_MAX_PAIRS];
+    const float* table;
+    const int* step;
+    int col, row_lo, row_hi, n_pairs;
+};
+template <typename T> int launch_cond_add(const CondAddArgs& a, hipStream_t st);
+int check_conditioning_rows(const float* rows, int n_rows);  // [n_rows][4] = {c, a, 0, 0}: finite, columns 2 and 3 zero
+void guess_mode_weights(int n_down, float* w);               // n_down + 1 weights: logspace(-1, 0, n_down + 1), the mid residual last
 template <typename T>
 int launch_softmax_bwd(const void* p, const float* dp, void* ds, int ld, long long rows, int nk, float scale, hipStream_t st);
 template <typename T>

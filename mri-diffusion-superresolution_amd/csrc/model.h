@@ -84,6 +84,21 @@ struct FreeUState {
     const int* step = nullptr;
 };
 
+// Conditioning strength: a sampler run with a conditioning table sets this on its UNet and its ControlNet for the
+// duration of the run (a guard clears it on every exit path).  Part of the workspace key.
+// UNet: the ControlNet residuals (NHWC, compute dtype, read where the ControlNet wrote them) are added by launch_cond_add - the down
+// residuals in one launch, the mid residual in a second - with f_k = w[k] * table[4 * (*step)] on rows [row_lo, row_hi) of the batch
+// (row_hi == 0: every row); the adapter features by the same kernel, one launch each, with column 1 on every row.
+// ControlNet: the output convolutions write straight into the caller's NHWC tensors (no export copy).
+struct CondState {
+    bool on = false;
+    bool guess = false;
+    const float* table = nullptr;  // [n_steps][4] = {c, a, 0, 0}
+    const int* step = nullptr;
+    int row_lo = 0, row_hi = 0;
+    float w[32] = {};              // per residual, the mid residual after the down residuals (PLAN_MAX_RES entries)
+};
+
 struct Model {
     mrisr_unet_cfg cfg{};
     bool is_controlnet = false;
@@ -93,6 +108,7 @@ struct Model {
     bool finalized = false;
     PagState pag;       // mrisr_model_set_pag: honoured by every forward_unet until cleared
     FreeUState freeu;   // mrisr_model_set_freeu: honoured by every forward_unet until cleared
+    CondState cond;     // set by a sampler run with a conditioning table, for that run only
     std::vector<std::unique_ptr<DevBuf>> packed;
 
     // packed modules

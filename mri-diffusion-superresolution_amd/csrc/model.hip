@@ -723,6 +723,10 @@ int Model::ensure_workspace(int B, int h, int w, int L, hipStream_t st) {
         if (freeu.sched) snprintf(key + n, sizeof(key) - n, ",fT");
         else snprintf(key + n, sizeof(key) - n, ",f%a:%a:%a:%a", (double)freeu.s[0], (double)freeu.s[1], (double)freeu.b[0], (double)freeu.b[1]);
     }
+    if (cond.on) {  // a run with a conditioning table: no import copies of the residuals (UNet), no staged outputs (ControlNet)
+        const size_t n = strlen(key);
+        snprintf(key + n, sizeof(key) - n, cond.guess ? ",cG%d:%d" : ",cT%d:%d", cond.row_lo, cond.row_hi);
+    }
     if (ws_key == key) return 0;
     int rc = cfg.compute_dtype == MRISR_F32 ? plan_t<float>(*this, B, h, w, L, st) : plan_t<bf16>(*this, B, h, w, L, st);
     if (rc) return rc;
@@ -764,6 +768,12 @@ int Model::forward_unet(const mrisr_tensor* sample, const mrisr_tensor* timestep
         MRISR_REQUIRE(!cache || cache->mode == CACHE_NONE, "FreeU together with a feature cache is not supported");
         MRISR_REQUIRE(!keep, "FreeU: not while a training forward is being recorded");
     }
+    if (cond.on) {  // likewise before the plan
+        MRISR_REQUIRE(!keep, "conditioning table: not while a training forward is being recorded");
+        MRISR_REQUIRE(cond.table && cond.step, "conditioning table: no table or step counter");
+        MRISR_REQUIRE(cond.row_hi == 0 || (cond.row_lo >= 0 && cond.row_lo < cond.row_hi && cond.row_hi <= B),
+                      "conditioning table: the row range lies outside the batch");
+    }
     TRY(ensure_workspace(B, h, w, L, st));
     const int t_scalar = timestep->ndim == 0 || timestep->shape[0] == 1;
     MRISR_REQUIRE(t_scalar || timestep->shape[0] == B, "timestep length");
@@ -793,6 +803,7 @@ int Model::forward_controlnet(const mrisr_tensor* sample, const mrisr_tensor* ti
     const int L = ehs ? (int)ehs->shape[1] : ctx_len;
     MRISR_REQUIRE(L > 0, "no encoder_hidden_states given and none cached");
     if (cond) MRISR_REQUIRE(cond->ndim == 4 && cond->shape[2] == 8 * h && cond->shape[3] == 8 * w, "controlnet_cond must be [B,3,8h,8w]");
+    if (this->cond.on) MRISR_REQUIRE(!keep, "conditioning table: not while a training forward is being recorded");
     TRY(ensure_workspace(B, h, w, L, st));
     const int t_scalar = timestep->ndim == 0 || timestep->shape[0] == 1;
     const long long* t = static_cast<const long long*>(timestep->data);

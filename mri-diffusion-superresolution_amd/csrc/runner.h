@@ -628,6 +628,36 @@ struct Runner {
         return 0;
     }
 
+    // Conditioning strength (m.cond.on): x_k += w_k * table[*step][col] * r_k for n (x, r) pairs, COND_MAX_PAIRS per
+    // launch.  r_k is read where it lies (NHWC, compute dtype: no import copy); it carries the rows [row_lo, row_hi) of x_k's batch
+    int cond_add(const Act* xs, const mrisr_tensor* rs, const float* w, int n, int col, int row_lo, int row_hi) {
+        MRISR_REQUIRE(!m.keep, "conditioning table: not while a training forward is being recorded");
+        if (dry) return 0;
+        for (int k0 = 0; k0 < n; k0 += COND_MAX_PAIRS) {
+            CondAddArgs a{};
+            a.table = m.cond.table; a.step = m.cond.step; a.col = col;
+            a.n_pairs = std::min(COND_MAX_PAIRS, n - k0);
+            for (int k = 0; k < a.n_pairs; ++k) {
+                const Act& x = xs[k0 + k];
+                const mrisr_tensor& t = rs[k0 + k];
+                const int lo = row_hi > 0 ? row_lo : 0, hi = row_hi > 0 ? row_hi : x.B;
+                MRISR_REQUIRE(t.ndim == 4 && t.layout == MRISR_NHWC && t.dtype == m.cfg.compute_dtype && t.data,
+                              "conditioning table: residuals and features must be NHWC in the compute dtype");
+                MRISR_REQUIRE(lo >= 0 && hi <= x.B && t.shape[0] == hi - lo && t.shape[1] == x.C && t.shape[2] == x.H && t.shape[3] == x.W,
+                              "residual shape mismatch");
+                a.row_lo = lo; a.row_hi = hi;
+                a.pair[k].x = x.p; a.pair[k].r = t.data; a.pair[k].per = (long long)x.H * x.W * x.C; a.pair[k].w = w ? w[k0 + k] : 1.f;
+            }
+            TRY(launch_cond_add<T>(a, st));
+        }
+        return 0;
+    }
+    // an adapter feature onto x: add_external, or - a run with a conditioning table - the scaled add with the table's column 1
+    int add_feature(Act& x, const mrisr_tensor& t) {
+        if (!m.cond.on) return add_external(x, t);
+        return cond_add(&x, &t, nullptr, 1, 1, 0, 0);
+    }
+
     // ---- encoder shared by UNet and ControlNet: down blocks (+skips) ----
     // last_skip >= 0 (a shallow pass over a feature cache): stop once skip s_last_skip is what the full pass would hand the decoder
     int encoder(Act x, const mrisr_tensor* intrablock, int n_intra, std::vector<Act>* skips, Act* out, int last_skip = -1) {
@@ -647,7 +677,7 @@ struct Runner {
                 if (has_attn) {
                     TRY(transformer(lv.xf[j], x, &y, &xn_next));
                     x = y;
-                    if (j + 1 == lv.res.size() && ib < n_intra) TRY(add_external(x, intrablock[ib++]));
+                    if (j + 1 == lv.res.size() && ib < n_intra) TRY(add_feature(x, intrablock[ib++]));
                 }
                 skips->push_back(x);
             }
@@ -664,7 +694,7 @@ struct Runner {
                 // tensor DownBlock2D also returned as res_samples[-1] - so the LAST skip pushed above carries the
                 // feature (as in the original TencentARC loop, which adds before hs.append(h)); the earlier skips of
                 // the block do not.  x shares its buffer with skips->back(): add in place.
-                TRY(add_external(x, intrablock[ib++]));
+                TRY(add_feature(x, intrablock[ib++]));
             }
         }
         *out = x;
@@ -742,11 +772,14 @@ struct Runner {
                     if (!dry) MRISR_CHECK_HIP(hipMemcpyAsync(c.p, x.p, x.numel() * sizeof(T), hipMemcpyDeviceToDevice, st));
                     skips[k] = c;
                 }
-                TRY(add_external(skips[k], down_res[k]));
+                if (!m.cond.on) TRY(add_external(skips[k], down_res[k]));
             }
+            // a run with a conditioning table: every down residual in one launch, scaled by w_k * c of the step
+            if (m.cond.on) TRY(cond_add(skips.data(), down_res, m.cond.w, n_down, 0, m.cond.row_lo, m.cond.row_hi));
         }
         if (!use) TRY(mid(x, &x));
-        if (mid_res) TRY(add_external(x, *mid_res));
+        if (mid_res && m.cond.on) TRY(cond_add(&x, mid_res, m.cond.w + n_down, 1, 0, m.cond.row_lo, m.cond.row_hi));
+        else if (mid_res) TRY(add_external(x, *mid_res));
         int q = 0;
         for (int i = 0; i < m.cfg.num_levels; ++i) {
             Level& lv = m.up[i];
@@ -827,6 +860,19 @@ struct Runner {
         TRY(encoder(x, nullptr, 0, &skips, &x));
         TRY(mid(x, &x));
         MRISR_REQUIRE(n_down == (int)skips.size(), "ControlNet output count");
+        if (m.cond.on && !dry) {
+            // a run with a conditioning table: the output convolutions write where the UNet's scaled add reads (no staging, no export copy)
+            MRISR_REQUIRE(!m.keep && scale == 1.0f, "conditioning table: scale 1 and no recorded training forward on the ControlNet");
+            for (int k = 0; k <= n_down; ++k) {
+                const Act& s_k = k < n_down ? skips[k] : x;
+                const mrisr_tensor& t = k < n_down ? down_out[k] : *mid_out;
+                MRISR_REQUIRE(t.ndim == 4 && t.layout == MRISR_NHWC && t.dtype == m.cfg.compute_dtype && t.data && t.shape[0] == s_k.B &&
+                                  t.shape[1] == s_k.C && t.shape[2] == s_k.H && t.shape[3] == s_k.W,
+                              "conditioning table: ControlNet outputs must be NHWC in the compute dtype, in the skips' shapes");
+                TRY(linear(s_k.p, (int)s_k.rows(), s_k.C, k < n_down ? m.cn_down[k] : m.cn_mid, ACT_NONE, nullptr, 0, nullptr, t.data, s_k.C));
+            }
+            return 0;
+        }
         for (int k = 0; k < n_down; ++k) {
             const size_t mk = m.arena.mark();
             Act o = new_act(skips[k].B, skips[k].H, skips[k].W, skips[k].C);

@@ -590,6 +590,12 @@ struct mrisr_sampler {
     std::vector<float> sched;
     DevBuf d_sched;
     bool sched_phi = false, sched_s = false, sched_g = false, sched_freeu = false;
+    // conditioning strength (mrisr_sampler_set_conditioning): host rows [n_steps][4] = {c, a, 0, 0} (empty: none - every
+    // residual and feature at full strength, added as before), the device table (reserved once, one address for the sampler's life), and
+    // what the checks need of the values: some row with c != 1 / a != 1
+    std::vector<float> cond;
+    DevBuf d_cond;
+    bool cond_guess = false, cond_c = false, cond_a = false;
     std::vector<float> sigma;  // host copy of each step's noise coefficient (which steps read a step_noise slab)
     DevBuf d_ts, d_coef, d_step, d_curt, d_eps;
     // multistep kinds: solver options, the clamped alphas_cumprod on the grid (+ alphas_cumprod[0]), the host rows of the current range,
@@ -633,8 +639,14 @@ struct mrisr_sampler {
 
 // The options that exclude each other, every rule once: the first rule that (UNet state, ControlNet attached, cache interval, tiles on,
 // PAG run) violates, or null.  The setters call it with the value they are about to set, the run with what is set; always before any launch.
-static const char* option_conflict(const Model& U, bool has_cnet, int cache_interval, bool tiles_on, bool pag_run) {
+// cond_table / guess: the conditioning table and guess mode of the run (the setters, which do not know the run's table, pass false).
+static const char* option_conflict(const Model& U, bool has_cnet, int cache_interval, bool tiles_on, bool pag_run, bool cond_table = false,
+                                   bool guess = false) {
     const bool cached = cache_interval > 1;
+    if (cond_table && cached) return "conditioning: a conditioning table together with a feature cache (interval > 1) is not supported";
+    if (guess && pag_run) return "conditioning: guess mode in a pag run is not supported";
+    if (guess && tiles_on) return "conditioning: guess mode together with tiles is not supported";
+    if (cond_table && U.keep) return "conditioning: a training forward is being recorded";
     if (cached && has_cnet) return "a feature cache (interval > 1) together with a ControlNet is not supported";
     if (cached && tiles_on) return "a feature cache (interval > 1) together with tiles is not supported";
     if (cached && U.freeu.on) return "a feature cache (interval > 1) together with FreeU is not supported (mrisr_model_set_freeu)";
@@ -831,6 +843,29 @@ int mrisr_sampler_set_schedule(mrisr_sampler* s, const float* rows_host, int n_r
     API_END
 }
 
+int mrisr_sampler_set_conditioning(mrisr_sampler* s, const float* rows_host, int n_rows, int guess_mode) {
+    API_BEGIN
+    MRISR_REQUIRE(s, "null sampler");
+    if (!rows_host || n_rows == 0) {  // cleared: the adds of before (other plan: the next run captures again)
+        MRISR_REQUIRE(!rows_host && n_rows == 0, "conditioning: NULL / 0 clears it; rows need n_rows == n_steps");
+        s->cond.clear();
+        s->cond_guess = s->cond_c = s->cond_a = false;
+        return 0;
+    }
+    MRISR_REQUIRE(n_rows == s->n_steps, "conditioning: n_rows must equal the sampler's n_steps (" + std::to_string(s->n_steps) + "), got " + std::to_string(n_rows));
+    if (int rc = check_conditioning_rows(rows_host, n_rows)) return rc;
+    TRY(s->d_cond.reserve(sizeof(float) * 4 * (size_t)s->n_steps, false));  // once per sampler: n_rows is always n_steps
+    s->cond.assign(rows_host, rows_host + 4 * (size_t)n_rows);
+    s->cond_guess = guess_mode != 0;
+    s->cond_c = s->cond_a = false;
+    for (int i = 0; i < n_rows; ++i) {
+        s->cond_c |= rows_host[4 * (size_t)i] != 1.f;
+        s->cond_a |= rows_host[4 * (size_t)i + 1] != 1.f;
+    }
+    return 0;
+    API_END
+}
+
 }  // extern "C"
 
 // ---- one run: mrisr_sampler_run (K = 1: B rows everywhere), mrisr_sampler_run_guided (K = 2) and mrisr_sampler_run_pag (pag: K = 2 or 3).
@@ -866,9 +901,17 @@ static int run_check(mrisr_sampler* s, const RunArgs& a, StepPlan& p) {
         MRISR_REQUIRE(K == 2 || K == 3, "pag run: the forward has 2B rows (pag alone) or 3B rows (with classifier-free guidance)");
         MRISR_REQUIRE(s->pag_mask != 0, "pag run: no applied block (mrisr_sampler_set_pag)");
     }
-    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, s->cache_interval, s->tile_h != 0, pag);
+    const bool ctab = !s->cond.empty(), guess = ctab && s->cond_guess;
+    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, s->cache_interval, s->tile_h != 0, pag, ctab, guess);
     MRISR_REQUIRE(!conflict, conflict);
     Model& U = *s->unet;
+    if (ctab) {  // the table only supplies values: one this run cannot honour is refused
+        MRISR_REQUIRE(s->cnet || !s->cond_c, "conditioning: rows with a controlnet scale (c) != 1 need a sampler with a ControlNet");
+        MRISR_REQUIRE(s->cnet || !guess, "conditioning: guess mode needs a sampler with a ControlNet");
+        MRISR_REQUIRE(a.n_intrablock > 0 || !s->cond_a, "conditioning: rows with an adapter scale (a) != 1 need a run with adapter features");
+        MRISR_REQUIRE(!U.cond.on && (!s->cnet || !s->cnet->cond.on), "conditioning: a model handle already carries a conditioning state");
+    }
+    const bool guess_half = guess && K == 2 && !pag;  // the ControlNet runs on the B conditional rows only
     const bool sched = !s->sched.empty();
     if (sched) {  // the run kind comes from the entry point; the table only supplies the values, and a value this kind cannot honour is refused
         MRISR_REQUIRE(U.freeu.on || !s->sched_freeu, "schedule: FreeU columns other than 1 need FreeU on the UNet (mrisr_model_set_freeu)");
@@ -922,7 +965,10 @@ static int run_check(mrisr_sampler* s, const RunArgs& a, StepPlan& p) {
                                                          : "guided run: C*h*w of the latents must be a multiple of 4");
     if (s->multistep()) MRISR_REQUIRE(B > 0 && per % 4 == 0, "multistep solvers: C*h*w of the latents must be a multiple of 4");
     if (a.lr) MRISR_REQUIRE(a.lr->dtype == MRISR_F32 && numel(a.lr) == n, "lr_latents: f32, same shape as latents");
-    if (cond && !tiled)
+    if (cond && guess_half)
+        MRISR_REQUIRE(cond->ndim == 4 && cond->shape[0] == B && cond->shape[2] == 8 * h && cond->shape[3] == 8 * w,
+                      "guided run in guess mode: controlnet_cond must be [B, C, 8h, 8w]: the ControlNet sees the conditional rows only");
+    else if (cond && !tiled)
         MRISR_REQUIRE(cond->ndim == 4 && cond->shape[0] == NB && cond->shape[2] == 8 * h && cond->shape[3] == 8 * w,
                       pag ? "pag run: controlnet_cond must be [K B, C, 8h, 8w] (the [B] images K times)"
                       : guided ? "guided run: controlnet_cond must be [2B, C, 8h, 8w] (the [B] images twice)"
@@ -975,6 +1021,13 @@ static int run_check(mrisr_sampler* s, const RunArgs& a, StepPlan& p) {
             p.freeu_s[0] = U.freeu.s[0]; p.freeu_s[1] = U.freeu.s[1]; p.freeu_b[0] = U.freeu.b[0]; p.freeu_b[1] = U.freeu.b[1];
         }
     }
+    if (ctab) {
+        // the conditioning table: the launches take its address, never its values - other values, same graph.  What chooses launches is
+        // here: table mode itself (the scaled adds; both workspace generations carry a marker for it), guess mode, the ControlNet's rows
+        p.d_cond = static_cast<const float*>(s->d_cond.p);
+        p.cond_guess = guess ? 1 : 0;
+        if (s->cnet) p.cnet_rows = guess_half ? B : FB;
+    }
     if (s->multistep()) {
         p.order = s->ms.order;
         p.final_zero = s->ms.final_zero; p.lower_order_final = s->ms.lower_order_final;
@@ -996,13 +1049,19 @@ static int run_operands(mrisr_sampler* s, const RunArgs& a, StepPlan& p, hipStre
     TRY(U.set_context(a.ehs, FB, p.fh, p.fw, st));
     if (s->cnet) {
         Model& C = *s->cnet;
-        TRY(C.set_context(a.ehs, FB, p.fh, p.fw, st));
+        const int CB = p.cnet_rows ? p.cnet_rows : FB;  // guess mode under classifier-free guidance: the conditional rows, the last B
+        mrisr_tensor ehs_c = *a.ehs;
+        if (CB != FB) {
+            ehs_c.shape[0] = CB;
+            ehs_c.data = static_cast<char*>(a.ehs->data) + (size_t)(FB - CB) * a.ehs->shape[1] * a.ehs->shape[2] * dtype_size(a.ehs->dtype);
+        }
+        TRY(C.set_context(&ehs_c, CB, p.fh, p.fw, st));
         TRY(C.set_cond(a.cond, p.L, st));
         p.n_res = C.num_skips();
         s->res_bufs.resize(p.n_res + 1);
         for (int k = 0; k <= p.n_res; ++k) {  // the mid residual last
             int64_t shape[4];
-            C.skip_shape(k, FB, p.fh, p.fw, shape);
+            C.skip_shape(k, CB, p.fh, p.fw, shape);
             if (!s->res_bufs[k]) s->res_bufs[k].reset(new DevBuf());
             TRY(s->res_bufs[k]->reserve((size_t)shape[0] * shape[1] * shape[2] * shape[3] * esz, false));
             p.res[k].data = s->res_bufs[k]->p;
@@ -1082,6 +1141,10 @@ static int run_buffers(mrisr_sampler* s, StepPlan& p, hipStream_t st) {
         MRISR_REQUIRE(s->sched.size() == (size_t)8 * s->n_steps && s->d_sched.bytes >= sizeof(float) * s->sched.size(), "schedule table size");
         MRISR_CHECK_HIP(hipMemcpyAsync(s->d_sched.p, s->sched.data(), sizeof(float) * s->sched.size(), hipMemcpyHostToDevice, st));
     }
+    if (p.d_cond) {  // the conditioning rows, indexed by the absolute step; pageable and replaceable like s->sched above
+        MRISR_REQUIRE(s->cond.size() == (size_t)4 * s->n_steps && s->d_cond.bytes >= sizeof(float) * s->cond.size(), "conditioning table size");
+        MRISR_CHECK_HIP(hipMemcpyAsync(s->d_cond.p, s->cond.data(), sizeof(float) * s->cond.size(), hipMemcpyHostToDevice, st));
+    }
     MRISR_CHECK_HIP(hipMemsetAsync(s->d_step.p, 0, 16, st));
     MRISR_CHECK_HIP(hipMemcpyAsync(s->d_step.p, &s->first, sizeof(int), hipMemcpyHostToDevice, st));
     return 0;
@@ -1136,7 +1199,14 @@ static int step_body(const StepPlan& p, Model& U, Model* C, int cache_mode, hipS
 
     hipLaunchKernelGGL(load_t_kernel, dim3(1), dim3(1), 0, st, p.d_curt, p.d_ts, static_cast<const int*>(p.d_step));
     if (tiled) TRY(launch_tile_gather(canvas, p.d_xt, tg, NB, p.C, st));
-    if (p.cnet) TRY(C->forward_controlnet(&xin, &tt, nullptr, nullptr, 1.0f, res, p.n_res, &res[p.n_res], st));
+    if (p.cnet) {
+        mrisr_tensor cin = xin;
+        if (p.cnet_rows && p.cnet_rows != FB) {  // guess mode under classifier-free guidance: the last B rows of the staging buffer
+            cin.shape[0] = p.cnet_rows;
+            cin.data = const_cast<float*>(canvas) + (size_t)(FB - p.cnet_rows) * per;
+        }
+        TRY(C->forward_controlnet(&cin, &tt, nullptr, nullptr, 1.0f, res, p.n_res, &res[p.n_res], st));
+    }
     TRY(U.forward_unet(&xin, &tt, nullptr, p.cnet ? res : nullptr, p.n_res, p.cnet ? &res[p.n_res] : nullptr, intra, p.n_intra, &eps_t, st,
                        p.cached ? &fc : nullptr));
     if (tiled) TRY(launch_tile_blend(p.d_et, p.d_eps, tg, NB, p.C, st));
@@ -1228,6 +1298,25 @@ static int sampler_run_impl(mrisr_sampler* s, const RunArgs& a, int use_graph, v
     if (p.freeu == 2) {
         fguard.m = &U;
         U.freeu.sched = p.d_sched; U.freeu.step = static_cast<const int*>(s->d_step.p);
+    }
+    // The conditioning table: for the duration of this run the UNet adds residuals and features with the scaled multi-tensor add and the
+    // ControlNet writes its outputs where that add reads them.  Set before the workspaces are planned (their keys carry the mode), cleared
+    // on every exit path: plain forwards on the handles add at full strength again
+    struct CondGuard {
+        Model* a = nullptr; Model* b = nullptr;
+        ~CondGuard() { if (a) a->cond = CondState(); if (b) b->cond = CondState(); }
+    } cguard;
+    if (p.d_cond) {
+        cguard.a = &U; cguard.b = s->cnet;
+        CondState cs;
+        cs.on = true; cs.guess = p.cond_guess != 0;
+        cs.table = p.d_cond; cs.step = static_cast<const int*>(s->d_step.p);
+        const int n_down = s->cnet ? s->cnet->num_skips() : 0;
+        for (int k = 0; k <= n_down; ++k) cs.w[k] = 1.f;
+        if (cs.guess) guess_mode_weights(n_down, cs.w);
+        if (s->cnet) { s->cnet->cond = cs; s->cnet->cond.row_lo = s->cnet->cond.row_hi = 0; }
+        if (p.cnet_rows && p.cnet_rows != p.K * p.B * p.T) { cs.row_lo = p.K * p.B * p.T - p.cnet_rows; cs.row_hi = p.K * p.B * p.T; }
+        U.cond = cs;
     }
     TRY(run_operands(s, a, p, st));
     TRY(run_buffers(s, p, st));

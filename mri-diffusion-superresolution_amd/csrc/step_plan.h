@@ -42,6 +42,7 @@ struct StepPlan {
     long long* d_curt;
     const long long* d_ts;
     const float* d_sched;  // per-step schedule table [n_steps][8] = {g, s, phi, freeu s1, s2, b1, b2, 0}, or null: the scalars below rule
+    const float* d_cond;   // conditioning table [n_steps][4] = {c, a, 0, 0}, or null: every residual at full strength
     // ---- model state the forwards bake in ----
     unsigned long long ws_gen_unet, ws_gen_cnet;  // workspace generations: persist / arena base addresses
     const float* tproj_unet;                      // per-run time-embedding tables (null: computed per step)
@@ -67,6 +68,9 @@ struct StepPlan {
     // with d_sched the VALUES of a schedule are not here (guidance_scale, guidance_rescale, pag_scale, freeu_s / freeu_b stay zero): only what
     // chooses kernels.  sched_phi: some row of the table has phi > 0 - the guided step is the rescale kernel.  sched_rows: the table's rows
     int sched_phi, sched_rows;
+    // with d_cond the VALUES of the conditioning table are not here either.  cond_guess: guess mode (the per-residual weights; under
+    // classifier-free guidance the ControlNet runs on the conditional rows only).  cnet_rows: the rows of the ControlNet's forward
+    int cond_guess, cnet_rows;
     int first;           // the step the run starts at (the time-embedding table's row 0)
     // ---- policy, not baked in: these live in the uploaded rows; a change captures again because set_solver promises it ----
     int final_zero, lower_order_final;

@@ -1518,6 +1518,7 @@ int Model::train_plan(const mrisr_tensor* sample, const mrisr_tensor* timestep, 
     const int t_scalar = timestep->ndim == 0 || timestep->shape[0] == 1;
     MRISR_REQUIRE(!pag.on(), "a training forward cannot be recorded while perturbed-attention guidance is set (mrisr_model_set_pag)");
     MRISR_REQUIRE(!freeu.on, "a training forward cannot be recorded while FreeU is on (mrisr_model_set_freeu)");
+    MRISR_REQUIRE(!cond.on, "a training forward cannot be recorded while a sampler's conditioning table is set on the handle");
     keep = true;
     int rc = ensure_workspace(B, h, w, (int)ehs->shape[1], st);
     if (!rc) {
@@ -1541,6 +1542,7 @@ int Model::train_step(const mrisr_tensor* sample, const mrisr_tensor* timestep, 
     MRISR_REQUIRE(t_scalar || timestep->shape[0] == B, "timestep length");
     MRISR_REQUIRE(!pag.on(), "a training forward cannot be recorded while perturbed-attention guidance is set (mrisr_model_set_pag)");
     MRISR_REQUIRE(!freeu.on, "a training forward cannot be recorded while FreeU is on (mrisr_model_set_freeu)");
+    MRISR_REQUIRE(!cond.on, "a training forward cannot be recorded while a sampler's conditioning table is set on the handle");
     keep = true;
     int rc = ensure_workspace(B, h, w, (int)ehs->shape[1], st);
     if (!rc) {

@@ -10,6 +10,7 @@ from .pipeline import (Sampler, check_cache, check_guidance, check_solver, decod
 from .pipeline import check_tiles, tile_tables  # noqa: F401
 from .pipeline import check_pag  # noqa: F401
 from .pipeline import check_schedule, step_schedule  # noqa: F401
+from .pipeline import check_conditioning, conditioning_schedule, guess_mode_weights  # noqa: F401
 from .models import transformer_block_names  # noqa: F401
 from .models import check_freeu, freeu_stage_names  # noqa: F401
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler,  # noqa: F401

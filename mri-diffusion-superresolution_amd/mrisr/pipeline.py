@@ -238,6 +238,70 @@ def step_schedule(timesteps, guidance_scale=1.0, guidance_rescale=0.0, pag_scale
     return rows
 
 
+CONDITIONING_COLUMNS = ("controlnet_conditioning_scale", "adapter_conditioning_scale", "padding", "padding")
+
+
+def check_conditioning(table, n_steps) -> np.ndarray:
+    """The rules of an explicit conditioning table (``Sampler.run(conditioning=)``), on numbers alone (no device is
+    touched): ``[n_steps, 4]`` rows ``{c, a, 0, 0}``, every value finite, columns 2 and 3 zero.  Returns it as a contiguous float32
+    array; raises ``ValueError`` naming the column."""
+    try:
+        a = np.ascontiguousarray(np.asarray(table, dtype=np.float32))
+    except (TypeError, ValueError):
+        raise ValueError("conditioning must be an array of numbers") from None
+    if a.ndim != 2 or a.shape != (int(n_steps), 4):
+        raise ValueError(f"conditioning must have shape [{int(n_steps)}, 4] (one row per step of the sampler), got {list(a.shape)}")
+    for c, name in enumerate(CONDITIONING_COLUMNS):
+        if not np.isfinite(a[:, c]).all():
+            raise ValueError(f"conditioning: column {c} ({name}) holds a value that is not finite")
+        if c >= 2 and (a[:, c] != 0).any():
+            raise ValueError(f"conditioning: column {c} ({name}) must be 0")
+    return a
+
+
+def conditioning_schedule(n_steps, controlnet_conditioning_scale=1.0, control_guidance_start=0.0, control_guidance_end=1.0,
+                          adapter_conditioning_scale=1.0, adapter_conditioning_factor=1.0) -> np.ndarray:
+    """The conditioning table of ``Sampler.run(conditioning=)`` for a run of ``n_steps`` steps: float32
+    ``[n_steps, 4]``, row i = ``{c_i, a_i, 0, 0}``.  Pure Python on the CPU.  The rules (diffusers is not available to this project: the
+    formulae are the specification):
+
+    * ``c_i = controlnet_conditioning_scale`` if step i is inside ``(control_guidance_start, control_guidance_end)`` - that is,
+      ``i / n >= start and (i + 1) / n <= end``, diffusers' ``controlnet_keep`` and the ``inside`` rule of ``step_schedule`` - and 0 otherwise.
+    * ``a_i = adapter_conditioning_scale`` if ``i < int(n * adapter_conditioning_factor)`` - the rule of diffusers' T2I-Adapter
+      pipeline - and 0 otherwise.
+    * So the defaults give the neutral row ``{1, 1, 0, 0}`` on every step.
+
+    Raises ``ValueError`` for ``n_steps < 1``, a value that is not finite (also once rounded to float32), ``start`` / ``end`` that break
+    ``0 <= start <= end <= 1`` or a factor outside [0, 1]."""
+    if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or n_steps < 1:
+        raise ValueError(f"n_steps must be an int >= 1, got {n_steps!r}")
+    n = int(n_steps)
+    c = _finite("controlnet_conditioning_scale", controlnet_conditioning_scale)
+    a = _finite("adapter_conditioning_scale", adapter_conditioning_scale)
+    lo, hi = _check_interval("(control_guidance_start, control_guidance_end)", (control_guidance_start, control_guidance_end))
+    fac = _finite("adapter_conditioning_factor", adapter_conditioning_factor, 0.0)
+    if fac > 1.0:
+        raise ValueError(f"adapter_conditioning_factor must lie in [0, 1], got {adapter_conditioning_factor!r}")
+    rows = np.zeros((n, 4), dtype=np.float32)
+    with np.errstate(over="ignore"):
+        for i in range(n):
+            rows[i, 0] = c if (i / n >= lo and (i + 1) / n <= hi) else 0.0
+            rows[i, 1] = a if i < int(n * fac) else 0.0
+    if not np.isfinite(rows).all():
+        raise ValueError("a value of the conditioning table is not finite in float32")
+    return rows
+
+
+def guess_mode_weights(n_down) -> np.ndarray:
+    """The per-residual weights of guess mode (diffusers' ``ControlNetModel.forward``): float32 ``logspace(-1, 0, n_down + 1)`` - the
+    ``n_down`` down residuals, then the mid residual at weight 1."""
+    if isinstance(n_down, bool) or not isinstance(n_down, (int, np.integer)) or n_down < 0:
+        raise ValueError(f"n_down must be an int >= 0, got {n_down!r}")
+    w = np.logspace(-1.0, 0.0, int(n_down) + 1).astype(np.float32)
+    w[-1] = 1.0
+    return w
+
+
 MULTISTEP_KINDS = ("unipc", "dpmsolver++")
 
 
@@ -473,9 +537,21 @@ class Sampler:
             step_noise: Optional[torch.Tensor] = None, controlnet_cond: Optional[torch.Tensor] = None,
             adapter_features: Optional[Sequence[torch.Tensor]] = None, pag_scale: float = 0.0, pag_applied_layers=("mid",),
             pag_adaptive_scale: float = 0.0, guidance_interval=None, pag_interval=None, freeu_interval=None, schedule=None,
-            use_graph: bool = True, guidance_scale: float = 1.0, guidance_rescale: float = 0.0,
+            controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0,
+            adapter_conditioning_scale: float = 1.0, adapter_conditioning_factor: float = 1.0, guess_mode: bool = False,
+            conditioning=None, use_graph: bool = True, guidance_scale: float = 1.0, guidance_rescale: float = 0.0,
             uncond_hidden_states: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Advance ``latents`` [B,C,h,w] (f32, updated IN PLACE) through every timestep.
+
+        Conditioning strength: ``controlnet_conditioning_scale`` (the ControlNet residuals times this),
+        ``control_guidance_start`` / ``control_guidance_end`` (fractions of the run outside which the residuals count 0),
+        ``adapter_conditioning_scale`` / ``adapter_conditioning_factor`` (the adapter features times the scale on the first
+        ``int(n * factor)`` steps, 0 afterwards) build a conditioning table with ``conditioning_schedule``; ``conditioning``: an explicit
+        ``[n_steps, 4]`` table (``check_conditioning``) instead of those five.  The captured step reads the strengths from the table, so
+        other values replay the same graph; a step with scale 0 still runs the ControlNet.  ``guess_mode`` (diffusers'): residual k is
+        weighted by ``guess_mode_weights``; under classifier-free guidance the ControlNet then runs on the conditional rows only and the
+        unconditional rows get no residual (``controlnet_cond`` stays [B]).  Not with PAG or tiles.  With none of the seven the call is
+        the one without a table: same launches, same bits.  A table is refused together with a feature cache.
 
         Per-step strengths: ``pag_adaptive_scale`` (the PAG scale decays as ``step_schedule`` states),
         ``guidance_interval`` / ``pag_interval`` / ``freeu_interval`` (``(start, end)`` fractions of the run: outside, that control is
@@ -520,6 +596,10 @@ class Sampler:
         self._pending_schedule = self._build_schedule(schedule, pag_adaptive_scale, guidance_interval, pag_interval, freeu_interval,
                                                       guidance_scale, guidance_rescale, pag_scale, bool(pag_mask),
                                                       uncond_hidden_states is not None)
+        self._pending_conditioning = self._build_conditioning(conditioning, controlnet_conditioning_scale, control_guidance_start,
+                                                              control_guidance_end, adapter_conditioning_scale,
+                                                              adapter_conditioning_factor, guess_mode, bool(pag_mask),
+                                                              bool(adapter_features))
         if pag_mask:
             return self._run_pag(latents, encoder_hidden_states, uncond_hidden_states, lr_latents, step_noise, controlnet_cond,
                                  adapter_features, use_graph, guidance_scale, guidance_rescale, float(pag_scale), pag_mask, plan)
@@ -554,6 +634,46 @@ class Sampler:
         return step_schedule(self._timesteps, guidance_scale=g if has_uncond else 1.0, guidance_rescale=phi, pag_scale=pag_scale,
                              pag_adaptive_scale=ad, guidance_interval=ivs["guidance_interval"], pag_interval=ivs["pag_interval"],
                              freeu=freeu, freeu_interval=ivs["freeu_interval"], num_train_timesteps=self._n_train)
+
+    def _build_conditioning(self, conditioning, c_scale, start, end, a_scale, factor, guess_mode, pag_on, has_features):
+        """(table, guess) of this ``run`` - float32 [n_steps, 4] and a bool - or None: no table, the call of before.  Everything is checked
+        here, before anything is launched."""
+        named = {"controlnet_conditioning_scale": (c_scale, 1.0), "control_guidance_start": (start, 0.0),
+                 "control_guidance_end": (end, 1.0), "adapter_conditioning_scale": (a_scale, 1.0),
+                 "adapter_conditioning_factor": (factor, 1.0)}
+        given = [k for k, (v, d) in named.items() if _finite(k, v) != d]
+        guess = bool(guess_mode)
+        if conditioning is not None:
+            if given:
+                raise ValueError(f"conditioning is an explicit table: it excludes {', '.join(given)}")
+            table = check_conditioning(conditioning, self.n_steps)
+        elif given or guess:
+            table = conditioning_schedule(self.n_steps, c_scale, start, end, a_scale, factor)
+        else:
+            return None
+        if self.controlnet is None and (guess or (table[:, 0] != 1).any()):
+            raise ValueError("controlnet_conditioning_scale / control_guidance_start / control_guidance_end / guess_mode need a sampler "
+                             "with a ControlNet")
+        if not has_features and (table[:, 1] != 1).any():
+            raise ValueError("adapter_conditioning_scale / adapter_conditioning_factor need adapter_features")
+        if guess and pag_on:
+            raise ValueError("guess_mode together with perturbed-attention guidance (pag_scale > 0) is not supported")
+        if guess and getattr(self, "tiles", None) is not None:
+            raise ValueError("guess_mode together with tiles is not supported")
+        if getattr(self, "cache_interval", 1) > 1:
+            raise ValueError("a conditioning table together with a feature cache (interval > 1) is not supported")
+        return table, guess
+
+    def _apply_conditioning(self):
+        """Hands the conditioning table of this run to the library, or clears the one an earlier run left there."""
+        pending, self._pending_conditioning = getattr(self, "_pending_conditioning", None), None
+        if pending is not None:
+            table, guess = pending
+            L.check(L.lib().mrisr_sampler_set_conditioning(self._h, table.ctypes.data_as(C.c_void_p), int(table.shape[0]), 1 if guess else 0))
+            self._conditioned = True
+        elif getattr(self, "_conditioned", False):
+            L.check(L.lib().mrisr_sampler_set_conditioning(self._h, None, 0, 0))
+            self._conditioned = False
 
     def _apply_schedule(self):
         """Hands the table of this run to the library, or clears the one an earlier run left there."""
@@ -614,7 +734,10 @@ class Sampler:
         ehs = (parts[0] if K == 1 else torch.cat(parts)).contiguous()
         lr = lr_latents.to(dev, torch.float32).contiguous() if lr_latents is not None else None
         nz = step_noise.to(dev, torch.float32).contiguous() if step_noise is not None else None
-        cond = rows(controlnet_cond) if controlnet_cond is not None else None
+        # guess mode under classifier-free guidance: the ControlNet sees the conditional rows only, its condition image stays [B]
+        pending = getattr(self, "_pending_conditioning", None)
+        cond_at_B = pending is not None and pending[1] and getattr(entry, "__name__", "") == "mrisr_sampler_run_guided"
+        cond = (controlnet_cond.to(dev).contiguous() if cond_at_B else rows(controlnet_cond)) if controlnet_cond is not None else None
         feats = [rows(f) for f in feats]
         if plan is not None:  # the K B rows, then their tiles: row (b, ti) of the forward is b * T + ti
             ehs, cond, feats = self._tile_operands(plan, latents.shape[2], latents.shape[3], ehs, cond, feats)
@@ -628,6 +751,7 @@ class Sampler:
         if setup is not None:
             setup()
         self._apply_schedule()
+        self._apply_conditioning()
         L.check(entry(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None, C.byref(t_nz) if t_nz else None, C.byref(t_e),
                       C.byref(t_c) if t_c else None, f_arr if feats else None, len(feats), *extra, 1 if use_graph else 0, L.stream_ptr()))
         self._keep = keep
@@ -638,8 +762,9 @@ class Sampler:
 def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weight_dtype, accelerator, fixed_embeds,
                    num_inference_steps=20, adapter=None, solver=None, cache_interval=1, cache_depth=1, tile=None, tile_overlap=0,
                    tile_window="gaussian", pag_scale=0.0, pag_applied_layers=("mid",), freeu=None, pag_adaptive_scale=0.0,
-                   guidance_interval=None, pag_interval=None, freeu_interval=None, guidance_scale=1.0, guidance_rescale=0.0,
-                   uncond_embeds=None):
+                   guidance_interval=None, pag_interval=None, freeu_interval=None, controlnet_conditioning_scale=1.0,
+                   control_guidance_start=0.0, control_guidance_end=1.0, adapter_conditioning_scale=1.0, adapter_conditioning_factor=1.0,
+                   guess_mode=False, guidance_scale=1.0, guidance_rescale=0.0, uncond_embeds=None):
     """Drop-in for the reference's validation sampler (res_srdiff.py:35-105): same inputs, same PIL panel out.
     The timestep loop is one fused sampler call; the per-step noise is drawn up front from the same global RNG
     stream, in the same order, as the reference's per-step ``torch.randn_like`` calls.  ``adapter`` (a T2I-Adapter):
@@ -654,7 +779,10 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     ``freeu``: a ``(s1, s2, b1, b2)`` tuple turns FreeU on (``unet.enable_freeu``) for this validation run; the UNet's previous FreeU
     state is restored afterwards, also on an error.  ``None``: the UNet's own state is used as it is.
     ``pag_adaptive_scale`` / ``guidance_interval`` / ``pag_interval`` / ``freeu_interval``: the per-step strengths of ``Sampler.run``
-    (``step_schedule``); the defaults leave the panel unchanged."""
+    (``step_schedule``); the defaults leave the panel unchanged.
+    ``controlnet_conditioning_scale`` / ``control_guidance_start`` / ``control_guidance_end`` / ``adapter_conditioning_scale`` /
+    ``adapter_conditioning_factor`` / ``guess_mode``: the conditioning strength of ``Sampler.run`` (``conditioning_schedule``); the
+    defaults leave the panel unchanged."""
     from PIL import Image
 
     freeu_vals = None
@@ -703,7 +831,10 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
                     guidance_scale=guidance_scale, guidance_rescale=guidance_rescale,
                     uncond_hidden_states=uncond_embeds[0:1] if uncond_embeds is not None else None, pag_scale=pag_scale,
                     pag_applied_layers=pag_applied_layers, pag_adaptive_scale=pag_adaptive_scale, guidance_interval=guidance_interval,
-                    pag_interval=pag_interval, freeu_interval=freeu_interval)
+                    pag_interval=pag_interval, freeu_interval=freeu_interval,
+                    controlnet_conditioning_scale=controlnet_conditioning_scale, control_guidance_start=control_guidance_start,
+                    control_guidance_end=control_guidance_end, adapter_conditioning_scale=adapter_conditioning_scale,
+                    adapter_conditioning_factor=adapter_conditioning_factor, guess_mode=guess_mode)
     finally:
         if freeu_vals is not None:
             if freeu_prev is None:

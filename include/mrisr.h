@@ -152,6 +152,17 @@ int mrisr_controlnet_forward(mrisr_model* m, const mrisr_tensor* sample, const m
                              mrisr_tensor* down_out, int n_down_out, mrisr_tensor* mid_out, void* stream);
 int mrisr_controlnet_set_cond(mrisr_model* m, const mrisr_tensor* cond, void* stream);
 
+/* ---- a forward on a row window of the planned batch ------------------------------------------------
+ * Rows [row_lo, row_hi) of the batch the handle's workspace is planned for (by a forward, mrisr_model_set_context or a sampler run), in the
+ * same workspace: nothing is planned again, and a full-batch forward afterwards finds its workspace as it left it.  `sample` carries
+ * row_hi - row_lo rows at the planned h, w; the context - and a ControlNet's condition image - are the ones cached for the full batch, read at
+ * the window's rows.  UNet handle: down (n_down tensors, or NULL / 0), mid (or NULL) and the n_intrablock features are inputs that carry the
+ * window's rows; `out` receives the prediction.  ControlNet handle: down (n_skips tensors) and mid are the outputs; no features, out NULL.
+ * A window must not contain perturbed samples (mrisr_model_set_pag), runs the whole network (no feature cache) and is refused while a
+ * training forward is being recorded.  The sampler's reduced steps (mrisr_sampler_set_skip) run through the same path. */
+int mrisr_model_forward_rows(mrisr_model* m, int row_lo, int row_hi, const mrisr_tensor* sample, const mrisr_tensor* timestep, mrisr_tensor* down,
+                             int n_down, mrisr_tensor* mid, const mrisr_tensor* intrablock, int n_intrablock, mrisr_tensor* out, void* stream);
+
 /* ---- T2I-Adapter (Adapter_XL, sk=True) ----------------------------------------------------------- */
 typedef struct {
     int32_t channels[4]; /* 320, 640, 1280, 1280 */
@@ -271,6 +282,21 @@ int mrisr_sampler_run_pag(mrisr_sampler* s, mrisr_tensor* latents, const mrisr_t
                           int use_graph, void* stream);
 /* step graphs this sampler has captured so far (a run whose key matches the previous one captures nothing) */
 int mrisr_sampler_num_captures(const mrisr_sampler* s);
+
+/* ---- skipping neutral steps ---------------------------------------------------------------------
+ * Off by default.  With on != 0 each step of the following runs leaves out what its table rows (mrisr_sampler_set_schedule,
+ * mrisr_sampler_set_conditioning; row i belongs to step i, also under mrisr_sampler_set_range) make neutral:
+ *   - a guided / pag run whose schedule row has g == 1 and s == 0 (pag alone: s == 0; phi does not matter) forwards the B conditional rows
+ *     only - the last B T of the K B T - and takes the reduced step, which writes the new state to every part of the staging buffer;
+ *   - a conditioning row with c == 0 launches neither the ControlNet nor the residual adds;
+ *   - a conditioning row with a == 0 hands the UNet no adapter features.
+ * A run without the table has nothing to skip.  Each of the up to 8 step variants is its own graph, captured the first time a run needs it
+ * from the one step plan (mrisr_sampler_num_captures counts each); other table values with the same neutral pattern replay them.  Refused
+ * together with a feature cache (interval > 1), by either setter.  With on == 0: the launches, bits and captures of a sampler without it. */
+int mrisr_sampler_set_skip(mrisr_sampler* s, int on);
+/* the last run: out = {sum over its steps of the rows of the UNet forward, steps that ran the ControlNet, steps that took adapter features,
+ * distinct step variants} */
+int mrisr_sampler_run_stats(const mrisr_sampler* s, int64_t out[4]);
 
 /* ---- FreeU (Si et al. 2023, "FreeU: Free Lunch in Diffusion U-Net"; the rule of diffusers' apply_freeu / fourier_filter) -----------
  * Off unless mrisr_model_set_freeu turned it on.  It rebalances the two inputs of the first two decoder blocks: the backbone half of the
@@ -768,6 +794,11 @@ int mrisr_op_pag_multistep_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x3
 int mrisr_op_scheduled_step(int step_kind, int K, int pag_alone, mrisr_tensor* x, mrisr_tensor* xK, const mrisr_tensor* epsK, const mrisr_tensor* lr,
                             const mrisr_tensor* noise, mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot,
                             float clip, const float* sched_host, int n_rows, void* stream);
+/* the reduced step (mrisr_sampler_set_skip) alone: as mrisr_op_scheduled_step without a schedule table, eps [B,C,h,w] the conditional
+ * prediction; the new x goes to x and to all K parts of xK [K B,C,h,w], history and corrected state as the guided step writes them. */
+int mrisr_op_reduced_step(int step_kind, int K, mrisr_tensor* x, mrisr_tensor* xK, const mrisr_tensor* eps, const mrisr_tensor* lr,
+                          const mrisr_tensor* noise, mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot,
+                          float clip, void* stream);
 
 /* the fused multistep step (MRISR_STEP_UNIPC / MRISR_STEP_DPMSOLVERPP) alone: x [B,C,h,w] f32 (in place), eps [B,C,h,w], lr or NULL,
  * hist [solver_order][B,C,h,w] f32 (x0 predictions; slot `slot` % solver_order is written, the prediction k steps back is read from

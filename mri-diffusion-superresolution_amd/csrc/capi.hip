@@ -164,6 +164,23 @@ int mrisr_controlnet_forward(mrisr_model* m, const mrisr_tensor* sample, const m
                                  (hipStream_t)stream);
     API_END
 }
+// One forward on the row window [row_lo, row_hi) of the batch the handle's workspace is planned for: `sample` carries the
+// window's rows; the context (ControlNet: and the condition image) is the one cached for the full batch; nothing is planned again.
+// UNet: down / mid (n_down of them, or 0 / NULL) and the features are inputs at the window's rows, `out` the prediction.
+// ControlNet: down / mid are the outputs; no features, no `out`.
+int mrisr_model_forward_rows(mrisr_model* m, int row_lo, int row_hi, const mrisr_tensor* sample, const mrisr_tensor* timestep, mrisr_tensor* down,
+                             int n_down, mrisr_tensor* mid, const mrisr_tensor* intrablock, int n_intrablock, mrisr_tensor* out, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(m && sample && timestep, "null argument");
+    const RowWindow rows{row_lo, row_hi};
+    if (m->is_controlnet) {
+        MRISR_REQUIRE(down && mid && n_intrablock == 0 && !out, "row window: a ControlNet takes its outputs and nothing else");
+        return m->forward_controlnet(sample, timestep, nullptr, nullptr, 1.0f, down, n_down, mid, (hipStream_t)stream, &rows);
+    }
+    MRISR_REQUIRE(out, "row window: a UNet needs its output tensor");
+    return m->forward_unet(sample, timestep, nullptr, down, n_down, mid, intrablock, n_intrablock, out, (hipStream_t)stream, nullptr, &rows);
+    API_END
+}
 int mrisr_controlnet_set_cond(mrisr_model* m, const mrisr_tensor* cond, void* stream) {
     API_BEGIN
     MRISR_REQUIRE(m && cond, "null argument");

@@ -561,6 +561,11 @@ int launch_guided_step(int K, int kind, float* x, float* xK, const float* epsK, 
                        const int* step_idx, float clip, float g, float s, float phi, int B, long long per, hipStream_t st,
                        float* hist = nullptr, float* xc = nullptr, int order = 0, const float* sched = nullptr, int sched_phi = 0,
                        int pag_alone = 0);
+//   the step of a neutral schedule row (g == 1, s == 0) from the conditional prediction alone: eps [B], the new x to the latents and to all
+//   K parts of xK [K B]; history and corrected state as the guided step writes them
+int launch_reduced_step(int K, int kind, float* x, float* xK, const float* eps, const float* lr, const float* noise, const float* coef_table,
+                        const int* step_idx, float clip, int B, long long per, hipStream_t st, float* hist = nullptr, float* xc = nullptr,
+                        int order = 0);
 //   the checks of a host schedule table [n_rows][8] = {g, s, phi, freeu s1, s2, b1, b2, 0}, before any device work: every value finite,
 //   s >= 0, phi in [0, 1], the FreeU values >= 0.  0, or an error code with the message naming the row and the field
 int check_schedule_rows(const float* rows, int n_rows);

@@ -99,6 +99,13 @@ struct CondState {
     float w[32] = {};              // per residual, the mid residual after the down residuals (PLAN_MAX_RES entries)
 };
 
+// A forward on a row window [lo, hi) of the batch the workspace is planned for: `sample` (and every residual and
+// feature) carries hi - lo rows, the persistent per-row buffers - the cross-attention K / V caches of every transformer block, the
+// ControlNet's condition embedding - are read at row lo, and nothing is planned again: ws_gen and ws_key stay as they are.
+struct RowWindow {
+    int lo = 0, hi = 0;
+};
+
 struct Model {
     mrisr_unet_cfg cfg{};
     bool is_controlnet = false;
@@ -138,6 +145,13 @@ struct Model {
     size_t cond_emb_bytes = 0;
     bool ctx_valid = false, cond_valid = false;
     bool keep = false;  // training forward: never release arena temporaries (the backward reads them)
+    // window forward (RowWindow): the rows of the planned batch this forward runs on, set for the duration of the call (win_n == 0: none);
+    // the window sizes whose dry pass has run against workspace generation win_gen (check_window)
+    int win_lo = 0, win_n = 0;
+    std::vector<int> win_sized;
+    unsigned long long win_gen = 0;
+    int check_window(int rows, hipStream_t st);  // dry pass at `rows` rows: tunes its GEMMs, proves (or makes) the arena large enough
+    int enter_window(const RowWindow& rows, int B, int h, int w, int L, hipStream_t st);
     // per-forward state
     float* tproj_out = nullptr;
     // fused sampler: the time embedding of EVERY step of the schedule computed once per run (they depend on the timestep only); the step then
@@ -164,10 +178,11 @@ struct Model {
     int ensure_workspace(int B, int h, int w, int L, hipStream_t st);
     int forward_unet(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,
                      const mrisr_tensor* down_res, int n_down, const mrisr_tensor* mid_res,
-                     const mrisr_tensor* intrablock, int n_intra, mrisr_tensor* out, hipStream_t st, const UNetCache* cache = nullptr);
+                     const mrisr_tensor* intrablock, int n_intra, mrisr_tensor* out, hipStream_t st, const UNetCache* cache = nullptr,
+                     const RowWindow* rows = nullptr);
     int forward_controlnet(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,
                            const mrisr_tensor* cond, float scale, mrisr_tensor* down_out, int n_down,
-                           mrisr_tensor* mid_out, hipStream_t st);
+                           mrisr_tensor* mid_out, hipStream_t st, const RowWindow* rows = nullptr);
     int set_context(const mrisr_tensor* ehs, int B, int h, int w, hipStream_t st);
     int set_cond(const mrisr_tensor* cond, int L, hipStream_t st);
 

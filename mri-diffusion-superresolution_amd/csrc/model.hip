@@ -5,6 +5,7 @@
 #include "model.h"
 #include "runner.h"
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -607,6 +608,9 @@ const HeadBuf& Model::head_buf_for_C(int C) const {
 }
 
 template <typename T>
+static int dry_forward(Model& m, int B, int h, int w, int L, bool with_context, hipStream_t st);
+
+template <typename T>
 static int plan_t(Model& m, int B, int h, int w, int L, hipStream_t st) {
     const mrisr_unet_cfg& c = m.cfg;
     constexpr int BK = 128 / (int)sizeof(T);
@@ -669,6 +673,21 @@ static int plan_t(Model& m, int B, int h, int w, int L, hipStream_t st) {
     m.ctx_valid = false;
     m.cond_valid = false;
     // dry pass -> exact arena size
+    const int rc = dry_forward<T>(m, B, h, w, L, true, st);
+    m.ctx_valid = false;
+    m.cond_valid = false;
+    if (rc) return rc;
+    TRY(m.arena.buf.reserve(m.arena.peak + 4096, false));
+    m.arena.reset();
+    return 0;
+}
+
+// The forward without a launch, on B rows of h x w: leaves the arena's peak in m.arena.peak and plans (bf16: tunes) every GEMM of that
+// shape.  with_context: the context projections and the condition embedding are part of the pass (a plan); without, they count as cached
+// (a row window).  The worst case either way: ControlNet residuals and adapter features present.
+template <typename T>
+static int dry_forward(Model& m, int B, int h, int w, int L, bool with_context, hipStream_t st) {
+    const mrisr_unet_cfg& c = m.cfg;
     m.arena.dry = true;
     m.arena.reset();
     m.arena.peak = 0;
@@ -676,6 +695,7 @@ static int plan_t(Model& m, int B, int h, int w, int L, hipStream_t st) {
     mrisr_tensor sample{}; sample.ndim = 4; sample.dtype = MRISR_F32;
     sample.shape[0] = B; sample.shape[1] = c.in_channels; sample.shape[2] = h; sample.shape[3] = w;
     mrisr_tensor ehs{}; ehs.ndim = 3; ehs.dtype = MRISR_F32; ehs.shape[0] = B; ehs.shape[1] = L; ehs.shape[2] = c.cross_attention_dim;
+    const mrisr_tensor* pe = with_context ? &ehs : nullptr;
     int rc;
     const int ns = m.num_skips();
     std::vector<mrisr_tensor> res(ns + 1);
@@ -692,19 +712,14 @@ static int plan_t(Model& m, int B, int h, int w, int L, hipStream_t st) {
             intra[i] = res[0];
             intra[i].shape[1] = c.block_out_channels[i]; intra[i].shape[2] = h >> i; intra[i].shape[3] = w >> i;
         }
-        rc = r.unet_forward(sample, nullptr, 0, &ehs, res.data(), ns, &res[ns], intra.data(), c.num_levels, out);
-        if (!rc) rc = r.unet_forward(sample, nullptr, 1, &ehs, res.data(), ns, &res[ns], intra.data(), c.num_levels, out);
+        rc = r.unet_forward(sample, nullptr, 0, pe, res.data(), ns, &res[ns], intra.data(), c.num_levels, out);
+        if (!rc) rc = r.unet_forward(sample, nullptr, 1, pe, res.data(), ns, &res[ns], intra.data(), c.num_levels, out);
     } else {
         mrisr_tensor cond = sample; cond.shape[1] = c.cond_channels; cond.shape[2] = 8 * h; cond.shape[3] = 8 * w;
-        rc = r.controlnet_forward(sample, nullptr, 0, &ehs, &cond, 1.0f, res.data(), ns, &res[ns]);
+        rc = r.controlnet_forward(sample, nullptr, 0, pe, with_context ? &cond : nullptr, 1.0f, res.data(), ns, &res[ns]);
     }
     m.arena.dry = false;
-    m.ctx_valid = false;
-    m.cond_valid = false;
-    if (rc) return rc;
-    TRY(m.arena.buf.reserve(m.arena.peak + 4096, false));
-    m.arena.reset();
-    return 0;
+    return rc;
 }
 
 int g_plan_salt = 0;
@@ -734,6 +749,56 @@ int Model::ensure_workspace(int B, int h, int w, int L, hipStream_t st) {
     return 0;
 }
 
+// A window of `rows` rows of the planned batch: one dry pass per (workspace generation, rows).  It plans every GEMM of that shape - the
+// bf16 engine times its candidates there, which must never happen inside a stream capture - and measures the arena's peak.  Most shapes
+// need less than the full batch does, but a smaller M can make the planner split K where the full batch does not, and the slabs of a split
+// are not bounded by the full batch's allocations: so the peak is measured, not assumed, and an arena that is too small is replaced by a
+// larger one.  That moves its base address, so ws_gen is bumped - graphs that baked the old one in are captured again - and nothing else
+// changes: the persistent buffers, ws_key and every planned shape stay.  The arena's own bound check holds in any case.
+int Model::check_window(int rows, hipStream_t st) {
+    MRISR_REQUIRE(finalized && !ws_key.empty() && ws_B > 0, "row window: no planned workspace (run a forward or set the context first)");
+    MRISR_REQUIRE(rows > 0 && rows <= ws_B, "row window: more rows than the planned batch");
+    MRISR_REQUIRE(!keep, "row window: not while a training forward is being recorded");
+    if (win_gen != ws_gen) { win_sized.clear(); win_gen = ws_gen; }
+    for (int r : win_sized) if (r == rows) return 0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    MRISR_CHECK_HIP(hipStreamIsCapturing(st, &cs));
+    MRISR_REQUIRE(cs == hipStreamCaptureStatusNone, "row window: a window of a new size must be sized before the stream is captured");
+    const int lo0 = win_lo, n0 = win_n;
+    const size_t off0 = arena.off, peak0 = arena.peak;
+    win_lo = ws_B - rows; win_n = rows;
+    const int rc = cfg.compute_dtype == MRISR_F32 ? dry_forward<float>(*this, rows, ws_h, ws_w, ctx_len, false, st)
+                                                  : dry_forward<bf16>(*this, rows, ws_h, ws_w, ctx_len, false, st);
+    const size_t need = arena.peak + 4096;
+    win_lo = lo0; win_n = n0;
+    arena.off = off0; arena.peak = std::max(peak0, arena.peak);
+    if (rc) return rc;
+    if (need > arena.buf.bytes) {
+        TRY(arena.buf.reserve(need, false));
+        ++ws_gen;
+        win_gen = ws_gen;
+    }
+    win_sized.push_back(rows);
+    return 0;
+}
+
+// what a window forward needs instead of ensure_workspace (whose key carries the batch, the PAG state and the conditioning row range, none of
+// which a window changes): a planned workspace of the same h, w, L whose batch contains the window.  Leaves win_lo / win_n set
+int Model::enter_window(const RowWindow& rows, int B, int h, int w, int L, hipStream_t st) {
+    MRISR_REQUIRE(finalized && !ws_key.empty(), "row window: no planned workspace (run a forward or set the context first)");
+    MRISR_REQUIRE(rows.lo >= 0 && rows.lo < rows.hi && rows.hi <= ws_B, "row window: [lo, hi) must lie inside the planned batch");
+    MRISR_REQUIRE(B == rows.hi - rows.lo, "row window: the sample must carry hi - lo rows");
+    MRISR_REQUIRE(h == ws_h && w == ws_w && L == ctx_len, "row window: h, w and the context length must be the planned ones");
+    MRISR_REQUIRE(ctx_valid && (!is_controlnet || cond_valid), "row window: the context (and the condition image) must be cached for the full batch");
+    MRISR_REQUIRE(!pag.on() || rows.lo >= pag.first + pag.count || rows.hi <= pag.first, "row window: a window never contains perturbed rows");
+    if (cond.on && !is_controlnet)
+        MRISR_REQUIRE(cond.row_hi == 0 || (cond.row_lo == rows.lo && cond.row_hi == rows.hi),
+                      "row window: the conditioning row range must be the window");
+    TRY(check_window(B, st));
+    win_lo = rows.lo; win_n = B;
+    return 0;
+}
+
 static int check_sample(const Model& m, const mrisr_tensor* s) {
     MRISR_REQUIRE(s && s->ndim == 4 && s->shape[1] == m.cfg.in_channels, "sample must be [B, in_channels, h, w]");
     return 0;
@@ -751,7 +816,8 @@ int Model::build_tproj_table(const long long* ts_dev, int rows, float* scratch, 
 
 int Model::forward_unet(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,
                         const mrisr_tensor* down_res, int n_down, const mrisr_tensor* mid_res,
-                        const mrisr_tensor* intrablock, int n_intra, mrisr_tensor* out, hipStream_t st, const UNetCache* cache) {
+                        const mrisr_tensor* intrablock, int n_intra, mrisr_tensor* out, hipStream_t st, const UNetCache* cache,
+                        const RowWindow* rows) {
     MRISR_REQUIRE(!is_controlnet, "not a UNet handle");
     TRY(check_sample(*this, sample));
     MRISR_REQUIRE(timestep && timestep->dtype == MRISR_I64 && timestep->ndim <= 1, "timestep: device int64, 0-dim or [B]");
@@ -759,8 +825,12 @@ int Model::forward_unet(const mrisr_tensor* sample, const mrisr_tensor* timestep
     const int B = (int)sample->shape[0], h = (int)sample->shape[2], w = (int)sample->shape[3];
     const int L = ehs ? (int)ehs->shape[1] : ctx_len;
     MRISR_REQUIRE(L > 0, "no encoder_hidden_states given and none cached");
+    if (rows) {  // a window never contains perturbed rows, reads the cached context and runs the whole network
+        MRISR_REQUIRE(!ehs, "row window: the context is the cached one (encoder_hidden_states must be null)");
+        MRISR_REQUIRE(!cache || cache->mode == CACHE_NONE, "row window: not together with a feature cache");
+    }
     if (pag.on()) {  // before the plan: nothing is launched for a state this batch cannot honour
-        MRISR_REQUIRE(pag.first + pag.count <= B, "perturbed-attention guidance: the perturbed samples lie outside the batch");
+        MRISR_REQUIRE(rows || pag.first + pag.count <= B, "perturbed-attention guidance: the perturbed samples lie outside the batch");
         MRISR_REQUIRE(!cache || cache->mode == CACHE_NONE, "perturbed-attention guidance together with a feature cache is not supported");
         MRISR_REQUIRE(!keep, "perturbed-attention guidance: not while a training forward is being recorded");
     }
@@ -771,10 +841,15 @@ int Model::forward_unet(const mrisr_tensor* sample, const mrisr_tensor* timestep
     if (cond.on) {  // likewise before the plan
         MRISR_REQUIRE(!keep, "conditioning table: not while a training forward is being recorded");
         MRISR_REQUIRE(cond.table && cond.step, "conditioning table: no table or step counter");
-        MRISR_REQUIRE(cond.row_hi == 0 || (cond.row_lo >= 0 && cond.row_lo < cond.row_hi && cond.row_hi <= B),
+        MRISR_REQUIRE(rows || cond.row_hi == 0 || (cond.row_lo >= 0 && cond.row_lo < cond.row_hi && cond.row_hi <= B),
                       "conditioning table: the row range lies outside the batch");
     }
-    TRY(ensure_workspace(B, h, w, L, st));
+    struct WinGuard {  // win_lo / win_n are this call's: cleared on every exit path
+        Model* m;
+        ~WinGuard() { m->win_lo = m->win_n = 0; }
+    } wguard{this};
+    if (rows) TRY(enter_window(*rows, B, h, w, L, st));
+    else TRY(ensure_workspace(B, h, w, L, st));
     const int t_scalar = timestep->ndim == 0 || timestep->shape[0] == 1;
     MRISR_REQUIRE(t_scalar || timestep->shape[0] == B, "timestep length");
     const long long* t = static_cast<const long long*>(timestep->data);
@@ -795,7 +870,7 @@ int Model::forward_unet(const mrisr_tensor* sample, const mrisr_tensor* timestep
 
 int Model::forward_controlnet(const mrisr_tensor* sample, const mrisr_tensor* timestep, const mrisr_tensor* ehs,
                               const mrisr_tensor* cond, float scale, mrisr_tensor* down_out, int n_down,
-                              mrisr_tensor* mid_out, hipStream_t st) {
+                              mrisr_tensor* mid_out, hipStream_t st, const RowWindow* rows) {
     MRISR_REQUIRE(is_controlnet, "not a ControlNet handle");
     TRY(check_sample(*this, sample));
     MRISR_REQUIRE(timestep && timestep->dtype == MRISR_I64 && timestep->ndim <= 1, "timestep: device int64, 0-dim or [B]");
@@ -804,7 +879,13 @@ int Model::forward_controlnet(const mrisr_tensor* sample, const mrisr_tensor* ti
     MRISR_REQUIRE(L > 0, "no encoder_hidden_states given and none cached");
     if (cond) MRISR_REQUIRE(cond->ndim == 4 && cond->shape[2] == 8 * h && cond->shape[3] == 8 * w, "controlnet_cond must be [B,3,8h,8w]");
     if (this->cond.on) MRISR_REQUIRE(!keep, "conditioning table: not while a training forward is being recorded");
-    TRY(ensure_workspace(B, h, w, L, st));
+    if (rows) MRISR_REQUIRE(!ehs && !cond, "row window: the context and the condition image are the cached ones (both must be null)");
+    struct WinGuard {
+        Model* m;
+        ~WinGuard() { m->win_lo = m->win_n = 0; }
+    } wguard{this};
+    if (rows) TRY(enter_window(*rows, B, h, w, L, st));
+    else TRY(ensure_workspace(B, h, w, L, st));
     const int t_scalar = timestep->ndim == 0 || timestep->shape[0] == 1;
     const long long* t = static_cast<const long long*>(timestep->data);
     if (cfg.compute_dtype == MRISR_F32) {

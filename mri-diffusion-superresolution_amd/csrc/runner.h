@@ -397,7 +397,8 @@ struct Runner {
     // each range one launch on a view of the head buffers offset by whole samples
     int self_attention(const XfW& xw, const HeadBuf& hb, T* ao) {
         const PagState& pg = m.pag;
-        if (!pg.on() || xw.index < 0 || !((pg.mask >> xw.index) & 1u)) return attention(hb, hb.k, hb.vt, hb.N, hb.npad, ao);
+        // (a row window never contains perturbed rows - Model::enter_window - so its attention is the unperturbed one)
+        if (m.win_n || !pg.on() || xw.index < 0 || !((pg.mask >> xw.index) & 1u)) return attention(hb, hb.k, hb.vt, hb.N, hb.npad, ao);
         MRISR_REQUIRE(!m.keep, "perturbed-attention guidance: not while a training forward is being recorded");
         MRISR_REQUIRE(!m.cfg.fp8_attention, "perturbed-attention guidance: not with fp8_attention");
         MRISR_REQUIRE(pg.first >= 0 && pg.first + pg.count <= hb.B, "perturbed-attention guidance: the perturbed samples lie outside the batch");
@@ -447,9 +448,20 @@ struct Runner {
     }
 
     // ---- Transformer2DModel with one BasicTransformerBlock (App. A.4) ----
+    // Row window (Model::win_lo / win_n): the head buffers are per-forward scratch, so the window uses their first
+    // win_n samples; the cross-attention caches are per row of the planned batch, so the window reads them from sample win_lo on
+    HeadBuf window_heads(const HeadBuf& hb) const {
+        HeadBuf v = hb;
+        if (m.win_n) v.B = m.win_n;
+        return v;
+    }
+    const void* window_kv(const void* cache, const HeadBuf& hb) const {
+        return static_cast<const char*>(cache) + (size_t)m.win_lo * hb.H * m.ctx_pad * hb.dpad * sizeof(T);
+    }
+
     int transformer(XfW& xw, const Act& x, Act* out, const Act* pre_normed = nullptr) {
         const int C = xw.C, M = (int)x.rows();
-        const HeadBuf& hb = m.head_buf(x.H * x.W, C);
+        const HeadBuf hb = window_heads(m.head_buf(x.H * x.W, C));
         Act o = new_act(x.B, x.H, x.W, C);
         if (!o.p) return 7;
         const size_t mk = m.arena.mark();
@@ -474,7 +486,7 @@ struct Runner {
             a.w1 = xw.out1.w; a.b1 = xw.out1.b; a.a1 = xw.out1.loraA; a.lb1 = xw.out1.loraB;
             a.ln_g = xw.ln2.g; a.ln_b = xw.ln2.b; a.ln_eps = 1e-5f;
             a.wq = xw.q2p; a.bq = xw.q2.b; a.aq = xw.q2.loraA; a.lbq = xw.q2.loraB;
-            a.kvp = xw.kvp; a.nk = m.ctx_len; a.scale = 1.0f / sqrtf((float)hb.hd);
+            a.kvp = static_cast<const char*>(xw.kvp) + xattn_tail_kv_bytes(m.win_lo); a.nk = m.ctx_len; a.scale = 1.0f / sqrtf((float)hb.hd);
             a.w2 = xw.out2p; a.b2 = xw.out2.b; a.a2 = xw.out2.loraA; a.lb2 = xw.out2.loraB;
             a.lora_r = xw.out1.R ? 4 : 0;
             if (!dry) TRY(launch_xattn_tail(a, st));
@@ -486,7 +498,7 @@ struct Runner {
             heads_args(&g, hb, hb.q, 0, nullptr, 0, nullptr, 0, hb.N, hb.npad);
             TRY(linear(t, M, C, xw.q2, ACT_NONE, nullptr, 0, &g, nullptr, 0, nullptr, &xw.ln2, nrm));
         }
-        TRY(attention(hb, xw.kc, xw.vtc, m.ctx_len, m.ctx_pad, ao));
+        TRY(attention(hb, window_kv(xw.kc, hb), window_kv(xw.vtc, hb), m.ctx_len, m.ctx_pad, ao));
         TRY(linear(ao, M, C, xw.out2, ACT_NONE, t, C, nullptr, t, C));
         }
         // GEGLU feed-forward
@@ -746,6 +758,9 @@ struct Runner {
                      const mrisr_tensor* intrablock, int n_intra, const mrisr_tensor& out, const UNetCache& fc = UNetCache()) {
         m.arena.reset();
         const int B = (int)sample.shape[0];
+        // the rows the ControlNet residuals cover: the conditioning state's range, or - a row window, which that range equals when it is set
+        // (Model::enter_window) - every row of this forward
+        const int res_lo = m.win_n ? 0 : m.cond.row_lo, res_hi = m.win_n ? 0 : m.cond.row_hi;
         // feature cache: the decoder is a flat sequence of n = num_skips() stages, stage q consuming skip n - 1 - q
         const bool store = fc.mode == CACHE_STORE, use = fc.mode == CACHE_USE;
         const int q0 = m.num_skips() - 1 - fc.depth;  // the stage whose input x is cached
@@ -775,10 +790,10 @@ struct Runner {
                 if (!m.cond.on) TRY(add_external(skips[k], down_res[k]));
             }
             // a run with a conditioning table: every down residual in one launch, scaled by w_k * c of the step
-            if (m.cond.on) TRY(cond_add(skips.data(), down_res, m.cond.w, n_down, 0, m.cond.row_lo, m.cond.row_hi));
+            if (m.cond.on) TRY(cond_add(skips.data(), down_res, m.cond.w, n_down, 0, res_lo, res_hi));
         }
         if (!use) TRY(mid(x, &x));
-        if (mid_res && m.cond.on) TRY(cond_add(&x, mid_res, m.cond.w + n_down, 1, 0, m.cond.row_lo, m.cond.row_hi));
+        if (mid_res && m.cond.on) TRY(cond_add(&x, mid_res, m.cond.w + n_down, 1, 0, res_lo, res_hi));
         else if (mid_res) TRY(add_external(x, *mid_res));
         int q = 0;
         for (int i = 0; i < m.cfg.num_levels; ++i) {
@@ -854,7 +869,8 @@ struct Runner {
         Act s, x;
         TRY(import_act(sample, &s, false));
         Act ce;
-        ce.p = m.cond_emb; ce.B = B; ce.H = s.H; ce.W = s.W; ce.C = m.cfg.block_out_channels[0];
+        ce.B = B; ce.H = s.H; ce.W = s.W; ce.C = m.cfg.block_out_channels[0];
+        ce.p = static_cast<char*>(m.cond_emb) + (size_t)m.win_lo * s.H * s.W * ce.C * sizeof(T);  // (a row window: its rows of the embedding)
         TRY(direct(s, m.conv_in, 1, ACT_NONE, &ce, &x));
         std::vector<Act> skips;
         TRY(encoder(x, nullptr, 0, &skips, &x));

@@ -421,6 +421,51 @@ int launch_guided_step(int K, int kind, float* x, float* xK, const float* epsK, 
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
+// ------------------------------------------------------------------------------------------------
+// reduced step: the step of a guided / pag run whose schedule row is neutral (g == 1, s == 0).  The guided
+// prediction of such a row is the conditional one, whatever phi (a prediction rescaled against itself: factor 1), so the forward ran on the
+// conditional rows alone and `eps` is their prediction [B] - the last part of the run's [K B] output buffer.  ONE launch: the update of any
+// step kind through guided_apply4, so the multistep history ring and UniPC's corrected state are written exactly as a guided step writes
+// them, and the new x goes to the caller's latents and to ALL K parts of the staging buffer - the next guided step finds every part
+// current.  float4 pieces, grid-stride; the preconditions of guided_step_kernel.
+// ------------------------------------------------------------------------------------------------
+template <int K>
+__global__ __launch_bounds__(256) void reduced_step_kernel(int kind, float* x, float* xK, const float* eps, const float* lr, const float* noise_base,
+                                                           const float* coef, const int* step, float clip, long long n, MsBuf ms) {
+    const int s = *step;
+    const StepRow r = load_step_row(kind, coef, s);
+    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
+    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256)
+        guided_apply4<K>(kind, r, msrow, ms, s, clip, x, xK, lr, noise, n, i, reinterpret_cast<const float4*>(eps)[i]);
+}
+// eps: [B] (n = B * per floats); xK: [K B]; hist / xc / order as launch_guided_step
+int launch_reduced_step(int K, int kind, float* x, float* xK, const float* eps, const float* lr, const float* noise, const float* coef_table,
+                        const int* step_idx, float clip, int B, long long per, hipStream_t st, float* hist, float* xc, int order) {
+    const std::string who = "reduced step: ";
+    MRISR_REQUIRE(K == 2 || K == 3, who + "2 or 3 parts");
+    MRISR_REQUIRE(kind >= MRISR_STEP_DDIM && kind <= MRISR_STEP_DPMSOLVERPP, who + "unknown step kind");
+    const bool multistep = kind > MRISR_STEP_DDPM;
+    const MsBuf ms{multistep ? hist : nullptr, multistep && kind == MRISR_STEP_UNIPC ? xc : nullptr, multistep ? order : 0};
+    if (multistep) {
+        if (int rc = check_multistep(x, eps, lr, ms, (long long)B * per)) return rc;
+        MRISR_REQUIRE(kind != MRISR_STEP_UNIPC || xc, who + "UniPC needs the corrected-state buffer");
+    }
+    MRISR_REQUIRE(x && xK && eps && coef_table && step_idx && B > 0 && per > 0, who + "null operand");
+    MRISR_REQUIRE(per % 4 == 0 && per < (1ll << 31), who + "the per-sample size must be a multiple of 4");
+    MRISR_REQUIRE(kind != MRISR_STEP_RESSHIFT || lr, who + "Res-SRDiff needs the LR anchor latents");
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    MRISR_REQUIRE(al16(x) && al16(xK) && al16(eps) && al16(lr) && al16(noise), who + "operands must be 16-byte aligned");
+    const long long n = (long long)B * per;
+    if (kind != MRISR_STEP_RESSHIFT && !multistep) lr = nullptr;
+    if (kind == MRISR_STEP_DDIM || multistep) noise = nullptr;
+    // eps once, x in, K + 1 stores of x; multistep: + `order` history reads, one history write, xc in and out
+    ProfScope ps("sampler_step", 0.0, (12.0 + 4.0 * K + (lr ? 4.0 : 0.0) + (multistep ? 4.0 * order + 4.0 + (ms.xc ? 8.0 : 0.0) : 0.0)) * n, st);
+    if (K == 3) hipLaunchKernelGGL(reduced_step_kernel<3>, dim3(nblocks(n >> 2)), dim3(256), 0, st, kind, x, xK, eps, lr, noise, coef_table, step_idx, clip, n, ms);
+    else hipLaunchKernelGGL(reduced_step_kernel<2>, dim3(nblocks(n >> 2)), dim3(256), 0, st, kind, x, xK, eps, lr, noise, coef_table, step_idx, clip, n, ms);
+    MRISR_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 __global__ void advance_step_kernel(int* step) { *step += 1; }
 int launch_advance_step(int* step_idx, hipStream_t st) {
     hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(1), 0, st, step_idx);
@@ -619,13 +664,22 @@ struct mrisr_sampler {
     int tile_h = 0, tile_w = 0, tile_oh = 0, tile_ow = 0, tile_window = MRISR_TILE_GAUSSIAN;
     TilePlan tiles;
     DevBuf d_tiles, d_xt, d_et;
-    hipGraphExec_t exec = nullptr;
-    hipGraphExec_t exec_shallow = nullptr;  // cache_interval > 1: exec is the full + store step, this the shallow one
-    StepPlan plan = new_step_plan();        // what exec / exec_shallow were captured from
+    // skipping (mrisr_sampler_set_skip): each step runs only the rows and networks its table rows need.  variant[i] of
+    // the last run: the STEP_* bits of step i (all zero with the option off); stats: what mrisr_sampler_run_stats reports
+    bool skip = false;
+    std::vector<unsigned char> variant;
+    long long stats[4] = {0, 0, 0, 0};
+    // one graph per step variant, each captured the first time a run needs it; exec[0] is the full step (cache_interval > 1: full + store)
+    hipGraphExec_t exec[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipGraphExec_t exec_shallow = nullptr;  // cache_interval > 1: the shallow step
+    StepPlan plan = new_step_plan();        // what every graph above was captured from
     void drop_graphs() {
-        if (exec) (void)hipGraphExecDestroy(exec);
+        for (hipGraphExec_t& e : exec) {
+            if (e) (void)hipGraphExecDestroy(e);
+            e = nullptr;
+        }
         if (exec_shallow) (void)hipGraphExecDestroy(exec_shallow);
-        exec = exec_shallow = nullptr;
+        exec_shallow = nullptr;
     }
     hipStream_t own_stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
@@ -640,9 +694,11 @@ struct mrisr_sampler {
 // The options that exclude each other, every rule once: the first rule that (UNet state, ControlNet attached, cache interval, tiles on,
 // PAG run) violates, or null.  The setters call it with the value they are about to set, the run with what is set; always before any launch.
 // cond_table / guess: the conditioning table and guess mode of the run (the setters, which do not know the run's table, pass false).
+// skip: the skipping of neutral steps (mrisr_sampler_set_skip).
 static const char* option_conflict(const Model& U, bool has_cnet, int cache_interval, bool tiles_on, bool pag_run, bool cond_table = false,
-                                   bool guess = false) {
+                                   bool guess = false, bool skip = false) {
     const bool cached = cache_interval > 1;
+    if (skip && cached) return "skipping neutral steps together with a feature cache (interval > 1) is not supported";
     if (cond_table && cached) return "conditioning: a conditioning table together with a feature cache (interval > 1) is not supported";
     if (guess && pag_run) return "conditioning: guess mode in a pag run is not supported";
     if (guess && tiles_on) return "conditioning: guess mode together with tiles is not supported";
@@ -769,7 +825,7 @@ int mrisr_sampler_set_cache(mrisr_sampler* s, int interval, int depth) {
     MRISR_REQUIRE(s, "null sampler");
     MRISR_REQUIRE(interval >= 1, "cache interval must be >= 1 (1: no cache)");
     MRISR_REQUIRE(depth >= 1 && depth <= s->unet->num_skips() - 1, "cache depth must lie in 1 .. num_skips - 1");
-    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, interval, s->tile_h != 0, false);
+    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, interval, s->tile_h != 0, false, false, false, s->skip);
     MRISR_REQUIRE(!conflict, conflict);
     if (interval != s->cache_interval || depth != s->cache_depth) s->drop_graphs();  // the next run captures again
     s->cache_interval = interval;
@@ -817,6 +873,24 @@ int mrisr_sampler_set_pag(mrisr_sampler* s, unsigned block_mask, float pag_scale
     return 0;
 }
 int mrisr_sampler_num_captures(const mrisr_sampler* s) { return s ? s->n_captures : 0; }
+
+// Skipping: with `on`, each step of the next runs forwards only the rows and networks its table rows need
+// (step_variant below).  Off (the default): every step is the full one - the launches, bits and captures of a sampler that never had it.
+// The variants share one step plan, so neither value drops a graph.
+int mrisr_sampler_set_skip(mrisr_sampler* s, int on) {
+    MRISR_REQUIRE(s, "null sampler");
+    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, s->cache_interval, s->tile_h != 0, false, false, false, on != 0);
+    MRISR_REQUIRE(!conflict, conflict);
+    s->skip = on != 0;
+    return 0;
+}
+// the last run: {sum over its steps of the UNet forward's rows, steps that ran the ControlNet, steps that took adapter features, distinct
+// step variants}
+int mrisr_sampler_run_stats(const mrisr_sampler* s, int64_t out[4]) {
+    MRISR_REQUIRE(s && out, "null argument");
+    for (int k = 0; k < 4; ++k) out[k] = s->stats[k];
+    return 0;
+}
 
 int mrisr_sampler_set_schedule(mrisr_sampler* s, const float* rows_host, int n_rows) {
     API_BEGIN
@@ -878,6 +952,28 @@ struct RunArgs {
     int n_intrablock, K;
     bool pag;
 };
+// Step variants: what a step may leave out, decided per step on the host from the float32 rows of the run's tables (row i
+// belongs to step i of the schedule, also under set_range); mrisr.step_variants states the same rule in Python.
+//   STEP_REDUCED:  a guided / pag run with a schedule table whose row has g == 1 and s == 0 (pag alone: s == 0; phi does not matter): the forward
+//                  runs on the conditional rows only - the last B T of the K B T - and the reduced step kernel steps from their prediction
+//   STEP_NO_CNET:  a ControlNet and a conditioning table with c == 0: neither the ControlNet forward nor the residual adds are launched
+//   STEP_NO_INTRA: adapter features and a conditioning table with a == 0: the UNet forward gets no features
+// Without the option (or the table) every step is variant 0, the full step.
+enum { STEP_REDUCED = 1, STEP_NO_CNET = 2, STEP_NO_INTRA = 4 };
+static int step_variant(const mrisr_sampler* s, const StepPlan& p, int n_intra, int i) {
+    int v = 0;
+    if (p.d_sched && p.K > 1) {
+        const float* r = &s->sched[8 * (size_t)i];
+        const bool pag_alone = p.pag && p.K == 2;
+        if (r[1] == 0.f && (pag_alone || r[0] == 1.f)) v |= STEP_REDUCED;
+    }
+    if (p.d_cond) {
+        const float* c = &s->cond[4 * (size_t)i];
+        if (p.cnet && c[0] == 0.f) v |= STEP_NO_CNET;
+        if (n_intra > 0 && c[1] == 0.f) v |= STEP_NO_INTRA;
+    }
+    return v;
+}
 static long long numel(const mrisr_tensor* t) { long long k = 1; for (int i = 0; i < t->ndim; ++i) k *= t->shape[i]; return k; }
 static mrisr_tensor plan_tensor(const PlanTensor& t, int cdt) {
     mrisr_tensor m{};
@@ -902,7 +998,7 @@ static int run_check(mrisr_sampler* s, const RunArgs& a, StepPlan& p) {
         MRISR_REQUIRE(s->pag_mask != 0, "pag run: no applied block (mrisr_sampler_set_pag)");
     }
     const bool ctab = !s->cond.empty(), guess = ctab && s->cond_guess;
-    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, s->cache_interval, s->tile_h != 0, pag, ctab, guess);
+    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, s->cache_interval, s->tile_h != 0, pag, ctab, guess, s->skip);
     MRISR_REQUIRE(!conflict, conflict);
     Model& U = *s->unet;
     if (ctab) {  // the table only supplies values: one this run cannot honour is refused
@@ -1082,6 +1178,13 @@ static int run_operands(mrisr_sampler* s, const RunArgs& a, StepPlan& p, hipStre
         else TRY(launch_nchw_to_nhwc<bf16>(f.data, f.dtype, s->intra_bufs[i]->p, (int)f.shape[0], (int)f.shape[1], (int)f.shape[2], (int)f.shape[3], st));
         p.intra[i].data = s->intra_bufs[i]->p;
     }
+    // reduced steps forward a row window of the planned batch: its shapes are sized (bf16: tuned) here, before anything is captured
+    bool any_reduced = false;
+    for (int i = s->first; i < s->last; ++i) any_reduced |= (s->variant[i] & STEP_REDUCED) != 0;
+    if (any_reduced) {
+        TRY(U.check_window(p.B * p.T, st));
+        if (s->cnet && !(p.cnet_rows && p.cnet_rows != FB)) TRY(s->cnet->check_window(p.B * p.T, st));
+    }
     p.ws_gen_unet = U.ws_gen;
     p.ws_gen_cnet = s->cnet ? s->cnet->ws_gen : 0ull;
     return 0;
@@ -1172,19 +1275,28 @@ static int run_temb_table(mrisr_sampler* s, StepPlan& p, hipStream_t st) {
 
 // ONE step: everything here comes from the plan (C: the ControlNet when p.cnet).  Workspaces are planned (set_context in run_operands), so
 // a captured body performs launches only.
-static int step_body(const StepPlan& p, Model& U, Model* C, int cache_mode, hipStream_t st) {
+// variant: the STEP_* bits of this step.  A reduced step runs everything on the row window [FB - B T, FB) of the planned batch: the last part of
+// the staging buffer, of the tile batch and of d_eps.
+static int step_body(const StepPlan& p, Model& U, Model* C, int cache_mode, int variant, hipStream_t st) {
     const int NB = p.K * p.B, FB = NB * p.T;
     const long long per = (long long)p.C * p.h * p.w, n = (long long)p.B * per;
     const bool tiled = p.T > 1;
+    const bool reduced = (variant & STEP_REDUCED) != 0, with_cnet = p.cnet && !(variant & STEP_NO_CNET);
+    const int n_intra = (variant & STEP_NO_INTRA) ? 0 : p.n_intra;
+    MRISR_REQUIRE(!reduced || (p.K > 1 && cache_mode == CACHE_NONE), "reduced step: a guided or pag run without a feature cache");
+    const int WB = reduced ? p.B * p.T : FB;   // rows of this step's forwards
+    const RowWindow win{FB - WB, FB};
+    const size_t win_off = (size_t)win.lo * p.C * p.fh * p.fw;  // the window's first element in a [FB, C, fh, fw] buffer
+    const size_t part_off = reduced ? (size_t)(p.K - 1) * n : 0;  // ... and in a [K B, C, h, w] canvas buffer (the same number when not tiled)
     mrisr_tensor tt{};
     tt.data = p.d_curt; tt.dtype = MRISR_I64; tt.ndim = 0;
     const float* canvas = p.K > 1 ? p.d_x2 : p.x;  // [NB, C, h, w]: what the forwards read, or what a tiled step gathers from
     mrisr_tensor xin{};                            // what the forwards read
-    xin.data = tiled ? p.d_xt : const_cast<float*>(canvas);
+    xin.data = (tiled ? p.d_xt : const_cast<float*>(canvas)) + win_off;
     xin.dtype = MRISR_F32; xin.layout = MRISR_NCHW; xin.ndim = 4;
-    xin.shape[0] = FB; xin.shape[1] = p.C; xin.shape[2] = p.fh; xin.shape[3] = p.fw;
+    xin.shape[0] = WB; xin.shape[1] = p.C; xin.shape[2] = p.fh; xin.shape[3] = p.fw;
     mrisr_tensor eps_t = xin;
-    eps_t.data = tiled ? p.d_et : p.d_eps;
+    eps_t.data = (tiled ? p.d_et : p.d_eps) + win_off;
     TileGrid tg;
     if (tiled) {
         tg.H = p.h; tg.W = p.w; tg.th = p.fh; tg.tw = p.fw; tg.ky = p.tile_ky; tg.kx = p.tile_kx;
@@ -1192,26 +1304,41 @@ static int step_body(const StepPlan& p, Model& U, Model* C, int cache_mode, hipS
         tg.vec4 = p.tile_vec4 != 0;
     }
     mrisr_tensor res[PLAN_MAX_RES], intra[PLAN_MAX_INTRA];
-    for (int k = 0; k <= p.n_res && p.cnet; ++k) res[k] = plan_tensor(p.res[k], p.cdt);
-    for (int i = 0; i < p.n_intra; ++i) intra[i] = plan_tensor(p.intra[i], p.cdt);
+    for (int k = 0; k <= p.n_res && p.cnet; ++k) {
+        res[k] = plan_tensor(p.res[k], p.cdt);
+        if (reduced) res[k].shape[0] = WB;  // the residuals of the window's rows, at the head of each buffer
+    }
+    for (int i = 0; i < n_intra; ++i) {
+        intra[i] = plan_tensor(p.intra[i], p.cdt);
+        if (reduced) {  // the features of the window's rows
+            const PlanTensor& f = p.intra[i];
+            intra[i].shape[0] = WB;
+            intra[i].data = static_cast<char*>(intra[i].data) + (size_t)win.lo * f.shape[1] * f.shape[2] * f.shape[3] * dtype_size(p.cdt);
+        }
+    }
     UNetCache fc;
     fc.mode = cache_mode; fc.depth = p.cache_depth; fc.p = p.d_cache;
 
     hipLaunchKernelGGL(load_t_kernel, dim3(1), dim3(1), 0, st, p.d_curt, p.d_ts, static_cast<const int*>(p.d_step));
-    if (tiled) TRY(launch_tile_gather(canvas, p.d_xt, tg, NB, p.C, st));
-    if (p.cnet) {
+    // (a reduced tiled step gathers from the last part of the staging buffer only, and blends into the window of d_eps)
+    if (tiled) TRY(launch_tile_gather(canvas + part_off, p.d_xt + win_off, tg, reduced ? p.B : NB, p.C, st));
+    if (with_cnet) {
         mrisr_tensor cin = xin;
-        if (p.cnet_rows && p.cnet_rows != FB) {  // guess mode under classifier-free guidance: the last B rows of the staging buffer
+        const bool cond_rows = p.cnet_rows && p.cnet_rows != FB;  // guess mode under classifier-free guidance: the ControlNet is planned for, and
+        if (cond_rows) {                                          // runs on, the last B rows of the staging buffer - a reduced step's window
             cin.shape[0] = p.cnet_rows;
             cin.data = const_cast<float*>(canvas) + (size_t)(FB - p.cnet_rows) * per;
         }
-        TRY(C->forward_controlnet(&cin, &tt, nullptr, nullptr, 1.0f, res, p.n_res, &res[p.n_res], st));
+        TRY(C->forward_controlnet(&cin, &tt, nullptr, nullptr, 1.0f, res, p.n_res, &res[p.n_res], st, reduced && !cond_rows ? &win : nullptr));
     }
-    TRY(U.forward_unet(&xin, &tt, nullptr, p.cnet ? res : nullptr, p.n_res, p.cnet ? &res[p.n_res] : nullptr, intra, p.n_intra, &eps_t, st,
-                       p.cached ? &fc : nullptr));
-    if (tiled) TRY(launch_tile_blend(p.d_et, p.d_eps, tg, NB, p.C, st));
+    TRY(U.forward_unet(&xin, &tt, nullptr, with_cnet ? res : nullptr, with_cnet ? p.n_res : 0, with_cnet ? &res[p.n_res] : nullptr, intra, n_intra,
+                       &eps_t, st, p.cached ? &fc : nullptr, reduced ? &win : nullptr));
+    if (tiled) TRY(launch_tile_blend(p.d_et + win_off, p.d_eps + part_off, tg, reduced ? p.B : NB, p.C, st));
     const bool multistep = p.kind > MRISR_STEP_DDPM;
-    if (p.K > 1) {
+    if (reduced) {
+        TRY(launch_reduced_step(p.K, p.kind, p.x, p.d_x2, p.d_eps + part_off, p.lr, p.noise, p.d_coef, p.d_step, p.clip, p.B, per, st, p.hist, p.xc,
+                                p.order));
+    } else if (p.K > 1) {
         // K = 3: [eps_p; eps_u; eps_c].  K = 2 of a pag run: [eps_p; eps_c], the guided step with eps_u := eps_p and g := 1 + s
         // with a schedule table the kernel reads the three scalars from row *d_step (and forms 1 + s itself): the plan holds zeros for them
         const bool pag_alone = p.pag && p.K == 2;
@@ -1229,34 +1356,57 @@ static int step_body(const StepPlan& p, Model& U, Model* C, int cache_mode, hipS
     return launch_advance_step(p.d_step, st);
 }
 
-// capture and replay: the stored graphs serve this run exactly when they were captured from an equal plan
+// capture and replay: the stored graphs serve this run exactly when they were captured from an equal plan.  One graph per step variant (and,
+// with a feature cache, the shallow step), each captured the first time a run needs it - all of them before the run's first launch - from the
+// same plan; which one a step replays is decided here, on the host.
 static int run_steps(mrisr_sampler* s, const StepPlan& p, int use_graph, hipStream_t st) {
     Model& U = *s->unet;
     const bool cached = p.cached != 0;
     auto mode_of = [&](int i) { return !cached ? CACHE_NONE : ((i - s->first) % s->cache_interval == 0 ? CACHE_STORE : CACHE_USE); };
+    const int FB = p.K * p.B * p.T;
+    unsigned used = 0;
+    for (int k = 0; k < 4; ++k) s->stats[k] = 0;
+    for (int i = s->first; i < s->last; ++i) {
+        const int v = s->variant[i];
+        used |= 1u << v;
+        s->stats[0] += (v & STEP_REDUCED) ? p.B * p.T : FB;
+        s->stats[1] += p.cnet && !(v & STEP_NO_CNET) ? 1 : 0;
+        s->stats[2] += p.n_intra > 0 && !(v & STEP_NO_INTRA) ? 1 : 0;
+    }
+    for (int v = 0; v < 8; ++v) s->stats[3] += (used >> v) & 1u;
     if (!use_graph) {
-        for (int i = s->first; i < s->last; ++i) TRY(step_body(p, U, s->cnet, mode_of(i), st));
+        for (int i = s->first; i < s->last; ++i) TRY(step_body(p, U, s->cnet, mode_of(i), s->variant[i], st));
         return 0;
     }
-    if (!s->exec || (cached && !s->exec_shallow) || !same_plan(s->plan, p)) {
+    if (!same_plan(s->plan, p)) {
         s->drop_graphs();
-        auto capture = [&](int cache_mode, hipGraphExec_t* exec) -> int {
-            hipGraph_t graph = nullptr;
-            MRISR_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            int rc = step_body(p, U, s->cnet, cache_mode, st);
-            hipError_t e = hipStreamEndCapture(st, &graph);
-            if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-            MRISR_CHECK_HIP(e);
-            MRISR_CHECK_HIP(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(graph);
-            ++s->n_captures;
-            return 0;
-        };
-        TRY(capture(cached ? CACHE_STORE : CACHE_NONE, &s->exec));
-        if (cached) TRY(capture(CACHE_USE, &s->exec_shallow));
-        s->plan = p;
+        s->plan = p;  // (now, not after the captures: a graph that exists was captured from s->plan, also when a capture below fails)
     }
-    for (int i = s->first; i < s->last; ++i) MRISR_CHECK_HIP(hipGraphLaunch(mode_of(i) == CACHE_USE ? s->exec_shallow : s->exec, st));
+    auto capture = [&](int cache_mode, int variant, hipGraphExec_t* exec) -> int {
+        hipGraph_t graph = nullptr;
+        MRISR_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        int rc = step_body(p, U, s->cnet, cache_mode, variant, st);
+        hipError_t e = hipStreamEndCapture(st, &graph);
+        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+        MRISR_CHECK_HIP(e);
+        MRISR_CHECK_HIP(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
+        (void)hipGraphDestroy(graph);
+        ++s->n_captures;
+        return 0;
+    };
+    if (cached) {  // both steps of a cached run, whatever its length: a change of range replays them
+        if (!s->exec[0] || !s->exec_shallow) {
+            s->drop_graphs();
+            TRY(capture(CACHE_STORE, 0, &s->exec[0]));
+            TRY(capture(CACHE_USE, 0, &s->exec_shallow));
+        }
+    } else {
+        if (s->first == s->last && !s->exec[0]) TRY(capture(CACHE_NONE, 0, &s->exec[0]));  // (an empty range captures the full step, as ever)
+        for (int i = s->first; i < s->last; ++i)  // in the order of first use
+            if (!s->exec[s->variant[i]]) TRY(capture(CACHE_NONE, s->variant[i], &s->exec[s->variant[i]]));
+    }
+    for (int i = s->first; i < s->last; ++i)
+        MRISR_CHECK_HIP(hipGraphLaunch(mode_of(i) == CACHE_USE ? s->exec_shallow : s->exec[s->variant[i]], st));
     return 0;
 }
 
@@ -1264,6 +1414,8 @@ static int sampler_run_impl(mrisr_sampler* s, const RunArgs& a, int use_graph, v
     API_BEGIN
     StepPlan p = new_step_plan();
     TRY(run_check(s, a, p));
+    s->variant.assign(s->n_steps, 0);
+    for (int i = s->first; i < s->last && s->skip; ++i) s->variant[i] = (unsigned char)step_variant(s, p, a.n_intrablock, i);
     hipStream_t user = (hipStream_t)stream;
     hipStream_t st = user;
     if (use_graph && user == nullptr) {
@@ -1338,10 +1490,12 @@ static int sampler_run_impl(mrisr_sampler* s, const RunArgs& a, int use_graph, v
 // ---- the single-step test entries: one static helper behind the four.  K = 1: the plain multistep step; K = 2 / 3: the guided / three-way
 // step on caller buffers xK / epsK [K B].  row_host holds `width` floats (this step kind's row), placed at row `slot` of a zeroed table; the
 // kernel sees the step counter `slot`.  hist / xc: the multistep kinds' ring and corrected state.  sched_host (K > 1): a schedule table of
-// n_rows rows, uploaded; the kernel reads {g, s, phi} from its row `slot` and g / sp / phi are not read.
+// n_rows rows, uploaded; the kernel reads {g, s, phi} from its row `slot` and g / sp / phi are not read.  reduced (K > 1): the reduced step -
+// epsK is the conditional prediction alone, [B].
 static int op_step(const char* who, int K, int step_kind, mrisr_tensor* x, mrisr_tensor* xK, const mrisr_tensor* epsK, const mrisr_tensor* lr,
                    const mrisr_tensor* noise, const float* row_host, int width, int slot, mrisr_tensor* hist, mrisr_tensor* xc, int solver_order,
-                   float clip, float g, float sp, float phi, void* stream, const float* sched_host = nullptr, int n_rows = 0, int pag_alone = 0) {
+                   float clip, float g, float sp, float phi, void* stream, const float* sched_host = nullptr, int n_rows = 0, int pag_alone = 0,
+                   bool reduced = false) {
     const std::string w = std::string(who) + ": ", sK = std::to_string(K);
     const std::string eps_name = K == 3 ? "eps3" : (K == 2 ? "eps2" : "eps");
     const bool multistep = hist != nullptr;
@@ -1349,7 +1503,8 @@ static int op_step(const char* who, int K, int step_kind, mrisr_tensor* x, mrisr
     const int B = (int)x->shape[0];
     const long long n = numel(x), per = n / B;
     if (multistep) MRISR_REQUIRE(per % 4 == 0, w + "C*h*w must be a multiple of 4");
-    MRISR_REQUIRE(epsK->dtype == MRISR_F32 && numel(epsK) == K * n, w + eps_name + " must be f32 [" + (K > 1 ? sK : "") + "B, C, h, w]");
+    if (reduced) MRISR_REQUIRE(epsK->dtype == MRISR_F32 && numel(epsK) == n, w + "eps must be f32 [B, C, h, w]: the conditional prediction");
+    else MRISR_REQUIRE(epsK->dtype == MRISR_F32 && numel(epsK) == K * n, w + eps_name + " must be f32 [" + (K > 1 ? sK : "") + "B, C, h, w]");
     if (xK) MRISR_REQUIRE(xK->dtype == MRISR_F32 && numel(xK) == K * n, w + "the staging buffer must be f32 [" + sK + "B, C, h, w]");
     if (lr) MRISR_REQUIRE(lr->dtype == MRISR_F32 && numel(lr) == n, w + "lr must be f32 [B, C, h, w]");
     // (the kernel reads slab `slot` of the noise: the single-slab entries run at slot 0, the scheduled one hands in slot + 1 slabs)
@@ -1377,7 +1532,11 @@ static int op_step(const char* who, int K, int step_kind, mrisr_tensor* x, mrisr
     }
     float* h = hist ? (float*)hist->data : nullptr;
     float* c = xc ? (float*)xc->data : nullptr;
-    if (K > 1)
+    if (reduced)
+        TRY(launch_reduced_step(K, step_kind, (float*)x->data, (float*)xK->data, (const float*)epsK->data, lr ? (const float*)lr->data : nullptr,
+                                noise ? (const float*)noise->data : nullptr, (const float*)d_rows.p, (const int*)d_step.p, clip, B, per, st, h, c,
+                                solver_order));
+    else if (K > 1)
         TRY(launch_guided_step(K, step_kind, (float*)x->data, (float*)xK->data, (const float*)epsK->data, lr ? (const float*)lr->data : nullptr,
                                noise ? (const float*)noise->data : nullptr, (const float*)d_rows.p, (const int*)d_step.p, clip, g, sp, phi, B, per,
                                st, h, c, solver_order, (const float*)d_sched.p, sched_phi, pag_alone));
@@ -1483,4 +1642,25 @@ int mrisr_op_scheduled_step(int step_kind, int K, int pag_alone, mrisr_tensor* x
     API_END
 }
 
+// the reduced step alone (parity test): the step of any kind from the conditional prediction eps [B] on caller buffers at
+// step counter `slot`, the new x to x and to all K parts of xK [K B].  row_host, hist, xc, solver_order, noise: as mrisr_op_scheduled_step
+int mrisr_op_reduced_step(int step_kind, int K, mrisr_tensor* x, mrisr_tensor* xK, const mrisr_tensor* eps, const mrisr_tensor* lr,
+                          const mrisr_tensor* noise, mrisr_tensor* hist, mrisr_tensor* xc, const float* row_host, int solver_order, int slot,
+                          float clip, void* stream) {
+    API_BEGIN
+    MRISR_REQUIRE(x && xK && eps && row_host, "reduced step: null argument");
+    MRISR_REQUIRE(step_kind >= MRISR_STEP_DDIM && step_kind <= MRISR_STEP_DPMSOLVERPP, "reduced step: unknown step kind");
+    MRISR_REQUIRE(K == 2 || K == 3, "reduced step: 2 or 3 parts");
+    MRISR_REQUIRE(slot >= 0 && slot < 1024, "reduced step: slot 0..1023");
+    const bool multistep = step_kind > MRISR_STEP_DDPM;
+    if (multistep) {
+        MRISR_REQUIRE(hist && !noise, "reduced step: the multistep kinds take the history ring and no noise");
+        MRISR_REQUIRE(solver_order >= 1 && solver_order <= 3, "reduced step: solver order 1..3");
+        MRISR_REQUIRE((step_kind == MRISR_STEP_UNIPC) == (xc != nullptr), "reduced step: the corrected-state buffer belongs to UniPC");
+    } else
+        MRISR_REQUIRE(!hist && !xc, "reduced step: hist / xc belong to the multistep kinds");
+    return op_step("reduced step", K, step_kind, x, xK, eps, lr, noise, row_host, multistep ? 16 : row_width(step_kind), slot,
+                   multistep ? hist : nullptr, multistep ? xc : nullptr, multistep ? solver_order : 0, clip, 0.f, 0.f, 0.f, stream, nullptr, 0, 0, true);
+    API_END
+}
 }  // extern "C"

@@ -66,6 +66,7 @@ EXPORTS = [
     "mrisr_model_set_freeu", "mrisr_op_freeu",
     "mrisr_sampler_set_schedule", "mrisr_op_scheduled_step", "mrisr_op_freeu_scheduled",
     "mrisr_sampler_set_conditioning", "mrisr_op_cond_add",
+    "mrisr_model_forward_rows", "mrisr_sampler_set_skip", "mrisr_sampler_run_stats", "mrisr_op_reduced_step",
     "mrisr_tile_tables", "mrisr_sampler_set_tiles", "mrisr_op_tile_gather", "mrisr_op_tile_blend",
     "mrisr_adapter_train_prepare", "mrisr_adapter_train_num_trainable", "mrisr_adapter_train_num_tensors",
     "mrisr_adapter_train_tensor_info", "mrisr_adapter_train_bind", "mrisr_adapter_train_refresh", "mrisr_adapter_backward", "mrisr_adapter_backward_level", "mrisr_adapter_train_level_range",
@@ -153,6 +154,10 @@ def lib() -> C.CDLL:
         L.mrisr_op_freeu_scheduled.argtypes = [I, P, P, P, P, I, I, I, I, I, I, P, I, I, P]
         L.mrisr_sampler_set_conditioning.argtypes = [P, P, I, I]
         L.mrisr_op_cond_add.argtypes = [I, I, P, P, P, P, P, I, I, I, I, I, P]
+        L.mrisr_model_forward_rows.argtypes = [P, I, I, P, P, P, I, P, P, I, P, P]
+        L.mrisr_sampler_set_skip.argtypes = [P, I]
+        L.mrisr_sampler_run_stats.argtypes = [P, P]
+        L.mrisr_op_reduced_step.argtypes = [I, I, P, P, P, P, P, P, P, P, I, I, F, P]
         L.mrisr_resize_scratch_bytes.restype = C.c_size_t
         L.mrisr_resize_scratch_bytes.argtypes = [C.c_int] * 6
         L.mrisr_resize_slices.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -17,6 +17,7 @@ import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -221,6 +222,25 @@ def _c_cfg(cfg: UNetConfig, compute_dtype, lora_rank, lora_fused, flash, fp8=Fal
     return c
 
 
+def _check_rows(rows, batch: int, has_context: bool):
+    """The ``rows=(lo, hi)`` argument of a window forward, on numbers alone: None, or two ints with ``0 <= lo < hi`` and ``hi - lo`` the
+    sample's batch; the context arguments must be absent.  Whether the window lies inside the planned batch is the library's check."""
+    if rows is None:
+        return None
+    try:
+        lo, hi = rows
+    except (TypeError, ValueError):
+        raise ValueError(f"rows must be a (lo, hi) pair of ints, got {rows!r}") from None
+    for v in (lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"rows must be a (lo, hi) pair of ints, got {rows!r}")
+    if not 0 <= lo < hi or hi - lo != batch:
+        raise ValueError(f"rows=(lo, hi) must satisfy 0 <= lo < hi with hi - lo the sample's batch {batch}, got {rows!r}")
+    if has_context:
+        raise ValueError("rows=(lo, hi): the context is the one cached for the full batch; encoder_hidden_states (and controlnet_cond) must be None")
+    return int(lo), int(hi)
+
+
 class _DeviceModel:
     """Shared plumbing: handle lifetime, state-dict <-> C ABI, timestep marshalling."""
     _create = None
@@ -365,13 +385,18 @@ class UNet2DConditionModel(_DeviceModel):
                  down_block_additional_residuals: Optional[Sequence[torch.Tensor]] = None,
                  mid_block_additional_residual: Optional[torch.Tensor] = None,
                  down_intrablock_additional_residuals: Optional[Sequence[torch.Tensor]] = None,
-                 return_dict: bool = True, **_unused):
+                 return_dict: bool = True, rows: Optional[Tuple[int, int]] = None, **_unused):
+        """``rows=(lo, hi)``: a forward on the row window [lo, hi) of the batch the workspace is planned for (by an earlier forward or
+        ``set_context``).  ``sample`` and every residual and feature carry the window's ``hi - lo`` rows,
+        ``encoder_hidden_states`` must be None - the context is the one cached for the full batch, read at the window's rows - and nothing
+        is planned again: a full-batch forward afterwards finds its workspace as it left it."""
         if not self._finalized:
             raise L.MrisrError("load_state_dict() first")
         if sample.ndim != 4 or sample.shape[1] != self.config.in_channels:
             raise ValueError(f"sample must be [B,{self.config.in_channels},h,w]; got {tuple(sample.shape)}")
         sample = sample.to(self.device).contiguous()
         B = sample.shape[0]
+        rows = _check_rows(rows, B, encoder_hidden_states is not None)
         t = self._timestep(timestep, B)
         ehs = encoder_hidden_states.to(self.device).contiguous() if encoder_hidden_states is not None else None
         down = [r.to(self.device).contiguous() for r in (down_block_additional_residuals or [])]
@@ -384,6 +409,11 @@ class UNet2DConditionModel(_DeviceModel):
         t_s, t_t, t_o = L.as_tensor(sample), L.as_tensor(t), L.as_tensor(out)
         t_e = L.as_tensor(ehs) if ehs is not None else None
         t_m = L.as_tensor(mid) if mid is not None else None
+        if rows is not None:
+            L.check(L.lib().mrisr_model_forward_rows(self._h, rows[0], rows[1], C.byref(t_s), C.byref(t_t), d_arr if down else None, len(down),
+                                                     C.byref(t_m) if t_m else None, i_arr if intra else None, len(intra), C.byref(t_o),
+                                                     L.stream_ptr()))
+            return _Output(out) if return_dict else (out,)
         L.check(L.lib().mrisr_unet_forward(self._h, C.byref(t_s), C.byref(t_t), C.byref(t_e) if t_e else None,
                                            d_arr if down else None, len(down), C.byref(t_m) if t_m else None,
                                            i_arr if intra else None, len(intra), C.byref(t_o), L.stream_ptr()))
@@ -474,11 +504,17 @@ class ControlNetModel(_DeviceModel):
 
     def __call__(self, sample: torch.Tensor, timestep, encoder_hidden_states: Optional[torch.Tensor] = None,
                  controlnet_cond: Optional[torch.Tensor] = None, conditioning_scale: float = 1.0,
-                 return_dict: bool = True, **_unused):
+                 return_dict: bool = True, rows: Optional[Tuple[int, int]] = None, **_unused):
+        """``rows=(lo, hi)``: a forward on the row window [lo, hi) of the planned batch, as ``UNet2DConditionModel``'s: ``sample`` carries the
+        window's rows, ``encoder_hidden_states`` and ``controlnet_cond`` must be None (both are the ones cached for the full batch) and
+        ``conditioning_scale`` 1."""
         if not self._finalized:
             raise L.MrisrError("load_state_dict() first")
         sample = sample.to(self.device).contiguous()
         B, _, h, w = sample.shape
+        rows = _check_rows(rows, B, encoder_hidden_states is not None or controlnet_cond is not None)
+        if rows is not None and conditioning_scale != 1.0:
+            raise ValueError("rows=(lo, hi): conditioning_scale must be 1")
         t = self._timestep(timestep, B)
         ehs = encoder_hidden_states.to(self.device).contiguous() if encoder_hidden_states is not None else None
         cond = controlnet_cond.to(self.device).contiguous() if controlnet_cond is not None else None
@@ -491,9 +527,13 @@ class ControlNetModel(_DeviceModel):
         t_s, t_t = L.as_tensor(sample), L.as_tensor(t)
         t_e = L.as_tensor(ehs) if ehs is not None else None
         t_c = L.as_tensor(cond) if cond is not None else None
-        L.check(L.lib().mrisr_controlnet_forward(self._h, C.byref(t_s), C.byref(t_t), C.byref(t_e) if t_e else None,
-                                                 C.byref(t_c) if t_c else None, C.c_float(conditioning_scale), d_arr,
-                                                 len(outs) - 1, C.byref(t_mid), L.stream_ptr()))
+        if rows is not None:
+            L.check(L.lib().mrisr_model_forward_rows(self._h, rows[0], rows[1], C.byref(t_s), C.byref(t_t), d_arr, len(outs) - 1, C.byref(t_mid),
+                                                     None, 0, None, L.stream_ptr()))
+        else:
+            L.check(L.lib().mrisr_controlnet_forward(self._h, C.byref(t_s), C.byref(t_t), C.byref(t_e) if t_e else None,
+                                                     C.byref(t_c) if t_c else None, C.c_float(conditioning_scale), d_arr,
+                                                     len(outs) - 1, C.byref(t_mid), L.stream_ptr()))
         if return_dict:
             return _ControlNetOutput(outs[:-1], outs[-1])
         return outs[:-1], outs[-1]

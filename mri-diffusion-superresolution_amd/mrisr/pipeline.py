@@ -10,7 +10,7 @@ plus ``sample`` - the timestep loop itself (``:63-96``) as ONE call into the C-A
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -292,6 +292,73 @@ def conditioning_schedule(n_steps, controlnet_conditioning_scale=1.0, control_gu
     return rows
 
 
+STEP_REDUCED, STEP_NO_CONTROLNET, STEP_NO_FEATURES = 1, 2, 4
+
+
+def step_variants(schedule, conditioning, K, has_controlnet=False, n_features=0, pag=False, n_steps=None) -> List[int]:
+    """What each step of a run with ``Sampler.run(skip_neutral=True)`` leaves out: one small int per step, a
+    sum of ``STEP_REDUCED`` (1), ``STEP_NO_CONTROLNET`` (2) and ``STEP_NO_FEATURES`` (4); 0 is the full step.  Pure Python on the CPU;
+    the library applies the same rule to the same float32 rows.  Row i belongs to step i of the schedule, also under ``set_range``.
+
+    * ``schedule``: the run's ``[n, 8]`` table (``check_schedule``) or None.  ``K``: the parts of the forward - 1 plain, 2 classifier-free
+      guidance or PAG alone (``pag=True``), 3 both.  With a table and ``K`` > 1, a row with ``g == 1`` and ``s == 0`` - PAG alone:
+      ``s == 0`` - is **reduced**: its guided prediction is the conditional one, so the forward runs on the B conditional rows only.
+      ``phi`` does not matter (the rescale factor of a prediction against itself is 1); ``-0.0`` counts as 0.
+    * ``conditioning``: the run's ``[n, 4]`` table (``check_conditioning``) or None.  With a ControlNet, a row with ``c == 0`` runs
+      **no ControlNet**; with ``n_features`` > 0, a row with ``a == 0`` takes **no adapter features**.
+    * A run without the relevant table, or without the network a column speaks of, has nothing to skip there.  FreeU is not part of a
+      variant.  With neither table the answer is ``n_steps`` zeros.
+
+    Raises ``ValueError`` for ``K`` outside 1..3, ``pag`` with ``K`` == 1, tables of different lengths or no length at all."""
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= 3:
+        raise ValueError(f"K must be 1, 2 or 3, got {K!r}")
+    if pag and K == 1:
+        raise ValueError("pag=True needs K = 2 (PAG alone) or 3 (with classifier-free guidance)")
+    if isinstance(n_features, bool) or not isinstance(n_features, (int, np.integer)) or n_features < 0:
+        raise ValueError(f"n_features must be an int >= 0, got {n_features!r}")
+    lengths = set()
+    if schedule is not None:
+        schedule = np.asarray(schedule, dtype=np.float32)
+        if schedule.ndim != 2 or schedule.shape[1] != 8:
+            raise ValueError(f"schedule must have shape [n, 8], got {list(schedule.shape)}")
+        lengths.add(int(schedule.shape[0]))
+    if conditioning is not None:
+        conditioning = np.asarray(conditioning, dtype=np.float32)
+        if conditioning.ndim != 2 or conditioning.shape[1] != 4:
+            raise ValueError(f"conditioning must have shape [n, 4], got {list(conditioning.shape)}")
+        lengths.add(int(conditioning.shape[0]))
+    if n_steps is not None:
+        lengths.add(int(n_steps))
+    if len(lengths) != 1:
+        raise ValueError("the tables (and n_steps) must agree on one number of steps" if lengths else
+                         "without a table the number of steps must be given (n_steps)")
+    n = lengths.pop()
+    out = []
+    for i in range(n):
+        v = 0
+        if schedule is not None and K > 1:
+            g, s = schedule[i, 0], schedule[i, 1]
+            if s == 0 and ((pag and K == 2) or g == 1):
+                v |= STEP_REDUCED
+        if conditioning is not None:
+            if has_controlnet and conditioning[i, 0] == 0:
+                v |= STEP_NO_CONTROLNET
+            if n_features > 0 and conditioning[i, 1] == 0:
+                v |= STEP_NO_FEATURES
+        out.append(v)
+    return out
+
+
+def check_skip(skip_neutral, cache_interval=1) -> bool:
+    """The argument rule of ``Sampler.run(skip_neutral=)`` (no device is touched): a bool; True is refused together with a feature cache
+    (``cache_interval`` > 1), whose shallow step has no reduced form.  Raises ``ValueError``."""
+    if not isinstance(skip_neutral, (bool, np.bool_)):
+        raise ValueError(f"skip_neutral must be a bool, got {skip_neutral!r}")
+    if skip_neutral and cache_interval > 1:
+        raise ValueError("skip_neutral=True together with a feature cache (interval > 1) is not supported")
+    return bool(skip_neutral)
+
+
 def guess_mode_weights(n_down) -> np.ndarray:
     """The per-residual weights of guess mode (diffusers' ``ControlNetModel.forward``): float32 ``logspace(-1, 0, n_down + 1)`` - the
     ``n_down`` down residuals, then the mid residual at weight 1."""
@@ -460,6 +527,9 @@ class Sampler:
         the step graph and the result of a sampler that never had one.  Changing either value captures the step graphs again."""
         interval, depth = check_cache(interval, depth, int(L.lib().mrisr_model_num_skips(self.unet._h)), self.controlnet is not None)
         self._check_cache_with(interval)
+        if getattr(self, "_skipping", False):  # skip_neutral is an argument of each run: what the last one left in the library is not a conflict
+            L.check(L.lib().mrisr_sampler_set_skip(self._h, 0))
+            self._skipping = False
         L.check(L.lib().mrisr_sampler_set_cache(self._h, interval, depth))
         self.cache_interval, self.cache_depth = interval, depth
 
@@ -537,18 +607,25 @@ class Sampler:
             step_noise: Optional[torch.Tensor] = None, controlnet_cond: Optional[torch.Tensor] = None,
             adapter_features: Optional[Sequence[torch.Tensor]] = None, pag_scale: float = 0.0, pag_applied_layers=("mid",),
             pag_adaptive_scale: float = 0.0, guidance_interval=None, pag_interval=None, freeu_interval=None, schedule=None,
-            controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0,
+            skip_neutral: bool = False, controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0,
             adapter_conditioning_scale: float = 1.0, adapter_conditioning_factor: float = 1.0, guess_mode: bool = False,
             conditioning=None, use_graph: bool = True, guidance_scale: float = 1.0, guidance_rescale: float = 0.0,
             uncond_hidden_states: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Advance ``latents`` [B,C,h,w] (f32, updated IN PLACE) through every timestep.
+
+        Skipping: with ``skip_neutral=True`` each step runs only the rows and networks its table rows need
+        (``step_variants``): a step whose schedule row is neutral (``g == 1`` and ``s == 0``) forwards the B conditional rows alone, a
+        step with ControlNet scale 0 launches no ControlNet, a step with adapter scale 0 takes no features.  In exact arithmetic the
+        result is the one without the option; in floating point it differs by rounding on the skipped steps.  Each variant is its own
+        captured graph, taken the first time a run needs it; ``last_run_stats`` tells what the run did.  Not with a feature cache.  The
+        default leaves everything as it is: same launches, same bits, same captures.
 
         Conditioning strength: ``controlnet_conditioning_scale`` (the ControlNet residuals times this),
         ``control_guidance_start`` / ``control_guidance_end`` (fractions of the run outside which the residuals count 0),
         ``adapter_conditioning_scale`` / ``adapter_conditioning_factor`` (the adapter features times the scale on the first
         ``int(n * factor)`` steps, 0 afterwards) build a conditioning table with ``conditioning_schedule``; ``conditioning``: an explicit
         ``[n_steps, 4]`` table (``check_conditioning``) instead of those five.  The captured step reads the strengths from the table, so
-        other values replay the same graph; a step with scale 0 still runs the ControlNet.  ``guess_mode`` (diffusers'): residual k is
+        other values replay the same graph; a step with scale 0 still runs the ControlNet unless ``skip_neutral`` is given.  ``guess_mode`` (diffusers'): residual k is
         weighted by ``guess_mode_weights``; under classifier-free guidance the ControlNet then runs on the conditional rows only and the
         unconditional rows get no residual (``controlnet_cond`` stays [B]).  Not with PAG or tiles.  With none of the seven the call is
         the one without a table: same launches, same bits.  A table is refused together with a feature cache.
@@ -561,7 +638,7 @@ class Sampler:
         (``check_schedule``) instead of those four; the scalar arguments then only choose the kind of run (``pag_scale > 0``: a PAG run;
         ``uncond_hidden_states`` with ``guidance_scale != 1``: the unconditional half) and their values are not read.  Row i belongs to
         step i of the schedule also under ``set_range``.  With none of the five the call is the one without a table: same launches,
-        same bits.  A step whose row is neutral still costs a guided step.
+        same bits.  A step whose row is neutral still costs a guided step unless ``skip_neutral`` is given.
 
         FreeU needs no argument: a UNet with ``enable_freeu`` applies it in every step, with every option below
         except the feature cache.
@@ -586,6 +663,7 @@ class Sampler:
             if lr_latents is not None and tuple(lr_latents.shape) != tuple(latents.shape):
                 raise ValueError(f"lr_latents must have the latents' shape {tuple(latents.shape)}, got {tuple(lr_latents.shape)}")
         self._check_cache_with(self.cache_interval)
+        self._pending_skip = check_skip(skip_neutral, self.cache_interval)
         plan = None
         if self.tiles is not None:  # a tiled run: the canvas and everything shaped after it is checked here, before any launch
             if latents.ndim != 4:
@@ -685,6 +763,16 @@ class Sampler:
             L.check(L.lib().mrisr_sampler_set_schedule(self._h, None, 0))
             self._scheduled = False
 
+    @property
+    def last_run_stats(self) -> dict:
+        """What the last ``run`` did, from the library's own count: ``unet_rows`` (the sum over its steps of the rows of the UNet forward),
+        ``controlnet_steps`` (steps that ran the ControlNet), ``feature_steps`` (steps that took adapter features), ``variants`` (distinct
+        step variants, ``step_variants``) and ``captures`` (step graphs this sampler has captured so far)."""
+        out = (C.c_int64 * 4)()
+        L.check(L.lib().mrisr_sampler_run_stats(self._h, out))
+        return {"unet_rows": int(out[0]), "controlnet_steps": int(out[1]), "feature_steps": int(out[2]), "variants": int(out[3]),
+                "captures": int(L.lib().mrisr_sampler_num_captures(self._h))}
+
     def _run_pag(self, latents, ehs_c, ehs_u, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, g, guidance_rescale,
                  s, mask, plan=None):
         """The PAG run: the rows [perturbed; conditional] or, with active classifier-free guidance, [perturbed; unconditional;
@@ -752,6 +840,10 @@ class Sampler:
             setup()
         self._apply_schedule()
         self._apply_conditioning()
+        skip, self._pending_skip = getattr(self, "_pending_skip", False), False
+        if skip or getattr(self, "_skipping", False):
+            L.check(L.lib().mrisr_sampler_set_skip(self._h, 1 if skip else 0))
+            self._skipping = skip
         L.check(entry(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None, C.byref(t_nz) if t_nz else None, C.byref(t_e),
                       C.byref(t_c) if t_c else None, f_arr if feats else None, len(feats), *extra, 1 if use_graph else 0, L.stream_ptr()))
         self._keep = keep
@@ -762,7 +854,7 @@ class Sampler:
 def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weight_dtype, accelerator, fixed_embeds,
                    num_inference_steps=20, adapter=None, solver=None, cache_interval=1, cache_depth=1, tile=None, tile_overlap=0,
                    tile_window="gaussian", pag_scale=0.0, pag_applied_layers=("mid",), freeu=None, pag_adaptive_scale=0.0,
-                   guidance_interval=None, pag_interval=None, freeu_interval=None, controlnet_conditioning_scale=1.0,
+                   guidance_interval=None, pag_interval=None, freeu_interval=None, skip_neutral=False, controlnet_conditioning_scale=1.0,
                    control_guidance_start=0.0, control_guidance_end=1.0, adapter_conditioning_scale=1.0, adapter_conditioning_factor=1.0,
                    guess_mode=False, guidance_scale=1.0, guidance_rescale=0.0, uncond_embeds=None):
     """Drop-in for the reference's validation sampler (res_srdiff.py:35-105): same inputs, same PIL panel out.
@@ -782,7 +874,9 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     (``step_schedule``); the defaults leave the panel unchanged.
     ``controlnet_conditioning_scale`` / ``control_guidance_start`` / ``control_guidance_end`` / ``adapter_conditioning_scale`` /
     ``adapter_conditioning_factor`` / ``guess_mode``: the conditioning strength of ``Sampler.run`` (``conditioning_schedule``); the
-    defaults leave the panel unchanged."""
+    defaults leave the panel unchanged.
+    ``skip_neutral``: as in ``Sampler.run`` - steps leave out the rows and networks the options above make neutral; the default
+    leaves the panel unchanged."""
     from PIL import Image
 
     freeu_vals = None
@@ -791,6 +885,7 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
             raise ValueError(f"freeu must be a (s1, s2, b1, b2) tuple, got {freeu!r}")
         freeu_vals = check_freeu(*freeu)
 
+    check_skip(skip_neutral, cache_interval)
     if solver is not None:
         check_solver(solver, getattr(noise_scheduler, "solver_order", 2), getattr(noise_scheduler, "final_sigmas_type", "zero"),
                      getattr(noise_scheduler, "lower_order_final", True), getattr(noise_scheduler, "disable_corrector", ()))
@@ -834,7 +929,7 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
                     pag_interval=pag_interval, freeu_interval=freeu_interval,
                     controlnet_conditioning_scale=controlnet_conditioning_scale, control_guidance_start=control_guidance_start,
                     control_guidance_end=control_guidance_end, adapter_conditioning_scale=adapter_conditioning_scale,
-                    adapter_conditioning_factor=adapter_conditioning_factor, guess_mode=guess_mode)
+                    adapter_conditioning_factor=adapter_conditioning_factor, guess_mode=guess_mode, skip_neutral=skip_neutral)
     finally:
         if freeu_vals is not None:
             if freeu_prev is None:

@@ -538,42 +538,11 @@ template <typename T> int launch_fill_zero(void* p, long long n, hipStream_t st)
 int launch_quant_rows_fp8(const void* src_bf16, int rows, int cols, void* dst8, float* scales, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
-// sampler steps (sampler.hip; f32 state, NCHW like the reference's latents)
+// sampler (sampler.hip; f32 state, NCHW like the reference's latents): the step kernels and their launchers are local to that file
 // ---------------------------------------------------------------------------------------------
-//   ddim: x = cx*x + ce*eps;   coefficients read from a device table indexed by *step_idx
-int launch_ddim_step(float* x, const float* eps, const float* coef_table, const int* step_idx, long long n,
-                     hipStream_t st);
-//   res-srdiff reverse step (reference res_srdiff.py:84-96): coef row = {sqrt_at, sqrt_1mat, sqrt_ap, sigma}
-int launch_ddpm_step(float* x, const float* eps, const float* noise, const float* coef_table, const int* step_idx, float clip,
-                     long long n, hipStream_t st);
-int launch_resshift_step(float* x, const float* eps, const float* lr, const float* noise, const float* coef_table,
-                         const int* step_idx, long long n, hipStream_t st);
-int launch_advance_step(int* step_idx, hipStream_t st);
-//   the guided step on the K parts of a [K B] forward's output epsK -> guided (and rescaled by phi against the conditional part) eps ->
-//   the step above of kind `kind`; the new x goes to x [B] and to all K parts of the staging buffer xK [K B].  `per` = elements per sample
-//   (multiple of 4).  K = 2, classifier-free guidance: [uncond rows; cond rows], e = eps_u + g (eps_c - eps_u); s is not read.  K = 3,
-//   perturbed-attention guidance with it: [perturbed rows; uncond rows; cond rows], e = eps_u + g (eps_c - eps_u) + s (eps_c - eps_p).
-//   (PAG alone is K = 2 on [eps_p; eps_c] with g = 1 + s.)
-//   sched (device, [n][8], or nullptr): the kernel reads {g, s, phi} from sched[8 * *step_idx + 0..2] instead of the three arguments
-//   (DESIGN.md section 29); pag_alone: K = 2 on [eps_p; eps_c], the kernel forms g = 1 + s of the row; sched_phi: some row has phi > 0 -
-//   the rescale kernel is launched (a row with phi == 0 gives the factor exactly 1 there).  The rows were checked by whoever built the table.
-int launch_guided_step(int K, int kind, float* x, float* xK, const float* epsK, const float* lr, const float* noise, const float* coef_table,
-                       const int* step_idx, float clip, float g, float s, float phi, int B, long long per, hipStream_t st,
-                       float* hist = nullptr, float* xc = nullptr, int order = 0, const float* sched = nullptr, int sched_phi = 0,
-                       int pag_alone = 0);
-//   the step of a neutral schedule row (g == 1, s == 0) from the conditional prediction alone: eps [B], the new x to the latents and to all
-//   K parts of xK [K B]; history and corrected state as the guided step writes them
-int launch_reduced_step(int K, int kind, float* x, float* xK, const float* eps, const float* lr, const float* noise, const float* coef_table,
-                        const int* step_idx, float clip, int B, long long per, hipStream_t st, float* hist = nullptr, float* xc = nullptr,
-                        int order = 0);
 //   the checks of a host schedule table [n_rows][8] = {g, s, phi, freeu s1, s2, b1, b2, 0}, before any device work: every value finite,
 //   s >= 0, phi in [0, 1], the FreeU values >= 0.  0, or an error code with the message naming the row and the field
 int check_schedule_rows(const float* rows, int n_rows);
-//   multistep step (MRISR_STEP_UNIPC / MRISR_STEP_DPMSOLVERPP): rows of 16 floats (sampler.hip), hist = `order` slabs of n floats (the x0
-//   predictions, slot step % order), xc = the previous corrected state (UniPC) or nullptr; lr (or nullptr) anchors the state: the solver
-//   runs on x - lr.  n must be a multiple of 4.  The guided form is launch_guided_step with the same three buffers.
-int launch_multistep_step(float* x, const float* eps, const float* lr, const float* coef_table, const int* step_idx, float* hist, float* xc,
-                          int order, long long n, hipStream_t st);
 //   forward shift (reference res_srdiff.py:7-25): per-sample alpha from table[t[b]]
 int launch_resshift_forward(const float* hr, const float* lr, const float* noise, const float* alphas_cumprod,
                             const long long* t, int t_is_scalar, float* out, int B, long long per_sample,

@@ -28,67 +28,9 @@ static inline unsigned nblocks(long long total) {
 // device-resident step counter (so one captured hipGraph replays for every step, and the reference's
 // host sync on `prev_t > 0` (res_srdiff.py:92) disappears: sigma is simply 0 on the last row).
 // ------------------------------------------------------------------------------------------------
-__global__ void ddim_step_kernel(float* x, const float* eps, const float* coef, const int* step, long long n) {
-    const int s = *step;
-    const float cx = coef[2 * s], ce = coef[2 * s + 1];
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-        x[i] = cx * x[i] + ce * eps[i];
-}
-int launch_ddim_step(float* x, const float* eps, const float* coef_table, const int* step_idx, long long n,
-                     hipStream_t st) {
-    ProfScope ps("sampler_step", 0.0, 12.0 * n, st);
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(nblocks(n)), dim3(256), 0, st, x, eps, coef_table, step_idx, n);
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-__global__ void resshift_step_kernel(float* x, const float* eps, const float* lr, const float* noise_base,
-                                     const float* coef, const int* step, long long n) {
-    const int s = *step;
-    const float* noise = noise_base ? noise_base + (size_t)s * n : nullptr;  // one [n] slab per stochastic step
-    // row = {sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sigma}
-    const float sat = coef[4 * s], s1mat = coef[4 * s + 1], sap = coef[4 * s + 2], sig = coef[4 * s + 3];
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float l = lr[i];
-        const float x0 = (x[i] - (1.f - sat) * l - s1mat * eps[i]) / sat;
-        float v = sap * x0 + (1.f - sap) * l;
-        if (sig != 0.f && noise) v += sig * noise[i];
-        x[i] = v;
-    }
-}
-int launch_resshift_step(float* x, const float* eps, const float* lr, const float* noise, const float* coef_table,
-                         const int* step_idx, long long n, hipStream_t st) {
-    ProfScope ps("sampler_step", 0.0, 20.0 * n, st);
-    hipLaunchKernelGGL(resshift_step_kernel, dim3(nblocks(n)), dim3(256), 0, st, x, eps, lr, noise, coef_table,
-                       step_idx, n);
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-__global__ void ddpm_step_kernel(float* x, const float* eps, const float* noise_base, const float* coef, const int* step, float clip,
-                                 long long n) {
-    const int s = *step;
-    const float* noise = noise_base ? noise_base + (size_t)s * n : nullptr;
-    // row = {1/sqrt(abar_t), sqrt(1-abar_t)/sqrt(abar_t), x0 coefficient, x_t coefficient, sigma}
-    const float ia = coef[8 * s], ie = coef[8 * s + 1], c0 = coef[8 * s + 2], cx = coef[8 * s + 3], sig = coef[8 * s + 4];
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float xv = x[i];
-        float x0 = ia * xv - ie * eps[i];
-        if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
-        float v = c0 * x0 + cx * xv;
-        if (sig != 0.f && noise) v += sig * noise[i];
-        x[i] = v;
-    }
-}
-int launch_ddpm_step(float* x, const float* eps, const float* noise, const float* coef_table, const int* step_idx, float clip,
-                     long long n, hipStream_t st) {
-    ProfScope ps("sampler_step", 0.0, 16.0 * n, st);
-    hipLaunchKernelGGL(ddpm_step_kernel, dim3(nblocks(n)), dim3(256), 0, st, x, eps, noise, coef_table, step_idx, clip, n);
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-// ------------------------------------------------------------------------------------------------
 // guided step (classifier-free guidance): ONE launch that combines the two halves of a [2B] UNet output,
 //   e = eps_u + g (eps_c - eps_u);   phi > 0:  e *= phi std_b(eps_c) / std_b(e) + (1 - phi)   (per sample b, n-1 as torch.std),
-// applies the DDIM / Res-SRDiff / DDPM update above to x with e, and writes the new x to the caller's latents and to both halves
+// applies the update of the step kind (step_value, multistep_value4) to x with e, and writes the new x to the caller's latents and to both halves
 // of the [2B] staging buffer the next forward reads.  eps2 rows 0..B-1 are unconditional, B..2B-1 conditional (diffusers' order).
 //   phi == 0: grid-stride over float4 pieces.
 //   phi  > 0: one workgroup of 1024 threads per sample; up to 16 Ki elements per sample both eps rows stay in registers (ITEMS
@@ -106,6 +48,26 @@ int launch_ddpm_step(float* x, const float* eps, const float* noise, const float
 // row.  Whether the rescale kernel runs is still the host's choice (some row has phi > 0); a row with phi == 0 gives the factor
 // 0 * r + 1 == 1 there, and a non-finite r is caught by the degenerate-sample guard.
 // ------------------------------------------------------------------------------------------------
+struct MsBuf { float* hist; float* xc; int R; };  // the multistep ring of R slabs; xc == nullptr: no corrector (DPM-Solver++)
+// What one step launch reads: step_body fills it from the StepPlan, op_step from its tensors, check_step checks it and every step kernel
+// takes it by value.
+struct StepArgs {
+    int kind = 0, K = 1;          // mrisr_step_kind; parts of the forward's output (1: unguided)
+    float* x = nullptr;           // the latents [B], in place
+    float* xK = nullptr;          // K > 1: the [K B] staging buffer, every part receives the new x
+    const float* eps = nullptr;   // the prediction: [K B], or [B] (K == 1 and the reduced step)
+    const float* lr = nullptr;    // LR anchor [B] or null
+    const float* noise = nullptr; // step-noise slabs [n_steps][B] or null; slab *step is read when the row's sigma != 0
+    const float* coef = nullptr;  // the coefficient table, row *step
+    const int* step = nullptr;
+    float clip = 0.f;
+    float g = 1.f, s = 0.f, phi = 0.f;  // guidance_scale (pag alone: 1 + pag_scale), pag_scale (K == 3), guidance_rescale
+    const float* sched = nullptr;       // schedule table [n][8] or null: row *step replaces the three scalars
+    int sched_phi = 0, pag_alone = 0;   // some row has phi > 0 (the rescale kernel runs); K == 2 on [eps_p; eps_c], g := 1 + s of the row
+    int B = 0;
+    long long per = 0;            // elements per sample
+    MsBuf ms{nullptr, nullptr, 0};  // multistep kinds: the history ring, UniPC's corrected state, the solver order
+};
 struct StepRow { float a, b, c, d, sig; };
 // the three guidance scalars of this step: the launch constants, or row s of the schedule table
 __device__ __forceinline__ void load_guidance(const float* sched, int s, int pag_alone, float& g, float& sp, float& phi) {
@@ -116,6 +78,10 @@ __device__ __forceinline__ void load_guidance(const float* sched, int s, int pag
     sp = pag_alone ? 0.f : qs;
     phi = q[2];
 }
+// row s of the first-order kinds' table
+//   DDIM       {cx, ce}:                                                                   x = cx x + ce eps
+//   Res-SRDiff {sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sigma}
+//   DDPM       {1/sqrt(abar_t), sqrt(1-abar_t)/sqrt(abar_t), x0 coefficient, x_t coefficient, sigma}
 __device__ __forceinline__ StepRow load_step_row(int kind, const float* coef, int s) {
     StepRow r{0.f, 0.f, 0.f, 0.f, 0.f};
     if (kind > MRISR_STEP_DDPM) return r;  // multistep kinds read their own 16-float row (multistep_value4)
@@ -124,7 +90,7 @@ __device__ __forceinline__ StepRow load_step_row(int kind, const float* coef, in
     else { r.a = coef[8 * s]; r.b = coef[8 * s + 1]; r.c = coef[8 * s + 2]; r.d = coef[8 * s + 3]; r.sig = coef[8 * s + 4]; }
     return r;
 }
-// the arithmetic of ddim_step_kernel / resshift_step_kernel / ddpm_step_kernel, one element
+// the update rule of the first-order kinds, one element: the only copy, for every K
 __device__ __forceinline__ float step_value(int kind, const StepRow& r, float clip, float xv, float e, float l, float nz, bool noisy) {
     if (kind == MRISR_STEP_DDIM) return r.a * xv + r.b * e;
     float v;
@@ -183,7 +149,6 @@ __device__ __forceinline__ void store_parts(float* x, float* xK, long long n, lo
 // m = (z - sigma eps) / alpha of a high-noise step, and order 1 is the DDIM expression itself.  R = solver_order slabs of n floats;
 // the slot an element overwrites is the one it read as h_R.  The ring and xc are zeroed by the host at the start of a run.
 // ------------------------------------------------------------------------------------------------
-struct MsBuf { float* hist; float* xc; int R; };  // xc == nullptr: no corrector (DPM-Solver++)
 constexpr int MS_ROW = 16;
 __device__ __forceinline__ float4 fma4(float c, float4 v, float4 acc) {
     return make_float4(fmaf(c, v.x, acc.x), fmaf(c, v.y, acc.y), fmaf(c, v.z, acc.z), fmaf(c, v.w, acc.w));
@@ -214,51 +179,57 @@ __device__ __forceinline__ float4 multistep_value4(const float* __restrict__ row
     if (ms.xc) reinterpret_cast<float4*>(ms.xc)[i] = zc;
     return make_float4(zn.x + l.x, zn.y + l.y, zn.z + l.z, zn.w + l.w);
 }
-__global__ __launch_bounds__(256) void multistep_step_kernel(float* x, const float* eps, const float* lr, const float* coef, const int* step,
-                                                             MsBuf ms, long long n) {
-    const int s = *step;
-    const float* row = coef + (size_t)MS_ROW * s;
+// what every step kernel derives from its StepArgs behind the load of *step, uniform over the launch
+struct StepCtx {
+    int s;
+    long long n;         // B * per
+    StepRow r;
+    const float* msrow;  // the multistep kinds' row, or null
+    const float* noise;  // this step's slab [n], or null: no noise given, or a row with sigma == 0
+};
+__device__ __forceinline__ StepCtx load_step_ctx(const StepArgs& a) {
+    StepCtx c;
+    c.s = *a.step;
+    c.n = (long long)a.B * a.per;
+    c.r = load_step_row(a.kind, a.coef, c.s);
+    c.msrow = a.ms.hist ? a.coef + (size_t)MS_ROW * c.s : nullptr;
+    c.noise = a.noise && c.r.sig != 0.f ? a.noise + (size_t)c.s * c.n : nullptr;
+    return c;
+}
+// the update of one float4 piece from the prediction e: the first-order kinds, or the multistep step; the new x goes to the caller's
+// latents and to PARTS parts of the staging buffer
+template <int PARTS>
+__device__ __forceinline__ void guided_apply4(const StepArgs& a, const StepCtx& c, long long i, float4 e) {
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256) {
-        const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
-        reinterpret_cast<float4*>(x)[i] =
-            multistep_value4(row, ms, s, n, i, reinterpret_cast<const float4*>(x)[i], reinterpret_cast<const float4*>(eps)[i], l);
-    }
-}
-static int check_multistep(const float* x, const float* eps, const float* lr, const MsBuf& ms, long long n) {
-    MRISR_REQUIRE(x && eps && ms.hist && ms.R >= 1 && ms.R <= 3, "multistep step: null operand or solver order outside 1..3");
-    MRISR_REQUIRE(n > 0 && n % 4 == 0, "multistep step: C*h*w of the latents must be a multiple of 4");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    MRISR_REQUIRE(al16(x) && al16(eps) && al16(lr) && al16(ms.hist) && al16(ms.xc), "multistep step: operands must be 16-byte aligned");
-    return 0;
-}
-int launch_multistep_step(float* x, const float* eps, const float* lr, const float* coef_table, const int* step_idx, float* hist, float* xc,
-                          int order, long long n, hipStream_t st) {
-    const MsBuf ms{hist, xc, order};
-    MRISR_REQUIRE(coef_table && step_idx, "multistep step: null operand");
-    if (int rc = check_multistep(x, eps, lr, ms, n)) return rc;
-    // x in and out, eps, `order` history reads, one history write, xc in and out, lr
-    ProfScope ps("sampler_step", 0.0, (16.0 + 4.0 * order + (xc ? 8.0 : 0.0) + (lr ? 4.0 : 0.0)) * n, st);
-    hipLaunchKernelGGL(multistep_step_kernel, dim3(nblocks(n >> 2)), dim3(256), 0, st, x, eps, lr, coef_table, step_idx, ms, n);
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-// the update of one float4 piece of a guided step with the guided prediction e: the step kinds above, or the multistep step; the
-// new x goes to the caller's latents and to all K parts of the staging buffer
-template <int K>
-__device__ __forceinline__ void guided_apply4(int kind, const StepRow& r, const float* msrow, const MsBuf& ms, int s, float clip, float* x,
-                                              float* xK, const float* lr, const float* noise, long long n, long long i, float4 e) {
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    const float4 l = lr ? reinterpret_cast<const float4*>(lr)[i] : z4;
+    const float4 xv = reinterpret_cast<const float4*>(a.x)[i];
+    const float4 l = a.lr ? reinterpret_cast<const float4*>(a.lr)[i] : z4;
     float4 v;
-    if (msrow) {
-        v = multistep_value4(msrow, ms, s, n, i, xv, e, l);
+    if (c.msrow) {
+        v = multistep_value4(c.msrow, a.ms, c.s, c.n, i, xv, e, l);
     } else {
-        const float4 nz = noise ? reinterpret_cast<const float4*>(noise)[i] : z4;
-        v = step_value4(kind, r, clip, xv, e, l, nz, noise != nullptr);
+        const float4 nz = c.noise ? reinterpret_cast<const float4*>(c.noise)[i] : z4;
+        v = step_value4(a.kind, c.r, a.clip, xv, e, l, nz, c.noise != nullptr);
     }
-    store_parts<K>(x, xK, n, i, v);
+    store_parts<PARTS>(a.x, a.xK, c.n, i, v);
+}
+// The plain first-order step (K = 1; DDIM / Res-SRDiff / DDPM): scalar and grid-stride over n, so an unguided run has no multiple-of-4
+// or alignment precondition.
+__global__ void plain_step_kernel(StepArgs a) {
+    const StepCtx c = load_step_ctx(a);
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < c.n; i += (long long)gridDim.x * 256)
+        a.x[i] = step_value(a.kind, c.r, a.clip, a.x[i], a.eps[i], a.lr ? a.lr[i] : 0.f, c.noise ? c.noise[i] : 0.f, c.noise != nullptr);
+}
+// The update from a single prediction eps [B], any step kind, float4 pieces, grid-stride.  PARTS = 0: the plain multistep step (K = 1).
+// PARTS = 2 / 3: the reduced step of a guided / pag run whose schedule row is neutral (g == 1, s == 0).  The guided
+// prediction of such a row is the conditional one, whatever phi (a prediction rescaled against itself: factor 1), so the forward ran on the
+// conditional rows alone and eps is their prediction - the last part of the run's [K B] output buffer.  The history ring and UniPC's
+// corrected state are written exactly as a guided step writes them, and the new x goes to ALL K parts of the staging buffer: the next
+// guided step finds every part current.
+template <int PARTS>
+__global__ __launch_bounds__(256) void single_step_kernel(StepArgs a) {
+    const StepCtx c = load_step_ctx(a);
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (c.n >> 2); i += (long long)gridDim.x * 256)
+        guided_apply4<PARTS>(a, c, i, reinterpret_cast<const float4*>(a.eps)[i]);
 }
 constexpr int GS_THREADS = 1024;
 // sums of (a, b) over the workgroup, the same value in every thread; `red` holds one pair per wave
@@ -282,36 +253,25 @@ __device__ __forceinline__ float rescale_factor(float qc, float qe, float me, in
 }
 
 template <int K>
-__global__ __launch_bounds__(256) void guided_step_kernel(int kind, float* x, float* xK, const float* epsK, const float* lr,
-                                                          const float* noise_base, const float* coef, const int* step, float clip,
-                                                          float g, float sp, long long n, MsBuf ms, const float* sched, int pag_alone) {
-    const int s = *step;
-    float phi = 0.f;  // not read here
-    load_guidance(sched, s, pag_alone, g, sp, phi);
-    const StepRow r = load_step_row(kind, coef, s);
-    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
-    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256) {
-        float4 c;
-        const float4 e = guide4<K>(epsK, n, i, g, sp, c);
-        guided_apply4<K>(kind, r, msrow, ms, s, clip, x, xK, lr, noise, n, i, e);
+__global__ __launch_bounds__(256) void guided_step_kernel(StepArgs a) {
+    const StepCtx c = load_step_ctx(a);
+    float g = a.g, sp = a.s, phi = 0.f;  // phi is not read here
+    load_guidance(a.sched, c.s, a.pag_alone, g, sp, phi);
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (c.n >> 2); i += (long long)gridDim.x * 256) {
+        float4 cc;
+        const float4 e = guide4<K>(a.eps, c.n, i, g, sp, cc);
+        guided_apply4<K>(a, c, i, e);
     }
 }
 
 template <int K, int ITEMS>
-__global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(int kind, float* x, float* xK, const float* epsK, const float* lr,
-                                                                         const float* noise_base, const float* coef, const int* step,
-                                                                         float clip, float g, float sp, float phi, int B, int per, MsBuf ms,
-                                                                         const float* sched, int pag_alone) {
+__global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(StepArgs a) {
     __shared__ float red[2 * GS_THREADS / 64];
-    const int s = *step;
-    load_guidance(sched, s, pag_alone, g, sp, phi);
-    const StepRow r = load_step_row(kind, coef, s);
-    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
-    const long long n = (long long)B * per;
-    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
-    const long long base4 = (long long)blockIdx.x * (per >> 2);
-    const int per4 = per >> 2;
+    const StepCtx cx = load_step_ctx(a);
+    float g = a.g, sp = a.s, phi = a.phi;
+    load_guidance(a.sched, cx.s, a.pag_alone, g, sp, phi);
+    const int per = (int)a.per, per4 = per >> 2;
+    const long long base4 = (long long)blockIdx.x * per4;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 e[ITEMS], c[ITEMS];
     float sc = 0.f, se = 0.f;
@@ -320,7 +280,7 @@ __global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(int kin
         const int j = threadIdx.x + k * GS_THREADS;
         e[k] = z4; c[k] = z4;
         if (j < per4) {
-            e[k] = guide4<K>(epsK, n, base4 + j, g, sp, c[k]);
+            e[k] = guide4<K>(a.eps, cx.n, base4 + j, g, sp, c[k]);
             sc += sum4(c[k]); se += sum4(e[k]);
         }
     }
@@ -335,139 +295,100 @@ __global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_kernel(int kin
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
         const int j = threadIdx.x + k * GS_THREADS;
-        if (j < per4) guided_apply4<K>(kind, r, msrow, ms, s, clip, x, xK, lr, noise, n, base4 + j, scale4(e[k], f));
+        if (j < per4) guided_apply4<K>(a, cx, base4 + j, scale4(e[k], f));
     }
 }
-// samples too large for the register file: the same three passes, each re-reading epsK
+// samples too large for the register file: the same three passes, each re-reading eps
 template <int K>
-__global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_reread_kernel(int kind, float* x, float* xK, const float* epsK, const float* lr,
-                                                                                const float* noise_base, const float* coef, const int* step,
-                                                                                float clip, float g, float sp, float phi, int B, int per, MsBuf ms,
-                                                                                const float* sched, int pag_alone) {
+__global__ __launch_bounds__(GS_THREADS) void guided_step_rescale_reread_kernel(StepArgs a) {
     __shared__ float red[2 * GS_THREADS / 64];
-    const int s = *step;
-    load_guidance(sched, s, pag_alone, g, sp, phi);
-    const StepRow r = load_step_row(kind, coef, s);
-    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
-    const long long n = (long long)B * per;
-    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
-    const long long base4 = (long long)blockIdx.x * (per >> 2);
-    const int per4 = per >> 2;
+    const StepCtx cx = load_step_ctx(a);
+    float g = a.g, sp = a.s, phi = a.phi;
+    load_guidance(a.sched, cx.s, a.pag_alone, g, sp, phi);
+    const int per = (int)a.per, per4 = per >> 2;
+    const long long base4 = (long long)blockIdx.x * per4;
     float4 c;
     float sc = 0.f, se = 0.f;
-    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 e = guide4<K>(epsK, n, base4 + j, g, sp, c); sc += sum4(c); se += sum4(e); }
+    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 e = guide4<K>(a.eps, cx.n, base4 + j, g, sp, c); sc += sum4(c); se += sum4(e); }
     block_sum2(sc, se, red);
     const float mc = sc / (float)per, me = se / (float)per;
     float qc = 0.f, qe = 0.f;
-    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 e = guide4<K>(epsK, n, base4 + j, g, sp, c); qc += ssq4(c, mc); qe += ssq4(e, me); }
+    for (int j = threadIdx.x; j < per4; j += GS_THREADS) { const float4 e = guide4<K>(a.eps, cx.n, base4 + j, g, sp, c); qc += ssq4(c, mc); qe += ssq4(e, me); }
     block_sum2(qc, qe, red);
     const float f = rescale_factor(qc, qe, me, per, phi);
     for (int j = threadIdx.x; j < per4; j += GS_THREADS)
-        guided_apply4<K>(kind, r, msrow, ms, s, clip, x, xK, lr, noise, n, base4 + j, scale4(guide4<K>(epsK, n, base4 + j, g, sp, c), f));
+        guided_apply4<K>(a, cx, base4 + j, scale4(guide4<K>(a.eps, cx.n, base4 + j, g, sp, c), f));
 }
 
 template <int K>
-static void launch_guided_kernels(int kind, float* x, float* xK, const float* epsK, const float* lr, const float* noise, const float* coef_table,
-                                  const int* step_idx, float clip, float g, float sp, float phi, int B, long long per, hipStream_t st, MsBuf ms,
-                                  const float* sched, int sched_phi, int pag_alone) {
-    const long long n = (long long)B * per;
-    if (sched ? !sched_phi : phi == 0.f) {
-        hipLaunchKernelGGL(guided_step_kernel<K>, dim3(nblocks(n >> 2)), dim3(256), 0, st, kind, x, xK, epsK, lr, noise, coef_table, step_idx,
-                           clip, g, sp, n, ms, sched, pag_alone);
+static void launch_guided_kernels(const StepArgs& a, hipStream_t st) {
+    const long long n = (long long)a.B * a.per;
+    if (a.sched ? !a.sched_phi : a.phi == 0.f) {
+        hipLaunchKernelGGL(guided_step_kernel<K>, dim3(nblocks(n >> 2)), dim3(256), 0, st, a);
         return;
     }
-#define MRISR_GS(ITEMS)                                                                                                                   \
-    hipLaunchKernelGGL((guided_step_rescale_kernel<K, ITEMS>), dim3(B), dim3(GS_THREADS), 0, st, kind, x, xK, epsK, lr, noise, coef_table, \
-                       step_idx, clip, g, sp, phi, B, (int)per, ms, sched, pag_alone)
-    if (per <= 4 * GS_THREADS) MRISR_GS(1);
-    else if (per <= 8 * GS_THREADS) MRISR_GS(2);
-    else if (per <= 16 * GS_THREADS) MRISR_GS(4);
-    else
-        hipLaunchKernelGGL(guided_step_rescale_reread_kernel<K>, dim3(B), dim3(GS_THREADS), 0, st, kind, x, xK, epsK, lr, noise, coef_table,
-                           step_idx, clip, g, sp, phi, B, (int)per, ms, sched, pag_alone);
-#undef MRISR_GS
+    if (a.per <= 4 * GS_THREADS) hipLaunchKernelGGL((guided_step_rescale_kernel<K, 1>), dim3(a.B), dim3(GS_THREADS), 0, st, a);
+    else if (a.per <= 8 * GS_THREADS) hipLaunchKernelGGL((guided_step_rescale_kernel<K, 2>), dim3(a.B), dim3(GS_THREADS), 0, st, a);
+    else if (a.per <= 16 * GS_THREADS) hipLaunchKernelGGL((guided_step_rescale_kernel<K, 4>), dim3(a.B), dim3(GS_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(guided_step_rescale_reread_kernel<K>, dim3(a.B), dim3(GS_THREADS), 0, st, a);
 }
-int launch_guided_step(int K, int kind, float* x, float* xK, const float* epsK, const float* lr, const float* noise, const float* coef_table,
-                       const int* step_idx, float clip, float g, float sp, float phi, int B, long long per, hipStream_t st, float* hist,
-                       float* xc, int order, const float* sched, int sched_phi, int pag_alone) {
-    MRISR_REQUIRE(K == 2 || K == 3, "guided step: 2 or 3 parts");
-    const std::string who = K == 3 ? "pag step: " : "guided step: ";
-    MRISR_REQUIRE(kind >= MRISR_STEP_DDIM && kind <= MRISR_STEP_DPMSOLVERPP, who + "unknown step kind");
-    const bool multistep = kind > MRISR_STEP_DDPM;
-    const MsBuf ms{multistep ? hist : nullptr, multistep && kind == MRISR_STEP_UNIPC ? xc : nullptr, multistep ? order : 0};
-    if (multistep) {
-        if (int rc = check_multistep(x, epsK, lr, ms, (long long)B * per)) return rc;
-        MRISR_REQUIRE(kind != MRISR_STEP_UNIPC || xc, who + "UniPC needs the corrected-state buffer");
-    }
-    MRISR_REQUIRE(x && xK && epsK && coef_table && step_idx && B > 0 && per > 0, who + "null operand");
-    MRISR_REQUIRE(per % 4 == 0 && per < (1ll << 31), who + "the per-sample size must be a multiple of 4");
-    if (sched) {  // the three scalars are not read: the rows were checked when the table was built
-        MRISR_REQUIRE(!pag_alone || K == 2, who + "pag alone is the step on 2 parts");
-        MRISR_REQUIRE((reinterpret_cast<uintptr_t>(sched) & 3) == 0, who + "the schedule table must be 4-byte aligned");
-    } else {
-        MRISR_REQUIRE(phi >= 0.f && phi <= 1.f, who + "guidance_rescale must lie in [0, 1]");
-        if (K == 3) MRISR_REQUIRE(std::isfinite(sp) && sp >= 0.f, who + "pag_scale must be finite and >= 0");
-    }
-    MRISR_REQUIRE(kind != MRISR_STEP_RESSHIFT || lr, who + "Res-SRDiff needs the LR anchor latents");
+// The operand checks of every step launch, once.  who: the message prefix of the launch - "guided step: " (K = 2), "pag step: " (K = 3),
+// "reduced step: ", "multistep step: " (K = 1; the plain first-order launch, which has nothing but null operands to check: "step: ").  Also drops what this kind does not read (lr, noise, the ring, xc), so the kernels and the
+// byte count below see null for it.
+static int check_step(const std::string& who, StepArgs& a, bool reduced) {
+    MRISR_REQUIRE(a.K == 2 || a.K == 3 || (a.K == 1 && !reduced), who + "2 or 3 parts");
+    MRISR_REQUIRE(a.kind >= MRISR_STEP_DDIM && a.kind <= MRISR_STEP_DPMSOLVERPP, who + "unknown step kind");
+    const bool multistep = a.kind > MRISR_STEP_DDPM, guided = a.K > 1 && !reduced;
+    const long long n = (long long)a.B * a.per;
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    MRISR_REQUIRE(al16(x) && al16(xK) && al16(epsK) && al16(lr) && al16(noise), who + "operands must be 16-byte aligned");
-    const long long n = (long long)B * per;
-    if (kind != MRISR_STEP_RESSHIFT && !multistep) lr = nullptr;
-    if (kind == MRISR_STEP_DDIM || multistep) noise = nullptr;
-    // epsK K times, x in, K + 1 stores of x; multistep: + `order` history reads, one history write, xc in and out
-    ProfScope ps("sampler_step", 0.0, ((K == 3 ? 32.0 : 28.0) + (lr ? 4.0 : 0.0) + (multistep ? 4.0 * order + 4.0 + (ms.xc ? 8.0 : 0.0) : 0.0)) * n, st);
-    if (K == 3) launch_guided_kernels<3>(kind, x, xK, epsK, lr, noise, coef_table, step_idx, clip, g, sp, phi, B, per, st, ms, sched, sched_phi, 0);
-    else launch_guided_kernels<2>(kind, x, xK, epsK, lr, noise, coef_table, step_idx, clip, g, sp, phi, B, per, st, ms, sched, sched_phi, pag_alone);
+    float* const xc = a.ms.xc;
+    a.ms = MsBuf{multistep ? a.ms.hist : nullptr, multistep && a.kind == MRISR_STEP_UNIPC ? xc : nullptr, multistep ? a.ms.R : 0};
+    if (multistep) {
+        MRISR_REQUIRE(a.x && a.eps && a.ms.hist && a.ms.R >= 1 && a.ms.R <= 3, "multistep step: null operand or solver order outside 1..3");
+        MRISR_REQUIRE(n > 0 && n % 4 == 0, "multistep step: C*h*w of the latents must be a multiple of 4");
+        MRISR_REQUIRE(al16(a.x) && al16(a.eps) && al16(a.lr) && al16(a.ms.hist) && al16(a.ms.xc), "multistep step: operands must be 16-byte aligned");
+        MRISR_REQUIRE(a.kind != MRISR_STEP_UNIPC || xc, who + "UniPC needs the corrected-state buffer");
+    }
+    MRISR_REQUIRE(a.x && a.eps && a.coef && a.step && (a.K == 1 || (a.xK && a.B > 0 && a.per > 0)), who + "null operand");
+    if (a.K > 1) MRISR_REQUIRE(a.per % 4 == 0 && a.per < (1ll << 31), who + "the per-sample size must be a multiple of 4");
+    if (guided && a.sched) {  // the three scalars are not read: the rows were checked when the table was built
+        MRISR_REQUIRE(!a.pag_alone || a.K == 2, who + "pag alone is the step on 2 parts");
+        MRISR_REQUIRE((reinterpret_cast<uintptr_t>(a.sched) & 3) == 0, who + "the schedule table must be 4-byte aligned");
+    } else if (guided) {
+        MRISR_REQUIRE(a.phi >= 0.f && a.phi <= 1.f, who + "guidance_rescale must lie in [0, 1]");
+        if (a.K == 3) MRISR_REQUIRE(std::isfinite(a.s) && a.s >= 0.f, who + "pag_scale must be finite and >= 0");
+    }
+    MRISR_REQUIRE(a.kind != MRISR_STEP_RESSHIFT || a.lr, who + "Res-SRDiff needs the LR anchor latents");
+    if (a.K > 1) MRISR_REQUIRE(al16(a.x) && al16(a.xK) && al16(a.eps) && al16(a.lr) && al16(a.noise), who + "operands must be 16-byte aligned");
+    if (a.kind != MRISR_STEP_RESSHIFT && !multistep) a.lr = nullptr;
+    if (a.kind == MRISR_STEP_DDIM || multistep) a.noise = nullptr;
+    return 0;
+}
+// ONE launch: the guided step of a [K B] prediction (K = 2, 3), the reduced step of a guided / pag run from the conditional prediction
+// [B], or the unguided step (K = 1)
+static int launch_step(StepArgs a, bool reduced, hipStream_t st) {
+    const bool multistep = a.kind > MRISR_STEP_DDPM, guided = a.K > 1 && !reduced;
+    const char* who = reduced ? "reduced step: " : a.K == 3 ? "pag step: " : a.K != 1 ? "guided step: " : multistep ? "multistep step: " : "step: ";
+    if (int rc = check_step(who, a, reduced)) return rc;
+    const long long n = (long long)a.B * a.per;
+    // eps (a guided step: K times), x in, 1 + K stores of x (K = 1: one), lr; the plain first-order step of a stochastic kind: + its noise
+    // slab; multistep: + `order` history reads, one history write, xc in and out
+    double bytes = guided ? (a.K == 3 ? 32.0 : 28.0) : 12.0 + (a.K > 1 ? 4.0 * a.K : 0.0);
+    bytes += (a.lr ? 4.0 : 0.0) + (multistep ? 4.0 * a.ms.R + 4.0 + (a.ms.xc ? 8.0 : 0.0) : 0.0);
+    if (a.K == 1 && (a.kind == MRISR_STEP_RESSHIFT || a.kind == MRISR_STEP_DDPM)) bytes += 4.0;
+    ProfScope ps("sampler_step", 0.0, bytes * n, st);
+    if (guided && a.K == 3) launch_guided_kernels<3>(a, st);
+    else if (guided) launch_guided_kernels<2>(a, st);
+    else if (a.K == 3) hipLaunchKernelGGL(single_step_kernel<3>, dim3(nblocks(n >> 2)), dim3(256), 0, st, a);
+    else if (a.K == 2) hipLaunchKernelGGL(single_step_kernel<2>, dim3(nblocks(n >> 2)), dim3(256), 0, st, a);
+    else if (multistep) hipLaunchKernelGGL(single_step_kernel<0>, dim3(nblocks(n >> 2)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(plain_step_kernel, dim3(nblocks(n)), dim3(256), 0, st, a);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
 }
-// ------------------------------------------------------------------------------------------------
-// reduced step: the step of a guided / pag run whose schedule row is neutral (g == 1, s == 0).  The guided
-// prediction of such a row is the conditional one, whatever phi (a prediction rescaled against itself: factor 1), so the forward ran on the
-// conditional rows alone and `eps` is their prediction [B] - the last part of the run's [K B] output buffer.  ONE launch: the update of any
-// step kind through guided_apply4, so the multistep history ring and UniPC's corrected state are written exactly as a guided step writes
-// them, and the new x goes to the caller's latents and to ALL K parts of the staging buffer - the next guided step finds every part
-// current.  float4 pieces, grid-stride; the preconditions of guided_step_kernel.
-// ------------------------------------------------------------------------------------------------
-template <int K>
-__global__ __launch_bounds__(256) void reduced_step_kernel(int kind, float* x, float* xK, const float* eps, const float* lr, const float* noise_base,
-                                                           const float* coef, const int* step, float clip, long long n, MsBuf ms) {
-    const int s = *step;
-    const StepRow r = load_step_row(kind, coef, s);
-    const float* msrow = ms.hist ? coef + (size_t)MS_ROW * s : nullptr;
-    const float* noise = noise_base && r.sig != 0.f ? noise_base + (size_t)s * n : nullptr;
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256)
-        guided_apply4<K>(kind, r, msrow, ms, s, clip, x, xK, lr, noise, n, i, reinterpret_cast<const float4*>(eps)[i]);
-}
-// eps: [B] (n = B * per floats); xK: [K B]; hist / xc / order as launch_guided_step
-int launch_reduced_step(int K, int kind, float* x, float* xK, const float* eps, const float* lr, const float* noise, const float* coef_table,
-                        const int* step_idx, float clip, int B, long long per, hipStream_t st, float* hist, float* xc, int order) {
-    const std::string who = "reduced step: ";
-    MRISR_REQUIRE(K == 2 || K == 3, who + "2 or 3 parts");
-    MRISR_REQUIRE(kind >= MRISR_STEP_DDIM && kind <= MRISR_STEP_DPMSOLVERPP, who + "unknown step kind");
-    const bool multistep = kind > MRISR_STEP_DDPM;
-    const MsBuf ms{multistep ? hist : nullptr, multistep && kind == MRISR_STEP_UNIPC ? xc : nullptr, multistep ? order : 0};
-    if (multistep) {
-        if (int rc = check_multistep(x, eps, lr, ms, (long long)B * per)) return rc;
-        MRISR_REQUIRE(kind != MRISR_STEP_UNIPC || xc, who + "UniPC needs the corrected-state buffer");
-    }
-    MRISR_REQUIRE(x && xK && eps && coef_table && step_idx && B > 0 && per > 0, who + "null operand");
-    MRISR_REQUIRE(per % 4 == 0 && per < (1ll << 31), who + "the per-sample size must be a multiple of 4");
-    MRISR_REQUIRE(kind != MRISR_STEP_RESSHIFT || lr, who + "Res-SRDiff needs the LR anchor latents");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    MRISR_REQUIRE(al16(x) && al16(xK) && al16(eps) && al16(lr) && al16(noise), who + "operands must be 16-byte aligned");
-    const long long n = (long long)B * per;
-    if (kind != MRISR_STEP_RESSHIFT && !multistep) lr = nullptr;
-    if (kind == MRISR_STEP_DDIM || multistep) noise = nullptr;
-    // eps once, x in, K + 1 stores of x; multistep: + `order` history reads, one history write, xc in and out
-    ProfScope ps("sampler_step", 0.0, (12.0 + 4.0 * K + (lr ? 4.0 : 0.0) + (multistep ? 4.0 * order + 4.0 + (ms.xc ? 8.0 : 0.0) : 0.0)) * n, st);
-    if (K == 3) hipLaunchKernelGGL(reduced_step_kernel<3>, dim3(nblocks(n >> 2)), dim3(256), 0, st, kind, x, xK, eps, lr, noise, coef_table, step_idx, clip, n, ms);
-    else hipLaunchKernelGGL(reduced_step_kernel<2>, dim3(nblocks(n >> 2)), dim3(256), 0, st, kind, x, xK, eps, lr, noise, coef_table, step_idx, clip, n, ms);
-    MRISR_CHECK_HIP(hipGetLastError());
-    return 0;
-}
+
 __global__ void advance_step_kernel(int* step) { *step += 1; }
-int launch_advance_step(int* step_idx, hipStream_t st) {
+static int launch_advance_step(int* step_idx, hipStream_t st) {
     hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(1), 0, st, step_idx);
     MRISR_CHECK_HIP(hipGetLastError());
     return 0;
@@ -620,6 +541,38 @@ static std::vector<float> build_multistep_rows(int kind, const MultistepOpts& o,
     return rows;
 }
 
+// A per-step table of a sampler (the schedule, [n_steps][8]; the conditioning strengths, [n_steps][4]): the host rows (empty: no table)
+// and the device buffer every run with a table uploads them to - reserved once, so its address is the same for every such run.
+struct StepTable {
+    const char* name;
+    int width;
+    std::vector<float> rows;
+    DevBuf dev;
+    bool on() const { return !rows.empty(); }
+    const float* row(int i) const { return &rows[(size_t)width * i]; }
+    // NULL / 0 clears the table (the next run has another plan and captures again); otherwise n_steps rows that pass `check`
+    int set(const float* rows_host, int n_rows, int n_steps, int (*check)(const float*, int)) {
+        const std::string who = std::string(name) + ": ";
+        if (!rows_host || n_rows == 0) {
+            MRISR_REQUIRE(!rows_host && n_rows == 0, who + "NULL / 0 clears it; rows need n_rows == n_steps");
+            rows.clear();
+            return 0;
+        }
+        MRISR_REQUIRE(n_rows == n_steps, who + "n_rows must equal the sampler's n_steps (" + std::to_string(n_steps) + "), got " + std::to_string(n_rows));
+        if (int rc = check(rows_host, n_rows)) return rc;
+        TRY(dev.reserve(sizeof(float) * width * (size_t)n_steps, false));  // once per sampler: n_rows is always n_steps
+        rows.assign(rows_host, rows_host + (size_t)width * n_rows);
+        return 0;
+    }
+    // The rows, indexed by the absolute step like the coefficient rows.  `rows` is pageable and may be replaced (set) right after the run
+    // returns: this relies on the runtime staging a pageable host-to-device copy before hipMemcpyAsync returns.
+    int upload(int n_steps, hipStream_t st) {
+        MRISR_REQUIRE(rows.size() == (size_t)width * n_steps && dev.bytes >= sizeof(float) * rows.size(), std::string(name) + " table size");
+        MRISR_CHECK_HIP(hipMemcpyAsync(dev.p, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice, st));
+        return 0;
+    }
+};
+
 struct mrisr_sampler {
     mrisr_model* unet = nullptr;
     mrisr_model* cnet = nullptr;
@@ -629,17 +582,13 @@ struct mrisr_sampler {
     unsigned pag_mask = 0;  // perturbed-attention guidance of mrisr_sampler_run_pag: the applied transformer blocks and the scale
     float pag_scale = 0.f;
     int n_captures = 0;     // step graphs captured so far (mrisr_sampler_num_captures)
-    // per-step schedule (mrisr_sampler_set_schedule): host rows [n_steps][8] (empty: none - the scalars above rule), the
-    // device table every run with a schedule uploads them to (reserved once, so its address is the same for every such run), and what
-    // the checks and the kernel choice need of the values: some row with phi > 0 / s > 0 / g != 1 / FreeU columns other than 1
-    std::vector<float> sched;
-    DevBuf d_sched;
+    // per-step schedule (mrisr_sampler_set_schedule): rows of 8 (no table: the scalars above rule), and what the
+    // checks and the kernel choice need of the values: some row with phi > 0 / s > 0 / g != 1 / FreeU columns other than 1
+    StepTable sched{"schedule", 8};
     bool sched_phi = false, sched_s = false, sched_g = false, sched_freeu = false;
-    // conditioning strength (mrisr_sampler_set_conditioning): host rows [n_steps][4] = {c, a, 0, 0} (empty: none - every
-    // residual and feature at full strength, added as before), the device table (reserved once, one address for the sampler's life), and
-    // what the checks need of the values: some row with c != 1 / a != 1
-    std::vector<float> cond;
-    DevBuf d_cond;
+    // conditioning strength (mrisr_sampler_set_conditioning): rows {c, a, 0, 0} (no table: every residual and feature
+    // at full strength, added as before), and what the checks need of the values: some row with c != 1 / a != 1
+    StepTable cond{"conditioning", 4};
     bool cond_guess = false, cond_c = false, cond_a = false;
     std::vector<float> sigma;  // host copy of each step's noise coefficient (which steps read a step_noise slab)
     DevBuf d_ts, d_coef, d_step, d_curt, d_eps;
@@ -691,24 +640,33 @@ struct mrisr_sampler {
     }
 };
 
-// The options that exclude each other, every rule once: the first rule that (UNet state, ControlNet attached, cache interval, tiles on,
-// PAG run) violates, or null.  The setters call it with the value they are about to set, the run with what is set; always before any launch.
-// cond_table / guess: the conditioning table and guess mode of the run (the setters, which do not know the run's table, pass false).
-// skip: the skipping of neutral steps (mrisr_sampler_set_skip).
-static const char* option_conflict(const Model& U, bool has_cnet, int cache_interval, bool tiles_on, bool pag_run, bool cond_table = false,
-                                   bool guess = false, bool skip = false) {
-    const bool cached = cache_interval > 1;
-    if (skip && cached) return "skipping neutral steps together with a feature cache (interval > 1) is not supported";
-    if (cond_table && cached) return "conditioning: a conditioning table together with a feature cache (interval > 1) is not supported";
-    if (guess && pag_run) return "conditioning: guess mode in a pag run is not supported";
-    if (guess && tiles_on) return "conditioning: guess mode together with tiles is not supported";
-    if (cond_table && U.keep) return "conditioning: a training forward is being recorded";
-    if (cached && has_cnet) return "a feature cache (interval > 1) together with a ControlNet is not supported";
-    if (cached && tiles_on) return "a feature cache (interval > 1) together with tiles is not supported";
+// The options of a sampler that exclude each other.  current_options reads them off the sampler as it stands: no pag run, no conditioning
+// table, which belong to a run.  A setter overrides the one field it is about to set, the run fills in its own three.
+struct Options {
+    bool has_cnet;
+    int cache_interval;
+    bool tiles_on;
+    bool pag_run;
+    bool cond_table, guess;  // the conditioning table and guess mode of the run
+    bool skip;               // the skipping of neutral steps (mrisr_sampler_set_skip)
+};
+static Options current_options(const mrisr_sampler* s) {
+    return Options{s->cnet != nullptr, s->cache_interval, s->tile_h != 0, false, false, false, s->skip};
+}
+// Every rule once: the first one that the UNet's state and `o` violate, or null.  Always asked before any launch.
+static const char* option_conflict(const Model& U, const Options& o) {
+    const bool cached = o.cache_interval > 1;
+    if (o.skip && cached) return "skipping neutral steps together with a feature cache (interval > 1) is not supported";
+    if (o.cond_table && cached) return "conditioning: a conditioning table together with a feature cache (interval > 1) is not supported";
+    if (o.guess && o.pag_run) return "conditioning: guess mode in a pag run is not supported";
+    if (o.guess && o.tiles_on) return "conditioning: guess mode together with tiles is not supported";
+    if (o.cond_table && U.keep) return "conditioning: a training forward is being recorded";
+    if (cached && o.has_cnet) return "a feature cache (interval > 1) together with a ControlNet is not supported";
+    if (cached && o.tiles_on) return "a feature cache (interval > 1) together with tiles is not supported";
     if (cached && U.freeu.on) return "a feature cache (interval > 1) together with FreeU is not supported (mrisr_model_set_freeu)";
-    if (cached && pag_run) return "pag run: a feature cache with interval > 1 is not supported (the shallow pass skips the blocks pag perturbs)";
-    if (pag_run && U.cfg.fp8_attention) return "pag run: not supported on a UNet built with fp8_attention";
-    if (pag_run && U.keep) return "pag run: a training forward is being recorded";
+    if (cached && o.pag_run) return "pag run: a feature cache with interval > 1 is not supported (the shallow pass skips the blocks pag perturbs)";
+    if (o.pag_run && U.cfg.fp8_attention) return "pag run: not supported on a UNet built with fp8_attention";
+    if (o.pag_run && U.keep) return "pag run: a training forward is being recorded";
     if (U.freeu.on && U.keep) return "FreeU: a training forward is being recorded";
     return nullptr;
 }
@@ -825,7 +783,9 @@ int mrisr_sampler_set_cache(mrisr_sampler* s, int interval, int depth) {
     MRISR_REQUIRE(s, "null sampler");
     MRISR_REQUIRE(interval >= 1, "cache interval must be >= 1 (1: no cache)");
     MRISR_REQUIRE(depth >= 1 && depth <= s->unet->num_skips() - 1, "cache depth must lie in 1 .. num_skips - 1");
-    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, interval, s->tile_h != 0, false, false, false, s->skip);
+    Options o = current_options(s);
+    o.cache_interval = interval;
+    const char* conflict = option_conflict(*s->unet, o);
     MRISR_REQUIRE(!conflict, conflict);
     if (interval != s->cache_interval || depth != s->cache_depth) s->drop_graphs();  // the next run captures again
     s->cache_interval = interval;
@@ -845,7 +805,9 @@ int mrisr_sampler_set_tiles(mrisr_sampler* s, int tile_h, int tile_w, int overla
     MRISR_REQUIRE(overlap_h >= 0 && overlap_w >= 0 && overlap_h < tile_h && overlap_w < tile_w && overlap_h % d == 0 && overlap_w % d == 0,
                   "overlap: a multiple of 2^(num_levels-1) in 0 .. tile - 1");
     MRISR_REQUIRE(window == MRISR_TILE_UNIFORM || window == MRISR_TILE_GAUSSIAN, "window: MRISR_TILE_UNIFORM or MRISR_TILE_GAUSSIAN");
-    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, s->cache_interval, true, false);
+    Options o = current_options(s);
+    o.tiles_on = true;
+    const char* conflict = option_conflict(*s->unet, o);
     MRISR_REQUIRE(!conflict, conflict);
     if (tile_h != s->tile_h || tile_w != s->tile_w || overlap_h != s->tile_oh || overlap_w != s->tile_ow || window != s->tile_window)
         s->drop_graphs();
@@ -879,7 +841,9 @@ int mrisr_sampler_num_captures(const mrisr_sampler* s) { return s ? s->n_capture
 // The variants share one step plan, so neither value drops a graph.
 int mrisr_sampler_set_skip(mrisr_sampler* s, int on) {
     MRISR_REQUIRE(s, "null sampler");
-    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, s->cache_interval, s->tile_h != 0, false, false, false, on != 0);
+    Options o = current_options(s);
+    o.skip = on != 0;
+    const char* conflict = option_conflict(*s->unet, o);
     MRISR_REQUIRE(!conflict, conflict);
     s->skip = on != 0;
     return 0;
@@ -895,19 +859,10 @@ int mrisr_sampler_run_stats(const mrisr_sampler* s, int64_t out[4]) {
 int mrisr_sampler_set_schedule(mrisr_sampler* s, const float* rows_host, int n_rows) {
     API_BEGIN
     MRISR_REQUIRE(s, "null sampler");
-    if (!rows_host || n_rows == 0) {  // cleared: the launch constants rule again (other plan: the next run captures again)
-        MRISR_REQUIRE(!rows_host && n_rows == 0, "schedule: NULL / 0 clears it; rows need n_rows == n_steps");
-        s->sched.clear();
-        s->sched_phi = s->sched_s = s->sched_g = s->sched_freeu = false;
-        return 0;
-    }
-    MRISR_REQUIRE(n_rows == s->n_steps, "schedule: n_rows must equal the sampler's n_steps (" + std::to_string(s->n_steps) + "), got " + std::to_string(n_rows));
-    if (int rc = check_schedule_rows(rows_host, n_rows)) return rc;
-    TRY(s->d_sched.reserve(sizeof(float) * 8 * (size_t)s->n_steps, false));  // once per sampler: n_rows is always n_steps
-    s->sched.assign(rows_host, rows_host + 8 * (size_t)n_rows);
+    TRY(s->sched.set(rows_host, n_rows, s->n_steps, check_schedule_rows));
     s->sched_phi = s->sched_s = s->sched_g = s->sched_freeu = false;
-    for (int i = 0; i < n_rows; ++i) {
-        const float* r = rows_host + 8 * (size_t)i;
+    for (int i = 0; i < s->n_steps && s->sched.on(); ++i) {
+        const float* r = s->sched.row(i);
         s->sched_g |= r[0] != 1.f;
         s->sched_s |= r[1] > 0.f;
         s->sched_phi |= r[2] > 0.f;
@@ -920,21 +875,12 @@ int mrisr_sampler_set_schedule(mrisr_sampler* s, const float* rows_host, int n_r
 int mrisr_sampler_set_conditioning(mrisr_sampler* s, const float* rows_host, int n_rows, int guess_mode) {
     API_BEGIN
     MRISR_REQUIRE(s, "null sampler");
-    if (!rows_host || n_rows == 0) {  // cleared: the adds of before (other plan: the next run captures again)
-        MRISR_REQUIRE(!rows_host && n_rows == 0, "conditioning: NULL / 0 clears it; rows need n_rows == n_steps");
-        s->cond.clear();
-        s->cond_guess = s->cond_c = s->cond_a = false;
-        return 0;
-    }
-    MRISR_REQUIRE(n_rows == s->n_steps, "conditioning: n_rows must equal the sampler's n_steps (" + std::to_string(s->n_steps) + "), got " + std::to_string(n_rows));
-    if (int rc = check_conditioning_rows(rows_host, n_rows)) return rc;
-    TRY(s->d_cond.reserve(sizeof(float) * 4 * (size_t)s->n_steps, false));  // once per sampler: n_rows is always n_steps
-    s->cond.assign(rows_host, rows_host + 4 * (size_t)n_rows);
-    s->cond_guess = guess_mode != 0;
+    TRY(s->cond.set(rows_host, n_rows, s->n_steps, check_conditioning_rows));
+    s->cond_guess = s->cond.on() && guess_mode != 0;
     s->cond_c = s->cond_a = false;
-    for (int i = 0; i < n_rows; ++i) {
-        s->cond_c |= rows_host[4 * (size_t)i] != 1.f;
-        s->cond_a |= rows_host[4 * (size_t)i + 1] != 1.f;
+    for (int i = 0; i < s->n_steps && s->cond.on(); ++i) {
+        s->cond_c |= s->cond.row(i)[0] != 1.f;
+        s->cond_a |= s->cond.row(i)[1] != 1.f;
     }
     return 0;
     API_END
@@ -963,12 +909,12 @@ enum { STEP_REDUCED = 1, STEP_NO_CNET = 2, STEP_NO_INTRA = 4 };
 static int step_variant(const mrisr_sampler* s, const StepPlan& p, int n_intra, int i) {
     int v = 0;
     if (p.d_sched && p.K > 1) {
-        const float* r = &s->sched[8 * (size_t)i];
+        const float* r = s->sched.row(i);
         const bool pag_alone = p.pag && p.K == 2;
         if (r[1] == 0.f && (pag_alone || r[0] == 1.f)) v |= STEP_REDUCED;
     }
     if (p.d_cond) {
-        const float* c = &s->cond[4 * (size_t)i];
+        const float* c = s->cond.row(i);
         if (p.cnet && c[0] == 0.f) v |= STEP_NO_CNET;
         if (n_intra > 0 && c[1] == 0.f) v |= STEP_NO_INTRA;
     }
@@ -997,8 +943,10 @@ static int run_check(mrisr_sampler* s, const RunArgs& a, StepPlan& p) {
         MRISR_REQUIRE(K == 2 || K == 3, "pag run: the forward has 2B rows (pag alone) or 3B rows (with classifier-free guidance)");
         MRISR_REQUIRE(s->pag_mask != 0, "pag run: no applied block (mrisr_sampler_set_pag)");
     }
-    const bool ctab = !s->cond.empty(), guess = ctab && s->cond_guess;
-    const char* conflict = option_conflict(*s->unet, s->cnet != nullptr, s->cache_interval, s->tile_h != 0, pag, ctab, guess, s->skip);
+    const bool ctab = s->cond.on(), guess = ctab && s->cond_guess;
+    Options o = current_options(s);
+    o.pag_run = pag; o.cond_table = ctab; o.guess = guess;
+    const char* conflict = option_conflict(*s->unet, o);
     MRISR_REQUIRE(!conflict, conflict);
     Model& U = *s->unet;
     if (ctab) {  // the table only supplies values: one this run cannot honour is refused
@@ -1008,7 +956,7 @@ static int run_check(mrisr_sampler* s, const RunArgs& a, StepPlan& p) {
         MRISR_REQUIRE(!U.cond.on && (!s->cnet || !s->cnet->cond.on), "conditioning: a model handle already carries a conditioning state");
     }
     const bool guess_half = guess && K == 2 && !pag;  // the ControlNet runs on the B conditional rows only
-    const bool sched = !s->sched.empty();
+    const bool sched = s->sched.on();
     if (sched) {  // the run kind comes from the entry point; the table only supplies the values, and a value this kind cannot honour is refused
         MRISR_REQUIRE(U.freeu.on || !s->sched_freeu, "schedule: FreeU columns other than 1 need FreeU on the UNet (mrisr_model_set_freeu)");
         MRISR_REQUIRE(pag || !s->sched_s, "schedule: rows with pag_scale (s) > 0 need a pag run (mrisr_sampler_run_pag)");
@@ -1105,7 +1053,7 @@ static int run_check(mrisr_sampler* s, const RunArgs& a, StepPlan& p) {
     if (sched && (guided || U.freeu.on)) {
         // a per-step schedule: the launches take the table's address, never its values - other values, same graph.  What chooses kernels
         // is here: the rescale kernel (some phi > 0) and FreeU's table mode (the UNet's workspace generation carries a marker for it)
-        p.d_sched = static_cast<const float*>(s->d_sched.p);
+        p.d_sched = static_cast<const float*>(s->sched.dev.p);
         p.sched_rows = s->n_steps;
         if (guided) p.sched_phi = s->sched_phi ? 1 : 0;
         if (U.freeu.on) p.freeu = 2;
@@ -1120,7 +1068,7 @@ static int run_check(mrisr_sampler* s, const RunArgs& a, StepPlan& p) {
     if (ctab) {
         // the conditioning table: the launches take its address, never its values - other values, same graph.  What chooses launches is
         // here: table mode itself (the scaled adds; both workspace generations carry a marker for it), guess mode, the ControlNet's rows
-        p.d_cond = static_cast<const float*>(s->d_cond.p);
+        p.d_cond = static_cast<const float*>(s->cond.dev.p);
         p.cond_guess = guess ? 1 : 0;
         if (s->cnet) p.cnet_rows = guess_half ? B : FB;
     }
@@ -1234,20 +1182,12 @@ static int run_buffers(mrisr_sampler* s, StepPlan& p, hipStream_t st) {
             MRISR_CHECK_HIP(hipMemsetAsync(s->d_xc.p, 0, (size_t)n * sizeof(float), st));
             p.xc = static_cast<float*>(s->d_xc.p);
         }
-        // ms_rows is pageable and may be rebuilt (set_solver / set_range) right after this call returns: like the copy of s->first
-        // below, this relies on the runtime staging a pageable host-to-device copy before hipMemcpyAsync returns
+        // ms_rows is pageable and may be rebuilt (set_solver / set_range) right after this call returns: staged like the tables' rows
+        // (StepTable::upload) and the copy of s->first below
         MRISR_CHECK_HIP(hipMemcpyAsync(s->d_coef.p, s->ms_rows.data(), sizeof(float) * s->ms_rows.size(), hipMemcpyHostToDevice, st));
     }
-    if (p.d_sched) {
-        // the schedule's rows, indexed by the absolute step like the coefficient rows; s->sched is pageable and may be replaced
-        // (mrisr_sampler_set_schedule) right after this call returns: staged before hipMemcpyAsync returns, like ms_rows above
-        MRISR_REQUIRE(s->sched.size() == (size_t)8 * s->n_steps && s->d_sched.bytes >= sizeof(float) * s->sched.size(), "schedule table size");
-        MRISR_CHECK_HIP(hipMemcpyAsync(s->d_sched.p, s->sched.data(), sizeof(float) * s->sched.size(), hipMemcpyHostToDevice, st));
-    }
-    if (p.d_cond) {  // the conditioning rows, indexed by the absolute step; pageable and replaceable like s->sched above
-        MRISR_REQUIRE(s->cond.size() == (size_t)4 * s->n_steps && s->d_cond.bytes >= sizeof(float) * s->cond.size(), "conditioning table size");
-        MRISR_CHECK_HIP(hipMemcpyAsync(s->d_cond.p, s->cond.data(), sizeof(float) * s->cond.size(), hipMemcpyHostToDevice, st));
-    }
+    if (p.d_sched) TRY(s->sched.upload(s->n_steps, st));
+    if (p.d_cond) TRY(s->cond.upload(s->n_steps, st));
     MRISR_CHECK_HIP(hipMemsetAsync(s->d_step.p, 0, 16, st));
     MRISR_CHECK_HIP(hipMemcpyAsync(s->d_step.p, &s->first, sizeof(int), hipMemcpyHostToDevice, st));
     return 0;
@@ -1334,25 +1274,22 @@ static int step_body(const StepPlan& p, Model& U, Model* C, int cache_mode, int 
     TRY(U.forward_unet(&xin, &tt, nullptr, with_cnet ? res : nullptr, with_cnet ? p.n_res : 0, with_cnet ? &res[p.n_res] : nullptr, intra, n_intra,
                        &eps_t, st, p.cached ? &fc : nullptr, reduced ? &win : nullptr));
     if (tiled) TRY(launch_tile_blend(p.d_et + win_off, p.d_eps + part_off, tg, reduced ? p.B : NB, p.C, st));
-    const bool multistep = p.kind > MRISR_STEP_DDPM;
-    if (reduced) {
-        TRY(launch_reduced_step(p.K, p.kind, p.x, p.d_x2, p.d_eps + part_off, p.lr, p.noise, p.d_coef, p.d_step, p.clip, p.B, per, st, p.hist, p.xc,
-                                p.order));
-    } else if (p.K > 1) {
+    StepArgs a;
+    a.kind = p.kind; a.K = p.K;
+    a.x = p.x; a.xK = p.d_x2; a.eps = p.d_eps + part_off;
+    a.lr = p.lr; a.noise = p.noise; a.coef = p.d_coef; a.step = p.d_step; a.clip = p.clip;
+    a.B = p.B; a.per = per;
+    a.ms = MsBuf{p.hist, p.xc, p.order};
+    if (p.K > 1 && !reduced) {
         // K = 3: [eps_p; eps_u; eps_c].  K = 2 of a pag run: [eps_p; eps_c], the guided step with eps_u := eps_p and g := 1 + s
         // with a schedule table the kernel reads the three scalars from row *d_step (and forms 1 + s itself): the plan holds zeros for them
-        const bool pag_alone = p.pag && p.K == 2;
-        const float g = pag_alone ? 1.f + p.pag_scale : p.guidance_scale;
-        TRY(launch_guided_step(p.K, p.kind, p.x, p.d_x2, p.d_eps, p.lr, p.noise, p.d_coef, p.d_step, p.clip, g, p.K == 3 ? p.pag_scale : 0.f,
-                               p.guidance_rescale, p.B, per, st, p.hist, p.xc, p.order, p.d_sched, p.sched_phi, pag_alone ? 1 : 0));
-    } else if (multistep)
-        TRY(launch_multistep_step(p.x, p.d_eps, p.lr, p.d_coef, p.d_step, p.hist, p.xc, p.order, n, st));
-    else if (p.kind == MRISR_STEP_DDIM)
-        TRY(launch_ddim_step(p.x, p.d_eps, p.d_coef, p.d_step, n, st));
-    else if (p.kind == MRISR_STEP_DDPM)
-        TRY(launch_ddpm_step(p.x, p.d_eps, p.noise, p.d_coef, p.d_step, p.clip, n, st));
-    else
-        TRY(launch_resshift_step(p.x, p.d_eps, p.lr, p.noise, p.d_coef, p.d_step, n, st));
+        a.pag_alone = p.pag && p.K == 2 ? 1 : 0;
+        a.g = a.pag_alone ? 1.f + p.pag_scale : p.guidance_scale;
+        a.s = p.K == 3 ? p.pag_scale : 0.f;
+        a.phi = p.guidance_rescale;
+        a.sched = p.d_sched; a.sched_phi = p.sched_phi;
+    }
+    TRY(launch_step(a, reduced, st));
     return launch_advance_step(p.d_step, st);
 }
 
@@ -1430,36 +1367,32 @@ static int sampler_run_impl(mrisr_sampler* s, const RunArgs& a, int use_graph, v
         MRISR_CHECK_HIP(hipStreamWaitEvent(st, s->ev_in, 0));
     }
     Model& U = *s->unet;
-    // perturbed rows first: samples [0, B) of the forward, [0, B T) of a tiled one.  Set before the workspace is planned (the plan and
-    // its key see it), cleared when this call returns, also on an error path: plain forwards on the handle stay unperturbed
-    struct PagGuard {
-        Model* m = nullptr;
-        ~PagGuard() { if (m) m->pag = PagState(); }
-    } pguard;
-    if (a.pag) {
+    // What this run parks on the model handles, cleared - exactly what was set - when this call returns, also on an error path: plain
+    // forwards on the handles stay as they were.  All of it is set before the workspaces are planned (the plans and their keys see it).
+    struct RunGuard {
+        Model& U;
+        Model* C;
+        bool pag = false, freeu = false, cond = false, tproj = false;
+        ~RunGuard() {
+            if (pag) U.pag = PagState();
+            if (freeu) { U.freeu.sched = nullptr; U.freeu.step = nullptr; }
+            if (cond) { U.cond = CondState(); if (C) C->cond = CondState(); }
+            if (tproj) { U.tproj_table = nullptr; if (C) C->tproj_table = nullptr; }
+        }
+    } guard{U, s->cnet};
+    if (a.pag) {  // perturbed rows first: samples [0, B) of the forward, [0, B T) of a tiled one
         MRISR_REQUIRE(!U.pag.on(), "pag run: the UNet handle already carries a pag state (mrisr_model_set_pag); clear it first");
-        pguard.m = &U;
+        guard.pag = true;
         U.pag.mask = s->pag_mask; U.pag.first = 0; U.pag.count = p.B * p.T;
     }
-    // FreeU from the schedule table: the UNet's launches read row *d_step for the duration of this run.  Set before the workspace is planned
-    // (its key carries the mode), cleared on every exit path: plain forwards on the handle take their four values by value again
-    struct FreeUGuard {
-        Model* m = nullptr;
-        ~FreeUGuard() { if (m) { m->freeu.sched = nullptr; m->freeu.step = nullptr; } }
-    } fguard;
-    if (p.freeu == 2) {
-        fguard.m = &U;
+    if (p.freeu == 2) {  // FreeU from the schedule table: the UNet's launches read row *d_step instead of their four values
+        guard.freeu = true;
         U.freeu.sched = p.d_sched; U.freeu.step = static_cast<const int*>(s->d_step.p);
     }
-    // The conditioning table: for the duration of this run the UNet adds residuals and features with the scaled multi-tensor add and the
-    // ControlNet writes its outputs where that add reads them.  Set before the workspaces are planned (their keys carry the mode), cleared
-    // on every exit path: plain forwards on the handles add at full strength again
-    struct CondGuard {
-        Model* a = nullptr; Model* b = nullptr;
-        ~CondGuard() { if (a) a->cond = CondState(); if (b) b->cond = CondState(); }
-    } cguard;
     if (p.d_cond) {
-        cguard.a = &U; cguard.b = s->cnet;
+        // the conditioning table: the UNet adds residuals and features with the scaled multi-tensor add and the ControlNet writes its
+        // outputs where that add reads them
+        guard.cond = true;
         CondState cs;
         cs.on = true; cs.guess = p.cond_guess != 0;
         cs.table = p.d_cond; cs.step = static_cast<const int*>(s->d_step.p);
@@ -1472,11 +1405,7 @@ static int sampler_run_impl(mrisr_sampler* s, const RunArgs& a, int use_graph, v
     }
     TRY(run_operands(s, a, p, st));
     TRY(run_buffers(s, p, st));
-    struct TableGuard {  // the models must not keep pointing at this sampler's table after the run (plain forward calls compute their own)
-        Model* a = nullptr; Model* b = nullptr;
-        ~TableGuard() { if (a) a->tproj_table = nullptr; if (b) b->tproj_table = nullptr; }
-    } tguard;
-    tguard.a = &U; tguard.b = s->cnet;
+    guard.tproj = true;  // the models must not keep pointing at this sampler's table after the run (plain forward calls compute their own)
     TRY(run_temb_table(s, p, st));
     TRY(run_steps(s, p, use_graph, st));
     if (st != user) {
@@ -1487,62 +1416,72 @@ static int sampler_run_impl(mrisr_sampler* s, const RunArgs& a, int use_graph, v
     API_END
 }
 
-// ---- the single-step test entries: one static helper behind the four.  K = 1: the plain multistep step; K = 2 / 3: the guided / three-way
-// step on caller buffers xK / epsK [K B].  row_host holds `width` floats (this step kind's row), placed at row `slot` of a zeroed table; the
-// kernel sees the step counter `slot`.  hist / xc: the multistep kinds' ring and corrected state.  sched_host (K > 1): a schedule table of
-// n_rows rows, uploaded; the kernel reads {g, s, phi} from its row `slot` and g / sp / phi are not read.  reduced (K > 1): the reduced step -
-// epsK is the conditional prediction alone, [B].
-static int op_step(const char* who, int K, int step_kind, mrisr_tensor* x, mrisr_tensor* xK, const mrisr_tensor* epsK, const mrisr_tensor* lr,
-                   const mrisr_tensor* noise, const float* row_host, int width, int slot, mrisr_tensor* hist, mrisr_tensor* xc, int solver_order,
-                   float clip, float g, float sp, float phi, void* stream, const float* sched_host = nullptr, int n_rows = 0, int pag_alone = 0,
-                   bool reduced = false) {
-    const std::string w = std::string(who) + ": ", sK = std::to_string(K);
+// ---- the single-step test entries (mrisr_op_*_step): each fills an OpStep, op_step runs it.  K = 1: the plain multistep step; K = 2 / 3: the
+// guided / three-way step on caller buffers xK / eps [K B].
+struct OpStep {
+    const char* who = "";         // the message prefix of the entry
+    int K = 1, kind = 0;
+    mrisr_tensor* x = nullptr;
+    mrisr_tensor* xK = nullptr;
+    const mrisr_tensor* eps = nullptr;
+    const mrisr_tensor* lr = nullptr;
+    const mrisr_tensor* noise = nullptr;
+    const float* row_host = nullptr;  // `width` floats, this step kind's row: placed at row `slot` of a zeroed table
+    int width = 0, slot = 0;          // the kernel sees the step counter `slot`
+    mrisr_tensor* hist = nullptr;     // the multistep kinds' ring and corrected state
+    mrisr_tensor* xc = nullptr;
+    int order = 0;
+    float clip = 0.f, g = 0.f, s = 0.f, phi = 0.f;
+    const float* sched_host = nullptr;  // K > 1: a schedule table of n_rows rows, uploaded; the kernel reads {g, s, phi} from its row `slot`
+    int n_rows = 0, pag_alone = 0;      // and g / s / phi are not read
+    bool reduced = false;               // K > 1: the reduced step - eps is the conditional prediction alone, [B]
+    void* stream = nullptr;
+};
+static int op_step(const OpStep& o) {
+    const int K = o.K, slot = o.slot;
+    const std::string w = std::string(o.who) + ": ", sK = std::to_string(K);
     const std::string eps_name = K == 3 ? "eps3" : (K == 2 ? "eps2" : "eps");
-    const bool multistep = hist != nullptr;
-    MRISR_REQUIRE(x->ndim == 4 && x->dtype == MRISR_F32 && x->shape[0] > 0, w + "x must be f32 [B, C, h, w]");
-    const int B = (int)x->shape[0];
-    const long long n = numel(x), per = n / B;
+    const bool multistep = o.hist != nullptr;
+    MRISR_REQUIRE(o.x->ndim == 4 && o.x->dtype == MRISR_F32 && o.x->shape[0] > 0, w + "x must be f32 [B, C, h, w]");
+    const int B = (int)o.x->shape[0];
+    const long long n = numel(o.x), per = n / B;
     if (multistep) MRISR_REQUIRE(per % 4 == 0, w + "C*h*w must be a multiple of 4");
-    if (reduced) MRISR_REQUIRE(epsK->dtype == MRISR_F32 && numel(epsK) == n, w + "eps must be f32 [B, C, h, w]: the conditional prediction");
-    else MRISR_REQUIRE(epsK->dtype == MRISR_F32 && numel(epsK) == K * n, w + eps_name + " must be f32 [" + (K > 1 ? sK : "") + "B, C, h, w]");
-    if (xK) MRISR_REQUIRE(xK->dtype == MRISR_F32 && numel(xK) == K * n, w + "the staging buffer must be f32 [" + sK + "B, C, h, w]");
-    if (lr) MRISR_REQUIRE(lr->dtype == MRISR_F32 && numel(lr) == n, w + "lr must be f32 [B, C, h, w]");
+    if (o.reduced) MRISR_REQUIRE(o.eps->dtype == MRISR_F32 && numel(o.eps) == n, w + "eps must be f32 [B, C, h, w]: the conditional prediction");
+    else MRISR_REQUIRE(o.eps->dtype == MRISR_F32 && numel(o.eps) == K * n, w + eps_name + " must be f32 [" + (K > 1 ? sK : "") + "B, C, h, w]");
+    if (o.xK) MRISR_REQUIRE(o.xK->dtype == MRISR_F32 && numel(o.xK) == K * n, w + "the staging buffer must be f32 [" + sK + "B, C, h, w]");
+    if (o.lr) MRISR_REQUIRE(o.lr->dtype == MRISR_F32 && numel(o.lr) == n, w + "lr must be f32 [B, C, h, w]");
     // (the kernel reads slab `slot` of the noise: the single-slab entries run at slot 0, the scheduled one hands in slot + 1 slabs)
-    if (noise) MRISR_REQUIRE(noise->dtype == MRISR_F32 && numel(noise) == (long long)(slot + 1) * n,
-                             w + (slot ? "noise must be f32 [slot + 1, B, C, h, w]: one slab per step up to this one" : "noise must be one f32 [B, C, h, w] slab"));
-    if (multistep) MRISR_REQUIRE(hist->dtype == MRISR_F32 && numel(hist) == (long long)solver_order * n, w + "hist must be f32 [order, B, C, h, w]");
-    if (xc) MRISR_REQUIRE(xc->dtype == MRISR_F32 && numel(xc) == n, w + "xc must be f32 [B, C, h, w]");
-    hipStream_t st = (hipStream_t)stream;
+    if (o.noise) MRISR_REQUIRE(o.noise->dtype == MRISR_F32 && numel(o.noise) == (long long)(slot + 1) * n,
+                               w + (slot ? "noise must be f32 [slot + 1, B, C, h, w]: one slab per step up to this one" : "noise must be one f32 [B, C, h, w] slab"));
+    if (multistep) MRISR_REQUIRE(o.hist->dtype == MRISR_F32 && numel(o.hist) == (long long)o.order * n, w + "hist must be f32 [order, B, C, h, w]");
+    if (o.xc) MRISR_REQUIRE(o.xc->dtype == MRISR_F32 && numel(o.xc) == n, w + "xc must be f32 [B, C, h, w]");
+    hipStream_t st = (hipStream_t)o.stream;
     // the table's row pitch of this kind (load_step_row / multistep_value4): at slot 0, where the first-order entries run, any pitch serves
-    const int pitch = multistep ? MS_ROW : (step_kind == MRISR_STEP_DDIM ? 2 : (step_kind == MRISR_STEP_RESSHIFT ? 4 : 8));
+    const int pitch = multistep ? MS_ROW : (o.kind == MRISR_STEP_DDIM ? 2 : (o.kind == MRISR_STEP_RESSHIFT ? 4 : 8));
     std::vector<float> rows((size_t)(slot + 1) * pitch, 0.f);
-    std::copy(row_host, row_host + width, rows.begin() + (size_t)slot * pitch);
-    DevBuf d_rows, d_step;
+    std::copy(o.row_host, o.row_host + o.width, rows.begin() + (size_t)slot * pitch);
+    DevBuf d_rows, d_step, d_sched;
     TRY(d_rows.reserve(sizeof(float) * rows.size(), false));
     TRY(d_step.reserve(16, true));
     MRISR_CHECK_HIP(hipMemcpyAsync(d_rows.p, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice, st));
     MRISR_CHECK_HIP(hipMemsetAsync(d_step.p, 0, 16, st));
     MRISR_CHECK_HIP(hipMemcpyAsync(d_step.p, &slot, sizeof(int), hipMemcpyHostToDevice, st));
-    DevBuf d_sched;
-    int sched_phi = 0;
-    if (sched_host) {
-        TRY(d_sched.reserve(sizeof(float) * 8 * (size_t)n_rows, false));
-        MRISR_CHECK_HIP(hipMemcpyAsync(d_sched.p, sched_host, sizeof(float) * 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
-        for (int i = 0; i < n_rows; ++i) sched_phi |= sched_host[8 * (size_t)i + 2] > 0.f ? 1 : 0;
+    auto f32 = [](const mrisr_tensor* t) { return t ? static_cast<float*>(t->data) : nullptr; };
+    StepArgs a;
+    a.kind = o.kind; a.K = K;
+    a.x = f32(o.x); a.xK = f32(o.xK); a.eps = f32(o.eps); a.lr = f32(o.lr); a.noise = f32(o.noise);
+    a.coef = static_cast<const float*>(d_rows.p); a.step = static_cast<const int*>(d_step.p);
+    a.clip = o.clip; a.g = o.g; a.s = o.s; a.phi = o.phi;
+    a.B = B; a.per = per;
+    a.ms = MsBuf{f32(o.hist), f32(o.xc), o.order};
+    if (o.sched_host) {
+        TRY(d_sched.reserve(sizeof(float) * 8 * (size_t)o.n_rows, false));
+        MRISR_CHECK_HIP(hipMemcpyAsync(d_sched.p, o.sched_host, sizeof(float) * 8 * (size_t)o.n_rows, hipMemcpyHostToDevice, st));
+        a.sched = static_cast<const float*>(d_sched.p);
+        a.pag_alone = o.pag_alone;
+        for (int i = 0; i < o.n_rows; ++i) a.sched_phi |= o.sched_host[8 * (size_t)i + 2] > 0.f ? 1 : 0;
     }
-    float* h = hist ? (float*)hist->data : nullptr;
-    float* c = xc ? (float*)xc->data : nullptr;
-    if (reduced)
-        TRY(launch_reduced_step(K, step_kind, (float*)x->data, (float*)xK->data, (const float*)epsK->data, lr ? (const float*)lr->data : nullptr,
-                                noise ? (const float*)noise->data : nullptr, (const float*)d_rows.p, (const int*)d_step.p, clip, B, per, st, h, c,
-                                solver_order));
-    else if (K > 1)
-        TRY(launch_guided_step(K, step_kind, (float*)x->data, (float*)xK->data, (const float*)epsK->data, lr ? (const float*)lr->data : nullptr,
-                               noise ? (const float*)noise->data : nullptr, (const float*)d_rows.p, (const int*)d_step.p, clip, g, sp, phi, B, per,
-                               st, h, c, solver_order, (const float*)d_sched.p, sched_phi, pag_alone));
-    else
-        TRY(launch_multistep_step((float*)x->data, (const float*)epsK->data, lr ? (const float*)lr->data : nullptr, (const float*)d_rows.p,
-                                  (const int*)d_step.p, h, c, solver_order, n, st));
+    TRY(launch_step(a, o.reduced, st));
     MRISR_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -1574,8 +1513,12 @@ int mrisr_op_guided_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, const
     API_BEGIN
     MRISR_REQUIRE(x && x2 && eps2 && coef_row_host, "guided step: null argument");
     MRISR_REQUIRE(step_kind >= MRISR_STEP_DDIM && step_kind <= MRISR_STEP_DDPM, "guided step: unknown step kind");
-    return op_step("guided step", 2, step_kind, x, x2, eps2, lr, noise, coef_row_host, row_width(step_kind), 0, nullptr, nullptr, 0, clip,
-                   guidance_scale, 0.f, guidance_rescale, stream);
+    OpStep o;
+    o.who = "guided step"; o.K = 2; o.kind = step_kind; o.stream = stream;
+    o.x = x; o.xK = x2; o.eps = eps2; o.lr = lr; o.noise = noise;
+    o.row_host = coef_row_host; o.width = row_width(step_kind);
+    o.clip = clip; o.g = guidance_scale; o.phi = guidance_rescale;
+    return op_step(o);
     API_END
 }
 // the three-way step alone: as mrisr_op_guided_step with x3 / eps3 [3B] = [perturbed; uncond; cond]
@@ -1585,8 +1528,12 @@ int mrisr_op_pag_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x3, const mr
     API_BEGIN
     MRISR_REQUIRE(x && x3 && eps3 && coef_row_host, "pag step: null argument");
     MRISR_REQUIRE(step_kind >= MRISR_STEP_DDIM && step_kind <= MRISR_STEP_DDPM, "pag step: unknown step kind");
-    return op_step("pag step", 3, step_kind, x, x3, eps3, lr, noise, coef_row_host, row_width(step_kind), 0, nullptr, nullptr, 0, clip,
-                   guidance_scale, pag_scale, guidance_rescale, stream);
+    OpStep o;
+    o.who = "pag step"; o.K = 3; o.kind = step_kind; o.stream = stream;
+    o.x = x; o.xK = x3; o.eps = eps3; o.lr = lr; o.noise = noise;
+    o.row_host = coef_row_host; o.width = row_width(step_kind);
+    o.clip = clip; o.g = guidance_scale; o.s = pag_scale; o.phi = guidance_rescale;
+    return op_step(o);
     API_END
 }
 // the multistep step alone (parity test): row_host = one 16-float row; slot = the step counter the kernel sees; x2 given: the guided form
@@ -1598,8 +1545,13 @@ int mrisr_op_multistep_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x2, co
     MRISR_REQUIRE(step_kind == MRISR_STEP_UNIPC || step_kind == MRISR_STEP_DPMSOLVERPP, "multistep step: UniPC or DPM-Solver++");
     MRISR_REQUIRE(solver_order >= 1 && solver_order <= 3 && slot >= 0 && slot < 1024, "multistep step: solver order 1..3, slot 0..1023");
     MRISR_REQUIRE((step_kind == MRISR_STEP_UNIPC) == (xc != nullptr), "multistep step: the corrected-state buffer belongs to UniPC");
-    return op_step("multistep step", x2 ? 2 : 1, step_kind, x, x2, eps, lr, nullptr, row_host, 16, slot, hist, xc, solver_order, 0.f, guidance_scale,
-                   0.f, guidance_rescale, stream);
+    OpStep o;
+    o.who = "multistep step"; o.K = x2 ? 2 : 1; o.kind = step_kind; o.stream = stream;
+    o.x = x; o.xK = x2; o.eps = eps; o.lr = lr;
+    o.row_host = row_host; o.width = MS_ROW; o.slot = slot;
+    o.hist = hist; o.xc = xc; o.order = solver_order;
+    o.g = guidance_scale; o.phi = guidance_rescale;
+    return op_step(o);
     API_END
 }
 // the three-way step of the multistep kinds alone: mrisr_op_multistep_step's guided form with x3 / eps3 [3B]
@@ -1611,8 +1563,13 @@ int mrisr_op_pag_multistep_step(int step_kind, mrisr_tensor* x, mrisr_tensor* x3
     MRISR_REQUIRE(step_kind == MRISR_STEP_UNIPC || step_kind == MRISR_STEP_DPMSOLVERPP, "pag multistep step: UniPC or DPM-Solver++");
     MRISR_REQUIRE(solver_order >= 1 && solver_order <= 3 && slot >= 0 && slot < 1024, "pag multistep step: solver order 1..3, slot 0..1023");
     MRISR_REQUIRE((step_kind == MRISR_STEP_UNIPC) == (xc != nullptr), "pag multistep step: the corrected-state buffer belongs to UniPC");
-    return op_step("pag multistep step", 3, step_kind, x, x3, eps3, lr, nullptr, row_host, 16, slot, hist, xc, solver_order, 0.f, guidance_scale,
-                   pag_scale, guidance_rescale, stream);
+    OpStep o;
+    o.who = "pag multistep step"; o.K = 3; o.kind = step_kind; o.stream = stream;
+    o.x = x; o.xK = x3; o.eps = eps3; o.lr = lr;
+    o.row_host = row_host; o.width = MS_ROW; o.slot = slot;
+    o.hist = hist; o.xc = xc; o.order = solver_order;
+    o.g = guidance_scale; o.s = pag_scale; o.phi = guidance_rescale;
+    return op_step(o);
     API_END
 }
 // the guided step with its three scalars read from a schedule table (parity test): the K = 2 step of classifier-free guidance, the K = 2
@@ -1636,9 +1593,14 @@ int mrisr_op_scheduled_step(int step_kind, int K, int pag_alone, mrisr_tensor* x
         MRISR_REQUIRE((step_kind == MRISR_STEP_UNIPC) == (xc != nullptr), "scheduled step: the corrected-state buffer belongs to UniPC");
     } else
         MRISR_REQUIRE(!hist && !xc, "scheduled step: hist / xc belong to the multistep kinds");
-    return op_step("scheduled step", K, step_kind, x, xK, epsK, lr, noise, row_host, multistep ? 16 : row_width(step_kind), slot,
-                   multistep ? hist : nullptr, multistep ? xc : nullptr, multistep ? solver_order : 0, clip, 0.f, 0.f, 0.f, stream, sched_host, n_rows,
-                   pag_alone ? 1 : 0);
+    OpStep o;
+    o.who = "scheduled step"; o.K = K; o.kind = step_kind; o.stream = stream;
+    o.x = x; o.xK = xK; o.eps = epsK; o.lr = lr; o.noise = noise;
+    o.row_host = row_host; o.width = multistep ? MS_ROW : row_width(step_kind); o.slot = slot;
+    o.hist = hist; o.xc = xc; o.order = multistep ? solver_order : 0;
+    o.clip = clip;
+    o.sched_host = sched_host; o.n_rows = n_rows; o.pag_alone = pag_alone ? 1 : 0;
+    return op_step(o);
     API_END
 }
 
@@ -1659,8 +1621,13 @@ int mrisr_op_reduced_step(int step_kind, int K, mrisr_tensor* x, mrisr_tensor* x
         MRISR_REQUIRE((step_kind == MRISR_STEP_UNIPC) == (xc != nullptr), "reduced step: the corrected-state buffer belongs to UniPC");
     } else
         MRISR_REQUIRE(!hist && !xc, "reduced step: hist / xc belong to the multistep kinds");
-    return op_step("reduced step", K, step_kind, x, xK, eps, lr, noise, row_host, multistep ? 16 : row_width(step_kind), slot,
-                   multistep ? hist : nullptr, multistep ? xc : nullptr, multistep ? solver_order : 0, clip, 0.f, 0.f, 0.f, stream, nullptr, 0, 0, true);
+    OpStep o;
+    o.who = "reduced step"; o.K = K; o.kind = step_kind; o.stream = stream; o.reduced = true;
+    o.x = x; o.xK = xK; o.eps = eps; o.lr = lr; o.noise = noise;
+    o.row_host = row_host; o.width = multistep ? MS_ROW : row_width(step_kind); o.slot = slot;
+    o.hist = hist; o.xc = xc; o.order = multistep ? solver_order : 0;
+    o.clip = clip;
+    return op_step(o);
     API_END
 }
 }  // extern "C"

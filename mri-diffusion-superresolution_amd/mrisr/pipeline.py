@@ -10,7 +10,7 @@ plus ``sample`` - the timestep loop itself (``:63-96``) as ONE call into the C-A
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -458,6 +458,101 @@ def _tile_crops(x, ys, xs, s_h, s_w):
     return torch.stack(crops, dim=1).flatten(0, 1).contiguous()
 
 
+def _build_schedule(n_steps, timesteps, n_train, freeu, schedule, pag_adaptive_scale, guidance_interval, pag_interval, freeu_interval, g, phi,
+                    pag_scale, pag_on, has_uncond):
+    """The schedule table of a ``Sampler.run`` (float32 [n_steps, 8]) or None: no table, the call of before.  ``timesteps`` / ``n_train``:
+    the sampler's grid; ``freeu``: the UNet's ``enable_freeu`` state or None.  Everything is checked here, before anything is launched."""
+    ad = _finite("pag_adaptive_scale", pag_adaptive_scale, 0.0)
+    ivs = {"guidance_interval": guidance_interval, "pag_interval": pag_interval, "freeu_interval": freeu_interval}
+    ivs = {k: (FULL_INTERVAL if v is None else _check_interval(k, v)) for k, v in ivs.items()}
+    given = [k for k, v in ivs.items() if v != FULL_INTERVAL] + (["pag_adaptive_scale"] if ad > 0.0 else [])
+    if schedule is not None:
+        if given:
+            raise ValueError(f"schedule is an explicit table: it excludes {', '.join(given)}")
+        return check_schedule(schedule, n_steps)
+    if not given:
+        return None
+    if (ad > 0.0 or ivs["pag_interval"] != FULL_INTERVAL) and not pag_on:
+        raise ValueError("pag_adaptive_scale / pag_interval need perturbed-attention guidance: pag_scale > 0")
+    if ivs["guidance_interval"] != FULL_INTERVAL and not (has_uncond and float(g) != 1.0):
+        raise ValueError("guidance_interval needs active classifier-free guidance: uncond_hidden_states and guidance_scale != 1")
+    if ivs["freeu_interval"] != FULL_INTERVAL and freeu is None:
+        raise ValueError("freeu_interval needs FreeU on the UNet (unet.enable_freeu): it schedules that state's four values")
+    return step_schedule(timesteps, guidance_scale=g if has_uncond else 1.0, guidance_rescale=phi, pag_scale=pag_scale,
+                         pag_adaptive_scale=ad, guidance_interval=ivs["guidance_interval"], pag_interval=ivs["pag_interval"],
+                         freeu=freeu, freeu_interval=ivs["freeu_interval"], num_train_timesteps=n_train)
+
+
+def _build_conditioning(n_steps, has_controlnet, tiles_on, cache_interval, conditioning, c_scale, start, end, a_scale, factor, guess_mode,
+                        pag_on, has_features):
+    """(table, guess) of a ``Sampler.run`` - float32 [n_steps, 4] and a bool - or None: no table, the call of before.  Everything is
+    checked here, before anything is launched."""
+    named = {"controlnet_conditioning_scale": (c_scale, 1.0), "control_guidance_start": (start, 0.0),
+             "control_guidance_end": (end, 1.0), "adapter_conditioning_scale": (a_scale, 1.0),
+             "adapter_conditioning_factor": (factor, 1.0)}
+    given = [k for k, (v, d) in named.items() if _finite(k, v) != d]
+    guess = bool(guess_mode)
+    if conditioning is not None:
+        if given:
+            raise ValueError(f"conditioning is an explicit table: it excludes {', '.join(given)}")
+        table = check_conditioning(conditioning, n_steps)
+    elif given or guess:
+        table = conditioning_schedule(n_steps, c_scale, start, end, a_scale, factor)
+    else:
+        return None
+    if not has_controlnet and (guess or (table[:, 0] != 1).any()):
+        raise ValueError("controlnet_conditioning_scale / control_guidance_start / control_guidance_end / guess_mode need a sampler "
+                         "with a ControlNet")
+    if not has_features and (table[:, 1] != 1).any():
+        raise ValueError("adapter_conditioning_scale / adapter_conditioning_factor need adapter_features")
+    if guess and pag_on:
+        raise ValueError("guess_mode together with perturbed-attention guidance (pag_scale > 0) is not supported")
+    if guess and tiles_on:
+        raise ValueError("guess_mode together with tiles is not supported")
+    if cache_interval > 1:
+        raise ValueError("a conditioning table together with a feature cache (interval > 1) is not supported")
+    return table, guess
+
+
+class _Run(NamedTuple):
+    """What one ``Sampler.run`` asks of the library: built once every check of ``run`` has passed, consumed by ``Sampler._launch``."""
+    entry: str                       # "mrisr_sampler_run" (one context), "mrisr_sampler_run_guided" ([unconditional; conditional],
+    contexts: tuple                  # diffusers' order) or "mrisr_sampler_run_pag" ([perturbed; (unconditional;) conditional])
+    extra: tuple = ()                # the entry's arguments between the feature count and ``use_graph``
+    setters: tuple = ()              # (setter, arguments after the handle): the scalar guidance / PAG values, set before the run
+    schedule: Optional[np.ndarray] = None  # the schedule table of this run
+    conditioning: Optional[tuple] = None   # (conditioning table, guess)
+    skip: bool = False
+    tile_plan: Optional[tuple] = None      # ``Sampler._tile_plan``
+    cond_at_B: bool = False          # guess mode under classifier-free guidance: the ControlNet sees [B] rows, its image stays [B]
+
+
+def _pag_run(latents, ehs_c, ehs_u, g, guidance_rescale, s, mask) -> dict:
+    """The ``_Run`` fields of a PAG run: the rows [perturbed; conditional] or, with active classifier-free guidance, [perturbed;
+    unconditional; conditional]; perturbed rows carry the conditional context."""
+    B, phi = latents.shape[0], float(guidance_rescale)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale!r}")
+    # (with PAG the rescale rule needs no active classifier-free guidance: check_guidance sees phi only when CFG can be active)
+    cfg_given = ehs_u is not None and float(g) != 1.0
+    with_cfg = check_guidance(g, phi if cfg_given else 0.0, ehs_c.shape, None if ehs_u is None else ehs_u.shape, B)
+    if latents.ndim != 4 or int(np.prod(latents.shape[1:])) % 4:
+        raise ValueError("pag_scale > 0 needs [B,C,h,w] latents with C*h*w a multiple of 4")
+    if ehs_c.ndim != 3 or ehs_c.shape[0] not in (1, B):
+        raise ValueError(f"encoder_hidden_states must be [1, L, D] or [{B}, L, D], got {tuple(ehs_c.shape)}")
+    return dict(entry="mrisr_sampler_run_pag", contexts=(ehs_c, ehs_u, ehs_c) if with_cfg else (ehs_c, ehs_c),
+                extra=(1 if with_cfg else 0,),
+                setters=(("mrisr_sampler_set_guidance", (float(g), phi)), ("mrisr_sampler_set_pag", (mask, s))))
+
+
+def _guided_run(latents, ehs_c, ehs_u, g, phi, guess) -> dict:
+    """The ``_Run`` fields of a run under classifier-free guidance."""
+    if int(np.prod(latents.shape[1:])) % 4:
+        raise ValueError("guided sampling needs C*h*w of the latents to be a multiple of 4")
+    return dict(entry="mrisr_sampler_run_guided", contexts=(ehs_u, ehs_c), setters=(("mrisr_sampler_set_guidance", (g, phi)),),
+                cond_at_B=guess)
+
+
 class Sampler:
     """Owns a C-ABI sampler (device tables + the captured step graph) for one (unet, controlnet, schedule)."""
 
@@ -489,7 +584,8 @@ class Sampler:
         ac = scheduler.alphas_cumprod.detach().cpu().to(torch.float32).numpy().copy()
         self.n_steps = len(ts)
         self._timesteps, self._n_train = ts, len(ac)  # what ``step_schedule`` needs to build a table for this sampler
-        self._scheduled = False                       # whether the library holds a schedule table from the previous run
+        # what the previous run left in the library: a schedule table, a conditioning table, the skip flag
+        self._scheduled, self._conditioned, self._skipping = False, False, False
         self._h = C.c_void_p()
         L.check(L.lib().mrisr_sampler_create(unet._h, controlnet._h if controlnet is not None else None,
                                              kinds[kind],
@@ -502,7 +598,7 @@ class Sampler:
 
     def __del__(self):
         try:
-            if getattr(self, "_h", None) and self._h.value:
+            if self._h.value:
                 L.lib().mrisr_sampler_destroy(self._h)
                 self._h = C.c_void_p()
         except Exception:
@@ -527,7 +623,7 @@ class Sampler:
         the step graph and the result of a sampler that never had one.  Changing either value captures the step graphs again."""
         interval, depth = check_cache(interval, depth, int(L.lib().mrisr_model_num_skips(self.unet._h)), self.controlnet is not None)
         self._check_cache_with(interval)
-        if getattr(self, "_skipping", False):  # skip_neutral is an argument of each run: what the last one left in the library is not a conflict
+        if self._skipping:  # skip_neutral is an argument of each run: what the last one left in the library is not a conflict
             L.check(L.lib().mrisr_sampler_set_skip(self._h, 0))
             self._skipping = False
         L.check(L.lib().mrisr_sampler_set_cache(self._h, interval, depth))
@@ -536,9 +632,9 @@ class Sampler:
     def _check_cache_with(self, interval: int):
         """What a feature cache of ``interval`` excludes on this sampler as it stands: FreeU on the UNet (which carries that state; ``run``
         takes no argument for it) and tiles.  ``set_cache`` asks with the interval it is about to set, ``run`` with the one that is set."""
-        if interval > 1 and getattr(self.unet, "freeu", None) is not None:
+        if interval > 1 and self.unet.freeu is not None:
             raise ValueError("a feature cache (interval > 1) together with FreeU (unet.enable_freeu) is not supported")
-        if interval > 1 and getattr(self, "tiles", None) is not None:
+        if interval > 1 and self.tiles is not None:
             raise ValueError("a feature cache (interval > 1) together with tiles is not supported")
 
     @property
@@ -557,13 +653,13 @@ class Sampler:
             L.check(L.lib().mrisr_sampler_set_tiles(self._h, 0, 0, 0, 0, 0))
             self.tiles = None
             return
-        t_h, t_w, o_h, o_w, window = check_tiles(tile, overlap, window, self.divisor, getattr(self, "cache_interval", 1) > 1)
+        t_h, t_w, o_h, o_w, window = check_tiles(tile, overlap, window, self.divisor, self.cache_interval > 1)
         L.check(L.lib().mrisr_sampler_set_tiles(self._h, t_h, t_w, o_h, o_w, L.TILE_WINDOWS[window]))
         self.tiles = (t_h, t_w, o_h, o_w, window)
 
     def _tile_plan(self, h: int, w: int):
         """(origins_y, origins_x, t_h, t_w) of a canvas of h x w latents, or None when the run is not tiled (off, or one tile)."""
-        if getattr(self, "tiles", None) is None:
+        if self.tiles is None:
             return None
         t_h, t_w, o_h, o_w, window = self.tiles
         d = self.divisor
@@ -663,7 +759,7 @@ class Sampler:
             if lr_latents is not None and tuple(lr_latents.shape) != tuple(latents.shape):
                 raise ValueError(f"lr_latents must have the latents' shape {tuple(latents.shape)}, got {tuple(lr_latents.shape)}")
         self._check_cache_with(self.cache_interval)
-        self._pending_skip = check_skip(skip_neutral, self.cache_interval)
+        skip = check_skip(skip_neutral, self.cache_interval)
         plan = None
         if self.tiles is not None:  # a tiled run: the canvas and everything shaped after it is checked here, before any launch
             if latents.ndim != 4:
@@ -671,143 +767,29 @@ class Sampler:
             plan = self._tile_plan(latents.shape[2], latents.shape[3])
         pag_mask = check_pag(pag_scale, pag_applied_layers, transformer_block_names(self.unet.config),
                              self.cache_interval > 1, self.unet.fp8_attention)
-        self._pending_schedule = self._build_schedule(schedule, pag_adaptive_scale, guidance_interval, pag_interval, freeu_interval,
-                                                      guidance_scale, guidance_rescale, pag_scale, bool(pag_mask),
-                                                      uncond_hidden_states is not None)
-        self._pending_conditioning = self._build_conditioning(conditioning, controlnet_conditioning_scale, control_guidance_start,
-                                                              control_guidance_end, adapter_conditioning_scale,
-                                                              adapter_conditioning_factor, guess_mode, bool(pag_mask),
-                                                              bool(adapter_features))
+        table = _build_schedule(self.n_steps, self._timesteps, self._n_train, self.unet.freeu, schedule, pag_adaptive_scale,
+                                guidance_interval, pag_interval, freeu_interval, guidance_scale, guidance_rescale, pag_scale, bool(pag_mask),
+                                uncond_hidden_states is not None)
+        conditioning = _build_conditioning(self.n_steps, self.controlnet is not None, self.tiles is not None, self.cache_interval,
+                                           conditioning, controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
+                                           adapter_conditioning_scale, adapter_conditioning_factor, guess_mode, bool(pag_mask),
+                                           bool(adapter_features))
         if pag_mask:
-            return self._run_pag(latents, encoder_hidden_states, uncond_hidden_states, lr_latents, step_noise, controlnet_cond,
-                                 adapter_features, use_graph, guidance_scale, guidance_rescale, float(pag_scale), pag_mask, plan)
-        if check_guidance(guidance_scale, guidance_rescale, encoder_hidden_states.shape,
-                          None if uncond_hidden_states is None else uncond_hidden_states.shape, latents.shape[0]):
-            return self._run_guided(latents, encoder_hidden_states, uncond_hidden_states, lr_latents, step_noise, controlnet_cond,
-                                    adapter_features, use_graph, float(guidance_scale), float(guidance_rescale), plan)
-        return self._launch(L.lib().mrisr_sampler_run, latents, (encoder_hidden_states,), lr_latents, step_noise, controlnet_cond,
-                            adapter_features, use_graph, plan)
-
-    def _build_schedule(self, schedule, pag_adaptive_scale, guidance_interval, pag_interval, freeu_interval, g, phi, pag_scale, pag_on,
-                        has_uncond):
-        """The schedule table of this ``run`` (float32 [n_steps, 8]) or None: no table, the call of before.  Everything is checked here,
-        before anything is launched."""
-        ad = _finite("pag_adaptive_scale", pag_adaptive_scale, 0.0)
-        ivs = {"guidance_interval": guidance_interval, "pag_interval": pag_interval, "freeu_interval": freeu_interval}
-        ivs = {k: (FULL_INTERVAL if v is None else _check_interval(k, v)) for k, v in ivs.items()}
-        given = [k for k, v in ivs.items() if v != FULL_INTERVAL] + (["pag_adaptive_scale"] if ad > 0.0 else [])
-        if schedule is not None:
-            if given:
-                raise ValueError(f"schedule is an explicit table: it excludes {', '.join(given)}")
-            return check_schedule(schedule, self.n_steps)
-        if not given:
-            return None
-        if (ad > 0.0 or ivs["pag_interval"] != FULL_INTERVAL) and not pag_on:
-            raise ValueError("pag_adaptive_scale / pag_interval need perturbed-attention guidance: pag_scale > 0")
-        if ivs["guidance_interval"] != FULL_INTERVAL and not (has_uncond and float(g) != 1.0):
-            raise ValueError("guidance_interval needs active classifier-free guidance: uncond_hidden_states and guidance_scale != 1")
-        freeu = getattr(self.unet, "freeu", None)
-        if ivs["freeu_interval"] != FULL_INTERVAL and freeu is None:
-            raise ValueError("freeu_interval needs FreeU on the UNet (unet.enable_freeu): it schedules that state's four values")
-        return step_schedule(self._timesteps, guidance_scale=g if has_uncond else 1.0, guidance_rescale=phi, pag_scale=pag_scale,
-                             pag_adaptive_scale=ad, guidance_interval=ivs["guidance_interval"], pag_interval=ivs["pag_interval"],
-                             freeu=freeu, freeu_interval=ivs["freeu_interval"], num_train_timesteps=self._n_train)
-
-    def _build_conditioning(self, conditioning, c_scale, start, end, a_scale, factor, guess_mode, pag_on, has_features):
-        """(table, guess) of this ``run`` - float32 [n_steps, 4] and a bool - or None: no table, the call of before.  Everything is checked
-        here, before anything is launched."""
-        named = {"controlnet_conditioning_scale": (c_scale, 1.0), "control_guidance_start": (start, 0.0),
-                 "control_guidance_end": (end, 1.0), "adapter_conditioning_scale": (a_scale, 1.0),
-                 "adapter_conditioning_factor": (factor, 1.0)}
-        given = [k for k, (v, d) in named.items() if _finite(k, v) != d]
-        guess = bool(guess_mode)
-        if conditioning is not None:
-            if given:
-                raise ValueError(f"conditioning is an explicit table: it excludes {', '.join(given)}")
-            table = check_conditioning(conditioning, self.n_steps)
-        elif given or guess:
-            table = conditioning_schedule(self.n_steps, c_scale, start, end, a_scale, factor)
+            kind = _pag_run(latents, encoder_hidden_states, uncond_hidden_states, guidance_scale, guidance_rescale, float(pag_scale), pag_mask)
+        elif check_guidance(guidance_scale, guidance_rescale, encoder_hidden_states.shape,
+                            None if uncond_hidden_states is None else uncond_hidden_states.shape, latents.shape[0]):
+            kind = _guided_run(latents, encoder_hidden_states, uncond_hidden_states, float(guidance_scale), float(guidance_rescale),
+                               conditioning is not None and conditioning[1])
         else:
-            return None
-        if self.controlnet is None and (guess or (table[:, 0] != 1).any()):
-            raise ValueError("controlnet_conditioning_scale / control_guidance_start / control_guidance_end / guess_mode need a sampler "
-                             "with a ControlNet")
-        if not has_features and (table[:, 1] != 1).any():
-            raise ValueError("adapter_conditioning_scale / adapter_conditioning_factor need adapter_features")
-        if guess and pag_on:
-            raise ValueError("guess_mode together with perturbed-attention guidance (pag_scale > 0) is not supported")
-        if guess and getattr(self, "tiles", None) is not None:
-            raise ValueError("guess_mode together with tiles is not supported")
-        if getattr(self, "cache_interval", 1) > 1:
-            raise ValueError("a conditioning table together with a feature cache (interval > 1) is not supported")
-        return table, guess
+            kind = dict(entry="mrisr_sampler_run", contexts=(encoder_hidden_states,))
+        return self._launch(_Run(schedule=table, conditioning=conditioning, skip=skip, tile_plan=plan, **kind), latents, lr_latents,
+                            step_noise, controlnet_cond, adapter_features, use_graph)
 
-    def _apply_conditioning(self):
-        """Hands the conditioning table of this run to the library, or clears the one an earlier run left there."""
-        pending, self._pending_conditioning = getattr(self, "_pending_conditioning", None), None
-        if pending is not None:
-            table, guess = pending
-            L.check(L.lib().mrisr_sampler_set_conditioning(self._h, table.ctypes.data_as(C.c_void_p), int(table.shape[0]), 1 if guess else 0))
-            self._conditioned = True
-        elif getattr(self, "_conditioned", False):
-            L.check(L.lib().mrisr_sampler_set_conditioning(self._h, None, 0, 0))
-            self._conditioned = False
-
-    def _apply_schedule(self):
-        """Hands the table of this run to the library, or clears the one an earlier run left there."""
-        table, self._pending_schedule = getattr(self, "_pending_schedule", None), None
-        if table is not None:
-            L.check(L.lib().mrisr_sampler_set_schedule(self._h, table.ctypes.data_as(C.c_void_p), int(table.shape[0])))
-            self._scheduled = True
-        elif getattr(self, "_scheduled", False):
-            L.check(L.lib().mrisr_sampler_set_schedule(self._h, None, 0))
-            self._scheduled = False
-
-    @property
-    def last_run_stats(self) -> dict:
-        """What the last ``run`` did, from the library's own count: ``unet_rows`` (the sum over its steps of the rows of the UNet forward),
-        ``controlnet_steps`` (steps that ran the ControlNet), ``feature_steps`` (steps that took adapter features), ``variants`` (distinct
-        step variants, ``step_variants``) and ``captures`` (step graphs this sampler has captured so far)."""
-        out = (C.c_int64 * 4)()
-        L.check(L.lib().mrisr_sampler_run_stats(self._h, out))
-        return {"unet_rows": int(out[0]), "controlnet_steps": int(out[1]), "feature_steps": int(out[2]), "variants": int(out[3]),
-                "captures": int(L.lib().mrisr_sampler_num_captures(self._h))}
-
-    def _run_pag(self, latents, ehs_c, ehs_u, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, g, guidance_rescale,
-                 s, mask, plan=None):
-        """The PAG run: the rows [perturbed; conditional] or, with active classifier-free guidance, [perturbed; unconditional;
-        conditional]; perturbed rows carry the conditional context.  Everything is checked before anything is launched."""
-        B, phi = latents.shape[0], float(guidance_rescale)
-        if not 0.0 <= phi <= 1.0:
-            raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale!r}")
-        # (with PAG the rescale rule needs no active classifier-free guidance: check_guidance sees phi only when CFG can be active)
-        cfg_given = ehs_u is not None and float(g) != 1.0
-        with_cfg = check_guidance(g, phi if cfg_given else 0.0, ehs_c.shape, None if ehs_u is None else ehs_u.shape, B)
-        if latents.ndim != 4 or int(np.prod(latents.shape[1:])) % 4:
-            raise ValueError("pag_scale > 0 needs [B,C,h,w] latents with C*h*w a multiple of 4")
-        if ehs_c.ndim != 3 or ehs_c.shape[0] not in (1, B):
-            raise ValueError(f"encoder_hidden_states must be [1, L, D] or [{B}, L, D], got {tuple(ehs_c.shape)}")
-        contexts = (ehs_c, ehs_u, ehs_c) if with_cfg else (ehs_c, ehs_c)
-
-        def setup():
-            L.check(L.lib().mrisr_sampler_set_guidance(self._h, float(g), phi))
-            L.check(L.lib().mrisr_sampler_set_pag(self._h, mask, s))
-        return self._launch(L.lib().mrisr_sampler_run_pag, latents, contexts, lr_latents, step_noise, controlnet_cond, adapter_features,
-                            use_graph, plan, setup, (1 if with_cfg else 0,))
-
-    def _run_guided(self, latents, ehs_c, ehs_u, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, g, phi, plan=None):
-        if int(np.prod(latents.shape[1:])) % 4:
-            raise ValueError("guided sampling needs C*h*w of the latents to be a multiple of 4")
-        return self._launch(L.lib().mrisr_sampler_run_guided, latents, (ehs_u, ehs_c), lr_latents, step_noise, controlnet_cond,
-                            adapter_features, use_graph, plan, lambda: L.check(L.lib().mrisr_sampler_set_guidance(self._h, g, phi)))
-
-    def _launch(self, entry, latents, contexts, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph, plan, setup=None,
-                extra=()):
-        """The one path into the library: ``entry`` is ``mrisr_sampler_run`` (one context), ``mrisr_sampler_run_guided`` ([unconditional;
-        conditional], diffusers' order) or ``mrisr_sampler_run_pag`` ([perturbed; (unconditional;) conditional]); ``extra`` are the
-        entry's arguments between the feature count and ``use_graph``; ``setup`` runs once every Python-side check has passed.
-        Timestep-invariant plumbing, once per run: each of the K contexts at B rows, images and features K times, then their tiles."""
-        B, dev, K = latents.shape[0], latents.device, len(contexts)
+    def _launch(self, run: _Run, latents, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph):
+        """The one path into the library.  Timestep-invariant plumbing, once per run: each of the K contexts at B rows, images and
+        features K times, then their tiles.  Then, every Python-side check having passed, what the run sets in the library: the scalar
+        setters, the tables of this run (a table an earlier run left there is cleared when this one has none), the skip flag."""
+        B, dev, K, plan = latents.shape[0], latents.device, len(run.contexts), run.tile_plan
         feats = list(adapter_features or [])
         if K > 1 or plan is not None:  # (the plain untiled call leaves a wrong batch to the library's own check)
             if controlnet_cond is not None and controlnet_cond.shape[0] != B:
@@ -818,14 +800,11 @@ class Sampler:
 
         def rows(t):  # [B] -> [K B]
             return (t.to(dev) if K == 1 else torch.cat([t.to(dev)] * K)).contiguous()
-        parts = [e.to(dev) if e.shape[0] == B else e.to(dev).expand(B, -1, -1) for e in contexts]
+        parts = [e.to(dev) if e.shape[0] == B else e.to(dev).expand(B, -1, -1) for e in run.contexts]
         ehs = (parts[0] if K == 1 else torch.cat(parts)).contiguous()
         lr = lr_latents.to(dev, torch.float32).contiguous() if lr_latents is not None else None
         nz = step_noise.to(dev, torch.float32).contiguous() if step_noise is not None else None
-        # guess mode under classifier-free guidance: the ControlNet sees the conditional rows only, its condition image stays [B]
-        pending = getattr(self, "_pending_conditioning", None)
-        cond_at_B = pending is not None and pending[1] and getattr(entry, "__name__", "") == "mrisr_sampler_run_guided"
-        cond = (controlnet_cond.to(dev).contiguous() if cond_at_B else rows(controlnet_cond)) if controlnet_cond is not None else None
+        cond = (controlnet_cond.to(dev).contiguous() if run.cond_at_B else rows(controlnet_cond)) if controlnet_cond is not None else None
         feats = [rows(f) for f in feats]
         if plan is not None:  # the K B rows, then their tiles: row (b, ti) of the forward is b * T + ti
             ehs, cond, feats = self._tile_operands(plan, latents.shape[2], latents.shape[3], ehs, cond, feats)
@@ -836,19 +815,37 @@ class Sampler:
         t_nz = L.as_tensor(nz, shape=(nz.shape[0] * nz.shape[1],) + tuple(nz.shape[2:])) if nz is not None else None
         t_c = L.as_tensor(cond) if cond is not None else None
         f_arr = L.tensor_array([L.as_tensor(f) for f in feats])
-        if setup is not None:
-            setup()
-        self._apply_schedule()
-        self._apply_conditioning()
-        skip, self._pending_skip = getattr(self, "_pending_skip", False), False
-        if skip or getattr(self, "_skipping", False):
-            L.check(L.lib().mrisr_sampler_set_skip(self._h, 1 if skip else 0))
-            self._skipping = skip
-        L.check(entry(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None, C.byref(t_nz) if t_nz else None, C.byref(t_e),
-                      C.byref(t_c) if t_c else None, f_arr if feats else None, len(feats), *extra, 1 if use_graph else 0, L.stream_ptr()))
+        lib = L.lib()
+        for setter, args in run.setters:
+            L.check(getattr(lib, setter)(self._h, *args))
+        if run.schedule is not None or self._scheduled:
+            table = run.schedule
+            L.check(lib.mrisr_sampler_set_schedule(self._h, table.ctypes.data_as(C.c_void_p), int(table.shape[0]))
+                    if table is not None else lib.mrisr_sampler_set_schedule(self._h, None, 0))
+            self._scheduled = table is not None
+        if run.conditioning is not None or self._conditioned:
+            table, guess = run.conditioning or (None, False)
+            L.check(lib.mrisr_sampler_set_conditioning(self._h, table.ctypes.data_as(C.c_void_p), int(table.shape[0]), 1 if guess else 0)
+                    if table is not None else lib.mrisr_sampler_set_conditioning(self._h, None, 0, 0))
+            self._conditioned = table is not None
+        if run.skip or self._skipping:
+            L.check(lib.mrisr_sampler_set_skip(self._h, 1 if run.skip else 0))
+            self._skipping = run.skip
+        L.check(getattr(lib, run.entry)(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None, C.byref(t_nz) if t_nz else None,
+                                        C.byref(t_e), C.byref(t_c) if t_c else None, f_arr if feats else None, len(feats), *run.extra,
+                                        1 if use_graph else 0, L.stream_ptr()))
         self._keep = keep
         return latents
 
+    @property
+    def last_run_stats(self) -> dict:
+        """What the last ``run`` did, from the library's own count: ``unet_rows`` (the sum over its steps of the rows of the UNet forward),
+        ``controlnet_steps`` (steps that ran the ControlNet), ``feature_steps`` (steps that took adapter features), ``variants`` (distinct
+        step variants, ``step_variants``) and ``captures`` (step graphs this sampler has captured so far)."""
+        out = (C.c_int64 * 4)()
+        L.check(L.lib().mrisr_sampler_run_stats(self._h, out))
+        return {"unet_rows": int(out[0]), "controlnet_steps": int(out[1]), "feature_steps": int(out[2]), "variants": int(out[3]),
+                "captures": int(L.lib().mrisr_sampler_num_captures(self._h))}
 
 @torch.no_grad()
 def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weight_dtype, accelerator, fixed_embeds,

@@ -141,16 +141,15 @@ def test_explicit_table_rules():
 
 
 def test_run_keyword_rules_need_no_device():
-    """``Sampler._build_schedule`` on a sampler without a handle: ``schedule`` excludes the four convenience keywords; each of those
-    needs its control to be active; none of them means no table."""
+    """``pipeline._build_schedule``, the function ``Sampler.run`` builds its table with, needs no sampler: ``schedule`` excludes the four
+    convenience keywords; each of those needs its control to be active; none of them means no table."""
     import mrisr
-    smp = object.__new__(mrisr.Sampler)  # no handle: nothing below may need one
-    smp.n_steps, smp._timesteps, smp._n_train = 5, trailing(5), 1000
-    smp.unet = type("U", (), {"freeu": None})()
+    from mrisr.pipeline import _build_schedule
+    unet = type("U", (), {"freeu": None})()
     table = constant_rows(5, 3.0)
 
     def build(schedule=None, ad=0.0, gi=None, pi=None, fi=None, g=3.0, phi=0.0, s=2.0, pag=True, uncond=True):
-        return smp._build_schedule(schedule, ad, gi, pi, fi, g, phi, s, pag, uncond)
+        return _build_schedule(5, trailing(5), 1000, unet.freeu, schedule, ad, gi, pi, fi, g, phi, s, pag, uncond)
 
     assert build() is None and build(gi=(0.0, 1.0), pi=(0, 1), fi=(0.0, 1.0)) is None  # none given: the call of before, no table
     assert np.array_equal(build(schedule=table), table)
@@ -176,7 +175,7 @@ def test_run_keyword_rules_need_no_device():
         build(fi=(0.0, 0.6))
     rows = build(ad=0.002, gi=(0.2, 0.8), phi=0.7)
     assert np.array_equal(rows, mrisr.step_schedule(trailing(5), 3.0, 0.7, 2.0, 0.002, (0.2, 0.8)))
-    smp.unet.freeu = fr.SD15_DOCS  # FreeU on: its four values fill the columns, over the whole run unless freeu_interval says otherwise
+    unet.freeu = fr.SD15_DOCS  # FreeU on: its four values fill the columns, over the whole run unless freeu_interval says otherwise
     rows = build(gi=(0.2, 0.8))
     assert all(tuple(r[3:7]) == tuple(np.float32(fr.SD15_DOCS)) for r in rows)
     rows = build(fi=(0.0, 0.6), pag=False, uncond=False, g=1.0, s=0.0)

@@ -11,7 +11,7 @@ import sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 names = [r["Kernel_Name"] for r in rows]
-cut = [i for i, n in enumerate(names) if "ddim_step_kernel" in n or "resshift_step_kernel" in n or "ddpm_step_kernel" in n]
+cut = [i for i, n in enumerate(names) if "plain_step_kernel" in n or "single_step_kernel" in n]
 lens = collections.Counter(cut[i + 1] - cut[i] for i in range(len(cut) - 1))
 per = lens.most_common(1)[0][0]
 good = [(cut[i], cut[i + 1]) for i in range(len(cut) - 1) if cut[i + 1] - cut[i] == per]

@@ -353,6 +353,29 @@ int mrisr_sampler_set_schedule(mrisr_sampler* s, const float* rows_host, int n_r
  * tiles; a table together with a feature cache.  Everything the runs refuse without a table stays refused. */
 int mrisr_sampler_set_conditioning(mrisr_sampler* s, const float* rows_host, int n_rows, int guess_mode);
 
+/* ---- low-frequency consistency (ILVR: Choi et al., ICCV 2021) ------------------------------------
+ * Off by default.  With a table, every step of the following runs ends with one more launch, after the reverse step and before the step
+ * counter advances, on the latent canvas:
+ *     x  <-  x + w phi_N( alpha ref + beta lr + sigma z - x )        {w, alpha, beta, sigma} = rows[step],   z = noise slab `step`
+ * phi_N: the mean over each N x N block (N = factor, 2 .. 8, dividing h and w), upsampled by N back to [h, w] with `filter`:
+ * MRISR_CONSIST_BILINEAR (torch's F.interpolate(F.avg_pool2d(d, N), scale_factor=N, mode="bilinear", align_corners=False): source
+ * coordinate (i + 0.5) / N - 0.5, negative clamped to 0, upper neighbour clamped to the last cell) or MRISR_CONSIST_NEAREST (an exact
+ * projection: at w = 1 the block means of the new x are those of the target).  ILVR itself filters bicubically both ways.
+ * ref: f32 [B, C, h, w]; noise: f32 [n_steps, B, C, h, w] or NULL (slab i is read when row i has sigma != 0 - a table with such a row needs
+ * it); lr: the run's lr_latents (NULL: no beta term).  Both pointers are REMEMBERED for the following runs: the caller keeps the buffers
+ * alive.  The new x goes to the latents and, in a guided / pag run, to every part of the staging buffer (also on a reduced step).
+ * The kernel reads its row with ordinary loads behind the load of the step counter, so the values are NOT part of the graph key: a run
+ * whose table has other values replays the stored graph.  Part of the key: the table's address, factor, filter, the ref and noise
+ * addresses.  A row with w == 0 still launches the kernel, which returns at once and leaves every bit as it was.
+ * rows_host NULL / n_rows 0 clears everything (ref and noise are ignored).  Refused before any device work: n_rows != n_steps, a value
+ * that is not finite, a factor or filter outside the accepted set, ref / noise that are not f32 of the shapes above (C: the UNet's
+ * in_channels), a sigma != 0 without noise, a feature cache with interval > 1.  Refused by the run before any launch: latents of another
+ * shape than ref, a factor that does not divide h and w of the canvas, a canvas that needs more than 64 KB of LDS,
+ * 4 (h w / N + h w / N^2) bytes (128 x 128 latents at N = 2 need 48 KB; 256 x 256 needs N >= 8), a feature cache. */
+typedef enum { MRISR_CONSIST_BILINEAR = 0, MRISR_CONSIST_NEAREST = 1 } mrisr_consist_filter;
+int mrisr_sampler_set_consistency(mrisr_sampler* s, int factor, int filter, const float* rows_host, int n_rows, const mrisr_tensor* ref,
+                                  const mrisr_tensor* noise);
+
 /* ---- tiled sampling (MultiDiffusion, Bar-Tal et al. 2023, with the Gaussian weights of Mixture of Diffusers, Jimenez 2023) -------
  * The latent canvas [NB, C, H, W] is cut into overlapping tiles, the forward runs on the tile batch [NB*T, C, t_h, t_w] and the tile
  * predictions are blended back before the reverse step, which stays on the canvas.  All sizes in latent pixels.
@@ -733,6 +756,14 @@ int mrisr_op_freeu_scheduled(int dtype, const void* hidden, const void* skip, vo
  * a weight that is not finite. */
 int mrisr_op_cond_add(int dtype, int n_pairs, void* const* x, const void* const* r, const int64_t* per_row, const float* weights,
                       const float* table_host, int n_rows, int slot, int col, int row_lo, int row_hi, void* stream);
+/* the consistency launch of mrisr_sampler_set_consistency alone, on device pointers: x [B,C,h,w] f32 (in place), xK [K B,C,h,w] f32 or NULL
+ * (every one of its K parts receives the new x; K = 1 .. 3, NULL only with K = 1), ref [B,C,h,w], lr [B,C,h,w] or NULL, noise
+ * [*step + 1 or more][B,C,h,w] or NULL, table_dev [rows][4] = {w, alpha, beta, sigma} and step_dev (one int: the row and slab the kernel
+ * reads) on the device.  Operands that are all 16-byte aligned with w % 4 == 0 take the 16-byte path, others the scalar one: same bits.
+ * Refused before any launch: null x / ref / table / step, K outside 1 .. 3, a factor outside 2 .. 8 or not dividing h and w, a filter other
+ * than 0 / 1, an LDS need above 64 KB, pointers not 4-byte aligned. */
+int mrisr_op_consistency(float* x, float* xK, int K, const float* ref, const float* lr, const float* noise, const float* table_dev,
+                         const int* step_dev, int B, int C, int h, int w, int factor, int filter, void* stream);
 /* dst[z][c][r] = src[z][r][c] for r < r_valid, 0 for r_valid <= r < R (T; pitches ld_src >= C, ld_dst >= R; batch strides in elements) */
 int mrisr_op_transpose(int dtype, const void* src, void* dst, int R, int C, int ld_src, int ld_dst, int64_t bs_src, int64_t bs_dst,
                        int batch, int r_valid, void* stream);

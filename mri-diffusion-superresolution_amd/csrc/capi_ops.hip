@@ -1102,6 +1102,21 @@ int mrisr_op_cond_add(int dtype, int n_pairs, void* const* x, const void* const*
     API_END
 }
 
+// the consistency launch alone (consist.hip): table and step counter already on the device
+int mrisr_op_consistency(float* x, float* xK, int K, const float* ref, const float* lr, const float* noise, const float* table_dev,
+                         const int* step_dev, int B, int C, int h, int w, int factor, int filter, void* stream) {
+    API_BEGIN
+    hipStream_t st = (hipStream_t)stream;
+    ConsistArgs a;
+    a.x = x; a.xK = xK; a.K = K; a.ref = ref; a.lr = lr; a.noise = noise; a.table = table_dev; a.step = step_dev;
+    a.B = B; a.C = C; a.h = h; a.w = w; a.factor = factor; a.filter = filter;
+    // (the launcher refuses null / misaligned pointers, K, the factor, the filter and the LDS need before it launches)
+    TRY(launch_consistency(a, st));
+    MRISR_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+    API_END
+}
+
 int mrisr_op_softmax_bwd(int dtype, const void* p, const float* dp, void* ds, int ld, int64_t rows, int nk, float scale, void* stream) {
     API_BEGIN
     TRY(bwd_dtype_ok(dtype));

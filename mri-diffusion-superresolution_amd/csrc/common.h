@@ -340,6 +340,28 @@ struct CondAddArgs {
 template <typename T> int launch_cond_add(const CondAddArgs& a, hipStream_t st);
 int check_conditioning_rows(const float* rows, int n_rows);  // [n_rows][4] = {c, a, 0, 0}: finite, columns 2 and 3 zero
 void guess_mode_weights(int n_down, float* w);               // n_down + 1 weights: logspace(-1, 0, n_down + 1), the mid residual last
+// low-frequency consistency (consist.hip): one launch, one workgroup per (sample, channel) plane,
+//   x += w phi_N(alpha ref + beta lr + sigma z - x),   {w, alpha, beta, sigma} = table[4 * (*step)],   z = noise slab *step (read when sigma != 0)
+// phi_N: the N x N block mean, upsampled by N (filter 0 bilinear, 1 nearest).  The new x goes to x and, with xK, to each of its K parts.
+constexpr int CONSIST_MIN_FACTOR = 2, CONSIST_MAX_FACTOR = 8;
+constexpr long long CONSIST_LDS_CAP = 65536;
+struct ConsistArgs {
+    float* x = nullptr;            // [B, C, h, w], in place
+    float* xK = nullptr;           // the [K B] staging buffer, or null
+    const float* ref = nullptr;    // [B, C, h, w]
+    const float* lr = nullptr;     // [B, C, h, w] or null
+    const float* noise = nullptr;  // [n_steps][B, C, h, w] or null
+    const float* table = nullptr;  // [n_steps][4]
+    const int* step = nullptr;
+    int K = 1, B = 0, C = 0, h = 0, w = 0, factor = 0, filter = 0;
+};
+// the row sums [h][w / N] and the coarse grid [h / N][w / N], f32
+inline long long consist_lds_bytes(int h, int w, int factor) {
+    return 4ll * ((long long)h * (w / factor) + (long long)(h / factor) * (w / factor));
+}
+int check_consistency_geometry(int factor, int filter, int h, int w);  // factor 2 .. 8 dividing h and w, filter 0 / 1, the LDS need <= 64 KB
+int check_consistency_rows(const float* rows, int n_rows);            // [n_rows][4] = {w, alpha, beta, sigma}: every value finite
+int launch_consistency(const ConsistArgs& a, hipStream_t st);
 template <typename T>
 int launch_softmax_bwd(const void* p, const float* dp, void* ds, int ld, long long rows, int nk, float scale, hipStream_t st);
 template <typename T>

@@ -590,6 +590,13 @@ struct mrisr_sampler {
     // at full strength, added as before), and what the checks need of the values: some row with c != 1 / a != 1
     StepTable cond{"conditioning", 4};
     bool cond_guess = false, cond_c = false, cond_a = false;
+    // low-frequency consistency (mrisr_sampler_set_consistency): rows {w, alpha, beta, sigma} (no table: no launch), the
+    // launch constants, and the caller's reference [B, C, h, w] and noise slabs [n_steps][B, C, h, w] (or null), remembered for the runs
+    StepTable cons{"consistency", 4};
+    int cons_factor = 0, cons_filter = 0;
+    const float* cons_ref = nullptr;
+    const float* cons_noise = nullptr;
+    long long cons_shape[4] = {0, 0, 0, 0};
     std::vector<float> sigma;  // host copy of each step's noise coefficient (which steps read a step_noise slab)
     DevBuf d_ts, d_coef, d_step, d_curt, d_eps;
     // multistep kinds: solver options, the clamped alphas_cumprod on the grid (+ alphas_cumprod[0]), the host rows of the current range,
@@ -649,15 +656,17 @@ struct Options {
     bool pag_run;
     bool cond_table, guess;  // the conditioning table and guess mode of the run
     bool skip;               // the skipping of neutral steps (mrisr_sampler_set_skip)
+    bool cons_table;         // the consistency table (mrisr_sampler_set_consistency)
 };
 static Options current_options(const mrisr_sampler* s) {
-    return Options{s->cnet != nullptr, s->cache_interval, s->tile_h != 0, false, false, false, s->skip};
+    return Options{s->cnet != nullptr, s->cache_interval, s->tile_h != 0, false, false, false, s->skip, s->cons.on()};
 }
 // Every rule once: the first one that the UNet's state and `o` violate, or null.  Always asked before any launch.
 static const char* option_conflict(const Model& U, const Options& o) {
     const bool cached = o.cache_interval > 1;
     if (o.skip && cached) return "skipping neutral steps together with a feature cache (interval > 1) is not supported";
     if (o.cond_table && cached) return "conditioning: a conditioning table together with a feature cache (interval > 1) is not supported";
+    if (o.cons_table && cached) return "consistency: a consistency table together with a feature cache (interval > 1) is not supported";
     if (o.guess && o.pag_run) return "conditioning: guess mode in a pag run is not supported";
     if (o.guess && o.tiles_on) return "conditioning: guess mode together with tiles is not supported";
     if (o.cond_table && U.keep) return "conditioning: a training forward is being recorded";
@@ -886,6 +895,46 @@ int mrisr_sampler_set_conditioning(mrisr_sampler* s, const float* rows_host, int
     API_END
 }
 
+int mrisr_sampler_set_consistency(mrisr_sampler* s, int factor, int filter, const float* rows_host, int n_rows, const mrisr_tensor* ref,
+                                  const mrisr_tensor* noise) {
+    API_BEGIN
+    MRISR_REQUIRE(s, "null sampler");
+    if (!rows_host || n_rows == 0) {  // clears everything: the next run has another plan and captures again
+        TRY(s->cons.set(rows_host, n_rows, s->n_steps, check_consistency_rows));
+        s->cons_factor = s->cons_filter = 0;
+        s->cons_ref = s->cons_noise = nullptr;
+        return 0;
+    }
+    MRISR_REQUIRE(n_rows == s->n_steps, "consistency: n_rows must equal the sampler's n_steps (" + std::to_string(s->n_steps) + "), got " + std::to_string(n_rows));
+    TRY(check_consistency_rows(rows_host, n_rows));
+    MRISR_REQUIRE(ref && ref->data && ref->ndim == 4 && ref->dtype == MRISR_F32 && ref->layout == MRISR_NCHW, "consistency: ref must be f32 [B, C, h, w]");
+    MRISR_REQUIRE(ref->shape[0] > 0 && ref->shape[1] == s->unet->cfg.in_channels && ref->shape[2] > 0 && ref->shape[3] > 0 &&
+                      ref->shape[2] < (1 << 20) && ref->shape[3] < (1 << 20),
+                  "consistency: ref must have the latents' shape [B, in_channels, h, w]");
+    TRY(check_consistency_geometry(factor, filter, (int)ref->shape[2], (int)ref->shape[3]));
+    bool noisy = false;
+    for (int i = 0; i < n_rows; ++i) noisy |= rows_host[4 * (size_t)i + 3] != 0.f;
+    MRISR_REQUIRE(noise || !noisy, "consistency: rows with sigma != 0 need the noise slabs");
+    if (noise) {
+        long long k = 1, per = 1;
+        for (int i = 0; i < noise->ndim; ++i) k *= noise->shape[i];
+        for (int i = 0; i < 4; ++i) per *= ref->shape[i];
+        MRISR_REQUIRE(noise->data && noise->dtype == MRISR_F32 && k == (long long)s->n_steps * per,
+                      "consistency: noise must be f32 [n_steps, B, C, h, w] with the shape of ref");
+    }
+    Options o = current_options(s);
+    o.cons_table = true;
+    const char* conflict = option_conflict(*s->unet, o);
+    MRISR_REQUIRE(!conflict, conflict);
+    TRY(s->cons.set(rows_host, n_rows, s->n_steps, check_consistency_rows));
+    s->cons_factor = factor; s->cons_filter = filter;
+    s->cons_ref = static_cast<const float*>(ref->data);
+    s->cons_noise = noise ? static_cast<const float*>(noise->data) : nullptr;
+    for (int i = 0; i < 4; ++i) s->cons_shape[i] = ref->shape[i];
+    return 0;
+    API_END
+}
+
 }  // extern "C"
 
 // ---- one run: mrisr_sampler_run (K = 1: B rows everywhere), mrisr_sampler_run_guided (K = 2) and mrisr_sampler_run_pag (pag: K = 2 or 3).
@@ -1072,6 +1121,16 @@ static int run_check(mrisr_sampler* s, const RunArgs& a, StepPlan& p) {
         p.cond_guess = guess ? 1 : 0;
         if (s->cnet) p.cnet_rows = guess_half ? B : FB;
     }
+    if (s->cons.on()) {
+        // the consistency launch runs on the canvas (tiles gather from it afterwards): its rules are checked against the canvas.  The launch takes
+        // the table's address, never its values - other values, same graph; factor, filter and the two buffers' addresses choose the launch
+        for (int i = 0; i < 4; ++i)
+            MRISR_REQUIRE(latents->shape[i] == s->cons_shape[i], "consistency: the reference must have the shape of the latents");
+        TRY(check_consistency_geometry(s->cons_factor, s->cons_filter, h, w));
+        p.d_cons = static_cast<const float*>(s->cons.dev.p);
+        p.cons_ref = s->cons_ref; p.cons_noise = s->cons_noise;
+        p.cons_factor = s->cons_factor; p.cons_filter = s->cons_filter;
+    }
     if (s->multistep()) {
         p.order = s->ms.order;
         p.final_zero = s->ms.final_zero; p.lower_order_final = s->ms.lower_order_final;
@@ -1188,6 +1247,7 @@ static int run_buffers(mrisr_sampler* s, StepPlan& p, hipStream_t st) {
     }
     if (p.d_sched) TRY(s->sched.upload(s->n_steps, st));
     if (p.d_cond) TRY(s->cond.upload(s->n_steps, st));
+    if (p.d_cons) TRY(s->cons.upload(s->n_steps, st));
     MRISR_CHECK_HIP(hipMemsetAsync(s->d_step.p, 0, 16, st));
     MRISR_CHECK_HIP(hipMemcpyAsync(s->d_step.p, &s->first, sizeof(int), hipMemcpyHostToDevice, st));
     return 0;
@@ -1290,6 +1350,15 @@ static int step_body(const StepPlan& p, Model& U, Model* C, int cache_mode, int 
         a.sched = p.d_sched; a.sched_phi = p.sched_phi;
     }
     TRY(launch_step(a, reduced, st));
+    if (p.d_cons) {
+        // low-frequency consistency: on the new state, row *d_step - so before the counter advances.  Every part of the
+        // staging buffer receives the result, also on a reduced step
+        ConsistArgs c;
+        c.x = p.x; c.xK = p.d_x2; c.K = p.K; c.ref = p.cons_ref; c.lr = p.lr; c.noise = p.cons_noise;
+        c.table = p.d_cons; c.step = p.d_step;
+        c.B = p.B; c.C = p.C; c.h = p.h; c.w = p.w; c.factor = p.cons_factor; c.filter = p.cons_filter;
+        TRY(launch_consistency(c, st));
+    }
     return launch_advance_step(p.d_step, st);
 }
 

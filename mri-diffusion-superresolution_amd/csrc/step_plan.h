@@ -43,6 +43,9 @@ struct StepPlan {
     const long long* d_ts;
     const float* d_sched;  // per-step schedule table [n_steps][8] = {g, s, phi, freeu s1, s2, b1, b2, 0}, or null: the scalars below rule
     const float* d_cond;   // conditioning table [n_steps][4] = {c, a, 0, 0}, or null: every residual at full strength
+    const float* d_cons;   // consistency table [n_steps][4] = {w, alpha, beta, sigma}, or null: no consistency launch
+    const float* cons_ref;    // ... its reference [B] and its noise slabs [n_steps][B] or null
+    const float* cons_noise;
     // ---- model state the forwards bake in ----
     unsigned long long ws_gen_unet, ws_gen_cnet;  // workspace generations: persist / arena base addresses
     const float* tproj_unet;                      // per-run time-embedding tables (null: computed per step)
@@ -71,6 +74,8 @@ struct StepPlan {
     // with d_cond the VALUES of the conditioning table are not here either.  cond_guess: guess mode (the per-residual weights; under
     // classifier-free guidance the ControlNet runs on the conditional rows only).  cnet_rows: the rows of the ControlNet's forward
     int cond_guess, cnet_rows;
+    // with d_cons the VALUES of the consistency table are not here either: only the launch constants, the factor N and the filter
+    int cons_factor, cons_filter;
     int first;           // the step the run starts at (the time-embedding table's row 0)
     // ---- policy, not baked in: these live in the uploaded rows; a change captures again because set_solver promises it ----
     int final_zero, lower_order_final;

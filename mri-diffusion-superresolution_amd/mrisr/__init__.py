@@ -11,6 +11,7 @@ from .pipeline import check_tiles, tile_tables  # noqa: F401
 from .pipeline import check_pag  # noqa: F401
 from .pipeline import check_schedule, step_schedule  # noqa: F401
 from .pipeline import check_conditioning, conditioning_schedule, guess_mode_weights  # noqa: F401
+from .pipeline import check_consistency, check_consistency_table, consistency_schedule  # noqa: F401
 from .pipeline import step_variants, STEP_REDUCED, STEP_NO_CONTROLNET, STEP_NO_FEATURES  # noqa: F401
 from .models import transformer_block_names  # noqa: F401
 from .models import check_freeu, freeu_stage_names  # noqa: F401

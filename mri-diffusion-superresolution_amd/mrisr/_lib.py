@@ -16,6 +16,7 @@ MRISR_NCHW, MRISR_NHWC = 0, 1
 STEP_DDIM, STEP_RESSHIFT, STEP_DDPM, STEP_UNIPC, STEP_DPMSOLVERPP = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_GEGLU = 0, 1, 2, 3
 TILE_WINDOWS = {"uniform": 0, "gaussian": 1}
+CONSISTENCY_FILTERS = {"bilinear": 0, "nearest": 1}
 
 _DT = {torch.float32: MRISR_F32, torch.bfloat16: MRISR_BF16, torch.float16: MRISR_F16, torch.int64: MRISR_I64}
 
@@ -66,6 +67,7 @@ EXPORTS = [
     "mrisr_model_set_freeu", "mrisr_op_freeu",
     "mrisr_sampler_set_schedule", "mrisr_op_scheduled_step", "mrisr_op_freeu_scheduled",
     "mrisr_sampler_set_conditioning", "mrisr_op_cond_add",
+    "mrisr_sampler_set_consistency", "mrisr_op_consistency",
     "mrisr_model_forward_rows", "mrisr_sampler_set_skip", "mrisr_sampler_run_stats", "mrisr_op_reduced_step",
     "mrisr_tile_tables", "mrisr_sampler_set_tiles", "mrisr_op_tile_gather", "mrisr_op_tile_blend",
     "mrisr_adapter_train_prepare", "mrisr_adapter_train_num_trainable", "mrisr_adapter_train_num_tensors",
@@ -154,6 +156,8 @@ def lib() -> C.CDLL:
         L.mrisr_op_freeu_scheduled.argtypes = [I, P, P, P, P, I, I, I, I, I, I, P, I, I, P]
         L.mrisr_sampler_set_conditioning.argtypes = [P, P, I, I]
         L.mrisr_op_cond_add.argtypes = [I, I, P, P, P, P, P, I, I, I, I, I, P]
+        L.mrisr_sampler_set_consistency.argtypes = [P, I, I, P, I, P, P]
+        L.mrisr_op_consistency.argtypes = [P, P, I, P, P, P, P, P, I, I, I, I, I, I, P]
         L.mrisr_model_forward_rows.argtypes = [P, I, I, P, P, P, I, P, P, I, P, P]
         L.mrisr_sampler_set_skip.argtypes = [P, I]
         L.mrisr_sampler_run_stats.argtypes = [P, P]

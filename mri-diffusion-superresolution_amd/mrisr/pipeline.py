@@ -292,6 +292,101 @@ def conditioning_schedule(n_steps, controlnet_conditioning_scale=1.0, control_gu
     return rows
 
 
+CONSISTENCY_FILTERS = dict(L.CONSISTENCY_FILTERS)
+CONSISTENCY_COLUMNS = ("weight", "alpha", "beta", "sigma")
+CONSISTENCY_LDS_CAP = 65536
+SAMPLER_KINDS = ("ddim", "resshift", "ddpm", "unipc", "dpmsolver++")
+
+
+def check_consistency(factor, filter, h, w, cache_interval=1):
+    """The argument rules of low-frequency consistency (``Sampler.run(consistency_ref=)``), on numbers alone (no
+    device is touched); returns the normalised (factor, filter id).  ``factor`` N: an int in 2..8 that divides ``h`` and ``w`` of the
+    latent canvas; ``filter``: "bilinear" or "nearest"; the canvas must fit the kernel's LDS scratch, ``4 (h w / N + h w / N^2)`` bytes
+    <= 64 KB (128 x 128 latents at N = 2 need 48 KB; 256 x 256 needs N >= 8); a feature cache (``cache_interval`` > 1) is refused.
+    Raises ``ValueError`` naming the argument."""
+    if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)) or not 2 <= factor <= 8:
+        raise ValueError(f"consistency_factor must be an int in 2..8, got {factor!r}")
+    if not isinstance(filter, str) or filter not in CONSISTENCY_FILTERS:
+        raise ValueError(f"consistency_filter must be one of {tuple(CONSISTENCY_FILTERS)}, got {filter!r}")
+    for name, v in (("h", h), ("w", w)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"{name} of the latents must be an int >= 1, got {v!r}")
+    N, h, w = int(factor), int(h), int(w)
+    if h % N or w % N:
+        raise ValueError(f"consistency_factor {N} must divide h and w of the latents, got {h} x {w}")
+    need = 4 * (h * (w // N) + (h // N) * (w // N))
+    if need > CONSISTENCY_LDS_CAP:
+        raise ValueError(f"consistency_factor {N} on {h} x {w} latents needs {need} bytes of LDS, more than {CONSISTENCY_LDS_CAP}: use a "
+                         "larger consistency_factor")
+    if cache_interval > 1:
+        raise ValueError("consistency_ref together with a feature cache (interval > 1) is not supported")
+    return N, CONSISTENCY_FILTERS[filter]
+
+
+def check_consistency_table(table, n_steps) -> np.ndarray:
+    """The rules of an explicit consistency table (``Sampler.run(consistency=)``), on numbers alone (no device is
+    touched): ``[n_steps, 4]`` rows ``{w, alpha, beta, sigma}``, every value finite.  Returns it as a contiguous float32 array; raises
+    ``ValueError`` naming the column."""
+    try:
+        with np.errstate(over="ignore"):  # (a value too large for float32 becomes inf and is named below)
+            a = np.ascontiguousarray(np.asarray(table, dtype=np.float32))
+    except (TypeError, ValueError):
+        raise ValueError("consistency must be an array of numbers") from None
+    if a.ndim != 2 or a.shape != (int(n_steps), 4):
+        raise ValueError(f"consistency must have shape [{int(n_steps)}, 4] (one row per step of the sampler), got {list(a.shape)}")
+    for c, name in enumerate(CONSISTENCY_COLUMNS):
+        if not np.isfinite(a[:, c]).all():
+            raise ValueError(f"consistency: column {c} ({name}) holds a value that is not finite")
+    return a
+
+
+def consistency_schedule(timesteps, alphas_cumprod, kind, anchored, weight=1.0, interval=FULL_INTERVAL, noisy=False,
+                         final_sigmas_type="zero") -> np.ndarray:
+    """The consistency table of ``Sampler.run(consistency=)`` for the ``n`` steps at ``timesteps``: float32
+    ``[n, 4]``, row i = ``{w_i, alpha_i, beta_i, sigma_i}``.  Pure Python on the CPU.  After step i the state is pulled towards
+    ``y_i = alpha_i ref + beta_i lr + sigma_i z_i``: the reference at the noise level of the state step i PRODUCES.  With ``a_p(i)`` the
+    cumulative alpha of that state - ``alphas_cumprod[timesteps[i + 1]]``, and for the last step the point the step rule of ``kind`` lands
+    on: 1 for "ddpm" and for the multistep kinds with ``final_sigmas_type="zero"``, ``alphas_cumprod[0]`` for "ddim", "resshift" and
+    "sigma_min" -
+
+    * ``alpha_i = sqrt(a_p)``;
+    * ``beta_i = 1 - sqrt(a_p)`` when ``anchored`` (the mean of the shift process: "resshift" always, any other kind run with
+      ``lr_latents``), else 0;
+    * ``sigma_i = sqrt(1 - a_p)`` when ``noisy`` (ILVR's noised reference; the run then needs ``consistency_noise``), else 0;
+    * ``w_i = weight`` when step i is inside ``interval`` (``i / n >= start and (i + 1) / n <= end``, the rule of ``step_schedule``), else 0.
+
+    Raises ``ValueError`` for an unknown ``kind`` or ``final_sigmas_type``, values that are not finite, ``weight`` < 0, a timestep outside
+    the table or an interval that breaks ``0 <= start <= end <= 1``."""
+    if kind not in SAMPLER_KINDS:
+        raise ValueError(f"kind must be one of {SAMPLER_KINDS}, got {kind!r}")
+    if final_sigmas_type not in ("zero", "sigma_min"):
+        raise ValueError(f"final_sigmas_type must be 'zero' or 'sigma_min', got {final_sigmas_type!r}")
+    ts = np.asarray(timesteps.detach().cpu().numpy() if isinstance(timesteps, torch.Tensor) else timesteps)
+    if ts.ndim != 1 or ts.size == 0 or not np.isfinite(ts.astype(np.float64)).all():
+        raise ValueError("timesteps must be a non-empty 1-D sequence of finite numbers")
+    ac = np.asarray(alphas_cumprod.detach().cpu().numpy() if isinstance(alphas_cumprod, torch.Tensor) else alphas_cumprod, dtype=np.float64)
+    if ac.ndim != 1 or ac.size == 0 or not np.isfinite(ac).all() or (ac < 0).any() or (ac > 1).any():
+        raise ValueError("alphas_cumprod must be a non-empty 1-D table of finite values in [0, 1]")
+    if (ts < 0).any() or (ts >= ac.size).any():
+        raise ValueError(f"timesteps must lie in [0, {ac.size}): the alphas_cumprod table")
+    wgt = _finite("weight", weight, 0.0)
+    lo, hi = _check_interval("interval", interval)
+    n = int(ts.size)
+    if kind == "ddpm" or (kind in MULTISTEP_KINDS and final_sigmas_type == "zero"):
+        a_last = 1.0
+    else:
+        a_last = float(ac[0])
+    rows = np.zeros((n, 4), dtype=np.float32)
+    with np.errstate(over="ignore"):
+        for i in range(n):
+            a_p = float(ac[int(ts[i + 1])]) if i + 1 < n else a_last
+            rows[i] = (wgt if (i / n >= lo and (i + 1) / n <= hi) else 0.0, np.sqrt(a_p), 1.0 - np.sqrt(a_p) if anchored else 0.0,
+                       np.sqrt(1.0 - a_p) if noisy else 0.0)
+    if not np.isfinite(rows).all():
+        raise ValueError("a value of the consistency table is not finite in float32")
+    return rows
+
+
 STEP_REDUCED, STEP_NO_CONTROLNET, STEP_NO_FEATURES = 1, 2, 4
 
 
@@ -514,6 +609,41 @@ def _build_conditioning(n_steps, has_controlnet, tiles_on, cache_interval, condi
     return table, guess
 
 
+def _build_consistency(n_steps, timesteps, alphas_cumprod, kind, final_sigmas_type, cache_interval, latents, anchored, ref, factor, weight,
+                       interval, filter, noise, table):
+    """(table, factor, filter id, ref, noise) of a ``Sampler.run`` - float32 [n_steps, 4], two ints, the reference and the noise slabs (or
+    None) as contiguous f32 tensors on the latents' device - or None: no consistency, the call of before.  Everything is checked here,
+    before anything is launched."""
+    if ref is None:
+        given = [k for k, on in (("consistency_factor", factor != 4), ("consistency_weight", weight != 1.0),
+                                 ("consistency_interval", interval is not None), ("consistency_filter", filter != "bilinear"),
+                                 ("consistency_noise", noise is not None), ("consistency", table is not None)) if on]
+        if given:
+            raise ValueError(f"{', '.join(given)} need consistency_ref: the reference whose low band the state keeps")
+        return None
+    if latents.ndim != 4:
+        raise ValueError("consistency_ref needs [B,C,h,w] latents")
+    N, fid = check_consistency(factor, filter, int(latents.shape[2]), int(latents.shape[3]), cache_interval)
+    if not isinstance(ref, torch.Tensor) or tuple(ref.shape) != tuple(latents.shape):
+        raise ValueError(f"consistency_ref must be a tensor of the latents' shape {tuple(latents.shape)}, got "
+                         f"{tuple(ref.shape) if isinstance(ref, torch.Tensor) else ref!r}")
+    if noise is not None and (not isinstance(noise, torch.Tensor) or tuple(noise.shape) != (n_steps,) + tuple(latents.shape)):
+        raise ValueError(f"consistency_noise must be a tensor of shape {(n_steps,) + tuple(latents.shape)} (one slab per step of the sampler), "
+                         f"got {tuple(noise.shape) if isinstance(noise, torch.Tensor) else noise!r}")
+    if table is not None:
+        given = [k for k, on in (("consistency_weight", weight != 1.0), ("consistency_interval", interval is not None)) if on]
+        if given:
+            raise ValueError(f"consistency is an explicit table: it excludes {', '.join(given)}")
+        rows = check_consistency_table(table, n_steps)
+        if noise is None and (rows[:, 3] != 0).any():
+            raise ValueError("consistency: rows with sigma != 0 need consistency_noise")
+    else:
+        rows = consistency_schedule(timesteps, alphas_cumprod, kind, anchored, weight, FULL_INTERVAL if interval is None else interval,
+                                    noisy=noise is not None, final_sigmas_type=final_sigmas_type)
+    dev = latents.device
+    return (rows, N, fid, ref.to(dev, torch.float32).contiguous(), noise.to(dev, torch.float32).contiguous() if noise is not None else None)
+
+
 class _Run(NamedTuple):
     """What one ``Sampler.run`` asks of the library: built once every check of ``run`` has passed, consumed by ``Sampler._launch``."""
     entry: str                       # "mrisr_sampler_run" (one context), "mrisr_sampler_run_guided" ([unconditional; conditional],
@@ -523,6 +653,7 @@ class _Run(NamedTuple):
     schedule: Optional[np.ndarray] = None  # the schedule table of this run
     conditioning: Optional[tuple] = None   # (conditioning table, guess)
     skip: bool = False
+    consistency: Optional[tuple] = None    # (consistency table, factor, filter id, ref, noise or None): ``_build_consistency``
     tile_plan: Optional[tuple] = None      # ``Sampler._tile_plan``
     cond_at_B: bool = False          # guess mode under classifier-free guidance: the ControlNet sees [B] rows, its image stays [B]
 
@@ -584,8 +715,9 @@ class Sampler:
         ac = scheduler.alphas_cumprod.detach().cpu().to(torch.float32).numpy().copy()
         self.n_steps = len(ts)
         self._timesteps, self._n_train = ts, len(ac)  # what ``step_schedule`` needs to build a table for this sampler
-        # what the previous run left in the library: a schedule table, a conditioning table, the skip flag
-        self._scheduled, self._conditioned, self._skipping = False, False, False
+        self._alphas_cumprod = ac                     # ... and ``consistency_schedule``
+        # what the previous run left in the library: a schedule table, a conditioning table, the skip flag, a consistency table
+        self._scheduled, self._conditioned, self._skipping, self._consistent = False, False, False, False
         self._h = C.c_void_p()
         L.check(L.lib().mrisr_sampler_create(unet._h, controlnet._h if controlnet is not None else None,
                                              kinds[kind],
@@ -626,6 +758,9 @@ class Sampler:
         if self._skipping:  # skip_neutral is an argument of each run: what the last one left in the library is not a conflict
             L.check(L.lib().mrisr_sampler_set_skip(self._h, 0))
             self._skipping = False
+        if self._consistent:  # likewise consistency_ref
+            L.check(L.lib().mrisr_sampler_set_consistency(self._h, 0, 0, None, 0, None, None))
+            self._consistent = False
         L.check(L.lib().mrisr_sampler_set_cache(self._h, interval, depth))
         self.cache_interval, self.cache_depth = interval, depth
 
@@ -703,11 +838,32 @@ class Sampler:
             step_noise: Optional[torch.Tensor] = None, controlnet_cond: Optional[torch.Tensor] = None,
             adapter_features: Optional[Sequence[torch.Tensor]] = None, pag_scale: float = 0.0, pag_applied_layers=("mid",),
             pag_adaptive_scale: float = 0.0, guidance_interval=None, pag_interval=None, freeu_interval=None, schedule=None,
-            skip_neutral: bool = False, controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0,
+            skip_neutral: bool = False, consistency_ref: Optional[torch.Tensor] = None, consistency_factor: int = 4,
+            consistency_weight: float = 1.0, consistency_interval=None, consistency_filter: str = "bilinear",
+            consistency_noise: Optional[torch.Tensor] = None, consistency=None,
+            controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0,
             adapter_conditioning_scale: float = 1.0, adapter_conditioning_factor: float = 1.0, guess_mode: bool = False,
             conditioning=None, use_graph: bool = True, guidance_scale: float = 1.0, guidance_rescale: float = 0.0,
             uncond_hidden_states: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Advance ``latents`` [B,C,h,w] (f32, updated IN PLACE) through every timestep.
+
+        Low-frequency consistency (ILVR, Choi et al. 2021): with ``consistency_ref`` [B,C,h,w] - for a
+        super-resolver the LR latents - every step ends with ``x <- x + w_i phi_N(y_i - x)``, ``y_i = alpha_i ref + beta_i lr + sigma_i z_i``
+        the reference at the noise level of the state the step produced (``consistency_schedule``) and ``phi_N`` the low-pass filter
+        "average over N x N blocks, upsample by N" with N = ``consistency_factor`` (2..8, dividing h and w; small: the reference decides
+        nearly everything, large: only the coarse anatomy) and ``consistency_filter`` "bilinear" or "nearest" (an exact projection: at
+        weight 1 the block means of the state ARE those of ``y_i``).  ``consistency_weight`` w >= 0 applies inside
+        ``consistency_interval`` (a ``(start, end)`` pair of fractions of the run, the rule of ``guidance_interval``; ILVR's conditioning
+        range) and 0 outside.  ``consistency_noise`` [n_steps,B,C,h,w]: the z_i, which turn the sigma column on (ILVR's noised reference);
+        without it the reference is not noised.  ``consistency``: an explicit ``[n_steps, 4]`` table ``{w, alpha, beta, sigma}``
+        (``check_consistency_table``) instead of the weight and the interval.  The captured step reads its row from the table, so other
+        weights and intervals replay the same graph; another factor, filter, reference buffer or noise buffer captures again.  A
+        ``consistency_ref`` (or ``consistency_noise``) that is already on the device, contiguous and float32 is passed by ADDRESS, not
+        copied: a caller who refills the same buffer between runs replays the graph.  It acts on the canvas after the step, so it
+        composes with every step kind, guidance, PAG, tiles, ``skip_neutral`` (a step of weight 0 still launches the kernel, which returns
+        at once), ControlNet, adapter features, FreeU and ``set_range``.  Not with a feature cache.  The canvas must fit the kernel's
+        LDS scratch (``check_consistency``).  Consistency is on exactly when ``consistency_ref`` is given; without it the other six are
+        refused and the call is the one of before: same launches, same bits, same captures.
 
         Skipping: with ``skip_neutral=True`` each step runs only the rows and networks its table rows need
         (``step_variants``): a step whose schedule row is neutral (``g == 1`` and ``s == 0``) forwards the B conditional rows alone, a
@@ -774,6 +930,10 @@ class Sampler:
                                            conditioning, controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
                                            adapter_conditioning_scale, adapter_conditioning_factor, guess_mode, bool(pag_mask),
                                            bool(adapter_features))
+        cons = _build_consistency(self.n_steps, self._timesteps, self._alphas_cumprod, self.kind, getattr(self, "final_sigmas_type", "zero"),
+                                  self.cache_interval, latents, self.kind == "resshift" or lr_latents is not None, consistency_ref,
+                                  consistency_factor, consistency_weight, consistency_interval, consistency_filter, consistency_noise,
+                                  consistency)
         if pag_mask:
             kind = _pag_run(latents, encoder_hidden_states, uncond_hidden_states, guidance_scale, guidance_rescale, float(pag_scale), pag_mask)
         elif check_guidance(guidance_scale, guidance_rescale, encoder_hidden_states.shape,
@@ -782,7 +942,7 @@ class Sampler:
                                conditioning is not None and conditioning[1])
         else:
             kind = dict(entry="mrisr_sampler_run", contexts=(encoder_hidden_states,))
-        return self._launch(_Run(schedule=table, conditioning=conditioning, skip=skip, tile_plan=plan, **kind), latents, lr_latents,
+        return self._launch(_Run(schedule=table, conditioning=conditioning, skip=skip, consistency=cons, tile_plan=plan, **kind), latents, lr_latents,
                             step_noise, controlnet_cond, adapter_features, use_graph)
 
     def _launch(self, run: _Run, latents, lr_latents, step_noise, controlnet_cond, adapter_features, use_graph):
@@ -831,6 +991,17 @@ class Sampler:
         if run.skip or self._skipping:
             L.check(lib.mrisr_sampler_set_skip(self._h, 1 if run.skip else 0))
             self._skipping = run.skip
+        if run.consistency is not None:
+            rows, N, fid, ref, cnz = run.consistency
+            keep += (ref, cnz)
+            t_ref = L.as_tensor(ref)
+            t_cnz = L.as_tensor(cnz, shape=(cnz.shape[0] * cnz.shape[1],) + tuple(cnz.shape[2:])) if cnz is not None else None
+            L.check(lib.mrisr_sampler_set_consistency(self._h, N, fid, rows.ctypes.data_as(C.c_void_p), int(rows.shape[0]), C.byref(t_ref),
+                                                      C.byref(t_cnz) if t_cnz else None))
+            self._consistent = True
+        elif self._consistent:
+            L.check(lib.mrisr_sampler_set_consistency(self._h, 0, 0, None, 0, None, None))
+            self._consistent = False
         L.check(getattr(lib, run.entry)(self._h, C.byref(t_lat), C.byref(t_lr) if t_lr else None, C.byref(t_nz) if t_nz else None,
                                         C.byref(t_e), C.byref(t_c) if t_c else None, f_arr if feats else None, len(feats), *run.extra,
                                         1 if use_graph else 0, L.stream_ptr()))
@@ -851,7 +1022,8 @@ class Sampler:
 def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weight_dtype, accelerator, fixed_embeds,
                    num_inference_steps=20, adapter=None, solver=None, cache_interval=1, cache_depth=1, tile=None, tile_overlap=0,
                    tile_window="gaussian", pag_scale=0.0, pag_applied_layers=("mid",), freeu=None, pag_adaptive_scale=0.0,
-                   guidance_interval=None, pag_interval=None, freeu_interval=None, skip_neutral=False, controlnet_conditioning_scale=1.0,
+                   guidance_interval=None, pag_interval=None, freeu_interval=None, skip_neutral=False, consistency_factor=None,
+                   consistency_weight=1.0, consistency_interval=None, consistency_filter="bilinear", controlnet_conditioning_scale=1.0,
                    control_guidance_start=0.0, control_guidance_end=1.0, adapter_conditioning_scale=1.0, adapter_conditioning_factor=1.0,
                    guess_mode=False, guidance_scale=1.0, guidance_rescale=0.0, uncond_embeds=None):
     """Drop-in for the reference's validation sampler (res_srdiff.py:35-105): same inputs, same PIL panel out.
@@ -873,8 +1045,15 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
     ``adapter_conditioning_factor`` / ``guess_mode``: the conditioning strength of ``Sampler.run`` (``conditioning_schedule``); the
     defaults leave the panel unchanged.
     ``skip_neutral``: as in ``Sampler.run`` - steps leave out the rows and networks the options above make neutral; the default
-    leaves the panel unchanged."""
+    leaves the panel unchanged.
+    ``consistency_factor`` (an int N in 2..8) turns low-frequency consistency on as in ``Sampler.run``, with the LR anchor latents as the
+    reference and ``consistency_weight`` / ``consistency_interval`` / ``consistency_filter`` as there; the reference is not noised (no
+    consistency noise is drawn: the global RNG stream is the default one).  ``None``: off, the other three must be at their defaults
+    and the panel is unchanged."""
     from PIL import Image
+
+    if consistency_factor is None and (consistency_weight != 1.0 or consistency_interval is not None or consistency_filter != "bilinear"):
+        raise ValueError("consistency_weight / consistency_interval / consistency_filter need consistency_factor")
 
     freeu_vals = None
     if freeu is not None:
@@ -918,6 +1097,9 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
             cond = control_image if tuple(control_image.shape[-2:]) == tuple(lr_raw.shape[-2:]) else \
                 prepare_condition_image(lr_raw, tuple(lr_raw.shape[-2:]))
             feats = adapter(cond.to(torch.float32))
+        cons = {} if consistency_factor is None else dict(
+            consistency_ref=lr_anchor, consistency_factor=consistency_factor, consistency_weight=consistency_weight,
+            consistency_interval=consistency_interval, consistency_filter=consistency_filter)
         sampler.run(latents, fixed_embeds[0:1], lr_latents=lr_anchor, step_noise=step_noise,
                     controlnet_cond=control_image if controlnet is not None else None, adapter_features=feats,
                     guidance_scale=guidance_scale, guidance_rescale=guidance_rescale,
@@ -926,7 +1108,7 @@ def log_validation(unet, controlnet, vae, val_dataloader, noise_scheduler, weigh
                     pag_interval=pag_interval, freeu_interval=freeu_interval,
                     controlnet_conditioning_scale=controlnet_conditioning_scale, control_guidance_start=control_guidance_start,
                     control_guidance_end=control_guidance_end, adapter_conditioning_scale=adapter_conditioning_scale,
-                    adapter_conditioning_factor=adapter_conditioning_factor, guess_mode=guess_mode, skip_neutral=skip_neutral)
+                    adapter_conditioning_factor=adapter_conditioning_factor, guess_mode=guess_mode, skip_neutral=skip_neutral, **cons)
     finally:
         if freeu_vals is not None:
             if freeu_prev is None:
